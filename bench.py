@@ -6,16 +6,18 @@ triangle mesh (the reference rebuilds its BVH per call, RayTracer.cpp:54) -> clo
 cell -> range / label / remission / end point / triangle images; meshes, rays and images resident in HBM.  Workload at
 N=1: BASELINE.json configs[1] ("C2": ~1 M-triangle scene, 64x2048 HDL-64E target, fov +3/-25), synthetic.
 
-    python bench.py [--gpus N --steps K --warmup W]            # N=1
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]     # N=1
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Scans shard over ranks (weak scaling), no data-path collective; the range + label images are gathered to rank 0 over
 RCCL inside the timed region (one logical gather issued in pieces that overlap the rendering) unless the links cannot
 carry them (LT_BENCH_GATHER=auto, the default: decided from a measured link rate before the clock; config.gather says
-which).  Rank 0 prints ONE JSON line (< 8 KB) with a compact `roofline` (dominant kernel k_sc_tris, HIP events on its
-launch stream) and `cpu_baseline` (the real reference raytracer, oracle/_ref, on this box's host cores).  Everything
-else -- the other strategy, the fusion / deform / mergemesh chains, PCIe-inclusive clocks -- is tools/bench_chains.py,
-which writes profiles/rNN/bench_extras.json.
+which).  Rank 0 prints ONE JSON line (< 8 KB).  A plain run sets up, warms up, times the K steps and prints it;
+--dump-outputs DIR writes what the last timed step computed (tools/bench_lib.dump_outputs).  --full adds, after the
+clock: `verified` / `verification` (timed scans against a fresh render and golden F5), a compact `roofline` (dominant
+kernel k_sc_tris, HIP events on its launch stream, plus a serial probe and counting passes) and `cpu_baseline` (the
+real reference raytracer, oracle/_ref, on the host's cores).  Everything else -- the other strategy, the fusion /
+deform / mergemesh chains, PCIe-inclusive clocks -- is tools/bench_chains.py, which writes profiles/rNN/bench_extras.json.
 """
 from __future__ import annotations
 
@@ -63,6 +65,11 @@ def parse(argv=None):
     ap.add_argument("--probe-only", action="store_true",
                     help="only the serial probe of the dominant kernel (the command profiled under rocprofv3 "
                          "--kernel-trace --stats so that roofline.avg_kernel_ms can be recomputed from a CSV)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: verification of the timed scans, the serial probe "
+                         "and the roofline record, the CPU baseline (without it: set up, warm up, time, print)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32/float64)")
     return ap.parse_args(argv)
 
 
@@ -73,8 +80,10 @@ def launch_command(n_gpus: int, argv, port: int):
 
 
 def relaunch_multi_gpu(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: become N ranks under torch.distributed.run."""
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: run N ranks under torch.distributed.run in a child
+    process and exit with its status."""
     import socket
+    import subprocess
     import torch
     if torch.cuda.device_count() < args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} requested but this node shows {torch.cuda.device_count()} GPU(s)")
@@ -85,7 +94,7 @@ def relaunch_multi_gpu(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL's peer-to-peer transport needs it here
     env.setdefault("OMP_NUM_THREADS", "8")
     sys.stdout.flush()
-    os.execve(sys.executable, launch_command(args.gpus, sys.argv[1:], port), env)
+    sys.exit(subprocess.run(launch_command(args.gpus, sys.argv[1:], port), env=env).returncode)
 
 
 class Harness:
@@ -173,9 +182,10 @@ class Harness:
         return t.to(self.dev if self.dist.get_backend() == "nccl" else "cpu")
 
     # ------------------------------------------------------------------------------------------ the timed region
-    def run(self, strategy, K, Wm, keep, groups=None, probe_every=PROBE_EVERY):
-        """Timed region for one strategy: (seconds, mean in-situ dominant-kernel ms, hits of the last scan, verification).
-        `groups`: batches in flight (default all --streams / --batch); HIP events around every `probe_every`-th launch."""
+    def run(self, strategy, K, Wm, keep, groups=None, probe_every=PROBE_EVERY, verify=True):
+        """Timed region for one strategy: (seconds, mean in-situ dominant-kernel ms, hits of the last scan, verification
+        or None without `verify`).  `groups`: batches in flight (default all --streams / --batch); HIP events around every
+        `probe_every`-th launch."""
         import ctypes as C
         from lidar_transfer_amd import _lib
         from lidar_transfer_amd.dist import XGMI_LINK_GBS, choose_gather, gather_to_root, measure_link_gbs
@@ -256,6 +266,9 @@ class Harness:
                 nb_all = (K + BATCH - 1) // BATCH
                 slot_rng = [arr([rng_p[min(b * BATCH + j, K - 1)] for j in range(BATCH)]) for b in range(nb_all)]
                 slot_col = [arr([col_p[min(b * BATCH + j, K - 1)] for j in range(BATCH)]) for b in range(nb_all)]
+        # scan i's end points / remissions / triangles land in scratch slot scratch_slot(i); the last scratch_span stay there
+        self.scratch_slot = lambda i: ((i // BATCH) % n_groups) * BATCH + i % BATCH
+        self.scratch_span = BATCH * n_groups
 
         def step_batch(i0, nb, slot0=None, timed=False):
             g = (i0 // BATCH) % n_groups
@@ -384,7 +397,7 @@ class Harness:
         assert recv is None or world == 1 or bool((recv[-1][0][1] > 0).any()), "rank 0 did not receive the peers' images"
         self.last_images = (range_all, color_all, recv)
         import bench_lib as bl
-        return dt, kern_ms, hits, (bl.verify_timed_scans(self, range_all, color_all, K, off) if (keep and K) else None)
+        return dt, kern_ms, hits, (bl.verify_timed_scans(self, range_all, color_all, K, off) if (verify and keep and K) else None)
 
     def gathered(self):
         """rank 0 after a gathering run: the (range [N, R] f32, label [N, R]) images of ALL ranks' scans, in job order"""
@@ -420,17 +433,23 @@ def main():
             emit({"probe_only": True, "strategy": args.strategy, "launches": 64, **rl})
         hz.close()
         return
-    dt, kern_ms, hits, verify = hz.run(args.strategy, hz.K, hz.Wm, keep=True)
+    dt, kern_ms, hits, _ = hz.run(args.strategy, hz.K, hz.Wm, keep=True, verify=False)
+    if args.dump_outputs and rank == 0:  # before anything else renders into the scratch images
+        bl.dump_outputs(hz, args.dump_outputs)
     if os.environ.get("LT_BENCH_DUMP") and rank == 0:  # tests: what rank 0 holds after the gather, in job order
         rg, lb = hz.gathered()
         np.savez(os.environ["LT_BENCH_DUMP"], range=rg.cpu().numpy(), label=lb.cpu().numpy().astype(np.int32))
-    try:
-        ser_ms = bl.serial_probe_ms(hz, args.strategy)
-    except Exception as e:  # noqa: BLE001  (never lose the headline line)
-        sys.stderr.write(f"bench.py: serial probe failed: {e!r}\n")
-        ser_ms = float("nan")
+    verify, ser_ms = None, float("nan")
+    if args.full:  # the side figures: none of them feeds the headline value
+        rng_all, col_all, _ = hz.last_images
+        verify = bl.verify_timed_scans(hz, rng_all, col_all, hz.K, hz.first if hz.job else 0) if hz.K else None
+        try:
+            ser_ms = bl.serial_probe_ms(hz, args.strategy)
+        except Exception as e:  # noqa: BLE001  (never lose the headline line)
+            sys.stderr.write(f"bench.py: serial probe failed: {e!r}\n")
     if rank == 0:
-        bl.count_work(hz, (args.strategy,))
+        if args.full:
+            bl.count_work(hz, (args.strategy,))
         n_scans = len(hz.job) if hz.job else world * hz.K
         xport = "RCCL" if (hz.dist.is_initialized() and hz.dist.get_backend() == "nccl") else "gloo (host transport)"
         value = n_scans * R / dt / 1e6
@@ -452,10 +471,11 @@ def main():
                        "gather": hz.gather_info or None, "warmup_ramp": hz.ramp_info,
                        "job": args.job or None, "scans_in_flight": hz.S, "scans_per_call": args.batch if args.strategy == "scatter" else 1},
             "scans_per_s": round(n_scans / dt, 2), "hit_fraction": round(hits / R, 4),
-            "verified": bool(verify and verify["ok"]), "verification": verify,
-            "roofline": bl.roofline_compact(hz, args.strategy, ser_ms, kern_ms, None if hz.job else step_s),
         }
-        if not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N=1 only
+        if args.full:
+            out.update(verified=bool(verify and verify["ok"]), verification=verify,
+                       roofline=bl.roofline_compact(hz, args.strategy, ser_ms, kern_ms, None if hz.job else step_s))
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N=1 only
             try:
                 out["cpu_baseline"] = bl.cpu_baseline_compact(hz.wl, 0, args.cpu_reps or 12)
             except Exception as e:  # noqa: BLE001

@@ -252,3 +252,53 @@ def mergemesh_seq_clouds(seed, src, render, limit):
     p, rm, lb = deform_mesh_clouds(seed, 1, src, render)[0]
     keep = (p[:, 0] < limit[0]) & (p[:, 1] > limit[1])
     return [(np.ascontiguousarray(p[keep]), np.ascontiguousarray(rm[keep]), np.ascontiguousarray(lb[keep]))]
+
+
+# ---- golden F16 (tests/golden/make_golden_live_fuzz.py): the projection and create_rays mirrors on random inputs ----------
+PROJ_FUZZ_COLOR_DICT = {0: [0, 0, 0], 10: [245, 150, 100], 40: [255, 0, 255], 48: [75, 0, 75], 50: [0, 200, 255],
+                        70: [0, 175, 0], 80: [150, 240, 255]}
+PROJ_FUZZ_KEYS = ("range", "index", "remission", "proj_x", "proj_y", "label")
+
+
+def projection_fuzz_cases(n=40):
+    """(H, W, fov_up, fov_down, points f64, remissions, labels u32, remove, beam angles or None) of 40 random clouds:
+    random image shapes, fields of view, `remove`, beam tables, depth-0 points, exact duplicates (depth ties), points outside
+    the field of view"""
+    rng = np.random.default_rng(2025)
+    for k in range(n):
+        H, W = int(rng.choice([5, 16, 32, 64])), int(rng.choice([7, 64, 257, 512, 1024]))
+        fu, fd = float(rng.choice([2.0, 3.0, 10.0, 15.0])), -float(rng.choice([16.6, 25.0, 30.0]))
+        n_pts = int(rng.integers(500, 20000))
+        pts, rem, lab = synth_cloud(300 + k, n_pts, dtype=np.float64, fov_up=fu + 3.0, fov_down=fd - 3.0)
+        pts[rng.integers(0, n_pts, 3)] = 0.0
+        dup = rng.integers(0, n_pts, 40)
+        pts[dup[:20]] = pts[dup[20:]]
+        remove = bool(rng.random() < 0.7)
+        beams = sorted((np.linspace(fd, fu, H) / 180.0 * np.pi).tolist()) if rng.random() < 0.3 else None
+        yield H, W, fu, fd, pts, rem, lab.astype(np.uint32), remove, beams
+
+
+def create_rays_fuzz_cases(n=30):
+    """(fov_up, fov_down, H, W) of 30 random sensor models"""
+    rng = np.random.default_rng(7)
+    for _k in range(n):
+        fu, fd = float(rng.uniform(0.5, 45.0)), -float(rng.uniform(5.0, 50.0))
+        yield fu, fd, int(rng.integers(1, 130)), int(rng.integers(1, 2100))
+
+
+def array_digest(a, dtype=None):
+    """SHA-256 of an array's shape, dtype and bytes (after a cast to `dtype`, when given): [32] uint8"""
+    import hashlib
+    a = np.ascontiguousarray(np.asarray(a) if dtype is None else np.asarray(a).astype(dtype))
+    h = hashlib.sha256(f"{a.shape}|{a.dtype.str}|".encode())
+    h.update(a.tobytes())
+    return np.frombuffer(h.digest(), np.uint8)
+
+
+def projection_fuzz_digests(range_image, index, remission, proj_x, proj_y, label_image):
+    """[6, 32] digests of one projection, in PROJ_FUZZ_KEYS order: range by its bits, the rest by value (index, proj_x / proj_y
+    and label as int64, remission as float64); proj_x / proj_y / label at the filled pixels only (index >= 0)"""
+    own = np.asarray(index) >= 0
+    return np.stack([array_digest(np.ascontiguousarray(range_image).view(np.int32)), array_digest(index, np.int64),
+                     array_digest(remission, np.float64), array_digest(np.asarray(proj_x)[own], np.int64),
+                     array_digest(np.asarray(proj_y)[own], np.int64), array_digest(np.asarray(label_image)[own], np.int64)])

@@ -230,7 +230,7 @@ def test_bench_cli_parses_without_a_gpu():
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True,
                          timeout=120)
     assert res.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in res.stdout
 
 

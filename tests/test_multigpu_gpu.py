@@ -237,7 +237,8 @@ def test_bench_under_torchrun_one_rank_rccl(gather):
     env.update(LT_BENCH_GATHER=gather, HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
                           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps",
-                          "2", "--warmup", "1", "--workload", "C1", "--scenes", "4", "--no-cpu-baseline", "--no-other", "--no-e2e", "--no-chain"],
+                          "2", "--warmup", "1", "--workload", "C1", "--scenes", "4", "--full", "--no-cpu-baseline", "--no-other", "--no-e2e",
+                          "--no-chain"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -250,11 +251,11 @@ def test_bench_under_torchrun_one_rank_rccl(gather):
 
 
 def test_bench_line_is_compact_and_complete(tmp_path):
-    """the default command's shape on a small configuration: ONE stdout line < 8 KB with the contract keys, a compact
+    """the --full command's shape on a small configuration: ONE stdout line < 8 KB with the contract keys, a compact
     roofline and cpu_baseline"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "C1",
-                          "--scenes", "4", "--cpu-reps", "2"], capture_output=True, text=True, timeout=900, env=env)
+                          "--scenes", "4", "--cpu-reps", "2", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0].encode()) < 8000, (len(lines), len(res.stdout))
@@ -269,12 +270,42 @@ def test_bench_line_is_compact_and_complete(tmp_path):
     assert out["verified"] is True and out["dtype"] == "f32" and out["scaling"] == "weak"
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run prints the headline without the --full records; --dump-outputs writes the last step's outputs
+    (float32 / float64, within 64 MB), the same bytes from two runs with the same arguments"""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "C1",
+                              "--scenes", "4", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, env=env)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, res.stdout
+        out = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        for k in ("roofline", "cpu_baseline", "verification"):
+            assert k not in out, k
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and np.isfinite(out["value"]) and out["value"] > 0
+        files = {p.stem: np.load(p) for p in sorted(d.glob("*.npy"))}
+        assert set(files) == {"range", "label", "endpoints", "endrem", "tri"}, sorted(files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64_000_000
+        assert files["range"].shape == (64, 32768) and files["label"].shape == files["range"].shape
+        assert files["endpoints"].shape == (24, 32768, 3) and files["tri"].shape == files["endrem"].shape == (24, 32768)
+        assert (files["range"] > 0).mean() > 0.5
+        dumps.append(files)
+    for k, a in dumps[0].items():
+        assert a.tobytes() == dumps[1][k].tobytes(), k
+
+
 def test_bench_job_c5_eight_ranks_sharing_the_gpu_equals_single_process(tmp_path):
     """Configuration C5 reduced (SemanticKITTI 00-07's real scan-count ratios / 100 = 169 output scans, 64 x 2048 images,
     20 k-triangle meshes) through bench.py's OWN chunked gather: 8 ranks (gloo transport, all on cuda:0 -- the one-GPU
     box) block-partition the job, render their unequal blocks and gather range + label images on rank 0 in pieces inside
     the timed region; what rank 0 holds equals the single-process run byte for byte."""
-    common = ["--job", "c5/100", "--tris", "20000", "--scenes", "8", "--streams", "8", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--job", "c5/100", "--tris", "20000", "--scenes", "8", "--streams", "8", "--warmup", "1", "--full", "--no-cpu-baseline"]
     base = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     one, eight = str(tmp_path / "one.npz"), str(tmp_path / "eight.npz")
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *common], capture_output=True, text=True, timeout=900,

@@ -317,6 +317,41 @@ def verify_timed_scans(hz, range_all, color_all, K, first=0):
             res["ok"] = res["ok"] and bool(gold)
     return res
 
+
+DUMP_SEED, DUMP_RAYS, DUMP_SCANS, DUMP_HELD, DUMP_MAX_BYTES = 2026, 32768, 64, 32, 64_000_000
+
+
+def dump_outputs(hz, out_dir):
+    """bench.py --dump-outputs: what the timed path computed in its LAST step, as `out_dir/<name>.npy`, so that two builds
+    can be compared output for output (the inputs are seeded: the same arguments give the same inputs).
+
+    A fixed, seeded sample of DUMP_RAYS ray cells (the same cells in every scan) of the step's last DUMP_SCANS scans:
+    `range` [scans, rays] f32 and `label` [scans, rays] f64 (the kept images); of the scans among them whose scratch
+    images were not reused afterwards (the last --streams scans, at most DUMP_HELD): `endpoints` [held, rays, 3] f32,
+    `endrem` [held, rays] f32 and `tri` [held, rays] f64 (hit triangle, -1 = miss).  Rank 0's own scans only."""
+    torch = hz.torch
+    rng_all, col_all, _ = hz.last_images
+    K, R = int(rng_all.shape[0]), hz.R
+    per_step = K if hz.job else hz.SPS
+    first = max(0, K - min(per_step, DUMP_SCANS))
+    cells = np.sort(np.random.default_rng(DUMP_SEED).choice(R, size=min(R, DUMP_RAYS), replace=False))
+    idx = torch.from_numpy(cells).to(hz.dev)
+    held = [i for i in range(first, K) if i + hz.scratch_span >= K][-DUMP_HELD:]
+    sl = [hz.scratch_slot(i) for i in held]
+    out = {"range": rng_all[first:K][:, idx].float(), "label": col_all[first:K][:, idx].double()}
+    if held:
+        out["endpoints"] = torch.stack([hz.scratch[s]["endpoints"].view(R, 3)[idx] for s in sl]).float()
+        out["endrem"] = torch.stack([hz.scratch[s]["endrem"].view(R)[idx] for s in sl]).float()
+        out["tri"] = torch.stack([hz.scratch[s]["tri"].view(R)[idx] for s in sl]).double()
+    torch.cuda.synchronize()
+    arrays = {k: v.cpu().numpy() for k, v in out.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
 # ------------------------------------------------------------------------------------------ roofline inputs
 def count_work(hz, strategies=("scatter",), n_lbvh=12):
     """counting passes outside the clock: candidate bins / nodes, Moller-Trumbore tests and accepted hits per scan"""

@@ -5,5 +5,5 @@ for fl in "" "-mllvm -amdgpu-enable-max-ilp-scheduling-strategy" "-mllvm -amdgpu
   export LIDARHIP_EXTRA_FLAGS="$fl"
   echo "=== flags: [$fl]"
   python -c "from lidar_transfer_amd import build; build.build_lib(force=True)" 2>&1 | tail -2
-  python bench.py --no-cpu-baseline --no-e2e --no-chain 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['avg_kernel_ms'], d['roofline']['isolated']['avg_kernel_ms'], d['other_strategy']['value'])"
+  python bench.py --full --no-cpu-baseline --no-e2e --no-chain 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['avg_kernel_ms'], d['roofline']['isolated']['avg_kernel_ms'], d['other_strategy']['value'])"
 done

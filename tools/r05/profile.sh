@@ -18,7 +18,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial_probe -o s -- 
 for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_BUSY_CYCLES"; do
   tag=$(echo $grp | cut -d' ' -f1)
   if [ "$tag" = "SQ_INSTS_VALU" ]; then tag=SQ_INSTS_VALU_group; fi
-  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_bench/$tag -o p -- python $R/bench.py --no-cpu-baseline --no-other --no-e2e --no-chain --steps 16 --warmup 2 > $O/pmc_bench_$tag.log 2>&1 || echo "FAILED pmc_bench $tag"
+  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_bench/$tag -o p -- python $R/bench.py --full --no-cpu-baseline --no-other --no-e2e --no-chain --steps 16 --warmup 2 > $O/pmc_bench_$tag.log 2>&1 || echo "FAILED pmc_bench $tag"
   rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_lbvh/$tag -o p -- python $R/tools/prof_scan.py --reps 5 > $O/pmc_lbvh_$tag.log 2>&1 || echo "FAILED pmc_lbvh $tag"
   rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_chain/$tag -o p -- python $R/tools/prof_chain.py 4 > $O/pmc_chain_$tag.log 2>&1 || echo "FAILED pmc_chain $tag"
 done
@@ -27,7 +27,7 @@ for grp in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "TCC_EA0_WRREQ_sum TCC_EA0_
   tag=$(echo $grp | tr ' ' '-')
   timeout 400 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/ea/$tag -o p -- python $R/bench.py --probe-only > $O/ea_$tag.log 2>&1 || echo "FAILED ea $tag"
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python $R/bench.py --no-cpu-baseline --no-e2e > $O/bench_profiled.json 2> $O/bench_profiled.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python $R/bench.py --full --no-cpu-baseline --no-e2e > $O/bench_profiled.json 2> $O/bench_profiled.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/iso_scatter -o s -- python $R/tools/prof_render.py --reps 40 > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/iso_lbvh -o s -- python $R/tools/prof_scan.py --reps 40 > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/chain -o s -- python $R/tools/prof_chain.py 12 > /dev/null 2>&1
@@ -49,5 +49,5 @@ done
 # the stats CSVs are what is kept; the per-dispatch traces are large
 find $O -name "*kernel_trace.csv" -size +2M -delete
 find $O -name "*counter_collection.csv" -size +4M -delete
-python bench.py > gpurun_out/r05/bench.json 2> gpurun_out/r05/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 600 gpurun_out/r05/bench.json
