@@ -417,34 +417,36 @@ class DeviceDeform:
                 beams = np.ascontiguousarray(self.beam_angles, dtype=np.float64)
             if out is None:
                 out = self.scene.alloc_outputs(self.n_rays, label_image=True)
+            org = (C.c_float * 3)(*[float(x) for x in origin])
+            flags = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE
+
+            def p(key):
+                a = out.get(key)
+                return a.data_ptr() if a is not None else None
+            pred = mm.pred
+            vol = None
+            if pred is not None:
+                vol = self._mm_vols.get(pred)
+                if vol is None:       # (another chain of the sequence verified this geometry)
+                    import numpy as np
+                    b = np.array(pred).reshape(3, 2)
+                    vol = self._mergemesh_volume(pred, np.ceil((b[:, 1] - b[:, 0]) / self._voxel_size).astype(int))
+            tflags = vol._flags if vol is not None else (_lib.LT_TSDF_HOST_MODE if self._fusion == "numpy" else self._merge)
+            geo, done = _lib.MMGeometry(), C.c_int(0)
+            with torch.cuda.device(self.device):
+                _lib.check(lib.lt_mergemesh_scan_dev(self.projector._h, mm._h, -1 if seq is None else int(seq),
+                                                     vol._h if vol is not None else None, self.mesh_obj._h, self.scene._h,
+                                                     self.rayset._h, cl, int(pts.dtype == torch.float64), self.t_fov_up,
+                                                     self.t_fov_down, self.H, self.W,
+                                                     beams.ctypes.data_as(vp) if beams is not None else None,
+                                                     0 if beams is None else len(beams), 1.0, tflags, org, p("endpoints"),
+                                                     p("endcolors"), p("range"), p("endrem"), p("tri"), flags, vp(st.cuda_stream),
+                                                     C.byref(geo), C.byref(done)), "lt_mergemesh_scan_dev")
         except BaseException:
             if seq is not None:
-                mm.skip(seq)
+                mm.skip(seq)   # (no-op when the native call has made the scan's geometry call already)
             raise
-        org = (C.c_float * 3)(*[float(x) for x in origin])
-        flags = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE
-
-        def p(key):
-            a = out.get(key)
-            return a.data_ptr() if a is not None else None
-        pred = mm.pred
-        vol = None
-        if pred is not None:
-            vol = self._mm_vols.get(pred)
-            if vol is None:       # (another chain of the sequence verified this geometry)
-                import numpy as np
-                b = np.array(pred).reshape(3, 2)
-                vol = self._mergemesh_volume(pred, np.ceil((b[:, 1] - b[:, 0]) / self._voxel_size).astype(int))
-        tflags = vol._flags if vol is not None else (_lib.LT_TSDF_HOST_MODE if self._fusion == "numpy" else self._merge)
-        geo, done = _lib.MMGeometry(), C.c_int(0)
         with torch.cuda.device(self.device):
-            _lib.check(lib.lt_mergemesh_scan_dev(self.projector._h, mm._h, -1 if seq is None else int(seq),
-                                                 vol._h if vol is not None else None, self.mesh_obj._h, self.scene._h, self.rayset._h,
-                                                 cl, int(pts.dtype == torch.float64), self.t_fov_up, self.t_fov_down, self.H, self.W,
-                                                 beams.ctypes.data_as(vp) if beams is not None else None,
-                                                 0 if beams is None else len(beams), 1.0, tflags, org, p("endpoints"),
-                                                 p("endcolors"), p("range"), p("endrem"), p("tri"), flags, vp(st.cuda_stream),
-                                                 C.byref(geo), C.byref(done)), "lt_mergemesh_scan_dev")
             mm.stats["scans"] += 1
             mm.settle(geo.ticket, geo)
             if geo.status == 1:

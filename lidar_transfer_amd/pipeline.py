@@ -366,16 +366,19 @@ class FusionScanPipeline:
         n = len(obs)
         vp = C.c_void_p
         cp, dp, rp = (vp * max(n, 1))(), (vp * max(n, 1))(), (vp * max(n, 1))()
+        if obs and len(obs[0]) == 5:  # ("mergemesh", points, rem, label, seq) items
+            try:
+                with torch.cuda.stream(st):
+                    if out is None:
+                        out = ch["scene"].alloc_outputs(self.n_rays, label_image=self.label_image)
+                    return self._scan_mergemesh(ch, obs, origin, out)
+            except BaseException:
+                self._mm_state.skip(obs[0][4])  # (a failed scan -- its outputs included -- must not hold up the later scans)
+                raise
         with torch.cuda.stream(st):
             if out is None:
                 out = ch["scene"].alloc_outputs(self.n_rays, label_image=self.label_image)
             h = w = 0
-            if obs and len(obs[0]) == 5:  # ("mergemesh", points, rem, label, seq) items
-                try:
-                    return self._scan_mergemesh(ch, obs, origin, out)
-                except BaseException:
-                    self._mm_state.skip(obs[0][4])  # (a failed scan must not hold up the sequence's later scans)
-                    raise
             if ch["vol"] is None:
                 raise RuntimeError("FusionScanPipeline: constructed with fixed_volume=False (submit_mergemesh only)")
             if obs and len(obs[0]) == 4:  # ("clouds", points, rem, label) items: ONE native call (lt_deform_scan_dev)
@@ -552,6 +555,8 @@ class FusionScanPipeline:
             if len(c) != 3 or not isinstance(c[0], torch.Tensor) or not c[0].is_cuda:
                 raise ValueError("clouds: (points, remissions, label) CUDA tensors")
             items.append(("mergemesh", c[0], c[1], c[2], self._mm_seq))
+        if not items:   # (before the sequence number moves: no scan would ever take it, and every later one would wait for it)
+            raise ValueError("FusionScanPipeline.submit_mergemesh: no clouds")
         self._mm_seq += 1
         return self._submit(items, origin, out, inputs_ready)
 
