@@ -317,6 +317,49 @@ int lt_range_projection_batch_dev(lt_projector* projector, int n_clouds, const l
                                   unsigned flags, const float* color_lut, int lut_len, const lt_proj_images* out,
                                   float range_init, float rem_init, float xyz_init, void* stream);
 
+/* ---- before the projection: raw scans -> the clouds `deform` projects ---------------------------- */
+
+/* From the bytes of velodyne/N.bin ([n,4] f32 x, y, z, remission) and labels/N.label ([n] u32) of the source scans of one
+ * output scan to the clouds MultiSemLaserScan.deform projects; replaces open_multiple_scans (auxiliary/laserscan.py:776-817)
+ * and the first statement of each deform branch (:845 / :878 / :949).  Per raw point of slot i, in file order:
+ *   1. l = label & 0xFFFF (:588)
+ *   2. dropped if (i != 0 and l in moving) or l in ignore (:802-807; n_scans == 1: only `ignore`, :809-817)
+ *   3. kept points keep their file order, slots follow each other in slot order (stable; np.concatenate, :939-945)
+ *   4. q = A [x y z 1]^T in float64 with A = poses[i] (apply_pose, :98-109), then r = B [q 1]^T with B = back -- two
+ *      transforms, each rounded to float64; back == NULL: q is the result (world coordinates)
+ *   5. every row as ((m0*x + m1*y) + m2*z) + m3, products and sums rounded separately (no fused multiply-add);
+ *      the remission is xyzr[3] unchanged, the label is l
+ * scans   HOST array of n_scans (1 .. LT_INGEST_MAX_SCANS) descriptors of DEVICE buffers, in the slot order of
+ *         open_multiple_scans (primary scan first); xyzr 16-byte aligned
+ * poses   HOST [n_scans][16] row-major float64: the pose of every slot's scan;  back  HOST [16]: inv(poses[idx]) or NULL
+ * ignore / moving   HOST class lists, any length, values 0 .. 65535 (anything else: LT_ERR_INVALID_ARG)
+ * flags   LT_INGEST_MERGED: ONE cloud out[0] of capacity sum(n) (the merged cloud of `cp` / `mergemesh`); otherwise one
+ *         cloud out[i] of capacity scans[i].n per slot (`mesh`).  Outputs: points [cap,3] f64, rem [cap] f32, label
+ *         [cap] u32 -- what lt_cloud takes with is_f64 = 1.  The tail [n_kept, cap) of every cloud is filled with points at
+ *         (0, 0, 0), remission 0, label 0: do_range_projection_new always removes depth-0 points (:307-309) and they sit behind
+ *         every kept point, so the projection may be launched with n = cap and the host never needs n_kept.
+ * n_kept  DEVICE [n_scans + 1]: kept points per slot, then their total
+ * work    DEVICE scratch of LT_INGEST_WORK_INTS(sum(n), n_scans) ints, the caller's (calls in flight on several streams
+ *         each bring their own)
+ * Asynchronous on `stream`; the host reads nothing back. */
+#define LT_INGEST_MERGED 1u
+#define LT_INGEST_MAX_SCANS 16
+#define LT_INGEST_LIST_ARGS 16 /* class lists up to this length travel as kernel arguments, longer ones as a bitmap in `work` */
+#define LT_INGEST_WORK_INTS(n_total, n_scans) (4096 + (n_total) / 256 + (n_scans) + 1)
+typedef struct lt_raw_scan {
+  const float* xyzr;
+  const unsigned* label;
+  int n;
+} lt_raw_scan;
+typedef struct lt_ingest_out {
+  double* points;
+  float* rem;
+  unsigned* label;
+} lt_ingest_out;
+int lt_ingest_scans_dev(int n_scans, const lt_raw_scan* scans, const double* poses, const double* back, const int* ignore,
+                        int n_ignore, const int* moving, int n_moving, unsigned flags, const lt_ingest_out* out,
+                        int* n_kept, int* work, void* stream);
+
 /* ---- before the render: class-aware TSDF fusion of range images (device-resident volumes) -------- */
 
 typedef struct lt_tsdf lt_tsdf; /* opaque: one (tsdf, weight, colour, rem) float32 record per voxel, [dim_x][dim_y][dim_z] */

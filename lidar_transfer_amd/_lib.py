@@ -21,6 +21,8 @@ LT_PROJ_REMOVE = 1
 LT_PROJ_NEW = 2
 LT_TSDF_MERGE = 1
 LT_TSDF_HOST_MODE = 2
+LT_INGEST_MERGED = 1
+LT_INGEST_MAX_SCANS = 16
 
 #: every symbol include/lidarhip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_dev", "lt_scene_set_mesh_host",
@@ -33,7 +35,7 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_hostpipe_flush", "lt_hostpipe_destroy", "lt_host_alloc", "lt_host_free", "lt_projector_create",
            "lt_projector_destroy", "lt_range_projection_batch_dev", "lt_mesh_renumber_dev",
            "lt_tsdf_integrate_multi_dev", "lt_deform_scan_dev", "lt_mm_state_create", "lt_mm_state_destroy", "lt_mm_state_reset",
-           "lt_mm_geometry_dev", "lt_mm_geometry_get", "lt_mergemesh_scan_dev", "lt_mergemesh_rerun_dev", "lt_abi_version"]
+           "lt_mm_geometry_dev", "lt_mm_geometry_get", "lt_mergemesh_scan_dev", "lt_mergemesh_rerun_dev", "lt_abi_version", "lt_ingest_scans_dev"]
 LT_ABI_VERSION = 7   # include/lidarhip.h: layout version of the structs mirrored below
 
 
@@ -64,6 +66,21 @@ class MMGeometry(C.Structure):
     """Mirror of ``lt_mm_geometry``: the volume geometry of one ``mergemesh`` output scan."""
     _fields_ = [("bnds_given", C.c_double * 6), ("bnds_after", C.c_double * 6), ("dim", C.c_int * 3), ("status", C.c_int),
                 ("ticket", C.c_int), ("reserved", C.c_int)]
+
+
+class RawScan(C.Structure):
+    """Mirror of ``lt_raw_scan``: DEVICE buffers holding the bytes of one ``velodyne/N.bin`` / ``labels/N.label`` pair."""
+    _fields_ = [("xyzr", C.c_void_p), ("label", C.c_void_p), ("n", C.c_int)]
+
+
+class IngestOut(C.Structure):
+    """Mirror of ``lt_ingest_out``: the DEVICE outputs of one prepared cloud (points f64, remissions f32, labels u32)."""
+    _fields_ = [("points", C.c_void_p), ("rem", C.c_void_p), ("label", C.c_void_p)]
+
+
+def ingest_work_ints(n_total: int, n_scans: int) -> int:
+    """``LT_INGEST_WORK_INTS`` (include/lidarhip.h)"""
+    return 4096 + n_total // 256 + n_scans + 1
 
 
 _lib = None
@@ -200,6 +217,9 @@ def load():
     for name in ("lt_mm_state_create", "lt_mm_state_destroy", "lt_mm_state_reset", "lt_mm_geometry_dev", "lt_mm_geometry_get",
                  "lt_mergemesh_scan_dev", "lt_mergemesh_rerun_dev", "lt_abi_version"):
         getattr(lib, name).restype = C.c_int
+    lib.lt_ingest_scans_dev.argtypes = [C.c_int, C.POINTER(RawScan), C.POINTER(C.c_double), C.POINTER(C.c_double), ip, C.c_int,
+                                        ip, C.c_int, C.c_uint, C.POINTER(IngestOut), vp, vp, vp]
+    lib.lt_ingest_scans_dev.restype = C.c_int
     lib.lt_abi_version.argtypes = []
     lib.lt_tsdf_volume_stride.argtypes = []
     if lib.lt_abi_version() != LT_ABI_VERSION:  # a stale prebuilt library: its structs are laid out differently

@@ -23,8 +23,9 @@ library's device entry points on ONE HIP stream:
     ``do_reverse_projection_new`` (:841-845), then ``write`` with ``index > 0`` (:1133-1144)
     =  ``lt_range_projection_batch_dev`` -> ``lt_reverse_projection_dev`` -> ``lt_pack_scan_dev``
 
-The clouds are CUDA tensors in the frame the reference projects them in (pose handling and file I/O are out of scope,
-DESIGN.md section 1); the host is touched twice per output scan: the mesh sizes inside marching cubes and the number
+The clouds are CUDA tensors in the frame the reference projects them in -- made from a sequence's files by
+``lidar_transfer_amd.ingest`` (``open_multiple_scans`` + the inverse pose on the device; :meth:`DeviceDeform.deform` puts
+it in front of the three adaptions) or by the caller; the host is touched twice per output scan: the mesh sizes inside marching cubes and the number
 of packed points.  There is no CPU path: everything ends in ``liblidarhip.so``.
 """
 from __future__ import annotations
@@ -499,6 +500,21 @@ class DeviceDeform:
                 res["bin"], res["label_file"] = self._pack(back, True, o["rem"].view(-1), o["label"].view(-1),
                                                            o["idx"].view(-1), self.n_rays, st)
         return res
+
+    # ---- open_multiple_scans + deform(adaption, poses, idx) ----------------------------------------------------------------
+    def deform(self, adaption, ingest, idx, back=None, **kw):
+        """The reference's loop body from the sequence's files (lidar_deform.py:412-415): ``ingest`` (a
+        :class:`lidar_transfer_amd.ingest.ScanIngest`) prepares the clouds of output scan ``idx`` on the caller's stream --
+        poses applied, moving / ignore classes removed, back in the primary scan's frame -- and :meth:`cp` / :meth:`mesh` /
+        :meth:`mergemesh` (``adaption``) takes them; ``kw`` goes to that method, ``back`` to ``ScanIngest.prepare``.  The clouds carry the raw scans' capacity
+        (depth-0 points behind the kept ones, which the projection removes): the kept counts never visit the host."""
+        if adaption not in ("cp", "mesh", "mergemesh"):
+            raise ValueError(f"DeviceDeform.deform: adaption {adaption!r} (cp, mesh or mergemesh)")
+        if ingest.device != self.device:
+            raise ValueError("DeviceDeform.deform: the ingest stage lives on another device")
+        st = self._stream()
+        clouds = ingest.prepare(idx, merged=adaption != "mesh", stream=st, back=back)
+        return getattr(self, adaption)(clouds, **kw)
 
     @staticmethod
     def write(out, out_dir, idx):
