@@ -550,6 +550,74 @@ int lt_compare_dev(const int* src_label, const float* src_color, const int* tgt_
                    unsigned long long* conf, float* range_diff, float* rem_diff, int* src_masked, int* tgt_masked,
                    double* sq_sum, void* stream);
 
+/* ---- evaluation on the device: the source reference scan and compare() into a small record -------------------------
+ *
+ * What lidar_deform.py does around `deform` per output scan when source and target image sizes agree (:396-409, :416-418):
+ * a SemLaserScan of the primary scan alone, and compare(scan, scans).  lt_evaluator owns the workspaces of both calls (z-min
+ * keys of the source image, an n_labels x n_labels pair-count matrix that is never copied, per-workgroup partial sums); one
+ * per caller thread / HIP stream: calls on one evaluator are serialised and must be queued in stream order.  n_labels: a
+ * multiple of 256, at most LT_COMPARE_MAX_NLABELS (512 covers SemanticKITTI's labels up to 259). */
+typedef struct lt_evaluator lt_evaluator;
+#define LT_COMPARE_MAX_NLABELS 2048
+#define LT_COMPARE_MAX_PRESENT 64 /* label values one record can hold */
+#define LT_COMPARE_OVERFLOW 1     /* lt_compare_record.status: more than LT_COMPARE_MAX_PRESENT values present        */
+#define LT_COMPARE_LABEL_RANGE 2  /* ... a masked label outside 0 .. n_labels - 1 (negative ones included)            */
+int lt_evaluator_create(lt_evaluator** ev, int n_labels, int device);
+int lt_evaluator_destroy(lt_evaluator* ev);
+
+/* [H*W] DEVICE images of the source reference scan; every member may be NULL. */
+typedef struct lt_source_images {
+  float* range;         /* proj_range, empty cells -1 (laserscan.py:37-39)                                            */
+  float* rem;           /* proj_remissions, empty cells -1                                                            */
+  int* label;           /* proj_label, empty cells 0                                                                  */
+  unsigned char* black; /* 1 where np.sum(proj_color, axis=2) == 0 (laserscan.py:1200): empty cells and black classes */
+  unsigned* bad_labels; /* ONE word: raw points whose label & 0xFFFF is outside the LUT (colorize() raises IndexError,  */
+                        /* laserscan.py:642); such a cell, if one wins, is black                                      */
+} lt_source_images;
+
+/* lt_source_scan_dev -- from ONE resident raw scan (the bytes of velodyne/N.bin + labels/N.label, as lt_ingest_scans_dev
+ * takes them) to the source reference image of lidar_deform.py:403-409.  Per raw point, in file order:
+ *   1. l = label & 0xFFFF (laserscan.py:588); l >= lut_len is counted into bad_labels (colorize runs before the removal)
+ *   2. dropped if l in ignore (remove_classes, :658-670; no `moving` list: the source scan is a primary scan)
+ *   3. x, y, z stay float32 and untransformed; do_range_projection(fov_up, fov_down, remove=True) in float32 (:202-292) --
+ *      the arithmetic of lt_range_projection_dev for float32 clouds with LT_PROJ_REMOVE, no beam angles (lidar_deform.py:396
+ *      constructs the scan without them): depth 0 and proj_y outside [0, 1] are dropped
+ *   4. winner per cell: the nearest point, the lowest index among equal depths.  A dropped point does not bid, and because
+ *      the removals keep the file order the raw index orders the kept points exactly as the kept index does
+ *   5. the cell receives the winner's float32 depth, xyzr[3], l, and black = (sum(color_lut[l]) == 0); empty: -1, -1, 0, 1
+ * ignore: HOST list, any length, values 0 .. 65535 (up to LT_INGEST_LIST_ARGS as kernel arguments, longer ones as a bitmap);
+ * color_lut: DEVICE [lut_len,3] f32 (SemLaserScan.color_lut).  Asynchronous on `stream`; the host reads nothing back. */
+int lt_source_scan_dev(lt_evaluator* ev, const lt_raw_scan* scan, const int* ignore, int n_ignore, double fov_up,
+                       double fov_down, int H, int W, const float* color_lut, int lut_len, const lt_source_images* out,
+                       void* stream);
+
+/* What compare() + iouEval.addBatch leave of one output scan, compacted on the device. */
+typedef struct lt_compare_record {
+  int status;              /* 0, LT_COMPARE_OVERFLOW or LT_COMPARE_LABEL_RANGE: then only sq_sum / n_cells are meaningful */
+  int n_present;           /* P: label values present in either masked image                                             */
+  int n_cells;
+  unsigned src_bad_labels; /* *src_bad_labels of the call (lt_source_images.bad_labels), 0 when NULL                      */
+  double sq_sum;           /* sum of the squared masked range differences (MSE = sq_sum / n_cells), bitwise reproducible  */
+  int present[LT_COMPARE_MAX_PRESENT];                            /* the P values, ascending; entries from P on: undefined */
+  unsigned counts[LT_COMPARE_MAX_PRESENT * LT_COMPARE_MAX_PRESENT]; /* dense P x P: counts[t * P + s] = cells whose masked   */
+                                                                  /* target label is present[t] and source label present[s]; */
+                                                                  /* entries from P * P on are undefined                     */
+} lt_compare_record;
+
+/* lt_compare_record_dev -- the array part of compare() (auxiliary/laserscan.py:1181-1301) + iouEval.addBatch
+ * (np_ioueval.py:31-47) of one output scan.  src_*: the images of lt_source_scan_dev; tgt_label / tgt_range: the target
+ * scan's label and range image (DeviceDeform's `label` / `range`; for `cp` the merged scan's, laserscan.py:1189-1194).
+ *   1. a cell that is black in the source, or whose source label is 0, is background in both images: labels 0, ranges 0
+ *   2. counts over the (target, source) pairs of masked labels, for the values present only, values ascending
+ *   3. sq_sum: float32 (source - target)^2 per cell, summed in float64 -- per workgroup in a fixed tree, the workgroups'
+ *      partial sums in a fixed order: two calls on the same images give the same bits
+ * The class renumbering and getIoU / getacc are the host's (lidar_transfer_amd.post.confusion_metrics).  `record`: DEVICE
+ * memory or pinned HOST memory (lt_host_alloc); it is written by an asynchronous copy behind the kernels, so the host reads
+ * it after an event recorded behind this call, without another synchronisation.  All images DEVICE pointers [n]. */
+int lt_compare_record_dev(lt_evaluator* ev, const int* src_label, const unsigned char* src_black, const int* tgt_label,
+                          const float* src_range, const float* tgt_range, int n, const unsigned* src_bad_labels,
+                          lt_compare_record* record, void* stream);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 
 /* Message of the last error raised on the calling thread ("" if none). */
@@ -560,7 +628,7 @@ const char* lt_version(void);
 
 /* Layout version of the structs this header declares (lt_proj_images, lt_stats, lt_mm_geometry ...): a caller compiled
  * against another header must not pass them.  lt_abi_version() returns the library's; the Python binding compares at load. */
-#define LT_ABI_VERSION 7
+#define LT_ABI_VERSION 8
 int lt_abi_version(void);
 
 #ifdef __cplusplus

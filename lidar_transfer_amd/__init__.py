@@ -8,6 +8,8 @@ implementation in this package (``oracle/`` is test infrastructure).
     fusion      throw_rays_at_mesh, TSDFVolume (fusion_lidar.py)
     laserscan   create_rays, LaserScan / SemLaserScan projections (laserscan.py)
     post        do_reverse_projection_new, pack_scan / write_scan, compare (laserscan.py, np_ioueval.py)
+    evaluate    Evaluator: the source reference scan + compare() into a small record, asynchronous (lidar_deform.py:396-418)
+    sequence    SequenceTransfer: a sequence on disk -> the transferred sequence on disk (lidar_deform.py's batch loop); CLI: python -m
     pipeline    ScanPipeline: the batch loop body, batches of scans in flight on one GPU; HostScanPipeline (host meshes
                 over PCIe); FusionScanPipeline (fuse -> marching cubes -> render per output scan, chains in flight)
     dist        scan_indices / partition / render_scans / gather_to_root: one process per GPU, one gather

@@ -1,0 +1,91 @@
+"""``python -m lidar_transfer_amd`` -- the reference's ``lidar_deform.py`` in batch mode (its flag surface, :78-137) on the device:
+
+    python -m lidar_transfer_amd -d DATASET -c config/approach_mergemesh.yaml -s 00 -t config/vlp32_1024.yaml -w -p output/
+
+``DATASET/config.yaml`` is the source sensor, ``--target`` the target sensor (default: the source), ``--config`` the approach
+YAML.  The tool is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
+``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  A missing dataset, labels or output
+folder ends with a message and exit status 1."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+
+def build_parser():
+    p = argparse.ArgumentParser("python -m lidar_transfer_amd")
+    p.add_argument("--dataset", "-d", type=str, required=True, help="Dataset to adapt. No Default")
+    p.add_argument("--config", "-c", type=str, default="config/approach_mergemesh.yaml", help="Approach config file. Defaults to %(default)s")
+    p.add_argument("--sequence", "-s", type=str, default="00", help="Sequence to transfer. Defaults to %(default)s")
+    p.add_argument("--target", "-t", type=str, default="", help="Target sensor config file. Defaults to the dataset's config.yaml")
+    p.add_argument("--offset", "-o", type=int, default=0, help="Scan to start at. Defaults to %(default)s")
+    p.add_argument("--output", "-p", type=str, default="output/", help="Output folder to write bin files to. Defaults to %(default)s")
+    p.add_argument("--batch", "-b", action="store_true", help="Run in batch mode (always on: there is no visualiser).")
+    p.add_argument("--write", "-w", action="store_true", help="Write new dataset to file.")
+    p.add_argument("--one_scan", action="store_true", help="Run only once.")
+    p.add_argument("--chains", type=int, default=1, help="Output scans in flight (mesh adaptions). Defaults to %(default)s")
+    p.add_argument("--fusion", choices=("cuda", "numpy"), default="cuda", help="Arithmetic of the TSDF fusion. Defaults to %(default)s")
+    p.add_argument("--resume", action="store_true", help="Skip scans whose two output files exist.")
+    p.add_argument("--log", type=str, default="", help="Write one JSON object per scan to this file.")
+    return p
+
+
+def check_paths(args):
+    """The reference's existence tests (lidar_deform.py:163-219), as messages: ``None`` when all is well"""
+    if args.write and not os.path.isdir(args.output):
+        return "Output folder doesn't exist! Exiting..."
+    seq = os.path.join(args.dataset, "sequences", args.sequence)
+    if not os.path.isdir(os.path.join(seq, "velodyne")):
+        return "Sequence folder doesn't exist! Exiting..."
+    if not os.path.isdir(os.path.join(seq, "labels")):
+        return "Labels folder doesn't exist! Exiting..."
+    if not os.path.isfile(os.path.join(args.dataset, "config.yaml")):
+        return "Error opening source config.yaml file %s." % os.path.join(args.dataset, "config.yaml")
+    for name, path in (("approach", args.config), ("target", args.target)):
+        if path and not os.path.isfile(path):
+            return "Error opening %s yaml file %s." % (name, path)
+    return None
+
+
+def main(argv=None):
+    args, _ = build_parser().parse_known_args(argv)
+    problem = check_paths(args)
+    if problem:
+        print(problem)
+        return 1
+    from .config import load_approach, load_sensor
+    source_path = os.path.join(args.dataset, "config.yaml")
+    target_path = args.target or source_path
+    try:
+        approach, source, target = load_approach(args.config), load_sensor(source_path), load_sensor(target_path)
+    except Exception as e:  # noqa: BLE001  (a YAML that cannot be read: message and status, as the reference's quit())
+        print(e)
+        print("Error opening yaml file.")
+        return 1
+    from .sequence import SequenceTransfer
+    log = open(args.log, "w") if args.log else None
+    try:
+        with SequenceTransfer((args.dataset, args.sequence), approach, source, target, out_dir=args.output if args.write else None,
+                              chains=args.chains, fusion=args.fusion, copy_files=(target_path, args.config)) as tr:
+            n_files = len(tr.source)
+            for rec in tr.run(offset=args.offset, one_scan=args.one_scan, resume=args.resume):
+                if rec["m_iou"] is not None:
+                    print("IoU: ", float(rec["m_iou"]))
+                    print("Acc: ", float(rec["m_acc"]))
+                    print("MSE: ", float(rec["MSE"]))
+                print("#" * 30, args.sequence, "-", rec["idx"], "/", n_files, "#" * 30, flush=True)
+                if log is not None:
+                    row = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in rec.items()}
+                    log.write(json.dumps(row) + "\n")
+            if log is not None:
+                log.write(json.dumps(dict(summary=tr.summary)) + "\n")
+    finally:
+        if log is not None:
+            log.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -23,6 +23,10 @@ LT_TSDF_MERGE = 1
 LT_TSDF_HOST_MODE = 2
 LT_INGEST_MERGED = 1
 LT_INGEST_MAX_SCANS = 16
+LT_COMPARE_MAX_NLABELS = 2048
+LT_COMPARE_MAX_PRESENT = 64
+LT_COMPARE_OVERFLOW = 1
+LT_COMPARE_LABEL_RANGE = 2
 
 #: every symbol include/lidarhip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_dev", "lt_scene_set_mesh_host",
@@ -35,8 +39,9 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_hostpipe_flush", "lt_hostpipe_destroy", "lt_host_alloc", "lt_host_free", "lt_projector_create",
            "lt_projector_destroy", "lt_range_projection_batch_dev", "lt_mesh_renumber_dev",
            "lt_tsdf_integrate_multi_dev", "lt_deform_scan_dev", "lt_mm_state_create", "lt_mm_state_destroy", "lt_mm_state_reset",
-           "lt_mm_geometry_dev", "lt_mm_geometry_get", "lt_mergemesh_scan_dev", "lt_mergemesh_rerun_dev", "lt_abi_version", "lt_ingest_scans_dev"]
-LT_ABI_VERSION = 7   # include/lidarhip.h: layout version of the structs mirrored below
+           "lt_mm_geometry_dev", "lt_mm_geometry_get", "lt_mergemesh_scan_dev", "lt_mergemesh_rerun_dev", "lt_abi_version", "lt_ingest_scans_dev",
+           "lt_evaluator_create", "lt_evaluator_destroy", "lt_source_scan_dev", "lt_compare_record_dev"]
+LT_ABI_VERSION = 8   # include/lidarhip.h: layout version of the structs mirrored below
 
 
 class Stats(C.Structure):
@@ -76,6 +81,18 @@ class RawScan(C.Structure):
 class IngestOut(C.Structure):
     """Mirror of ``lt_ingest_out``: the DEVICE outputs of one prepared cloud (points f64, remissions f32, labels u32)."""
     _fields_ = [("points", C.c_void_p), ("rem", C.c_void_p), ("label", C.c_void_p)]
+
+
+class SourceImages(C.Structure):
+    """Mirror of ``lt_source_images``: the [H*W] DEVICE images of the source reference scan; NULL = not wanted."""
+    _fields_ = [(k, C.c_void_p) for k in ("range", "rem", "label", "black", "bad_labels")]
+
+
+class CompareRecord(C.Structure):
+    """Mirror of ``lt_compare_record``: what ``compare()`` + ``iouEval.addBatch`` leave of one output scan."""
+    _fields_ = [("status", C.c_int), ("n_present", C.c_int), ("n_cells", C.c_int), ("src_bad_labels", C.c_uint),
+                ("sq_sum", C.c_double), ("present", C.c_int * LT_COMPARE_MAX_PRESENT),
+                ("counts", C.c_uint * (LT_COMPARE_MAX_PRESENT * LT_COMPARE_MAX_PRESENT))]
 
 
 def ingest_work_ints(n_total: int, n_scans: int) -> int:
@@ -220,6 +237,13 @@ def load():
     lib.lt_ingest_scans_dev.argtypes = [C.c_int, C.POINTER(RawScan), C.POINTER(C.c_double), C.POINTER(C.c_double), ip, C.c_int,
                                         ip, C.c_int, C.c_uint, C.POINTER(IngestOut), vp, vp, vp]
     lib.lt_ingest_scans_dev.restype = C.c_int
+    lib.lt_evaluator_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
+    lib.lt_evaluator_destroy.argtypes = [vp]
+    lib.lt_source_scan_dev.argtypes = [vp, C.POINTER(RawScan), ip, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_int,
+                                       C.POINTER(SourceImages), vp]
+    lib.lt_compare_record_dev.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    for name in ("lt_evaluator_create", "lt_evaluator_destroy", "lt_source_scan_dev", "lt_compare_record_dev"):
+        getattr(lib, name).restype = C.c_int
     lib.lt_abi_version.argtypes = []
     lib.lt_tsdf_volume_stride.argtypes = []
     if lib.lt_abi_version() != LT_ABI_VERSION:  # a stale prebuilt library: its structs are laid out differently

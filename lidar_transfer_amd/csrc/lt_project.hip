@@ -16,6 +16,7 @@
 // was read from file (laserscan.py:131-136), float64 after a pose was applied (laserscan.py:98-104).
 // float32 transcendental results are the correctly rounded value (computed in double, rounded once).
 #include "lt_internal.h"
+#include "lt_projpoint.h"  // project_point, pb_key: shared with lt_evaluate.hip
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -23,62 +24,6 @@
 #include <new>
 
 #define LT_EMPTY_IDX 0x7F7F7F7F  // hipMemset(0x7F) pattern: larger than any point index
-
-template <typename T>
-struct proj_out {
-  int cell;   // py * W + px, or -1 when the point is dropped
-  T depth, xf, yf;
-  int px, py;
-};
-
-__device__ __forceinline__ float lt_atan2(float y, float x) { return (float)atan2((double)y, (double)x); }
-__device__ __forceinline__ double lt_atan2(double y, double x) { return atan2(y, x); }
-__device__ __forceinline__ float lt_asin(float q) { return (float)asin((double)q); }
-__device__ __forceinline__ double lt_asin(double q) { return asin(q); }
-__device__ __forceinline__ float lt_sqrt(float v) { return sqrtf(v); }
-__device__ __forceinline__ double lt_sqrt(double v) { return sqrt(v); }
-__device__ __forceinline__ float lt_floor(float v) { return floorf(v); }
-__device__ __forceinline__ double lt_floor(double v) { return floor(v); }
-
-// one point through laserscan.py:214-262 (resp. :304-351); all constants pre-rounded to T by the host
-template <typename T>
-__device__ __forceinline__ proj_out<T> project_point(T x, T y, T z, T pi_t, T abs_fov_down, T fov, int H, int W,
-                                                     const double* __restrict__ beams, int n_beams,
-                                                     bool drop_zero, bool drop_outside) {
-  proj_out<T> o;
-  const T depth = lt_sqrt((x * x + y * y) + z * z);  // np.linalg.norm(points, 2, axis=1)
-  T yaw = -lt_atan2(y, x);
-  T pitch = lt_asin(z / depth);
-  if (n_beams > 0) {  // nearest hard-coded beam angle, first minimum (laserscan.py:233-238)
-    double best = fabs((double)pitch - beams[0]);
-    int bi = 0;
-    for (int k = 1; k < n_beams; ++k) {
-      const double dlt = fabs((double)pitch - beams[k]);
-      if (dlt < best) { best = dlt; bi = k; }
-    }
-    pitch = (T)beams[bi];
-  }
-  T px = (T)0.5 * (yaw / pi_t + (T)1.0);
-  T py = (T)1.0 - (pitch + abs_fov_down) / fov;
-  bool keep = true;
-  if (drop_zero && depth == (T)0) keep = false;
-  if (drop_outside && !(py >= (T)0 && py <= (T)1)) keep = false;
-  if (!(depth == depth) || !(px == px) || !(py == py)) keep = false;  // NaN never reaches an image
-  px *= (T)W;
-  py *= (T)H;
-  o.xf = px;
-  o.yf = py;
-  T fx = lt_floor(px), fy = lt_floor(py);
-  fx = fx < (T)(W - 1) ? fx : (T)(W - 1);
-  fx = fx > (T)0 ? fx : (T)0;
-  fy = fy < (T)(H - 1) ? fy : (T)(H - 1);
-  fy = fy > (T)0 ? fy : (T)0;
-  o.px = (int)fx;
-  o.py = (int)fy;
-  o.depth = depth;
-  o.cell = keep ? o.py * W + o.px : -1;
-  return o;
-}
 
 // pass 1: project, z-min of the depth bits, per-workgroup count of kept points
 template <typename T>
@@ -388,7 +333,6 @@ extern "C" int lt_range_projection_dev(const void* points, int is_f64, const flo
 // 0x80000000 | index otherwise (lowest index first): one atomicMin yields exactly that point.  float32 clouds never round.
 // The OLD variant on float32 clouds: closest point, lowest index among equal depths (k_project's rule) -- the same key.
 #define LT_PB_MAX 8
-#define LT_PB_EMPTY (~0ull)
 
 struct pb_cloud {
   const void* pts; const float* rem; const unsigned* label;
@@ -412,18 +356,6 @@ __device__ __forceinline__ int pb_find_cloud(const pb_args& A, int block) {
   for (int k = 1; k < LT_PB_MAX; ++k)
     if (k < A.n_clouds && block >= A.c[k].block0) c = k;
   return c;
-}
-
-template <typename T>
-__device__ __forceinline__ unsigned long long pb_key(T depth, int i) {
-  const float df = (float)depth;
-  const bool up = (double)depth < (double)df;  // lies below its float32 value: replaces an incumbent of the same bucket
-  const unsigned lo = up ? (0x7fffffffu - (unsigned)i) : (0x80000000u | (unsigned)i);
-  return ((unsigned long long)__float_as_uint(df) << 32) | lo;
-}
-__device__ __forceinline__ int pb_key_index(unsigned long long k) {
-  const unsigned lo = (unsigned)k;
-  return (lo & 0x80000000u) ? (int)(lo & 0x7fffffffu) : (int)(0x7fffffffu - lo);
 }
 
 // order-preserving map double -> uint64 (and back): unsigned comparison of the keys == comparison of the values

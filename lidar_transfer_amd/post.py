@@ -85,6 +85,42 @@ def write_scan(out_dir, idx, back_points, label_image, remissions, index=None):
     return b.shape[0]
 
 
+def confusion_metrics(value, counts, nclasses):
+    """The host tail of ``compare()`` on the tiny matrix: ``value`` -- the label values present, ascending; ``counts[t, s]`` --
+    cells whose masked target label is ``value[t]`` and source label ``value[s]``.  The reference renumbers IN PLACE on the
+    arrays it scans (laserscan.py:1216-1222: label[label == value] = i for the sorted values present).  For non-negative
+    labels that is the rank (u_i >= i: no rank meets a value still to come); with negative labels a rank can equal a later
+    value and the two classes MERGE ({-1, 0, 3}: -1 -> 0, then every 0 -> 1) -- replayed here on the list of values, not on
+    the images.  Then ``iouEval`` (np_ioueval.py:45-70) with the empty classes ignored.  Returns ``(final, m_iou, m_acc,
+    iou)``; ``final[j]`` = class of the pixels whose raw label is ``value[j]``.  Both :func:`compare` and the device records
+    of ``lt_compare_record_dev`` (:mod:`lidar_transfer_amd.evaluate`) end here."""
+    value = np.asarray(value)
+    counts = np.asarray(counts, np.int64)
+    cur = value.copy()
+    for i, v in enumerate(value):
+        cur[cur == v] = i
+    final = cur
+    if len(final) and int(final.max()) >= nclasses:
+        # np.add.at would raise IndexError in the reference (np_ioueval.py:47)
+        raise IndexError(f"compare: class index {int(final.max())} after renumbering but nclasses = {nclasses}")
+    cm = np.zeros((nclasses, nclasses), np.int64)
+    np.add.at(cm, (final[:, None], final[None, :]), counts)
+    used = np.unique(final)
+    ignore = np.setdiff1d(np.arange(nclasses), used)
+    include = np.array([c for c in range(nclasses) if c not in set(ignore.tolist())], dtype=np.int64)
+    c2 = cm.copy()
+    c2[ignore] = 0
+    c2[:, ignore] = 0
+    tp = np.diag(c2)
+    fp = c2.sum(axis=1) - tp
+    fn = c2.sum(axis=0) - tp
+    union = tp + fp + fn + 1e-15
+    iou = tp / union
+    m_iou = (tp[include] / union[include]).mean()
+    m_acc = tp.sum() / (tp[include].sum() + fp[include].sum() + 1e-15)
+    return final, m_iou, m_acc, iou
+
+
 def compare(source_label, source_color, target_label, source_range, target_range, source_rem, target_rem, nclasses):
     """Array part of ``compare()`` (auxiliary/laserscan.py:1181-1301) + ``iouEval`` (np_ioueval.py).
 
@@ -133,32 +169,7 @@ def compare(source_label, source_color, target_label, source_range, target_range
     value = np.where(present >= mx, mx - 1 - present, present) if lo < 0 else present.copy()
     order = np.argsort(value, kind="stable")
     present, value = present[order], value[order]
-    # The reference renumbers IN PLACE on the arrays it scans (laserscan.py:1216-1222: label[label == value] = i for
-    # the sorted values present).  For non-negative labels that is the rank (u_i >= i: no rank meets a value still to
-    # come); with negative labels a rank can equal a later value and the two classes MERGE ({-1, 0, 3}: -1 -> 0, then
-    # every 0 -> 1).  Replayed here on the list of values, not on the images.
-    cur = value.copy()
-    for i, v in enumerate(value):
-        cur[cur == v] = i
-    final = cur  # final[j] = class of the pixels whose raw label is value[j]
-    if len(final) and int(final.max()) >= nclasses:
-        # np.add.at would raise IndexError in the reference (np_ioueval.py:47)
-        raise IndexError(f"compare: class index {int(final.max())} after renumbering but nclasses = {nclasses}")
-    cm = np.zeros((nclasses, nclasses), np.int64)
-    np.add.at(cm, (final[:, None], final[None, :]), conf[np.ix_(present, present)])
-    used = np.unique(final)
-    ignore = np.setdiff1d(np.arange(nclasses), used)
-    include = np.array([c for c in range(nclasses) if c not in set(ignore.tolist())], dtype=np.int64)
-    c2 = cm.copy()
-    c2[ignore] = 0
-    c2[:, ignore] = 0
-    tp = np.diag(c2)
-    fp = c2.sum(axis=1) - tp
-    fn = c2.sum(axis=0) - tp
-    union = tp + fp + fn + 1e-15
-    iou = tp / union
-    m_iou = (tp[include] / union[include]).mean()
-    m_acc = tp.sum() / (tp[include].sum() + fp[include].sum() + 1e-15)
+    final, m_iou, m_acc, iou = confusion_metrics(value, conf[np.ix_(present, present)], nclasses)
     remap = np.full(NL, -1, np.int32)
     remap[present] = final.astype(np.int32)
     return dict(range_diff=rd.cpu().numpy().reshape(H, W), rem_diff=md.cpu().numpy().reshape(H, W), m_iou=m_iou,

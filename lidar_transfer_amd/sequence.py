@@ -1,0 +1,344 @@
+"""A whole sequence: the reference's batch loop (lidar_deform.py:385-462) from a SemanticKITTI sequence on disk to the
+transferred sequence on disk, with the metrics ``compare()`` prints per scan.
+
+    tr = SequenceTransfer((dataset, "00"), approach, source_sensor, target_sensor, out_dir="output", chains=3)
+    for rec in tr.run():                                   # records in scan order
+        rec["idx"], rec["n_points"], rec["m_iou"], rec["m_acc"], rec["MSE"], rec["iou"]
+    tr.close()
+
+Per output scan, all queued without the host waiting in between: ``ScanIngest.prepare`` (raw scans -> clouds) on the
+submitting thread's stream; an event orders the chain's stream behind it; on the chain's stream ``DeviceDeform.cp / mesh /
+mergemesh``, then -- when source and target images have one size -- the source reference scan and ``compare()`` into a
+pinned record (:mod:`lidar_transfer_amd.evaluate`), then ``write``'s packing, an asynchronous copy of the packed bytes into
+pinned memory and an event; ONE writer thread waits for that event and writes ``velodyne/N.bin`` / ``labels/N.label``.
+``chains > 1`` (mesh adaptions): every chain owns a ``DeviceDeform``, an ``Evaluator``, a HIP stream and a host thread; scans
+are dealt to the chains in turn; ``mergemesh``'s bounds statements run in scan order whichever chain a scan lands on
+(``MergeMeshState``, shared).  Thread counts are ``chains`` + 1, never derived from the machine's CPU count.  There is no CPU
+path: everything ends in ``liblidarhip.so``."""
+from __future__ import annotations
+
+import collections
+import os
+import queue
+import shutil
+import threading
+
+import numpy as np
+
+from .deform import DeviceDeform, MergeMeshState
+from .evaluate import Evaluator
+from .ingest import ScanIngest, SequenceSource
+
+ADAPTIONS = ("cp", "mesh", "mergemesh")
+
+
+def sensor_tuple(s):
+    """``(H, W, fov_up, fov_down)`` of a :class:`lidar_transfer_amd.config.SensorModel` (or such a tuple itself)"""
+    if hasattr(s, "fov_up"):
+        return int(s.H), int(s.W), float(s.fov_up), float(s.fov_down)
+    return int(s[0]), int(s[1]), float(s[2]), float(s[3])
+
+
+def output_paths(out_dir, sequence, idx):
+    """``<out_dir>/sequences/<seq>/velodyne/NNNNNN.bin`` and ``.../labels/NNNNNN.label`` (lidar_deform.py:166-168, laserscan.py:1162-1173)"""
+    base = os.path.join(out_dir, "sequences", str(sequence))
+    name = str(int(idx)).zfill(6)
+    return os.path.join(base, "velodyne", name + ".bin"), os.path.join(base, "labels", name + ".label")
+
+
+def plausible_output(out_dir, sequence, idx):
+    """``resume``'s test: both files exist, the ``.bin`` is a whole number of 16-byte points and the ``.label`` a quarter of it"""
+    b, l = output_paths(out_dir, sequence, idx)
+    try:
+        sb, sl = os.path.getsize(b), os.path.getsize(l)
+    except OSError:
+        return False
+    return sb % 16 == 0 and sl * 4 == sb
+
+
+def cache_scans_needed(number_of_scans, chains, batch_interval):
+    """raw scans that must stay resident: those of one output scan plus what the scans in flight have moved on by"""
+    return int(number_of_scans) + int(chains) * max(int(batch_interval), 1)
+
+
+class _Writer:
+    """ONE thread: waits for a scan's event, writes its two files"""
+
+    def __init__(self):
+        self.q = queue.Queue()
+        self.thread = threading.Thread(target=self._loop, daemon=True)
+        self.thread.start()
+
+    def _loop(self):
+        while True:
+            item = self.q.get()
+            if item is None:
+                return
+            job, paths, hb, hl, n, event = item
+            try:
+                event.synchronize()
+                for p in paths:
+                    os.makedirs(os.path.dirname(p), exist_ok=True)
+                hb.numpy()[:n].tofile(paths[0])
+                hl.numpy()[:n].view(np.uint32).tofile(paths[1])
+            except BaseException as e:  # noqa: BLE001  (handed to the generator as this scan's exception)
+                job["error"] = e
+            job["written"].set()
+
+    def close(self):
+        self.q.put(None)
+        self.thread.join()
+
+
+def _chain_worker(runner_work, q):
+    while True:
+        item = q.get()
+        if item is None:
+            return
+        runner_work(*item)
+
+
+class SequenceTransfer:
+    """See the module docstring.  ``source_seq``: a :class:`SequenceSource` (then ``sequence`` names the output folder) or
+    ``(dataset, sequence)``; ``approach``: :class:`lidar_transfer_amd.config.Approach`; sensors: ``SensorModel`` or ``(H, W,
+    fov_up, fov_down)``.  ``out_dir=None``: nothing is written.  ``evaluate=None``: compare when source and target images
+    have one size, as lidar_deform.py:416 does.  ``fusion``: ``"cuda"`` or ``"numpy"`` (the reference's two fusion modes).
+    ``nclasses``: default ``len(approach.color_map)`` (lidar_deform.py:359).  ``copy_files``: paths (the target and approach
+    YAML) copied next to the output once (lidar_deform.py:446-452)."""
+
+    def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
+                 device=None, sequence="00", nclasses=None, copy_files=()):
+        import torch
+        self._torch = torch
+        if approach.adaption not in ADAPTIONS:
+            raise ValueError(f"adaption {approach.adaption!r} (cp, mesh or mergemesh)")
+        if int(chains) < 1:
+            raise ValueError("chains: at least one")
+        self.approach, self.adaption = approach, approach.adaption
+        self.source_sensor, self.target_sensor = sensor_tuple(source_sensor), sensor_tuple(target_sensor)
+        self.chains = 1 if self.adaption == "cp" else int(chains)     # `cp` always runs on one chain
+        self.fusion, self.out_dir = fusion, out_dir
+        self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
+        self.copy_files = [p for p in copy_files if p]
+        same = self.source_sensor[:2] == self.target_sensor[:2]
+        if evaluate and not same:
+            raise ValueError("evaluate: source and target images differ in size (lidar_deform.py:416)")
+        self.evaluate = same if evaluate is None else bool(evaluate)
+        need = cache_scans_needed(approach.number_of_scans, self.chains, approach.batch_interval)
+        idx = torch.cuda.current_device() if device is None else int(device)
+        if isinstance(source_seq, SequenceSource):
+            self.source, self._own_source, self.sequence = source_seq, False, str(sequence)
+            if self.source.cache_scans < need:
+                raise ValueError(f"SequenceSource(cache_scans={self.source.cache_scans}) is too small: number_of_scans "
+                                 f"{approach.number_of_scans} with {self.chains} scan(s) in flight needs {need}")
+        else:
+            dataset, self.sequence = source_seq[0], str(source_seq[1])
+            self.source, self._own_source = SequenceSource(dataset, self.sequence, device=idx, cache_scans=max(16, need)), True
+        self.device = self.source.device
+        self.ingest = ScanIngest(self.source, approach)
+        beams = getattr(source_sensor, "beam_angles", None)
+        self._configured_bnds = np.array(approach.voxel_bounds).copy() if self.adaption != "cp" else None
+        self._mm = None
+        self._chains = []
+        self._writer = None
+        self._copied = False
+        self.summary = {}
+        try:
+            if self.adaption == "mergemesh":
+                self.vol_bnds = self._configured_bnds.copy()   # the ONE array of the sequence, kept current
+                self._mm = MergeMeshState(self.vol_bnds, approach.voxel_size, idx)
+            rayset = None
+            for c in range(self.chains):
+                if self.adaption == "cp":
+                    dd = DeviceDeform(self.source_sensor, self.target_sensor, None, beam_angles=beams,
+                                      preserve_float=approach.preserve_float, device=idx, fusion=fusion)
+                else:
+                    dd = DeviceDeform(self.source_sensor, self.target_sensor,
+                                      None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
+                                      beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
+                                      mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm)
+                    rayset = dd.rayset
+                ch = dict(dd=dd, ev=None, q=None, thread=None,
+                          stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
+                if self.evaluate:
+                    ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx)
+                if self.chains > 1:
+                    ch["q"] = queue.Queue()
+                    ch["thread"] = threading.Thread(target=_chain_worker, args=(self._work, ch["q"]), daemon=True)
+                    ch["thread"].start()
+                self._chains.append(ch)
+            if out_dir is not None:
+                self._writer = _Writer()
+        except BaseException:
+            self.close()
+            raise
+
+    # ---- the scan list -------------------------------------------------------------------------------------------------
+    def scan_indices(self, offset=0, one_scan=False):
+        idx = self.approach.scan_indices(len(self.source), offset)
+        return idx[:1] if one_scan else idx
+
+    # ---- one scan on its chain (the chain's thread, or the caller's with one chain) ---------------------------------------
+    def _work(self, ch, job):
+        torch = self._torch
+        dd, st = ch["dd"], ch["stream"]
+        try:
+            with torch.cuda.device(self.device), torch.cuda.stream(st):
+                if job["ready"] is not None:
+                    st.wait_event(job["ready"])      # the ingest was queued on the submitting thread's stream
+                clouds = job["clouds"]
+                if job["skipped"]:                   # resume: only mergemesh's bounds are replayed
+                    dd.mergemesh_bounds(clouds, seq=job["k"])
+                    return
+                if self.adaption == "cp":
+                    out = dd.cp(clouds, pack=False)
+                elif self.adaption == "mesh":
+                    out = dd.mesh(clouds, pack=False)
+                else:
+                    out = dd.mergemesh(clouds, pack=False, seq=job["k"])
+                    job["bnds_after"] = np.array(out["vol_bnds_after"]).reshape(3, 2)
+                if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
+                    src = ch["ev"].source_scan(*job["raw"], stream=st)
+                    job["record"] = ch["ev"].compare(src, out["label"], out["range"], stream=st)
+                    job["images"] = (src, out)
+                if self.adaption == "cp":
+                    b, l = dd._pack(out["back_points"], True, out["rem"].view(-1), out["label"].view(-1), out["index"].view(-1),
+                                    dd.n_rays, st)
+                else:
+                    b, l = dd._pack(out["endpoints"], False, out["rem"].reshape(-1), out["label"].reshape(-1), None, dd.n_rays, st)
+                n = int(b.shape[0])
+                job["n_points"] = n
+                if self._writer is not None:
+                    hb = torch.empty((max(n, 1), 4), dtype=torch.float32, pin_memory=True)
+                    hl = torch.empty((max(n, 1),), dtype=torch.int32, pin_memory=True)
+                    if n:
+                        hb[:n].copy_(b, non_blocking=True)
+                        hl[:n].copy_(l, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(st)
+                    job["keep"] = (b, l, out)
+                    self._writer.q.put((job, output_paths(self.out_dir, self.sequence, job["idx"]), hb, hl, n, ev))
+                else:
+                    job["written"].set()
+        except BaseException as e:  # noqa: BLE001  (handed to the generator as this scan's exception)
+            job["error"] = e
+            if self._mm is not None:
+                self._mm.skip(job["k"])              # (no-op when the scan's geometry call was made after all)
+            job["written"].set()
+        finally:
+            job["done"].set()
+
+    def _submit(self, k, idx, resume):
+        torch = self._torch
+        job = dict(k=k, idx=int(idx), done=threading.Event(), written=threading.Event(), error=None, record=None, skipped=False,
+                   n_points=None, bnds_after=None)
+        if resume and self.out_dir is not None and plausible_output(self.out_dir, self.sequence, idx):
+            job["skipped"] = True
+            job["n_points"] = os.path.getsize(output_paths(self.out_dir, self.sequence, idx)[0]) // 16
+            job["written"].set()
+            if self._mm is None:
+                job["done"].set()
+                return job
+        st = torch.cuda.current_stream(self.device)
+        job["clouds"] = self.ingest.prepare(idx, merged=self.adaption != "mesh", stream=st)
+        if self.evaluate and not job["skipped"]:
+            job["raw"] = self.source.raw(idx, st)
+        ch = self._chains[k % len(self._chains)]
+        job["ready"] = None                          # (one chain: the same stream, already in order)
+        if ch["q"] is not None:
+            job["ready"] = torch.cuda.Event()
+            job["ready"].record(st)
+            ch["q"].put((ch, job))
+        else:
+            self._work(ch, job)
+        return job
+
+    def _collect(self, job):
+        job["done"].wait()
+        job["written"].wait()
+        if job["error"] is not None:
+            raise job["error"]
+        rec = dict(idx=job["idx"], n_points=job["n_points"], m_iou=None, m_acc=None, MSE=None, iou=None, skipped=job["skipped"])
+        if job["bnds_after"] is not None:
+            rec["bnds_after"] = job["bnds_after"]
+        if job["record"] is not None:
+            try:
+                rec.update(job["record"].metrics(self.nclasses))
+            except OverflowError:        # more label values than a record holds: this scan through post.compare
+                from .post import compare
+                src, out = job["images"]
+                h = lambda t: t.cpu().numpy()   # noqa: E731
+                color = np.where(h(src["black"])[:, :, None] != 0, 0.0, 1.0) * np.ones((1, 1, 3))
+                m = compare(h(src["label"]), color, h(out["label"]), h(src["range"]), h(out["range"]), h(src["rem"]), h(out["rem"]),
+                            self.nclasses)
+                rec.update(m_iou=m["m_iou"], m_acc=m["m_acc"], MSE=m["MSE"], iou=m["iou"])
+        if self.out_dir is not None and not self._copied and not job["skipped"]:
+            base = os.path.join(self.out_dir, "sequences", self.sequence)
+            for p in self.copy_files:
+                shutil.copy2(p, base)
+            self._copied = True
+        for key in ("clouds", "raw", "images", "keep", "record"):
+            job.pop(key, None)
+        return rec
+
+    def run(self, offset=0, one_scan=False, resume=False):
+        """Generator of one record per output scan, in scan order: ``idx``, ``n_points``, ``m_iou`` / ``m_acc`` / ``MSE`` /
+        ``iou`` (``None`` when the run does not compare), ``skipped`` (``resume`` found both output files), ``bnds_after``
+        (mergemesh).  A failed scan or a failed write surfaces as that scan's exception; later scans are not started."""
+        indices = self.scan_indices(offset, one_scan)
+        if self._mm is not None:
+            self._mm.reset(self._configured_bnds)        # a run is one sequence: it starts from the configured bounds
+        pending = collections.deque()
+        n_done = 0
+        try:
+            for k, idx in enumerate(indices):
+                pending.append(self._submit(k, idx, resume))
+                while len(pending) >= self.chains:
+                    rec = self._collect(pending.popleft())
+                    n_done += 1
+                    yield rec
+            while pending:
+                rec = self._collect(pending.popleft())
+                n_done += 1
+                yield rec
+        finally:
+            for job in pending:                          # (a failure or an abandoned generator: let what is queued finish)
+                job["done"].wait()
+                job["written"].wait()
+            self.summary = dict(scans=n_done, chains=self.chains, adaption=self.adaption, fusion=self.fusion,
+                                mm_stats=dict(self._mm.stats) if self._mm is not None else None,
+                                source_stats=dict(self.source.stats))
+
+    def close(self):
+        for ch in getattr(self, "_chains", []):
+            if ch["q"] is not None:
+                ch["q"].put(None)
+        for ch in getattr(self, "_chains", []):
+            if ch["thread"] is not None:
+                ch["thread"].join()
+            if ch["ev"] is not None:
+                ch["ev"].close()
+        if getattr(self, "_writer", None) is not None:
+            self._writer.close()
+            self._writer = None
+        chains, self._chains = getattr(self, "_chains", []), []
+        for ch in reversed(chains):                      # (the first chain owns the shared ray set)
+            ch["dd"].close()
+        if getattr(self, "_mm", None) is not None:
+            self._mm.close()
+            self._mm = None
+        if getattr(self, "_own_source", False) and getattr(self, "source", None) is not None:
+            self.source.close()
+            self._own_source = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
