@@ -222,6 +222,11 @@ int lt_scene_destroy(lt_scene* scene);
  * trigonometry is cast to float32 last.  fov_up / fov_down in degrees. */
 int lt_create_rays_dev(double fov_up, double fov_down, int H, int W, float* rays, void* stream);
 
+/* The same rays for a sensor mounted at a pose of its own: every direction, still in float64, is turned by `rot`
+ * (HOST, [9] row-major rotation of the pose; NULL = identity = the call above) as ((r0*x + r1*y) + r2*z) per
+ * component, each product and sum rounded on its own, and cast to float32 last.  Asynchronous on `stream`. */
+int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, int W, const double* rot, float* rays, void* stream);
+
 #define LT_PROJ_REMOVE 1u /* `remove=True`: drop depth == 0 and points whose proj_y is outside [0, 1]   */
 #define LT_PROJ_NEW 2u    /* do_range_projection_new: depth == 0 is always dropped (laserscan.py:306-309) */
 
@@ -530,6 +535,12 @@ int lt_mergemesh_rerun_dev(lt_projector* projector, lt_tsdf* vol, lt_mesh* mesh,
 int lt_reverse_projection_dev(const float* range_img, const void* proj_x, const void* proj_y,
                               int coords_are_f64, double fov_up, double fov_down, int H, int W,
                               double* back_points, void* stream);
+
+/* Points into another frame: out[i] = float32(((m0*x + m1*y) + m2*z) + m3) per row of T, in float64 from the float32
+ * point.  points / out [n,3] f32 DEVICE (out may be points), tri [n] i32 DEVICE or NULL: rows with tri < 0 (rays
+ * that missed) are copied unchanged.  T: HOST [16] row-major (read before the call returns; the last row is not
+ * used).  Asynchronous on `stream`. */
+int lt_points_to_frame_dev(const float* points, const int* tri, int n, const double* T, float* out, void* stream);
 
 /* Pack a rendered scan in SemanticKITTI layout; replaces the filtering and the per-point struct.pack loops
  * of MultiSemLaserScan.write (auxiliary/laserscan.py:1133-1178).  Keeps, in order, the cells with

@@ -3,7 +3,9 @@
     python -m lidar_transfer_amd -d DATASET -c config/approach_mergemesh.yaml -s 00 -t config/vlp32_1024.yaml -w -p output/
 
 ``DATASET/config.yaml`` is the source sensor, ``--target`` the target sensor (default: the source), ``--config`` the approach
-YAML.  The tool is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
+YAML -- its ``transformation`` (16 numbers, ``x_target = T . x_source``) mounts the target sensor at a pose of its own: the
+output is then in the target's frame, no metrics are printed and every row of ``--log`` carries ``"mounted": true``.  The tool
+is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
 ``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  A missing dataset, labels or output
 folder ends with a message and exit status 1."""
 from __future__ import annotations
@@ -60,6 +62,7 @@ def main(argv=None):
     target_path = args.target or source_path
     try:
         approach, source, target = load_approach(args.config), load_sensor(source_path), load_sensor(target_path)
+        approach.mount()   # (a transformation that is not a rigid motion: said here, not half way into the run)
     except Exception as e:  # noqa: BLE001  (a YAML that cannot be read: message and status, as the reference's quit())
         print(e)
         print("Error opening yaml file.")
@@ -78,6 +81,8 @@ def main(argv=None):
                 print("#" * 30, args.sequence, "-", rec["idx"], "/", n_files, "#" * 30, flush=True)
                 if log is not None:
                     row = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in rec.items()}
+                    if tr.mounted:
+                        row["mounted"] = True
                     log.write(json.dumps(row) + "\n")
             if log is not None:
                 log.write(json.dumps(dict(summary=tr.summary)) + "\n")

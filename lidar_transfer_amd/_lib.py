@@ -40,7 +40,8 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_projector_destroy", "lt_range_projection_batch_dev", "lt_mesh_renumber_dev",
            "lt_tsdf_integrate_multi_dev", "lt_deform_scan_dev", "lt_mm_state_create", "lt_mm_state_destroy", "lt_mm_state_reset",
            "lt_mm_geometry_dev", "lt_mm_geometry_get", "lt_mergemesh_scan_dev", "lt_mergemesh_rerun_dev", "lt_abi_version", "lt_ingest_scans_dev",
-           "lt_evaluator_create", "lt_evaluator_destroy", "lt_source_scan_dev", "lt_compare_record_dev"]
+           "lt_evaluator_create", "lt_evaluator_destroy", "lt_source_scan_dev", "lt_compare_record_dev",
+           "lt_create_rays_pose_dev", "lt_points_to_frame_dev"]
 LT_ABI_VERSION = 8   # include/lidarhip.h: layout version of the structs mirrored below
 
 
@@ -244,6 +245,10 @@ def load():
     lib.lt_compare_record_dev.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     for name in ("lt_evaluator_create", "lt_evaluator_destroy", "lt_source_scan_dev", "lt_compare_record_dev"):
         getattr(lib, name).restype = C.c_int
+    lib.lt_create_rays_pose_dev.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), vp, vp]
+    lib.lt_create_rays_pose_dev.restype = C.c_int
+    lib.lt_points_to_frame_dev.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), vp, vp]
+    lib.lt_points_to_frame_dev.restype = C.c_int
     lib.lt_abi_version.argtypes = []
     lib.lt_tsdf_volume_stride.argtypes = []
     if lib.lt_abi_version() != LT_ABI_VERSION:  # a stale prebuilt library: its structs are laid out differently

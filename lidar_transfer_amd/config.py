@@ -109,10 +109,47 @@ class Approach:
             lut[key] = np.array(value, np.float32) / 255.0
         return lut
 
+    def mount(self):
+        """The target sensor's mounting: ``None`` when ``transformation`` is empty, ``None`` or the exact identity, else the
+        validated ``(T, P)`` float64 pair (see :func:`mount_of`)."""
+        return mount_of(self.transformation)
+
     def scan_indices(self, n_scan_files: int, offset: int = 0):
         """Scan list of the batch loop (``lidar_deform.py:385-390, :457-459``)."""
         from .dist import scan_indices
         return scan_indices(n_scan_files, self.number_of_scans, offset, self.batch_interval)
+
+
+def mount_of(transformation):
+    """``transformation`` of the approach file as the target sensor's mounting.  ``T`` (16 numbers, row-major 4x4) maps
+    coordinates in the source sensor's frame of the primary scan to the target sensor's frame, ``x_target = T . x_source``;
+    the target sensor stands at ``P = inv(T) = [Rp | tp]`` in the scene.  Returns ``None`` for an empty list, ``None`` or the
+    exact identity (nothing downstream changes then), else ``(T, P)`` as float64 [4, 4] arrays; a ``(T, P)`` pair returned
+    earlier is accepted as well.  ``ValueError`` unless ``T`` is rigid: 16 numbers, last row ``0 0 0 1``,
+    ``max |R . R^T - I| <= 1e-6``, ``det R > 0``."""
+    if transformation is None:
+        return None
+    if isinstance(transformation, tuple) and len(transformation) == 2 and np.shape(transformation[0]) == (4, 4):
+        transformation = transformation[0]
+    t = np.asarray(transformation, dtype=np.float64)
+    if t.size == 0:
+        return None
+    if t.size != 16:
+        raise ValueError(f"transformation: 16 numbers (a row-major 4x4 matrix), not {t.size}")
+    T = np.ascontiguousarray(t.reshape(4, 4))
+    if not np.all(np.isfinite(T)):
+        raise ValueError("transformation: not finite")
+    if np.array_equal(T, np.eye(4)):
+        return None
+    if not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+        raise ValueError(f"transformation: the last row is 0 0 0 1, not {T[3].tolist()}")
+    R = T[:3, :3]
+    err = float(np.abs(R @ R.T - np.eye(3)).max())
+    if not err <= 1e-6:
+        raise ValueError(f"transformation: the upper-left 3x3 is not a rotation (|R R^T - I| = {err:.3g} > 1e-6)")
+    if not np.linalg.det(R) > 0:
+        raise ValueError("transformation: the upper-left 3x3 is a reflection (det < 0)")
+    return T, np.ascontiguousarray(np.linalg.inv(T))
 
 
 def load_approach(path_or_dict) -> Approach:

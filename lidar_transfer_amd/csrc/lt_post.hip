@@ -47,6 +47,44 @@ extern "C" int lt_reverse_projection_dev(const float* range_img, const void* pro
   return LT_OK;
 }
 
+// ---- rendered points into another frame (the target sensor's, when it is mounted at a pose of its own) ----------
+// float32 point widened to float64, ((m0 * x + m1 * y) + m2 * z) + m3 per row of T (lt_ingest_scans_dev's row form; every
+// product and sum rounded on its own), rounded to float32.  Rows with tri < 0 (misses) are copied as they are: (0, 0, 0)
+// stays (0, 0, 0) for write()'s filter.  One thread per point reads its three floats before it writes them (out may be
+// points); 12-byte rows: three 4-byte accesses, nothing wider is aligned.
+struct lt_mat12 { double m[12]; };
+
+__global__ __launch_bounds__(256) void k_points_to_frame(const float* pts, const int* __restrict__ tri, int n,
+                                                         lt_mat12 T, float* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float fx = pts[3 * (size_t)i], fy = pts[3 * (size_t)i + 1], fz = pts[3 * (size_t)i + 2];
+  if (tri && tri[i] < 0) {
+    out[3 * (size_t)i] = fx;
+    out[3 * (size_t)i + 1] = fy;
+    out[3 * (size_t)i + 2] = fz;
+    return;
+  }
+  const double x = (double)fx, y = (double)fy, z = (double)fz;
+  out[3 * (size_t)i] = (float)(((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3]);
+  out[3 * (size_t)i + 1] = (float)(((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7]);
+  out[3 * (size_t)i + 2] = (float)(((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11]);
+}
+
+extern "C" int lt_points_to_frame_dev(const float* points, const int* tri, int n, const double* T, float* out,
+                                      void* stream) {
+  if (n < 0 || !T || (n > 0 && (!points || !out))) {
+    lt_set_error("lt_points_to_frame_dev: invalid argument (n=%d)", n);
+    return LT_ERR_INVALID_ARG;
+  }
+  if (n == 0) return LT_OK;
+  lt_mat12 M;
+  for (int k = 0; k < 12; ++k) M.m[k] = T[k];
+  hipLaunchKernelGGL(k_points_to_frame, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, points, tri, n, M, out);
+  LT_HIP(hipGetLastError());
+  return LT_OK;
+}
+
 // ---- scan packer ----------------------------------------------------------------------------------------------
 template <typename T>
 __device__ __forceinline__ bool pack_keep(const T* __restrict__ pts, const int* __restrict__ label,

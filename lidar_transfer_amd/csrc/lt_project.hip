@@ -187,6 +187,44 @@ extern "C" int lt_create_rays_dev(double fov_up, double fov_down, int H, int W, 
   return LT_OK;
 }
 
+// ---- create_rays of a sensor at its own pose: the direction above, still in float64, turned by the row-major rotation
+// `rot` of the pose -- ((r0 * x + r1 * y) + r2 * z) per component, every product and sum rounded on its own
+// (-ffp-contract=off) -- and cast to float32 last.  A kernel of its own: k_create_rays stays what it was.
+struct lt_rot9 { double m[9]; };
+
+__global__ __launch_bounds__(256) void k_create_rays_pose(double fov_up, double fov_down, int H, int W, lt_rot9 R,
+                                                          float* __restrict__ rays) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= H * W) return;
+  const int h = idx / W, w = idx - h * W;
+  double yaw_deg = W > 1 ? (w == W - 1 ? 360.0 : 0.0 + w * (360.0 / (W - 1))) : 0.0;
+  yaw_deg += 180.0;
+  if (yaw_deg > 360.0) yaw_deg -= 360.0;
+  const double yaw = yaw_deg / 180. * M_PI;
+  double pd = H > 1 ? (h == H - 1 ? fov_down : fov_up + h * ((fov_down - fov_up) / (H - 1))) : fov_up;
+  const double p = M_PI / 2 - pd / 180. * M_PI;
+  const double sp = sin(p);
+  const double x = sp * cos(-yaw), y = sp * sin(-yaw), z = cos(p) * 1.0;
+  rays[3 * (size_t)idx] = (float)((R.m[0] * x + R.m[1] * y) + R.m[2] * z);
+  rays[3 * (size_t)idx + 1] = (float)((R.m[3] * x + R.m[4] * y) + R.m[5] * z);
+  rays[3 * (size_t)idx + 2] = (float)((R.m[6] * x + R.m[7] * y) + R.m[8] * z);
+}
+
+extern "C" int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, int W, const double* rot, float* rays,
+                                       void* stream) {
+  if (!rot) return lt_create_rays_dev(fov_up, fov_down, H, W, rays, stream);
+  if (H <= 0 || W <= 0 || !rays) {
+    lt_set_error("lt_create_rays_pose_dev: invalid argument (H=%d W=%d)", H, W);
+    return LT_ERR_INVALID_ARG;
+  }
+  lt_rot9 R;
+  for (int k = 0; k < 9; ++k) R.m[k] = rot[k];
+  hipLaunchKernelGGL(k_create_rays_pose, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, fov_up, fov_down,
+                     H, W, R, rays);
+  LT_HIP(hipGetLastError());
+  return LT_OK;
+}
+
 // ---- host orchestration -------------------------------------------------------------------------------------
 namespace {
 struct proj_ws {

@@ -134,17 +134,25 @@ class DeviceDeform:
     """
 
     def __init__(self, source, target, vol_bnds=None, voxel_size=0.1, beam_angles=None, t_beam_angles=None,
-                 preserve_float=False, device=None, merge=True, fusion="cuda", mesh_volume=True, rayset=None, mm_state=None):
+                 preserve_float=False, device=None, merge=True, fusion="cuda", mesh_volume=True, rayset=None, mm_state=None,
+                 transformation=None):
         """``fusion``: ``"cuda"`` -- the arithmetic of the reference's CUDA kernel (class-aware with ``merge``), or ``"numpy"`` --
         that of its numpy branch (``FUSION_GPU_MODE == 0``, fusion_lidar.py:290-388; what goldens F13 / F14 are made by).
         ``vol_bnds``: [3,2]; for :meth:`mergemesh` it is STATE, clipped in place call after call exactly as the reference
         clips the one ``voxel_bounds`` array it hands every ``MultiSemLaserScan`` (lidar_deform.py:321-401,
         laserscan.py:960-962, fusion_lidar.py:36) -- pass a numpy array to see it.  ``mesh_volume=False``: do not allocate the
         fixed volume of :meth:`mesh` (a caller that only runs ``mergemesh``).  ``rayset`` / ``mm_state``: a shared target ray set
-        (read-only) and a shared :class:`MergeMeshState` -- several chains of one sequence (``FusionScanPipeline``)."""
+        (read-only) and a shared :class:`MergeMeshState` -- several chains of one sequence (``FusionScanPipeline``).
+        ``transformation``: the approach file's key (16 numbers, ``x_target = T . x_source``; or ``Approach.mount()``'s pair)
+        -- the target sensor stands at ``P = inv(T) = [Rp | tp]`` in the primary scan's frame: its rays are ``Rp . d`` cast
+        from ``float32(tp)`` into the scene, which is still fused in the primary scan's frame, and the hits' ``endpoints``
+        are brought into the target's frame by ``T`` (``endpoints_scene``: as rendered); ``cp`` takes its cloud into the
+        target frame on ingest (:meth:`deform`).  Empty, ``None`` or the identity: none of this runs.  A shared ``rayset``
+        must have been built for the same pose (``RaySet(..., pose=P)``)."""
         import numpy as np
         import torch
 
+        from .config import mount_of
         from .fusion import DeviceMesh, TSDFVolume
         from .laserscan import Projector, create_rays_device
         self._torch = torch
@@ -165,6 +173,11 @@ class DeviceDeform:
         self.vol_bnds = None
         self._mm_state, self._mm_own = mm_state, mm_state is None
         self._rayset_own = rayset is None
+        self.mount = mount_of(transformation)
+        self.origin = (0.0, 0.0, 0.0)          # the target sensor in the scene: where mesh / mergemesh cast from by default
+        if self.mount is not None:
+            self.origin = tuple(float(np.float32(x)) for x in self.mount[1][:3, 3])
+            self._T = np.ascontiguousarray(self.mount[0], dtype=np.float64)
         if mm_state is not None and vol_bnds is None:
             vol_bnds = mm_state.vol_bnds
         if vol_bnds is not None:
@@ -177,11 +190,16 @@ class DeviceDeform:
                 self._merge = self.vol._flags
             self.mesh_obj = DeviceMesh(idx)
             self.scene = Scene(idx)
+            pose = self.mount[1] if self.mount is not None else None
             if rayset is None:
-                rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=idx)
-                self.rayset = RaySet(rays, self.t_H)
+                rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=idx,
+                                          rot=pose[:3, :3] if pose is not None else None)
+                self.rayset = RaySet(rays, self.t_H, pose=pose)
                 self._rays = rays
             else:
+                theirs = getattr(rayset, "pose", None)
+                if (theirs is None) != (pose is None) or (pose is not None and not np.array_equal(theirs, pose)):
+                    raise ValueError("DeviceDeform: the shared rayset was built for another sensor pose than `transformation`")
                 self.rayset = rayset
         self.n_rays = self.t_H * self.t_W
 
@@ -198,6 +216,36 @@ class DeviceDeform:
         self._last_stream = st
         return st
 
+    # ---- a target sensor at its own pose: the hits into its frame ---------------------------------------------------------
+    def _render_into(self, out):
+        """what the render writes when the target is mounted: the scene-frame endpoints go to a buffer of their own (the
+        caller's ``endpoints`` receive the target frame), and the hit triangle is always wanted (misses stay (0, 0, 0))"""
+        if self.mount is None or out.get("endpoints") is None:
+            return out
+        torch = self._torch
+        rout = dict(out)
+        rout["endpoints"] = torch.empty_like(out["endpoints"])
+        if rout.get("tri") is None:
+            rout["tri"] = torch.empty((self.n_rays,), dtype=torch.int32, device=self.device)
+        return rout
+
+    def _to_target(self, rout, out, st):
+        """(endpoints in the target's frame, endpoints as rendered): ``lt_points_to_frame_dev`` on the chain's stream"""
+        if rout is out:
+            return out["endpoints"], out["endpoints"]
+        _lib.check(self._lib.lt_points_to_frame_dev(rout["endpoints"].data_ptr(), rout["tri"].data_ptr(), self.n_rays,
+                                                    self._T.ctypes.data_as(C.POINTER(C.c_double)), out["endpoints"].data_ptr(),
+                                                    C.c_void_p(st.cuda_stream)), "lt_points_to_frame_dev")
+        return out["endpoints"], rout["endpoints"]
+
+    def cp_back(self, pose):
+        """``cp`` with a mounted target: the second transform of the ingest, ``T . inv(pose of the primary scan)`` (float64,
+        host) -- the merged cloud arrives in the target's frame; ``None`` (the ingest's default) without a mounting"""
+        import numpy as np
+        if self.mount is None:
+            return None
+        return np.matmul(self.mount[0], np.linalg.inv(pose))
+
     # ---- write(): filter + pack (laserscan.py:1133-1178) -------------------------------------------------------------
     def _pack(self, points, is_f64, rem, label, index, n, st):
         torch = self._torch
@@ -211,13 +259,17 @@ class DeviceDeform:
         return out_bin[:kept.value], out_lab[:kept.value]
 
     # ---- deform('mesh') + write ---------------------------------------------------------------------------------------
-    def mesh(self, clouds, origin=(0.0, 0.0, 0.0), pack=True, timing=None):
+    def mesh(self, clouds, origin=None, pack=True, timing=None):
         """``clouds``: one (points [n,3] f32|f64, remissions [n] f32, label [n] i32) triple of CUDA tensors per source scan,
         already in the primary scan's frame (laserscan.py:876-879).  Returns the target scan: ``range`` / ``rem`` [t_H,t_W]
         f32, ``label`` [t_H,t_W] i32 (``label_image``, :912), ``endpoints`` [t_H*t_W,3] f32 (``back_points``), ``tri``, the
         source images per scan under ``source``, and -- with ``pack`` -- ``bin`` [N,4] f32 + ``label_file`` [N] i32, the
         bytes ``write`` puts into ``velodyne/N.bin`` and ``labels/N.label``.  ``timing``: a list that receives CUDA events
-        (start, projected, rendered, packed) when given."""
+        (start, projected, rendered, packed) when given.  ``origin``: where the rays start in the scene (default: the target
+        sensor's position, (0, 0, 0) unless it is mounted elsewhere); ``endpoints`` are in the target sensor's frame,
+        ``endpoints_scene`` as rendered."""
+        if origin is None:
+            origin = self.origin
         if self.vol is None:
             raise RuntimeError("DeviceDeform.mesh: constructed without vol_bnds")
         torch, lib = self._torch, self._lib
@@ -235,19 +287,21 @@ class DeviceDeform:
         for k, o in enumerate(src):
             cp[k], dp[k], rp[k] = o["label_folded"].data_ptr(), o["range"].data_ptr(), o["rem"].data_ptr()
         out = self.scene.alloc_outputs(self.n_rays, label_image=True)
+        rout = self._render_into(out)
         org = (C.c_float * 3)(*[float(x) for x in origin])
         flags = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE
         with torch.cuda.device(self.device):
             _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, n, cp, dp, rp,
-                                              self.H, self.W, 1.0, self._merge, org, out["endpoints"].data_ptr(),
+                                              self.H, self.W, 1.0, self._merge, org, rout["endpoints"].data_ptr(),
                                               out["endcolors"].data_ptr(), out["range"].data_ptr(),
                                               out["endrem"].data_ptr(), out["tri"].data_ptr(), flags, vp(st.cuda_stream), 0),
                        "lt_fusion_scan_dev")
+            ends, ends_scene = self._to_target(rout, out, st)
             if ev:
                 ev[2].record(st)
             res = dict(range=out["range"].view(self.t_H, self.t_W), rem=out["endrem"].view(self.t_H, self.t_W),
-                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=out["endpoints"], tri=out["tri"],
-                       source=src, n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces)
+                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=ends, endpoints_scene=ends_scene,
+                       tri=out["tri"], source=src, n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces)
             if pack:  # adaption != 'cp': no index filter (laserscan.py:1145-1148)
                 res["bin"], res["label_file"] = self._pack(out["endpoints"], False, out["endrem"], out["endcolors"], None,
                                                            self.n_rays, st)
@@ -310,7 +364,7 @@ class DeviceDeform:
         self._mm_vols[key] = vol
         return vol
 
-    def mergemesh(self, clouds, origin=(0.0, 0.0, 0.0), pack=True, out=None, seq=None, source_images=False):
+    def mergemesh(self, clouds, origin=None, pack=True, out=None, seq=None, source_images=False):
         """``clouds``: the (points, remissions, label) CUDA triples of the source scans, already in the primary scan's frame
         (``apply_inv_pose``, laserscan.py:949: pose handling is out of scope).  Returns what :meth:`mesh` returns -- the
         target scan's ``range`` / ``rem`` / ``label`` images, ``endpoints``, ``tri``, the merged cloud's source image under
@@ -320,7 +374,10 @@ class DeviceDeform:
         record afterwards (``mm_state.stats``: scans / waited = no prediction yet / rerun = the bounds moved).  ``seq``: this
         scan's number in its sequence when several chains share the state.  By default the whole scan is ONE native call
         (``lt_mergemesh_scan_dev``; the source image stays inside the projector); ``source_images=True`` composes it from
-        the public steps instead and returns the merged cloud's images under ``source``."""
+        the public steps instead and returns the merged cloud's images under ``source``.  ``origin`` / ``endpoints`` /
+        ``endpoints_scene``: as for :meth:`mesh`."""
+        if origin is None:
+            origin = self.origin
         if self.vol_bnds is None:
             raise RuntimeError("DeviceDeform.mergemesh: constructed without vol_bnds")
         torch, lib = self._torch, self._lib
@@ -345,11 +402,12 @@ class DeviceDeform:
         cp, dp, rp = (vp * 1)(src["label_folded"].data_ptr()), (vp * 1)(src["range"].data_ptr()), (vp * 1)(src["rem"].data_ptr())
         if out is None:
             out = self.scene.alloc_outputs(self.n_rays, label_image=True)
+        rout = self._render_into(out)
         org = (C.c_float * 3)(*[float(x) for x in origin])
         flags = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE
 
         def p(key):
-            a = out.get(key)
+            a = rout.get(key)
             return a.data_ptr() if a is not None else None
 
         def chain(vol):
@@ -386,9 +444,10 @@ class DeviceDeform:
                     mm.stats["rerun"] += 1
                     vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
                     chain(vol)
+            ends, ends_scene = self._to_target(rout, out, st)
             res = dict(range=out["range"].view(self.t_H, self.t_W), rem=out["endrem"].view(self.t_H, self.t_W),
-                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=out["endpoints"], tri=out["tri"],
-                       source=src, n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces,
+                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=ends, endpoints_scene=ends_scene,
+                       tri=rout["tri"], source=src, n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces,
                        vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
                        vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol)
             if pack:
@@ -418,11 +477,12 @@ class DeviceDeform:
                 beams = np.ascontiguousarray(self.beam_angles, dtype=np.float64)
             if out is None:
                 out = self.scene.alloc_outputs(self.n_rays, label_image=True)
+            rout = self._render_into(out)
             org = (C.c_float * 3)(*[float(x) for x in origin])
             flags = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE
 
             def p(key):
-                a = out.get(key)
+                a = rout.get(key)
                 return a.data_ptr() if a is not None else None
             pred = mm.pred
             vol = None
@@ -461,8 +521,10 @@ class DeviceDeform:
                                                       self.H, self.W, 1.0, vol._flags, org, p("endpoints"), p("endcolors"),
                                                       p("range"), p("endrem"), p("tri"), flags, vp(st.cuda_stream)),
                            "lt_mergemesh_rerun_dev")
+            ends, ends_scene = self._to_target(rout, out, st)
             res = dict(range=out["range"].view(self.t_H, self.t_W), rem=out["endrem"].view(self.t_H, self.t_W),
-                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=out["endpoints"], tri=out["tri"],
+                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=ends, endpoints_scene=ends_scene,
+                       tri=rout["tri"],
                        n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces,
                        vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
                        vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol, _keep=(pts, rem, lab))
@@ -513,6 +575,8 @@ class DeviceDeform:
         if ingest.device != self.device:
             raise ValueError("DeviceDeform.deform: the ingest stage lives on another device")
         st = self._stream()
+        if back is None and adaption == "cp":    # a mounted target: the merged cloud straight into its frame
+            back = self.cp_back(ingest.source.poses[int(idx)])
         clouds = ingest.prepare(idx, merged=adaption != "mesh", stream=st, back=back)
         return getattr(self, adaption)(clouds, **kw)
 

@@ -24,8 +24,10 @@ def create_rays(fov_up, fov_down, H, W):
     return np.ascontiguousarray(beams.reshape(H * W, 3).astype(np.float32))
 
 
-def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None):
-    """:func:`create_rays` computed by the HIP kernel into a ``torch`` tensor ``[H*W, 3] f32`` on the GPU."""
+def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=None):
+    """:func:`create_rays` computed by the HIP kernel into a ``torch`` tensor ``[H*W, 3] f32`` on the GPU.  ``rot``: the
+    rotation [3, 3] of the sensor's pose (``Approach.mount()[1][:3, :3]``) -- every direction is turned by it in float64,
+    ``(r0 * x + r1 * y) + r2 * z`` per component, before the cast to float32; ``None``: the sensor's own frame."""
     import ctypes as C
 
     import torch
@@ -36,8 +38,16 @@ def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None):
     out = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
     st = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.device(dev):
-        _lib.check(lib.lt_create_rays_dev(float(fov_up), float(fov_down), int(H), int(W), out.data_ptr(),
-                                          C.c_void_p(st.cuda_stream)), "lt_create_rays_dev")
+        if rot is None:
+            _lib.check(lib.lt_create_rays_dev(float(fov_up), float(fov_down), int(H), int(W), out.data_ptr(),
+                                              C.c_void_p(st.cuda_stream)), "lt_create_rays_dev")
+        else:
+            r = np.ascontiguousarray(rot, dtype=np.float64)
+            if r.shape != (3, 3):
+                raise ValueError("rot: a 3x3 rotation")
+            _lib.check(lib.lt_create_rays_pose_dev(float(fov_up), float(fov_down), int(H), int(W),
+                                                   r.ctypes.data_as(C.POINTER(C.c_double)), out.data_ptr(),
+                                                   C.c_void_p(st.cuda_stream)), "lt_create_rays_pose_dev")
     return out
 
 

@@ -305,10 +305,16 @@ class FusionScanPipeline:
     The observation tensors must be COMPLETE when a chain reads them: by default ``submit`` waits (on the host) for the
     caller's current stream; a caller whose images are finished anyway passes ``inputs_ready=True``.  The tensors are kept
     referenced until the scan is done; the images are complete when ``wait`` returns.  A scan is ONE native call
-    (``lt_fusion_scan_dev``) on its chain's thread, so the interpreter lock is free while the GPU works."""
+    (``lt_fusion_scan_dev``) on its chain's thread, so the interpreter lock is free while the GPU works.
+
+    ``transformation`` (the approach file's key, or ``Approach.mount()``'s pair): the target sensor stands at ``P = inv(T)``
+    in the scene.  ``rays`` must then be that sensor's posed rays (``create_rays_device(..., rot=P[:3, :3])``); every
+    ``submit*`` casts them from ``float32(P[:3, 3])`` unless it is given an ``origin``, and a scan's ``endpoints`` arrive in
+    the target's frame (``lt_points_to_frame_dev`` on the chain's stream, hits only), ``endpoints_scene`` as rendered.
+    Empty, ``None`` or the identity: nothing changes."""
 
     def __init__(self, vol_bnds, voxel_size, fov_up, fov_down, rays, H, chains=3, device=None, merge=True,
-                 label_image=False, source_hw=None, beam_angles=None, fixed_volume=True):
+                 label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None):
         import queue
         import threading
         import weakref
@@ -323,7 +329,14 @@ class FusionScanPipeline:
         self.device = rays.device if device is None else torch.device("cuda", device)
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
-        self.rayset = RaySet(rays, H)  # one read-only ray set for all chains
+        from .config import mount_of
+        self.mount = mount_of(transformation)
+        self.origin = (0.0, 0.0, 0.0)
+        if self.mount is not None:
+            import numpy as np
+            self.origin = tuple(float(np.float32(x)) for x in self.mount[1][:3, 3])
+            self._T = np.ascontiguousarray(self.mount[0], dtype=np.float64)
+        self.rayset = RaySet(rays, H, pose=self.mount[1] if self.mount is not None else None)  # one read-only ray set for all chains
         self.n_rays = self.rayset.n_rays
         self.label_image = bool(label_image)
         self._flags = _lib.LT_TRACE_WRITE_MISSES | (_lib.LT_TRACE_LABEL_IMAGE if label_image else 0)
@@ -357,6 +370,25 @@ class FusionScanPipeline:
         self._next = 0
         for ch in self._chains:
             ch["thread"].start()
+
+    # ---- a mounted target: the hits into its frame, on the chain's stream -------------------------------------------------
+    def _render_into(self, out):
+        if self.mount is None or out.get("endpoints") is None:
+            return out
+        torch = self._torch
+        rout = dict(out)
+        rout["endpoints"] = torch.empty_like(out["endpoints"])
+        if rout.get("tri") is None:
+            rout["tri"] = torch.empty((self.n_rays,), dtype=torch.int32, device=self.device)
+        return rout
+
+    def _to_target(self, rout, out, st, res):
+        if rout is out:
+            return
+        _lib.check(self._lib.lt_points_to_frame_dev(rout["endpoints"].data_ptr(), rout["tri"].data_ptr(), self.n_rays,
+                                                    self._T.ctypes.data_as(C.POINTER(C.c_double)), out["endpoints"].data_ptr(),
+                                                    C.c_void_p(st.cuda_stream)), "lt_points_to_frame_dev")
+        res["endpoints_scene"] = rout["endpoints"]
 
     # ---- a chain's thread ---------------------------------------------------------------------------------------------
     def _scan(self, ch, obs, origin, out):
@@ -399,9 +431,11 @@ class FusionScanPipeline:
                 keep += [c, d, r]
                 cp[k], dp[k], rp[k] = c.data_ptr(), d.data_ptr(), r.data_ptr()
         org = (C.c_float * 3)(*[float(x) for x in origin])
+        with torch.cuda.stream(st):
+            rout = self._render_into(out)
 
         def p(key):
-            a = out.get(key)
+            a = rout.get(key)
             return a.data_ptr() if a is not None else None
         # the whole chain of the scan in ONE native call: the interpreter lock is released for all of it.  The call
         # returns with the render QUEUED (it waits for the stream once, inside marching cubes: the mesh sizes); an event
@@ -409,9 +443,10 @@ class FusionScanPipeline:
         _lib.check(lib.lt_fusion_scan_dev(ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h, self.rayset._h, n, cp, dp, rp, h, w,
                                           1.0, self._merge, org, p("endpoints"), p("endcolors"), p("range"), p("endrem"),
                                           p("tri"), self._flags, vp(st.cuda_stream), 0), "lt_fusion_scan_dev")
+        res = dict(out)
+        self._to_target(rout, out, st, res)
         done = torch.cuda.Event()
         done.record(st)
-        res = dict(out)
         res["n_verts"], res["n_faces"] = ch["mesh"].n_verts, ch["mesh"].n_faces
         res["_done"] = (done, keep, obs)  # (temporaries and observations stay referenced until the event has passed)
         return res
@@ -437,9 +472,10 @@ class FusionScanPipeline:
             import numpy as np
             beams = np.ascontiguousarray(self._beam_angles, dtype=np.float64)
         org = (C.c_float * 3)(*[float(x) for x in origin])
+        rout = self._render_into(out)   # (on the chain's stream: _scan calls this inside `with torch.cuda.stream`)
 
         def p(key):
-            a = out.get(key)
+            a = rout.get(key)
             return a.data_ptr() if a is not None else None
         _lib.check(lib.lt_deform_scan_dev(ch["projector"]._h, ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h, self.rayset._h, n, cl,
                                           int(dt == torch.float64), self._src_fov[0], self._src_fov[1], self._src_hw[0],
@@ -447,9 +483,10 @@ class FusionScanPipeline:
                                           0 if beams is None else len(beams), 1.0, self._merge, org, p("endpoints"),
                                           p("endcolors"), p("range"), p("endrem"), p("tri"), self._flags,
                                           C.c_void_p(st.cuda_stream), 0), "lt_deform_scan_dev")
+        res = dict(out)
+        self._to_target(rout, out, st, res)
         done = torch.cuda.Event()
         done.record(st)
-        res = dict(out)
         res["n_verts"], res["n_faces"] = ch["mesh"].n_verts, ch["mesh"].n_faces
         res["_done"] = (done, keep, items)
         return res
@@ -466,7 +503,8 @@ class FusionScanPipeline:
             sensor_s = (self._src_hw[0], self._src_hw[1], self._src_fov[0], self._src_fov[1])
             sensor_t = (a["H"], self.n_rays // a["H"], self._src_fov[0], self._src_fov[1])
             dd = DeviceDeform(sensor_s, sensor_t, None, a["voxel_size"], beam_angles=self._beam_angles, device=self.device.index,
-                              merge=a["merge"], mesh_volume=False, rayset=self.rayset, mm_state=self._mm_state)
+                              merge=a["merge"], mesh_volume=False, rayset=self.rayset, mm_state=self._mm_state,
+                              transformation=self.mount)
             ch["deform"] = dd
         clouds = [(pts, rem, lab) for _, pts, rem, lab, _ in items]
         with torch.cuda.stream(ch["stream"]):
@@ -476,6 +514,8 @@ class FusionScanPipeline:
         res = dict(out)
         for k in ("n_verts", "n_faces", "vol_dim", "vol_origin", "vol_bnds_after"):
             res[k] = got[k]
+        if self.mount is not None:
+            res["endpoints_scene"] = got["endpoints_scene"]
         res["_done"] = (done, [got.get("source"), got.get("_keep")], items)
         return res
 
@@ -491,7 +531,7 @@ class FusionScanPipeline:
         ev.set()
 
     # ---- caller's side --------------------------------------------------------------------------------------------------
-    def submit(self, observations, origin=(0.0, 0.0, 0.0), out=None, inputs_ready=False):
+    def submit(self, observations, origin=None, out=None, inputs_ready=False):
         """Queue one output scan: ``observations`` = the (color_im, depth_im, rem_im) CUDA tensors fused into its volume,
         in order.  Returns the ticket.  ``out``: a dict like ``Scene.alloc_outputs`` returns (missing keys are not written).
         ``inputs_ready``: the caller guarantees that the observation tensors are complete (no wait for its stream)."""
@@ -514,10 +554,12 @@ class FusionScanPipeline:
             t = self._next
             self._next += 1
             self._done[t] = threading.Event()
+        if origin is None:   # the target sensor's own position: (0, 0, 0) unless it is mounted elsewhere
+            origin = self.origin
         self._chains[t % len(self._chains)]["q"].put((t, obs, tuple(origin), out))
         return t
 
-    def submit_clouds(self, clouds, origin=(0.0, 0.0, 0.0), out=None, inputs_ready=False):
+    def submit_clouds(self, clouds, origin=None, out=None, inputs_ready=False):
         """Queue one output scan from the POINT CLOUDS of its source scans: ``clouds`` = ``(points [n,3] f32|f64, remissions
         [n] f32, label [n] i32)`` CUDA tensors per source scan, in the primary scan's frame (laserscan.py:876-879).  The
         chain projects them (``lt_range_projection_batch_dev``, one launch sequence, nothing read back) and runs the fusion
@@ -532,7 +574,7 @@ class FusionScanPipeline:
             items.append(("clouds", c[0], c[1], c[2]))
         return self._submit(items, origin, out, inputs_ready)
 
-    def submit_mergemesh(self, clouds, origin=(0.0, 0.0, 0.0), out=None, inputs_ready=False):
+    def submit_mergemesh(self, clouds, origin=None, out=None, inputs_ready=False):
         """Queue one output scan of the reference's DEFAULT adaption (config/lidar_transfer.yaml:3; laserscan.py:921-1012): the
         source scans' clouds merged, projected with the TARGET field of view (this pipeline's ``fov_up`` / ``fov_down``) onto the
         SOURCE image (``source_hw``), ``vol_bnds`` clipped by the kept points' rounded bounds -- the statements run on the

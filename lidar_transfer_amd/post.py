@@ -45,6 +45,33 @@ def do_reverse_projection_new(range_image, proj_x, proj_y, fov_up, fov_down, pre
     return out.cpu().numpy()
 
 
+def points_to_frame(points, T, tri=None, out=None, stream=None):
+    """``points`` ([n, 3] float32 CUDA tensor, contiguous) into the frame ``T`` (4x4, row-major, host) maps to:
+    ``float32(((m0 * x + m1 * y) + m2 * z) + m3)`` per row of ``T``, in float64 from the float32 point
+    (``lt_points_to_frame_dev``; asynchronous on ``stream``, default the current one).  ``tri`` ([n] int32 CUDA): rows with
+    ``tri < 0`` -- rays that missed -- are copied unchanged.  ``out``: where the result goes (``points`` itself is allowed);
+    default a fresh tensor."""
+    import torch
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or not points.is_contiguous():
+        raise ValueError("points: contiguous float32 CUDA tensor [n, 3]")
+    n = points.numel() // 3
+    m = np.ascontiguousarray(T, dtype=np.float64)
+    if m.size != 16:
+        raise ValueError("T: a 4x4 transform")
+    if tri is not None and (tri.dtype != torch.int32 or not tri.is_contiguous() or tri.numel() != n or tri.device != points.device):
+        raise ValueError("tri: contiguous int32 CUDA tensor [n] on the points' device")
+    if out is None:
+        out = torch.empty_like(points)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != points.numel() or out.device != points.device:
+        raise ValueError("out: contiguous float32 CUDA tensor of the points' shape and device")
+    st = torch.cuda.current_stream(points.device) if stream is None else stream
+    with torch.cuda.device(points.device):
+        _lib.check(_lib.load().lt_points_to_frame_dev(points.data_ptr(), tri.data_ptr() if tri is not None else None, n,
+                                                      m.ctypes.data_as(C.POINTER(C.c_double)), out.data_ptr(),
+                                                      C.c_void_p(st.cuda_stream)), "lt_points_to_frame_dev")
+    return out
+
+
 def pack_scan(back_points, label_image, remissions, index=None):
     """Filtering + packing of ``MultiSemLaserScan.write`` (auxiliary/laserscan.py:1133-1160): returns
     ``(bin [N,4] float32, label [N] uint32)`` -- byte-for-byte what the reference writes to

@@ -104,7 +104,10 @@ class SequenceTransfer:
     fov_up, fov_down)``.  ``out_dir=None``: nothing is written.  ``evaluate=None``: compare when source and target images
     have one size, as lidar_deform.py:416 does.  ``fusion``: ``"cuda"`` or ``"numpy"`` (the reference's two fusion modes).
     ``nclasses``: default ``len(approach.color_map)`` (lidar_deform.py:359).  ``copy_files``: paths (the target and approach
-    YAML) copied next to the output once (lidar_deform.py:446-452)."""
+    YAML) copied next to the output once (lidar_deform.py:446-452).  A non-identity ``approach.transformation`` mounts the
+    target sensor at a pose of its own (``Approach.mount()``; ``DeviceDeform(transformation=...)``): the output is in the
+    target's frame, ``compare()`` against the source scan would mean nothing, so ``evaluate=None`` resolves to ``False`` and
+    ``evaluate=True`` raises; ``mounted`` tells."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -123,7 +126,12 @@ class SequenceTransfer:
         same = self.source_sensor[:2] == self.target_sensor[:2]
         if evaluate and not same:
             raise ValueError("evaluate: source and target images differ in size (lidar_deform.py:416)")
-        self.evaluate = same if evaluate is None else bool(evaluate)
+        self.mount = approach.mount()                # (raises ValueError on a transformation that is not rigid)
+        self.mounted = self.mount is not None
+        if evaluate and self.mounted:
+            raise ValueError("evaluate: the target sensor is mounted at its own pose (approach.transformation): its scan "
+                             "cannot be compared with the source scan cell by cell")
+        self.evaluate = (same and not self.mounted) if evaluate is None else bool(evaluate)
         need = cache_scans_needed(approach.number_of_scans, self.chains, approach.batch_interval)
         idx = torch.cuda.current_device() if device is None else int(device)
         if isinstance(source_seq, SequenceSource):
@@ -151,12 +159,14 @@ class SequenceTransfer:
             for c in range(self.chains):
                 if self.adaption == "cp":
                     dd = DeviceDeform(self.source_sensor, self.target_sensor, None, beam_angles=beams,
-                                      preserve_float=approach.preserve_float, device=idx, fusion=fusion)
+                                      preserve_float=approach.preserve_float, device=idx, fusion=fusion,
+                                      transformation=self.mount)
                 else:
                     dd = DeviceDeform(self.source_sensor, self.target_sensor,
                                       None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
                                       beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
-                                      mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm)
+                                      mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm,
+                                      transformation=self.mount)
                     rayset = dd.rayset
                 ch = dict(dd=dd, ev=None, q=None, thread=None,
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
@@ -240,7 +250,8 @@ class SequenceTransfer:
                 job["done"].set()
                 return job
         st = torch.cuda.current_stream(self.device)
-        job["clouds"] = self.ingest.prepare(idx, merged=self.adaption != "mesh", stream=st)
+        back = self._chains[0]["dd"].cp_back(self.source.poses[int(idx)]) if self.adaption == "cp" else None
+        job["clouds"] = self.ingest.prepare(idx, merged=self.adaption != "mesh", stream=st, back=back)
         if self.evaluate and not job["skipped"]:
             job["raw"] = self.source.raw(idx, st)
         ch = self._chains[k % len(self._chains)]
@@ -306,6 +317,7 @@ class SequenceTransfer:
                 job["done"].wait()
                 job["written"].wait()
             self.summary = dict(scans=n_done, chains=self.chains, adaption=self.adaption, fusion=self.fusion,
+                                mounted=self.mounted,
                                 mm_stats=dict(self._mm.stats) if self._mm is not None else None,
                                 source_stats=dict(self.source.stats))
 
