@@ -1,0 +1,95 @@
+"""What the chain layer (``deform.py``, ``pipeline.py``, ``sequence.py``) hands the library's device entry points, in one
+place: the merged cloud, the ``lt_cloud`` and beam tables, origin and output pointers, and the target sensor's mounting.
+Private; imports without a GPU and without the library (torch and numpy on first use)."""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _lib
+
+TRACE_FLAGS = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE   # every cell written, ``endcolors`` = the label image
+OUT_KEYS = ("endpoints", "endcolors", "range", "endrem", "tri")        # the render's outputs in the entry points' order
+
+
+def merged_cloud(clouds):
+    """``(points, rem, label)`` of the source scans as ONE cloud (laserscan.py:834-839, :939-949): the tensors themselves
+    when there is one scan, else their concatenation in order"""
+    if len(clouds) == 1:
+        return clouds[0][0], clouds[0][1], clouds[0][2]
+    import torch
+    return tuple(torch.cat([c[k] for c in clouds]) for k in range(3))
+
+
+def cloud_table(clouds):
+    """``(lt_cloud array, tensors to keep alive, is_f64)`` of ``(points, rem, label)`` CUDA triples as the native scan calls
+    read them: contiguous points of ONE dtype (float32 or float64, else ``TypeError``), ``rem`` float32, ``label`` int32.
+    The array points into the kept tensors, which may be copies: keep them until the stream is done with them."""
+    import torch
+    cl = (_lib.Cloud * len(clouds))()
+    keep = []
+    dt = clouds[0][0].dtype
+    for k, (pts, rem, lab) in enumerate(clouds):
+        if pts.dtype != dt or dt not in (torch.float32, torch.float64):
+            raise TypeError("clouds: float32 or float64 points, one dtype per output scan")
+        pts = pts.contiguous()
+        rem = rem.contiguous() if rem.dtype == torch.float32 else rem.to(torch.float32).contiguous()
+        lab = lab.contiguous() if lab.dtype == torch.int32 else lab.to(torch.int32).contiguous()
+        keep += [pts, rem, lab]
+        cl[k].points, cl[k].rem, cl[k].label, cl[k].n = pts.data_ptr(), rem.data_ptr(), lab.data_ptr(), int(pts.shape[0])
+    return cl, keep, int(dt == torch.float64)
+
+
+def beam_table(beam_angles):
+    """``(pointer or None, n, array to keep alive)`` of a sensor's beam angles (float64)"""
+    if beam_angles is None or len(beam_angles) == 0:
+        return None, 0, None
+    import numpy as np
+    beams = np.ascontiguousarray(beam_angles, dtype=np.float64)
+    return beams.ctypes.data_as(C.c_void_p), len(beams), beams
+
+
+def origin3(origin):
+    return (C.c_float * 3)(*[float(x) for x in origin])
+
+
+def out_ptrs(out):
+    """the five output pointers ``endpoints, endcolors, range, endrem, tri``; ``None`` = not wanted"""
+    return tuple(out[k].data_ptr() if out.get(k) is not None else None for k in OUT_KEYS)
+
+
+class Mount:
+    """The target sensor's mounting from the approach file's ``transformation`` (``config.mount_of``).  ``pair``: ``(T, P)``,
+    or ``None`` for no mounting (``None``, empty, the identity) -- then nothing here allocates or launches.  ``T``
+    (``x_target = T . x_source``, float64, contiguous) takes the hits into the target's frame; ``P = inv(T)`` is the pose the
+    target's ray set is built with; ``origin``: where its rays start in the scene, ``float32(P[:3, 3])``."""
+
+    def __init__(self, transformation):
+        from .config import mount_of
+        self.pair = mount_of(transformation)
+        self.T = self.P = None
+        self.origin = (0.0, 0.0, 0.0)
+        if self.pair is not None:
+            import numpy as np
+            self.T = np.ascontiguousarray(self.pair[0], dtype=np.float64)
+            self.P = self.pair[1]
+            self.origin = tuple(float(np.float32(x)) for x in self.P[:3, 3])
+
+    def render_into(self, out, n_rays, device):
+        """What the render writes: ``out`` itself without a mounting or without ``endpoints``; else the scene-frame end
+        points go to a buffer of their own (the caller's ``endpoints`` receive the target frame) and the hit triangle is
+        always wanted (misses stay (0, 0, 0)).  Allocates on the current stream."""
+        if self.pair is None or out.get("endpoints") is None:
+            return out
+        import torch
+        rout = dict(out)
+        rout["endpoints"] = torch.empty_like(out["endpoints"])
+        if rout.get("tri") is None:
+            rout["tri"] = torch.empty((n_rays,), dtype=torch.int32, device=device)
+        return rout
+
+    def to_target(self, rout, out, stream):
+        """the hits of ``rout["endpoints"]`` (as rendered) into the target's frame in ``out["endpoints"]``, on ``stream``"""
+        if rout is out:
+            return
+        from .post import points_to_frame
+        points_to_frame(rout["endpoints"], self.T, tri=rout["tri"], out=out["endpoints"], stream=stream)

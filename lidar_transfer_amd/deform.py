@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import _lib
+from . import _chain, _lib
 from .raytracer import RaySet, Scene
 
 
@@ -152,7 +152,6 @@ class DeviceDeform:
         import numpy as np
         import torch
 
-        from .config import mount_of
         from .fusion import DeviceMesh, TSDFVolume
         from .laserscan import Projector, create_rays_device
         self._torch = torch
@@ -173,11 +172,9 @@ class DeviceDeform:
         self.vol_bnds = None
         self._mm_state, self._mm_own = mm_state, mm_state is None
         self._rayset_own = rayset is None
-        self.mount = mount_of(transformation)
-        self.origin = (0.0, 0.0, 0.0)          # the target sensor in the scene: where mesh / mergemesh cast from by default
-        if self.mount is not None:
-            self.origin = tuple(float(np.float32(x)) for x in self.mount[1][:3, 3])
-            self._T = np.ascontiguousarray(self.mount[0], dtype=np.float64)
+        self._mounting = _chain.Mount(transformation)
+        # ``origin``: the target sensor in the scene, where mesh / mergemesh cast from by default
+        self.mount, self.origin = self._mounting.pair, self._mounting.origin
         if mm_state is not None and vol_bnds is None:
             vol_bnds = mm_state.vol_bnds
         if vol_bnds is not None:
@@ -190,7 +187,7 @@ class DeviceDeform:
                 self._merge = self.vol._flags
             self.mesh_obj = DeviceMesh(idx)
             self.scene = Scene(idx)
-            pose = self.mount[1] if self.mount is not None else None
+            pose = self._mounting.P
             if rayset is None:
                 rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=idx,
                                           rot=pose[:3, :3] if pose is not None else None)
@@ -216,28 +213,6 @@ class DeviceDeform:
         self._last_stream = st
         return st
 
-    # ---- a target sensor at its own pose: the hits into its frame ---------------------------------------------------------
-    def _render_into(self, out):
-        """what the render writes when the target is mounted: the scene-frame endpoints go to a buffer of their own (the
-        caller's ``endpoints`` receive the target frame), and the hit triangle is always wanted (misses stay (0, 0, 0))"""
-        if self.mount is None or out.get("endpoints") is None:
-            return out
-        torch = self._torch
-        rout = dict(out)
-        rout["endpoints"] = torch.empty_like(out["endpoints"])
-        if rout.get("tri") is None:
-            rout["tri"] = torch.empty((self.n_rays,), dtype=torch.int32, device=self.device)
-        return rout
-
-    def _to_target(self, rout, out, st):
-        """(endpoints in the target's frame, endpoints as rendered): ``lt_points_to_frame_dev`` on the chain's stream"""
-        if rout is out:
-            return out["endpoints"], out["endpoints"]
-        _lib.check(self._lib.lt_points_to_frame_dev(rout["endpoints"].data_ptr(), rout["tri"].data_ptr(), self.n_rays,
-                                                    self._T.ctypes.data_as(C.POINTER(C.c_double)), out["endpoints"].data_ptr(),
-                                                    C.c_void_p(st.cuda_stream)), "lt_points_to_frame_dev")
-        return out["endpoints"], rout["endpoints"]
-
     def cp_back(self, pose):
         """``cp`` with a mounted target: the second transform of the ingest, ``T . inv(pose of the primary scan)`` (float64,
         host) -- the merged cloud arrives in the target's frame; ``None`` (the ingest's default) without a mounting"""
@@ -257,6 +232,24 @@ class DeviceDeform:
                                               out_lab.data_ptr(), C.byref(kept), C.c_void_p(st.cuda_stream)),
                    "lt_pack_scan_dev")
         return out_bin[:kept.value], out_lab[:kept.value]
+
+    def pack_result(self, out, stream=None):
+        """``write``'s packing for a result of :meth:`cp`, :meth:`mesh` or :meth:`mergemesh` made with ``pack=False``:
+        ``(bin [N,4] f32, label_file [N] i32)``.  ``cp`` packs its float64 ``back_points`` where ``index > 0``
+        (laserscan.py:1133-1144); the mesh adaptions their float32 ``endpoints``, no index filter (:1145-1148)."""
+        st = stream if stream is not None else self._stream()
+        rem, label = out["rem"].reshape(-1), out["label"].reshape(-1)
+        if "back_points" in out:
+            return self._pack(out["back_points"], True, rem, label, out["index"].reshape(-1), self.n_rays, st)
+        return self._pack(out["endpoints"], False, rem, label, None, self.n_rays, st)
+
+    def _result(self, out, rout, **more):
+        """what :meth:`mesh` and :meth:`mergemesh` return of a rendered scan (``rout``: what the render wrote, ``out`` with the
+        end points in the target's frame)"""
+        return dict(range=out["range"].view(self.t_H, self.t_W), rem=out["endrem"].view(self.t_H, self.t_W),
+                    label=out["endcolors"].view(self.t_H, self.t_W), endpoints=out["endpoints"],
+                    endpoints_scene=rout["endpoints"], tri=rout["tri"], n_verts=self.mesh_obj.n_verts,
+                    n_faces=self.mesh_obj.n_faces, **more)
 
     # ---- deform('mesh') + write ---------------------------------------------------------------------------------------
     def mesh(self, clouds, origin=None, pack=True, timing=None):
@@ -287,24 +280,17 @@ class DeviceDeform:
         for k, o in enumerate(src):
             cp[k], dp[k], rp[k] = o["label_folded"].data_ptr(), o["range"].data_ptr(), o["rem"].data_ptr()
         out = self.scene.alloc_outputs(self.n_rays, label_image=True)
-        rout = self._render_into(out)
-        org = (C.c_float * 3)(*[float(x) for x in origin])
-        flags = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE
+        rout = self._mounting.render_into(out, self.n_rays, self.device)
         with torch.cuda.device(self.device):
             _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, n, cp, dp, rp,
-                                              self.H, self.W, 1.0, self._merge, org, rout["endpoints"].data_ptr(),
-                                              out["endcolors"].data_ptr(), out["range"].data_ptr(),
-                                              out["endrem"].data_ptr(), out["tri"].data_ptr(), flags, vp(st.cuda_stream), 0),
-                       "lt_fusion_scan_dev")
-            ends, ends_scene = self._to_target(rout, out, st)
+                                              self.H, self.W, 1.0, self._merge, _chain.origin3(origin), *_chain.out_ptrs(rout),
+                                              _chain.TRACE_FLAGS, vp(st.cuda_stream), 0), "lt_fusion_scan_dev")
+            self._mounting.to_target(rout, out, st)
             if ev:
                 ev[2].record(st)
-            res = dict(range=out["range"].view(self.t_H, self.t_W), rem=out["endrem"].view(self.t_H, self.t_W),
-                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=ends, endpoints_scene=ends_scene,
-                       tri=out["tri"], source=src, n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces)
-            if pack:  # adaption != 'cp': no index filter (laserscan.py:1145-1148)
-                res["bin"], res["label_file"] = self._pack(out["endpoints"], False, out["endrem"], out["endcolors"], None,
-                                                           self.n_rays, st)
+            res = self._result(out, rout, source=src)
+            if pack:
+                res["bin"], res["label_file"] = self.pack_result(res, st)
             if ev:
                 ev[3].record(st)
                 timing.append(ev)
@@ -330,14 +316,10 @@ class DeviceDeform:
         (``lidar_transfer_amd.dist.mergemesh_plan``: the scans before the block are replayed through this)."""
         if self.vol_bnds is None:
             raise RuntimeError("DeviceDeform.mergemesh_bounds: constructed without vol_bnds")
-        torch = self._torch
         mm = self._mm()
         st = self._stream()
-        pts = torch.cat([c[0] for c in clouds]) if len(clouds) != 1 else clouds[0][0]
-        rem = torch.cat([c[1] for c in clouds]) if len(clouds) != 1 else clouds[0][1]
-        lab = torch.cat([c[2] for c in clouds]) if len(clouds) != 1 else clouds[0][2]
-        src = self.projector.project([(pts, rem, lab)], self.t_fov_up, self.t_fov_down, self.H, self.W, new=True, remove=True,
-                                     beam_angles=self.beam_angles, outputs=("range", "bnds"), stream=st)[0]
+        src = self.projector.project([_chain.merged_cloud(clouds)], self.t_fov_up, self.t_fov_down, self.H, self.W, new=True,
+                                     remove=True, beam_angles=self.beam_angles, outputs=("range", "bnds"), stream=st)[0]
         with mm._turn:
             mm.pred = None   # (the next scan waits for its own record: the replayed ones were not verified on the host)
         return mm.geometry(src["bnds"], st, seq)
@@ -361,6 +343,7 @@ class DeviceDeform:
             vol = TSDFVolume(np.array(key).reshape(3, 2), self._voxel_size, self.t_fov_up, self.t_fov_down, device=self._idx,
                              merge=self._merge_flag, mode=self._fusion)   # (3) the TARGET field of view (:968-969)
             assert tuple(int(x) for x in vol._vol_dim) == tuple(int(x) for x in dim)
+            vol.bnds_given = key   # (what the library keeps as the volume's ``bnds_given``: is this a scan's geometry?)
         self._mm_vols[key] = vol
         return vol
 
@@ -380,132 +363,28 @@ class DeviceDeform:
             origin = self.origin
         if self.vol_bnds is None:
             raise RuntimeError("DeviceDeform.mergemesh: constructed without vol_bnds")
-        torch, lib = self._torch, self._lib
+        torch = self._torch
         mm = self._mm()
-        if not source_images:
-            return self._mergemesh_native(mm, clouds, origin, pack, out, seq)
-        try:
+        try:   # (a scan that fails before its geometry call gives up its turn; a no-op once the call has been made)
             st = self._stream()
-            pts = torch.cat([c[0] for c in clouds]) if len(clouds) != 1 else clouds[0][0]
-            rem = torch.cat([c[1] for c in clouds]) if len(clouds) != 1 else clouds[0][1]
-            lab = torch.cat([c[2] for c in clouds]) if len(clouds) != 1 else clouds[0][2]
-            # (1) + (2): the SOURCE image size and beam angles, the TARGET field of view (laserscan.py:929-931, :952-954)
-            src = self.projector.project([(pts, rem, lab)], self.t_fov_up, self.t_fov_down, self.H, self.W, new=True, remove=True,
-                                         beam_angles=self.beam_angles, outputs=("range", "rem", "label_folded", "bnds"),
-                                         stream=st)[0]
-        except BaseException:
-            if seq is not None:
-                mm.skip(seq)
-            raise
-        ticket = mm.geometry(src["bnds"], st, seq)
-        vp = C.c_void_p
-        cp, dp, rp = (vp * 1)(src["label_folded"].data_ptr()), (vp * 1)(src["range"].data_ptr()), (vp * 1)(src["rem"].data_ptr())
-        if out is None:
-            out = self.scene.alloc_outputs(self.n_rays, label_image=True)
-        rout = self._render_into(out)
-        org = (C.c_float * 3)(*[float(x) for x in origin])
-        flags = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE
-
-        def p(key):
-            a = rout.get(key)
-            return a.data_ptr() if a is not None else None
-
-        def chain(vol):
-            _lib.check(lib.lt_fusion_scan_dev(vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, 1, cp, dp, rp,
-                                              self.H, self.W, 1.0, vol._flags, org, p("endpoints"), p("endcolors"), p("range"),
-                                              p("endrem"), p("tri"), flags, vp(st.cuda_stream), 0), "lt_fusion_scan_dev")
-
-        def verdict(geo):
-            mm.settle(ticket, geo)
-            if geo.status == 1:
-                raise ValueError("DeviceDeform.mergemesh: no point survives the projection (numpy: zero-size array to amin)")
-            if geo.status == 2:
-                raise RuntimeError(f"DeviceDeform.mergemesh: the clipped volume is empty (bounds {list(geo.bnds_given)})")
-
-        with torch.cuda.device(self.device):
-            pred = mm.pred
-            mm.stats["scans"] += 1
-            if pred is None:          # the first scan of a sequence: nothing to assume
-                mm.stats["waited"] += 1
-                geo = mm.get(ticket)
-                verdict(geo)
-                vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
-                chain(vol)
-            else:
-                vol = self._mm_vols.get(pred)
-                if vol is None:       # (another chain of the sequence verified this geometry)
-                    import numpy as np
-                    b = np.array(pred).reshape(3, 2)
-                    vol = self._mergemesh_volume(pred, np.ceil((b[:, 1] - b[:, 0]) / self._voxel_size).astype(int))
-                chain(vol)            # (waits for the stream once, inside marching cubes: the record has arrived with it)
-                geo = mm.get(ticket)
-                verdict(geo)
-                if tuple(geo.bnds_given) != pred:   # the bounds moved: this scan once more, on its own geometry
-                    mm.stats["rerun"] += 1
-                    vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
-                    chain(vol)
-            ends, ends_scene = self._to_target(rout, out, st)
-            res = dict(range=out["range"].view(self.t_H, self.t_W), rem=out["endrem"].view(self.t_H, self.t_W),
-                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=ends, endpoints_scene=ends_scene,
-                       tri=rout["tri"], source=src, n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces,
-                       vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
-                       vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol)
-            if pack:
-                res["bin"], res["label_file"] = self._pack(out["endpoints"], False, out["endrem"], out["endcolors"], None,
-                                                           self.n_rays, st)
-        return res
-
-    def _mergemesh_native(self, mm, clouds, origin, pack, out, seq):
-        """:meth:`mergemesh` as one native call per scan (+ one more when the bounds moved)"""
-        torch, lib = self._torch, self._lib
-        vp = C.c_void_p
-        try:
-            st = self._stream()
-            pts = torch.cat([c[0] for c in clouds]) if len(clouds) != 1 else clouds[0][0]
-            rem = torch.cat([c[1] for c in clouds]) if len(clouds) != 1 else clouds[0][1]
-            lab = torch.cat([c[2] for c in clouds]) if len(clouds) != 1 else clouds[0][2]
-            if pts.dtype not in (torch.float32, torch.float64):
-                raise TypeError("clouds: float32 or float64 points")
-            pts = pts.contiguous()
-            rem = rem.contiguous() if rem.dtype == torch.float32 else rem.to(torch.float32).contiguous()
-            lab = lab.contiguous() if lab.dtype == torch.int32 else lab.to(torch.int32).contiguous()
-            cl = (_lib.Cloud * 1)()
-            cl[0].points, cl[0].rem, cl[0].label, cl[0].n = pts.data_ptr(), rem.data_ptr(), lab.data_ptr(), int(pts.shape[0])
-            beams = None
-            if self.beam_angles:
-                import numpy as np
-                beams = np.ascontiguousarray(self.beam_angles, dtype=np.float64)
+            cloud = _chain.merged_cloud(clouds)
             if out is None:
                 out = self.scene.alloc_outputs(self.n_rays, label_image=True)
-            rout = self._render_into(out)
-            org = (C.c_float * 3)(*[float(x) for x in origin])
-            flags = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE
-
-            def p(key):
-                a = rout.get(key)
-                return a.data_ptr() if a is not None else None
-            pred = mm.pred
-            vol = None
+            rout = self._mounting.render_into(out, self.n_rays, self.device)
+            first, again, more = (self._mm_composed if source_images else self._mm_native)(
+                mm, cloud, seq, _chain.origin3(origin), _chain.out_ptrs(rout), st)
+            pred, vol = mm.pred, None
             if pred is not None:
                 vol = self._mm_vols.get(pred)
                 if vol is None:       # (another chain of the sequence verified this geometry)
                     import numpy as np
                     b = np.array(pred).reshape(3, 2)
                     vol = self._mergemesh_volume(pred, np.ceil((b[:, 1] - b[:, 0]) / self._voxel_size).astype(int))
-            tflags = vol._flags if vol is not None else (_lib.LT_TSDF_HOST_MODE if self._fusion == "numpy" else self._merge)
-            geo, done = _lib.MMGeometry(), C.c_int(0)
             with torch.cuda.device(self.device):
-                _lib.check(lib.lt_mergemesh_scan_dev(self.projector._h, mm._h, -1 if seq is None else int(seq),
-                                                     vol._h if vol is not None else None, self.mesh_obj._h, self.scene._h,
-                                                     self.rayset._h, cl, int(pts.dtype == torch.float64), self.t_fov_up,
-                                                     self.t_fov_down, self.H, self.W,
-                                                     beams.ctypes.data_as(vp) if beams is not None else None,
-                                                     0 if beams is None else len(beams), 1.0, tflags, org, p("endpoints"),
-                                                     p("endcolors"), p("range"), p("endrem"), p("tri"), flags, vp(st.cuda_stream),
-                                                     C.byref(geo), C.byref(done)), "lt_mergemesh_scan_dev")
+                geo, done = first(vol)
         except BaseException:
             if seq is not None:
-                mm.skip(seq)   # (no-op when the native call has made the scan's geometry call already)
+                mm.skip(seq)
             raise
         with torch.cuda.device(self.device):
             mm.stats["scans"] += 1
@@ -514,24 +393,66 @@ class DeviceDeform:
                 raise ValueError("DeviceDeform.mergemesh: no point survives the projection (numpy: zero-size array to amin)")
             if geo.status == 2:
                 raise RuntimeError(f"DeviceDeform.mergemesh: the clipped volume is empty (bounds {list(geo.bnds_given)})")
-            if not done.value:
+            if not done:   # nothing to assume (the first scan of a sequence), or the bounds moved: on its own geometry
                 mm.stats["waited" if vol is None else "rerun"] += 1
                 vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
-                _lib.check(lib.lt_mergemesh_rerun_dev(self.projector._h, vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h,
-                                                      self.H, self.W, 1.0, vol._flags, org, p("endpoints"), p("endcolors"),
-                                                      p("range"), p("endrem"), p("tri"), flags, vp(st.cuda_stream)),
-                           "lt_mergemesh_rerun_dev")
-            ends, ends_scene = self._to_target(rout, out, st)
-            res = dict(range=out["range"].view(self.t_H, self.t_W), rem=out["endrem"].view(self.t_H, self.t_W),
-                       label=out["endcolors"].view(self.t_H, self.t_W), endpoints=ends, endpoints_scene=ends_scene,
-                       tri=rout["tri"],
-                       n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces,
-                       vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
-                       vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol, _keep=(pts, rem, lab))
+                again(vol)
+            self._mounting.to_target(rout, out, st)
+            res = self._result(out, rout, vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
+                               vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol, **more)
             if pack:
-                res["bin"], res["label_file"] = self._pack(out["endpoints"], False, out["endrem"], out["endcolors"], None,
-                                                           self.n_rays, st)
+                res["bin"], res["label_file"] = self.pack_result(res, st)
         return res
+
+    # The two ways of issuing a mergemesh scan's device calls: ``first(vol or None) -> (geo, done)`` = projection + bounds
+    # statements [+ the chain on ``vol``, the predicted geometry] + the record, ``done``: the chain ran on the scan's own
+    # geometry; ``again(vol)`` = the chain once more on the projected images; and what the way adds to the result.
+    def _mm_native(self, mm, cloud, seq, org, ptrs, st):
+        """one native call per scan (+ ``lt_mergemesh_rerun_dev``): the source images stay inside the projector"""
+        lib, vp = self._lib, C.c_void_p
+        cl, keep, is_f64 = _chain.cloud_table([cloud])
+        beams = _chain.beam_table(self.beam_angles)   # (pointer, n, the array: alive as long as the callables)
+        p = self.projector._h
+
+        def first(vol):
+            tflags = vol._flags if vol is not None else (_lib.LT_TSDF_HOST_MODE if self._fusion == "numpy" else self._merge)
+            geo, done = _lib.MMGeometry(), C.c_int(0)
+            _lib.check(lib.lt_mergemesh_scan_dev(p, mm._h, -1 if seq is None else int(seq), vol._h if vol is not None else None,
+                                                 self.mesh_obj._h, self.scene._h, self.rayset._h, cl, is_f64, self.t_fov_up,
+                                                 self.t_fov_down, self.H, self.W, beams[0], beams[1], 1.0, tflags, org, *ptrs,
+                                                 _chain.TRACE_FLAGS, vp(st.cuda_stream), C.byref(geo), C.byref(done)),
+                       "lt_mergemesh_scan_dev")
+            return geo, bool(done.value)
+
+        def again(vol):
+            _lib.check(lib.lt_mergemesh_rerun_dev(p, vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, self.H, self.W, 1.0,
+                                                  vol._flags, org, *ptrs, _chain.TRACE_FLAGS, vp(st.cuda_stream)),
+                       "lt_mergemesh_rerun_dev")
+        return first, again, dict(_keep=tuple(keep))
+
+    def _mm_composed(self, mm, cloud, seq, org, ptrs, st):
+        """the public steps -- ``project``, ``lt_mm_geometry_dev``, ``lt_fusion_scan_dev`` -- with the merged cloud's images
+        returned under ``source``"""
+        vp = C.c_void_p
+        src = {}
+
+        def again(vol):
+            cp, dp, rp = (vp * 1)(src["label_folded"].data_ptr()), (vp * 1)(src["range"].data_ptr()), (vp * 1)(src["rem"].data_ptr())
+            _lib.check(self._lib.lt_fusion_scan_dev(vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, 1, cp, dp, rp, self.H,
+                                                    self.W, 1.0, vol._flags, org, *ptrs, _chain.TRACE_FLAGS, vp(st.cuda_stream), 0),
+                       "lt_fusion_scan_dev")
+
+        def first(vol):
+            # (1) + (2): the SOURCE image size and beam angles, the TARGET field of view (laserscan.py:929-931, :952-954)
+            src.update(self.projector.project([cloud], self.t_fov_up, self.t_fov_down, self.H, self.W, new=True, remove=True,
+                                              beam_angles=self.beam_angles, outputs=("range", "rem", "label_folded", "bnds"),
+                                              stream=st)[0])
+            ticket = mm.geometry(src["bnds"], st, seq)
+            if vol is not None:
+                again(vol)            # (waits for the stream once, inside marching cubes: the record has arrived with it)
+            geo = mm.get(ticket)
+            return geo, vol is not None and geo.status == 0 and tuple(geo.bnds_given) == vol.bnds_given
+        return first, again, dict(source=src)
 
     # ---- deform('cp') + write -----------------------------------------------------------------------------------------
     def cp(self, clouds, pack=True):
@@ -542,12 +463,9 @@ class DeviceDeform:
         that; float32 clouds with ``preserve_float`` are re-projected in float64 here as well (numpy would stay in float32)."""
         torch, lib = self._torch, self._lib
         st = self._stream()
-        pts = torch.cat([c[0] for c in clouds]) if len(clouds) != 1 else clouds[0][0]
-        rem = torch.cat([c[1] for c in clouds]) if len(clouds) != 1 else clouds[0][1]
-        lab = torch.cat([c[2] for c in clouds]) if len(clouds) != 1 else clouds[0][2]
         pf = self.preserve_float
         outs = ("idx", "range", "rem", "label") + (("proj_xf", "proj_yf") if pf else ("proj_x", "proj_y"))
-        o = self.projector.project([(pts, rem, lab)], self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, new=True,
+        o = self.projector.project([_chain.merged_cloud(clouds)], self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, new=True,
                                    remove=True, beam_angles=self.t_beam_angles, outputs=outs, stream=st)[0]
         px, py = (o["proj_xf"], o["proj_yf"]) if pf else (o["proj_x"], o["proj_y"])
         if pf and px.dtype != torch.float64:
@@ -559,8 +477,7 @@ class DeviceDeform:
                                                      C.c_void_p(st.cuda_stream)), "lt_reverse_projection_dev")
             res = dict(range=o["range"], rem=o["rem"], label=o["label"], index=o["idx"], back_points=back)
             if pack:
-                res["bin"], res["label_file"] = self._pack(back, True, o["rem"].view(-1), o["label"].view(-1),
-                                                           o["idx"].view(-1), self.n_rays, st)
+                res["bin"], res["label_file"] = self.pack_result(res, st)
         return res
 
     # ---- open_multiple_scans + deform(adaption, poses, idx) ----------------------------------------------------------------

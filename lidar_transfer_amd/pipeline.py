@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import _lib
+from . import _chain, _lib
 from .raytracer import RaySet, Scene
 
 
@@ -329,14 +329,9 @@ class FusionScanPipeline:
         self.device = rays.device if device is None else torch.device("cuda", device)
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
-        from .config import mount_of
-        self.mount = mount_of(transformation)
-        self.origin = (0.0, 0.0, 0.0)
-        if self.mount is not None:
-            import numpy as np
-            self.origin = tuple(float(np.float32(x)) for x in self.mount[1][:3, 3])
-            self._T = np.ascontiguousarray(self.mount[0], dtype=np.float64)
-        self.rayset = RaySet(rays, H, pose=self.mount[1] if self.mount is not None else None)  # one read-only ray set for all chains
+        self._mounting = _chain.Mount(transformation)
+        self.mount, self.origin = self._mounting.pair, self._mounting.origin
+        self.rayset = RaySet(rays, H, pose=self._mounting.P)  # one read-only ray set for all chains
         self.n_rays = self.rayset.n_rays
         self.label_image = bool(label_image)
         self._flags = _lib.LT_TRACE_WRITE_MISSES | (_lib.LT_TRACE_LABEL_IMAGE if label_image else 0)
@@ -371,131 +366,83 @@ class FusionScanPipeline:
         for ch in self._chains:
             ch["thread"].start()
 
-    # ---- a mounted target: the hits into its frame, on the chain's stream -------------------------------------------------
-    def _render_into(self, out):
-        if self.mount is None or out.get("endpoints") is None:
-            return out
-        torch = self._torch
-        rout = dict(out)
-        rout["endpoints"] = torch.empty_like(out["endpoints"])
-        if rout.get("tri") is None:
-            rout["tri"] = torch.empty((self.n_rays,), dtype=torch.int32, device=self.device)
-        return rout
-
-    def _to_target(self, rout, out, st, res):
-        if rout is out:
-            return
-        _lib.check(self._lib.lt_points_to_frame_dev(rout["endpoints"].data_ptr(), rout["tri"].data_ptr(), self.n_rays,
-                                                    self._T.ctypes.data_as(C.POINTER(C.c_double)), out["endpoints"].data_ptr(),
-                                                    C.c_void_p(st.cuda_stream)), "lt_points_to_frame_dev")
-        res["endpoints_scene"] = rout["endpoints"]
-
     # ---- a chain's thread ---------------------------------------------------------------------------------------------
-    def _scan(self, ch, obs, origin, out):
-        torch, lib = self._torch, self._lib
-        st = ch["stream"]
-        keep = []
-        n = len(obs)
-        vp = C.c_void_p
-        cp, dp, rp = (vp * max(n, 1))(), (vp * max(n, 1))(), (vp * max(n, 1))()
-        if obs and len(obs[0]) == 5:  # ("mergemesh", points, rem, label, seq) items
-            try:
-                with torch.cuda.stream(st):
-                    if out is None:
-                        out = ch["scene"].alloc_outputs(self.n_rays, label_image=self.label_image)
-                    return self._scan_mergemesh(ch, obs, origin, out)
-            except BaseException:
-                self._mm_state.skip(obs[0][4])  # (a failed scan -- its outputs included -- must not hold up the later scans)
-                raise
-        with torch.cuda.stream(st):
-            if out is None:
-                out = ch["scene"].alloc_outputs(self.n_rays, label_image=self.label_image)
-            h = w = 0
-            if ch["vol"] is None:
-                raise RuntimeError("FusionScanPipeline: constructed with fixed_volume=False (submit_mergemesh only)")
-            if obs and len(obs[0]) == 4:  # ("clouds", points, rem, label) items: ONE native call (lt_deform_scan_dev)
-                return self._scan_clouds(ch, obs, origin, out)
-            for k, (color_im, depth_im, rem_im) in enumerate(obs):
-                # float32 FIRST, then fold RGB into one channel -- the reference's order (fusion_lidar.py:260-264:
-                # color_im.astype(np.float32), then floor(b*256*256 + g*256 + r)); folding in the caller's dtype wraps a
-                # uint8 image to 0 and overflows float16
-                c = color_im.to(torch.float32)
-                if c.dim() == 3:
-                    c = torch.floor(c[:, :, 0] * 256 * 256 + c[:, :, 1] * 256 + c[:, :, 2])
-                c = c.contiguous()
-                d = depth_im.to(torch.float32).contiguous()
-                r = rem_im.to(torch.float32).contiguous()
-                if k and (d.shape[0], d.shape[1]) != (h, w):
-                    raise ValueError("observations of one output scan must have one image shape")
-                h, w = d.shape[0], d.shape[1]
-                keep += [c, d, r]
-                cp[k], dp[k], rp[k] = c.data_ptr(), d.data_ptr(), r.data_ptr()
-        org = (C.c_float * 3)(*[float(x) for x in origin])
-        with torch.cuda.stream(st):
-            rout = self._render_into(out)
+    def _scan(self, ch, kind, items, origin, out, seq):
+        """one job on its chain's stream: ``kind`` is ``"images"`` (:meth:`submit`), ``"clouds"`` or ``"mergemesh"``"""
+        torch = self._torch
+        try:
+            with torch.cuda.stream(ch["stream"]):
+                if out is None:
+                    out = ch["scene"].alloc_outputs(self.n_rays, label_image=self.label_image)
+                if kind == "mergemesh":
+                    return self._scan_mergemesh(ch, items, origin, out, seq)
+                if ch["vol"] is None:
+                    raise RuntimeError("FusionScanPipeline: constructed with fixed_volume=False (submit_mergemesh only)")
+                rout = self._mounting.render_into(out, self.n_rays, self.device)
+                scan = self._scan_clouds if kind == "clouds" else self._scan_images
+                keep = scan(ch, items, _chain.origin3(origin), _chain.out_ptrs(rout))
+                return self._finish(ch, out, rout, ch["mesh"], keep, items)
+        except BaseException:
+            if kind == "mergemesh":
+                self._mm_state.skip(seq)  # (a failed scan -- its outputs included -- must not hold up the later scans)
+            raise
 
-        def p(key):
-            a = rout.get(key)
-            return a.data_ptr() if a is not None else None
-        # the whole chain of the scan in ONE native call: the interpreter lock is released for all of it.  The call
-        # returns with the render QUEUED (it waits for the stream once, inside marching cubes: the mesh sizes); an event
-        # behind the render is what wait() waits for, so the chain's next scan is queued while this one still renders.
-        _lib.check(lib.lt_fusion_scan_dev(ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h, self.rayset._h, n, cp, dp, rp, h, w,
-                                          1.0, self._merge, org, p("endpoints"), p("endcolors"), p("range"), p("endrem"),
-                                          p("tri"), self._flags, vp(st.cuda_stream), 0), "lt_fusion_scan_dev")
-        res = dict(out)
-        self._to_target(rout, out, st, res)
-        done = torch.cuda.Event()
-        done.record(st)
-        res["n_verts"], res["n_faces"] = ch["mesh"].n_verts, ch["mesh"].n_faces
-        res["_done"] = (done, keep, obs)  # (temporaries and observations stay referenced until the event has passed)
-        return res
-
-    def _scan_clouds(self, ch, items, origin, out):
-        """projection of the source scans + the fusion chain, one native call on this chain's stream"""
-        torch, lib = self._torch, self._lib
-        st = ch["stream"]
-        n = len(items)
-        cl = (_lib.Cloud * n)()
-        keep = []
-        dt = items[0][1].dtype
-        for k, (_, pts, rem, lab) in enumerate(items):
-            if pts.dtype != dt or dt not in (torch.float32, torch.float64):
-                raise TypeError("clouds: float32 or float64 points, one dtype per output scan")
-            pts = pts.contiguous()
-            rem = rem.contiguous() if rem.dtype == torch.float32 else rem.to(torch.float32).contiguous()
-            lab = lab.contiguous() if lab.dtype == torch.int32 else lab.to(torch.int32).contiguous()
-            keep += [pts, rem, lab]
-            cl[k].points, cl[k].rem, cl[k].label, cl[k].n = pts.data_ptr(), rem.data_ptr(), lab.data_ptr(), int(pts.shape[0])
-        beams = None
-        if self._beam_angles:
-            import numpy as np
-            beams = np.ascontiguousarray(self._beam_angles, dtype=np.float64)
-        org = (C.c_float * 3)(*[float(x) for x in origin])
-        rout = self._render_into(out)   # (on the chain's stream: _scan calls this inside `with torch.cuda.stream`)
-
-        def p(key):
-            a = rout.get(key)
-            return a.data_ptr() if a is not None else None
-        _lib.check(lib.lt_deform_scan_dev(ch["projector"]._h, ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h, self.rayset._h, n, cl,
-                                          int(dt == torch.float64), self._src_fov[0], self._src_fov[1], self._src_hw[0],
-                                          self._src_hw[1], beams.ctypes.data_as(C.c_void_p) if beams is not None else None,
-                                          0 if beams is None else len(beams), 1.0, self._merge, org, p("endpoints"),
-                                          p("endcolors"), p("range"), p("endrem"), p("tri"), self._flags,
-                                          C.c_void_p(st.cuda_stream), 0), "lt_deform_scan_dev")
-        res = dict(out)
-        self._to_target(rout, out, st, res)
-        done = torch.cuda.Event()
-        done.record(st)
-        res["n_verts"], res["n_faces"] = ch["mesh"].n_verts, ch["mesh"].n_faces
+    def _finish(self, ch, out, rout, mesh, keep, items, **more):
+        """What every scan ends in: the hits into the target's frame (a mounted target; ``rout``: what the render wrote), an
+        event behind the render on the chain's stream -- what wait() waits for, so the chain's next scan is queued while this
+        one still renders -- and the result; temporaries and inputs stay referenced until the event has passed."""
+        res = dict(out, n_verts=mesh.n_verts, n_faces=mesh.n_faces, **more)
+        if rout is not out:
+            self._mounting.to_target(rout, out, ch["stream"])
+            res["endpoints_scene"] = rout["endpoints"]
+        done = self._torch.cuda.Event()
+        done.record(ch["stream"])
         res["_done"] = (done, keep, items)
         return res
 
-    def _scan_mergemesh(self, ch, items, origin, out):
+    def _scan_images(self, ch, obs, org, ptrs):
+        """the fusion chain on the caller's images.  ONE native call: the interpreter lock is released for all of it, and it
+        returns with the render QUEUED (it waits for the stream once, inside marching cubes: the mesh sizes)"""
+        torch = self._torch
+        n = len(obs)
+        vp = C.c_void_p
+        cp, dp, rp = (vp * max(n, 1))(), (vp * max(n, 1))(), (vp * max(n, 1))()
+        keep = []
+        h = w = 0
+        for k, (color_im, depth_im, rem_im) in enumerate(obs):
+            # float32 FIRST, then fold RGB into one channel -- the reference's order (fusion_lidar.py:260-264:
+            # color_im.astype(np.float32), then floor(b*256*256 + g*256 + r)); folding in the caller's dtype wraps a
+            # uint8 image to 0 and overflows float16
+            c = color_im.to(torch.float32)
+            if c.dim() == 3:
+                c = torch.floor(c[:, :, 0] * 256 * 256 + c[:, :, 1] * 256 + c[:, :, 2])
+            c = c.contiguous()
+            d = depth_im.to(torch.float32).contiguous()
+            r = rem_im.to(torch.float32).contiguous()
+            if k and (d.shape[0], d.shape[1]) != (h, w):
+                raise ValueError("observations of one output scan must have one image shape")
+            h, w = d.shape[0], d.shape[1]
+            keep += [c, d, r]
+            cp[k], dp[k], rp[k] = c.data_ptr(), d.data_ptr(), r.data_ptr()
+        _lib.check(self._lib.lt_fusion_scan_dev(ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h, self.rayset._h, n, cp, dp, rp, h, w,
+                                                1.0, self._merge, org, *ptrs, self._flags, vp(ch["stream"].cuda_stream), 0),
+                   "lt_fusion_scan_dev")
+        return keep
+
+    def _scan_clouds(self, ch, clouds, org, ptrs):
+        """projection of the source scans + the fusion chain, ONE native call (``lt_deform_scan_dev``)"""
+        cl, keep, is_f64 = _chain.cloud_table(clouds)
+        beams, n_beams, _ = _chain.beam_table(self._beam_angles)
+        _lib.check(self._lib.lt_deform_scan_dev(ch["projector"]._h, ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h, self.rayset._h,
+                                                len(clouds), cl, is_f64, self._src_fov[0], self._src_fov[1], self._src_hw[0],
+                                                self._src_hw[1], beams, n_beams, 1.0, self._merge, org, *ptrs, self._flags,
+                                                C.c_void_p(ch["stream"].cuda_stream), 0), "lt_deform_scan_dev")
+        return keep
+
+    def _scan_mergemesh(self, ch, clouds, origin, out, seq):
         """deform('mergemesh') of one output scan on this chain (DeviceDeform.mergemesh on the chain's stream): projection
         with the target field of view -> the bounds statements on the shared device state, in sequence order -> fusion
         chain on the predicted geometry -> verified against the record"""
-        torch = self._torch
         dd = ch.get("deform")
         if dd is None:
             from .deform import DeviceDeform
@@ -506,23 +453,16 @@ class FusionScanPipeline:
                               merge=a["merge"], mesh_volume=False, rayset=self.rayset, mm_state=self._mm_state,
                               transformation=self.mount)
             ch["deform"] = dd
-        clouds = [(pts, rem, lab) for _, pts, rem, lab, _ in items]
-        with torch.cuda.stream(ch["stream"]):
-            got = dd.mergemesh(clouds, origin, pack=False, out=out, seq=items[0][4])
-            done = torch.cuda.Event()
-            done.record(ch["stream"])
-        res = dict(out)
-        for k in ("n_verts", "n_faces", "vol_dim", "vol_origin", "vol_bnds_after"):
-            res[k] = got[k]
-        if self.mount is not None:
-            res["endpoints_scene"] = got["endpoints_scene"]
-        res["_done"] = (done, [got.get("source"), got.get("_keep")], items)
-        return res
+        got = dd.mergemesh(clouds, origin, pack=False, out=out, seq=seq)
+        more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after")}
+        if self.mount is not None:   # (the chain's DeviceDeform has taken the hits into the target's frame)
+            more["endpoints_scene"] = got["endpoints_scene"]
+        return self._finish(ch, out, out, dd.mesh_obj, [got.get("source"), got.get("_keep")], clouds, **more)
 
     def _run_job(self, ch, job):
-        ticket, obs, origin, out = job
+        ticket = job[0]
         try:
-            res = self._scan(ch, obs, origin, out)
+            res = self._scan(ch, *job[1:])
         except BaseException as e:  # noqa: BLE001  (handed to the waiter)
             res = e
         with self._lock:
@@ -535,7 +475,6 @@ class FusionScanPipeline:
         """Queue one output scan: ``observations`` = the (color_im, depth_im, rem_im) CUDA tensors fused into its volume,
         in order.  Returns the ticket.  ``out``: a dict like ``Scene.alloc_outputs`` returns (missing keys are not written).
         ``inputs_ready``: the caller guarantees that the observation tensors are complete (no wait for its stream)."""
-        import threading
         torch = self._torch
         if not self._chains:
             raise RuntimeError("FusionScanPipeline.submit: the pipeline is closed")
@@ -543,9 +482,9 @@ class FusionScanPipeline:
         for o in obs:
             if len(o) != 3 or not all(isinstance(a, torch.Tensor) and a.is_cuda for a in o):
                 raise ValueError("observations: (color_im, depth_im, rem_im) CUDA tensors")
-        return self._submit(obs, origin, out, inputs_ready)
+        return self._submit("images", obs, origin, out, inputs_ready)
 
-    def _submit(self, obs, origin, out, inputs_ready):
+    def _submit(self, kind, items, origin, out, inputs_ready, seq=None):
         import threading
         torch = self._torch
         if not inputs_ready:
@@ -556,7 +495,7 @@ class FusionScanPipeline:
             self._done[t] = threading.Event()
         if origin is None:   # the target sensor's own position: (0, 0, 0) unless it is mounted elsewhere
             origin = self.origin
-        self._chains[t % len(self._chains)]["q"].put((t, obs, tuple(origin), out))
+        self._chains[t % len(self._chains)]["q"].put((t, kind, items, tuple(origin), out, seq))
         return t
 
     def submit_clouds(self, clouds, origin=None, out=None, inputs_ready=False):
@@ -571,8 +510,9 @@ class FusionScanPipeline:
         for c in clouds:
             if len(c) != 3 or not isinstance(c[0], torch.Tensor) or not c[0].is_cuda:
                 raise ValueError("clouds: (points, remissions, label) CUDA tensors")
-            items.append(("clouds", c[0], c[1], c[2]))
-        return self._submit(items, origin, out, inputs_ready)
+            items.append((c[0], c[1], c[2]))
+        # (no source scan at all: the empty volume of ``submit([])``)
+        return self._submit("clouds" if items else "images", items, origin, out, inputs_ready)
 
     def submit_mergemesh(self, clouds, origin=None, out=None, inputs_ready=False):
         """Queue one output scan of the reference's DEFAULT adaption (config/lidar_transfer.yaml:3; laserscan.py:921-1012): the
@@ -596,11 +536,11 @@ class FusionScanPipeline:
         for c in clouds:
             if len(c) != 3 or not isinstance(c[0], torch.Tensor) or not c[0].is_cuda:
                 raise ValueError("clouds: (points, remissions, label) CUDA tensors")
-            items.append(("mergemesh", c[0], c[1], c[2], self._mm_seq))
+            items.append((c[0], c[1], c[2]))
         if not items:   # (before the sequence number moves: no scan would ever take it, and every later one would wait for it)
             raise ValueError("FusionScanPipeline.submit_mergemesh: no clouds")
-        self._mm_seq += 1
-        return self._submit(items, origin, out, inputs_ready)
+        seq, self._mm_seq = self._mm_seq, self._mm_seq + 1
+        return self._submit("mergemesh", items, origin, out, inputs_ready, seq=seq)
 
     def reset_bounds(self, vol_bnds):
         """A new sequence for :meth:`submit_mergemesh`: every submitted scan is completed, then the bounds state goes back to

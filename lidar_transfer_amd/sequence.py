@@ -211,11 +211,7 @@ class SequenceTransfer:
                     src = ch["ev"].source_scan(*job["raw"], stream=st)
                     job["record"] = ch["ev"].compare(src, out["label"], out["range"], stream=st)
                     job["images"] = (src, out)
-                if self.adaption == "cp":
-                    b, l = dd._pack(out["back_points"], True, out["rem"].view(-1), out["label"].view(-1), out["index"].view(-1),
-                                    dd.n_rays, st)
-                else:
-                    b, l = dd._pack(out["endpoints"], False, out["rem"].reshape(-1), out["label"].reshape(-1), None, dd.n_rays, st)
+                b, l = dd.pack_result(out, st)
                 n = int(b.shape[0])
                 job["n_points"] = n
                 if self._writer is not None:

@@ -640,6 +640,63 @@ def test_mergemesh_composed_from_the_public_steps_equals_the_one_call_scan():
     dd.close()
 
 
+def test_mergemesh_bad_scans_leave_both_ways_of_issuing_the_calls_in_the_same_state():
+    """One protocol serves ``mergemesh()`` (one native call per scan) and ``mergemesh(source_images=True)`` (the public steps):
+    over valid / valid with moved bounds / NO POINT SURVIVES / valid / EMPTY CLIPPED VOLUME / valid, both raise the same
+    exception types at the two bad scans, count the same scans / waited / rerun and leave the same bounds after EVERY scan,
+    and the valid scans are equal bit for bit.  (The target looks up to 89 degrees, as in the error-path test: the cloud
+    lifted by 40 m survives the projection and lies outside the allowed volume.)  The sixth scan's cloud is a valid one, but the
+    reference dies in ``TSDFVolume.__init__`` with the clip of the fifth already in its array (lt_mergemesh.hip keeps it the
+    same way: z min above z max), so on that array every later scan of the sequence meets an empty volume too -- the sixth raises like
+    the fifth, in both ways; a seventh after ``reset_bounds`` shows the object itself is sound."""
+    import torch
+    from lidar_transfer_amd.deform import DeviceDeform
+    seq = _mm_sequence(3)
+    pts, rem, lab = seq[2][0]
+    nothing = [(pts * 0.0, rem, lab)]                                     # every point at depth 0
+    above = [(pts + torch.tensor([0.0, 0.0, 40.0], dtype=pts.dtype, device="cuda"), rem, lab)]
+    scans = [seq[0], seq[2], nothing, seq[2], above, seq[2]]              # (seq[2] is cut back further than seq[0]: the bounds move)
+    bad = {2: ValueError, 4: RuntimeError, 5: RuntimeError}
+    cfg = [[-7, 7], [-7, 7], [-2, 3]]
+    src, tgt = (32, 512, 3.0, -25.0), (32, 512, 89.0, -25.0)
+    runs = []
+    for source_images in (False, True):
+        bnds = np.array(cfg)
+        dd = DeviceDeform(src, tgt, bnds, 0.1, mesh_volume=False)
+        steps = []
+        for k, clouds in enumerate(scans + [seq[2]]):
+            if k == len(scans):
+                dd.reset_bounds(np.array(cfg))
+            step = dict(raised=None)
+            try:
+                got = dd.mergemesh(clouds, source_images=source_images)
+                torch.cuda.synchronize()
+                step.update(range=got["range"].clone(), label=got["label"].clone(), bin=got["bin"].clone(), vol_dim=got["vol_dim"])
+                assert ("source" in got) == source_images and ("_keep" in got) == (not source_images)
+            except (ValueError, RuntimeError) as e:
+                step["raised"] = type(e)
+            step.update(stats=dict(dd._mm_state.stats), bnds=bnds.copy())
+            steps.append(step)
+        dd.close()
+        runs.append(steps)
+    for k, (a, b) in enumerate(zip(*runs)):
+        assert a["raised"] is b["raised"] is bad.get(k), (k, a["raised"], b["raised"])
+        assert a["stats"] == b["stats"], (k, a["stats"], b["stats"])
+        assert np.array_equal(a["bnds"], b["bnds"]) and a["bnds"].dtype == b["bnds"].dtype, (k, a["bnds"], b["bnds"])
+        if k not in bad:
+            assert a["vol_dim"] == b["vol_dim"], k
+            assert torch.equal(a["range"].view(torch.int32), b["range"].view(torch.int32)) and torch.equal(a["label"], b["label"]), k
+            assert torch.equal(a["bin"], b["bin"]) and (a["range"] > 0).sum().item() > 50, k
+    # the protocol as the default way has always run it: the first scan waits, the scan whose bounds moved runs again, a bad
+    # scan counts as a scan and nothing else
+    assert runs[0][1]["stats"] == {"scans": 2, "waited": 1, "rerun": 1}
+    assert runs[0][2]["stats"] == {"scans": 3, "waited": 1, "rerun": 1}
+    assert runs[0][3]["stats"] == {"scans": 4, "waited": 1, "rerun": 1}     # (a bad scan leaves the prediction alone)
+    assert runs[0][5]["stats"] == {"scans": 6, "waited": 1, "rerun": 1} and runs[0][5]["bnds"][2, 0] > runs[0][5]["bnds"][2, 1]
+    assert runs[0][6]["stats"] == {"scans": 7, "waited": 2, "rerun": 1}     # (after the reset there is nothing to assume)
+    assert not np.array_equal(runs[0][0]["bnds"], runs[0][1]["bnds"]) and np.array_equal(runs[0][1]["bnds"], runs[0][2]["bnds"])
+
+
 @pytest.mark.parametrize("pipelined", [False, True])
 def test_mergemesh_sequences_equal_the_references_own_runs(pipelined):
     """Golden F14c (tests/golden/make_golden_mergemesh_seq.py): the reference's `deform('mergemesh')` + `write()` for SIX output
