@@ -65,10 +65,8 @@ __global__ __launch_bounds__(256) void k_tsdf_fill(float4* __restrict__ vol, siz
 // `fresh`: the voxel's column has not been written since the last reset, so the old values are the initial ones
 // (tsdf 1, weight 0, colour 0, remission 0) and need not be loaded
 template <bool MERGE>
-__device__ __forceinline__ int tsdf_update(float* __restrict__ tsdf_vol, float* __restrict__ /*weight_vol*/,
-                                            float* __restrict__ /*color_vol*/, float* __restrict__ /*rem_vol*/, int voxel_idx,
-                                            float dist, float obs_weight, float new_color, float new_rem,
-                                            bool fresh = false) {
+__device__ __forceinline__ int tsdf_update(float* __restrict__ tsdf_vol, int voxel_idx, float dist, float obs_weight,
+                                            float new_color, float new_rem, bool fresh = false) {
   float4* const vox = LT_VOX(tsdf_vol, voxel_idx);
   const float4 o = fresh ? make_float4(1.0f, 0.0f, 0.0f, 0.0f) : *vox;  // (tsdf, weight, colour, remission)
   if (!MERGE) {
@@ -158,11 +156,11 @@ __device__ __forceinline__ float axis_rho_limit(float oz, float voxel_size, int 
   return LT_AXIS_RHO * fmaxf(fabsf(oz), fabsf(__fmaf_rn((float)(dim_z - 1), voxel_size, oz)));
 }
 
-struct col_plain {
-  bool plain;
-  int px;      // colinfo[cx * dim_y + cy]
-  float rho2;  // fma(pt_y, pt_y, pt_x * pt_x): the conservative candidate tests work on it
-  int col;     // cx * dim_y + cy: the exact evaluation takes pt_x, pt_y from it (col_xy)
+struct col_plain {  // (as declared: not plain -- every voxel by the reference's own decomposition of its index)
+  bool plain = false;
+  int px = -2;      // colinfo[cx * dim_y + cy]
+  float rho2 = 0.f;  // fma(pt_y, pt_y, pt_x * pt_x): the conservative candidate tests work on it
+  int col = 0;     // cx * dim_y + cy: the exact evaluation takes pt_x, pt_y from it (col_xy)
 };
 // (pt_x, pt_y) of table column `col` -- the kernel's `vol_origin + voxel * voxel_size` on voxel_x = cx, voxel_y = cy (:101-103)
 __device__ __forceinline__ void col_xy(int col, int dim_y, float voxel_size, float ox, float oy, float& pt_x, float& pt_y) {
@@ -176,7 +174,6 @@ __device__ __forceinline__ void col_xy(int col, int dim_y, float voxel_size, flo
 __device__ __forceinline__ col_plain col_plain_of(int cx, int cy, int z0, int z1, int vol_dim_y, int vol_dim_z, float ox,
                                                   float oy, float voxel_size, const int* __restrict__ colinfo) {
   col_plain C;
-  C.plain = false; C.px = -2; C.rho2 = 0.f; C.col = 0;
   if (z1 <= z0) return C;
   const int cc = cx * vol_dim_y + cy;
   const int i0 = cc * vol_dim_z + z0, i1 = cc * vol_dim_z + z1 - 1;
@@ -193,14 +190,15 @@ __device__ __forceinline__ col_plain col_plain_of(int cx, int cy, int z0, int z1
   return C;
 }
 
-template <bool MERGE>
-__device__ __forceinline__ int tsdf_voxel(
-    int voxel_idx, float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
-    float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
-    float sin_up_hi, float sin_down_lo, const float* __restrict__ color_im, const float* __restrict__ depth_im,
-    const float* __restrict__ rem_im, const int* __restrict__ colinfo, unsigned* __restrict__ col_epoch,
-    unsigned epoch, bool fresh, const col_plain& C, int z_plain, const float2* __restrict__ dct, int want_py = -1) {
+// The geometry half of the reference kernel for one voxel (:95-146): its world point, its image column px (the column's
+// share from the caller for a plain walk, col_plain), depth, pitch and image row py.  false: the voxel leaves -- a dead
+// column, outside the vertical field of view, or not in row want_py (>= 0: the pixel-centric integrate, where a voxel is
+// evaluated by the visitor of ITS OWN pixel only -- the conservative candidate sets of neighbouring rows overlap, and
+// the update is not idempotent).  The image reads and the update are the callers': tsdf_voxel, tsdf_voxel_multi.
+__device__ __forceinline__ bool tsdf_project(int voxel_idx, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy,
+                                             float oz, float voxel_size, int im_h, int im_w, float fov_up, float fov_down,
+                                             float sin_up_hi, float sin_down_lo, const int* __restrict__ colinfo,
+                                             const col_plain& C, int z_plain, int want_py, int& px_out, int& py_out, float& depth_out) {
   int px = -2;
   float pt_x, pt_y, pt_z;
   if (C.plain) {
@@ -219,7 +217,7 @@ __device__ __forceinline__ int tsdf_voxel(
     const bool in_table = ix >= 0 && ix < vol_dim_x && iy >= 0 && iy < vol_dim_y;
     if (in_table) {
       px = colinfo[ix * vol_dim_y + iy];
-      if (px == -1) return 0;
+      if (px == -1) return false;
       if (px >= 0) px &= 0x3FFFFFFF;  // (the wedge table's per-column image column carries a flag bit: LT_WD_QUIRK_FLAG)
     }
     pt_x = __fmaf_rn(voxel_x, voxel_size, ox);
@@ -240,17 +238,31 @@ __device__ __forceinline__ int tsdf_voxel(
   // clearly outside the vertical field of view (NaN passes on -- and so does |s| > 1: on the sensor's axis the device
   // library's norm3df, a 1-ulp square root, can return less than |pt_z|; asinf is then NaN, no comparison of the
   // reference holds and the voxel IS written through pixel row 0 -- LT_AXIS_RHO)
-  if ((s > sin_up_hi || s < sin_down_lo) && fabsf(s) <= 1.0f) return 0;
+  if ((s > sin_up_hi || s < sin_down_lo) && fabsf(s) <= 1.0f) return false;
   const float pitch = asinf(s);
-  if (pitch > fov_up || pitch < fov_down) return 0;
+  if (pitch > fov_up || pitch < fov_down) return false;
   float proj_y = (float)(1.0 - (double)((pitch + fabsf(fov_down)) / fov));
   proj_y *= (float)im_h;
   int py = (int)floorf(proj_y);
   py = min(im_h - 1, py);
   py = max(0, py);
-  // (the pixel-centric integrate, k_tsdf_integrate_pix: a voxel is evaluated by the visitor of ITS OWN pixel only -- the
-  // conservative candidate sets of neighbouring rows overlap, and the update is not idempotent)
-  if (want_py >= 0 && py != want_py) return 0;
+  if (want_py >= 0 && py != want_py) return false;
+  px_out = px; py_out = py; depth_out = depth;
+  return true;
+}
+
+// one observation: tsdf_project, the voxel's pixel, tsdf_update
+template <bool MERGE>
+__device__ __forceinline__ int tsdf_voxel(
+    int voxel_idx, float* __restrict__ tsdf_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
+    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
+    float sin_up_hi, float sin_down_lo, const float* __restrict__ rem_im, const int* __restrict__ colinfo, bool fresh,
+    const col_plain& C, int z_plain, const float2* __restrict__ dct, int want_py = -1) {
+  int px, py;
+  float depth;
+  if (!tsdf_project(voxel_idx, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, fov_up, fov_down,
+                    sin_up_hi, sin_down_lo, colinfo, C, z_plain, want_py, px, py, depth))
+    return 0;
   const float2 dc = dct[px * im_h + py];  // (depth_im, color_im)[py * im_w + px], transposed copy (lt_tsdf::dct)
   const float new_rem = rem_im[py * im_w + px];  // (issued with it: one round trip, not two)
   const float depth_value = dc.x;
@@ -258,7 +270,7 @@ __device__ __forceinline__ int tsdf_voxel(
   const float depth_diff = depth_value - depth;
   if (depth_diff < -trunc_margin) return 0;
   const float dist = fminf(1.0f, depth_diff / trunc_margin);
-  return tsdf_update<MERGE>(tsdf_vol, weight_vol, color_vol, rem_vol, voxel_idx, dist, obs_weight, dc.y, new_rem, fresh);
+  return tsdf_update<MERGE>(tsdf_vol, voxel_idx, dist, obs_weight, dc.y, new_rem, fresh);
 }
 
 // Can voxel z of a FRESH plain column be written by the class-aware update?  On a fresh volume (the reference builds one
@@ -326,6 +338,39 @@ __device__ __forceinline__ void col_zrange(const col_geom& G, int cx, int cy, in
 __device__ __forceinline__ int nth_set_bit(unsigned long long m, int n) {
   for (int k = 0; k < n; ++k) m &= m - 1;
   return m ? __ffsll((long long)m) - 1 : -1;
+}
+
+// inclusive prefix sum of v over the 64 lanes of the wave
+__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// The signs of the values a wave has just written (code: tsdf_update's) -> the columns' sign words.  The voxels of one column
+// sit in neighbouring lanes and (mostly) in one 64-bit word: the bits are ORed together over each run of lanes holding one
+// word, and the first lane of the run issues the atomic.  CLEAR = false: the volume is fresh, every bit is 0 -- only code 2
+// needs a write; true: code 1 clears its bit as well.  Every lane of the wave must call it (shuffles).
+template <bool CLEAR>
+__device__ __forceinline__ void sign_run_merge(unsigned long long* __restrict__ sign_bits, int code, int col, int z,
+                                               int words_z, int lane) {
+  const bool act = CLEAR ? code != 0 : code == 2;
+  const int wkey = act ? col * words_z + (z >> 6) : -1 - lane;  // (unique when there is nothing to write)
+  unsigned long long set = code == 2 ? 1ull << (z & 63) : 0ull, clr = CLEAR && code == 1 ? 1ull << (z & 63) : 0ull;
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) {  // runs of up to 16 lanes (a run is one column's interval: ~10 voxels)
+    const unsigned long long os = __shfl_down(set, o, 64), oc = CLEAR ? __shfl_down(clr, o, 64) : 0ull;
+    const int ok = __shfl_down(wkey, o, 64);
+    if (lane + o < 64 && ok == wkey) { set |= os; clr |= oc; }
+  }
+  const int prev = __shfl_up(wkey, 1, 64);
+  if (act && (lane == 0 || prev != wkey || (lane & 15) == 0)) {  // (lane & 15: a run longer than 16 lanes)
+    if (!CLEAR || set) atomicOr(sign_bits + (size_t)wkey, set);
+    if (CLEAR && clr) atomicAnd(sign_bits + (size_t)wkey, ~clr);
+  }
 }
 
 // per voxel column (x, y): its image column px -- the kernel's own expressions on voxel_x = x, voxel_y = y -- or -1
@@ -413,12 +458,10 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
     if (lane < n) {
       const int e = qn - n + lane;
       const int col = q_col[wv][e], z = q_z[wv][e];
-      col_plain Cq;
-      Cq.plain = true; Cq.px = q_px[wv][e]; Cq.rho2 = q_rho2[wv][e]; Cq.col = col;
-      const int code = tsdf_voxel<MERGE>(col * vol_dim_z + z, tsdf_vol, weight_vol, color_vol, rem_vol, vol_dim_x,
-                                         vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, trunc_margin, obs_weight,
-                                         fov_up, fov_down, sin_up_hi, sin_down_lo, color_im, depth_im, rem_im, colinfo,
-                                         col_epoch, epoch, true, Cq, z, dct);
+      const col_plain Cq = {true, q_px[wv][e], q_rho2[wv][e], col};
+      const int code = tsdf_voxel<MERGE>(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz,
+                                         voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
+                                         sin_down_lo, rem_im, colinfo, true, Cq, z, dct);
       if (code) {  // the sign of the value written -> the column's sign bit (other lanes may hold voxels of the same word)
         unsigned long long* w = sign_bits + (size_t)col * words_z + (z >> 6);
         const unsigned long long bit = 1ull << (z & 63);
@@ -450,7 +493,6 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
       if ((quad & 3) != wv) continue;  // (another wave of the workgroup)
       int z0 = 0, z1 = 0, cc = 0;
       col_plain C;
-      C.plain = false; C.px = -2; C.rho2 = 0.f; C.col = 0;
       const bool fresh = bit >= 0 && !((wm >> bit) & 1ull);
       if (bit >= 0) {
         cc = chunk * 64 + bit;
@@ -496,10 +538,9 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
           if (any_direct) {
             int code = 0;
             if (!band && z >= z0 && z < z1)
-              code = tsdf_voxel<MERGE>(cc * vol_dim_z + z, tsdf_vol, weight_vol, color_vol, rem_vol, vol_dim_x, vol_dim_y,
-                                       vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up,
-                                       fov_down, sin_up_hi, sin_down_lo, color_im, depth_im, rem_im, colinfo, col_epoch,
-                                       epoch, fresh, C, z, dct);
+              code = tsdf_voxel<MERGE>(cc * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz,
+                                       voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
+                                       sin_down_lo, rem_im, colinfo, fresh, C, z, dct);
             const unsigned long long wrote_w = __ballot(code != 0), neg_w = __ballot(code == 2);
             wrote = (wrote_w >> (16 * grp)) & 0xFFFFull;
             neg = (neg_w >> (16 * grp)) & 0xFFFFull;
@@ -697,6 +738,89 @@ __device__ __forceinline__ void col_mark_written(unsigned* __restrict__ col_zw, 
   chunk_epoch[c >> 6] = epoch;
 }
 
+// ---- several observations of a FRESH volume in ONE pass (lt_tsdf_integrate_multi_dev) --------------------------------------
+// The reference's `mesh` adaption fuses `number_of_scans` range images into one new volume, all of them re-projected into
+// the primary pose (laserscan.py:874-897): every observation projects a voxel into the SAME pixel, and the update of a voxel
+// depends on that voxel's own state and its pixel only.  So instead of n passes -- the second one onwards with a snapshot of
+// the written ranges, a pass over every voxel inside them and the pixel pass beside it (0.11 ms each) -- ONE pixel pass over
+// the union of the observations' candidate intervals: a voxel's geometry (depth, pitch, row: the costly part) is evaluated
+// once, then the n updates run IN ORDER on the voxel's state in registers (the expressions of tsdf_update, operation by
+// operation) and the four fields are stored once.  Bit-identical to n calls of lt_tsdf_integrate_dev
+// (tests/test_tsdf_gpu.py).  Class-aware branch only (the plain average writes the whole frustum: the column walk).
+#define LT_TSDF_MULTI_MAX 8
+struct tsdf_obs_ptrs {  // the images of the observations, by value (kernel arguments)
+  const float* color[LT_TSDF_MULTI_MAX];
+  const float* depth[LT_TSDF_MULTI_MAX];
+  const float* rem[LT_TSDF_MULTI_MAX];
+};
+
+// (depth, colour, remission, -) of pixel (row, px) of observation k at obs4[(k * im_w + px) * im_h + row]: the transposed,
+// packed copy the kernels read (one 16-B load per observation and voxel; rows of one image column contiguous)
+__global__ __launch_bounds__(256) void k_tsdf_dct4(tsdf_obs_ptrs O, int n_obs, int im_h, int im_w, float4* __restrict__ obs4) {
+  const int n_pix = im_h * im_w;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pix * n_obs) return;
+  const int k = i / n_pix, p = i - k * n_pix;
+  const int y = p / im_w, x = p - y * im_w;
+  float d = 0.f, c = 0.f, r = 0.f;
+#pragma unroll
+  for (int q = 0; q < LT_TSDF_MULTI_MAX; ++q)  // (the pointer table lives in scalar registers: select, do not index)
+    if (q == k) { d = O.depth[q][p]; c = O.color[q][p]; r = O.rem[q][p]; }
+  obs4[(size_t)k * n_pix + (size_t)x * im_h + y] = make_float4(d, c, r, 0.f);
+}
+
+// the n class-aware updates of one voxel of a FRESH volume (fusion_lidar.py:177, :191-228; tsdf_update<true> above, on
+// registers): returns 0 untouched, 1 written (> 0), 2 written not > 0 (the sign bit, as tsdf_update)
+__device__ __forceinline__ int tsdf_updates_fresh(float* __restrict__ tsdf_vol, int voxel_idx, float depth, float trunc_margin,
+                                                   float obs_weight, const float4* __restrict__ obs4, size_t pix, size_t n_pix,
+                                                   int n_obs) {
+  float tv = 1.0f, wv = 0.0f, cv = 0.0f, rv = 0.0f;  // the initial volume (fusion_lidar.py:47-63)
+  bool written = false;
+  for (int k = 0; k < n_obs; ++k) {
+    const float4 o = obs4[(size_t)k * n_pix + pix];
+    const float depth_value = o.x, new_color = o.y, new_rem = o.z;
+    if (depth_value == 0.f) continue;
+    const float depth_diff = depth_value - depth;
+    if (depth_diff < -trunc_margin) continue;
+    const float dist = fminf(1.0f, depth_diff / trunc_margin);
+    const float dist_old = wv;  // sic: the reference compares against the weight volume
+    if (cv == new_color) {      // same class: integrate
+      const float w_old = wv;
+      const float w_new = w_old + obs_weight;
+      wv = w_new;
+      tv = __fmaf_rn(tv, w_old, dist) / w_new;
+      rv = __fmaf_rn(rv, w_old, new_rem) / w_new;
+      written = true;
+    } else if (dist < dist_old) {  // other class: the closer observation wins
+      tv = dist;
+      const float new_b = floorf(new_color / (256 * 256));
+      const float new_g = floorf((new_color - new_b * 256 * 256) / 256);
+      const float new_r = new_color - new_b * 256 * 256 - new_g * 256;
+      cv = new_b * 256 * 256 + new_g * 256 + new_r;
+      rv = new_rem;
+      written = true;
+    }
+  }
+  if (!written) return 0;
+  *LT_VOX(tsdf_vol, voxel_idx) = make_float4(tv, wv, cv, rv);
+  return !(tv > 0.0f) ? 2 : 1;
+}
+
+// n observations of a fresh volume: tsdf_project, then the n updates; want_py as in tsdf_voxel
+__device__ __forceinline__ int tsdf_voxel_multi(
+    int voxel_idx, float* __restrict__ tsdf_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
+    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
+    float sin_up_hi, float sin_down_lo, const int* __restrict__ colinfo, const col_plain& C, int z_plain,
+    const float4* __restrict__ obs4, int n_obs, int want_py = -1) {
+  int px, py;
+  float depth;
+  if (!tsdf_project(voxel_idx, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, fov_up, fov_down,
+                    sin_up_hi, sin_down_lo, colinfo, C, z_plain, want_py, px, py, depth))
+    return 0;
+  return tsdf_updates_fresh(tsdf_vol, voxel_idx, depth, trunc_margin, obs_weight, obs4, (size_t)px * im_h + py,
+                            (size_t)im_h * im_w, n_obs);
+}
+
 // One workgroup = 64 consecutive pixels of the transposed image (rows of one image column: they walk the same wedge), its
 // four waves share the work, which is flattened twice so that no lane waits for a far pixel's long lists:
 //   A  wave 0, lane = pixel: the two binary searches -> the pixel's run of table entries [k0, k0 + n); prefix sum of n
@@ -717,20 +841,23 @@ __device__ __forceinline__ void col_mark_written(unsigned* __restrict__ col_zw, 
 #ifndef LT_PIX_WPE
 #define LT_PIX_WPE 5
 #endif
-template <bool MERGE, bool VCOUNT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE, 8))) void k_tsdf_integrate_pix(
-    float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
-    float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, float inv_vs, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up,
-    float fov_down, float sin_up_hi, float sin_down_lo, const float* __restrict__ color_im,
-    const float* __restrict__ depth_im, const float* __restrict__ rem_im, const int* __restrict__ wd_px,
-    unsigned* __restrict__ col_epoch, unsigned epoch, unsigned long long* __restrict__ sign_bits, int words_z,
-    unsigned* __restrict__ col_zw, unsigned* __restrict__ chunk_epoch, const float2* __restrict__ dct,
-    const float4* __restrict__ rowtab, const int* __restrict__ wd_start, const int2* __restrict__ wd_ent, const uint32_t* __restrict__ wd_key, int rho_bits,
+// ONE body for both entry points: k_tsdf_integrate_pix (one observation; MULTI = false) and k_tsdf_integrate_pix_multi (up
+// to LT_TSDF_MULTI_MAX observations of a fresh volume at once; MULTI = true).  They differ at four places, each an
+// `if constexpr`: where a pixel's depth interval comes from (phase A), the zw_snap clipping, the voxel evaluation -- and the
+// launch attribute on the kernels themselves.  What a kernel does not have it passes as nullptr / 1.
+// zw_snap (single only; NULL on a fresh volume): the columns' written z ranges as they were BEFORE this observation.  The
+// voxels inside them may hold anything -- k_tsdf_integrate_written has evaluated every one of them -- and are skipped here;
+// everything else still holds the initial values, so the superset argument (and `fresh` = true) stands.
+template <bool MULTI, bool VCOUNT>
+__device__ __forceinline__ void pix_body(
+    float* __restrict__ tsdf_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz, float voxel_size,
+    float inv_vs, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down, float sin_up_hi,
+    float sin_down_lo, const float* __restrict__ rem_im, const float4* __restrict__ obs4, int n_obs,
+    const int* __restrict__ wd_px, unsigned* __restrict__ col_epoch, unsigned epoch,
+    unsigned long long* __restrict__ sign_bits, int words_z, unsigned* __restrict__ col_zw,
+    unsigned* __restrict__ chunk_epoch, const float2* __restrict__ dct, const float4* __restrict__ rowtab,
+    const int* __restrict__ wd_start, const int2* __restrict__ wd_ent, const uint32_t* __restrict__ wd_key, int rho_bits,
     float qscale, const unsigned* __restrict__ zw_snap, unsigned long long* __restrict__ dbg) {
-  // zw_snap (NULL on a fresh volume): the columns' written z ranges as they were BEFORE this observation.  The voxels inside
-  // them may hold anything -- k_tsdf_integrate_written has evaluated every one of them -- and are skipped here; everything
-  // else still holds the initial values, so this kernel's superset argument (and `fresh` = true) stands.
   const int n_cols_all = vol_dim_x * vol_dim_y;
   // per pixel of the workgroup
   __shared__ int p_k0[64], p_pre[65], p_r[64], p_px[64];
@@ -757,36 +884,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
   // first table index in [a, b) whose rho quantum is >= q (b if none): the wedges are sorted by it.  The 64 pixels of a
   // workgroup search the SAME wedge(s): 22 dependent global loads per pixel became one coalesced copy into LDS
   bool staged = false;  // (workgroup-uniform: the whole search range is in LDS)
-  auto lower = [&](int a, int b, uint32_t q) {
-    if (staged) {
-      while (a < b) {
-        const int m = (a + b) >> 1;
-        if (skey[m - stage0] < q) a = m + 1;
-        else b = m;
-      }
-    } else {
-      while (a < b) {
-        const int m = (a + b) >> 1;
-        if (wd_key[m] < q) a = m + 1;
-        else b = m;
-      }
+  auto lower_in = [](const uint32_t* key, int off, int a, int b, uint32_t q) {
+    while (a < b) {
+      const int m = (a + b) >> 1;
+      if (key[m - off] < q) a = m + 1;
+      else b = m;
     }
     return a;
   };
+  auto lower = [&](int a, int b, uint32_t q) { return staged ? lower_in(skey, stage0, a, b, q) : lower_in(wd_key, 0, a, b, q); };
   // (An item's chunks dealt to several workgroups, each repeating phase A, were measured: 2 parts 88 us, 4 parts 129 against
   // 65 -- an item is 6 us of phase A, 3 of its first chunk's pairs and 9 of voxel rounds: tools/tsdf_written_times.py --pix.)
   for (int p0 = blockIdx.x * 64; p0 < n_pix; p0 += gridDim.x * 64) {  // (workgroup-uniform)
     const unsigned long long tm0 = VCOUNT ? (unsigned long long)wall_clock64() : 0ull;  // (100 MHz; debug)
     LT_PIX_MARK(0);
     // ---- A: the pixels' runs of table entries ------------------------------------------------------------------------
-    // (wave 0's own loads -- its pixel, its row's table entry, its wedge's extent -- are issued BEFORE the staging and its
-    // barrier: one dependent round trip less per item)
-    const int pA = p0 + lane;
-    const bool inA = wave == 0 && pA < n_pix;
-    const int pxA = inA ? pA / im_h : 0, rA = inA ? pA - pxA * im_h : 0;
-    const float2 dcA = inA ? dct[pA] : make_float2(0.f, 1.f);
-    const float4 rowA = rowtab[rA];
-    const int s0A = wd_start[pxA], s1A = wd_start[pxA + 1];
+    // a lane's pixel (row r, column px) at [px * im_h + r] of the transposed images, its row's table entry (tan_lo, tan_hi,
+    // cos_min, cos_max; tan_lo > tan_hi: no voxel can take this row) and its wedge's extent [s0, s1)
+    const int p = p0 + lane;
+    bool in = false;
+    int px = 0, r = 0, s0 = 0, s1 = 0;
+    float4 row;
+    auto locate = [&](bool in_) {
+      in = in_; px = in ? p / im_h : 0; r = in ? p - px * im_h : 0;
+      row = rowtab[r]; s0 = wd_start[px]; s1 = wd_start[px + 1];
+    };
+    [[maybe_unused]] float2 dcA;
+    if constexpr (!MULTI) {
+      // wave 0's own loads are issued BEFORE the staging and its barrier: one dependent round trip less per item.  (Not in
+      // the fused kernel: the registers they hold across the barrier take it from 5 to 4 waves per SIMD.)
+      locate(wave == 0 && p < n_pix);
+      dcA = in ? dct[p] : make_float2(0.f, 1.f);
+    }
     {  // stage the quanta of the wedges these 64 pixels search (one image column when im_h is a multiple of 64)
       const int px_a = p0 / im_h, px_b = min(p0 + 63, n_pix - 1) / im_h;
       stage0 = wd_start[px_a];
@@ -808,27 +937,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
       }
       __syncthreads();
     }
-    if (wave != 0) {
+    if (wave != 0)
       for (int i = tid - 64; i < LT_PIX_AGG; i += 192) { a_lo[i] = 0u; a_hi[i] = 0u; }
-    }
     if (wave == 0) {
-      const bool in = inA;  // pixel (row r, column px) at dct[px * im_h + r]
-      const int px = pxA, r = rA;
-      const float2 dc = dcA;
-      const float D = dc.x;
-      const float4 row = rowA;  // (tan_lo, tan_hi, cos_min, cos_max); tan_lo > tan_hi: no voxel can take this row
+      if constexpr (MULTI) locate(p < n_pix);
       const bool row_ok = row.x <= row.y;
-      const bool finite = D == D && fabsf(D) < 1e30f;
-      // the reference leaves at depth_value == 0; with another colour than 0 only the band is written (and nothing at all
-      // through a NaN / infinite depth: dist = 1); colour 0: everything in front of D + trunc (all of it for NaN / inf)
-      const bool zero_class = in && row_ok && D != 0.f && dc.y == 0.0f;
-      const bool normal = in && row_ok && D != 0.f && dc.y != 0.0f && finite;
-      const float eps = __fmaf_rn(4e-6f, fabsf(D) + trunc_margin, 1e-6f);
-      const float d_hi = finite ? D + trunc_margin + eps : 3e38f;
-      const float d_lo = zero_class ? 0.f : D - eps;
-      const int s0 = s0A, s1 = s1A;
+      // the pixel's depth interval [d_lo, d_hi]: the reference leaves at depth_value == 0; with another colour than 0 only
+      // the band is written (and nothing at all through a NaN / infinite depth: dist = 1); colour 0: everything in front of
+      // D + trunc (all of it for NaN / inf).  Several observations: the UNION of their intervals -- a voxel an observation
+      // can write lies in that observation's interval while it still holds its initial values, and once written (by an
+      // earlier observation: inside an earlier interval) anywhere in front of ITS band: a band further out extends the
+      // union's upper end, and the voxels in front of it that earlier observations wrote are inside the union already
+      bool any = false;
+      float d_lo = 3e38f, d_hi = 0.f;
+      if constexpr (MULTI) {
+        for (int kk = 0; kk < n_obs; ++kk) {
+          const float4 o4 = in ? obs4[(size_t)kk * ((size_t)im_h * im_w) + p] : make_float4(0.f, 1.f, 0.f, 0.f);
+          const float D = o4.x;
+          const bool finite = D == D && fabsf(D) < 1e30f;
+          const bool zero_class_k = in && row_ok && D != 0.f && o4.y == 0.0f;
+          const bool normal_k = in && row_ok && D != 0.f && o4.y != 0.0f && finite;
+          if (normal_k || zero_class_k) {
+            const float eps = __fmaf_rn(4e-6f, fabsf(D) + trunc_margin, 1e-6f);
+            const float hi_k = finite ? D + trunc_margin + eps : 3e38f;
+            const float lo_k = zero_class_k ? 0.f : D - eps;
+            if (hi_k > 0.f) { any = true; d_lo = fminf(d_lo, lo_k); d_hi = fmaxf(d_hi, hi_k); }
+          }
+        }
+      } else {
+        const float D = dcA.x;
+        const bool finite = D == D && fabsf(D) < 1e30f;
+        const bool zero_class = in && row_ok && D != 0.f && dcA.y == 0.0f;
+        const bool normal = in && row_ok && D != 0.f && dcA.y != 0.0f && finite;
+        const float eps = __fmaf_rn(4e-6f, fabsf(D) + trunc_margin, 1e-6f);
+        d_hi = finite ? D + trunc_margin + eps : 3e38f;
+        d_lo = zero_class ? 0.f : D - eps;
+        any = (normal || zero_class) && d_hi > 0.f;
+      }
       int k = 0, kend = 0;
-      if ((normal || zero_class) && d_hi > 0.f) {
+      if (any) {
         const float rho1 = fmaxf(d_lo, 0.f) * row.z * 0.999999f;
         const float f1 = floorf(rho1 * qscale) - 2.f;
         const uint32_t q1 = (uint32_t)fminf(fmaxf(f1, 0.f), (float)qmax);
@@ -841,12 +988,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
         }
       }
       const int cnt = kend - k;
-      int inc = cnt;  // inclusive wave scan
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
+      const int inc = wave_scan_incl(cnt, lane);
       p_k0[lane] = k; p_pre[lane] = inc - cnt; p_r[lane] = r; p_px[lane] = px;
       p_tlo[lane] = row.x; p_thi[lane] = row.y; p_dlo[lane] = d_lo; p_dhi[lane] = d_hi;
       if (lane == 63) p_pre[64] = inc;
@@ -902,15 +1044,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
             }
           }
           int partial = 0;
-          if (zw_snap && zend >= z) {  // the part of the interval the column pass has done already
-            const int olo = LT_ZW_LO(zw_snap[e.x]), ohi = LT_ZW_HI(zw_snap[n_cols_all + e.x]);
-            if (ohi >= olo) {
-              if (z >= olo && zend <= ohi) zend = z - 1;      // all of it (the usual case of a repeated observation)
-              else if (z >= olo && z <= ohi) z = ohi + 1;     // its lower end
-              else if (zend >= olo && zend <= ohi) zend = olo - 1;  // its upper end
-              else if (z < olo && zend > ohi) partial = 0x40000000;  // a hole in the middle: decided per voxel
+          if constexpr (!MULTI)
+            if (zw_snap && zend >= z) {  // the part of the interval the column pass has done already
+              const int olo = LT_ZW_LO(zw_snap[e.x]), ohi = LT_ZW_HI(zw_snap[n_cols_all + e.x]);
+              if (ohi >= olo) {
+                if (z >= olo && zend <= ohi) zend = z - 1;      // all of it (the usual case of a repeated observation)
+                else if (z >= olo && z <= ohi) z = ohi + 1;     // its lower end
+                else if (zend >= olo && zend <= ohi) zend = olo - 1;  // its upper end
+                else if (z < olo && zend > ohi) partial = 0x40000000;  // a hole in the middle: decided per voxel
+              }
             }
-          }
           len[u] = max(zend - z + 1, 0);
           c_col[slot] = e.x; c_rho2[slot] = __int_as_float(e.y); c_z0[slot] = z; c_src[slot] = sidx | partial;
           // the column's written range and stamp once per PAIR, for the whole candidate interval (a superset is safe, as in
@@ -921,7 +1064,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
               atomicMax(&a_lo[kk - agg_k0], (unsigned)(0x7FFF - z));
               atomicMax(&a_hi[kk - agg_k0], (unsigned)(zend + 1));
             } else {
-              col_mark_written(col_zw, col_epoch, chunk_epoch, epoch, vol_dim_x * vol_dim_y, e.x, z, zend);
+              col_mark_written(col_zw, col_epoch, chunk_epoch, epoch, n_cols_all, e.x, z, zend);
             }
           }
 #endif
@@ -931,12 +1074,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
       int run = 0;  // voxels of the passes before
 #pragma unroll
       for (int u = 0; u < PPT; ++u) {
-        int inc = len[u];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const int t = __shfl_up(inc, o, 64);
-          if (lane >= o) inc += t;
-        }
+        const int inc = wave_scan_incl(len[u], lane);
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
         int woff = 0;
@@ -953,45 +1091,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
       if (VCOUNT && tid == 0 && base == 0) atomicAdd(&dbg[5], tm1 - tm0);  // ... + first chunk's pairs and scan
       if (base == 0) LT_PIX_MARK(2);
       // the chunk's voxels, one per thread and round
-      for (int jb = 0; jb < V; jb += 256) {  // (workgroup-uniform trips: the run aggregation below shuffles)
+      for (int jb = 0; jb < V; jb += 256) {  // (workgroup-uniform trips: sign_run_merge shuffles)
         const int j = jb + tid;
         int code = 0, col = 0, z = 0;
         if (j < V) {
-        int sl = 0;  // largest slot < n_slots with c_pre[slot] <= j
+          int sl = 0;  // largest slot < n_slots with c_pre[slot] <= j
 #pragma unroll
-        for (int st = LT_PIX_CHUNK / 2; st >= 1; st >>= 1)
-          if (sl + st < n_slots && c_pre[sl + st] <= j) sl += st;
-        const int sflag = c_src[sl], sidx = sflag & 63;
-        col = c_col[sl]; z = c_z0[sl] + (j - c_pre[sl]);
-        bool mine = true;
-        if (sflag & 0x40000000) mine = z < LT_ZW_LO(zw_snap[col]) || z > LT_ZW_HI(zw_snap[n_cols_all + col]);
-        col_plain Cq;
-        Cq.plain = true; Cq.px = p_px[sidx]; Cq.rho2 = c_rho2[sl]; Cq.col = col;
+          for (int st = LT_PIX_CHUNK / 2; st >= 1; st >>= 1)
+            if (sl + st < n_slots && c_pre[sl + st] <= j) sl += st;
+          const int sflag = c_src[sl], sidx = sflag & 63;
+          col = c_col[sl]; z = c_z0[sl] + (j - c_pre[sl]);
+          bool mine = true;
+          if constexpr (!MULTI)
+            if (sflag & 0x40000000) mine = z < LT_ZW_LO(zw_snap[col]) || z > LT_ZW_HI(zw_snap[n_cols_all + col]);
+          const col_plain Cq = {true, p_px[sidx], c_rho2[sl], col};
 #ifdef LT_PIX_NO_EVAL  // timing experiment: everything but the evaluation (nothing is written)
-        mine = false;
+          mine = false;
 #endif
-        if (mine)
-        code = tsdf_voxel<MERGE>(col * vol_dim_z + z, tsdf_vol, weight_vol, color_vol, rem_vol, vol_dim_x,
-                                           vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, trunc_margin,
-                                           obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, color_im, depth_im,
-                                           rem_im, wd_px, col_epoch, epoch, true, Cq, z, dct, p_r[sidx]);
+          if (mine) {
+            if constexpr (MULTI)
+              code = tsdf_voxel_multi(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz,
+                                      voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
+                                      sin_down_lo, wd_px, Cq, z, obs4, n_obs, p_r[sidx]);
+            else
+              code = tsdf_voxel<true>(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz,
+                                      voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
+                                      sin_down_lo, rem_im, wd_px, true, Cq, z, dct, p_r[sidx]);
+          }
         }
-        // sign bits: the volume is fresh, every bit is 0 -- only negative values need a write; the voxels of a pair sit in
-        // neighbouring lanes and (mostly) in one 64-bit word: OR them together over the run, one atomic per run
 #ifdef LT_PIX_NO_BITS  // timing experiment: no sign bits (marching cubes would see nothing)
         code = 0;
 #endif
-        const int wkey = code == 2 ? col * words_z + (z >> 6) : -1 - lane;  // (unique when there is nothing to write)
-        unsigned long long bits = code == 2 ? 1ull << (z & 63) : 0ull;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {  // runs of up to 16 lanes (a run is one column's interval: ~10 voxels)
-          const unsigned long long ob = __shfl_down(bits, o, 64);
-          const int ok = __shfl_down(wkey, o, 64);
-          if (lane + o < 64 && ok == wkey) bits |= ob;
-        }
-        const int prev = __shfl_up(wkey, 1, 64);
-        if (code == 2 && (lane == 0 || prev != wkey || (lane & 15) == 0))  // (lane & 15: a run longer than 16 lanes)
-          atomicOr(sign_bits + (size_t)wkey, bits);
+        sign_run_merge<false>(sign_bits, code, col, z, words_z, lane);
         if (VCOUNT) {  // (one atomic per wave and round: a per-voxel atomic on one address would be the whole kernel)
           const unsigned long long wr = __ballot(code != 0);
           if (lane == 0 && wr) atomicAdd(&dbg[2], (unsigned long long)__popcll(wr));
@@ -1011,9 +1142,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
         const unsigned hi1 = a_hi[i];
         if (hi1) {
           const int c = wd_ent[agg_k0 + i].x;
-          const int n_cols = vol_dim_x * vol_dim_y;
           atomicMax(&col_zw[c], a_lo[i]);  // (atomic: with an image height that does not divide 64 two workgroups share a wedge)
-          atomicMax(&col_zw[n_cols + c], hi1);
+          atomicMax(&col_zw[n_cols_all + c], hi1);
           col_epoch[c] = epoch;
           chunk_epoch[c >> 6] = epoch;
         }
@@ -1023,125 +1153,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE,
   }
 }
 
-// ---- several observations of a FRESH volume in ONE pass (lt_tsdf_integrate_multi_dev) --------------------------------------
-// The reference's `mesh` adaption fuses `number_of_scans` range images into one new volume, all of them re-projected into
-// the primary pose (laserscan.py:874-897): every observation projects a voxel into the SAME pixel, and the update of a voxel
-// depends on that voxel's own state and its pixel only.  So instead of n passes -- the second one onwards with a snapshot of
-// the written ranges, a pass over every voxel inside them and the pixel pass beside it (0.11 ms each) -- ONE pixel pass over
-// the union of the observations' candidate intervals: a voxel's geometry (depth, pitch, row: the costly part) is evaluated
-// once, then the n updates run IN ORDER on the voxel's state in registers (the expressions of tsdf_update, operation by
-// operation) and the four fields are stored once.  Bit-identical to n calls of lt_tsdf_integrate_dev
-// (tests/test_tsdf_gpu.py).  Class-aware branch only (the plain average writes the whole frustum: the column walk).
-#define LT_TSDF_MULTI_MAX 8
-struct tsdf_obs_ptrs {  // the images of the observations, by value (kernel arguments)
-  const float* color[LT_TSDF_MULTI_MAX];
-  const float* depth[LT_TSDF_MULTI_MAX];
-  const float* rem[LT_TSDF_MULTI_MAX];
-};
-
-// (depth, colour, remission, -) of pixel (row, px) of observation k at obs4[(k * im_w + px) * im_h + row]: the transposed,
-// packed copy the kernels read (one 16-B load per observation and voxel; rows of one image column contiguous)
-__global__ __launch_bounds__(256) void k_tsdf_dct4(tsdf_obs_ptrs O, int n_obs, int im_h, int im_w, float4* __restrict__ obs4) {
-  const int n_pix = im_h * im_w;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pix * n_obs) return;
-  const int k = i / n_pix, p = i - k * n_pix;
-  const int y = p / im_w, x = p - y * im_w;
-  float d = 0.f, c = 0.f, r = 0.f;
-#pragma unroll
-  for (int q = 0; q < LT_TSDF_MULTI_MAX; ++q)  // (the pointer table lives in scalar registers: select, do not index)
-    if (q == k) { d = O.depth[q][p]; c = O.color[q][p]; r = O.rem[q][p]; }
-  obs4[(size_t)k * n_pix + (size_t)x * im_h + y] = make_float4(d, c, r, 0.f);
-}
-
-// the n class-aware updates of one voxel of a FRESH volume (fusion_lidar.py:177, :191-228; tsdf_update<true> above, on
-// registers): returns 0 untouched, 1 written (> 0), 2 written not > 0 (the sign bit, as tsdf_update)
-__device__ __forceinline__ int tsdf_updates_fresh(float* __restrict__ tsdf_vol, float* __restrict__ weight_vol,
-                                                   float* __restrict__ color_vol, float* __restrict__ rem_vol, int voxel_idx,
-                                                   float depth, float trunc_margin, float obs_weight,
-                                                   const float4* __restrict__ obs4, size_t pix, size_t n_pix, int n_obs) {
-  float tv = 1.0f, wv = 0.0f, cv = 0.0f, rv = 0.0f;  // the initial volume (fusion_lidar.py:47-63)
-  bool written = false;
-  for (int k = 0; k < n_obs; ++k) {
-    const float4 o = obs4[(size_t)k * n_pix + pix];
-    const float depth_value = o.x, new_color = o.y, new_rem = o.z;
-    if (depth_value == 0.f) continue;
-    const float depth_diff = depth_value - depth;
-    if (depth_diff < -trunc_margin) continue;
-    const float dist = fminf(1.0f, depth_diff / trunc_margin);
-    const float dist_old = wv;  // sic: the reference compares against the weight volume
-    if (cv == new_color) {      // same class: integrate
-      const float w_old = wv;
-      const float w_new = w_old + obs_weight;
-      wv = w_new;
-      tv = __fmaf_rn(tv, w_old, dist) / w_new;
-      rv = __fmaf_rn(rv, w_old, new_rem) / w_new;
-      written = true;
-    } else if (dist < dist_old) {  // other class: the closer observation wins
-      tv = dist;
-      const float new_b = floorf(new_color / (256 * 256));
-      const float new_g = floorf((new_color - new_b * 256 * 256) / 256);
-      const float new_r = new_color - new_b * 256 * 256 - new_g * 256;
-      cv = new_b * 256 * 256 + new_g * 256 + new_r;
-      rv = new_rem;
-      written = true;
-    }
-  }
-  if (!written) return 0;
-  *LT_VOX(tsdf_vol, voxel_idx) = make_float4(tv, wv, cv, rv);
-  return !(tv > 0.0f) ? 2 : 1;
-}
-
-// tsdf_voxel's geometry (the reference's expressions, :95-146), then the n updates; want_py as there
-__device__ __forceinline__ int tsdf_voxel_multi(
-    int voxel_idx, float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
+template <bool MERGE, bool VCOUNT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE, 8))) void k_tsdf_integrate_pix(
+    float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
     float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
-    float sin_up_hi, float sin_down_lo, const int* __restrict__ colinfo, const col_plain& C, int z_plain,
-    const float4* __restrict__ obs4, int n_obs, int want_py = -1) {
-  int px = -2;
-  float pt_x, pt_y, pt_z;
-  if (C.plain) {
-    px = C.px;
-    col_xy(C.col, vol_dim_y, voxel_size, ox, oy, pt_x, pt_y);
-    pt_z = __fmaf_rn((float)z_plain, voxel_size, oz);
-  } else {
-    const float voxel_x = floorf(((float)voxel_idx) / ((float)(vol_dim_y * vol_dim_z)));
-    const float voxel_y = floorf(((float)(voxel_idx - ((int)voxel_x) * vol_dim_y * vol_dim_z)) / ((float)vol_dim_z));
-    const float voxel_z = (float)(voxel_idx - ((int)voxel_x) * vol_dim_y * vol_dim_z - ((int)voxel_y) * vol_dim_z);
-    const int ix = (int)voxel_x, iy = (int)voxel_y;
-    const bool in_table = ix >= 0 && ix < vol_dim_x && iy >= 0 && iy < vol_dim_y;
-    if (in_table) {
-      px = colinfo[ix * vol_dim_y + iy];
-      if (px == -1) return 0;
-      if (px >= 0) px &= 0x3FFFFFFF;
-    }
-    pt_x = __fmaf_rn(voxel_x, voxel_size, ox);
-    pt_y = __fmaf_rn(voxel_y, voxel_size, oy);
-    pt_z = __fmaf_rn(voxel_z, voxel_size, oz);
-    if (px < 0) {
-      const float yaw = -atan2f(pt_y, pt_x);
-      float proj_x = (float)(0.5 * ((double)yaw / LT_PI_D + 1.0));
-      proj_x *= (float)im_w;
-      px = (int)floorf(proj_x);
-      px = min(im_w - 1, px);
-      px = max(0, px);
-    }
-  }
-  const float fov = fabsf(fov_up) + fabsf(fov_down);
-  const float depth = norm3df(pt_x, pt_y, pt_z);  // the device library's, as the reference's source gets it (header note)
-  const float s = pt_z / depth;
-  if ((s > sin_up_hi || s < sin_down_lo) && fabsf(s) <= 1.0f) return 0;  // (|s| > 1: see tsdf_voxel)
-  const float pitch = asinf(s);
-  if (pitch > fov_up || pitch < fov_down) return 0;
-  float proj_y = (float)(1.0 - (double)((pitch + fabsf(fov_down)) / fov));
-  proj_y *= (float)im_h;
-  int py = (int)floorf(proj_y);
-  py = min(im_h - 1, py);
-  py = max(0, py);
-  if (want_py >= 0 && py != want_py) return 0;
-  return tsdf_updates_fresh(tsdf_vol, weight_vol, color_vol, rem_vol, voxel_idx, depth, trunc_margin, obs_weight, obs4,
-                            (size_t)px * im_h + py, (size_t)im_h * im_w, n_obs);
+    float voxel_size, float inv_vs, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up,
+    float fov_down, float sin_up_hi, float sin_down_lo, const float* __restrict__ color_im,
+    const float* __restrict__ depth_im, const float* __restrict__ rem_im, const int* __restrict__ wd_px,
+    unsigned* __restrict__ col_epoch, unsigned epoch, unsigned long long* __restrict__ sign_bits, int words_z,
+    unsigned* __restrict__ col_zw, unsigned* __restrict__ chunk_epoch, const float2* __restrict__ dct,
+    const float4* __restrict__ rowtab, const int* __restrict__ wd_start, const int2* __restrict__ wd_ent, const uint32_t* __restrict__ wd_key, int rho_bits,
+    float qscale, const unsigned* __restrict__ zw_snap, unsigned long long* __restrict__ dbg) {
+  pix_body<false, VCOUNT>(tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, inv_vs, im_h, im_w, trunc_margin,
+                          obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, rem_im, nullptr, 1, wd_px, col_epoch, epoch,
+                          sign_bits, words_z, col_zw, chunk_epoch, dct, rowtab, wd_start, wd_ent, wd_key, rho_bits, qscale,
+                          zw_snap, dbg);
 }
 
 template <bool VCOUNT>
@@ -1155,289 +1181,10 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_pix_multi(
     unsigned* __restrict__ col_zw, unsigned* __restrict__ chunk_epoch,
     const float4* __restrict__ rowtab, const int* __restrict__ wd_start, const int2* __restrict__ wd_ent, const uint32_t* __restrict__ wd_key, int rho_bits,
     float qscale, unsigned long long* __restrict__ dbg) {
-  // k_tsdf_integrate_pix for n_obs observations of a FRESH volume at once (see above): a pixel's candidate interval is the
-  // UNION of the observations' -- a voxel an observation can write lies in that observation's interval while it still holds
-  // its initial values, and once written (by an earlier observation: inside an earlier interval) anywhere in front of the band.
-  const size_t n_pix_all = (size_t)im_h * im_w;
-  // per pixel of the workgroup
-  __shared__ int p_k0[64], p_pre[65], p_r[64], p_px[64];
-  __shared__ float p_tlo[64], p_thi[64], p_dlo[64], p_dhi[64];
-  // per pair of the chunk (one block: phase A borrows it as the staging area of the wedge's rho quanta)
-  __shared__ int c_buf[LT_PIX_STAGE > 4 * LT_PIX_CHUNK + 1 ? LT_PIX_STAGE : 4 * LT_PIX_CHUNK + 1];
-  int* const c_col = c_buf;
-  int* const c_z0 = c_buf + LT_PIX_CHUNK;
-  int* const c_src = c_buf + 2 * LT_PIX_CHUNK;
-  int* const c_pre = c_buf + 3 * LT_PIX_CHUNK;  // [LT_PIX_CHUNK + 1]
-  __shared__ float c_rho2[LT_PIX_CHUNK];
-  __shared__ int wsum[4];
-  // the columns' written ranges, merged in LDS first: the pairs of a workgroup fall on a few dozen table entries of ONE
-  // wedge (a wall's column is visited by dozens of rows), and two global atomics + two stores per PAIR were 43 of the
-  // kernel's 92 us (tools/pix_sections.sh).  a_lo / a_hi are indexed by table entry - a_k0 and hold the col_zw encoding
-  // (0x7fff - lo, hi + 1; 0 = nothing); a workgroup whose pairs span more than LT_PIX_AGG entries marks directly.
-  __shared__ unsigned a_lo[LT_PIX_AGG], a_hi[LT_PIX_AGG];
-  __shared__ int a_k0, a_span;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t qmax = (1u << rho_bits) - 2u;
-  const int n_pix = im_h * im_w;
-  const uint32_t* const skey = (const uint32_t*)c_buf;  // staged quanta of [stage0, stage0 + n_stage)
-  int stage0 = 0, n_stage = 0;
-  // first table index in [a, b) whose rho quantum is >= q (b if none): the wedges are sorted by it.  The 64 pixels of a
-  // workgroup search the SAME wedge(s): 22 dependent global loads per pixel became one coalesced copy into LDS
-  bool staged = false;  // (workgroup-uniform: the whole search range is in LDS)
-  auto lower = [&](int a, int b, uint32_t q) {
-    if (staged) {
-      while (a < b) {
-        const int m = (a + b) >> 1;
-        if (skey[m - stage0] < q) a = m + 1;
-        else b = m;
-      }
-    } else {
-      while (a < b) {
-        const int m = (a + b) >> 1;
-        if (wd_key[m] < q) a = m + 1;
-        else b = m;
-      }
-    }
-    return a;
-  };
-  for (int p0 = blockIdx.x * 64; p0 < n_pix; p0 += gridDim.x * 64) {  // (workgroup-uniform)
-    const unsigned long long tm0 = VCOUNT ? (unsigned long long)wall_clock64() : 0ull;  // (100 MHz; debug)
-    LT_PIX_MARK(0);
-    // ---- A: the pixels' runs of table entries ------------------------------------------------------------------------
-    {  // stage the quanta of the wedges these 64 pixels search (one image column when im_h is a multiple of 64)
-      const int px_a = p0 / im_h, px_b = min(p0 + 63, n_pix - 1) / im_h;
-      stage0 = wd_start[px_a];
-      n_stage = wd_start[px_b + 1] - stage0;
-      staged = n_stage <= LT_PIX_STAGE;  // (a longer run of wedges is searched in global memory)
-#ifdef LT_PIX_NO_STAGE  // (timing experiment)
-      staged = false;
-#endif
-      if (staged)
-      {  // all loads first, then the LDS stores: the rolled loop waited for every load before it issued the next
-        // (up to 15 dependent round trips, as in k_tsdf_integrate_pix)
-        constexpr int NS = (LT_PIX_STAGE + 255) / 256;
-        uint32_t sv[NS];
-#pragma unroll
-        for (int k = 0; k < NS; ++k) sv[k] = tid + 256 * k < n_stage ? wd_key[stage0 + tid + 256 * k] : 0u;
-#pragma unroll
-        for (int k = 0; k < NS; ++k)
-          if (tid + 256 * k < n_stage) c_buf[tid + 256 * k] = (int)sv[k];
-      }
-      __syncthreads();
-    }
-    if (wave != 0) {
-      for (int i = tid - 64; i < LT_PIX_AGG; i += 192) { a_lo[i] = 0u; a_hi[i] = 0u; }
-    }
-    if (wave == 0) {
-      const int p = p0 + lane;  // pixel (row r, column px) at [px * im_h + r] of the transposed images
-      const bool in = p < n_pix;
-      const int px = in ? p / im_h : 0, r = in ? p - px * im_h : 0;
-      const float4 row = rowtab[r];  // (tan_lo, tan_hi, cos_min, cos_max); tan_lo > tan_hi: no voxel can take this row
-      const bool row_ok = row.x <= row.y;
-      // per observation as in k_tsdf_integrate_pix; the union: [min d_lo, max d_hi]
-      bool any = false;
-      float d_lo = 3e38f, d_hi = 0.f;
-      for (int kk = 0; kk < n_obs; ++kk) {
-        const float4 o4 = in ? obs4[(size_t)kk * n_pix_all + p] : make_float4(0.f, 1.f, 0.f, 0.f);
-        const float D = o4.x;
-        const bool finite = D == D && fabsf(D) < 1e30f;
-        const bool zero_class_k = in && row_ok && D != 0.f && o4.y == 0.0f;
-        const bool normal_k = in && row_ok && D != 0.f && o4.y != 0.0f && finite;
-        if (normal_k || zero_class_k) {
-          const float eps = __fmaf_rn(4e-6f, fabsf(D) + trunc_margin, 1e-6f);
-          const float hi_k = finite ? D + trunc_margin + eps : 3e38f;
-          // (once a voxel has been written -- by an earlier observation, inside an earlier interval -- a later one updates it
-          // anywhere in front of ITS band: a later observation's band further out extends the union's upper end, and the
-          // voxels in front of it that earlier observations wrote are inside the union already)
-          const float lo_k = zero_class_k ? 0.f : D - eps;
-          if (hi_k > 0.f) { any = true; d_lo = fminf(d_lo, lo_k); d_hi = fmaxf(d_hi, hi_k); }
-        }
-      }
-      const bool normal = any, zero_class = false;
-      const int s0 = wd_start[px], s1 = wd_start[px + 1];
-      int k = 0, kend = 0;
-      if ((normal || zero_class) && d_hi > 0.f) {
-        const float rho1 = fmaxf(d_lo, 0.f) * row.z * 0.999999f;
-        const float f1 = floorf(rho1 * qscale) - 2.f;
-        const uint32_t q1 = (uint32_t)fminf(fmaxf(f1, 0.f), (float)qmax);
-        k = lower(s0, s1, q1);
-        kend = s1;
-        if (d_hi < 3e38f) {
-          const float f2 = floorf(d_hi * row.w * 1.000001f * qscale) + 2.f;
-          const uint32_t q2 = (uint32_t)fminf(fmaxf(f2, 0.f), (float)qmax);
-          kend = lower(k, s1, q2 + 1u);
-        }
-      }
-      const int cnt = kend - k;
-      int inc = cnt;  // inclusive wave scan
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
-      p_k0[lane] = k; p_pre[lane] = inc - cnt; p_r[lane] = r; p_px[lane] = px;
-      p_tlo[lane] = row.x; p_thi[lane] = row.y; p_dlo[lane] = d_lo; p_dhi[lane] = d_hi;
-      if (lane == 63) p_pre[64] = inc;
-      // the span of table entries the workgroup's pairs fall on
-      int kmin = cnt > 0 ? k : 0x7fffffff, kmax = cnt > 0 ? kend : 0;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        kmin = min(kmin, __shfl_xor(kmin, o, 64));
-        kmax = max(kmax, __shfl_xor(kmax, o, 64));
-      }
-      if (lane == 0) { a_k0 = kmin; a_span = kmax > kmin ? kmax - kmin : 0; }
-    }
-    __syncthreads();
-    const int T = p_pre[64];
-    const int agg_k0 = a_k0, agg_span = a_span;
-    const bool agg = agg_span <= LT_PIX_AGG;  // (workgroup-uniform)
-    if (VCOUNT && tid == 0) atomicAdd(&dbg[4], (unsigned long long)wall_clock64() - tm0);  // phase A
-    LT_PIX_MARK(1);
-    // ---- B: chunks of pairs ---------------------------------------------------------------------------------------------
-    for (int base = 0; base < T; base += LT_PIX_CHUNK) {
-      constexpr int PPT = LT_PIX_CHUNK / 256;  // pairs per thread
-      int len[PPT];
-#pragma unroll
-      for (int u = 0; u < PPT; ++u) {
-        const int slot = u * 256 + tid, i = base + slot;
-        len[u] = 0;
-        if (i < T) {
-          int sidx = 0;  // largest s with p_pre[s] <= i
-#pragma unroll
-          for (int st = 32; st >= 1; st >>= 1)
-            if (p_pre[sidx + st] <= i) sidx += st;
-          const int kk = p_k0[sidx] + (i - p_pre[sidx]);
-          const int2 e = wd_ent[kk];
-          int z = 1, zend = 0;
-          if (e.x >= 0) {  // (the quirk tail of the last wedge carries column -1)
-            const float rho2 = __int_as_float(e.y), rho = sqrtf(rho2);
-            const float d_lo = p_dlo[sidx], d_hi = p_dhi[sidx];
-            const float hi2 = d_hi * d_hi - rho2;
-            if (hi2 >= 0.f) {  // (else the whole column lies beyond the band; false also for NaN)
-              const float zmax = sqrtf(hi2) * 1.000001f + 1e-6f;
-              const float lo2 = d_lo > 0.f ? d_lo * d_lo - rho2 : -1.f;
-              const float zmin = lo2 > 0.f ? fmaxf(sqrtf(lo2) * 0.999999f - 1e-6f, 0.f) : 0.f;
-              const float za = rho * p_tlo[sidx], zb = rho * p_thi[sidx];  // pt_z of the row in this column
-              float lo, hi;
-              if (za >= 0.f) { lo = fmaxf(za, zmin); hi = fminf(zb, zmax); }
-              else if (zb <= 0.f) { lo = fmaxf(za, -zmax); hi = fminf(zb, -zmin); }
-              else { lo = fmaxf(za, -zmax); hi = fminf(zb, zmax); }
-              if (lo <= hi) {
-                const float fz0 = ceilf((lo - oz) * inv_vs - 0.02f), fz1 = floorf((hi - oz) * inv_vs + 0.02f);
-                z = (int)fmaxf(fz0, 0.f);
-                zend = (int)fminf(fz1, (float)(vol_dim_z - 1));
-              }
-            }
-          }
-          const int partial = 0;
-          len[u] = max(zend - z + 1, 0);
-          c_col[slot] = e.x; c_rho2[slot] = __int_as_float(e.y); c_z0[slot] = z; c_src[slot] = sidx | partial;
-          // the column's written range and stamp once per PAIR, for the whole candidate interval (a superset is safe, as in
-          // the column walk) -- per written voxel, the ten threads holding one column's band voxels fought over one word
-#ifndef LT_PIX_NO_MARK  // (timing experiment)
-          if (len[u] > 0) {
-            if (agg) {
-              atomicMax(&a_lo[kk - agg_k0], (unsigned)(0x7FFF - z));
-              atomicMax(&a_hi[kk - agg_k0], (unsigned)(zend + 1));
-            } else {
-              col_mark_written(col_zw, col_epoch, chunk_epoch, epoch, vol_dim_x * vol_dim_y, e.x, z, zend);
-            }
-          }
-#endif
-        }
-      }
-      // exclusive prefix of the interval lengths over the chunk's slots (slot = u * 256 + tid: strided passes)
-      int run = 0;  // voxels of the passes before
-#pragma unroll
-      for (int u = 0; u < PPT; ++u) {
-        int inc = len[u];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const int t = __shfl_up(inc, o, 64);
-          if (lane >= o) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wsum[w];
-        const int tot = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        c_pre[u * 256 + tid] = run + woff + inc - len[u];
-        run += tot;
-        __syncthreads();
-      }
-      if (tid == 0) c_pre[LT_PIX_CHUNK] = run;
-      __syncthreads();
-      const int V = run, n_slots = min(T - base, LT_PIX_CHUNK);
-      const unsigned long long tm1 = VCOUNT ? (unsigned long long)wall_clock64() : 0ull;
-      if (VCOUNT && tid == 0 && base == 0) atomicAdd(&dbg[5], tm1 - tm0);  // ... + first chunk's pairs and scan
-      if (base == 0) LT_PIX_MARK(2);
-      // the chunk's voxels, one per thread and round
-      for (int jb = 0; jb < V; jb += 256) {  // (workgroup-uniform trips: the run aggregation below shuffles)
-        const int j = jb + tid;
-        int code = 0, col = 0, z = 0;
-        if (j < V) {
-        int sl = 0;  // largest slot < n_slots with c_pre[slot] <= j
-#pragma unroll
-        for (int st = LT_PIX_CHUNK / 2; st >= 1; st >>= 1)
-          if (sl + st < n_slots && c_pre[sl + st] <= j) sl += st;
-        const int sflag = c_src[sl], sidx = sflag & 63;
-        col = c_col[sl]; z = c_z0[sl] + (j - c_pre[sl]);
-        bool mine = true;
-        col_plain Cq;
-        Cq.plain = true; Cq.px = p_px[sidx]; Cq.rho2 = c_rho2[sl]; Cq.col = col;
-#ifdef LT_PIX_NO_EVAL  // timing experiment: everything but the evaluation (nothing is written)
-        mine = false;
-#endif
-        if (mine)
-        code = tsdf_voxel_multi(col * vol_dim_z + z, tsdf_vol, weight_vol, color_vol, rem_vol, vol_dim_x, vol_dim_y, vol_dim_z,
-                                ox, oy, oz, voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
-                                sin_down_lo, wd_px, Cq, z, obs4, n_obs, p_r[sidx]);
-        }
-        // sign bits: the volume is fresh, every bit is 0 -- only negative values need a write; the voxels of a pair sit in
-        // neighbouring lanes and (mostly) in one 64-bit word: OR them together over the run, one atomic per run
-#ifdef LT_PIX_NO_BITS  // timing experiment: no sign bits (marching cubes would see nothing)
-        code = 0;
-#endif
-        const int wkey = code == 2 ? col * words_z + (z >> 6) : -1 - lane;  // (unique when there is nothing to write)
-        unsigned long long bits = code == 2 ? 1ull << (z & 63) : 0ull;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {  // runs of up to 16 lanes (a run is one column's interval: ~10 voxels)
-          const unsigned long long ob = __shfl_down(bits, o, 64);
-          const int ok = __shfl_down(wkey, o, 64);
-          if (lane + o < 64 && ok == wkey) bits |= ob;
-        }
-        const int prev = __shfl_up(wkey, 1, 64);
-        if (code == 2 && (lane == 0 || prev != wkey || (lane & 15) == 0))  // (lane & 15: a run longer than 16 lanes)
-          atomicOr(sign_bits + (size_t)wkey, bits);
-        if (VCOUNT) {  // (one atomic per wave and round: a per-voxel atomic on one address would be the whole kernel)
-          const unsigned long long wr = __ballot(code != 0);
-          if (lane == 0 && wr) atomicAdd(&dbg[2], (unsigned long long)__popcll(wr));
-        }
-      }
-      if (VCOUNT && tid == 0) {
-        atomicAdd(&dbg[0], (unsigned long long)n_slots); atomicAdd(&dbg[1], (unsigned long long)V);
-        atomicAdd(&dbg[6], (unsigned long long)wall_clock64() - tm1);  // the voxel rounds
-        atomicAdd(&dbg[7], 1ull);
-      }
-      __syncthreads();  // the chunk's arrays are reused
-    }
-    LT_PIX_MARK(3);
-    // the merged ranges -> col_zw, stamps: once per column (all pairs of all chunks have merged: the barrier above)
-    if (agg)
-      for (int i = tid; i < agg_span; i += 256) {
-        const unsigned hi1 = a_hi[i];
-        if (hi1) {
-          const int c = wd_ent[agg_k0 + i].x;
-          const int n_cols = vol_dim_x * vol_dim_y;
-          atomicMax(&col_zw[c], a_lo[i]);  // (atomic: with an image height that does not divide 64 two workgroups share a wedge)
-          atomicMax(&col_zw[n_cols + c], hi1);
-          col_epoch[c] = epoch;
-          chunk_epoch[c >> 6] = epoch;
-        }
-      }
-    LT_PIX_MARK(4);
-    __syncthreads();  // ... and the pixels'
-  }
+  pix_body<true, VCOUNT>(tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, inv_vs, im_h, im_w, trunc_margin,
+                         obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, nullptr, obs4, n_obs, wd_px, col_epoch, epoch,
+                         sign_bits, words_z, col_zw, chunk_epoch, nullptr, rowtab, wd_start, wd_ent, wd_key, rho_bits, qscale,
+                         nullptr, dbg);
 }
 
 // the quirk columns (not in the wedge table) for the n observations at once, one thread per voxel
@@ -1452,10 +1199,9 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_quirk_multi(
   if (i >= (long long)n_q * vol_dim_z) return;
   const int col = (int)qcols[i / vol_dim_z], z = (int)(i % vol_dim_z);
   col_plain C;
-  C.plain = false; C.px = -2; C.rho2 = 0.f; C.col = 0;
-  const int code = tsdf_voxel_multi(col * vol_dim_z + z, tsdf_vol, weight_vol, color_vol, rem_vol, vol_dim_x, vol_dim_y,
-                                    vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down,
-                                    sin_up_hi, sin_down_lo, wd_px, C, z, obs4, n_obs);
+  const int code = tsdf_voxel_multi(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size,
+                                    im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, wd_px,
+                                    C, z, obs4, n_obs);
   if (code) {
     if (code == 2) atomicOr(sign_bits + (size_t)col * words_z + (z >> 6), 1ull << (z & 63));  // (fresh volume: the bit is 0)
     col_mark_written(col_zw, col_epoch, chunk_epoch, epoch, vol_dim_x * vol_dim_y, col, z, z);
@@ -1533,12 +1279,7 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_written(
           }
         }
       }
-      int inc = len;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
+      const int inc = wave_scan_incl(len, lane);
       w_lo[lane] = lo; w_px[lane] = px; w_rho2[lane] = rho2; w_pre[lane] = inc - len;
       if (lane == 63) w_pre[64] = inc;
     }
@@ -1548,7 +1289,7 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_written(
     st_pro += st_b - st_a; st_n += 1;
 #endif
     const int V = w_pre[64];
-    for (int jb = 0; jb < V; jb += 256) {  // (workgroup-uniform trips: the run aggregation below shuffles)
+    for (int jb = 0; jb < V; jb += 256) {  // (workgroup-uniform trips: sign_run_merge shuffles)
       const int j = jb + tid;
       int code = 0, cc = 0, z = 0;
       if (j < V) {
@@ -1558,27 +1299,13 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_written(
           if (w_pre[sidx + st] <= j) sidx += st;
         cc = chunk * 64 + sidx;
         z = w_lo[sidx] + (j - w_pre[sidx]);
-        col_plain C;
-        C.plain = true; C.px = w_px[sidx]; C.rho2 = w_rho2[sidx]; C.col = cc;
-        code = tsdf_voxel<MERGE>(cc * vol_dim_z + z, tsdf_vol, weight_vol, color_vol, rem_vol, vol_dim_x, vol_dim_y, vol_dim_z,
-                                 ox, oy, oz, voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
-                                 sin_down_lo, color_im, depth_im, rem_im, wd_px, col_epoch, epoch, false, C, z, dct);
+        const col_plain C = {true, w_px[sidx], w_rho2[sidx], cc};
+        code = tsdf_voxel<MERGE>(cc * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size,
+                                 im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, rem_im,
+                                 wd_px, false, C, z, dct);
       }
-      // the sign of every value written: set the bit (negative) or clear it; one OR and one AND-NOT per run of lanes that
-      // hold voxels of one column's word (a column's range is consecutive in j)
-      const int wkey = code ? cc * words_z + (z >> 6) : -1 - lane;
-      unsigned long long set = code == 2 ? 1ull << (z & 63) : 0ull, clr = code == 1 ? 1ull << (z & 63) : 0ull;
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
-        const unsigned long long os = __shfl_down(set, o, 64), oc = __shfl_down(clr, o, 64);
-        const int ok = __shfl_down(wkey, o, 64);
-        if (lane + o < 64 && ok == wkey) { set |= os; clr |= oc; }
-      }
-      const int prev = __shfl_up(wkey, 1, 64);
-      if (code && (lane == 0 || prev != wkey || (lane & 15) == 0)) {
-        if (set) atomicOr(sign_bits + (size_t)wkey, set);
-        if (clr) atomicAnd(sign_bits + (size_t)wkey, ~clr);
-      }
+      // the sign of every value written: set the bit (negative) or clear it (a column's range is consecutive in j)
+      sign_run_merge<true>(sign_bits, code, cc, z, words_z, lane);
     }
     __syncthreads();  // the chunk's arrays are reused
 #ifdef LT_TSDF_STAMP
@@ -1611,11 +1338,9 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_quirk(
   if (i >= (long long)n_q * vol_dim_z) return;
   const int col = (int)qcols[i / vol_dim_z], z = (int)(i % vol_dim_z);
   col_plain C;
-  C.plain = false; C.px = -2; C.rho2 = 0.f; C.col = 0;
-  const int code = tsdf_voxel<MERGE>(col * vol_dim_z + z, tsdf_vol, weight_vol, color_vol, rem_vol, vol_dim_x, vol_dim_y,
-                                     vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up,
-                                     fov_down, sin_up_hi, sin_down_lo, color_im, depth_im, rem_im, wd_px, col_epoch, epoch,
-                                     fresh != 0, C, z, dct);
+  const int code = tsdf_voxel<MERGE>(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size,
+                                     im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, rem_im,
+                                     wd_px, fresh != 0, C, z, dct);
   if (code) {
     unsigned long long* w = sign_bits + (size_t)col * words_z + (z >> 6);
     const unsigned long long bit = 1ull << (z & 63);
@@ -1637,22 +1362,42 @@ extern "C" int lt_tsdf_destroy(lt_tsdf* t) {
   return LT_OK;
 }
 
-// geometry of the per-column z range: slopes of the field of view with the 1e-5 margin of the sine test on the angles;
-// off for fields of view beyond +-80 degrees
 static unsigned long long* g_tsdf_dbg = nullptr;  // LIDARHIP_DEBUG_TSDF: per-wave stamps of k_tsdf_integrate_cols
 static unsigned long long* g_pix_dbg = nullptr;   // ... and {pairs, candidate voxels, written voxels} of k_tsdf_integrate_pix
 
-static col_geom tsdf_geom(const lt_tsdf* t) {
+// the volume's field of view as the kernels take it: other_params[6] * PI / 180.0 in double, stored to float
+// (fusion_lidar.py:124-125; the launch passes the degrees as float32, :278-280); the sine thresholds of the conservative
+// field-of-view test, 1e-5 beyond the limits (asinf is good to ~1e-7); tangents are used up to +-80 degrees
+struct tsdf_fov { float fu, fd, su, sd; bool tan_ok; };
+static tsdf_fov tsdf_fov_of(const lt_tsdf* t) {
   const float fu = (float)((double)(float)t->fov_up_deg * LT_PI_D / 180.0);
   const float fd = (float)((double)(float)t->fov_down_deg * LT_PI_D / 180.0);
+  return {fu, fd, (float)(sin((double)fu) + 1e-5), (float)(sin((double)fd) - 1e-5),
+          fabs((double)fu) < 1.39 && fabs((double)fd) < 1.39};
+}
+
+// geometry of the per-column z range: slopes of the field of view with the 1e-5 margin of the sine test on the angles
+static col_geom tsdf_geom(const lt_tsdf* t, const tsdf_fov& F) {
   col_geom G;
   G.dim_y = t->dim[1]; G.dim_z = t->dim[2];
   G.ox = t->origin[0]; G.oy = t->origin[1]; G.oz = t->origin[2];
   G.voxel_size = t->voxel_size;
-  G.tan_ok = fabs((double)fu) < 1.39 && fabs((double)fd) < 1.39;
-  G.tan_up = G.tan_ok ? (float)tan((double)fu + 1e-5) : 0.f;
-  G.tan_down = G.tan_ok ? (float)tan((double)fd - 1e-5) : 0.f;
+  G.tan_ok = F.tan_ok;
+  G.tan_up = G.tan_ok ? (float)tan((double)F.fu + 1e-5) : 0.f;
+  G.tan_down = G.tan_ok ? (float)tan((double)F.fd - 1e-5) : 0.f;
   return G;
+}
+
+// a per-call device buffer of `cap` elements that must hold `need`: re-allocated with `alloc` elements when it does not.
+// (A growth event, not steady state: the device is synchronised before the old buffer goes, as hipFree would anyway.)
+template <class T, class N>
+static int tsdf_grow(T*& buf, N& cap, size_t need, size_t alloc) {
+  if (need <= (size_t)cap) return LT_OK;
+  if (buf) { LT_HIP(hipDeviceSynchronize()); (void)hipFree(buf); buf = nullptr; }
+  cap = 0;
+  LT_HIP(hipMalloc((void**)&buf, alloc * sizeof(T)));
+  cap = (N)alloc;
+  return LT_OK;
 }
 
 static int tsdf_full_reset(lt_tsdf* t, hipStream_t stream) {
@@ -1768,20 +1513,20 @@ static int tsdf_wedge_build(lt_tsdf* t, int im_w, int rho_bits, hipStream_t stre
   if (!t->wd_px || !t->wd_ent || !t->wd_key) {
     // all three or none: an allocation that fails half way must not leave a non-NULL wd_px behind (the next integrate
     // would skip this block and launch the table kernels on NULL tables)
+    auto drop = [&]() {
+      if (t->wd_px) (void)hipFree(t->wd_px);
+      if (t->wd_ent) (void)hipFree(t->wd_ent);
+      if (t->wd_key) (void)hipFree(t->wd_key);
+      t->wd_px = nullptr; t->wd_ent = nullptr; t->wd_key = nullptr;
+    };
     if (t->wd_px || t->wd_ent || t->wd_key) LT_HIP(hipStreamSynchronize(stream));
-    if (t->wd_px) (void)hipFree(t->wd_px);
-    if (t->wd_ent) (void)hipFree(t->wd_ent);
-    if (t->wd_key) (void)hipFree(t->wd_key);
-    t->wd_px = nullptr; t->wd_ent = nullptr; t->wd_key = nullptr;
+    drop();
     t->wd_w = 0;
     bool ok = hipMalloc((void**)&t->wd_px, (size_t)n * sizeof(int)) == hipSuccess &&
               hipMalloc((void**)&t->wd_ent, (size_t)n * sizeof(int2)) == hipSuccess &&
               hipMalloc((void**)&t->wd_key, (size_t)n * sizeof(unsigned)) == hipSuccess;
     if (!ok) {
-      if (t->wd_px) (void)hipFree(t->wd_px);
-      if (t->wd_ent) (void)hipFree(t->wd_ent);
-      if (t->wd_key) (void)hipFree(t->wd_key);
-      t->wd_px = nullptr; t->wd_ent = nullptr; t->wd_key = nullptr;
+      drop();
       (void)hipGetLastError();
       lt_set_error("lt_tsdf: out of device memory for the wedge table (%d columns)", n);
       return LT_ERR_NO_MEMORY;
@@ -1867,43 +1612,76 @@ static int tsdf_rowtab(lt_tsdf* t, int im_h, float fu, float fd, hipStream_t str
     tab[r] = make_float4(nextafterf((float)tan(lo), -INFINITY), nextafterf((float)tan(hi), INFINITY),
                          nextafterf((float)cmin, 0.f), nextafterf((float)cmax, 2.f));
   }
-  if (im_h > t->rowtab_h) {
-    if (t->rowtab) { LT_HIP(hipStreamSynchronize(stream)); (void)hipFree(t->rowtab); t->rowtab = nullptr; }
-    LT_HIP(hipMalloc((void**)&t->rowtab, (size_t)im_h * sizeof(float4)));
-    t->rowtab_h = im_h;
-  }
+  LT_CHECK(tsdf_grow(t->rowtab, t->rowtab_h, (size_t)im_h, (size_t)im_h));
   // (a blocking copy from pageable memory: the vector may go out of scope when this returns)
   LT_HIP(hipMemcpyAsync(t->rowtab, tab.data(), (size_t)im_h * sizeof(float4), hipMemcpyHostToDevice, stream));
   LT_HIP(hipStreamSynchronize(stream));
   return LT_OK;
 }
 
-static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* depth_im, const float* rem_im, int im_h,
-                              int im_w, float obs_weight, float fu, float fd, int rho_bits, bool fresh_volume,
-                              hipStream_t stream) {
+// ---- which integrate runs: LIDARHIP_TSDF_PIX, read once.  The class-aware update where tsdf_pix_applies: ------------------
+//   value          lt_tsdf_integrate_dev                                   lt_tsdf_integrate_multi_dev
+//   unset, "", 2   pixel pass, every observation                           fused pass (fresh volume, n_obs >= 2), the rest ->
+//   0              column walk                                             not fused: one lt_tsdf_integrate_dev each
+//   1              pixel pass on a fresh volume, column walk afterwards    not fused: one lt_tsdf_integrate_dev each
+//   anything else  pixel pass, every observation                           not fused: one lt_tsdf_integrate_dev each
+// (LIDARHIP_TSDF_MULTI=0 switches the fused pass off as well.)
+enum tsdf_pix_mode { TSDF_PIX_WALK, TSDF_PIX_FRESH_ONLY, TSDF_PIX_DEFAULT };
+struct tsdf_pix_knob { tsdf_pix_mode mode; bool fuse; };
+static tsdf_pix_knob tsdf_pix_env() {
+  static const tsdf_pix_knob K = []() {
+    const char *e = getenv("LIDARHIP_TSDF_PIX"), *m = getenv("LIDARHIP_TSDF_MULTI");
+    const tsdf_pix_mode mode = e && strcmp(e, "0") == 0 ? TSDF_PIX_WALK : (e && strcmp(e, "1") == 0 ? TSDF_PIX_FRESH_ONLY : TSDF_PIX_DEFAULT);
+    return tsdf_pix_knob{mode, (!e || e[0] == 0 || strcmp(e, "2") == 0) && !(m && strcmp(m, "0") == 0)};
+  }();
+  return K;
+}
+
+// The pixel pass applies to the class-aware update of a volume whose columns carry their stamps, for a field of view the
+// row table's tangents cover, with at least 12 bits left for the rho quantum beside the image column in a 30-bit sort key.
+static bool tsdf_pix_applies(const lt_tsdf* t, unsigned flags, int im_w, const tsdf_fov& F, int* rho_bits) {
+  int px_bits = 1;
+  while ((1 << px_bits) < im_w) ++px_bits;
+  *rho_bits = 30 - px_bits;
+  return (flags & LT_TSDF_MERGE) && !t->all_dirty && F.tan_ok && 30 - px_bits >= 12 && fabsf(F.fu) + fabsf(F.fd) > 0.f;
+}
+
+// the wedge table of (im_w, rho_bits) and the row table of im_h (the field of view is fixed per volume), made when missing
+static int tsdf_pix_tables(lt_tsdf* t, int im_h, int im_w, int rho_bits, const tsdf_fov& F, hipStream_t stream) {
   if (t->wd_w != im_w || t->wd_rho_bits != rho_bits) LT_CHECK(tsdf_wedge_build(t, im_w, rho_bits, stream));
-  // the row table depends on (im_h, fov): both fixed for a sensor model; keyed by im_h and re-made when it changes
   if (t->rowtab_for_h != im_h || !t->rowtab) {
     t->rowtab_for_h = 0;
-    LT_CHECK(tsdf_rowtab(t, im_h, fu, fd, stream));
+    LT_CHECK(tsdf_rowtab(t, im_h, F.fu, F.fd, stream));
     t->rowtab_for_h = im_h;
   }
-  if ((size_t)im_w * im_h > t->cap_dct) {
-    if (t->dct) { LT_HIP(hipDeviceSynchronize()); (void)hipFree(t->dct); t->dct = nullptr; t->cap_dct = 0; }
-    LT_HIP(hipMalloc((void**)&t->dct, (size_t)im_w * im_h * sizeof(float2)));
-    t->cap_dct = (size_t)im_w * im_h;
-  }
-  hipLaunchKernelGGL(k_tsdf_dct, dim3((im_h * im_w + 255) / 256), dim3(256), 0, stream, depth_im, color_im, im_h, im_w, t->dct);
-  const float su = (float)(sin((double)fu) + 1e-5), sd = (float)(sin((double)fd) - 1e-5);
-  const int words_z = (t->dim[2] + 63) / 64;
-  const int n_pix = im_h * im_w;
-  // a workgroup per 64 pixels -- unless that is more than the chip holds at once (5 per CU: 97 VGPRs, 27.5 KB of LDS): the
-  // workgroups then walk the groups of 64 in turn, so that the launch is ONE round of resident workgroups
-  // (LIDARHIP_PIX_WGS=n: n workgroups; =0: one per 64 pixels)
+  return LT_OK;
+}
+
+// grid of a pixel pass: a workgroup per 64 pixels -- unless that is more than the chip holds at once (waves_per_eu
+// workgroups per CU: the kernel's occupancy): the workgroups then walk the groups of 64 in turn, so that the launch is
+// ONE round of resident workgroups.  (LIDARHIP_PIX_WGS=n: n workgroups; =0: one per 64 pixels)
+static unsigned tsdf_pix_grid(const lt_tsdf* t, size_t n_pix, int waves_per_eu) {
   static const int env_wgs = []() { const char* e = getenv("LIDARHIP_PIX_WGS"); return e ? atoi(e) : -1; }();
-  const int res_wgs = lt_cu_count(t->device) * LT_PIX_WPE;
-  const int groups = (n_pix + 63) / 64;
-  const unsigned nb = (unsigned)min(groups, env_wgs > 0 ? env_wgs : (env_wgs == 0 ? (1 << 20) : res_wgs));
+  const int groups = (int)((n_pix + 63) / 64);
+  return (unsigned)min(groups, env_wgs > 0 ? env_wgs : (env_wgs == 0 ? (1 << 20) : lt_cu_count(t->device) * waves_per_eu));
+}
+// k_tsdf_integrate_pix_multi carries no waves_per_eu attribute: this is its compiler-reported occupancy (96 VGPRs, 27.5 KB
+// of LDS), not LT_PIX_WPE, which a -D can change
+#define LT_PIX_MULTI_WPE 5
+// what the argument list of every integrate kernel starts with: the volume, and (after inv_vs, where there is one) the view
+#define LT_VOL_ARGS \
+  t->tsdf, t->weight, t->color, t->rem, t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2], t->voxel_size
+#define LT_VIEW_ARGS im_h, im_w, t->trunc_margin, obs_weight, F.fu, F.fd, F.su, F.sd
+
+static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* depth_im, const float* rem_im, int im_h,
+                              int im_w, float obs_weight, const tsdf_fov& F, int rho_bits, bool fresh_volume,
+                              hipStream_t stream) {
+  LT_CHECK(tsdf_pix_tables(t, im_h, im_w, rho_bits, F, stream));
+  const size_t n_pix = (size_t)im_w * im_h;
+  LT_CHECK(tsdf_grow(t->dct, t->cap_dct, n_pix, n_pix));
+  hipLaunchKernelGGL(k_tsdf_dct, dim3((im_h * im_w + 255) / 256), dim3(256), 0, stream, depth_im, color_im, im_h, im_w, t->dct);
+  const int words_z = (t->dim[2] + 63) / 64;
+  const unsigned nb = tsdf_pix_grid(t, n_pix, LT_PIX_WPE);
   const unsigned* zw_snap = nullptr;
   if (!fresh_volume) {
     // the written ranges as they stand before this observation (32 MB on the default volume: a device copy), then every
@@ -1914,30 +1692,25 @@ static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* de
     zw_snap = t->zw_snap;
     hipLaunchKernelGGL(k_tsdf_integrate_written<true>,
                        dim3((unsigned)lt_deal_count((int)((n_cols + 63) / 64), LT_WRITTEN_CHUNKS_PER_WG, t->dim[1], 1)), dim3(256), 0,
-                       stream, t->tsdf, t->weight, t->color, t->rem, t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1],
-                       t->origin[2], t->voxel_size, im_h, im_w, t->trunc_margin, obs_weight, fu, fd, su, sd, color_im, depth_im,
-                       rem_im, t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, zw_snap, t->dct, t->chunk_epoch);
+                       stream, LT_VOL_ARGS, LT_VIEW_ARGS, color_im, depth_im, rem_im, t->wd_px, t->col_epoch, t->epoch, t->bits,
+                       words_z, zw_snap, t->dct, t->chunk_epoch);
   }
   // LIDARHIP_DEBUG_TSDF=1: pairs / candidate voxels / written voxels of the launch (lt_debug_tsdf_pix_counts)
   static const bool want_cnt = getenv("LIDARHIP_DEBUG_TSDF") != nullptr;
   if (want_cnt && !g_pix_dbg) LT_HIP(hipMalloc((void**)&g_pix_dbg, 8 * sizeof(unsigned long long)));
   if (want_cnt) LT_HIP(hipMemsetAsync(g_pix_dbg, 0, 8 * sizeof(unsigned long long), stream));
-#define LT_PIX_ARGS                                                                                                          \
-  t->tsdf, t->weight, t->color, t->rem, t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2],           \
-      t->voxel_size, 1.0f / t->voxel_size, im_h, im_w, t->trunc_margin, obs_weight, fu, fd, su, sd, color_im, depth_im, rem_im, \
-      t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, t->col_zw, t->chunk_epoch, t->dct, t->rowtab, t->wd_start, t->wd_ent, \
-      t->wd_key,                                                                                                            \
-      t->wd_rho_bits, t->wd_qscale, zw_snap, g_pix_dbg
+#define LT_PIX_ARGS                                                                                                         \
+  LT_VOL_ARGS, 1.0f / t->voxel_size, LT_VIEW_ARGS, color_im, depth_im, rem_im, t->wd_px, t->col_epoch, t->epoch, t->bits,   \
+      words_z, t->col_zw, t->chunk_epoch, t->dct, t->rowtab, t->wd_start, t->wd_ent, t->wd_key, t->wd_rho_bits, t->wd_qscale, \
+      zw_snap, g_pix_dbg
   if (want_cnt) hipLaunchKernelGGL((k_tsdf_integrate_pix<true, true>), dim3(nb), dim3(256), 0, stream, LT_PIX_ARGS);
   else hipLaunchKernelGGL((k_tsdf_integrate_pix<true, false>), dim3(nb), dim3(256), 0, stream, LT_PIX_ARGS);
 #undef LT_PIX_ARGS
   if (t->wd_n_quirk > 0) {
     const long long nv = (long long)t->wd_n_quirk * t->dim[2];
-    hipLaunchKernelGGL(k_tsdf_integrate_quirk<true>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, t->tsdf, t->weight,
-                       t->color, t->rem, t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2],
-                       t->voxel_size, im_h, im_w, t->trunc_margin, obs_weight, fu, fd, su, sd, color_im, depth_im, rem_im,
-                       t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, t->col_zw, t->chunk_epoch, t->dct, t->wd_qcols, t->wd_n_quirk,
-                       fresh_volume ? 1 : 0);
+    hipLaunchKernelGGL(k_tsdf_integrate_quirk<true>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, LT_VOL_ARGS,
+                       LT_VIEW_ARGS, color_im, depth_im, rem_im, t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, t->col_zw,
+                       t->chunk_epoch, t->dct, t->wd_qcols, t->wd_n_quirk, fresh_volume ? 1 : 0);
   }
   LT_HIP(hipGetLastError());
   return LT_OK;
@@ -2010,8 +1783,6 @@ extern "C" int lt_tsdf_integrate_dev(lt_tsdf* t, const float* color_im, const fl
   }
   hipStream_t stream = (hipStream_t)stream_;
   LT_HIP(hipSetDevice(t->device));
-  // other_params[6] * PI / 180.0 in double, stored to float (fusion_lidar.py:124-125); the launch passes the
-  // degrees as float32 (:278-280)
   if (flags & LT_TSDF_HOST_MODE) {
     // self.fov_up / 180.0 * np.pi (fusion_lidar.py:308-309); every voxel is visited: no column stamps -> all_dirty
     const double fu_d = t->fov_up_deg / 180.0 * LT_PI_D, fd_d = t->fov_down_deg / 180.0 * LT_PI_D;
@@ -2023,42 +1794,20 @@ extern "C" int lt_tsdf_integrate_dev(lt_tsdf* t, const float* color_im, const fl
     t->n_obs += 1;
     return LT_OK;
   }
-  const float fu = (float)((double)(float)t->fov_up_deg * LT_PI_D / 180.0);
-  const float fd = (float)((double)(float)t->fov_down_deg * LT_PI_D / 180.0);
-  // ---- a fresh volume, the class-aware update: driven by the pixels (k_tsdf_integrate_pix) --------------------------------
-  static const bool pix_off = []() { const char* e = getenv("LIDARHIP_TSDF_PIX"); return e && strcmp(e, "0") == 0; }();
-  const bool tan_ok = fabs((double)fu) < 1.39 && fabs((double)fd) < 1.39;
-  int px_bits = 1;
-  while ((1 << px_bits) < im_w) ++px_bits;
-  // (LIDARHIP_TSDF_PIX=1: only the first observation of a fresh volume; default: every observation)
-  static const bool pix_fresh_only = []() { const char* e = getenv("LIDARHIP_TSDF_PIX"); return e && strcmp(e, "1") == 0; }();
-  const bool use_pix = !pix_off && (flags & LT_TSDF_MERGE) && (t->n_obs == 0 || !pix_fresh_only) && !t->all_dirty && tan_ok &&
-                       30 - px_bits >= 12 && fabsf(fu) + fabsf(fd) > 0.f;
+  const tsdf_fov F = tsdf_fov_of(t);
+  // ---- the class-aware update: driven by the pixels (k_tsdf_integrate_pix) -- see the table at tsdf_pix_env ---------------
+  const tsdf_pix_mode mode = tsdf_pix_env().mode;
+  int rho_bits = 0;
+  const bool use_pix = mode != TSDF_PIX_WALK && (t->n_obs == 0 || mode != TSDF_PIX_FRESH_ONLY) &&
+                       tsdf_pix_applies(t, flags, im_w, F, &rho_bits);
   const bool fresh_volume = t->n_obs == 0;
   t->n_obs += 1;
   if (use_pix)
-    return tsdf_integrate_pix(t, color_im, depth_im, rem_im, im_h, im_w, obs_weight, fu, fd, 30 - px_bits, fresh_volume, stream);
-  if (im_w > t->cap_w) {
-    if (t->colmax) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(t->colmax);
-      t->colmax = nullptr;
-    }
-    LT_HIP(hipMalloc((void**)&t->colmax, (size_t)im_w * sizeof(float)));
-    t->cap_w = im_w;
-  }
-  if ((size_t)im_w * im_h > t->cap_dct) {
-    if (t->dct) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(t->dct);
-      t->dct = nullptr;
-      t->cap_dct = 0;
-    }
-    LT_HIP(hipMalloc((void**)&t->dct, (size_t)im_w * im_h * sizeof(float2)));
-    t->cap_dct = (size_t)im_w * im_h;
-  }
+    return tsdf_integrate_pix(t, color_im, depth_im, rem_im, im_h, im_w, obs_weight, F, rho_bits, fresh_volume, stream);
+  LT_CHECK(tsdf_grow(t->colmax, t->cap_w, (size_t)im_w, (size_t)im_w));
+  LT_CHECK(tsdf_grow(t->dct, t->cap_dct, (size_t)im_w * im_h, (size_t)im_w * im_h));
   const int n_cols = t->dim[0] * t->dim[1];
-  const col_geom G = tsdf_geom(t);
+  const col_geom G = tsdf_geom(t, F);
   // behind the table: one flag per chunk of 64 columns, then the walks' z ranges and the columns' rho^2
   const size_t n_flags = ((size_t)n_cols + 63) / 64 + 64;
   unsigned* colz = (unsigned*)(t->colinfo + n_cols + n_flags);
@@ -2068,32 +1817,24 @@ extern "C" int lt_tsdf_integrate_dev(lt_tsdf* t, const float* color_im, const fl
   hipLaunchKernelGGL(k_tsdf_columns, dim3((n_cols + 255) / 256), dim3(256), 0, stream, t->dim[0], t->dim[1], t->origin[0],
                      t->origin[1], t->voxel_size, im_w, t->trunc_margin, t->colmax, t->colinfo, t->colinfo + n_cols, G,
                      t->dim[2], colz, colrho2);
-  // sine thresholds of the conservative field-of-view test: 1e-5 beyond the limits (asinf is good to ~1e-7)
-  const float su = (float)(sin((double)fu) + 1e-5), sd = (float)(sin((double)fd) - 1e-5);
   static const int env_blocks = []() { const char* e = getenv("LIDARHIP_TSDF_BLOCKS"); return e ? atoi(e) : 0; }();
   const unsigned nbc = (unsigned)min((n_cols + 63) / 64, env_blocks > 0 ? env_blocks : (1 << 20));  // a chunk of 64 columns each
   // debug (LIDARHIP_DEBUG_TSDF=1, tools/tsdf_wave_times.py): start / duration of every wave at 100 MHz
   static const bool want_dbg = getenv("LIDARHIP_DEBUG_TSDF") != nullptr;
   if (want_dbg && !g_tsdf_dbg) LT_HIP(hipMalloc((void**)&g_tsdf_dbg, (size_t)LT_TSDF_DBG_WAVES * 2 * sizeof(unsigned long long)));
   unsigned long long* dbg = g_tsdf_dbg;
-  const float fov_abs = fabsf(fu) + fabsf(fd);
+  const float fov_abs = fabsf(F.fu) + fabsf(F.fd);
   // the band test's pitch polynomial is good to 1e-5 rad for |sin| <= 0.5 and its row choice has +-0.25 row of slack: it is
   // used for fields of view inside +-30 degrees with rows at least 2e-4 rad apart (every spinning LiDAR); otherwise
   // kA = NaN switches it off and every voxel takes the exact evaluation
-  const bool band_ok = fabsf(su) <= 0.5f && fabsf(sd) <= 0.5f && fov_abs / (float)im_h >= 2e-4f;
-  const float kA = band_ok ? -(float)im_h / fov_abs : NAN, kB = (float)im_h * (1.0f - fabsf(fd) / fov_abs);
-  if (flags & LT_TSDF_MERGE)
-    hipLaunchKernelGGL(k_tsdf_integrate_cols<true>, dim3(nbc), dim3(256), 0, stream, t->tsdf, t->weight, t->color, t->rem,
-                       t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2], t->voxel_size, im_h, im_w,
-                       t->trunc_margin, obs_weight, fu, fd, su, sd, color_im, depth_im, rem_im, t->colinfo, t->col_epoch,
-                       t->epoch, G, t->bits, (t->dim[2] + 63) / 64, t->col_zw, t->dct, kA, kB, t->colinfo + n_cols, colz, colrho2, t->all_dirty, dbg,
-                       t->chunk_epoch);
-  else
-    hipLaunchKernelGGL(k_tsdf_integrate_cols<false>, dim3(nbc), dim3(256), 0, stream, t->tsdf, t->weight, t->color, t->rem,
-                       t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2], t->voxel_size, im_h, im_w,
-                       t->trunc_margin, obs_weight, fu, fd, su, sd, color_im, depth_im, rem_im, t->colinfo, t->col_epoch,
-                       t->epoch, G, t->bits, (t->dim[2] + 63) / 64, t->col_zw, t->dct, kA, kB, t->colinfo + n_cols, colz, colrho2, t->all_dirty, dbg,
-                       t->chunk_epoch);
+  const bool band_ok = fabsf(F.su) <= 0.5f && fabsf(F.sd) <= 0.5f && fov_abs / (float)im_h >= 2e-4f;
+  const float kA = band_ok ? -(float)im_h / fov_abs : NAN, kB = (float)im_h * (1.0f - fabsf(F.fd) / fov_abs);
+#define LT_COLS_ARGS                                                                                                     \
+  LT_VOL_ARGS, LT_VIEW_ARGS, color_im, depth_im, rem_im, t->colinfo, t->col_epoch, t->epoch, G, t->bits,                 \
+      (t->dim[2] + 63) / 64, t->col_zw, t->dct, kA, kB, t->colinfo + n_cols, colz, colrho2, t->all_dirty, dbg, t->chunk_epoch
+  if (flags & LT_TSDF_MERGE) hipLaunchKernelGGL(k_tsdf_integrate_cols<true>, dim3(nbc), dim3(256), 0, stream, LT_COLS_ARGS);
+  else hipLaunchKernelGGL(k_tsdf_integrate_cols<false>, dim3(nbc), dim3(256), 0, stream, LT_COLS_ARGS);
+#undef LT_COLS_ARGS
   LT_HIP(hipGetLastError());
   return LT_OK;
 }
@@ -2113,56 +1854,33 @@ extern "C" int lt_tsdf_integrate_multi_dev(lt_tsdf* t, int n_obs, const float* c
     }
   hipStream_t stream = (hipStream_t)stream_;
   LT_HIP(hipSetDevice(t->device));
-  const float fu = (float)((double)(float)t->fov_up_deg * LT_PI_D / 180.0);
-  const float fd = (float)((double)(float)t->fov_down_deg * LT_PI_D / 180.0);
-  static const bool pix_off = []() { const char* e = getenv("LIDARHIP_TSDF_PIX"); return e && e[0] != 0 && strcmp(e, "2") != 0; }();
-  static const bool multi_off = []() { const char* e = getenv("LIDARHIP_TSDF_MULTI"); return e && strcmp(e, "0") == 0; }();
-  const bool tan_ok = fabs((double)fu) < 1.39 && fabs((double)fd) < 1.39;
-  int px_bits = 1;
-  while ((1 << px_bits) < im_w) ++px_bits;
+  const tsdf_fov F = tsdf_fov_of(t);
   // the fused pass: the class-aware update of a FRESH volume, under the conditions of the pixel-centric integrate
-  const bool fuse = !pix_off && !multi_off && (flags & LT_TSDF_MERGE) && !(flags & LT_TSDF_HOST_MODE) && t->n_obs == 0 && !t->all_dirty && tan_ok &&
-                    30 - px_bits >= 12 && fabsf(fu) + fabsf(fd) > 0.f && n_obs >= 2;
+  int rho_bits = 0;
+  const bool fuse = tsdf_pix_env().fuse && !(flags & LT_TSDF_HOST_MODE) && t->n_obs == 0 && n_obs >= 2 &&
+                    tsdf_pix_applies(t, flags, im_w, F, &rho_bits);
   int done = 0;
   if (fuse) {
     const int n = n_obs < LT_TSDF_MULTI_MAX ? n_obs : LT_TSDF_MULTI_MAX;
-    const int rho_bits = 30 - px_bits;
-    if (t->wd_w != im_w || t->wd_rho_bits != rho_bits) LT_CHECK(tsdf_wedge_build(t, im_w, rho_bits, stream));
-    if (t->rowtab_for_h != im_h || !t->rowtab) {
-      t->rowtab_for_h = 0;
-      LT_CHECK(tsdf_rowtab(t, im_h, fu, fd, stream));
-      t->rowtab_for_h = im_h;
-    }
+    LT_CHECK(tsdf_pix_tables(t, im_h, im_w, rho_bits, F, stream));
     const size_t n_pix = (size_t)im_h * im_w;
-    if ((size_t)n * n_pix > t->cap_obs4) {
-      if (t->obs4) { LT_HIP(hipStreamSynchronize(stream)); (void)hipFree(t->obs4); t->obs4 = nullptr; t->cap_obs4 = 0; }
-      LT_HIP(hipMalloc((void**)&t->obs4, (size_t)LT_TSDF_MULTI_MAX * n_pix * sizeof(float4)));
-      t->cap_obs4 = (size_t)LT_TSDF_MULTI_MAX * n_pix;
-    }
+    LT_CHECK(tsdf_grow(t->obs4, t->cap_obs4, (size_t)n * n_pix, (size_t)LT_TSDF_MULTI_MAX * n_pix));
     tsdf_obs_ptrs O;
     for (int k = 0; k < LT_TSDF_MULTI_MAX; ++k) {
       const int q = k < n ? k : 0;
       O.color[k] = color_ims[q]; O.depth[k] = depth_ims[q]; O.rem[k] = rem_ims[q];
     }
     hipLaunchKernelGGL(k_tsdf_dct4, dim3((unsigned)((n * n_pix + 255) / 256)), dim3(256), 0, stream, O, n, im_h, im_w, t->obs4);
-    const float su = (float)(sin((double)fu) + 1e-5), sd = (float)(sin((double)fd) - 1e-5);
     const int words_z = (t->dim[2] + 63) / 64;
-    static const int env_wgs = []() { const char* e = getenv("LIDARHIP_PIX_WGS"); return e ? atoi(e) : -1; }();
-    const int res_wgs = lt_cu_count(t->device) * 5;
-    const int groups = (int)((n_pix + 63) / 64);
-    const unsigned nb = (unsigned)min(groups, env_wgs > 0 ? env_wgs : (env_wgs == 0 ? (1 << 20) : res_wgs));
-    hipLaunchKernelGGL((k_tsdf_integrate_pix_multi<false>), dim3(nb), dim3(256), 0, stream, t->tsdf, t->weight, t->color, t->rem,
-                       t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2], t->voxel_size,
-                       1.0f / t->voxel_size, im_h, im_w, t->trunc_margin, obs_weight, fu, fd, su, sd, (const float4*)t->obs4, n,
-                       t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, t->col_zw, t->chunk_epoch, t->rowtab, t->wd_start,
-                       t->wd_ent, t->wd_key, t->wd_rho_bits, t->wd_qscale, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL((k_tsdf_integrate_pix_multi<false>), dim3(tsdf_pix_grid(t, n_pix, LT_PIX_MULTI_WPE)), dim3(256), 0, stream,
+                       LT_VOL_ARGS, 1.0f / t->voxel_size, LT_VIEW_ARGS, (const float4*)t->obs4, n, t->wd_px, t->col_epoch,
+                       t->epoch, t->bits, words_z, t->col_zw, t->chunk_epoch, t->rowtab, t->wd_start, t->wd_ent, t->wd_key,
+                       t->wd_rho_bits, t->wd_qscale, (unsigned long long*)nullptr);
     if (t->wd_n_quirk > 0) {
       const long long nv = (long long)t->wd_n_quirk * t->dim[2];
-      hipLaunchKernelGGL(k_tsdf_integrate_quirk_multi, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, t->tsdf,
-                         t->weight, t->color, t->rem, t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2],
-                         t->voxel_size, im_h, im_w, t->trunc_margin, obs_weight, fu, fd, su, sd, (const float4*)t->obs4, n,
-                         t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, t->col_zw, t->chunk_epoch, t->wd_qcols,
-                         t->wd_n_quirk);
+      hipLaunchKernelGGL(k_tsdf_integrate_quirk_multi, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, LT_VOL_ARGS,
+                         LT_VIEW_ARGS, (const float4*)t->obs4, n, t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, t->col_zw,
+                         t->chunk_epoch, t->wd_qcols, t->wd_n_quirk);
     }
     LT_HIP(hipGetLastError());
     t->n_obs += n;

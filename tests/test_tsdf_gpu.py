@@ -241,7 +241,8 @@ np.savez(sys.argv[1], **{f"{k}{i}": a for k, v in out.items() for i, a in enumer
 @pytest.mark.parametrize("merge,fu,fd,voxel,hw", [(True, 10.0, -25.0, 0.05, (32, 256)), (False, 10.0, -25.0, 0.05, (32, 256)),
                                                    (True, 40.0, -50.0, 0.05, (32, 256)), (True, 2.0, -24.8, 0.05, (32, 256)),
                                                    (True, 10.0, -25.0, 0.25, (32, 256)), (False, 10.0, -25.0, 0.25, (32, 256)),
-                                                   (True, 15.0, -20.0, 0.25, (25, 301)), (True, 5.0, -30.0, 0.25, (70, 97))])
+                                                   (True, 15.0, -20.0, 0.25, (25, 301)), (True, 5.0, -30.0, 0.25, (70, 97)),
+                                                   (True, 10.0, -25.0, 0.05, (32, 64))])
 def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge, fu, fd, voxel, hw):
     """The work-saving integrate (per-column image column and dead-column test, conservative sine test, dirty-column
     reset) against the plain one-thread-per-voxel restatement of the reference kernel (oracle/lt_tsdf_dense.hip: an ORACLE
@@ -257,7 +258,12 @@ def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge,
     columns holding only the reference's "no data" depth -1 -- with voxel_size 0.25 the truncation margin is 1.25 m, so the
     voxels within 0.25 m of the sensor ARE written through such pixels (depth_diff = -1 - depth >= -trunc_margin).  Image
     shapes 25 x 301 and 70 x 97: the pixel kernel's workgroups of 64 pixels then straddle image columns, and the wedge table
-    is built for a width that is not a power of two."""
+    is built for a width that is not a power of two.  Image 32 x 64 at voxel 0.05 (600 x 600 columns): a wedge is a
+    5.6 degree sector (2 pi / 64 = 0.098 rad) that holds at least 0.5 * 0.098 * 15^2 / 0.0025 ~ 4400 columns, and a group
+    of 64 pixels spans two image columns -- every workgroup's search range exceeds LT_PIX_STAGE (3840) and takes the
+    unstaged search in global memory; and its pairs fall on two wedges (a colour-0 pixel at 9 m alone on 0.5 * 0.098 * 81 /
+    0.0025 ~ 1600 entries): more than LT_PIX_AGG (1024) table entries, so the workgroups mark the columns' written ranges
+    directly (col_mark_written) instead of merging them in LDS."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -294,7 +300,8 @@ def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge,
 
 
 @pytest.mark.parametrize("fu,fd,voxel,hw,n_obs", [(10.0, -25.0, 0.05, (32, 256), 4), (5.0, -30.0, 0.25, (70, 97), 3),
-                                                    (10.0, -25.0, 0.05, (32, 256), 11), (40.0, -50.0, 0.05, (32, 256), 2)])
+                                                    (10.0, -25.0, 0.05, (32, 256), 11), (40.0, -50.0, 0.05, (32, 256), 2),
+                                                    (10.0, -25.0, 0.05, (32, 64), 3), (5.0, -30.0, 0.25, (70, 97), 9)])
 def test_fused_observations_equal_one_integrate_per_observation(fu, fd, voxel, hw, n_obs):
     """lt_tsdf_integrate_multi_dev -- all observations of a fresh volume in ONE pixel pass, the updates applied in order on
     the voxel's state in registers -- against one lt_tsdf_integrate_dev per observation (itself bit-identical to the
@@ -303,7 +310,11 @@ def test_fused_observations_equal_one_integrate_per_observation(fu, fd, voxel, h
     neighbouring scans do -- centimetre noise, holes, other labels (the "other class" branch), label 0 (the fresh volume's
     own class: long runs), no-data columns, NaN / infinite pixels -- plus one observation whose surface lies a metre in front
     of the others' and one a metre behind (bands that do not overlap).  11 observations: more than one fused pass holds
-    (8), the rest take the single-observation path on the then non-fresh volume."""
+    (8), the rest take the single-observation path on the then non-fresh volume; 9: one full fused pass of exactly
+    LT_TSDF_MULTI_MAX, then one observation through zw_snap.  Image 32 x 64 at voxel 0.05: a wedge of the 600 x 600 columns
+    is a 5.6 degree sector of at least 0.5 * 0.098 * 15^2 / 0.0025 ~ 4400 columns and a group of 64 pixels spans two image
+    columns, so the fused kernel's searches are unstaged (more than LT_PIX_STAGE = 3840 quanta) and a workgroup's pairs, on
+    two wedges, span more than LT_PIX_AGG = 1024 entries (written ranges marked directly), as in the test above."""
     import torch
     from lidar_transfer_amd.fusion import TSDFVolume
     H, W = hw
