@@ -1288,3 +1288,11 @@ extern "C" int lt_debug_scatter_large(lt_scene* s, int* out, int n) {
   LT_HIP(hipMemcpy(out, s->sc_large, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   return LT_OK;
 }
+// the bin grid a ray set was given (prm_host): nb = (nb_az, nb_el), p = (az_scale, az_off, el_lo, el_scale, dev_az, dev_el)
+extern "C" int lt_debug_rayset_params(lt_rayset* r, int* nb, float* p) {
+  if (!r || !nb || !p) return LT_ERR_INVALID_ARG;
+  const rs_params& P = r->prm_host;
+  nb[0] = P.nb_az; nb[1] = P.nb_el;
+  p[0] = P.az_scale; p[1] = P.az_off; p[2] = P.el_lo; p[3] = P.el_scale; p[4] = P.dev_az; p[5] = P.dev_el;
+  return LT_OK;
+}
