@@ -227,8 +227,27 @@ int lt_create_rays_dev(double fov_up, double fov_down, int H, int W, float* rays
  * component, each product and sum rounded on its own, and cast to float32 last.  Asynchronous on `stream`. */
 int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, int W, const double* rot, float* rays, void* stream);
 
+/* The rays of a sensor with a BEAM TABLE: lt_create_rays_dev's expressions with beams_deg[h] (HOST, [H] float64, degrees,
+ * row 0 first -- descending, so that row 0 is the highest beam as fov_up is above) in place of the evenly spaced angle of
+ * row h: p = pi/2 - beams_deg[h] / 180 * pi, then the same three products; with `rot` (HOST [9], NULL = none)
+ * lt_create_rays_pose_dev's rotation in float64 before the one cast to float32.  A table equal to
+ * linspace(fov_up, fov_down, H) gives lt_create_rays_dev's / lt_create_rays_pose_dev's rays bit for bit.  The table is
+ * copied to the device once per call and the call waits for `stream`: it is made once per sensor model. */
+int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, const double* rot, float* rays, void* stream);
+
 #define LT_PROJ_REMOVE 1u /* `remove=True`: drop depth == 0 and points whose proj_y is outside [0, 1]   */
 #define LT_PROJ_NEW 2u    /* do_range_projection_new: depth == 0 is always dropped (laserscan.py:306-309) */
+/* LT_PROJ_BEAM_ROWS -- the image rows are the beams of a TABLE (a target sensor whose beams are not evenly spaced), defined
+ * together with LT_PROJ_NEW | LT_PROJ_REMOVE only (any other combination: LT_ERR_INVALID_ARG), for lt_range_projection_dev,
+ * lt_range_projection and lt_range_projection_batch_dev.  `beam_angles` then carries Brad[H] (the table in radians,
+ * descending: row 0 is the highest beam) followed by halfw[H] (half the smaller gap to the neighbouring beams in radians;
+ * the one existing gap for the first and the last row; unused for H == 1), and n_beams == H (at most 511).  Per point: the
+ * column as without the flag; the pitch q in the cloud's dtype (asin correctly rounded in either dtype), widened to float64; row = the first
+ * minimum of |q - Brad[k]|; the point is kept iff |q - Brad[row]| <= halfw[row] (H == 1: iff fov_down <= q <= fov_up in
+ * radians) -- a beam samples its own direction, not the gap beside it.  depth == 0 and NaN as without the flag; the z-min
+ * rule is the same.  proj_y is the row, proj_yf the winner's pitch in radians (the cloud's dtype), proj_x / proj_xf as
+ * without the flag; an EMPTY cell holds 0 in all four. */
+#define LT_PROJ_BEAM_ROWS 4u
 
 /*
  * lt_range_projection_dev -- point cloud -> H x W spherical image, closest point per cell (atomic
@@ -535,6 +554,14 @@ int lt_mergemesh_rerun_dev(lt_projector* projector, lt_tsdf* vol, lt_mesh* mesh,
 int lt_reverse_projection_dev(const float* range_img, const void* proj_x, const void* proj_y,
                               int coords_are_f64, double fov_up, double fov_down, int H, int W,
                               double* back_points, void* stream);
+
+/* The same for a sensor with a BEAM TABLE (what LT_PROJ_BEAM_ROWS projected): yaw = (proj_x / W * 2 - 1) * pi as above;
+ * the elevation e = Brad[proj_y] (proj_x / proj_y int32; Brad: DEVICE [H] float64, the table in radians) or -- with
+ * preserve_float -- the pitch image itself (proj_x and the pitch float64; Brad may be NULL); pitch = pi/2 - e; the point is
+ * depth * sin(pitch) * cos(-yaw), depth * sin(pitch) * sin(-yaw), depth * cos(pitch), multiplied left to right in
+ * float64.  One thread per cell, asynchronous on `stream`. */
+int lt_reverse_projection_beams_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
+                                    int preserve_float, const double* Brad, int H, int W, double* back_points, void* stream);
 
 /* Points into another frame: out[i] = float32(((m0*x + m1*y) + m2*z) + m3) per row of T, in float64 from the float32
  * point.  points / out [n,3] f32 DEVICE (out may be points), tri [n] i32 DEVICE or NULL: rows with tri < 0 (rays

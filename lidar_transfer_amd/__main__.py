@@ -4,7 +4,10 @@
 
 ``DATASET/config.yaml`` is the source sensor, ``--target`` the target sensor (default: the source), ``--config`` the approach
 YAML -- its ``transformation`` (16 numbers, ``x_target = T . x_source``) mounts the target sensor at a pose of its own: the
-output is then in the target's frame, no metrics are printed and every row of ``--log`` carries ``"mounted": true``.  The tool
+output is then in the target's frame, no metrics are printed and every row of ``--log`` carries ``"mounted": true``.  A
+target YAML with ``beam_model: table`` (config/vlp32c_table_1024.yaml) switches on the target's real beam geometry: rays and
+image rows at the angles of its ``beam_angles``; no metrics are printed and every row of ``--log`` carries
+``"beam_model": "table"``.  The tool
 is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
 ``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  A missing dataset, labels or output
 folder ends with a message and exit status 1."""
@@ -63,6 +66,8 @@ def main(argv=None):
     try:
         approach, source, target = load_approach(args.config), load_sensor(source_path), load_sensor(target_path)
         approach.mount()   # (a transformation that is not a rigid motion: said here, not half way into the run)
+        from .config import refuse_source_table
+        refuse_source_table(source)
     except Exception as e:  # noqa: BLE001  (a YAML that cannot be read: message and status, as the reference's quit())
         print(e)
         print("Error opening yaml file.")
@@ -83,6 +88,8 @@ def main(argv=None):
                     row = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in rec.items()}
                     if tr.mounted:
                         row["mounted"] = True
+                    if tr.beam_model != "linear":
+                        row["beam_model"] = tr.beam_model
                     log.write(json.dumps(row) + "\n")
             if log is not None:
                 log.write(json.dumps(dict(summary=tr.summary)) + "\n")

@@ -48,6 +48,19 @@ def beam_table(beam_angles):
     return beams.ctypes.data_as(C.c_void_p), len(beams), beams
 
 
+def beam_rows_table(table):
+    """``(pointer, H, array to keep alive)`` of a target sensor's beam TABLE (``SensorModel.beam_table()``, degrees,
+    descending) as ``LT_PROJ_BEAM_ROWS`` reads it: ``Brad`` followed by ``halfw`` (``config.beam_rows``), float64 [2 H].
+    A table that already is such a marshalled triple is returned as it is."""
+    if isinstance(table, tuple):
+        return table
+    import numpy as np
+
+    from .config import beam_rows
+    t = np.ascontiguousarray(np.concatenate(beam_rows(table)), dtype=np.float64)
+    return t.ctypes.data_as(C.c_void_p), len(t) // 2, t
+
+
 def origin3(origin):
     return (C.c_float * 3)(*[float(x) for x in origin])
 

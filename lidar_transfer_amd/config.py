@@ -13,6 +13,10 @@ Host logic only: what the files say is turned into the arguments of the device p
 ``RaySet``, ``TSDFVolume``, the scan index list).  ``beam_angles`` is sorted in place like the reference does and
 is ``None`` when absent; ``create_rays`` ignores it (``laserscan.py:1092-1119``), the projection uses it
 (``laserscan.py:233-238``).
+
+``beam_model: table`` (optional, default ``linear``) is this project's own key, for a TARGET sensor: its ``beam_angles`` are
+then the real elevation of every beam in degrees -- its rays leave at these angles and a point's image row is its nearest
+beam (:meth:`SensorModel.beam_table`).  Without the key ``beam_angles`` keeps the meaning above.
 """
 from __future__ import annotations
 
@@ -33,6 +37,7 @@ class SensorModel:
     fov_hor: float
     beam_angles: Optional[List[float]] = None
     raw: dict = field(default_factory=dict, repr=False)
+    beam_model: str = "linear"
 
     @property
     def H(self) -> int:
@@ -51,7 +56,50 @@ class SensorModel:
         """Host mirror of ``MultiSemLaserScan.create_rays(fov_up, fov_down, H, W)`` for this model:
         ``[H*W, 3]`` float32 (beam_angles are ignored there, as in the reference)."""
         from .laserscan import create_rays
-        return create_rays(self.fov_up, self.fov_down, self.H, self.W)
+        return create_rays(self.fov_up, self.fov_down, self.H, self.W, beam_table=self.beam_table())
+
+    def beam_table(self):
+        """``None`` for ``beam_model: linear``; for ``table`` the beams' elevations in degrees, float64 [H], sorted
+        descending -- row 0 is the highest beam, as ``create_rays``' row 0 is ``fov_up``.  ``ValueError`` unless there is
+        one angle per beam, all are finite with |angle| < 90, neighbours differ by at least 1e-6 degrees and every angle
+        lies in ``[fov_down, fov_up]`` (``mergemesh`` fuses only what the target's field of view holds, laserscan.py:952,
+        :968: a beam outside it would look at nothing)."""
+        if self.beam_model == "linear":
+            return None
+        if self.beam_model != "table":
+            raise ValueError(f"sensor {self.name!r}: beam_model {self.beam_model!r} (linear or table)")
+        try:
+            b = np.array(sorted((float(a) for a in (self.beam_angles or ())), reverse=True), dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"sensor {self.name!r}: beam_model table needs beam_angles, a list of numbers") from None
+        return check_beam_table(b, self.H, self.fov_up, self.fov_down, f"sensor {self.name!r}")
+
+
+def check_beam_table(b, H, fov_up, fov_down, who="beam table"):
+    """the conditions of :meth:`SensorModel.beam_table` on a descending float64 table; returns it"""
+    if b.ndim != 1 or len(b) != int(H):
+        raise ValueError(f"{who}: {b.size} beam_angles for {int(H)} beams")
+    if not np.all(np.isfinite(b)) or not np.all(np.abs(b) < 90.0):
+        raise ValueError(f"{who}: beam_angles must be finite and within (-90, 90) degrees")
+    if len(b) > 1 and not np.all(b[:-1] - b[1:] >= 1e-6):
+        raise ValueError(f"{who}: neighbouring beam_angles must differ by at least 1e-6 degrees")
+    if not np.all((b >= float(fov_down)) & (b <= float(fov_up))):
+        raise ValueError(f"{who}: every beam angle must lie in [fov_down, fov_up] = [{fov_down}, {fov_up}]")
+    return b
+
+
+def beam_rows(table):
+    """What the row rule of a beam table reads (``LT_PROJ_BEAM_ROWS``), float64, derived once: ``Brad = B / 180 * pi`` and
+    ``halfw[k]``, half the smaller of the gaps to the two neighbours in radians (the one existing gap for the first and the
+    last row; 0 and unused for H = 1)."""
+    B = np.asarray(table, dtype=np.float64)
+    Brad = B / 180.0 * np.pi
+    halfw = np.zeros_like(Brad)
+    if len(Brad) > 1:
+        gap = Brad[:-1] - Brad[1:]
+        halfw[0], halfw[-1] = gap[0] / 2, gap[-1] / 2
+        halfw[1:-1] = np.minimum(gap[:-1], gap[1:]) / 2
+    return Brad, halfw
 
 
 def _load_yaml(path_or_dict):
@@ -79,7 +127,17 @@ def load_sensor(path_or_dict) -> SensorModel:
         beam_angles.sort()
     except Exception:
         beam_angles = None
-    return SensorModel(name, fov_up, fov_down, beams, angle_res_hor, fov_hor, beam_angles, raw=cfg)
+    model = SensorModel(name, fov_up, fov_down, beams, angle_res_hor, fov_hor, beam_angles, raw=cfg,
+                        beam_model=str(cfg.get("beam_model", "linear")))
+    model.beam_table()   # (a table that cannot be used: said at load time)
+    return model
+
+
+def refuse_source_table(source):
+    """A table is a property of the TARGET: the TSDF kernel's pixel model of the source scan is the reference's linear one."""
+    if getattr(source, "beam_model", "linear") != "linear":
+        raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: beam_model {source.beam_model!r} is for target sensors "
+                         "only (the source scan is fused by the reference's evenly spaced pixel model)")
 
 
 @dataclass

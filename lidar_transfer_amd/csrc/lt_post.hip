@@ -47,6 +47,53 @@ extern "C" int lt_reverse_projection_dev(const float* range_img, const void* pro
   return LT_OK;
 }
 
+// ---- reverse projection of a sensor with a BEAM TABLE: the yaw as above, the elevation e = Brad[row] (or the winner's
+// pitch itself with `preserve_float`), pitch = pi / 2 - e, the three products multiplied left to right.  A row outside
+// the table (no caller makes one) reads its nearest end, never memory beside the table.
+template <typename P>
+__global__ __launch_bounds__(256) void k_reverse_beams(const float* __restrict__ range, const P* __restrict__ px,
+                                                       const P* __restrict__ py, int n, double W,
+                                                       const double* __restrict__ Brad, int H, int py_is_pitch,
+                                                       double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double depth = (double)range[i];
+  const double x = (double)px[i] / W;
+  const double yaw = (x * 2 - 1.0) * M_PI;
+  double e;
+  if (py_is_pitch) {
+    e = (double)py[i];
+  } else {
+    int r = (int)py[i];
+    r = r < 0 ? 0 : (r > H - 1 ? H - 1 : r);
+    e = Brad[r];
+  }
+  const double pitch = M_PI / 2 - e;
+  const double sp = sin(pitch);
+  out[3 * (size_t)i] = depth * sp * cos(-yaw);
+  out[3 * (size_t)i + 1] = depth * sp * sin(-yaw);
+  out[3 * (size_t)i + 2] = depth * cos(pitch);
+}
+
+extern "C" int lt_reverse_projection_beams_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
+                                               int preserve_float, const double* Brad, int H, int W, double* back_points,
+                                               void* stream) {
+  if (H <= 0 || W <= 0 || !range_img || !proj_x || !proj_y_or_pitch || !back_points || (!preserve_float && !Brad)) {
+    lt_set_error("lt_reverse_projection_beams_dev: invalid argument");
+    return LT_ERR_INVALID_ARG;
+  }
+  const int n = H * W;
+  hipStream_t st = (hipStream_t)stream;
+  if (preserve_float)
+    hipLaunchKernelGGL(k_reverse_beams<double>, dim3((n + 255) / 256), dim3(256), 0, st, range_img, (const double*)proj_x,
+                       (const double*)proj_y_or_pitch, n, (double)W, Brad, H, 1, back_points);
+  else
+    hipLaunchKernelGGL(k_reverse_beams<int>, dim3((n + 255) / 256), dim3(256), 0, st, range_img, (const int*)proj_x,
+                       (const int*)proj_y_or_pitch, n, (double)W, Brad, H, 0, back_points);
+  LT_HIP(hipGetLastError());
+  return LT_OK;
+}
+
 // ---- rendered points into another frame (the target sensor's, when it is mounted at a pose of its own) ----------
 // float32 point widened to float64, ((m0 * x + m1 * y) + m2 * z) + m3 per row of T (lt_ingest_scans_dev's row form; every
 // product and sum rounded on its own), rounded to float32.  Rows with tri < 0 (misses) are copied as they are: (0, 0, 0)

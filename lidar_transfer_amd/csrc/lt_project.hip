@@ -25,8 +25,9 @@
 
 #define LT_EMPTY_IDX 0x7F7F7F7F  // hipMemset(0x7F) pattern: larger than any point index
 
-// pass 1: project, z-min of the depth bits, per-workgroup count of kept points
-template <typename T>
+// pass 1: project, z-min of the depth bits, per-workgroup count of kept points (BEAMS: the rows of a beam table,
+// project_point_beams; `beams` is then its table)
+template <typename T, int BEAMS = 0>
 __global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int n, T pi_t, T abs_fov_down, T fov,
                                                  int H, int W, const double* __restrict__ beams, int n_beams,
                                                  int drop_zero, int drop_outside, int round_key,
@@ -38,8 +39,10 @@ __global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int 
   const int i = blockIdx.x * 256 + threadIdx.x;
   bool keep = false;
   if (i < n) {
-    const proj_out<T> o = project_point<T>(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], pi_t,
-                                           abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
+    const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    const proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
+                                : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
+                                                   drop_outside);
     cell[i] = o.cell;
     depth_d[i] = (double)o.depth;
     xf[i] = o.xf;
@@ -225,6 +228,72 @@ extern "C" int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, in
   return LT_OK;
 }
 
+// ---- create_rays of a sensor with a BEAM TABLE: k_create_rays' expressions with the table's angle (degrees) of row h in
+// place of the linspace term, and -- `posed` -- k_create_rays_pose's rotation in float64 before the one cast to float32.
+// A kernel of its own: the two above stay what they were.
+__global__ __launch_bounds__(256) void k_create_rays_beams(const double* __restrict__ beams_deg, int H, int W, lt_rot9 R,
+                                                           int posed, float* __restrict__ rays) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= H * W) return;
+  const int h = idx / W, w = idx - h * W;
+  double yaw_deg = W > 1 ? (w == W - 1 ? 360.0 : 0.0 + w * (360.0 / (W - 1))) : 0.0;
+  yaw_deg += 180.0;
+  if (yaw_deg > 360.0) yaw_deg -= 360.0;
+  const double yaw = yaw_deg / 180. * M_PI;
+  const double pd = beams_deg[h];
+  const double p = M_PI / 2 - pd / 180. * M_PI;
+  const double sp = sin(p);
+  const double x = sp * cos(-yaw), y = sp * sin(-yaw), z = cos(p) * 1.0;
+  if (posed) {
+    rays[3 * (size_t)idx] = (float)((R.m[0] * x + R.m[1] * y) + R.m[2] * z);
+    rays[3 * (size_t)idx + 1] = (float)((R.m[3] * x + R.m[4] * y) + R.m[5] * z);
+    rays[3 * (size_t)idx + 2] = (float)((R.m[6] * x + R.m[7] * y) + R.m[8] * z);
+  } else {
+    rays[3 * (size_t)idx] = (float)x;
+    rays[3 * (size_t)idx + 1] = (float)y;
+    rays[3 * (size_t)idx + 2] = (float)z;
+  }
+}
+
+extern "C" int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, const double* rot, float* rays,
+                                        void* stream) {
+  if (!beams_deg || H <= 0 || W <= 0 || !rays) {
+    lt_set_error("lt_create_rays_beams_dev: invalid argument (H=%d W=%d)", H, W);
+    return LT_ERR_INVALID_ARG;
+  }
+  lt_rot9 R;
+  for (int k = 0; k < 9; ++k) R.m[k] = rot ? rot[k] : (k % 4 == 0 ? 1.0 : 0.0);
+  // once per sensor model: the table goes to the device in a buffer of this call, which waits for its kernel
+  double* d_beams = nullptr;
+  LT_HIP(hipMalloc((void**)&d_beams, (size_t)H * sizeof(double)));
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemcpyAsync(d_beams, beams_deg, (size_t)H * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_create_rays_beams, dim3((H * W + 255) / 256), dim3(256), 0, st, (const double*)d_beams, H, W, R,
+                       rot ? 1 : 0, rays);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_beams);
+  LT_HIP(e);
+  return LT_OK;
+}
+
+// LT_PROJ_BEAM_ROWS: the caller's table (Brad[H], halfw[H]) checked and completed by the field of view in radians, which
+// the H == 1 keep rule reads: tab[2 * H + 2].  Returns the number of doubles, 0 when the arguments do not fit the flag.
+static int beam_rows_table(const char* who, const double* beam_angles, int n_beams, unsigned flags, int H, double fov_up_deg,
+                           double fov_down_deg, double* tab) {
+  if (flags != (LT_PROJ_BEAM_ROWS | LT_PROJ_NEW | LT_PROJ_REMOVE) || n_beams != H || !beam_angles || 2 * H + 2 > 1024) {
+    lt_set_error("%s: LT_PROJ_BEAM_ROWS goes with LT_PROJ_NEW | LT_PROJ_REMOVE only (flags=%u) and a table of n_beams == H "
+                 "<= 511 rows (n_beams=%d H=%d)", who, flags, n_beams, H);
+    return 0;
+  }
+  memcpy(tab, beam_angles, 2 * (size_t)H * sizeof(double));
+  tab[2 * H] = fov_down_deg / 180.0 * M_PI;
+  tab[2 * H + 1] = fov_up_deg / 180.0 * M_PI;
+  return 2 * H + 2;
+}
+
 // ---- host orchestration -------------------------------------------------------------------------------------
 namespace {
 struct proj_ws {
@@ -294,10 +363,15 @@ int run_projection(proj_ws& w, const T* pts, const float* rem, const unsigned* l
   w.armed = false;
   const int round_key = (flags & LT_PROJ_NEW) ? 1 : 0;
   if (n > 0) {
-    hipLaunchKernelGGL(k_project<T>, dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
-                       (const double*)w.beams, n_beams, (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW)) ? 1 : 0,
-                       (flags & LT_PROJ_REMOVE) ? 1 : 0, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
-                       w.blockcount);
+    if (flags & LT_PROJ_BEAM_ROWS)
+      hipLaunchKernelGGL((k_project<T, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
+                         (const double*)w.beams, n_beams, 1, 1, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
+                         w.blockcount);
+    else
+      hipLaunchKernelGGL(k_project<T>, dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
+                         (const double*)w.beams, n_beams, (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW)) ? 1 : 0,
+                         (flags & LT_PROJ_REMOVE) ? 1 : 0, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
+                         w.blockcount);
     hipLaunchKernelGGL(k_assign<T>, dim3(nb), dim3(256), 0, st, pts, rem, label, n, W, (const int*)w.cell,
                        (const double*)w.depth_d, (const T*)w.xf, (const T*)w.yf,
                        (const unsigned long long*)w.cellmin, w.blockcount, round_key, w.idxmin,
@@ -333,12 +407,20 @@ extern "C" int lt_range_projection_dev(const void* points, int is_f64, const flo
     lt_set_error("lt_range_projection: invalid argument (n=%d H=%d W=%d n_beams=%d)", n, H, W, n_beams);
     return LT_ERR_INVALID_ARG;
   }
+  double tab[1024];
+  int n_tab = 0;
+  if (flags & LT_PROJ_BEAM_ROWS) {
+    n_tab = beam_rows_table("lt_range_projection", beam_angles, n_beams, flags, H, fov_up, fov_down, tab);
+    if (!n_tab) return LT_ERR_INVALID_ARG;
+  }
   std::lock_guard<std::mutex> lock(g_pmu);
   int dev = 0;
   LT_HIP(hipGetDevice(&dev));
   LT_CHECK(pws_reserve(g_pws, dev, (size_t)n, (size_t)H * W));
   hipStream_t st = (hipStream_t)stream;
-  if (n_beams > 0)
+  if (n_tab > 0)  // (run_projection waits for the stream before `tab` goes out of scope)
+    LT_HIP(hipMemcpyAsync(g_pws.beams, tab, n_tab * sizeof(double), hipMemcpyHostToDevice, st));
+  else if (n_beams > 0)
     LT_HIP(hipMemcpyAsync(g_pws.beams, beam_angles, n_beams * sizeof(double), hipMemcpyHostToDevice, st));
   if (is_f64)
     return run_projection<double>(g_pws, (const double*)points, rem, label, n, fov_up, fov_down, H, W, n_beams, flags,
@@ -406,7 +488,8 @@ __device__ __forceinline__ double pb_unord(unsigned long long k) {
 }
 
 // MODE 0: the single-key variants (NEW on any dtype, OLD on float32).  MODE 1: OLD on float64 -- depth minimum only.
-template <typename T, int MODE>
+// BEAMS: the rows of a beam table (project_point_beams; `beams` is then its table), MODE 0 only.
+template <typename T, int MODE, int BEAMS = 0>
 __global__ __launch_bounds__(256) void k_pb_project(pb_args A, T pi_t, T abs_fov_down, T fov, int H, int W,
                                                     const double* __restrict__ beams, int n_beams, int drop_zero,
                                                     int drop_outside) {
@@ -416,8 +499,10 @@ __global__ __launch_bounds__(256) void k_pb_project(pb_args A, T pi_t, T abs_fov
   bool keep = false;
   if (i < c.n) {
     const T* pts = (const T*)c.pts;
-    const proj_out<T> o = project_point<T>(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], pi_t,
-                                           abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
+    const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    const proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
+                                : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
+                                                   drop_outside);
     keep = o.cell >= 0;
     if (keep) {
       if (MODE == 0) atomicMin(&c.key[o.cell], pb_key<T>(o.depth, i));
@@ -542,7 +627,7 @@ __global__ __launch_bounds__(64) void k_pb_bnds(pb_args A) {
   if (c.bacc) pb_fold_bounds(c, threadIdx.x);
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, int BEAMS = 0>
 __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cloud, T pi_t, T abs_fov_down, T fov, int H,
                                                     int W, const double* __restrict__ beams, int n_beams, int drop_zero,
                                                     int drop_outside, const float* __restrict__ lut, int lut_len,
@@ -557,15 +642,17 @@ __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cl
   const bool has = key != LT_PB_EMPTY;
   const T* pts = (const T*)c.pts;
   const bool want_xy = c.px_img || c.py_img || c.xf_img || c.yf_img;
-  // an empty cell's pixel coordinates are those of the LAST kept point: numpy's index -1 (laserscan.py:384-388)
-  int i = has ? pb_key_index(key) : ((want_xy && have_prefix) ? c.meta[1] : -1);
+  // an empty cell's pixel coordinates are those of the LAST kept point: numpy's index -1 (laserscan.py:384-388); with a beam
+  // table they are 0
+  int i = has ? pb_key_index(key) : ((!BEAMS && want_xy && have_prefix) ? c.meta[1] : -1);
   T x = (T)0, y = (T)0, z = (T)0;
   proj_out<T> o;
   o.depth = (T)0; o.xf = (T)0; o.yf = (T)0; o.px = 0; o.py = 0; o.cell = -1;
   if (i >= 0) {
     x = pts[3 * (size_t)i]; y = pts[3 * (size_t)i + 1]; z = pts[3 * (size_t)i + 2];
     if (has ? (want_xy || c.range_img) : true)
-      o = project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
+      o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
+                : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
   }
   int k = -1;
   if (has && have_prefix) k = c.wprefix[i >> 6] + __popcll(c.keep[i >> 6] & ((1ull << (i & 63)) - 1ull));
@@ -662,8 +749,12 @@ int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool nee
   const double fov = fabs(fd) + fabs(fu);
   const int drop_zero = (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW)) ? 1 : 0, drop_outside = (flags & LT_PROJ_REMOVE) ? 1 : 0;
   const int cells = H * W, bpc = (cells + 255) / 256;
+  const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0;  // (never with old_f64: the flag goes with LT_PROJ_NEW)
   if (total_blocks > 0) {
-    if (old_f64) {
+    if (rows) {
+      hipLaunchKernelGGL((k_pb_project<T, 0, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
+                         (const double*)p->beams, n_beams, drop_zero, drop_outside);
+    } else if (old_f64) {
       hipLaunchKernelGGL((k_pb_project<T, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
                          (const double*)p->beams, n_beams, drop_zero, drop_outside);
       hipLaunchKernelGGL(k_pb_assign, dim3(total_blocks), dim3(256), 0, st, A, M_PI, fabs(fd), fov, H, W,
@@ -675,7 +766,11 @@ int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool nee
   }
   if (need_prefix) hipLaunchKernelGGL(k_pb_prefix, dim3(A.n_clouds), dim3(256), 0, st, A);
   else if (bnds_only) hipLaunchKernelGGL(k_pb_bnds, dim3(A.n_clouds), dim3(64), 0, st, A);
-  if (old_f64)
+  if (rows)
+    hipLaunchKernelGGL((k_pb_resolve<T, 0, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd), (T)fov,
+                       H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init, rem_init,
+                       xyz_init, need_prefix ? 1 : 0);
+  else if (old_f64)
     hipLaunchKernelGGL((k_pb_resolve<T, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd), (T)fov,
                        H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init, rem_init,
                        xyz_init, need_prefix ? 1 : 0);
@@ -739,6 +834,12 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
       (n_beams > 0 && !beam_angles)) {
     lt_set_error("lt_range_projection_batch_dev: invalid argument (n_clouds=%d H=%d W=%d n_beams=%d)", n_clouds, H, W, n_beams);
     return LT_ERR_INVALID_ARG;
+  }
+  double tab[1024];
+  if (flags & LT_PROJ_BEAM_ROWS) {  // from here on `beam_angles` / `n_beams` are the completed table
+    n_beams = beam_rows_table("lt_range_projection_batch_dev", beam_angles, n_beams, flags, H, fov_up, fov_down, tab);
+    if (!n_beams) return LT_ERR_INVALID_ARG;
+    beam_angles = tab;
   }
   size_t n_max = 0;
   for (int k = 0; k < n_clouds; ++k) {

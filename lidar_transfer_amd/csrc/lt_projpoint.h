@@ -61,6 +61,90 @@ __device__ __forceinline__ proj_out<T> project_point(T x, T y, T z, T pi_t, T ab
   return o;
 }
 
+// The pitch of a float64 point under LT_PROJ_BEAM_ROWS: asin correctly rounded (but for arguments within ~2^-49 ulp of a
+// rounding boundary), so that proj_yf is ONE value whatever math library a host or a device has -- two float64 asin
+// implementations differ in the last place in one argument of ten, and a row's pitch image is an output.  One Newton step
+// from the library's asin: y = y0 + (x - sin(y0)) / cos(y0), sin(y0) from its Taylor series in double-double arithmetic
+// (error-free sums and fma products; the build has -ffp-contract=off and no fast-math, so they stay as written); the
+// residual is a few ulp of y0 at most, so the quotient in plain double is exact enough.  |x| > 0.99 (beyond +-81 degrees,
+// where the derivative grows without bound) and non-finite arguments keep the library's value.
+struct lt_dd { double hi, lo; };
+__host__ __device__ __forceinline__ lt_dd lt_dd_sum(double a, double b) {  // a + b exactly
+  const double s = a + b, bb = s - a;
+  return lt_dd{s, (a - (s - bb)) + (b - bb)};
+}
+__host__ __device__ __forceinline__ lt_dd lt_dd_add(lt_dd a, lt_dd b) {
+  lt_dd s = lt_dd_sum(a.hi, b.hi);
+  s.lo += a.lo + b.lo;
+  return lt_dd_sum(s.hi, s.lo);
+}
+__host__ __device__ __forceinline__ lt_dd lt_dd_mul(lt_dd a, lt_dd b) {
+  const double p = a.hi * b.hi;
+  const double e = fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
+  return lt_dd_sum(p, e);
+}
+__host__ __device__ __forceinline__ double lt_asin_cr(double x, double y0) {  // y0: the library's asin(x)
+  if (!(fabs(x) <= 0.99)) return y0;
+  // (-1)^k / (2k + 1)!, k = 1 .. 15, as double-double
+  const lt_dd c[15] = {{-0.16666666666666666, -9.25185853854297e-18}, {0.008333333333333333, 1.1564823173178714e-19},
+                       {-0.0001984126984126984, -1.7209558293420705e-22}, {2.7557319223985893e-06, -1.858393274046472e-22},
+                       {-2.505210838544172e-08, 1.448814070935912e-24}, {1.6059043836821613e-10, 1.2585294588752098e-26},
+                       {-7.647163731819816e-13, -7.03872877733453e-30}, {2.8114572543455206e-15, 1.6508842730861433e-31},
+                       {-8.22063524662433e-18, -2.2141894119604265e-34}, {1.9572941063391263e-20, -1.3643503830087908e-36},
+                       {-3.868170170630684e-23, 8.843177655482344e-40}, {6.446950284384474e-26, -1.9330404233703465e-42},
+                       {-9.183689863795546e-29, -1.4303150396787322e-45}, {1.1309962886447716e-31, 1.0498015412959506e-47},
+                       {-1.216125041553518e-34, -5.586290567888806e-51}};
+  const lt_dd y = {y0, 0.0};
+  const lt_dd y2 = lt_dd_mul(y, y);
+  lt_dd q = c[14];
+#pragma unroll
+  for (int k = 13; k >= 0; --k) q = lt_dd_add(lt_dd_mul(q, y2), c[k]);
+  q = lt_dd_mul(lt_dd_mul(q, y2), y);                 // sin(y0) - y0
+  const lt_dd r = lt_dd_add(lt_dd_sum(x, -y0), lt_dd{-q.hi, -q.lo});   // x - sin(y0)
+  return y0 + (r.hi + r.lo) / cos(y0);
+}
+__device__ __forceinline__ float lt_pitch_beams(float q) { return lt_asin(q); }
+__device__ __forceinline__ double lt_pitch_beams(double q) { return lt_asin_cr(q, asin(q)); }
+
+// One point into the image of a sensor with a BEAM TABLE (LT_PROJ_BEAM_ROWS): the column as above, the row is the NEAREST
+// beam.  `tab` (device, float64): Brad[H] descending, halfw[H], fov_down and fov_up in radians.  The pitch q is computed in
+// T (the correctly rounded asin for both dtypes) and widened to float64; row = the first minimum of |q - Brad[k]|: a
+// binary search for the first beam at or below q, then one comparison of the bracketing pair (neighbouring beams are at least 1e-6 degrees apart, so no beam
+// further out can tie).  Kept iff |q - Brad[row]| <= halfw[row] -- a beam samples its own direction, not the gap beside it;
+// H == 1: iff fov_down <= q <= fov_up.  depth == 0 and NaN never reach an image.  yf = q, py = row.
+template <typename T>
+__device__ __forceinline__ proj_out<T> project_point_beams(T x, T y, T z, T pi_t, int H, int W,
+                                                           const double* __restrict__ tab) {
+  proj_out<T> o;
+  const T depth = lt_sqrt((x * x + y * y) + z * z);
+  const T yaw = -lt_atan2(y, x);
+  const T pitch = lt_pitch_beams(z / depth);  // (float32: correctly rounded already, through double)
+  const double q = (double)pitch;
+  int lo = 0, hi = H;  // -> the first k with Brad[k] <= q (H: none)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tab[mid] > q) lo = mid + 1; else hi = mid;
+  }
+  int row = lo;
+  if (lo >= H) row = H - 1;
+  else if (lo > 0 && !(fabs(q - tab[lo]) < fabs(q - tab[lo - 1]))) row = lo - 1;
+  T px = (T)0.5 * (yaw / pi_t + (T)1.0);
+  bool keep = H > 1 ? fabs(q - tab[row]) <= tab[H + row] : (q >= tab[2 * H] && q <= tab[2 * H + 1]);
+  if (depth == (T)0) keep = false;
+  if (!(depth == depth) || !(px == px) || !(q == q)) keep = false;
+  px *= (T)W;
+  o.xf = px;
+  o.yf = pitch;
+  T fx = lt_floor(px);
+  fx = fx < (T)(W - 1) ? fx : (T)(W - 1);
+  fx = fx > (T)0 ? fx : (T)0;
+  o.px = (int)fx;
+  o.py = row;
+  o.depth = depth;
+  o.cell = keep ? row * W + o.px : -1;
+  return o;
+}
+
 // The z-min key of one point (see the batched projection in lt_project.hip): hi word = float32 bits of the depth (positive
 // floats order like unsigned integers); lo word = 0x7fffffff - index for a point whose depth lies BELOW its float32 value
 // (they beat the others, the highest index first), 0x80000000 | index otherwise (lowest index first).  float32 clouds never

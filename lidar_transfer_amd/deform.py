@@ -135,7 +135,7 @@ class DeviceDeform:
 
     def __init__(self, source, target, vol_bnds=None, voxel_size=0.1, beam_angles=None, t_beam_angles=None,
                  preserve_float=False, device=None, merge=True, fusion="cuda", mesh_volume=True, rayset=None, mm_state=None,
-                 transformation=None):
+                 transformation=None, t_beam_table=None):
         """``fusion``: ``"cuda"`` -- the arithmetic of the reference's CUDA kernel (class-aware with ``merge``), or ``"numpy"`` --
         that of its numpy branch (``FUSION_GPU_MODE == 0``, fusion_lidar.py:290-388; what goldens F13 / F14 are made by).
         ``vol_bnds``: [3,2]; for :meth:`mergemesh` it is STATE, clipped in place call after call exactly as the reference
@@ -148,7 +148,13 @@ class DeviceDeform:
         from ``float32(tp)`` into the scene, which is still fused in the primary scan's frame, and the hits' ``endpoints``
         are brought into the target's frame by ``T`` (``endpoints_scene``: as rendered); ``cp`` takes its cloud into the
         target frame on ingest (:meth:`deform`).  Empty, ``None`` or the identity: none of this runs.  A shared ``rayset``
-        must have been built for the same pose (``RaySet(..., pose=P)``)."""
+        must have been built for the same pose (``RaySet(..., pose=P)``).
+        ``t_beam_table``: the TARGET sensor's beam table (``SensorModel.beam_table()``: [t_H] degrees, descending; ``None``:
+        evenly spaced beams, nothing of this runs) -- the target's rays leave at the table's angles (turned by the pose when
+        there is a ``transformation`` as well), so ``mesh`` and ``mergemesh`` change by their rays alone, and ``cp`` puts a
+        point into the row of its nearest beam (``LT_PROJ_BEAM_ROWS``) and re-projects it along that beam
+        (``lt_reverse_projection_beams_dev``).  A shared ``rayset`` must have been built for the same table
+        (``RaySet(..., beam_table=...)``)."""
         import numpy as np
         import torch
 
@@ -173,6 +179,13 @@ class DeviceDeform:
         self._mm_state, self._mm_own = mm_state, mm_state is None
         self._rayset_own = rayset is None
         self._mounting = _chain.Mount(transformation)
+        self.t_beam_table = self._t_rows = self._t_brad = None
+        if t_beam_table is not None:
+            from .config import check_beam_table
+            self.t_beam_table = check_beam_table(np.ascontiguousarray(t_beam_table, dtype=np.float64), self.t_H, self.t_fov_up,
+                                                 self.t_fov_down, "DeviceDeform: t_beam_table")
+            self._t_rows = _chain.beam_rows_table(self.t_beam_table)     # marshalled once: Brad, halfw
+            self._t_brad = torch.from_numpy(self._t_rows[2][:self.t_H].copy()).to(self.device)
         # ``origin``: the target sensor in the scene, where mesh / mergemesh cast from by default
         self.mount, self.origin = self._mounting.pair, self._mounting.origin
         if mm_state is not None and vol_bnds is None:
@@ -190,13 +203,17 @@ class DeviceDeform:
             pose = self._mounting.P
             if rayset is None:
                 rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=idx,
-                                          rot=pose[:3, :3] if pose is not None else None)
-                self.rayset = RaySet(rays, self.t_H, pose=pose)
+                                          rot=pose[:3, :3] if pose is not None else None, beam_table=self.t_beam_table)
+                self.rayset = RaySet(rays, self.t_H, pose=pose, beam_table=self.t_beam_table)
                 self._rays = rays
             else:
                 theirs = getattr(rayset, "pose", None)
                 if (theirs is None) != (pose is None) or (pose is not None and not np.array_equal(theirs, pose)):
                     raise ValueError("DeviceDeform: the shared rayset was built for another sensor pose than `transformation`")
+                theirs = getattr(rayset, "beam_table", None)
+                if (theirs is None) != (self.t_beam_table is None) or \
+                        (theirs is not None and not np.array_equal(theirs, self.t_beam_table)):
+                    raise ValueError("DeviceDeform: the shared rayset was built for another beam table than `t_beam_table`")
                 self.rayset = rayset
         self.n_rays = self.t_H * self.t_W
 
@@ -465,16 +482,23 @@ class DeviceDeform:
         st = self._stream()
         pf = self.preserve_float
         outs = ("idx", "range", "rem", "label") + (("proj_xf", "proj_yf") if pf else ("proj_x", "proj_y"))
+        rows = self._t_rows
         o = self.projector.project([_chain.merged_cloud(clouds)], self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, new=True,
-                                   remove=True, beam_angles=self.t_beam_angles, outputs=outs, stream=st)[0]
+                                   remove=True, beam_angles=self.t_beam_angles if rows is None else None, outputs=outs,
+                                   stream=st, beam_table=rows)[0]
         px, py = (o["proj_xf"], o["proj_yf"]) if pf else (o["proj_x"], o["proj_y"])
         if pf and px.dtype != torch.float64:
             px, py = px.double(), py.double()
         back = torch.empty((self.n_rays, 3), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(lib.lt_reverse_projection_dev(o["range"].data_ptr(), px.data_ptr(), py.data_ptr(), int(pf),
-                                                     self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, back.data_ptr(),
-                                                     C.c_void_p(st.cuda_stream)), "lt_reverse_projection_dev")
+            if rows is not None:    # along the winner's beam (or its own pitch with preserve_float)
+                _lib.check(lib.lt_reverse_projection_beams_dev(o["range"].data_ptr(), px.data_ptr(), py.data_ptr(), int(pf),
+                                                               self._t_brad.data_ptr(), self.t_H, self.t_W, back.data_ptr(),
+                                                               C.c_void_p(st.cuda_stream)), "lt_reverse_projection_beams_dev")
+            else:
+                _lib.check(lib.lt_reverse_projection_dev(o["range"].data_ptr(), px.data_ptr(), py.data_ptr(), int(pf),
+                                                         self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, back.data_ptr(),
+                                                         C.c_void_p(st.cuda_stream)), "lt_reverse_projection_dev")
             res = dict(range=o["range"], rem=o["rem"], label=o["label"], index=o["idx"], back_points=back)
             if pack:
                 res["bin"], res["label_file"] = self.pack_result(res, st)

@@ -5,17 +5,19 @@ from __future__ import annotations
 import numpy as np
 
 
-def create_rays(fov_up, fov_down, H, W):
+def create_rays(fov_up, fov_down, H, W, beam_table=None):
     """Unit ray direction per (beam, azimuth) cell, ``float32 [H*W, 3]``, row-major ``h*W + w``.
 
     Restatement of ``MultiSemLaserScan.create_rays`` (auxiliary/laserscan.py:1092-1119), quirks
     included: ``linspace(0, 360, W)`` contains both end points, so column 0 and column W-1 are
     the same direction; ``beam_angles`` are ignored; float64 trigonometry, cast to float32 last.
+    ``beam_table`` (``SensorModel.beam_table()``: [H] degrees, row 0 first) takes the place of
+    ``linspace(fov_up, fov_down, H)``: the rays of a sensor whose beams are not evenly spaced.
     """
     yaw = np.linspace(0, 360, W) + 180
     yaw[yaw > 360] -= 360
     yaw = yaw / 180. * np.pi
-    pitch = np.pi / 2 - np.linspace(fov_up, fov_down, H) / 180. * np.pi
+    pitch = np.pi / 2 - _beam_degrees(beam_table, fov_up, fov_down, H) / 180. * np.pi
     sp, cp = np.sin(pitch), np.cos(pitch)
     beams = np.empty((H, W, 3), dtype=np.float64)
     beams[:, :, 0] = sp[:, None] * np.cos(-yaw)[None, :]
@@ -24,10 +26,20 @@ def create_rays(fov_up, fov_down, H, W):
     return np.ascontiguousarray(beams.reshape(H * W, 3).astype(np.float32))
 
 
-def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=None):
+def _beam_degrees(beam_table, fov_up, fov_down, H):
+    if beam_table is None:
+        return np.linspace(fov_up, fov_down, H)
+    b = np.ascontiguousarray(beam_table, dtype=np.float64)
+    if b.shape != (int(H),):
+        raise ValueError(f"beam_table: {b.size} angles for H = {H} rows")
+    return b
+
+
+def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=None, beam_table=None):
     """:func:`create_rays` computed by the HIP kernel into a ``torch`` tensor ``[H*W, 3] f32`` on the GPU.  ``rot``: the
     rotation [3, 3] of the sensor's pose (``Approach.mount()[1][:3, :3]``) -- every direction is turned by it in float64,
-    ``(r0 * x + r1 * y) + r2 * z`` per component, before the cast to float32; ``None``: the sensor's own frame."""
+    ``(r0 * x + r1 * y) + r2 * z`` per component, before the cast to float32; ``None``: the sensor's own frame.
+    ``beam_table``: as for :func:`create_rays` (``lt_create_rays_beams_dev``; the call waits for ``stream``)."""
     import ctypes as C
 
     import torch
@@ -37,14 +49,22 @@ def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=Non
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
     out = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
     st = torch.cuda.current_stream(dev) if stream is None else stream
+    r = None
+    if rot is not None:
+        r = np.ascontiguousarray(rot, dtype=np.float64)
+        if r.shape != (3, 3):
+            raise ValueError("rot: a 3x3 rotation")
     with torch.cuda.device(dev):
-        if rot is None:
+        if beam_table is not None:
+            b = _beam_degrees(beam_table, fov_up, fov_down, H)
+            dp = C.POINTER(C.c_double)
+            _lib.check(lib.lt_create_rays_beams_dev(b.ctypes.data_as(dp), int(H), int(W),
+                                                    r.ctypes.data_as(dp) if r is not None else None, out.data_ptr(),
+                                                    C.c_void_p(st.cuda_stream)), "lt_create_rays_beams_dev")
+        elif rot is None:
             _lib.check(lib.lt_create_rays_dev(float(fov_up), float(fov_down), int(H), int(W), out.data_ptr(),
                                               C.c_void_p(st.cuda_stream)), "lt_create_rays_dev")
         else:
-            r = np.ascontiguousarray(rot, dtype=np.float64)
-            if r.shape != (3, 3):
-                raise ValueError("rot: a 3x3 rotation")
             _lib.check(lib.lt_create_rays_pose_dev(float(fov_up), float(fov_down), int(H), int(W),
                                                    r.ctypes.data_as(C.POINTER(C.c_double)), out.data_ptr(),
                                                    C.c_void_p(st.cuda_stream)), "lt_create_rays_pose_dev")
@@ -67,7 +87,10 @@ class Projector:
     ``TSDFVolume.integrate`` folds from ``proj_label3``), ``proj_x`` / ``proj_y`` / ``proj_xf`` / ``proj_yf``, ``n_kept``
     (a 1-element int32 tensor), ``bnds`` (a [3,2] float64 tensor: ``get_bnds()`` of the kept points, laserscan.py:678-681).
     Empty cells: 0 / -1 / 0 for range / rem / xyz with ``new`` (laserscan.py:362-368), -1
-    everywhere for the old variant (:37-53)."""
+    everywhere for the old variant (:37-53).  ``beam_table`` (``SensorModel.beam_table()``, [H] degrees descending; with
+    ``new`` and ``remove`` only): the rows are the beams of the table (``LT_PROJ_BEAM_ROWS``) -- a point goes to its nearest
+    beam and is kept only within half the gap to that beam's nearer neighbour; ``proj_y`` is the row, ``proj_yf`` the
+    winner's pitch in radians, empty cells hold 0 in ``proj_x`` / ``proj_y`` / ``proj_xf`` / ``proj_yf``."""
 
     _IMG = {"idx": ("int32", 1), "range": ("float32", 1), "xyz": ("float32", 3), "rem": ("float32", 1), "label": ("int32", 1),
             "color": ("float32", 3), "mask": ("float32", 1), "label_folded": ("float32", 1), "proj_x": ("int32", 1),
@@ -88,7 +111,7 @@ class Projector:
         self._h = h
 
     def project(self, clouds, fov_up, fov_down, H, W, new=True, remove=False, beam_angles=None, color_lut=None,
-                outputs=("range", "rem", "label"), out=None, stream=None):
+                outputs=("range", "rem", "label"), out=None, stream=None, beam_table=None):
         import ctypes as C
 
         from . import _lib
@@ -137,11 +160,16 @@ class Projector:
             beams = np.ascontiguousarray(beam_angles, dtype=np.float64)
         st = torch.cuda.current_stream(self.device) if stream is None else stream
         flags = (_lib.LT_PROJ_NEW if new else 0) | (_lib.LT_PROJ_REMOVE if remove else 0)
+        if beam_table is not None:   # Brad followed by halfw, n_beams == H
+            from ._chain import beam_rows_table
+            flags |= _lib.LT_PROJ_BEAM_ROWS
+            beams = beam_rows_table(beam_table)[2]
+        n_beams = 0 if beams is None else (int(H) if beam_table is not None else len(beams))
         init = (0.0, -1.0, 0.0) if new else (-1.0, -1.0, -1.0)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.lt_range_projection_batch_dev(
                 self._h, n, cl, int(dt == torch.float64), float(fov_up), float(fov_down), int(H), int(W),
-                beams.ctypes.data_as(C.c_void_p) if beams is not None else None, 0 if beams is None else len(beams), flags,
+                beams.ctypes.data_as(C.c_void_p) if beams is not None else None, n_beams, flags,
                 lut.data_ptr() if lut is not None else None, 0 if lut is None else int(lut.shape[0]), im, *init,
                 C.c_void_p(st.cuda_stream)), "lt_range_projection_batch_dev")
         self._keep = (keep, lut)  # inputs stay referenced until the next call (the kernels are queued, not finished)

@@ -311,7 +311,10 @@ class FusionScanPipeline:
     in the scene.  ``rays`` must then be that sensor's posed rays (``create_rays_device(..., rot=P[:3, :3])``); every
     ``submit*`` casts them from ``float32(P[:3, 3])`` unless it is given an ``origin``, and a scan's ``endpoints`` arrive in
     the target's frame (``lt_points_to_frame_dev`` on the chain's stream, hits only), ``endpoints_scene`` as rendered.
-    Empty, ``None`` or the identity: nothing changes."""
+    Empty, ``None`` or the identity: nothing changes.
+
+    A target sensor with a beam table (``SensorModel.beam_table()``) needs nothing but its rays: pass
+    ``create_rays_device(..., beam_table=table)`` (with ``rot`` when it is mounted as well) as ``rays``."""
 
     def __init__(self, vol_bnds, voxel_size, fov_up, fov_down, rays, H, chains=3, device=None, merge=True,
                  label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None):

@@ -267,11 +267,13 @@ class RaySet:
     """A ray batch prepared for :meth:`Scene.render` (``lt_rayset`` in include/lidarhip.h): directions
     normalised like the reference (Vector3.h:73-89) and binned by azimuth x elevation.  One per sensor
     model; reuse it for every scan.  ``pose``: the [4, 4] pose of the sensor the rays were generated for (``None``: its own
-    frame) -- only remembered, so that a chain handed a shared ray set can tell whether it was built for its sensor."""
+    frame) and ``beam_table``: the beam table the rays were generated from (``None``: evenly spaced beams) -- only remembered,
+    so that a chain handed a shared ray set can tell whether it was built for its sensor."""
 
-    def __init__(self, rays, H, exact_normalize=False, stream=None, pose=None):
+    def __init__(self, rays, H, exact_normalize=False, stream=None, pose=None, beam_table=None):
         import torch
         self.pose = None if pose is None else np.array(pose, dtype=np.float64).reshape(4, 4)
+        self.beam_table = None if beam_table is None else np.array(beam_table, dtype=np.float64).reshape(-1)
         if not isinstance(rays, torch.Tensor) or rays.dtype != torch.float32 or not rays.is_contiguous() \
                 or not rays.is_cuda:
             raise ValueError("rays: contiguous float32 CUDA tensor [R, 3] expected")
