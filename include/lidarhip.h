@@ -177,6 +177,15 @@ typedef struct lt_rayset lt_rayset; /* opaque: normalised directions of one ray 
  * `stream` once -- a ray set is built once per sensor model); `rays` is not referenced afterwards. */
 int lt_rayset_create_dev(lt_rayset** rayset, const float* rays, int n_rays, int height, unsigned flags,
                          void* stream);
+/* The same with a bin grid of the caller's size: nb_az / nb_el > 0 are the numbers of azimuth / elevation bins (more than
+ * 8192 / 4096 are clamped to that), 0 keeps lt_rayset_create_dev's rule for that axis (W = n_rays / height columns, refitted
+ * to W - 1 when the rays close the circle inclusively; `height` rows) -- (0, 0) IS lt_rayset_create_dev.  A given nb_az is
+ * not refitted.  The azimuth grid is always the full periodic circle with the phase of ray 0; how far the rays sit from
+ * their bins' centres is measured, so every grid renders the same image and only the speed differs: fastest when the rays
+ * sit on bin centres.  For a sensor whose W columns span only `span` degrees (lt_create_rays_sector_dev) that is
+ * nb_az = round(W * 360 / span): the occupied bins are then a contiguous arc and the others stay empty. */
+int lt_rayset_create_grid_dev(lt_rayset** rayset, const float* rays, int n_rays, int height, int nb_az, int nb_el,
+                              unsigned flags, void* stream);
 int lt_rayset_destroy(lt_rayset* rayset);
 
 /* Closest hit of every ray of `rayset`, all cast from `origin` (HOST pointer to 3 floats), against the
@@ -235,6 +244,16 @@ int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, int W, const 
  * copied to the device once per call and the call waits for `stream`: it is made once per sensor model. */
 int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, const double* rot, float* rays, void* stream);
 
+/* The rays of a sensor with a horizontal SECTOR: its W columns span `span_deg` degrees (0 < span < 360) around the direction
+ * `center_deg` (atan2(y, x) in the sensor's frame: 0 is +x, positive to the left; |center| <= 360).  Column 0 is the left
+ * edge, columns run clockwise seen from above as in the full image; column w is the cell [w, w + 1) * span / W and its ray
+ * leaves through the cell's CENTRE: yaw_deg = (-center - span / 2) + (w + 0.5) * (span / W), yaw = yaw_deg / 180 * pi (not
+ * wrapped), then lt_create_rays_dev's expressions.  The row term is linspace(fov_up, fov_down, H), or beams_deg[h] as in
+ * lt_create_rays_beams_dev when `beams_deg` (HOST [H], NULL = evenly spaced) is given; `rot` (HOST [9], NULL = none) is
+ * lt_create_rays_pose_dev's rotation.  Asynchronous on `stream` without a table; with one the call waits for `stream`. */
+int lt_create_rays_sector_dev(const double* beams_deg, double fov_up, double fov_down, int H, int W, double center_deg,
+                              double span_deg, const double* rot, float* rays, void* stream);
+
 #define LT_PROJ_REMOVE 1u /* `remove=True`: drop depth == 0 and points whose proj_y is outside [0, 1]   */
 #define LT_PROJ_NEW 2u    /* do_range_projection_new: depth == 0 is always dropped (laserscan.py:306-309) */
 /* LT_PROJ_BEAM_ROWS -- the image rows are the beams of a TABLE (a target sensor whose beams are not evenly spaced), defined
@@ -248,6 +267,20 @@ int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, const double
  * rule is the same.  proj_y is the row, proj_yf the winner's pitch in radians (the cloud's dtype), proj_x / proj_xf as
  * without the flag; an EMPTY cell holds 0 in all four. */
 #define LT_PROJ_BEAM_ROWS 4u
+/* LT_PROJ_SECTOR -- the image columns are those of a horizontal SECTOR (lt_create_rays_sector_dev), defined together with
+ * LT_PROJ_NEW | LT_PROJ_REMOVE only, with or without LT_PROJ_BEAM_ROWS (any other combination: LT_ERR_INVALID_ARG), for the
+ * same three calls.  The sector's two numbers -- yc = -center / 180 * pi, the yaw of its middle (|yc| <= pi), and its width
+ * in radians (0 < span < 2 pi) -- are set beforehand: lt_projector_set_sector for lt_range_projection_batch_dev,
+ * lt_range_projection_set_sector for the two single-cloud calls (below); the flag without a sector set is
+ * LT_ERR_INVALID_ARG, so no existing signature, struct or argument changes its meaning (`beam_angles` / `n_beams` are as
+ * without the flag; at most 510 rows / 1022 angles).  Per point, in the cloud's dtype T with pi, yc and span rounded to T: yaw = -atan2(y, x); d = yaw - yc, plus
+ * 2 pi if d < -pi, minus 2 pi if d >= pi (a sector may straddle the seam behind the sensor); u = d / span + 0.5; the point
+ * is kept iff 0 <= u < 1 on top of every condition without the flag; proj_xf = u * W, proj_x = floor(proj_xf) clamped to
+ * [0, W - 1] -- the column whose ray is nearest.  Rows, the z-min rule and the empty cells are as without the flag. */
+#define LT_PROJ_SECTOR 8u
+/* The sector that LT_PROJ_SECTOR reads in lt_range_projection_dev / lt_range_projection (one per process, kept until set
+ * again; span == 0 clears it).  LT_ERR_INVALID_ARG unless |yaw_center| <= pi and 0 < span < 2 pi (radians). */
+int lt_range_projection_set_sector(double yaw_center, double span);
 
 /*
  * lt_range_projection_dev -- point cloud -> H x W spherical image, closest point per cell (atomic
@@ -336,6 +369,10 @@ typedef struct lt_proj_images {
 } lt_proj_images;
 int lt_projector_create(lt_projector** projector, int device);
 int lt_projector_destroy(lt_projector* projector);
+/* The sector that LT_PROJ_SECTOR reads in this projector's lt_range_projection_batch_dev calls (kept until set again;
+ * span == 0 clears it): yaw_center = -center / 180 * pi, span the width, radians.  LT_ERR_INVALID_ARG unless
+ * |yaw_center| <= pi and 0 < span < 2 pi.  Host side only: it takes effect with the next call. */
+int lt_projector_set_sector(lt_projector* projector, double yaw_center, double span);
 int lt_range_projection_batch_dev(lt_projector* projector, int n_clouds, const lt_cloud* clouds, int is_f64,
                                   double fov_up, double fov_down, int H, int W, const double* beam_angles, int n_beams,
                                   unsigned flags, const float* color_lut, int lut_len, const lt_proj_images* out,
@@ -562,6 +599,16 @@ int lt_reverse_projection_dev(const float* range_img, const void* proj_x, const 
  * float64.  One thread per cell, asynchronous on `stream`. */
 int lt_reverse_projection_beams_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
                                     int preserve_float, const double* Brad, int H, int W, double* back_points, void* stream);
+
+/* The same for a sensor with a horizontal SECTOR (what LT_PROJ_SECTOR projected): yaw = yaw_center + ((proj_x + 0.5) / W -
+ * 0.5) * span from the int32 column -- the centre of its cell, the direction of its ray -- or, with preserve_float, yaw =
+ * yaw_center + (proj_xf / W - 0.5) * span from the float64 column (yaw_center = -center / 180 * pi and span in radians, as
+ * the flag takes them).  The elevation: beam_rows == 0 -- lt_reverse_projection_dev's linear rule from proj_y (int32, or
+ * float64 with preserve_float), Brad unused; beam_rows != 0 -- lt_reverse_projection_beams_dev's, Brad[proj_y] or the pitch
+ * image.  The point is depth * sin(pitch) * cos(-yaw), ..., multiplied left to right in float64.  Asynchronous. */
+int lt_reverse_projection_sector_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
+                                     int preserve_float, int beam_rows, const double* Brad, double fov_up, double fov_down,
+                                     int H, int W, double yaw_center, double span, double* back_points, void* stream);
 
 /* Points into another frame: out[i] = float32(((m0*x + m1*y) + m2*z) + m3) per row of T, in float64 from the float32
  * point.  points / out [n,3] f32 DEVICE (out may be points), tri [n] i32 DEVICE or NULL: rows with tri < 0 (rays

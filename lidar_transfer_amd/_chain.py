@@ -61,6 +61,17 @@ def beam_rows_table(table):
     return t.ctypes.data_as(C.c_void_p), len(t) // 2, t
 
 
+def sector_pair(sector):
+    """A target sensor's SECTOR (``SensorModel.sector()``, ``(center_deg, span_deg)``) as ``LT_PROJ_SECTOR`` and
+    ``lt_reverse_projection_sector_dev`` read it: float64 [2], the yaw of its middle and its width in radians
+    (``config.sector_radians``).  A float64 array of two is taken as already marshalled."""
+    import numpy as np
+    if isinstance(sector, np.ndarray):
+        return sector
+    from .config import check_sector, sector_radians
+    return np.array(sector_radians(check_sector(sector)), dtype=np.float64)
+
+
 def origin3(origin):
     return (C.c_float * 3)(*[float(x) for x in origin])
 

@@ -17,6 +17,11 @@ is ``None`` when absent; ``create_rays`` ignores it (``laserscan.py:1092-1119``)
 ``beam_model: table`` (optional, default ``linear``) is this project's own key, for a TARGET sensor: its ``beam_angles`` are
 then the real elevation of every beam in degrees -- its rays leave at these angles and a point's image row is its nearest
 beam (:meth:`SensorModel.beam_table`).  Without the key ``beam_angles`` keeps the meaning above.
+
+``azimuth_model: sector`` (optional, default ``full``) and ``azimuth_center`` (degrees, default 0) are this project's own
+keys as well, for a TARGET sensor: ``fov_hor`` is then the width of the sensor's horizontal field of view around the
+direction ``azimuth_center`` and the ``W`` columns span that sector alone (:meth:`SensorModel.sector`).  Without
+the key ``fov_hor`` only sets ``W`` and the columns go round the whole circle, as in the reference.
 """
 from __future__ import annotations
 
@@ -38,6 +43,8 @@ class SensorModel:
     beam_angles: Optional[List[float]] = None
     raw: dict = field(default_factory=dict, repr=False)
     beam_model: str = "linear"
+    azimuth_model: str = "full"
+    azimuth_center: float = 0.0
 
     @property
     def H(self) -> int:
@@ -56,7 +63,19 @@ class SensorModel:
         """Host mirror of ``MultiSemLaserScan.create_rays(fov_up, fov_down, H, W)`` for this model:
         ``[H*W, 3]`` float32 (beam_angles are ignored there, as in the reference)."""
         from .laserscan import create_rays
-        return create_rays(self.fov_up, self.fov_down, self.H, self.W, beam_table=self.beam_table())
+        return create_rays(self.fov_up, self.fov_down, self.H, self.W, beam_table=self.beam_table(), sector=self.sector())
+
+    def sector(self):
+        """``None`` for ``azimuth_model: full``; for ``sector`` ``(center_deg, span_deg)`` as floats: the ``W`` columns span
+        ``span_deg = fov_hor`` degrees around the direction ``center_deg = azimuth_center`` (``atan2(y, x)`` in the sensor's
+        frame: 0 is straight ahead, positive to the left), column 0 at the left edge, clockwise seen from above.  A centre
+        beyond +-180 comes back reduced by a full turn.  ``ValueError`` for another model, a ``fov_hor`` outside (0, 360),
+        or a centre that is not finite or beyond +-360."""
+        if self.azimuth_model == "full":
+            return None
+        if self.azimuth_model != "sector":
+            raise ValueError(f"sensor {self.name!r}: azimuth_model {self.azimuth_model!r} (full or sector)")
+        return check_sector((self.azimuth_center, self.fov_hor), f"sensor {self.name!r}")
 
     def beam_table(self):
         """``None`` for ``beam_model: linear``; for ``table`` the beams' elevations in degrees, float64 [H], sorted
@@ -86,6 +105,31 @@ def check_beam_table(b, H, fov_up, fov_down, who="beam table"):
     if not np.all((b >= float(fov_down)) & (b <= float(fov_up))):
         raise ValueError(f"{who}: every beam angle must lie in [fov_down, fov_up] = [{fov_down}, {fov_up}]")
     return b
+
+
+def check_sector(sector, who="sector"):
+    """the conditions of :meth:`SensorModel.sector` on ``(center_deg, span_deg)``; returns the pair as floats, the centre
+    within [-180, 180]"""
+    try:
+        c, s = (float(v) for v in sector)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: azimuth_center and fov_hor must be numbers") from None
+    if not (0.0 < s < 360.0):
+        raise ValueError(f"{who}: azimuth_model sector needs 0 < fov_hor < 360 (fov_hor = {s})")
+    if not (np.isfinite(c) and abs(c) <= 360.0):
+        raise ValueError(f"{who}: azimuth_center must be finite and within +-360 degrees (azimuth_center = {c})")
+    if c > 180.0:
+        c -= 360.0
+    elif c < -180.0:
+        c += 360.0
+    return c, s
+
+
+def sector_radians(sector):
+    """What the column rule of a sector reads (``LT_PROJ_SECTOR``, ``lt_reverse_projection_sector_dev``), float64: the yaw of
+    its middle ``yc = -center / 180 * pi`` and its width ``span / 180 * pi``."""
+    c, s = sector
+    return -c / 180. * np.pi, s / 180. * np.pi
 
 
 def beam_rows(table):
@@ -128,8 +172,10 @@ def load_sensor(path_or_dict) -> SensorModel:
     except Exception:
         beam_angles = None
     model = SensorModel(name, fov_up, fov_down, beams, angle_res_hor, fov_hor, beam_angles, raw=cfg,
-                        beam_model=str(cfg.get("beam_model", "linear")))
+                        beam_model=str(cfg.get("beam_model", "linear")),
+                        azimuth_model=str(cfg.get("azimuth_model", "full")), azimuth_center=cfg.get("azimuth_center", 0.0))
     model.beam_table()   # (a table that cannot be used: said at load time)
+    model.sector()       # (the same for a sector)
     return model
 
 
@@ -138,6 +184,13 @@ def refuse_source_table(source):
     if getattr(source, "beam_model", "linear") != "linear":
         raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: beam_model {source.beam_model!r} is for target sensors "
                          "only (the source scan is fused by the reference's evenly spaced pixel model)")
+
+
+def refuse_source_sector(source):
+    """A sector is a property of the TARGET as well: the source scan is fused by the reference's full-circle pixel model."""
+    if getattr(source, "azimuth_model", "full") != "full":
+        raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: azimuth_model {source.azimuth_model!r} is for target "
+                         "sensors only (the source scan is fused by the reference's full-circle pixel model)")
 
 
 @dataclass

@@ -94,6 +94,69 @@ extern "C" int lt_reverse_projection_beams_dev(const float* range_img, const voi
   return LT_OK;
 }
 
+// ---- reverse projection of a sensor with a horizontal SECTOR (what LT_PROJ_SECTOR projected): the column's yaw is that of
+// its ray, the CENTRE of cell px -- yaw = yc + ((px + 0.5) / W - 0.5) * span -- or, with `preserve_float`, the winner's own:
+// yaw = yc + (xf / W - 0.5) * span.  The elevation is k_reverse's linear rule (BEAMS 0) or k_reverse_beams' (BEAMS 1:
+// Brad[row], or the pitch image with `preserve_float`); the three products are multiplied left to right as there.
+template <typename P, int BEAMS>
+__global__ __launch_bounds__(256) void k_reverse_sector(const float* __restrict__ range, const P* __restrict__ px,
+                                                        const P* __restrict__ py, int n, double W, double H, double fov,
+                                                        double abs_fov_down, const double* __restrict__ Brad, int py_is_float,
+                                                        double yc, double span, double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double depth = (double)range[i];
+  const double x = py_is_float ? (double)px[i] / W : ((double)px[i] + 0.5) / W;
+  const double yaw = yc + (x - 0.5) * span;
+  double pitch;
+  if (BEAMS) {
+    double e;
+    if (py_is_float) {
+      e = (double)py[i];
+    } else {
+      int r = (int)py[i];
+      const int h = (int)H;
+      r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
+      e = Brad[r];
+    }
+    pitch = M_PI / 2 - e;
+  } else {
+    const double y = (double)py[i] / H;
+    pitch = M_PI / 2 - (1.0 * fov - y * fov - abs_fov_down);
+  }
+  const double sp = sin(pitch);
+  out[3 * (size_t)i] = depth * sp * cos(-yaw);
+  out[3 * (size_t)i + 1] = depth * sp * sin(-yaw);
+  out[3 * (size_t)i + 2] = depth * cos(pitch);
+}
+
+extern "C" int lt_reverse_projection_sector_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
+                                                int preserve_float, int beam_rows, const double* Brad, double fov_up,
+                                                double fov_down, int H, int W, double yaw_center, double span,
+                                                double* back_points, void* stream) {
+  if (H <= 0 || W <= 0 || !range_img || !proj_x || !proj_y_or_pitch || !back_points ||
+      (beam_rows && !preserve_float && !Brad) || !(fabs(yaw_center) <= M_PI) || !(span > 0.0 && span < 2 * M_PI)) {
+    lt_set_error("lt_reverse_projection_sector_dev: invalid argument (H=%d W=%d yaw_center=%g span=%g)", H, W, yaw_center, span);
+    return LT_ERR_INVALID_ARG;
+  }
+  const double fu = fov_up / 180.0 * M_PI, fd = fov_down / 180.0 * M_PI;
+  const double fov = fabs(fd) + fabs(fu);
+  const int n = H * W;
+  const dim3 grid((n + 255) / 256), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define LT_REV_SECTOR(P, B)                                                                                              \
+  hipLaunchKernelGGL((k_reverse_sector<P, B>), grid, block, 0, st, range_img, (const P*)proj_x, (const P*)proj_y_or_pitch, n, \
+                     (double)W, (double)H, fov, fabs(fd), Brad, preserve_float ? 1 : 0, yaw_center, span, back_points)
+  if (preserve_float) {
+    if (beam_rows) LT_REV_SECTOR(double, 1); else LT_REV_SECTOR(double, 0);
+  } else {
+    if (beam_rows) LT_REV_SECTOR(int, 1); else LT_REV_SECTOR(int, 0);
+  }
+#undef LT_REV_SECTOR
+  LT_HIP(hipGetLastError());
+  return LT_OK;
+}
+
 // ---- rendered points into another frame (the target sensor's, when it is mounted at a pose of its own) ----------
 // float32 point widened to float64, ((m0 * x + m1 * y) + m2 * z) + m3 per row of T (lt_ingest_scans_dev's row form; every
 // product and sum rounded on its own), rounded to float32.  Rows with tri < 0 (misses) are copied as they are: (0, 0, 0)

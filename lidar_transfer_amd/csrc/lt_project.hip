@@ -26,8 +26,9 @@
 #define LT_EMPTY_IDX 0x7F7F7F7F  // hipMemset(0x7F) pattern: larger than any point index
 
 // pass 1: project, z-min of the depth bits, per-workgroup count of kept points (BEAMS: the rows of a beam table,
-// project_point_beams; `beams` is then its table)
-template <typename T, int BEAMS = 0>
+// project_point_beams; `beams` is then its table.  SECTOR: the columns of a horizontal sector, project_sector_column; its two
+// numbers follow the table -- 2 H + 2 doubles -- or the n_beams angles in `beams`)
+template <typename T, int BEAMS = 0, int SECTOR = 0>
 __global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int n, T pi_t, T abs_fov_down, T fov,
                                                  int H, int W, const double* __restrict__ beams, int n_beams,
                                                  int drop_zero, int drop_outside, int round_key,
@@ -40,9 +41,10 @@ __global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int 
   bool keep = false;
   if (i < n) {
     const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-    const proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
-                                : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
-                                                   drop_outside);
+    proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
+                          : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
+                                             drop_outside);
+    if (SECTOR) project_sector_column<T>(o, x, y, pi_t, W, beams + (BEAMS ? 2 * H + 2 : n_beams));
     cell[i] = o.cell;
     depth_d[i] = (double)o.depth;
     xf[i] = o.xf;
@@ -279,6 +281,65 @@ extern "C" int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, c
   return LT_OK;
 }
 
+// ---- create_rays of a sensor with a horizontal SECTOR: column w is the cell [w, w + 1) * span / W counted clockwise from the
+// sector's left edge, and its ray leaves through the cell's CENTRE -- yaw_deg = (-center - span / 2) + (w + 0.5) * (span / W),
+// not wrapped (sin and cos are periodic); from there on k_create_rays' expressions.  The row term is k_create_rays' linspace
+// or -- `beams_deg` given -- the table's angle as in k_create_rays_beams; `posed`: k_create_rays_pose's rotation in float64
+// before the one cast to float32.  One kernel for the four combinations; the three kernels above stay what they were.
+__global__ __launch_bounds__(256) void k_create_rays_sector(const double* __restrict__ beams_deg, double fov_up,
+                                                            double fov_down, int H, int W, double center_deg, double span_deg,
+                                                            lt_rot9 R, int posed, float* __restrict__ rays) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= H * W) return;
+  const int h = idx / W, w = idx - h * W;
+  const double yaw_deg = (-center_deg - span_deg / 2) + (w + 0.5) * (span_deg / W);
+  const double yaw = yaw_deg / 180. * M_PI;
+  const double pd = beams_deg ? beams_deg[h]
+                              : (H > 1 ? (h == H - 1 ? fov_down : fov_up + h * ((fov_down - fov_up) / (H - 1))) : fov_up);
+  const double p = M_PI / 2 - pd / 180. * M_PI;
+  const double sp = sin(p);
+  const double x = sp * cos(-yaw), y = sp * sin(-yaw), z = cos(p) * 1.0;
+  if (posed) {
+    rays[3 * (size_t)idx] = (float)((R.m[0] * x + R.m[1] * y) + R.m[2] * z);
+    rays[3 * (size_t)idx + 1] = (float)((R.m[3] * x + R.m[4] * y) + R.m[5] * z);
+    rays[3 * (size_t)idx + 2] = (float)((R.m[6] * x + R.m[7] * y) + R.m[8] * z);
+  } else {
+    rays[3 * (size_t)idx] = (float)x;
+    rays[3 * (size_t)idx + 1] = (float)y;
+    rays[3 * (size_t)idx + 2] = (float)z;
+  }
+}
+
+extern "C" int lt_create_rays_sector_dev(const double* beams_deg, double fov_up, double fov_down, int H, int W,
+                                         double center_deg, double span_deg, const double* rot, float* rays, void* stream) {
+  if (H <= 0 || W <= 0 || !rays || !(fabs(center_deg) <= 360.0) || !(span_deg > 0.0 && span_deg < 360.0)) {
+    lt_set_error("lt_create_rays_sector_dev: invalid argument (H=%d W=%d center=%g span=%g)", H, W, center_deg, span_deg);
+    return LT_ERR_INVALID_ARG;
+  }
+  lt_rot9 R;
+  for (int k = 0; k < 9; ++k) R.m[k] = rot ? rot[k] : (k % 4 == 0 ? 1.0 : 0.0);
+  hipStream_t st = (hipStream_t)stream;
+  if (!beams_deg) {
+    hipLaunchKernelGGL(k_create_rays_sector, dim3((H * W + 255) / 256), dim3(256), 0, st, (const double*)nullptr, fov_up,
+                       fov_down, H, W, center_deg, span_deg, R, rot ? 1 : 0, rays);
+    LT_HIP(hipGetLastError());
+    return LT_OK;
+  }
+  // with a table (once per sensor model): it goes to the device in a buffer of this call, which waits for its kernel
+  double* d_beams = nullptr;
+  LT_HIP(hipMalloc((void**)&d_beams, (size_t)H * sizeof(double)));
+  hipError_t e = hipMemcpyAsync(d_beams, beams_deg, (size_t)H * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_create_rays_sector, dim3((H * W + 255) / 256), dim3(256), 0, st, (const double*)d_beams, fov_up,
+                       fov_down, H, W, center_deg, span_deg, R, rot ? 1 : 0, rays);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_beams);
+  LT_HIP(e);
+  return LT_OK;
+}
+
 // LT_PROJ_BEAM_ROWS: the caller's table (Brad[H], halfw[H]) checked and completed by the field of view in radians, which
 // the H == 1 keep rule reads: tab[2 * H + 2].  Returns the number of doubles, 0 when the arguments do not fit the flag.
 static int beam_rows_table(const char* who, const double* beam_angles, int n_beams, unsigned flags, int H, double fov_up_deg,
@@ -292,6 +353,36 @@ static int beam_rows_table(const char* who, const double* beam_angles, int n_bea
   tab[2 * H] = fov_down_deg / 180.0 * M_PI;
   tab[2 * H + 1] = fov_up_deg / 180.0 * M_PI;
   return 2 * H + 2;
+}
+
+// LT_PROJ_SECTOR: the two numbers of the sector -- the yaw of its middle (|.| <= pi) and its width (in (0, 2 pi)), radians --
+// come from lt_projector_set_sector / lt_range_projection_set_sector (`sec`, NULL: none was set).  They are appended to
+// `tab`: behind the n_tab doubles of the completed table when LT_PROJ_BEAM_ROWS is set as well, else behind a copy of the
+// n_beams angles (n_beams may be 0).  Returns the number of doubles, 0 when the arguments do not fit the flag.
+static int sector_tail(const char* who, const double* sec, const double* beam_angles, int n_beams, unsigned flags, double* tab,
+                       int n_tab) {
+  const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0;
+  if ((flags & ~LT_PROJ_BEAM_ROWS) != (LT_PROJ_SECTOR | LT_PROJ_NEW | LT_PROJ_REMOVE) || !sec || n_beams < 0 ||
+      (n_beams > 0 && !beam_angles) || (rows ? n_tab : n_beams) + 2 > 1024) {
+    lt_set_error("%s: LT_PROJ_SECTOR goes with LT_PROJ_NEW | LT_PROJ_REMOVE only, with or without LT_PROJ_BEAM_ROWS (flags=%u), "
+                 "and after the sector was set (%s; n_beams=%d)", who, flags, sec ? "it was" : "it was not", n_beams);
+    return 0;
+  }
+  if (!rows) {
+    if (n_beams > 0) memcpy(tab, beam_angles, (size_t)n_beams * sizeof(double));
+    n_tab = n_beams;
+  }
+  tab[n_tab] = sec[0];
+  tab[n_tab + 1] = sec[1];
+  return n_tab + 2;
+}
+
+static bool sector_ok(const char* who, double yaw_center, double span) {
+  if (!(fabs(yaw_center) <= M_PI) || !(span > 0.0 && span < 2 * M_PI)) {
+    lt_set_error("%s: yaw of the sector's middle %g (|.| <= pi) and width %g (0 < . < 2 pi), radians", who, yaw_center, span);
+    return false;
+  }
+  return true;
 }
 
 // ---- host orchestration -------------------------------------------------------------------------------------
@@ -313,6 +404,8 @@ struct proj_ws {
 };
 std::mutex g_pmu;
 proj_ws g_pws;
+double g_sector[2] = {0.0, 0.0};  // lt_range_projection_set_sector
+bool g_sector_set = false;
 
 void pws_free(proj_ws& w) {
   void* ps[] = {w.cell, w.depth_d, w.xf, w.yf, w.blockcount, w.orig_of, w.cellmin, w.idxmin, w.idxlast, w.beams};
@@ -363,7 +456,15 @@ int run_projection(proj_ws& w, const T* pts, const float* rem, const unsigned* l
   w.armed = false;
   const int round_key = (flags & LT_PROJ_NEW) ? 1 : 0;
   if (n > 0) {
-    if (flags & LT_PROJ_BEAM_ROWS)
+    if ((flags & LT_PROJ_BEAM_ROWS) && (flags & LT_PROJ_SECTOR))
+      hipLaunchKernelGGL((k_project<T, 1, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
+                         (const double*)w.beams, n_beams, 1, 1, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
+                         w.blockcount);
+    else if (flags & LT_PROJ_SECTOR)
+      hipLaunchKernelGGL((k_project<T, 0, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
+                         (const double*)w.beams, n_beams, 1, 1, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
+                         w.blockcount);
+    else if (flags & LT_PROJ_BEAM_ROWS)
       hipLaunchKernelGGL((k_project<T, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
                          (const double*)w.beams, n_beams, 1, 1, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
                          w.blockcount);
@@ -393,6 +494,15 @@ int run_projection(proj_ws& w, const T* pts, const float* rem, const unsigned* l
 }
 }  // namespace
 
+extern "C" int lt_range_projection_set_sector(double yaw_center, double span) {
+  if (span != 0.0 && !sector_ok("lt_range_projection_set_sector", yaw_center, span)) return LT_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(g_pmu);
+  g_sector[0] = yaw_center;
+  g_sector[1] = span;
+  g_sector_set = span != 0.0;
+  return LT_OK;
+}
+
 extern "C" int lt_range_projection_dev(const void* points, int is_f64, const float* rem, const unsigned* label,
                                        int n, double fov_up, double fov_down, int H, int W,
                                        const double* beam_angles, int n_beams, unsigned flags,
@@ -410,10 +520,14 @@ extern "C" int lt_range_projection_dev(const void* points, int is_f64, const flo
   double tab[1024];
   int n_tab = 0;
   if (flags & LT_PROJ_BEAM_ROWS) {
-    n_tab = beam_rows_table("lt_range_projection", beam_angles, n_beams, flags, H, fov_up, fov_down, tab);
+    n_tab = beam_rows_table("lt_range_projection", beam_angles, n_beams, flags & ~LT_PROJ_SECTOR, H, fov_up, fov_down, tab);
     if (!n_tab) return LT_ERR_INVALID_ARG;
   }
   std::lock_guard<std::mutex> lock(g_pmu);
+  if (flags & LT_PROJ_SECTOR) {
+    n_tab = sector_tail("lt_range_projection", g_sector_set ? g_sector : nullptr, beam_angles, n_beams, flags, tab, n_tab);
+    if (!n_tab) return LT_ERR_INVALID_ARG;
+  }
   int dev = 0;
   LT_HIP(hipGetDevice(&dev));
   LT_CHECK(pws_reserve(g_pws, dev, (size_t)n, (size_t)H * W));
@@ -488,8 +602,9 @@ __device__ __forceinline__ double pb_unord(unsigned long long k) {
 }
 
 // MODE 0: the single-key variants (NEW on any dtype, OLD on float32).  MODE 1: OLD on float64 -- depth minimum only.
-// BEAMS: the rows of a beam table (project_point_beams; `beams` is then its table), MODE 0 only.
-template <typename T, int MODE, int BEAMS = 0>
+// BEAMS: the rows of a beam table (project_point_beams; `beams` is then its table), MODE 0 only.  SECTOR: the columns of a
+// horizontal sector (project_sector_column; its two numbers follow the table or the n_beams angles), MODE 0 only.
+template <typename T, int MODE, int BEAMS = 0, int SECTOR = 0>
 __global__ __launch_bounds__(256) void k_pb_project(pb_args A, T pi_t, T abs_fov_down, T fov, int H, int W,
                                                     const double* __restrict__ beams, int n_beams, int drop_zero,
                                                     int drop_outside) {
@@ -500,9 +615,10 @@ __global__ __launch_bounds__(256) void k_pb_project(pb_args A, T pi_t, T abs_fov
   if (i < c.n) {
     const T* pts = (const T*)c.pts;
     const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-    const proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
-                                : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
-                                                   drop_outside);
+    proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
+                          : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
+                                             drop_outside);
+    if (SECTOR) project_sector_column<T>(o, x, y, pi_t, W, beams + (BEAMS ? 2 * H + 2 : n_beams));
     keep = o.cell >= 0;
     if (keep) {
       if (MODE == 0) atomicMin(&c.key[o.cell], pb_key<T>(o.depth, i));
@@ -627,7 +743,7 @@ __global__ __launch_bounds__(64) void k_pb_bnds(pb_args A) {
   if (c.bacc) pb_fold_bounds(c, threadIdx.x);
 }
 
-template <typename T, int MODE, int BEAMS = 0>
+template <typename T, int MODE, int BEAMS = 0, int SECTOR = 0>
 __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cloud, T pi_t, T abs_fov_down, T fov, int H,
                                                     int W, const double* __restrict__ beams, int n_beams, int drop_zero,
                                                     int drop_outside, const float* __restrict__ lut, int lut_len,
@@ -650,9 +766,11 @@ __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cl
   o.depth = (T)0; o.xf = (T)0; o.yf = (T)0; o.px = 0; o.py = 0; o.cell = -1;
   if (i >= 0) {
     x = pts[3 * (size_t)i]; y = pts[3 * (size_t)i + 1]; z = pts[3 * (size_t)i + 2];
-    if (has ? (want_xy || c.range_img) : true)
+    if (has ? (want_xy || c.range_img) : true) {
       o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
                 : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
+      if (SECTOR) project_sector_column<T>(o, x, y, pi_t, W, beams + (BEAMS ? 2 * H + 2 : n_beams));
+    }
   }
   int k = -1;
   if (has && have_prefix) k = c.wprefix[i >> 6] + __popcll(c.keep[i >> 6] & ((1ull << (i & 63)) - 1ull));
@@ -694,6 +812,8 @@ struct lt_projector {
   double* beams = nullptr;                  // [1024]
   double beams_host[1024];
   int n_beams_cached = -1;
+  double sector[2] = {0.0, 0.0};            // lt_projector_set_sector
+  bool sector_set = false;
   unsigned long long* bacc = nullptr;       // [LT_PB_MAX][bacc_blocks][6] per-workgroup partial bounds of the clouds (no arming: every
   size_t bacc_blocks = 0;                   // workgroup of k_pb_project writes its six words)
   float* img = nullptr;                     // lt_deform_scan_dev: [n][3][H * W] source images (range, remission, folded label)
@@ -750,8 +870,16 @@ int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool nee
   const int drop_zero = (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW)) ? 1 : 0, drop_outside = (flags & LT_PROJ_REMOVE) ? 1 : 0;
   const int cells = H * W, bpc = (cells + 255) / 256;
   const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0;  // (never with old_f64: the flag goes with LT_PROJ_NEW)
+  const bool sector = (flags & LT_PROJ_SECTOR) != 0;   // (the same)
   if (total_blocks > 0) {
-    if (rows) {
+    if (sector) {
+      if (rows)
+        hipLaunchKernelGGL((k_pb_project<T, 0, 1, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H,
+                           W, (const double*)p->beams, n_beams, drop_zero, drop_outside);
+      else
+        hipLaunchKernelGGL((k_pb_project<T, 0, 0, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H,
+                           W, (const double*)p->beams, n_beams, drop_zero, drop_outside);
+    } else if (rows) {
       hipLaunchKernelGGL((k_pb_project<T, 0, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
                          (const double*)p->beams, n_beams, drop_zero, drop_outside);
     } else if (old_f64) {
@@ -766,7 +894,15 @@ int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool nee
   }
   if (need_prefix) hipLaunchKernelGGL(k_pb_prefix, dim3(A.n_clouds), dim3(256), 0, st, A);
   else if (bnds_only) hipLaunchKernelGGL(k_pb_bnds, dim3(A.n_clouds), dim3(64), 0, st, A);
-  if (rows)
+  if (sector && rows)
+    hipLaunchKernelGGL((k_pb_resolve<T, 0, 1, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd),
+                       (T)fov, H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init,
+                       rem_init, xyz_init, need_prefix ? 1 : 0);
+  else if (sector)
+    hipLaunchKernelGGL((k_pb_resolve<T, 0, 0, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd),
+                       (T)fov, H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init,
+                       rem_init, xyz_init, need_prefix ? 1 : 0);
+  else if (rows)
     hipLaunchKernelGGL((k_pb_resolve<T, 0, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd), (T)fov,
                        H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init, rem_init,
                        xyz_init, need_prefix ? 1 : 0);
@@ -811,6 +947,18 @@ extern "C" int lt_projector_create(lt_projector** pj, int device) {
   return LT_OK;
 }
 
+extern "C" int lt_projector_set_sector(lt_projector* p, double yaw_center, double span) {
+  if (!p || (span != 0.0 && !sector_ok("lt_projector_set_sector", yaw_center, span))) {
+    if (!p) lt_set_error("lt_projector_set_sector: NULL projector");
+    return LT_ERR_INVALID_ARG;
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  p->sector[0] = yaw_center;
+  p->sector[1] = span;
+  p->sector_set = span != 0.0;
+  return LT_OK;
+}
+
 extern "C" int lt_projector_destroy(lt_projector* p) {
   if (!p) return LT_OK;
   (void)hipSetDevice(p->device);
@@ -836,11 +984,15 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
     return LT_ERR_INVALID_ARG;
   }
   double tab[1024];
+  const double* given = beam_angles;
+  const int n_given = n_beams;
   if (flags & LT_PROJ_BEAM_ROWS) {  // from here on `beam_angles` / `n_beams` are the completed table
-    n_beams = beam_rows_table("lt_range_projection_batch_dev", beam_angles, n_beams, flags, H, fov_up, fov_down, tab);
+    n_beams = beam_rows_table("lt_range_projection_batch_dev", beam_angles, n_beams, flags & ~LT_PROJ_SECTOR, H, fov_up,
+                              fov_down, tab);
     if (!n_beams) return LT_ERR_INVALID_ARG;
     beam_angles = tab;
   }
+  int n_dev = n_beams;  // doubles of `beam_angles` that the kernels read: with a sector, two more than n_beams
   size_t n_max = 0;
   for (int k = 0; k < n_clouds; ++k) {
     if (clouds[k].n < 0 || (clouds[k].n > 0 && !clouds[k].points)) {
@@ -850,6 +1002,12 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
     n_max = std::max(n_max, (size_t)clouds[k].n);
   }
   std::lock_guard<std::mutex> lock(p->mu);
+  if (flags & LT_PROJ_SECTOR) {
+    n_dev = sector_tail("lt_range_projection_batch_dev", p->sector_set ? p->sector : nullptr, given, n_given, flags, tab,
+                        (flags & LT_PROJ_BEAM_ROWS) ? n_beams : 0);
+    if (!n_dev) return LT_ERR_INVALID_ARG;
+    beam_angles = tab;
+  }
   LT_HIP(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
   const bool old_f64 = is_f64 && !(flags & LT_PROJ_NEW);
@@ -867,12 +1025,12 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
   }
   p->armed = false;  // (until the resolve pass of this call has been queued)
   if (old_f64) p->dmin_armed = false;
-  if (n_beams > 0 && (n_beams != p->n_beams_cached || memcmp(p->beams_host, beam_angles, n_beams * sizeof(double)) != 0)) {
+  if (n_dev > 0 && (n_dev != p->n_beams_cached || memcmp(p->beams_host, beam_angles, n_dev * sizeof(double)) != 0)) {
     // the table is read by kernels of EARLIER calls on this stream: the copy is stream-ordered behind them; a pageable
     // source is staged by the runtime before the call returns, so beams_host may be overwritten by the next call
-    memcpy(p->beams_host, beam_angles, n_beams * sizeof(double));
-    LT_HIP(hipMemcpyAsync(p->beams, p->beams_host, n_beams * sizeof(double), hipMemcpyHostToDevice, st));
-    p->n_beams_cached = n_beams;
+    memcpy(p->beams_host, beam_angles, n_dev * sizeof(double));
+    LT_HIP(hipMemcpyAsync(p->beams, p->beams_host, n_dev * sizeof(double), hipMemcpyHostToDevice, st));
+    p->n_beams_cached = n_dev;
   }
   for (int g0 = 0; g0 < n_clouds; g0 += LT_PB_MAX) {
     pb_args A;

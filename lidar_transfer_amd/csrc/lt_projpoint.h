@@ -145,6 +145,30 @@ __device__ __forceinline__ proj_out<T> project_point_beams(T x, T y, T z, T pi_t
   return o;
 }
 
+// The column of a sensor with a horizontal SECTOR (LT_PROJ_SECTOR), on top of a point projected by either function above --
+// its row, depth, pitch and keep conditions stay, the full-circle column is replaced.  `sec` (device, float64): the yaw of
+// the sector's middle yc = -azimuth_center and its width, both in radians; like pi they are rounded to T once.  d = yaw - yc
+// is brought into [-pi, pi) by one wrap (|yc| <= pi; a sector may straddle the seam behind the sensor), u = d / span + 0.5
+// is the position across the sector: kept iff 0 <= u < 1 as well, px = u * W, column = floor(px) clamped -- column w is the
+// cell [w, w + 1) * span / W, whose centre is the ray of that column (lt_create_rays_sector_dev).
+template <typename T>
+__device__ __forceinline__ void project_sector_column(proj_out<T>& o, T x, T y, T pi_t, int W, const double* __restrict__ sec) {
+  const T yc = (T)sec[0], span_t = (T)sec[1], twopi_t = (T)2 * pi_t;
+  const T yaw = -lt_atan2(y, x);
+  T d = yaw - yc;
+  if (d < -pi_t) d += twopi_t;
+  if (d >= pi_t) d -= twopi_t;
+  const T u = d / span_t + (T)0.5;
+  const bool in = u >= (T)0 && u < (T)1;  // (NaN: neither)
+  const T px = u * (T)W;
+  o.xf = px;
+  T fx = lt_floor(px);
+  fx = fx < (T)(W - 1) ? fx : (T)(W - 1);
+  fx = fx > (T)0 ? fx : (T)0;
+  o.px = (int)fx;
+  o.cell = (o.cell >= 0 && in) ? o.py * W + o.px : -1;
+}
+
 // The z-min key of one point (see the batched projection in lt_project.hip): hi word = float32 bits of the depth (positive
 // floats order like unsigned integers); lo word = 0x7fffffff - index for a point whose depth lies BELOW its float32 value
 // (they beat the others, the highest index first), 0x80000000 | index otherwise (lowest index first).  float32 clouds never

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void k_rs_fit(const float2* __restrict__ ang, 
 }
 
 // reduce the elevation partials (every workgroup redoes it: 2 KB), publish the grid, bin id per ray
-__global__ __launch_bounds__(256) void k_rs_keys(const float2* __restrict__ ang, int n, int nb_az, int nb_el,
+__global__ __launch_bounds__(256) void k_rs_keys(const float2* __restrict__ ang, int n, int nb_az, int nb_el, int refit,
                                                  const float* __restrict__ partial, rs_params* __restrict__ prm,
                                                  uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
   __shared__ float red[4][2];
@@ -139,9 +139,10 @@ __global__ __launch_bounds__(256) void k_rs_keys(const float2* __restrict__ ang,
   lo = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
   hi = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
   if (!(lo <= hi)) { lo = 0.f; hi = 0.f; }
-  // W - 1 columns when that grid clearly fits the rays better (inclusive [-pi, pi] models)
+  // W - 1 columns when that grid clearly fits the rays better (inclusive [-pi, pi] models); a caller who chose the number
+  // of columns (lt_rayset_create_grid_dev) keeps it: `refit` is 0 and k_rs_fit did not run
   const int nb_max = nb_az;
-  if (nb_az >= 5 && prm->dev_fit[1] + 0.01f < prm->dev_fit[0]) nb_az -= 1;
+  if (refit && nb_az >= 5 && prm->dev_fit[1] + 0.01f < prm->dev_fit[0]) nb_az -= 1;
   rs_params p;
   p.nb_az = nb_az; p.nb_el = nb_el;
   p.az_scale = (float)nb_az / (2.0f * LT_PI_F);
@@ -978,10 +979,13 @@ extern "C" int lt_rayset_destroy(lt_rayset* r) {
   return LT_OK;
 }
 
-extern "C" int lt_rayset_create_dev(lt_rayset** out, const float* rays, int n_rays, int height, unsigned flags,
-                                    void* stream_) {
-  if (!out || n_rays < 0 || height <= 0 || (n_rays > 0 && !rays)) {
-    lt_set_error("lt_rayset_create_dev: invalid argument (n_rays=%d height=%d)", n_rays, height);
+// The one body of lt_rayset_create_dev (grid_az = grid_el = 0) and lt_rayset_create_grid_dev: grid_az / grid_el > 0 are the
+// caller's numbers of azimuth / elevation bins (clamped to 8192 / 4096), 0 is the image's own rule for that axis -- W
+// columns refitted to W - 1 by k_rs_keys, `height` rows.  A chosen grid_az is not refitted.
+static int rs_create(const char* who, lt_rayset** out, const float* rays, int n_rays, int height, int grid_az, int grid_el,
+                     unsigned flags, void* stream_) {
+  if (!out || n_rays < 0 || height <= 0 || grid_az < 0 || grid_el < 0 || (n_rays > 0 && !rays)) {
+    lt_set_error("%s: invalid argument (n_rays=%d height=%d nb_az=%d nb_el=%d)", who, n_rays, height, grid_az, grid_el);
     return LT_ERR_INVALID_ARG;
   }
   *out = nullptr;
@@ -996,15 +1000,16 @@ extern "C" int lt_rayset_create_dev(lt_rayset** out, const float* rays, int n_ra
   r->n_rays = n;
   r->height = height;
   r->norm_flags = flags & (LT_TRACE_NORM_EXACT | LT_TRACE_NORM_AMD);
-  r->nb_az = W < 1 ? 1 : (W > 8192 ? 8192 : W);
-  r->nb_el = height > 4096 ? 4096 : height;
+  const int want_az = grid_az > 0 ? grid_az : W, want_el = grid_el > 0 ? grid_el : height;
+  r->nb_az = want_az < 1 ? 1 : (want_az > 8192 ? 8192 : want_az);
+  r->nb_el = want_el > 4096 ? 4096 : want_el;
   const size_t nbins = (size_t)r->nb_az * r->nb_el + 1;  // + the NaN bin
   const size_t nn = n > 0 ? n : 1;
   const int nb = (int)((nn + LT_SORT_TILE - 1) / LT_SORT_TILE);
   int rc = LT_OK;
 #define RS_ALLOC(ptr, bytes)                                                  \
   if (rc == LT_OK && hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) {      \
-    lt_set_error("lt_rayset_create_dev: hipMalloc of %zu bytes failed", (size_t)(bytes)); \
+    lt_set_error("%s: hipMalloc of %zu bytes failed", who, (size_t)(bytes)); \
     rc = LT_ERR_NO_MEMORY;                                                    \
   }
   RS_ALLOC(r->dirs, nn * sizeof(float4));
@@ -1026,16 +1031,17 @@ extern "C" int lt_rayset_create_dev(lt_rayset** out, const float* rays, int n_ra
     return rc;
   }
   if (hipMemsetAsync(r->prm, 0, sizeof(rs_params), stream) != hipSuccess) {
-    lt_set_error("lt_rayset_create_dev: hipMemsetAsync failed");
+    lt_set_error("%s: hipMemsetAsync failed", who);
     rs_free(r);
     free(r);
     return LT_ERR_HIP;
   }
   hipLaunchKernelGGL(k_rs_dirs, dim3(256), dim3(256), 0, stream, rays, n, r->norm_flags, r->dirs, r->ang, r->partial);
   // (prm->dev_az / dev_el start at 0: hipMemsetAsync below, before k_rs_keys accumulates them)
-  hipLaunchKernelGGL(k_rs_fit, dim3(64), dim3(256), 0, stream, r->ang, n, r->nb_az, r->prm);
+  const int refit = grid_az > 0 ? 0 : 1;
+  if (refit) hipLaunchKernelGGL(k_rs_fit, dim3(64), dim3(256), 0, stream, r->ang, n, r->nb_az, r->prm);
   hipLaunchKernelGGL(k_rs_keys, dim3((n + 255) / 256 > 0 ? (n + 255) / 256 : 1), dim3(256), 0, stream, r->ang, n,
-                     r->nb_az, r->nb_el, r->partial, r->prm, r->keys[0], r->vals[0]);
+                     r->nb_az, r->nb_el, refit, r->partial, r->prm, r->keys[0], r->vals[0]);
   int buf = 0;
   if (n > 0) lt_sort_pairs(r->keys, r->vals, r->hist, n, 30, stream, &buf);
   r->bin_rays = r->vals[buf];
@@ -1047,7 +1053,7 @@ extern "C" int lt_rayset_create_dev(lt_rayset** out, const float* rays, int n_ra
                      (int)nbins, r->grid);
   const hipError_t le = hipGetLastError();
   if (le != hipSuccess) {
-    lt_set_error("lt_rayset_create_dev: kernel launch failed: %s", hipGetErrorString(le));
+    lt_set_error("%s: kernel launch failed: %s", who, hipGetErrorString(le));
     (void)hipStreamSynchronize(stream);
     rs_free(r);
     free(r);
@@ -1057,7 +1063,7 @@ extern "C" int lt_rayset_create_dev(lt_rayset** out, const float* rays, int n_ra
   // used on any stream
   if (hipStreamSynchronize(stream) != hipSuccess ||
       hipMemcpy(&r->prm_host, r->prm, sizeof(rs_params), hipMemcpyDeviceToHost) != hipSuccess) {
-    lt_set_error("lt_rayset_create_dev: ray set preparation failed: %s", hipGetErrorString(hipGetLastError()));
+    lt_set_error("%s: ray set preparation failed: %s", who, hipGetErrorString(hipGetLastError()));
     rs_free(r);
     free(r);
     return LT_ERR_HIP;
@@ -1065,6 +1071,16 @@ extern "C" int lt_rayset_create_dev(lt_rayset** out, const float* rays, int n_ra
   rs_derive(r->prm_host);
   *out = r;
   return LT_OK;
+}
+
+extern "C" int lt_rayset_create_dev(lt_rayset** out, const float* rays, int n_rays, int height, unsigned flags,
+                                    void* stream) {
+  return rs_create("lt_rayset_create_dev", out, rays, n_rays, height, 0, 0, flags, stream);
+}
+
+extern "C" int lt_rayset_create_grid_dev(lt_rayset** out, const float* rays, int n_rays, int height, int nb_az, int nb_el,
+                                         unsigned flags, void* stream) {
+  return rs_create("lt_rayset_create_grid_dev", out, rays, n_rays, height, nb_az, nb_el, flags, stream);
 }
 
 // Per-scene state of a render: the z-min cells (one per ray, armed = all-ones; k_sc_resolve re-arms what it reads,

@@ -33,7 +33,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _chain, _lib
-from .raytracer import RaySet, Scene
+from .raytracer import RaySet, Scene, sector_grid
 
 
 class MergeMeshState:
@@ -135,7 +135,7 @@ class DeviceDeform:
 
     def __init__(self, source, target, vol_bnds=None, voxel_size=0.1, beam_angles=None, t_beam_angles=None,
                  preserve_float=False, device=None, merge=True, fusion="cuda", mesh_volume=True, rayset=None, mm_state=None,
-                 transformation=None, t_beam_table=None):
+                 transformation=None, t_beam_table=None, t_sector=None):
         """``fusion``: ``"cuda"`` -- the arithmetic of the reference's CUDA kernel (class-aware with ``merge``), or ``"numpy"`` --
         that of its numpy branch (``FUSION_GPU_MODE == 0``, fusion_lidar.py:290-388; what goldens F13 / F14 are made by).
         ``vol_bnds``: [3,2]; for :meth:`mergemesh` it is STATE, clipped in place call after call exactly as the reference
@@ -154,7 +154,15 @@ class DeviceDeform:
         there is a ``transformation`` as well), so ``mesh`` and ``mergemesh`` change by their rays alone, and ``cp`` puts a
         point into the row of its nearest beam (``LT_PROJ_BEAM_ROWS``) and re-projects it along that beam
         (``lt_reverse_projection_beams_dev``).  A shared ``rayset`` must have been built for the same table
-        (``RaySet(..., beam_table=...)``)."""
+        (``RaySet(..., beam_table=...)``).
+        ``t_sector``: the TARGET sensor's horizontal sector (``SensorModel.sector()``: ``(center_deg, span_deg)``; ``None``: the
+        full circle, nothing of this runs) -- the target's ``t_W`` columns span the sector alone: its rays leave through the
+        centres of the sector's cells (with a table and a pose as above), so ``mesh`` and ``mergemesh`` change by their rays
+        and by the ray set's bin grid, which is laid out at the sector's resolution (``raytracer.sector_grid``), alone
+        (``mergemesh`` still fuses what the source origin sees inside the target's vertical field of view); ``cp`` puts a
+        point into the column whose ray is nearest, drops what lies outside the sector (``LT_PROJ_SECTOR``) and re-projects
+        it along that ray (``lt_reverse_projection_sector_dev``).  A shared ``rayset`` must have been built for the same
+        sector (``RaySet(..., sector=...)``)."""
         import numpy as np
         import torch
 
@@ -186,6 +194,11 @@ class DeviceDeform:
                                                  self.t_fov_down, "DeviceDeform: t_beam_table")
             self._t_rows = _chain.beam_rows_table(self.t_beam_table)     # marshalled once: Brad, halfw
             self._t_brad = torch.from_numpy(self._t_rows[2][:self.t_H].copy()).to(self.device)
+        self.t_sector = self._t_sec = None
+        if t_sector is not None:
+            from .config import check_sector
+            self.t_sector = check_sector(t_sector, "DeviceDeform: t_sector")
+            self._t_sec = _chain.sector_pair(self.t_sector)              # marshalled once: yaw of the middle, width (radians)
         # ``origin``: the target sensor in the scene, where mesh / mergemesh cast from by default
         self.mount, self.origin = self._mounting.pair, self._mounting.origin
         if mm_state is not None and vol_bnds is None:
@@ -203,8 +216,10 @@ class DeviceDeform:
             pose = self._mounting.P
             if rayset is None:
                 rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=idx,
-                                          rot=pose[:3, :3] if pose is not None else None, beam_table=self.t_beam_table)
-                self.rayset = RaySet(rays, self.t_H, pose=pose, beam_table=self.t_beam_table)
+                                          rot=pose[:3, :3] if pose is not None else None, beam_table=self.t_beam_table,
+                                          sector=self.t_sector)
+                self.rayset = RaySet(rays, self.t_H, pose=pose, beam_table=self.t_beam_table, sector=self.t_sector,
+                                     grid=None if self.t_sector is None else sector_grid(self.t_W, self.t_sector))
                 self._rays = rays
             else:
                 theirs = getattr(rayset, "pose", None)
@@ -214,6 +229,8 @@ class DeviceDeform:
                 if (theirs is None) != (self.t_beam_table is None) or \
                         (theirs is not None and not np.array_equal(theirs, self.t_beam_table)):
                     raise ValueError("DeviceDeform: the shared rayset was built for another beam table than `t_beam_table`")
+                if getattr(rayset, "sector", None) != self.t_sector:
+                    raise ValueError("DeviceDeform: the shared rayset was built for another sector than `t_sector`")
                 self.rayset = rayset
         self.n_rays = self.t_H * self.t_W
 
@@ -485,13 +502,19 @@ class DeviceDeform:
         rows = self._t_rows
         o = self.projector.project([_chain.merged_cloud(clouds)], self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, new=True,
                                    remove=True, beam_angles=self.t_beam_angles if rows is None else None, outputs=outs,
-                                   stream=st, beam_table=rows)[0]
+                                   stream=st, beam_table=rows, sector=self._t_sec)[0]
         px, py = (o["proj_xf"], o["proj_yf"]) if pf else (o["proj_x"], o["proj_y"])
         if pf and px.dtype != torch.float64:
             px, py = px.double(), py.double()
         back = torch.empty((self.n_rays, 3), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            if rows is not None:    # along the winner's beam (or its own pitch with preserve_float)
+            if self._t_sec is not None:   # along the ray of the winner's column (or its own yaw with preserve_float)
+                _lib.check(lib.lt_reverse_projection_sector_dev(
+                    o["range"].data_ptr(), px.data_ptr(), py.data_ptr(), int(pf), int(rows is not None),
+                    self._t_brad.data_ptr() if rows is not None else None, self.t_fov_up, self.t_fov_down, self.t_H, self.t_W,
+                    float(self._t_sec[0]), float(self._t_sec[1]), back.data_ptr(), C.c_void_p(st.cuda_stream)),
+                    "lt_reverse_projection_sector_dev")
+            elif rows is not None:    # along the winner's beam (or its own pitch with preserve_float)
                 _lib.check(lib.lt_reverse_projection_beams_dev(o["range"].data_ptr(), px.data_ptr(), py.data_ptr(), int(pf),
                                                                self._t_brad.data_ptr(), self.t_H, self.t_W, back.data_ptr(),
                                                                C.c_void_p(st.cuda_stream)), "lt_reverse_projection_beams_dev")

@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 
 
-def create_rays(fov_up, fov_down, H, W, beam_table=None):
+def create_rays(fov_up, fov_down, H, W, beam_table=None, sector=None):
     """Unit ray direction per (beam, azimuth) cell, ``float32 [H*W, 3]``, row-major ``h*W + w``.
 
     Restatement of ``MultiSemLaserScan.create_rays`` (auxiliary/laserscan.py:1092-1119), quirks
@@ -13,9 +13,16 @@ def create_rays(fov_up, fov_down, H, W, beam_table=None):
     the same direction; ``beam_angles`` are ignored; float64 trigonometry, cast to float32 last.
     ``beam_table`` (``SensorModel.beam_table()``: [H] degrees, row 0 first) takes the place of
     ``linspace(fov_up, fov_down, H)``: the rays of a sensor whose beams are not evenly spaced.
+    ``sector`` (``SensorModel.sector()``: ``(center_deg, span_deg)``): the W columns span that sector alone --
+    column w is the cell ``[w, w + 1) * span / W`` from the sector's left edge, clockwise seen from above, and its ray
+    leaves through the cell's centre (no closed-``linspace`` quirk: a sector does not close).
     """
-    yaw = np.linspace(0, 360, W) + 180
-    yaw[yaw > 360] -= 360
+    if sector is None:
+        yaw = np.linspace(0, 360, W) + 180
+        yaw[yaw > 360] -= 360
+    else:
+        c, s = (float(v) for v in sector)
+        yaw = (-c - s / 2) + (np.arange(W, dtype=np.float64) + 0.5) * (s / W)   # not wrapped: sin and cos are periodic
     yaw = yaw / 180. * np.pi
     pitch = np.pi / 2 - _beam_degrees(beam_table, fov_up, fov_down, H) / 180. * np.pi
     sp, cp = np.sin(pitch), np.cos(pitch)
@@ -35,11 +42,12 @@ def _beam_degrees(beam_table, fov_up, fov_down, H):
     return b
 
 
-def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=None, beam_table=None):
+def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=None, beam_table=None, sector=None):
     """:func:`create_rays` computed by the HIP kernel into a ``torch`` tensor ``[H*W, 3] f32`` on the GPU.  ``rot``: the
     rotation [3, 3] of the sensor's pose (``Approach.mount()[1][:3, :3]``) -- every direction is turned by it in float64,
     ``(r0 * x + r1 * y) + r2 * z`` per component, before the cast to float32; ``None``: the sensor's own frame.
-    ``beam_table``: as for :func:`create_rays` (``lt_create_rays_beams_dev``; the call waits for ``stream``)."""
+    ``beam_table``: as for :func:`create_rays` (``lt_create_rays_beams_dev``; the call waits for ``stream``).
+    ``sector``: as for :func:`create_rays` (``lt_create_rays_sector_dev``, with or without a table and a rotation)."""
     import ctypes as C
 
     import torch
@@ -55,7 +63,16 @@ def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=Non
         if r.shape != (3, 3):
             raise ValueError("rot: a 3x3 rotation")
     with torch.cuda.device(dev):
-        if beam_table is not None:
+        if sector is not None:
+            from .config import check_sector
+            c, s = check_sector(sector, "create_rays_device: sector")
+            dp = C.POINTER(C.c_double)
+            b = _beam_degrees(beam_table, fov_up, fov_down, H) if beam_table is not None else None
+            _lib.check(lib.lt_create_rays_sector_dev(b.ctypes.data_as(dp) if b is not None else None, float(fov_up),
+                                                     float(fov_down), int(H), int(W), c, s,
+                                                     r.ctypes.data_as(dp) if r is not None else None, out.data_ptr(),
+                                                     C.c_void_p(st.cuda_stream)), "lt_create_rays_sector_dev")
+        elif beam_table is not None:
             b = _beam_degrees(beam_table, fov_up, fov_down, H)
             dp = C.POINTER(C.c_double)
             _lib.check(lib.lt_create_rays_beams_dev(b.ctypes.data_as(dp), int(H), int(W),
@@ -90,7 +107,10 @@ class Projector:
     everywhere for the old variant (:37-53).  ``beam_table`` (``SensorModel.beam_table()``, [H] degrees descending; with
     ``new`` and ``remove`` only): the rows are the beams of the table (``LT_PROJ_BEAM_ROWS``) -- a point goes to its nearest
     beam and is kept only within half the gap to that beam's nearer neighbour; ``proj_y`` is the row, ``proj_yf`` the
-    winner's pitch in radians, empty cells hold 0 in ``proj_x`` / ``proj_y`` / ``proj_xf`` / ``proj_yf``."""
+    winner's pitch in radians, empty cells hold 0 in ``proj_x`` / ``proj_y`` / ``proj_xf`` / ``proj_yf``.  ``sector``
+    (``SensorModel.sector()``, ``(center_deg, span_deg)``; with ``new`` and ``remove`` only, with or without a table): the
+    columns are those of the sector (``LT_PROJ_SECTOR``) -- a point outside it is dropped, ``proj_xf`` is its position
+    across the sector times ``W``, ``proj_x`` the column whose ray is nearest."""
 
     _IMG = {"idx": ("int32", 1), "range": ("float32", 1), "xyz": ("float32", 3), "rem": ("float32", 1), "label": ("int32", 1),
             "color": ("float32", 3), "mask": ("float32", 1), "label_folded": ("float32", 1), "proj_x": ("int32", 1),
@@ -111,7 +131,7 @@ class Projector:
         self._h = h
 
     def project(self, clouds, fov_up, fov_down, H, W, new=True, remove=False, beam_angles=None, color_lut=None,
-                outputs=("range", "rem", "label"), out=None, stream=None, beam_table=None):
+                outputs=("range", "rem", "label"), out=None, stream=None, beam_table=None, sector=None):
         import ctypes as C
 
         from . import _lib
@@ -165,6 +185,13 @@ class Projector:
             flags |= _lib.LT_PROJ_BEAM_ROWS
             beams = beam_rows_table(beam_table)[2]
         n_beams = 0 if beams is None else (int(H) if beam_table is not None else len(beams))
+        if sector is not None:       # set when it changes; the flag reads it
+            from ._chain import sector_pair
+            flags |= _lib.LT_PROJ_SECTOR
+            sec = tuple(float(v) for v in sector_pair(sector))
+            if sec != getattr(self, "_sector", None):
+                _lib.check(self._lib.lt_projector_set_sector(self._h, sec[0], sec[1]), "lt_projector_set_sector")
+                self._sector = sec
         init = (0.0, -1.0, 0.0) if new else (-1.0, -1.0, -1.0)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.lt_range_projection_batch_dev(

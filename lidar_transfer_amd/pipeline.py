@@ -314,10 +314,14 @@ class FusionScanPipeline:
     Empty, ``None`` or the identity: nothing changes.
 
     A target sensor with a beam table (``SensorModel.beam_table()``) needs nothing but its rays: pass
-    ``create_rays_device(..., beam_table=table)`` (with ``rot`` when it is mounted as well) as ``rays``."""
+    ``create_rays_device(..., beam_table=table)`` (with ``rot`` when it is mounted as well) as ``rays``.
+
+    A target sensor with a horizontal sector (``SensorModel.sector()``) needs its rays,
+    ``create_rays_device(..., sector=sector)``, and -- for speed alone -- a bin grid at the sector's resolution:
+    ``grid=sector_grid(W, sector)`` (``raytracer.sector_grid``; ``grid`` goes to the ``RaySet``, ``None``: the image's rule)."""
 
     def __init__(self, vol_bnds, voxel_size, fov_up, fov_down, rays, H, chains=3, device=None, merge=True,
-                 label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None):
+                 label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None, grid=None):
         import queue
         import threading
         import weakref
@@ -334,7 +338,7 @@ class FusionScanPipeline:
         self.device = torch.device("cuda", idx)
         self._mounting = _chain.Mount(transformation)
         self.mount, self.origin = self._mounting.pair, self._mounting.origin
-        self.rayset = RaySet(rays, H, pose=self._mounting.P)  # one read-only ray set for all chains
+        self.rayset = RaySet(rays, H, pose=self._mounting.P, grid=grid)  # one read-only ray set for all chains
         self.n_rays = self.rayset.n_rays
         self.label_image = bool(label_image)
         self._flags = _lib.LT_TRACE_WRITE_MISSES | (_lib.LT_TRACE_LABEL_IMAGE if label_image else 0)

@@ -263,15 +263,29 @@ class Scene:
         _lib.check(self._lib.lt_scene_status(self._h), "lt_scene_status")
 
 
+def sector_grid(W, sector):
+    """The bin grid of a sector sensor's ray set, ``RaySet(..., grid=sector_grid(W, sector))``: the azimuth bins at the
+    sector's own resolution, ``min(8192, round(W * 360 / span))`` over the full circle, so that its rays sit on (or, when
+    that is no integer, within ``0.5 * span / 360`` of a bin of) the bin centres; the elevation axis by the image's rule."""
+    return min(8192, int(round(int(W) * 360.0 / float(sector[1])))), 0
+
+
 class RaySet:
     """A ray batch prepared for :meth:`Scene.render` (``lt_rayset`` in include/lidarhip.h): directions
     normalised like the reference (Vector3.h:73-89) and binned by azimuth x elevation.  One per sensor
     model; reuse it for every scan.  ``pose``: the [4, 4] pose of the sensor the rays were generated for (``None``: its own
-    frame) and ``beam_table``: the beam table the rays were generated from (``None``: evenly spaced beams) -- only remembered,
-    so that a chain handed a shared ray set can tell whether it was built for its sensor."""
+    frame), ``beam_table``: the beam table the rays were generated from (``None``: evenly spaced beams) and ``sector``: the
+    ``(center_deg, span_deg)`` the columns span (``None``: the full circle) -- only remembered, so that a chain handed a
+    shared ray set can tell whether it was built for its sensor.  ``grid``: ``(nb_az, nb_el)``, the size of the bin grid
+    (``lt_rayset_create_grid_dev``; 0 = the image's own rule for that axis, ``None`` = ``(0, 0)``) -- any grid renders the same
+    image, the fastest is the one whose bin centres the rays sit on: :func:`sector_grid` for a sector."""
 
-    def __init__(self, rays, H, exact_normalize=False, stream=None, pose=None, beam_table=None):
+    def __init__(self, rays, H, exact_normalize=False, stream=None, pose=None, beam_table=None, sector=None, grid=None):
         import torch
+        self.sector = None if sector is None else (float(sector[0]), float(sector[1]))
+        self.grid = None if grid is None else (int(grid[0]), int(grid[1]))
+        if self.grid is not None and min(self.grid) < 0:
+            raise ValueError("grid: (nb_az, nb_el), both >= 0")
         self.pose = None if pose is None else np.array(pose, dtype=np.float64).reshape(4, 4)
         self.beam_table = None if beam_table is None else np.array(beam_table, dtype=np.float64).reshape(-1)
         if not isinstance(rays, torch.Tensor) or rays.dtype != torch.float32 or not rays.is_contiguous() \
@@ -283,9 +297,14 @@ class RaySet:
         st = torch.cuda.current_stream(rays.device) if stream is None else stream
         h = C.c_void_p()
         with torch.cuda.device(rays.device):
-            _lib.check(self._lib.lt_rayset_create_dev(C.byref(h), rays.data_ptr(), rays.numel() // 3, int(H),
-                                                      _norm_flag(exact_normalize),
-                                                      C.c_void_p(st.cuda_stream)), "lt_rayset_create_dev")
+            if self.grid is None:
+                _lib.check(self._lib.lt_rayset_create_dev(C.byref(h), rays.data_ptr(), rays.numel() // 3, int(H),
+                                                          _norm_flag(exact_normalize),
+                                                          C.c_void_p(st.cuda_stream)), "lt_rayset_create_dev")
+            else:
+                _lib.check(self._lib.lt_rayset_create_grid_dev(C.byref(h), rays.data_ptr(), rays.numel() // 3, int(H),
+                                                               self.grid[0], self.grid[1], _norm_flag(exact_normalize),
+                                                               C.c_void_p(st.cuda_stream)), "lt_rayset_create_grid_dev")
             st.synchronize()
         self._h = h
 

@@ -110,7 +110,9 @@ class SequenceTransfer:
     ``evaluate=True`` raises; ``mounted`` tells.  A target ``SensorModel`` with ``beam_model: table`` brings its beam table
     (``DeviceDeform(t_beam_table=...)``): the source scan is projected by the evenly spaced model and cannot be compared row
     for row, so ``evaluate`` behaves as for a mounted target; ``beam_model`` tells.  A source sensor with a table is
-    refused."""
+    refused.  A target ``SensorModel`` with ``azimuth_model: sector`` brings its sector (``DeviceDeform(t_sector=...)``): its
+    columns are not the source scan's full-circle columns, so ``evaluate`` behaves the same way; ``azimuth_model`` tells.  A
+    source sensor with a sector is refused."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -121,12 +123,15 @@ class SequenceTransfer:
         if int(chains) < 1:
             raise ValueError("chains: at least one")
         self.approach, self.adaption = approach, approach.adaption
-        from .config import refuse_source_table
+        from .config import refuse_source_sector, refuse_source_table
         refuse_source_table(source_sensor)
+        refuse_source_sector(source_sensor)
         self.source_sensor, self.target_sensor = sensor_tuple(source_sensor), sensor_tuple(target_sensor)
         # (sensor_tuple drops the table; ValueError on one that cannot be used)
         self.beam_table = target_sensor.beam_table() if hasattr(target_sensor, "beam_table") else None
         self.beam_model = "linear" if self.beam_table is None else "table"
+        self.sector = target_sensor.sector() if hasattr(target_sensor, "sector") else None
+        self.azimuth_model = "full" if self.sector is None else "sector"
         self.chains = 1 if self.adaption == "cp" else int(chains)     # `cp` always runs on one chain
         self.fusion, self.out_dir = fusion, out_dir
         self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
@@ -142,7 +147,11 @@ class SequenceTransfer:
         if evaluate and self.beam_table is not None:
             raise ValueError("evaluate: the target sensor has a beam table (beam_model: table): its rows are not the source "
                              "scan's evenly spaced rows, the two cannot be compared cell by cell")
-        self.evaluate = (same and not self.mounted and self.beam_table is None) if evaluate is None else bool(evaluate)
+        if evaluate and self.sector is not None:
+            raise ValueError("evaluate: the target sensor has a horizontal sector (azimuth_model: sector): its columns are not "
+                             "the source scan's full-circle columns, the two cannot be compared cell by cell")
+        self.evaluate = (same and not self.mounted and self.beam_table is None and self.sector is None) \
+            if evaluate is None else bool(evaluate)
         need = cache_scans_needed(approach.number_of_scans, self.chains, approach.batch_interval)
         idx = torch.cuda.current_device() if device is None else int(device)
         if isinstance(source_seq, SequenceSource):
@@ -171,13 +180,15 @@ class SequenceTransfer:
                 if self.adaption == "cp":
                     dd = DeviceDeform(self.source_sensor, self.target_sensor, None, beam_angles=beams,
                                       preserve_float=approach.preserve_float, device=idx, fusion=fusion,
-                                      transformation=self.mount, t_beam_table=self.beam_table)
+                                      transformation=self.mount, t_beam_table=self.beam_table,
+                                      t_sector=self.sector)
                 else:
                     dd = DeviceDeform(self.source_sensor, self.target_sensor,
                                       None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
                                       beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
                                       mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm,
-                                      transformation=self.mount, t_beam_table=self.beam_table)
+                                      transformation=self.mount, t_beam_table=self.beam_table,
+                                      t_sector=self.sector)
                     rayset = dd.rayset
                 ch = dict(dd=dd, ev=None, q=None, thread=None,
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
@@ -324,7 +335,7 @@ class SequenceTransfer:
                 job["done"].wait()
                 job["written"].wait()
             self.summary = dict(scans=n_done, chains=self.chains, adaption=self.adaption, fusion=self.fusion,
-                                mounted=self.mounted, beam_model=self.beam_model,
+                                mounted=self.mounted, beam_model=self.beam_model, azimuth_model=self.azimuth_model,
                                 mm_stats=dict(self._mm.stats) if self._mm is not None else None,
                                 source_stats=dict(self.source.stats))
 

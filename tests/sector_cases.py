@@ -1,0 +1,218 @@
+"""What the sector tests share (TEST INFRASTRUCTURE): the sectors, and host restatements of the three arithmetic contracts of a
+target sensor with a horizontal sector (``azimuth_model: sector``) -- its rays, the column of a projected point
+with the reference's sequential z-min loop, and the reverse projection -- in the operation order the contracts fix.  Nothing
+here imports ``lidar_transfer_amd`` for arithmetic; the row rule of a beam table is tests/beam_cases.py's."""
+from __future__ import annotations
+
+import numpy as np
+
+import beam_cases as bc
+
+#: (centre, span, W): W * 360 / span an integer; not an integer; straddling the seam behind the sensor; tiny
+SECTORS = ((0.0, 120.0, 256), (35.0, 70.4, 301), (170.0, 100.0, 200), (-90.0, 30.0, 7))
+#: the sectors of the ulp rule on the rays: (-90, 30, 7) has a cell centre exactly on -90 degrees
+RAY_SECTORS = SECTORS[:3]
+LT_BIN_SLACK = 4e-3
+
+
+def yaw_deg(sector, W):
+    """the yaw of every column's ray in degrees, float64 [W]: the centre of the cell [w, w + 1) * span / W, not wrapped"""
+    c, s = float(sector[0]), float(sector[1])
+    return (-c - s / 2) + (np.arange(W, dtype=np.float64) + 0.5) * (s / W)
+
+
+def rays_f64(sector, W, fov=None, H=None, table=None):
+    """the three float64 components of the sector's rays BEFORE the cast, [H*W, 3]: ``create_rays``' expressions
+    (laserscan.py:1092-1119) from the yaw above; rows ``linspace(fov_up, fov_down, H)`` or the table's angles"""
+    yaw = yaw_deg(sector, W) / 180. * np.pi
+    deg = np.linspace(fov[0], fov[1], H) if table is None else np.asarray(table, np.float64)
+    pitch = np.pi / 2 - deg / 180. * np.pi
+    sp, cp = np.sin(pitch), np.cos(pitch)
+    out = np.empty((len(pitch), W, 3), np.float64)
+    out[:, :, 0] = sp[:, None] * np.cos(-yaw)[None, :]
+    out[:, :, 1] = sp[:, None] * np.sin(-yaw)[None, :]
+    out[:, :, 2] = cp[:, None] * np.ones(W)[None, :]
+    return out.reshape(-1, 3)
+
+
+def sector_rays(sector, W, fov=None, H=None, table=None, rot=None):
+    """the sector's rays, float32 [H*W, 3]; with ``rot`` turned in float64 as ((r0 * x + r1 * y) + r2 * z) per component
+    before the one cast"""
+    d = rays_f64(sector, W, fov, H, table)
+    if rot is not None:
+        x, y, z = d[:, 0], d[:, 1], d[:, 2]
+        r = np.asarray(rot, np.float64)
+        d = np.stack([(r[k, 0] * x + r[k, 1] * y) + r[k, 2] * z for k in range(3)], 1)
+    return np.ascontiguousarray(d.astype(np.float32))
+
+
+def columns(points, sector, W):
+    """The column contract in the cloud's dtype T, constants rounded to T once: yaw = -atan2(y, x) (float32: through double,
+    rounded once); d = yaw - yc, one wrap into [-pi, pi); u = d / span + 0.5; inside iff 0 <= u < 1; px = u * W; column =
+    floor(px) clamped.  ``near``: px within 4 ulp of an integer or u within 4 ulp of 0 or 1, the ulp of the yaw scaled by
+    W / span included -- ``slack`` is that width per point (px = (yaw - yc) / span * W + W / 2 carries the yaw's rounding
+    with the factor W / span whatever its own size is)."""
+    pts = np.asarray(points)
+    T = pts.dtype.type
+    c, s = float(sector[0]), float(sector[1])
+    pi_t, twopi_t = T(np.pi), T(2 * np.pi)
+    yc, span_t = T(-c / 180. * np.pi), T(s / 180. * np.pi)
+    with np.errstate(all="ignore"):
+        yaw = -np.arctan2(pts[:, 1].astype(np.float64), pts[:, 0].astype(np.float64)).astype(pts.dtype)
+        d = yaw - yc
+        d = np.where(d < -pi_t, d + twopi_t, d)
+        d = np.where(d >= pi_t, d - twopi_t, d)
+        u = d / span_t + T(0.5)
+        inside = (u >= 0) & (u < 1)
+        px = u * T(W)
+        col = np.maximum(0, np.minimum(W - 1, np.floor(px)))
+        col = np.where(np.isnan(col), W - 1, col).astype(np.int32)
+        slack = 4 * np.spacing(np.abs(px)).astype(np.float64) + \
+            4 * np.spacing(np.abs(yaw)).astype(np.float64) * (W / float(span_t))
+        pxd, ud = px.astype(np.float64), u.astype(np.float64)
+        near = ((np.abs(pxd - np.round(pxd)) <= slack) & inside) | (np.abs(ud) * W <= slack) | (np.abs(ud - 1) * W <= slack)
+        near &= ~np.isnan(pxd)
+    return dict(yaw=yaw, u=u, px=px.astype(pts.dtype), col=col, inside=inside, near=near, slack=slack)
+
+
+def project(points, rem, label, sector, W, H, fov, table=None):
+    """``do_range_projection_new(remove=True)`` + ``do_label_projection_new`` (laserscan.py:294-391, :672-676) for a sensor
+    with a sector: rows by the reference's linear rule (or, with ``table``, by tests/beam_cases.py's row and keep rule), the
+    column and the extra keep condition by :func:`columns`, then the literal sequential loop of :372-382.  Returns the images
+    (``idx``: numbering of the kept points; ``proj_x`` / ``proj_y`` / ``proj_xf`` / ``proj_yf`` of the winner; an empty cell holds those of
+    the LAST kept point as numpy's index -1 does -- 0 with a table or when nothing was kept), ``xf_slack`` (per cell: 4 ulp of
+    the winner's ``proj_xf``, the ulp of its yaw scaled by W / span included), ``kept`` and ``near`` (masks over the input)
+    and ``col`` / ``row``."""
+    pts = np.asarray(points)
+    T = pts.dtype.type
+    cl = columns(pts, sector, W)
+    with np.errstate(all="ignore"):
+        depth = np.sqrt((pts[:, 0] * pts[:, 0] + pts[:, 1] * pts[:, 1]) + pts[:, 2] * pts[:, 2])
+        ratio = pts[:, 2] / depth
+        if table is None:
+            fu, fd = fov[0] / 180.0 * np.pi, fov[1] / 180.0 * np.pi
+            fovr = abs(fd) + abs(fu)
+            pitch = np.arcsin(ratio.astype(np.float64)).astype(pts.dtype) if pts.dtype == np.float32 else np.arcsin(ratio)
+            py = T(1.0) - (pitch + T(abs(fd))) / T(fovr)
+            ok = (depth != 0) & (py >= 0) & (py <= 1) & ~np.isnan(depth) & ~np.isnan(py)
+            py = py * T(H)
+            row = np.maximum(0, np.minimum(H - 1, np.floor(py)))
+            row = np.where(np.isnan(row), 0, row).astype(np.int32)
+            near_row = np.zeros(len(pts), bool)
+            yf = py
+        else:
+            full = bc.project(pts, None, None, table, fov, W)            # rows and their keep rule; its columns are not used
+            ok, row, near_row, yf = full["kept"], full["row"].astype(np.int32), full["near"], full["pitch"]
+    kept = ok & cl["inside"]
+    near = (cl["near"] | near_row) & ok
+    col = cl["col"]
+    kd, kc, kr, kxf, kyf, ksl = depth[kept], col[kept], row[kept], cl["px"][kept], yf[kept], cl["slack"][kept]
+    krem = np.asarray(rem)[kept] if rem is not None else None
+    klab = np.asarray(label)[kept] if label is not None else None
+    index = np.full((H, W), -1, np.int32)
+    range_image = np.full((H, W), 0, np.float32)
+    rem_image = np.full((H, W), -1, np.float32)
+    for i in range(len(kd)):                                   # laserscan.py:373-382
+        y, x = kr[i], kc[i]
+        if kd[i] < range_image[y, x] or index[y, x] == -1:
+            range_image[y, x] = kd[i]
+            index[y, x] = i
+            if krem is not None:
+                rem_image[y, x] = krem[i]
+    n = len(kd)
+    last = index.copy()
+    if table is None and n:
+        last[last < 0] = n - 1                                    # numpy's index -1: the last kept point
+    has = last >= 0
+    win = np.where(has, last, 0)
+    pick = lambda a, zero: np.where(has, a[win], zero) if n else np.full((H, W), zero, a.dtype)   # noqa: E731
+    occupied = index >= 0
+    lab_image = np.where(occupied, klab.astype(np.int32)[np.where(occupied, index, 0)], 0) if (klab is not None and n) \
+        else np.zeros((H, W), np.int32)
+    return dict(idx=index, range=range_image, rem=rem_image, label=lab_image.astype(np.int32),
+                proj_x=pick(kc, np.int32(0)).astype(np.int32), proj_y=pick(kr, np.int32(0)).astype(np.int32),
+                proj_xf=pick(kxf, T(0)).astype(pts.dtype), proj_yf=pick(kyf, T(0)).astype(pts.dtype),
+                xf_slack=pick(ksl, np.float64(0)), kept=kept, near=near, row=row, col=col, inside=cl["inside"])
+
+
+def near_cells(p, W):
+    """[H, W] mask of the cells a point flagged ``near`` may touch: its own column and row and the ones beside them (the
+    columns periodically: an edge point may fall out of the sector instead)"""
+    H = p["idx"].shape[0]
+    m = np.zeros((H, W), bool)
+    r, c = p["row"][p["near"]], p["col"][p["near"]]
+    for dr in (-1, 0, 1):
+        for dc in (-1, 0, 1):
+            m[np.clip(r + dr, 0, H - 1), np.clip(c + dc, 0, W - 1)] = True
+    return m
+
+
+def reverse_projection(range_image, proj_x, proj_y, sector, fov, preserve_float, table=None):
+    """float64 [H*W, 3]: yaw = yc + ((px + 0.5) / W - 0.5) * span from the int32 column, yaw = yc + (xf / W - 0.5) * span with
+    ``preserve_float``; the elevation by ``do_reverse_projection_new``'s linear rule (laserscan.py:475-501) or the table's
+    (tests/beam_cases.py); the three products left to right"""
+    depth = np.asarray(range_image)
+    H, W = depth.shape
+    c, s = float(sector[0]), float(sector[1])
+    yc, span = -c / 180. * np.pi, s / 180. * np.pi
+    px = np.asarray(proj_x, np.float64)
+    x = px / W if preserve_float else (px + 0.5) / W
+    yaw = yc + (x - 0.5) * span
+    if table is None:
+        fu, fd = fov[0] / 180.0 * np.pi, fov[1] / 180.0 * np.pi
+        fovr = abs(fd) + abs(fu)
+        y = np.asarray(proj_y, np.float64) / H
+        pitch = np.pi / 2 - (1.0 * fovr - y * fovr - abs(fd))
+    else:
+        Brad = bc.rows_of(table)[0]
+        e = np.asarray(proj_y, np.float64) if preserve_float else Brad[np.asarray(proj_y)]
+        pitch = np.pi / 2 - e
+    X = depth * np.sin(pitch) * np.cos(-yaw)
+    Y = depth * np.sin(pitch) * np.sin(-yaw)
+    Z = depth * np.cos(pitch)
+    return np.stack([X, Y, Z], 2).reshape(-1, 3)
+
+
+def seeded_cloud(sector, fov, n, dtype, seed):
+    """``n`` random points over the FULL circle (depth 2 .. 60 m, elevations over the field of view and a little beyond) whose
+    first rows are the chosen ones: on the sector's left edge, on its right edge, 1e-3 rad outside either, on the centre,
+    behind the seam (from 1000 points on: the points ON an edge are near a boundary by construction, and a small cloud has
+    no room for them under the cap on such points), at depth 0 and NaN (from 16 points on); above 64 points an eighth of the
+    random ones twice and once at half the depth (the z-min and its tie rule).  Returns (points [n, 3] dtype, rem [n] f32,
+    label [n] i32)."""
+    rng = np.random.default_rng(seed)
+    c, s = np.radians(sector[0]), np.radians(sector[1])
+    fu, fd = np.radians(fov[0]), np.radians(fov[1])
+    el = rng.uniform(fd - 0.03, fu + 0.03, n)
+    az = rng.uniform(-np.pi, np.pi, n)
+    dist = rng.uniform(2.0, 60.0, n)
+    mid = (fu + fd) / 2
+    if n < 16:                                                    # one or two points: inside the sector, or nothing is kept
+        az, el = c + rng.uniform(-0.4, 0.4, n) * s, rng.uniform(0.8 * fd + 0.2 * fu, 0.2 * fd + 0.8 * fu, n)
+    special = [c + s / 2, c - s / 2, c + s / 2 + 1e-3, c - s / 2 - 1e-3, c, np.pi, -np.pi, np.nextafter(np.pi, 0), c + np.pi]
+    if n < 1000:
+        special = []
+    for j, a in enumerate(special):
+        az[j], el[j] = a, mid
+    pts = np.stack([dist * np.cos(el) * np.cos(az), dist * np.cos(el) * np.sin(az), dist * np.sin(el)], 1).astype(dtype)
+    for j, v in enumerate(([0, 0, 0], [np.nan, 1, 1], [1, 1, np.nan])):
+        if n >= 16:
+            pts[len(special) + j] = v
+    if n > 64:
+        m = n // 8
+        pts[n // 2:n // 2 + m] = pts[16:16 + m]
+        pts[n // 2 + m:n // 2 + 2 * m] = pts[16:16 + m] * dtype(0.5)
+    rem = rng.random(n).astype(np.float32)
+    lab = rng.integers(1, 250, n).astype(np.int32)
+    return np.ascontiguousarray(pts), rem, lab
+
+
+def grid_dev_az(rays, W, nb_az):
+    """float64 restatement of the ray set's ``dev_az``: the largest distance of a ray's azimuth from the centre of its bin on
+    a grid of ``nb_az`` columns over the full circle with the phase of ray 0"""
+    r = np.asarray(rays, np.float64)
+    phi = np.arctan2(r[:, 1], r[:, 0])
+    sc = nb_az / (2 * np.pi)
+    x0 = (phi[0] + np.pi) * sc
+    x = (phi + np.pi) * sc - (x0 - np.floor(x0 + 0.5))
+    return float(np.abs(x - np.floor(x + 0.5)).max())

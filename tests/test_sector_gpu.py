@@ -1,0 +1,789 @@
+"""A target sensor with a horizontal sector (``azimuth_model: sector``), on the device: its rays against the float64
+restatement; a render of the sector's ray set on the fitted and on the default bin grid and by the LBVH against the
+brute-force oracle and the compiled reference raytracer; ``lt_rayset_create_grid_dev`` against ``lt_rayset_create_dev``; the
+column rule of ``LT_PROJ_SECTOR`` against the literal sequential loop; the reverse projection; the round trip of the rays;
+``DeviceDeform`` / ``SequenceTransfer`` / the CLI with a sector target against a chain composed here from the independent
+pieces of tests/oracle_chain.py on the product's downloaded sector rays; and the guard that a target without a sector takes
+exactly the path it took.  Restatements: tests/sector_cases.py; the conditions on the inputs: tests/test_sector_cpu.py."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+import beam_cases as bc  # noqa: E402
+import mount_common as mc  # noqa: E402
+import sector_cases as sc  # noqa: E402
+import test_beam_table_gpu as btg  # noqa: E402
+import test_evaluate_cpu as ev  # noqa: E402
+import test_ingest_cpu as cpu  # noqa: E402
+import test_mount_gpu as tm  # noqa: E402
+import test_sector_cpu as stc  # noqa: E402
+import test_sequence_cpu as sq  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+LT_ERR_INVALID_ARG = -1
+T_EXAMPLE = tm.T_EXAMPLE
+LINEAR_FOV = stc.LINEAR_FOV
+#: the F17 sequence's target of these tests: a (0, 120) sector on 32 x 171
+SEQ_SECTOR = (0.0, 120.0)
+SEQ_TARGET = (32, 171, 3.0, -25.0)
+_bits, _differs, _up = btg._bits, btg._differs, btg._up
+
+
+def _rows(kind):
+    """(table, fov, H) of the two row models the tests combine a sector with"""
+    return (None, LINEAR_FOV, 16) if kind == "linear" else (bc.VLP32C, bc.VLP32C_FOV, 32)
+
+
+# ---- 1: rays --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("posed", [False, True])
+@pytest.mark.parametrize("si", range(len(sc.RAY_SECTORS)))
+def test_device_rays_of_a_sector_equal_the_restatement(si, posed):
+    from lidar_transfer_amd.laserscan import create_rays_device
+    c, s, W = sc.RAY_SECTORS[si]
+    rot = mc.POSE_GENERAL[:3, :3] if posed else None
+    for table, fov, H in ((None, LINEAR_FOV, 1), (None, LINEAR_FOV, 16), (bc.VLP32C, bc.VLP32C_FOV, 32)):
+        dev = create_rays_device(fov[0], fov[1], H, W, rot=rot, beam_table=table, sector=(c, s)).cpu().numpy()
+        assert dev.shape == (H * W, 3) and dev.dtype == np.float32
+        n = tm._rays_rule(dev, sc.sector_rays((c, s), W, fov, H, table, rot), (c, s, W, H, posed))
+        assert np.abs(np.linalg.norm(dev.astype(np.float64), axis=1) - 1).max() < 1e-6
+        print(f"\nsector ({c}, {s}) x {H} x {W}, posed {posed}: {n} of {dev.size} elements not bit-equal to the restatement")
+
+
+def test_sector_rays_without_a_rotation_and_with_the_identity_are_equal_by_value():
+    from lidar_transfer_amd.laserscan import create_rays_device
+    for c, s, W in sc.SECTORS:
+        for table, fov, H in (_rows("linear"), _rows("table")):
+            none = create_rays_device(fov[0], fov[1], H, W, beam_table=table, sector=(c, s)).cpu().numpy()
+            eye = create_rays_device(fov[0], fov[1], H, W, rot=np.eye(3), beam_table=table, sector=(c, s)).cpu().numpy()
+            assert np.array_equal(eye, none), (c, s)               # by value: 0 * x may turn a zero's sign
+    for bad in ((0.0, 0.0), (0.0, 360.0), (float("nan"), 90.0), (400.0, 90.0)):
+        with pytest.raises(ValueError):
+            create_rays_device(2.0, -24.8, 4, 8, sector=bad)
+
+
+# ---- 2: render ------------------------------------------------------------------------------------------------------------------
+def _render(mesh, trays, origin, H, grid, lbvh=False):
+    """the scatter on the given bin grid (with its counters and the grid) and, asked for, the LBVH on the same mesh"""
+    import torch
+    from lidar_transfer_amd.raytracer import RaySet, Scene
+    dev = torch.device("cuda", 0)
+    scn = Scene(0)
+    scn.set_mesh(*[torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in mesh])
+    rs = RaySet(trays, H, grid=grid)
+    prm = btg._rayset_params(rs)
+    a = scn.render(rs, origin, count=True)
+    stats = a.pop("stats")
+    b = None
+    if lbvh:
+        scn.build()
+        b = scn.trace(trays, origin, H)
+    torch.cuda.synchronize()
+    a = {k: x.cpu().numpy() for k, x in a.items()}
+    b = None if b is None else {k: x.cpu().numpy() for k, x in b.items()}
+    rs.close()
+    scn.close()
+    return a, b, prm, stats
+
+
+def _assert_brute(got, brute, n, tag):
+    for k in ("tri", "range", "endcolors", "endrem", "endpoints"):
+        bad = np.nonzero((_bits(got[k]) != _bits(brute[k])).reshape(n, -1).any(1))[0]
+        assert bad.size == 0, f"{tag} {k} differs from MODE_BRUTE at {bad.size} rays, first {bad[:5]}"
+
+
+@pytest.mark.parametrize("case", range(len(stc.RENDER_CASES)))
+def test_render_of_sector_rays_equals_brute_force_and_the_compiled_reference(case, capfd):
+    """tests/test_sector_cpu.py checked the scene and the three ray sets; the rays here are the product's own"""
+    import oracle_chain as oc
+    from lidar_transfer_amd.laserscan import create_rays_device
+    from lidar_transfer_amd.raytracer import sector_grid
+    from lidar_transfer_amd.synth import synth_scene
+    from oracle import binding as ob
+    if not ob.ref_available("strict"):
+        pytest.skip("oracle/_ref not built (the reference checkout was absent at build time)")
+    name, sector, W, table, fov, H, P = stc.RENDER_CASES[case]
+    mesh = synth_scene(stc.RENDER_SEED, stc.RENDER_TRIS)
+    rot = None if P is None else P[:3, :3]
+    trays = create_rays_device(fov[0], fov[1], H, W, rot=rot, beam_table=table, sector=sector)
+    rays = trays.cpu().numpy()
+    tm._rays_rule(rays, sc.sector_rays(sector, W, fov, H, table, rot), name)
+    org = np.zeros(3, np.float32) if P is None else mc.origin_of(P)
+    o3 = tuple(float(x) for x in org)
+    nb_fit = int(round(W * 360.0 / sector[1]))
+    assert sector_grid(W, sector) == (nb_fit, 0)
+    fit, lbvh, prm_f, st_f = _render(mesh, trays, o3, H, sector_grid(W, sector), lbvh=True)
+    dflt, _, prm_d, st_d = _render(mesh, trays, o3, H, None)
+    brute = ob.oracle_trace(rays, org, *mesh, H, mode=ob.MODE_BRUTE, norm=ob.NORM_SSE_TABLE, nthreads=oc.THREADS)
+    for tag, got in (("scatter/fitted", fit), ("scatter/default", dflt), ("lbvh", lbvh)):
+        _assert_brute(got, brute, H * W, f"{name}: {tag}")
+    ref = tm._reference_trace(rays, org, mesh, H)
+    capfd.readouterr()  # the reference printf()s
+    same = np.ones(H * W, bool)
+    for k in ("range", "endcolors", "endrem", "endpoints"):
+        same &= (_bits(ref[k]) == _bits(brute[k])).reshape(H * W, -1).all(1)
+    for k in ("range", "endcolors", "endrem", "endpoints"):
+        for tag, got in (("scatter/fitted", fit), ("scatter/default", dflt), ("lbvh", lbvh)):
+            assert np.array_equal(_bits(got[k])[same], _bits(ref[k])[same]), f"{name}: {tag} {k} vs the compiled reference"
+    hits = int((brute["tri"] >= 0).sum())
+    assert hits > 0.3 * H * W
+    # the grids
+    print(f"\n{name}: fitted grid nb_az {prm_f['nb_az']} dev_az {prm_f['dev_az']:.4f}, candidate bins {st_f['nodes_visited']}, "
+          f"triangle tests {st_f['tris_tested']} ({st_f['tris_tested'] / (H * W):.1f} per ray); default grid nb_az {prm_d['nb_az']} "
+          f"dev_az {prm_d['dev_az']:.4f}, candidate bins {st_d['nodes_visited']}, triangle tests {st_d['tris_tested']} "
+          f"({st_d['tris_tested'] / (H * W):.1f} per ray); {hits} hits, the reference differs from MODE_BRUTE at "
+          f"{int((~same).sum())} of {H * W} rays")
+    assert prm_f["nb_az"] == nb_fit, prm_f
+    want = sc.grid_dev_az(rays, W, nb_fit)
+    assert abs(prm_f["dev_az"] - want) <= sc.LT_BIN_SLACK, (prm_f["dev_az"], want)
+    assert prm_d["nb_az"] in (W, W - 1) and prm_d["dev_az"] > 0.25, prm_d          # the irregular path is what ran
+    if P is None:                                                 # (a posed sensor's azimuths are not evenly spaced in the scene)
+        assert prm_f["dev_az"] <= 0.5 * sector[1] / 360 + sc.LT_BIN_SLACK, prm_f
+    if case == 0:
+        assert prm_f["dev_az"] <= sc.LT_BIN_SLACK, prm_f
+        assert st_f["tris_tested"] < st_d["tris_tested"], (st_f, st_d)
+
+
+# ---- 3: lt_rayset_create_dev is what it was ---------------------------------------------------------------------------------
+def _all_params(rs):
+    lib = rs._lib
+    lib.lt_debug_rayset_params.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    lib.lt_debug_rayset_params.restype = C.c_int
+    nb, p = (C.c_int * 2)(), (C.c_float * 6)()
+    assert lib.lt_debug_rayset_params(rs._h, nb, p) == 0
+    return tuple(nb) + tuple(np.array(list(p), np.float32).view(np.int32).tolist())
+
+
+def test_the_grid_entry_point_with_zeros_is_lt_rayset_create_dev():
+    import oracle_chain as oc
+    import torch
+    from lidar_transfer_amd.laserscan import create_rays_device
+    from lidar_transfer_amd.raytracer import RaySet, Scene
+    from lidar_transfer_amd.synth import synth_scene
+    from oracle import binding as ob
+    mesh = synth_scene(stc.RENDER_SEED, stc.RENDER_TRIS)
+    dev = torch.device("cuda", 0)
+    scn = Scene(0)
+    scn.set_mesh(*[torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in mesh])
+    org = (0.0, 0.0, 0.0)
+    for tag, H, W, kw in (("16 x 301", 16, 301, {}), ("vlp32c x 200", 32, 200, dict(beam_table=bc.VLP32C))):
+        fov = bc.VLP32C_FOV if kw else (15.0, -15.0)
+        trays = create_rays_device(fov[0], fov[1], H, W, **kw)
+        old, new = RaySet(trays, H), RaySet(trays, H, grid=(0, 0))
+        assert _all_params(old) == _all_params(new), tag
+        assert _all_params(old)[0] in (W, W - 1) and _all_params(old)[1] == H
+        a, b = scn.render(old, org), scn.render(new, org)
+        torch.cuda.synchronize()
+        for k in a:
+            assert a[k].cpu().numpy().tobytes() == b[k].cpu().numpy().tobytes(), (tag, k)
+        old.close()
+        new.close()
+        if kw:
+            continue
+        rays = trays.cpu().numpy()
+        brute = ob.oracle_trace(rays, np.zeros(3, np.float32), *mesh, H, mode=ob.MODE_BRUTE, norm=ob.NORM_SSE_TABLE, nthreads=oc.THREADS)
+        _assert_brute({k: v.cpu().numpy() for k, v in a.items()}, brute, H * W, tag)
+        for nb_az, want in ((1, 1), (8192, 8192), (10000, 8192)):   # the one above the cap is clamped
+            rs = RaySet(trays, H, grid=(nb_az, 0))
+            p = _all_params(rs)
+            assert p[:2] == (want, H), (nb_az, p)
+            got = scn.render(rs, org)
+            torch.cuda.synchronize()
+            _assert_brute({k: v.cpu().numpy() for k, v in got.items()}, brute, H * W, f"{tag} nb_az {nb_az}")
+            rs.close()
+        rs = RaySet(trays, H, grid=(0, 40))                        # an elevation grid of the caller's
+        assert _all_params(rs)[1] == 40
+        got = scn.render(rs, org)
+        torch.cuda.synchronize()
+        _assert_brute({k: v.cpu().numpy() for k, v in got.items()}, brute, H * W, f"{tag} nb_el 40")
+        rs.close()
+    with pytest.raises(ValueError):
+        RaySet(trays, H, grid=(-1, 0))
+    scn.close()
+
+
+# ---- 4: projection --------------------------------------------------------------------------------------------------------------
+PROJ_KEYS = ("idx", "range", "rem", "label", "proj_x", "proj_y")
+
+
+def _check_projection(got, want, W, n, tag):
+    """bit for bit on every cell no near-boundary point touches, ``proj_xf`` to 4 ulp, the ulp of the yaw scaled by W / span
+    included (``xf_slack``: a float64 cloud's yaw comes from two ``atan2`` an ulp apart, and ``px = (yaw - yc) / span * W + W / 2``
+    carries that with the factor W / span however small ``px`` itself is; float32 clouds are bit-equal); the numbering ``idx`` of the kept points
+    is compared when both sides kept the same number (a point ON the sector's edge, left out of the comparison, may be kept
+    on one side only and shift it), else which cells are occupied"""
+    skip = sc.near_cells(want, W)
+    near, kept = int(want["near"].sum()), int(want["kept"].sum())
+    assert near <= stc.NEAR_CAP * n, (tag, near, n)               # the cap is a condition
+    n_got = int(got["n_kept"].cpu()[0])
+    assert abs(n_got - kept) <= near, (tag, n_got, kept)
+    g = {k: got[k].cpu().numpy() for k in PROJ_KEYS + ("proj_xf",)}
+    bad = {k: int(_differs(g[k], want[k])[~skip].sum()) for k in PROJ_KEYS}
+    if n_got != kept:
+        bad["idx"] = int(((g["idx"] >= 0) != (want["idx"] >= 0))[~skip].sum())
+    xf_g, xf_w = g["proj_xf"], want["proj_xf"]
+    ulps = 4 * np.abs(xf_g.astype(np.float64) - xf_w.astype(np.float64))[~skip] / \
+        np.maximum(want["xf_slack"][~skip], np.finfo(np.float64).tiny)
+    print(f"\nprojection {tag}: kept {kept} ({n_got} on the device), near a boundary {near}, cells left out {int(skip.sum())}, "
+          f"cells differing {bad}, proj_xf off by at most {ulps.max() if ulps.size else 0:.1f} ulp")
+    for k in PROJ_KEYS:
+        assert bad[k] == 0, (tag, k, bad[k])
+    assert not ulps.size or ulps.max() <= 4, (tag, ulps.max())
+    return near
+
+
+@pytest.mark.parametrize("rows", ["linear", "table"])
+@pytest.mark.parametrize("si", range(len(sc.SECTORS)))
+def test_projected_columns_equal_the_literal_loop(si, rows):
+    import torch
+    from lidar_transfer_amd.laserscan import Projector
+    c, s, W = sc.SECTORS[si]
+    table, fov, H = _rows(rows)
+    outs = PROJ_KEYS + ("proj_xf", "n_kept")
+    pj = Projector()
+    for n, dtype in stc.CLOUDS:                                  # (tests/test_sector_cpu.py: the mask flags float32 points of these)
+        cloud = sc.seeded_cloud((c, s), fov, n, dtype, stc.cloud_seed(si, n))
+        want = sc.project(*cloud, (c, s), W, H, fov, table)
+        got = pj.project([_up(cloud)], fov[0], fov[1], H, W, new=True, remove=True, outputs=outs, beam_table=table, sector=(c, s))[0]
+        torch.cuda.synchronize()
+        _check_projection(got, want, W, n, f"({c}, {s}, {W}) {rows} {np.dtype(dtype).name} n={n}")
+        if n == 20000:
+            assert (want["idx"] >= 0).sum() > min(1000, 0.5 * H * W)
+            inside = want["kept"]                                   # nothing outside the sector reached the image
+            assert int(got["n_kept"].cpu()[0]) <= int(inside.sum()) + int(want["near"].sum())
+    # two clouds in one batch on a side stream
+    c1 = sc.seeded_cloud((c, s), fov, 257, np.float32, seed=3)
+    c2 = sc.seeded_cloud((c, s), fov, 20000, np.float32, seed=stc.cloud_seed(si, 20000))
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        d1, d2 = _up(c1), _up(c2)
+        got = pj.project([d1, d2], fov[0], fov[1], H, W, new=True, remove=True, outputs=outs, beam_table=table, sector=(c, s), stream=st)
+    st.synchronize()
+    for g, cl, tag in ((got[0], c1, "batch/0"), (got[1], c2, "batch/1")):
+        w = sc.project(*cl, (c, s), W, H, fov, table)
+        if w["near"].sum() <= stc.NEAR_CAP * len(cl[0]):
+            _check_projection(g, w, W, len(cl[0]), tag)
+    pj.close()
+
+
+def test_the_single_cloud_entry_points_take_the_sector_flag_too():
+    from lidar_transfer_amd import _lib
+    from lidar_transfer_amd.config import beam_rows, sector_radians
+    lib = _lib.load()
+    c, s, W = sc.SECTORS[2]
+    for rows in ("linear", "table"):
+        table, fov, H = _rows(rows)
+        pts, rem, lab = sc.seeded_cloud((c, s), fov, 5000, np.float64, seed=9)
+        want = sc.project(pts, rem, lab, (c, s), W, H, fov, table)
+        sec = sector_radians((c, s))
+        tab = np.ascontiguousarray(np.concatenate(list(beam_rows(table)))) if table is not None else None
+        nb = H if table is not None else 0
+        n = len(pts)
+        o = dict(px=np.empty(n, np.int32), xf=np.empty(n, np.float64), idx=np.empty((H, W), np.int32), range=np.empty((H, W), np.float32))
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        kept = C.c_int(0)
+        flags = _lib.LT_PROJ_SECTOR | _lib.LT_PROJ_NEW | _lib.LT_PROJ_REMOVE | (_lib.LT_PROJ_BEAM_ROWS if table is not None else 0)
+        args = lambda fl, nbm, t: [vp(pts), 1, vp(rem), vp(lab.view(np.uint32)), n, fov[0], fov[1], H, W, t, nbm, fl, None, 0, None, None,   # noqa: E731
+                                   None, None, vp(o["px"]), None, vp(o["xf"]), None, vp(o["idx"]), vp(o["range"]), None, None, None, None,
+                                   None, 0.0, -1.0, 0.0, C.byref(kept)]
+        vt = vp(tab) if tab is not None else None
+        assert lib.lt_range_projection_set_sector(0.0, 0.0) == 0
+        assert lib.lt_range_projection(*args(flags, nb, vt)) == LT_ERR_INVALID_ARG      # no sector set
+        assert b"LT_PROJ_SECTOR" in lib.lt_last_error()
+        for bad in ((4.0, 1.0), (0.0, -1.0), (0.0, 2 * np.pi), (float("nan"), 1.0)):
+            assert lib.lt_range_projection_set_sector(*bad) == LT_ERR_INVALID_ARG, bad
+        assert lib.lt_range_projection_set_sector(*sec) == 0
+        assert lib.lt_range_projection(*args(flags, nb, vt)) == 0, lib.lt_last_error()
+        k = kept.value
+        skip = sc.near_cells(want, W)
+        n_near = int(want["near"].sum())
+        assert abs(k - int(want["kept"].sum())) <= n_near and k > 500
+        assert not _differs(o["range"], want["range"])[~skip].any()
+        assert np.array_equal(o["idx"][~skip] >= 0, want["idx"][~skip] >= 0) and ((want["idx"] >= 0) & ~skip).sum() > 300
+        if k == int(want["kept"].sum()):
+            sure = ~want["near"][want["kept"]]
+            assert np.array_equal(o["px"][:k][sure], want["col"][want["kept"]][sure])
+        for fl in (_lib.LT_PROJ_SECTOR, _lib.LT_PROJ_SECTOR | _lib.LT_PROJ_NEW, _lib.LT_PROJ_SECTOR | _lib.LT_PROJ_REMOVE,
+                   flags | 16):
+            assert lib.lt_range_projection(*args(fl, nb, vt)) == LT_ERR_INVALID_ARG, fl
+            assert b"LT_PROJ_" in lib.lt_last_error()            # (with a table the table's own check may speak first)
+        assert lib.lt_range_projection_set_sector(0.0, 0.0) == 0                         # cleared: refused again
+        assert lib.lt_range_projection(*args(flags, nb, vt)) == LT_ERR_INVALID_ARG
+
+
+def test_any_other_flag_combination_with_the_sector_flag_is_refused():
+    import torch
+    from lidar_transfer_amd import _lib
+    from lidar_transfer_amd.config import beam_rows, sector_radians
+    from lidar_transfer_amd.laserscan import Projector
+    lib = _lib.load()
+    c, s, W = sc.SECTORS[0]
+    table, fov, H = _rows("table")
+    cloud = _up(sc.seeded_cloud((c, s), fov, 257, np.float32, seed=1))
+    pj = Projector()
+    for new, remove in ((False, False), (True, False), (False, True)):
+        with pytest.raises(RuntimeError, match="LT_PROJ_SECTOR"):
+            pj.project([cloud], fov[0], fov[1], H, W, new=new, remove=remove, sector=(c, s))
+    sec = sector_radians((c, s))
+    tab = np.ascontiguousarray(np.concatenate(list(beam_rows(table))))
+    cl, im = (_lib.Cloud * 1)(), (_lib.ProjImages * 1)()
+    rng = torch.empty((H, W), dtype=torch.float32, device="cuda")
+    cl[0].points, cl[0].rem, cl[0].label, cl[0].n = cloud[0].data_ptr(), cloud[1].data_ptr(), cloud[2].data_ptr(), 257
+    im[0].range = rng.data_ptr()
+    S, B, N, R = _lib.LT_PROJ_SECTOR, _lib.LT_PROJ_BEAM_ROWS, _lib.LT_PROJ_NEW, _lib.LT_PROJ_REMOVE
+    call = lambda fl, nb, t: lib.lt_range_projection_batch_dev(pj._h, 1, cl, 0, fov[0], fov[1], H, W, t, nb, fl, None, 0, im,   # noqa: E731
+                                                               0.0, -1.0, 0.0, None)
+    vt = tab.ctypes.data_as(C.c_void_p)
+    fresh = Projector()                                            # no sector was ever set on this one
+    assert lib.lt_range_projection_batch_dev(fresh._h, 1, cl, 0, fov[0], fov[1], H, W, None, 0, S | N | R, None, 0, im,
+                                             0.0, -1.0, 0.0, None) == LT_ERR_INVALID_ARG
+    assert lib.lt_range_projection_batch_dev(fresh._h, 1, cl, 0, fov[0], fov[1], H, W, vt, H, S | B | N | R, None, 0, im,
+                                             0.0, -1.0, 0.0, None) == LT_ERR_INVALID_ARG
+    fresh.close()
+    for bad in ((0.0, 2 * np.pi), (3.5, 1.0), (float("nan"), 1.0), (0.0, -1.0)):
+        assert lib.lt_projector_set_sector(pj._h, *bad) == LT_ERR_INVALID_ARG, bad
+    assert lib.lt_projector_set_sector(None, *sec) == LT_ERR_INVALID_ARG
+    assert lib.lt_projector_set_sector(pj._h, *sec) == 0
+    for fl, nb, t in ((S, 0, None), (S | N, 0, None), (S | R, 0, None), (S | B, H, vt), (S | B | N, H, vt), (S | B | R, H, vt),
+                      (S | N | R | 16, 0, None), (S | B | N | R, H - 1, vt), (S | B | N | R, H, None)):
+        assert call(fl, nb, t) == LT_ERR_INVALID_ARG, (fl, nb)
+    assert call(S | N | R, 0, None) == 0 and call(S | B | N | R, H, vt) == 0
+    assert lib.lt_projector_set_sector(pj._h, 0.0, 0.0) == 0       # cleared: the flag is refused again
+    assert call(S | N | R, 0, None) == LT_ERR_INVALID_ARG and call(S | B | N | R, H, vt) == LT_ERR_INVALID_ARG
+    assert call(N | R, 0, None) == 0 and call(B | N | R, H, vt) == 0      # and the flags there were are what they were
+    torch.cuda.synchronize()
+    pj.close()
+
+
+# ---- 5: reverse projection ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows", ["linear", "table"])
+@pytest.mark.parametrize("preserve_float", [False, True])
+@pytest.mark.parametrize("shape", [(1, 1), (16, 301), (32, 200)])
+def test_reverse_projection_of_a_sector_equals_the_float64_restatement(shape, preserve_float, rows):
+    """rtol = atol = 1e-13 is tests/test_post_shapes_gpu.py's bound for the linear kernel (two float64 math libraries): kept
+    from there, not derived.  The largest differences are printed (profiles/sector/README.md records them)."""
+    import torch
+    from lidar_transfer_amd import _lib
+    from lidar_transfer_amd.config import sector_radians
+    lib = _lib.load()
+    H, W = shape
+    sector = {1: (-90.0, 30.0), 16: (35.0, 70.4), 32: (170.0, 100.0)}[H]
+    table = None if rows == "linear" else {1: np.array([-3.0]), 16: np.linspace(2.0, -24.8, 16) + 0.3 * np.cos(np.arange(16)), 32: bc.VLP32C}[H]
+    fov = LINEAR_FOV if table is None else (float(table.max()) + 1, float(table.min()) - 1)
+    Brad = np.zeros(H) if table is None else bc.rows_of(table)[0]
+    rng = np.random.default_rng(H * W + 7)
+    r = rng.uniform(0.5, 80.0, (H, W)).astype(np.float32)
+    r[rng.random((H, W)) < 0.2] = 0.0
+    if preserve_float:
+        px = rng.uniform(0, W, (H, W))
+        py = rng.uniform(0, H, (H, W)) if table is None else rng.uniform(Brad.min() - 0.05, Brad.max() + 0.05, (H, W))
+    else:
+        px = rng.integers(0, W, (H, W)).astype(np.int32)
+        py = rng.integers(0, H, (H, W)).astype(np.int32)
+    want = sc.reverse_projection(r, px, py, sector, fov, preserve_float, table)
+    yc, span = sector_radians(sector)
+    d = [torch.from_numpy(a).cuda() for a in (r, px, py, Brad)]
+    for stream in (None, torch.cuda.Stream()):
+        out = torch.full((H * W + 1, 3), -7.0, dtype=torch.float64, device="cuda")
+        st = torch.cuda.current_stream() if stream is None else stream
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream())
+        rc = lib.lt_reverse_projection_sector_dev(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), int(preserve_float),
+                                                  int(table is not None), d[3].data_ptr() if table is not None else None,
+                                                  fov[0], fov[1], H, W, yc, span, out.data_ptr(), C.c_void_p(st.cuda_stream))
+        assert rc == 0, lib.lt_last_error()
+        st.synchronize()
+        got = out.cpu().numpy()
+        assert (got[-1] == -7.0).all()                          # nothing past the last cell
+        got = got[:-1]
+        with np.errstate(all="ignore"):
+            rel = np.where(want != 0, np.abs(got - want) / np.abs(want), np.where(got == want, 0.0, np.inf))
+        print(f"\nreverse {H}x{W} {rows} preserve_float={preserve_float}: largest relative difference {rel.max():.1e}, largest "
+              f"absolute {np.abs(got - want).max():.1e}")
+        assert np.allclose(got, want, rtol=1e-13, atol=1e-13)
+    good = [d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), int(preserve_float), int(table is not None), d[3].data_ptr(),
+            fov[0], fov[1], H, W, yc, span, out.data_ptr(), None]
+    for k, v in ((0, None), (1, None), (2, None), (12, None), (10, 4.0), (10, float("nan")), (11, 0.0), (11, 2 * np.pi), (8, 0)):
+        b = list(good)
+        b[k] = v
+        assert lib.lt_reverse_projection_sector_dev(*b) == LT_ERR_INVALID_ARG, k
+    if table is not None and not preserve_float:
+        b = list(good)
+        b[5] = None
+        assert lib.lt_reverse_projection_sector_dev(*b) == LT_ERR_INVALID_ARG
+
+
+# ---- 6: round trip on the device --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows", ["linear", "table"])
+@pytest.mark.parametrize("si", range(len(sc.SECTORS)))
+def test_the_rays_come_back_from_the_round_trip(si, rows):
+    """The sector rays x 17.3 m, projected with ``LT_PROJ_SECTOR``, land each in its own column (with the table in its own row
+    too); the reverse projection of that image returns the points to 1e-4 m: a float32 ray at 17.3 m is about 1e-6 m, with
+    margin for the two trigonometric round trips.  With the table the int32 image does (a cell's centre and its beam ARE the
+    ray).  The reference's linear row model re-projects an int32 row through its top edge (laserscan.py:475-501, y = proj_y /
+    H), not along the ray, whatever the columns are: there the int32 image returns the AZIMUTH (as an arc at 17.3 m) and the
+    ``preserve_float`` image the points."""
+    import torch
+    from lidar_transfer_amd import _lib
+    from lidar_transfer_amd.config import sector_radians
+    from lidar_transfer_amd.laserscan import Projector, create_rays_device
+    lib = _lib.load()
+    c, s, W = sc.SECTORS[si]
+    table, fov, H = _rows(rows)
+    rays = create_rays_device(fov[0], fov[1], H, W, beam_table=table, sector=(c, s))
+    pts = (rays.double() * 17.3).float().contiguous()
+    pj = Projector()
+    o = pj.project([(pts, None, None)], fov[0], fov[1], H, W, new=True, remove=True,
+                   outputs=("idx", "range", "proj_x", "proj_y", "proj_xf", "proj_yf"), beam_table=table, sector=(c, s))[0]
+    torch.cuda.synchronize()
+    idx = o["idx"].cpu().numpy()
+    occ = idx >= 0
+    if table is not None:
+        assert np.array_equal(idx.reshape(-1), np.arange(H * W)), (c, s)      # every ray kept, in its own cell
+    else:                                                          # (the outermost linear rows sit ON the field of view's edge)
+        assert occ[1:-1].all()
+        assert np.array_equal(idx[occ], np.arange(int(occ.sum())))    # the k-th kept ray in the k-th occupied cell: its own
+    assert np.array_equal(o["proj_x"].cpu().numpy()[occ], np.tile(np.arange(W), (H, 1))[occ])
+    assert np.array_equal(o["proj_y"].cpu().numpy()[occ], np.repeat(np.arange(H), W).reshape(H, W)[occ])
+    yc, span = sector_radians((c, s))
+    brad = torch.from_numpy(bc.rows_of(table)[0]).cuda() if table is not None else None
+    p = pts.cpu().numpy().astype(np.float64).reshape(H, W, 3)
+
+    def reverse(px, py, pf):
+        back = torch.empty((H * W, 3), dtype=torch.float64, device="cuda")
+        rc = lib.lt_reverse_projection_sector_dev(o["range"].data_ptr(), px.data_ptr(), py.data_ptr(), pf, int(table is not None),
+                                                  brad.data_ptr() if brad is not None else None, fov[0], fov[1], H, W, yc, span,
+                                                  back.data_ptr(), None)
+        assert rc == 0
+        torch.cuda.synchronize()
+        return back.cpu().numpy().reshape(H, W, 3)
+
+    b = reverse(o["proj_x"], o["proj_y"], 0)
+    if table is None:
+        az_b, az_p = np.arctan2(b[..., 1], b[..., 0]), np.arctan2(p[..., 1], p[..., 0])
+        arc = float((np.abs((az_b - az_p + np.pi) % (2 * np.pi) - np.pi)[occ] * 17.3).max())
+        assert arc <= 1e-4, arc
+        bf = reverse(o["proj_xf"].double(), o["proj_yf"].double(), 1)
+        off = float(np.abs(bf - p)[occ].max())
+        print(f"\nround trip ({c}, {s}, {W}) linear: int32 image, largest azimuth arc at 17.3 m {arc:.2e} m; preserve_float image, "
+              f"largest coordinate difference {off:.2e} m over {int(occ.sum())} rays")
+    else:
+        off = float(np.abs(b - p)[occ].max())
+        print(f"\nround trip ({c}, {s}, {W}) table: int32 image, largest coordinate difference {off:.2e} m over {int(occ.sum())} rays")
+    assert off <= 1e-4, off
+    pj.close()
+
+
+# ---- 7: composed ----------------------------------------------------------------------------------------------------------------
+def _sector_rays_dev(target, sector, P=None, table=None):
+    """the product's sector rays, downloaded, after they passed the rays' rule against the restatement"""
+    from lidar_transfer_amd.laserscan import create_rays_device
+    tH, tW, tfu, tfd = target
+    rot = None if P is None else P[:3, :3]
+    rays = create_rays_device(tfu, tfd, tH, tW, rot=rot, beam_table=table, sector=sector).cpu().numpy()
+    tm._rays_rule(rays, sc.sector_rays(sector, tW, (tfu, tfd), tH, table, rot), "sector rays of the oracle chain")
+    return rays
+
+
+@pytest.mark.parametrize("mounted", [False, True])
+def test_mesh_with_a_sector_target_equals_the_composed_oracle_chain(mounted):
+    import oracle_chain as oc
+    import pin_cases
+    import test_default_chain_gpu as dc
+    import torch
+    from lidar_transfer_amd.deform import DeviceDeform
+    tm._need_reference_builds()
+    T = T_EXAMPLE if mounted else None
+    P = tm._pose_of(T) if mounted else None
+    _, src, _, n_scans, bnds, voxel, seeds = pin_cases.deform_mesh_case(0)
+    sector = (35.0, 70.4)
+    tgt = (16, 301, 3.0, -25.0)
+    clouds = pin_cases.deform_mesh_clouds(seeds[0], n_scans, src, dc._host_render)
+    with DeviceDeform(src, tgt, bnds.copy(), voxel, transformation=T, t_sector=sector) as dd:
+        assert dd.rayset.sector == sector and dd.rayset.grid == (int(round(301 * 360 / 70.4)), 0)
+        assert btg._rayset_params(dd.rayset)["nb_az"] == int(round(301 * 360 / 70.4))
+        got = dd.mesh(tm._dev(clouds))
+        torch.cuda.synchronize()
+        H, W, fu, fd = src
+        b = np.array(bnds, copy=True)
+        dim, origin = oc.volume_geometry(b, voxel)
+        vol = oc.RefVolume(dim, origin, voxel, fu, fd)
+        for pts, rem, lab in clouds:
+            rng, remi, labi, _ = oc.project(pts, rem, lab, H, W, fu, fd)
+            vol.integrate(labi, rng, remi)
+        dc._check_volumes(dd.vol.get_volume_tensors(), dict(fields=[t.cpu() for t in vol.fields]), "sector")   # fusion: untouched
+        want = btg._finish(vol, tgt, _sector_rays_dev(tgt, sector, P), P, T)
+        ties = {}
+        btg._check_scan(got, want, f"mesh/sector/{mounted}", ties)
+        with DeviceDeform(src, tgt, bnds.copy(), voxel, transformation=T) as plain:       # the full circle: another scan
+            base = plain.mesh(tm._dev(clouds))
+            torch.cuda.synchronize()
+            assert not np.array_equal(base["range"].cpu().numpy(), got["range"].cpu().numpy())
+    print(f"\nmesh with a sector target (mounted: {mounted}) vs the composed oracle chain: (exact-t tie pixels, in-plane pixels) {ties}")
+
+
+def _target_model(**kw):
+    from lidar_transfer_amd.config import load_sensor
+    tH, tW, tfu, tfd = SEQ_TARGET
+    cfg = dict(name="front 120", fov_up=tfu, fov_down=tfd, beams=tH, angle_res_hor=0.7, fov_hor=SEQ_SECTOR[1],
+               azimuth_model="sector", azimuth_center=SEQ_SECTOR[0])
+    cfg.update(kw)
+    m = load_sensor(cfg)
+    return m
+
+
+_SEQ_ORACLE = dict(outs=[], bnds=None)
+
+
+def _oracle_sequence(n):
+    """the composed chain over the first ``n`` output scans of the F17 sequence on ONE bounds array, rendered with the sector
+    rays (cached: the sequence test compares its files with the same scans)"""
+    import oracle_chain as oc
+    from lidar_transfer_amd.ingest import relative_indices
+    g17, g18, a = btg._seq_setup()
+    st = _SEQ_ORACLE
+    if st["bnds"] is None:
+        st["bnds"] = a.voxel_bounds.copy()
+        st["rays"] = _sector_rays_dev(SEQ_TARGET, SEQ_SECTOR)
+    raw, poses = cpu.raw_scans(g17), [np.array(p, np.float64) for p in g17["poses"]]
+    H, W = ev.SOURCE[0], ev.SOURCE[1]
+    tfu, tfd = SEQ_TARGET[2], SEQ_TARGET[3]
+    indices = [int(x) for x in a.scan_indices(len(raw))]
+    while len(st["outs"]) < n:
+        idx = indices[len(st["outs"])]
+        slots = [idx + r for r in relative_indices(a.number_of_scans)]
+        pts, rem, lab = cpu.restate(raw, poses, slots, np.linalg.inv(poses[idx]), a.ignore, a.moving, merged=True)[0]
+        rng, remi, labi, kept = oc.project(pts, rem, lab.astype(np.int64), H, W, tfu, tfd)    # the full circle: not cropped
+        dim, origin, given = oc.mergemesh_bounds(st["bnds"], kept, a.voxel_size)
+        vol = oc.RefVolume(dim, origin, a.voxel_size, tfu, tfd)
+        vol.integrate(labi, rng, remi)
+        w = btg._finish(vol, SEQ_TARGET, st["rays"])
+        w.update(idx=idx, vol_dim=tuple(int(x) for x in dim), bnds_after=st["bnds"].copy())
+        st["outs"].append(w)
+    return st["outs"][:n]
+
+
+def test_mergemesh_sequence_with_a_sector_target_equals_the_composed_oracle_chain():
+    import torch
+    from lidar_transfer_amd.deform import DeviceDeform
+    from lidar_transfer_amd.ingest import ScanIngest
+    tm._need_reference_builds()
+    g17, g18, a = btg._seq_setup()
+    want = _oracle_sequence(3)
+    src = tm._source(g17)
+    ing = ScanIngest(src, a)
+    b = a.voxel_bounds.copy()
+    ties = {}
+    with DeviceDeform(ev.SOURCE, SEQ_TARGET, b, a.voxel_size, mesh_volume=False, t_sector=SEQ_SECTOR) as dd:
+        for w in want:
+            got = dd.deform("mergemesh", ing, w["idx"])
+            torch.cuda.synchronize()
+            tag = f"mm{w['idx']}"
+            assert got["vol_dim"] == w["vol_dim"], tag
+            assert np.array_equal(np.array(got["vol_bnds_after"]).reshape(3, 2), w["bnds_after"].astype(np.float64)), tag
+            btg._check_scan(got, w, tag, ties)
+    src.close()
+    print(f"\nmergemesh with a sector target vs the composed oracle chain: (exact-t tie pixels, in-plane pixels) {ties}")
+
+
+@pytest.mark.parametrize("rows", ["linear", "table"])
+@pytest.mark.parametrize("preserve_float", [False, True])
+def test_cp_with_a_sector_target_writes_the_restatements_bytes(preserve_float, rows):
+    """the restated ingest, the literal loop with the column rule, the restated reverse projection and write()"""
+    import oracle_chain as oc
+    import torch
+    from lidar_transfer_amd.deform import DeviceDeform
+    from lidar_transfer_amd.ingest import ScanIngest, relative_indices
+    g17, g18, a = btg._seq_setup("cp")
+    raw, poses = cpu.raw_scans(g17), [np.array(p, np.float64) for p in g17["poses"]]
+    src = tm._source(g17)
+    ing = ScanIngest(src, a)
+    table = bc.VLP32C if rows == "table" else None
+    tH, tW = SEQ_TARGET[:2]
+    fov = bc.VLP32C_FOV if rows == "table" else SEQ_TARGET[2:]
+    tgt = (tH, tW, fov[0], fov[1])
+    with DeviceDeform(ev.SOURCE, tgt, None, preserve_float=preserve_float, t_beam_table=table, t_sector=SEQ_SECTOR) as dd, \
+            DeviceDeform(ev.SOURCE, tgt, None, preserve_float=preserve_float, t_beam_table=table) as plain:
+        for idx in a.scan_indices(len(raw))[:2]:
+            got = dd.deform("cp", ing, idx)
+            base = plain.deform("cp", ing, idx)
+            torch.cuda.synchronize()
+            slots = [idx + r for r in relative_indices(a.number_of_scans)]
+            pts, rem, lab = cpu.restate(raw, poses, slots, np.linalg.inv(poses[idx]), a.ignore, a.moving, merged=True)[0]
+            p = sc.project(pts, rem, lab.astype(np.int64), SEQ_SECTOR, tW, tH, fov, table)
+            assert not p["near"].any(), "a point of the sequence lies on a column boundary: choose another scan"
+            px, py = (p["proj_xf"], p["proj_yf"]) if preserve_float else (p["proj_x"], p["proj_y"])
+            back = sc.reverse_projection(p["range"], px, py, SEQ_SECTOR, fov, preserve_float, table)
+            wb, wl = oc.pack_write(back, p["label"], p["rem"], index=p["idx"])
+            assert wb.shape[0] > 100
+            assert np.array_equal(got["index"].cpu().numpy(), p["idx"]), idx
+            assert np.array_equal(got["label_file"].cpu().numpy().view(np.uint32), wl), f"cp {idx}: label bytes"
+            gb = got["bin"].cpu().numpy()
+            diff = int((gb.view(np.uint32) != wb.view(np.uint32)).sum())
+            print(f"\ncp with a sector target ({rows}), scan {idx}, preserve_float={preserve_float}: {wb.shape[0]} points, {diff} of "
+                  f"{wb.size} words differ")
+            assert np.array_equal(gb.view(np.uint8), wb.view(np.uint8)), f"cp {idx}: velodyne bytes"
+            assert gb.tobytes() != base["bin"].cpu().numpy().tobytes()
+    src.close()
+
+
+def _run_sequence(a, target, out_dir, chains, **kw):
+    from lidar_transfer_amd.sequence import SequenceTransfer
+    g17, g18 = cpu.gold(), sq.gold18()
+    src = tm._source(g17)
+    with SequenceTransfer(src, a, ev.SOURCE, target, out_dir=str(out_dir), chains=chains, nclasses=int(g18["nclasses"]), **kw) as tr:
+        recs = list(tr.run())
+        info = dict(azimuth_model=tr.azimuth_model, evaluate=tr.evaluate, summary=tr.summary)
+    src.close()
+    return recs, info
+
+
+def test_sequence_with_a_sector_target_writes_the_oracles_files(tmp_path):
+    import oracle_chain as oc
+    from lidar_transfer_amd.sequence import SequenceTransfer
+    tm._need_reference_builds()
+    g17, g18, a = btg._seq_setup()
+    model = _target_model()
+    assert (model.H, model.W, model.sector()) == (32, 171, SEQ_SECTOR)
+    r1, i1 = _run_sequence(a, model, tmp_path / "c1", 1)
+    assert i1["azimuth_model"] == "sector" and i1["evaluate"] is False and i1["summary"]["azimuth_model"] == "sector"
+    r3, i3 = _run_sequence(a, model, tmp_path / "c3", 3)
+    assert i3["summary"]["chains"] == 3
+    r0, i0 = _run_sequence(a, SEQ_TARGET, tmp_path / "full", 1)
+    assert i0["azimuth_model"] == "full" and i0["summary"]["azimuth_model"] == "full"
+    indices = [r["idx"] for r in r1]
+    assert indices == [int(x) for x in a.scan_indices(8)] == [r["idx"] for r in r3] and len(indices) >= 3
+    want = _oracle_sequence(len(indices))
+    for rec, rec3, w in zip(r1, r3, want):
+        idx = rec["idx"]
+        for r in (rec, rec3):
+            assert r["m_iou"] is None and r["MSE"] is None and not r["skipped"]
+            assert np.array_equal(r["bnds_after"], w["bnds_after"].astype(np.float64)), idx
+        if "bin" not in w:                                      # (scans the DeviceDeform test did not visit)
+            sel = tm._rule_images(w)
+            w["bin"], w["label_file"] = oc.pack_write(sel["endpoints"], sel["label"], sel["endrem"])
+        b1, l1 = tm._read(tmp_path / "c1", idx)
+        assert b1 == w["bin"].tobytes(), f"scan {idx}: velodyne file"
+        assert l1 == w["label_file"].astype(np.uint32).tobytes(), f"scan {idx}: label file"
+        assert (b1, l1) == tm._read(tmp_path / "c3", idx), f"scan {idx}: one chain vs three"
+        assert tm._read(tmp_path / "full", idx)[0] != b1, f"scan {idx}: the sector changed nothing"
+    # a sector target of the source's size: with the full circle this run would compare; asked to, it refuses; a SOURCE sector too
+    same_size = _target_model(beams=ev.SOURCE[0], angle_res_hor=SEQ_SECTOR[1] / ev.SOURCE[1], fov_up=ev.SOURCE[2], fov_down=ev.SOURCE[3])
+    assert (same_size.H, same_size.W) == ev.SOURCE[:2]
+    src = tm._source(g17)
+    try:
+        with SequenceTransfer(src, a, ev.SOURCE, same_size) as tr:
+            assert tr.evaluate is False and tr.azimuth_model == "sector"
+        with SequenceTransfer(src, a, ev.SOURCE, ev.SOURCE) as tr:
+            assert tr.evaluate is True and tr.azimuth_model == "full"
+        with pytest.raises(ValueError, match="sector"):
+            SequenceTransfer(src, a, ev.SOURCE, same_size, evaluate=True)
+        with pytest.raises(ValueError, match="target"):
+            SequenceTransfer(src, a, same_size, ev.SOURCE)
+    finally:
+        src.close()
+
+
+def test_cli_on_the_shipped_sector_file_prints_no_metrics_and_logs_the_azimuth_model(tmp_path):
+    import json
+    import subprocess
+    g17, g18, a = btg._seq_setup()
+    data = tmp_path / "data"
+    seq = data / "sequences" / "00"
+    (seq / "velodyne").mkdir(parents=True)
+    (seq / "labels").mkdir()
+    for k, (xyzr, lab) in enumerate(cpu.raw_scans(g17)):
+        xyzr.tofile(seq / "velodyne" / f"{k:06d}.bin")
+        lab.tofile(seq / "labels" / f"{k:06d}.label")
+    g17["calib_txt"].tofile(seq / "calib.txt")
+    g17["poses_txt"].tofile(seq / "poses.txt")
+    H, W, fu, fd = 64, 1024, 2.0, -24.8                         # the size of the shipped target: a full-circle one would compare
+    (data / "config.yaml").write_text(f"name: src\nfov_up: {fu}\nfov_down: {fd}\nbeams: {H}\nangle_res_hor: {360.0 / W!r}\nfov_hor: 360.0\n")
+    cm = "\n".join(f"  {k}: {list(v)}" for k, v in ev.COLOR_DICT.items())
+    cfg = tmp_path / "approach.yaml"
+    cfg.write_text(f"adaption: mergemesh\npreserve_float: false\nnumber_of_scans: {a.number_of_scans}\n"
+                   f"batch_interval: {a.batch_interval}\nvoxel_size: {a.voxel_size!r}\n"
+                   f"voxel_bounds: {[float(x) for x in np.asarray(a.voxel_bounds).reshape(-1)]}\n"
+                   f"transformation: []\nignore: {a.ignore}\nmoving: {a.moving}\ncolor_map:\n{cm}\n")
+    full = tmp_path / "full.yaml"
+    full.write_text("name: full\nfov_up: 2.0\nfov_down: -24.8\nbeams: 64\nangle_res_hor: 0.3515625\nfov_hor: 360\n")
+    outs = {}
+    for name, target, more in (("sector", os.path.join(ROOT, "config", "front120_64x1024.yaml"), []),
+                               ("full", str(full), ["--one_scan"])):
+        out = tmp_path / f"out_{name}"
+        out.mkdir()
+        log = tmp_path / f"{name}.jsonl"
+        res = subprocess.run([sys.executable, "-m", "lidar_transfer_amd", "-d", str(data), "-c", str(cfg), "-s", "00", "-t", target,
+                              "-w", "-p", str(out), "--log", str(log)] + more, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-3000:]
+        rows = [json.loads(x) for x in log.read_text().splitlines()]
+        outs[name] = (res.stdout, rows, tm._read(out, rows[0]["idx"]))
+    so, rows, files = outs["sector"]
+    assert "IoU:" not in so and "Acc:" not in so and "MSE:" not in so
+    assert len(rows) >= 3 and all(r["azimuth_model"] == "sector" and r["m_iou"] is None for r in rows[:-1])
+    assert rows[-1]["summary"]["azimuth_model"] == "sector"
+    so, rows, files0 = outs["full"]
+    assert "IoU:" in so and all("azimuth_model" not in r for r in rows[:-1]) and rows[-1]["summary"]["azimuth_model"] == "full"
+    assert files[0] != files0[0] and len(files[0]) > 1600
+
+
+# ---- nothing changes without it ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("adaption", ["cp", "mesh", "mergemesh"])
+def test_a_full_target_and_a_target_without_the_key_change_nothing(adaption):
+    import torch
+    from lidar_transfer_amd.config import load_sensor
+    from lidar_transfer_amd.deform import DeviceDeform
+    from lidar_transfer_amd.ingest import ScanIngest
+    g17, g18, a = btg._seq_setup(adaption)
+    t = g18["target_t"]
+    target = (int(t[0]), int(t[1]), float(t[2]), float(t[3]))
+    cfg = dict(name="t", fov_up=target[2], fov_down=target[3], beams=target[0], angle_res_hor=360.0 / target[1], fov_hor=360.0)
+    models = [load_sensor(dict(cfg)), load_sensor(dict(cfg, azimuth_model="full")), load_sensor(dict(cfg, azimuth_model="full", azimuth_center=30))]
+    assert all((m.H, m.W) == target[:2] and m.sector() is None for m in models)
+    src = tm._source(g17)
+    ing = ScanIngest(src, a)
+    res = []
+    for kw in ({}, dict(t_sector=models[0].sector()), dict(t_sector=models[1].sector()), dict(t_sector=models[2].sector())):
+        bnds = None if adaption == "cp" else a.voxel_bounds.copy()
+        with DeviceDeform(ev.SOURCE, target, bnds, a.voxel_size, mesh_volume=adaption == "mesh", **kw) as dd:
+            assert dd.t_sector is None and (dd.rayset is None or (dd.rayset.sector is None and dd.rayset.grid is None))
+            outs = []
+            for idx in a.scan_indices(8)[:2]:
+                out = dd.deform(adaption, ing, idx)
+                torch.cuda.synchronize()
+                outs.append({k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in out.items()})
+            res.append(outs)
+    for other in res[1:]:
+        for x, y in zip(res[0], other):
+            tm._same(x, y, adaption)
+    assert res[0][0]["bin"].shape[0] > 100
+    src.close()
+
+
+def test_a_shared_rayset_must_have_been_built_for_the_same_sector():
+    from lidar_transfer_amd.deform import DeviceDeform
+    from lidar_transfer_amd.laserscan import create_rays_device
+    from lidar_transfer_amd.raytracer import RaySet, sector_grid
+    src, tgt = (16, 64, 3.0, -25.0), (16, 64, 3.0, -25.0)
+    bnds = np.array([[-4.0, 4.0], [-4.0, 4.0], [-2.0, 2.0]])
+    mk = lambda s: RaySet(create_rays_device(tgt[2], tgt[3], tgt[0], tgt[1], sector=s), tgt[0], sector=s,   # noqa: E731
+                          grid=None if s is None else sector_grid(tgt[1], s))
+    plain, front, left = mk(None), mk((0.0, 120.0)), mk((40.0, 120.0))
+    for rs, s, ok in ((plain, None, True), (plain, (0.0, 120.0), False), (front, (0.0, 120.0), True), (front, None, False),
+                      (left, (0.0, 120.0), False), (front, (0, 120), True), (left, (400.0 - 360.0, 120.0), True), (front, (0.0, 90.0), False)):
+        if ok:
+            DeviceDeform(src, tgt, bnds.copy(), 0.25, mesh_volume=False, rayset=rs, t_sector=s).close()
+        else:
+            with pytest.raises(ValueError, match="sector"):
+                DeviceDeform(src, tgt, bnds.copy(), 0.25, mesh_volume=False, rayset=rs, t_sector=s)
+    for bad in ((0.0, 360.0), (0.0, 0.0), (float("nan"), 90.0), (0.0,)):
+        with pytest.raises(ValueError):
+            DeviceDeform(src, tgt, None, t_sector=bad)
+    for rs in (plain, front, left):
+        rs.close()
