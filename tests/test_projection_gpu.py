@@ -106,7 +106,9 @@ def test_projection_at_baseline_scale_vs_reference(tag, method):
     `do_label_projection_new` by SHA-256 (dtype and shape included).  float32 clouds -- what `open_scan` reads from a
     .bin file: numpy's float32 arcsin / arctan2 are not correctly rounded and differ from every other libm (and
     between numpy builds) in the last bit, which moves about one point in 1e5 across a pixel border; there the
-    per-point outputs must be identical and the images may differ in a handful of cells."""
+    per-point outputs must be identical and the images may differ in a handful of cells.  This loose float32 comparison pins
+    the reference's numpy arrays, not the kernel: the kernel's float32 path is held bit for bit, no cell exempt, by
+    tests/test_projection_shapes_gpu.py."""
     import hashlib
     from lidar_transfer_amd.laserscan import SemLaserScan
     from lidar_transfer_amd.synth import synth_cloud
@@ -154,7 +156,9 @@ def test_projection_at_baseline_scale_vs_reference(tag, method):
 def test_projection_fuzz_vs_cpu_restatement(seed):
     """Random clouds, image shapes, fields of view, beam tables and removal modes: the HIP projections against
     oracle/projection.py (itself pinned to the reference's arrays in tests/test_oracle_cpu.py).  float64 clouds must
-    match exactly; float32 clouds may differ in the few cells numpy's float32 arcsin / arctan2 rounding moves."""
+    match exactly; float32 clouds may differ in the few cells numpy's float32 arcsin / arctan2 rounding moves.  That loose
+    float32 comparison pins the reference's numpy loops, not the kernel: the exact float32 check, no cell exempt, is
+    tests/test_projection_shapes_gpu.py."""
     from oracle import projection as op
     from lidar_transfer_amd.laserscan import SemLaserScan
     rng = np.random.default_rng(1000 + seed)
