@@ -25,6 +25,14 @@ int lt_cu_count(int device);
     if (rc__ != LT_OK) return rc__; \
   } while (0)
 
+// The instantiation of a sensor-model kernel (projection, reverse projection) for a beam table (`rows`) and a horizontal
+// sector: LAUNCH(BEAMS, SECTOR) is a macro that holds the kernel's one launch statement, expanded with the two as literals.
+#define LT_FOR_MODEL(rows, sector, LAUNCH)                         \
+  do {                                                             \
+    if (rows) { if (sector) LAUNCH(1, 1); else LAUNCH(1, 0); }     \
+    else { if (sector) LAUNCH(0, 1); else LAUNCH(0, 0); }          \
+  } while (0)
+
 // ---- device data layout -----------------------------------------------------------------------
 // Sorted triangle record, 48 B = 3 x float4 (one 16-B-aligned dwordx4 load each):
 //   q0 = (v0.x, v0.y, v0.z, e1.x)   q1 = (e1.y, e1.z, e2.x, e2.y)   q2 = (e2.z, face, -, -)

@@ -8,110 +8,38 @@
 #include "lt_internal.h"
 #include <math.h>
 #include <mutex>
+#include <type_traits>
 
 // ---- reverse projection (float64, as numpy computes it from int32 / float64 pixel coordinates) ------------
-template <typename P>
+// One kernel for every target sensor.  P: int32 coordinates, or float64 (`preserve_float`: the winner's own).
+//   yaw    the full circle: theta = (px / W * 2 - 1) * pi.  SECTOR (what LT_PROJ_SECTOR projected): the column's yaw is that
+//          of its ray, the CENTRE of cell px -- yaw = yc + ((px + 0.5) / W - 0.5) * span -- or, with float64 coordinates, the
+//          winner's own: yaw = yc + (xf / W - 0.5) * span
+//   pitch  the linear rows: 90 - phi.  BEAMS (a beam table): the elevation e = Brad[row], or the winner's pitch itself with
+//          float64 coordinates; pitch = pi / 2 - e.  A row outside the table (no caller makes one) reads its nearest end,
+//          never memory beside the table
+// The three products are multiplied left to right.
+template <typename P, int BEAMS, int SECTOR>
 __global__ __launch_bounds__(256) void k_reverse(const float* __restrict__ range, const P* __restrict__ px,
                                                  const P* __restrict__ py, int n, double W, double H, double fov,
-                                                 double abs_fov_down, double* __restrict__ out) {
+                                                 double abs_fov_down, const double* __restrict__ Brad, double yc, double span,
+                                                 double* __restrict__ out) {
+  constexpr bool is_float = std::is_same<P, double>::value;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double depth = (double)range[i];
-  const double x = (double)px[i] / W, y = (double)py[i] / H;
-  const double yaw = (x * 2 - 1.0) * M_PI;                                  // theta
-  const double pitch = M_PI / 2 - (1.0 * fov - y * fov - abs_fov_down);     // 90 - phi
-  const double sp = sin(pitch);
-  out[3 * (size_t)i] = depth * sp * cos(-yaw);
-  out[3 * (size_t)i + 1] = depth * sp * sin(-yaw);
-  out[3 * (size_t)i + 2] = depth * cos(pitch);
-}
-
-extern "C" int lt_reverse_projection_dev(const float* range_img, const void* proj_x, const void* proj_y,
-                                         int coords_are_f64, double fov_up, double fov_down, int H, int W,
-                                         double* back_points, void* stream) {
-  if (H <= 0 || W <= 0 || !range_img || !proj_x || !proj_y || !back_points) {
-    lt_set_error("lt_reverse_projection_dev: invalid argument");
-    return LT_ERR_INVALID_ARG;
-  }
-  const double fu = fov_up / 180.0 * M_PI, fd = fov_down / 180.0 * M_PI;
-  const double fov = fabs(fd) + fabs(fu);
-  const int n = H * W;
-  hipStream_t st = (hipStream_t)stream;
-  if (coords_are_f64)
-    hipLaunchKernelGGL(k_reverse<double>, dim3((n + 255) / 256), dim3(256), 0, st, range_img, (const double*)proj_x,
-                       (const double*)proj_y, n, (double)W, (double)H, fov, fabs(fd), back_points);
-  else
-    hipLaunchKernelGGL(k_reverse<int>, dim3((n + 255) / 256), dim3(256), 0, st, range_img, (const int*)proj_x,
-                       (const int*)proj_y, n, (double)W, (double)H, fov, fabs(fd), back_points);
-  LT_HIP(hipGetLastError());
-  return LT_OK;
-}
-
-// ---- reverse projection of a sensor with a BEAM TABLE: the yaw as above, the elevation e = Brad[row] (or the winner's
-// pitch itself with `preserve_float`), pitch = pi / 2 - e, the three products multiplied left to right.  A row outside
-// the table (no caller makes one) reads its nearest end, never memory beside the table.
-template <typename P>
-__global__ __launch_bounds__(256) void k_reverse_beams(const float* __restrict__ range, const P* __restrict__ px,
-                                                       const P* __restrict__ py, int n, double W,
-                                                       const double* __restrict__ Brad, int H, int py_is_pitch,
-                                                       double* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double depth = (double)range[i];
-  const double x = (double)px[i] / W;
-  const double yaw = (x * 2 - 1.0) * M_PI;
-  double e;
-  if (py_is_pitch) {
-    e = (double)py[i];
+  double yaw;
+  if (SECTOR) {
+    const double x = is_float ? (double)px[i] / W : ((double)px[i] + 0.5) / W;
+    yaw = yc + (x - 0.5) * span;
   } else {
-    int r = (int)py[i];
-    r = r < 0 ? 0 : (r > H - 1 ? H - 1 : r);
-    e = Brad[r];
+    const double x = (double)px[i] / W;
+    yaw = (x * 2 - 1.0) * M_PI;                                             // theta
   }
-  const double pitch = M_PI / 2 - e;
-  const double sp = sin(pitch);
-  out[3 * (size_t)i] = depth * sp * cos(-yaw);
-  out[3 * (size_t)i + 1] = depth * sp * sin(-yaw);
-  out[3 * (size_t)i + 2] = depth * cos(pitch);
-}
-
-extern "C" int lt_reverse_projection_beams_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
-                                               int preserve_float, const double* Brad, int H, int W, double* back_points,
-                                               void* stream) {
-  if (H <= 0 || W <= 0 || !range_img || !proj_x || !proj_y_or_pitch || !back_points || (!preserve_float && !Brad)) {
-    lt_set_error("lt_reverse_projection_beams_dev: invalid argument");
-    return LT_ERR_INVALID_ARG;
-  }
-  const int n = H * W;
-  hipStream_t st = (hipStream_t)stream;
-  if (preserve_float)
-    hipLaunchKernelGGL(k_reverse_beams<double>, dim3((n + 255) / 256), dim3(256), 0, st, range_img, (const double*)proj_x,
-                       (const double*)proj_y_or_pitch, n, (double)W, Brad, H, 1, back_points);
-  else
-    hipLaunchKernelGGL(k_reverse_beams<int>, dim3((n + 255) / 256), dim3(256), 0, st, range_img, (const int*)proj_x,
-                       (const int*)proj_y_or_pitch, n, (double)W, Brad, H, 0, back_points);
-  LT_HIP(hipGetLastError());
-  return LT_OK;
-}
-
-// ---- reverse projection of a sensor with a horizontal SECTOR (what LT_PROJ_SECTOR projected): the column's yaw is that of
-// its ray, the CENTRE of cell px -- yaw = yc + ((px + 0.5) / W - 0.5) * span -- or, with `preserve_float`, the winner's own:
-// yaw = yc + (xf / W - 0.5) * span.  The elevation is k_reverse's linear rule (BEAMS 0) or k_reverse_beams' (BEAMS 1:
-// Brad[row], or the pitch image with `preserve_float`); the three products are multiplied left to right as there.
-template <typename P, int BEAMS>
-__global__ __launch_bounds__(256) void k_reverse_sector(const float* __restrict__ range, const P* __restrict__ px,
-                                                        const P* __restrict__ py, int n, double W, double H, double fov,
-                                                        double abs_fov_down, const double* __restrict__ Brad, int py_is_float,
-                                                        double yc, double span, double* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double depth = (double)range[i];
-  const double x = py_is_float ? (double)px[i] / W : ((double)px[i] + 0.5) / W;
-  const double yaw = yc + (x - 0.5) * span;
   double pitch;
   if (BEAMS) {
     double e;
-    if (py_is_float) {
+    if (is_float) {
       e = (double)py[i];
     } else {
       int r = (int)py[i];
@@ -122,12 +50,58 @@ __global__ __launch_bounds__(256) void k_reverse_sector(const float* __restrict_
     pitch = M_PI / 2 - e;
   } else {
     const double y = (double)py[i] / H;
-    pitch = M_PI / 2 - (1.0 * fov - y * fov - abs_fov_down);
+    pitch = M_PI / 2 - (1.0 * fov - y * fov - abs_fov_down);                // 90 - phi
   }
   const double sp = sin(pitch);
   out[3 * (size_t)i] = depth * sp * cos(-yaw);
   out[3 * (size_t)i + 1] = depth * sp * sin(-yaw);
   out[3 * (size_t)i + 2] = depth * cos(pitch);
+}
+
+// `rows`: a beam table (Brad; the field of view is not read then).  `sec` = (yaw of the middle, width) in radians, or
+// NULL: the full circle.
+static int reverse_launch(const float* range_img, const void* proj_x, const void* proj_y, int coords_are_f64,
+                          const double* Brad, bool rows, double fov_up, double fov_down, int H, int W, const double* sec,
+                          double* back_points, hipStream_t st) {
+  const double fu = fov_up / 180.0 * M_PI, fd = fov_down / 180.0 * M_PI;
+  const double fov = fabs(fd) + fabs(fu);
+  const int n = H * W;
+  const bool sector = sec != nullptr;
+  const double yc = sec ? sec[0] : 0.0, span = sec ? sec[1] : 0.0;
+#define LT_REVERSE(P, B, S)                                                                                                  \
+  hipLaunchKernelGGL((k_reverse<P, B, S>), dim3((n + 255) / 256), dim3(256), 0, st, range_img, (const P*)proj_x,             \
+                     (const P*)proj_y, n, (double)W, (double)H, fov, fabs(fd), Brad, yc, span, back_points)
+#define LT_REVERSE_F64(B, S) LT_REVERSE(double, B, S)
+#define LT_REVERSE_I32(B, S) LT_REVERSE(int, B, S)
+  if (coords_are_f64) LT_FOR_MODEL(rows, sector, LT_REVERSE_F64);
+  else LT_FOR_MODEL(rows, sector, LT_REVERSE_I32);
+#undef LT_REVERSE
+#undef LT_REVERSE_F64
+#undef LT_REVERSE_I32
+  LT_HIP(hipGetLastError());
+  return LT_OK;
+}
+
+extern "C" int lt_reverse_projection_dev(const float* range_img, const void* proj_x, const void* proj_y,
+                                         int coords_are_f64, double fov_up, double fov_down, int H, int W,
+                                         double* back_points, void* stream) {
+  if (H <= 0 || W <= 0 || !range_img || !proj_x || !proj_y || !back_points) {
+    lt_set_error("lt_reverse_projection_dev: invalid argument");
+    return LT_ERR_INVALID_ARG;
+  }
+  return reverse_launch(range_img, proj_x, proj_y, coords_are_f64, nullptr, false, fov_up, fov_down, H, W, nullptr, back_points,
+                        (hipStream_t)stream);
+}
+
+extern "C" int lt_reverse_projection_beams_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
+                                               int preserve_float, const double* Brad, int H, int W, double* back_points,
+                                               void* stream) {
+  if (H <= 0 || W <= 0 || !range_img || !proj_x || !proj_y_or_pitch || !back_points || (!preserve_float && !Brad)) {
+    lt_set_error("lt_reverse_projection_beams_dev: invalid argument");
+    return LT_ERR_INVALID_ARG;
+  }
+  return reverse_launch(range_img, proj_x, proj_y_or_pitch, preserve_float, Brad, true, 0.0, 0.0, H, W, nullptr, back_points,
+                        (hipStream_t)stream);
 }
 
 extern "C" int lt_reverse_projection_sector_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
@@ -139,22 +113,9 @@ extern "C" int lt_reverse_projection_sector_dev(const float* range_img, const vo
     lt_set_error("lt_reverse_projection_sector_dev: invalid argument (H=%d W=%d yaw_center=%g span=%g)", H, W, yaw_center, span);
     return LT_ERR_INVALID_ARG;
   }
-  const double fu = fov_up / 180.0 * M_PI, fd = fov_down / 180.0 * M_PI;
-  const double fov = fabs(fd) + fabs(fu);
-  const int n = H * W;
-  const dim3 grid((n + 255) / 256), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define LT_REV_SECTOR(P, B)                                                                                              \
-  hipLaunchKernelGGL((k_reverse_sector<P, B>), grid, block, 0, st, range_img, (const P*)proj_x, (const P*)proj_y_or_pitch, n, \
-                     (double)W, (double)H, fov, fabs(fd), Brad, preserve_float ? 1 : 0, yaw_center, span, back_points)
-  if (preserve_float) {
-    if (beam_rows) LT_REV_SECTOR(double, 1); else LT_REV_SECTOR(double, 0);
-  } else {
-    if (beam_rows) LT_REV_SECTOR(int, 1); else LT_REV_SECTOR(int, 0);
-  }
-#undef LT_REV_SECTOR
-  LT_HIP(hipGetLastError());
-  return LT_OK;
+  const double sec[2] = {yaw_center, span};
+  return reverse_launch(range_img, proj_x, proj_y_or_pitch, preserve_float, Brad, beam_rows != 0, fov_up, fov_down, H, W, sec,
+                        back_points, (hipStream_t)stream);
 }
 
 // ---- rendered points into another frame (the target sensor's, when it is mounted at a pose of its own) ----------

@@ -25,10 +25,8 @@
 
 #define LT_EMPTY_IDX 0x7F7F7F7F  // hipMemset(0x7F) pattern: larger than any point index
 
-// pass 1: project, z-min of the depth bits, per-workgroup count of kept points (BEAMS: the rows of a beam table,
-// project_point_beams; `beams` is then its table.  SECTOR: the columns of a horizontal sector, project_sector_column; its two
-// numbers follow the table -- 2 H + 2 doubles -- or the n_beams angles in `beams`)
-template <typename T, int BEAMS = 0, int SECTOR = 0>
+// pass 1: project, z-min of the depth bits, per-workgroup count of kept points (BEAMS, SECTOR and `beams`: project_model)
+template <typename T, int BEAMS, int SECTOR>
 __global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int n, T pi_t, T abs_fov_down, T fov,
                                                  int H, int W, const double* __restrict__ beams, int n_beams,
                                                  int drop_zero, int drop_outside, int round_key,
@@ -41,10 +39,8 @@ __global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int 
   bool keep = false;
   if (i < n) {
     const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-    proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
-                          : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
-                                             drop_outside);
-    if (SECTOR) project_sector_column<T>(o, x, y, pi_t, W, beams + (BEAMS ? 2 * H + 2 : n_beams));
+    const proj_out<T> o = project_model<T, BEAMS, SECTOR>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
+                                                          drop_outside);
     cell[i] = o.cell;
     depth_d[i] = (double)o.depth;
     xf[i] = o.xf;
@@ -163,22 +159,84 @@ __global__ __launch_bounds__(256) void k_resolve(const T* __restrict__ pts, cons
 }
 
 // ---- create_rays (laserscan.py:1092-1119): float64 trigonometry, cast to float32 last ---------------------
-__global__ __launch_bounds__(256) void k_create_rays(double fov_up, double fov_down, int H, int W,
+// One body for every target sensor.  The three choices are template arguments: as flags read at run time they cost the plain
+// sensor (lt_create_rays_dev, 64 x 2048) 0.18 us per call, more than its run-to-run spread (profiles/projection_model).
+//   column  the full circle: np.linspace(0, 360, W), + 180, wrapped.  SECTOR: column w is the cell [w, w + 1) * span / W
+//           counted clockwise from the sector's left edge, and its ray leaves through the cell's CENTRE -- not wrapped (sin
+//           and cos are periodic)
+//   row     np.linspace(fov_up, fov_down, H), or -- BEAMS: `beams_deg` (device, [H]) -- the table's angle (degrees) of row h
+//   pose    POSED: the direction, still in float64, turned by the row-major rotation R of the sensor's pose --
+//           ((r0 * x + r1 * y) + r2 * z) per component, every product and sum rounded on its own (-ffp-contract=off).
+//           Unposed rays are cast as they are, not turned by the identity: -0.0 + 0.0 is +0.0
+struct lt_rot9 { double m[9]; };
+
+template <int BEAMS, int SECTOR, int POSED>
+__global__ __launch_bounds__(256) void k_create_rays(const double* __restrict__ beams_deg, double fov_up, double fov_down,
+                                                     int H, int W, double center_deg, double span_deg, lt_rot9 R,
                                                      float* __restrict__ rays) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= H * W) return;
   const int h = idx / W, w = idx - h * W;
-  // np.linspace(a, b, n)[i] = a + i * ((b - a) / (n - 1)), last element forced to b
-  double yaw_deg = W > 1 ? (w == W - 1 ? 360.0 : 0.0 + w * (360.0 / (W - 1))) : 0.0;
-  yaw_deg += 180.0;
-  if (yaw_deg > 360.0) yaw_deg -= 360.0;
+  double yaw_deg;
+  if (SECTOR) {
+    yaw_deg = (-center_deg - span_deg / 2) + (w + 0.5) * (span_deg / W);
+  } else {
+    // np.linspace(a, b, n)[i] = a + i * ((b - a) / (n - 1)), last element forced to b
+    yaw_deg = W > 1 ? (w == W - 1 ? 360.0 : 0.0 + w * (360.0 / (W - 1))) : 0.0;
+    yaw_deg += 180.0;
+    if (yaw_deg > 360.0) yaw_deg -= 360.0;
+  }
   const double yaw = yaw_deg / 180. * M_PI;
-  double pd = H > 1 ? (h == H - 1 ? fov_down : fov_up + h * ((fov_down - fov_up) / (H - 1))) : fov_up;
+  const double pd = BEAMS ? beams_deg[h]
+                        : (H > 1 ? (h == H - 1 ? fov_down : fov_up + h * ((fov_down - fov_up) / (H - 1))) : fov_up);
   const double p = M_PI / 2 - pd / 180. * M_PI;
   const double sp = sin(p);
-  rays[3 * (size_t)idx] = (float)(sp * cos(-yaw));
-  rays[3 * (size_t)idx + 1] = (float)(sp * sin(-yaw));
-  rays[3 * (size_t)idx + 2] = (float)(cos(p) * 1.0);
+  const double x = sp * cos(-yaw), y = sp * sin(-yaw), z = cos(p) * 1.0;
+  if (POSED) {
+    rays[3 * (size_t)idx] = (float)((R.m[0] * x + R.m[1] * y) + R.m[2] * z);
+    rays[3 * (size_t)idx + 1] = (float)((R.m[3] * x + R.m[4] * y) + R.m[5] * z);
+    rays[3 * (size_t)idx + 2] = (float)((R.m[6] * x + R.m[7] * y) + R.m[8] * z);
+  } else {
+    rays[3 * (size_t)idx] = (float)x;
+    rays[3 * (size_t)idx + 1] = (float)y;
+    rays[3 * (size_t)idx + 2] = (float)z;
+  }
+}
+
+// `beams_deg` (host, [H]) or NULL, `sec` = (center, span) in degrees or NULL, `rot` (host, [9]) or NULL.  Without a table the
+// launch is asynchronous.  With one (once per sensor model) the table goes to the device in a buffer of this call, which
+// waits for its kernel.
+static int create_rays_launch(const double* beams_deg, double fov_up, double fov_down, int H, int W, const double* sec,
+                              const double* rot, float* rays, hipStream_t st) {
+  lt_rot9 R;
+  for (int k = 0; k < 9; ++k) R.m[k] = rot ? rot[k] : 0.0;  // (read by the POSED kernels only)
+  const dim3 grid((H * W + 255) / 256), block(256);
+  const double center_deg = sec ? sec[0] : 0.0, span_deg = sec ? sec[1] : 0.0;
+  double* d_beams = nullptr;
+  hipError_t e = hipSuccess;
+  if (beams_deg) {
+    LT_HIP(hipMalloc((void**)&d_beams, (size_t)H * sizeof(double)));
+    e = hipMemcpyAsync(d_beams, beams_deg, (size_t)H * sizeof(double), hipMemcpyHostToDevice, st);
+  }
+  if (e == hipSuccess) {
+#define LT_RAYS(B, S, P)                                                                                              \
+  hipLaunchKernelGGL((k_create_rays<B, S, P>), grid, block, 0, st, (const double*)d_beams, fov_up, fov_down, H, W, center_deg, \
+                     span_deg, R, rays)
+#define LT_RAYS_POSED(B, S) LT_RAYS(B, S, 1)
+#define LT_RAYS_UNPOSED(B, S) LT_RAYS(B, S, 0)
+    if (rot) LT_FOR_MODEL(beams_deg != nullptr, sec != nullptr, LT_RAYS_POSED);
+    else LT_FOR_MODEL(beams_deg != nullptr, sec != nullptr, LT_RAYS_UNPOSED);
+#undef LT_RAYS
+#undef LT_RAYS_POSED
+#undef LT_RAYS_UNPOSED
+    e = hipGetLastError();
+  }
+  if (beams_deg) {
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(d_beams);
+  }
+  LT_HIP(e);
+  return LT_OK;
 }
 
 extern "C" int lt_create_rays_dev(double fov_up, double fov_down, int H, int W, float* rays, void* stream) {
@@ -186,33 +244,7 @@ extern "C" int lt_create_rays_dev(double fov_up, double fov_down, int H, int W, 
     lt_set_error("lt_create_rays_dev: invalid argument (H=%d W=%d)", H, W);
     return LT_ERR_INVALID_ARG;
   }
-  hipLaunchKernelGGL(k_create_rays, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, fov_up, fov_down,
-                     H, W, rays);
-  LT_HIP(hipGetLastError());
-  return LT_OK;
-}
-
-// ---- create_rays of a sensor at its own pose: the direction above, still in float64, turned by the row-major rotation
-// `rot` of the pose -- ((r0 * x + r1 * y) + r2 * z) per component, every product and sum rounded on its own
-// (-ffp-contract=off) -- and cast to float32 last.  A kernel of its own: k_create_rays stays what it was.
-struct lt_rot9 { double m[9]; };
-
-__global__ __launch_bounds__(256) void k_create_rays_pose(double fov_up, double fov_down, int H, int W, lt_rot9 R,
-                                                          float* __restrict__ rays) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= H * W) return;
-  const int h = idx / W, w = idx - h * W;
-  double yaw_deg = W > 1 ? (w == W - 1 ? 360.0 : 0.0 + w * (360.0 / (W - 1))) : 0.0;
-  yaw_deg += 180.0;
-  if (yaw_deg > 360.0) yaw_deg -= 360.0;
-  const double yaw = yaw_deg / 180. * M_PI;
-  double pd = H > 1 ? (h == H - 1 ? fov_down : fov_up + h * ((fov_down - fov_up) / (H - 1))) : fov_up;
-  const double p = M_PI / 2 - pd / 180. * M_PI;
-  const double sp = sin(p);
-  const double x = sp * cos(-yaw), y = sp * sin(-yaw), z = cos(p) * 1.0;
-  rays[3 * (size_t)idx] = (float)((R.m[0] * x + R.m[1] * y) + R.m[2] * z);
-  rays[3 * (size_t)idx + 1] = (float)((R.m[3] * x + R.m[4] * y) + R.m[5] * z);
-  rays[3 * (size_t)idx + 2] = (float)((R.m[6] * x + R.m[7] * y) + R.m[8] * z);
+  return create_rays_launch(nullptr, fov_up, fov_down, H, W, nullptr, nullptr, rays, (hipStream_t)stream);
 }
 
 extern "C" int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, int W, const double* rot, float* rays,
@@ -222,39 +254,7 @@ extern "C" int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, in
     lt_set_error("lt_create_rays_pose_dev: invalid argument (H=%d W=%d)", H, W);
     return LT_ERR_INVALID_ARG;
   }
-  lt_rot9 R;
-  for (int k = 0; k < 9; ++k) R.m[k] = rot[k];
-  hipLaunchKernelGGL(k_create_rays_pose, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, fov_up, fov_down,
-                     H, W, R, rays);
-  LT_HIP(hipGetLastError());
-  return LT_OK;
-}
-
-// ---- create_rays of a sensor with a BEAM TABLE: k_create_rays' expressions with the table's angle (degrees) of row h in
-// place of the linspace term, and -- `posed` -- k_create_rays_pose's rotation in float64 before the one cast to float32.
-// A kernel of its own: the two above stay what they were.
-__global__ __launch_bounds__(256) void k_create_rays_beams(const double* __restrict__ beams_deg, int H, int W, lt_rot9 R,
-                                                           int posed, float* __restrict__ rays) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= H * W) return;
-  const int h = idx / W, w = idx - h * W;
-  double yaw_deg = W > 1 ? (w == W - 1 ? 360.0 : 0.0 + w * (360.0 / (W - 1))) : 0.0;
-  yaw_deg += 180.0;
-  if (yaw_deg > 360.0) yaw_deg -= 360.0;
-  const double yaw = yaw_deg / 180. * M_PI;
-  const double pd = beams_deg[h];
-  const double p = M_PI / 2 - pd / 180. * M_PI;
-  const double sp = sin(p);
-  const double x = sp * cos(-yaw), y = sp * sin(-yaw), z = cos(p) * 1.0;
-  if (posed) {
-    rays[3 * (size_t)idx] = (float)((R.m[0] * x + R.m[1] * y) + R.m[2] * z);
-    rays[3 * (size_t)idx + 1] = (float)((R.m[3] * x + R.m[4] * y) + R.m[5] * z);
-    rays[3 * (size_t)idx + 2] = (float)((R.m[6] * x + R.m[7] * y) + R.m[8] * z);
-  } else {
-    rays[3 * (size_t)idx] = (float)x;
-    rays[3 * (size_t)idx + 1] = (float)y;
-    rays[3 * (size_t)idx + 2] = (float)z;
-  }
+  return create_rays_launch(nullptr, fov_up, fov_down, H, W, nullptr, rot, rays, (hipStream_t)stream);
 }
 
 extern "C" int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, const double* rot, float* rays,
@@ -263,51 +263,7 @@ extern "C" int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, c
     lt_set_error("lt_create_rays_beams_dev: invalid argument (H=%d W=%d)", H, W);
     return LT_ERR_INVALID_ARG;
   }
-  lt_rot9 R;
-  for (int k = 0; k < 9; ++k) R.m[k] = rot ? rot[k] : (k % 4 == 0 ? 1.0 : 0.0);
-  // once per sensor model: the table goes to the device in a buffer of this call, which waits for its kernel
-  double* d_beams = nullptr;
-  LT_HIP(hipMalloc((void**)&d_beams, (size_t)H * sizeof(double)));
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(d_beams, beams_deg, (size_t)H * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_create_rays_beams, dim3((H * W + 255) / 256), dim3(256), 0, st, (const double*)d_beams, H, W, R,
-                       rot ? 1 : 0, rays);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d_beams);
-  LT_HIP(e);
-  return LT_OK;
-}
-
-// ---- create_rays of a sensor with a horizontal SECTOR: column w is the cell [w, w + 1) * span / W counted clockwise from the
-// sector's left edge, and its ray leaves through the cell's CENTRE -- yaw_deg = (-center - span / 2) + (w + 0.5) * (span / W),
-// not wrapped (sin and cos are periodic); from there on k_create_rays' expressions.  The row term is k_create_rays' linspace
-// or -- `beams_deg` given -- the table's angle as in k_create_rays_beams; `posed`: k_create_rays_pose's rotation in float64
-// before the one cast to float32.  One kernel for the four combinations; the three kernels above stay what they were.
-__global__ __launch_bounds__(256) void k_create_rays_sector(const double* __restrict__ beams_deg, double fov_up,
-                                                            double fov_down, int H, int W, double center_deg, double span_deg,
-                                                            lt_rot9 R, int posed, float* __restrict__ rays) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= H * W) return;
-  const int h = idx / W, w = idx - h * W;
-  const double yaw_deg = (-center_deg - span_deg / 2) + (w + 0.5) * (span_deg / W);
-  const double yaw = yaw_deg / 180. * M_PI;
-  const double pd = beams_deg ? beams_deg[h]
-                              : (H > 1 ? (h == H - 1 ? fov_down : fov_up + h * ((fov_down - fov_up) / (H - 1))) : fov_up);
-  const double p = M_PI / 2 - pd / 180. * M_PI;
-  const double sp = sin(p);
-  const double x = sp * cos(-yaw), y = sp * sin(-yaw), z = cos(p) * 1.0;
-  if (posed) {
-    rays[3 * (size_t)idx] = (float)((R.m[0] * x + R.m[1] * y) + R.m[2] * z);
-    rays[3 * (size_t)idx + 1] = (float)((R.m[3] * x + R.m[4] * y) + R.m[5] * z);
-    rays[3 * (size_t)idx + 2] = (float)((R.m[6] * x + R.m[7] * y) + R.m[8] * z);
-  } else {
-    rays[3 * (size_t)idx] = (float)x;
-    rays[3 * (size_t)idx + 1] = (float)y;
-    rays[3 * (size_t)idx + 2] = (float)z;
-  }
+  return create_rays_launch(beams_deg, 0.0, 0.0, H, W, nullptr, rot, rays, (hipStream_t)stream);
 }
 
 extern "C" int lt_create_rays_sector_dev(const double* beams_deg, double fov_up, double fov_down, int H, int W,
@@ -316,65 +272,45 @@ extern "C" int lt_create_rays_sector_dev(const double* beams_deg, double fov_up,
     lt_set_error("lt_create_rays_sector_dev: invalid argument (H=%d W=%d center=%g span=%g)", H, W, center_deg, span_deg);
     return LT_ERR_INVALID_ARG;
   }
-  lt_rot9 R;
-  for (int k = 0; k < 9; ++k) R.m[k] = rot ? rot[k] : (k % 4 == 0 ? 1.0 : 0.0);
-  hipStream_t st = (hipStream_t)stream;
-  if (!beams_deg) {
-    hipLaunchKernelGGL(k_create_rays_sector, dim3((H * W + 255) / 256), dim3(256), 0, st, (const double*)nullptr, fov_up,
-                       fov_down, H, W, center_deg, span_deg, R, rot ? 1 : 0, rays);
-    LT_HIP(hipGetLastError());
-    return LT_OK;
-  }
-  // with a table (once per sensor model): it goes to the device in a buffer of this call, which waits for its kernel
-  double* d_beams = nullptr;
-  LT_HIP(hipMalloc((void**)&d_beams, (size_t)H * sizeof(double)));
-  hipError_t e = hipMemcpyAsync(d_beams, beams_deg, (size_t)H * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_create_rays_sector, dim3((H * W + 255) / 256), dim3(256), 0, st, (const double*)d_beams, fov_up,
-                       fov_down, H, W, center_deg, span_deg, R, rot ? 1 : 0, rays);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d_beams);
-  LT_HIP(e);
-  return LT_OK;
+  const double sec[2] = {center_deg, span_deg};
+  return create_rays_launch(beams_deg, fov_up, fov_down, H, W, sec, rot, rays, (hipStream_t)stream);
 }
 
-// LT_PROJ_BEAM_ROWS: the caller's table (Brad[H], halfw[H]) checked and completed by the field of view in radians, which
-// the H == 1 keep rule reads: tab[2 * H + 2].  Returns the number of doubles, 0 when the arguments do not fit the flag.
-static int beam_rows_table(const char* who, const double* beam_angles, int n_beams, unsigned flags, int H, double fov_up_deg,
-                           double fov_down_deg, double* tab) {
-  if (flags != (LT_PROJ_BEAM_ROWS | LT_PROJ_NEW | LT_PROJ_REMOVE) || n_beams != H || !beam_angles || 2 * H + 2 > 1024) {
+// The doubles a projection uploads for its sensor model, into `tab` [1024]; returns their number (0: none), -1 when the
+// arguments do not fit the flags.  Layout (project_model reads it):
+//   neither flag        the caller's n_beams hard-coded angles (n_beams may be 0)
+//   LT_PROJ_BEAM_ROWS   the caller's table (Brad[H], halfw[H]) checked and completed by the field of view in radians, which
+//                       the H == 1 keep rule reads: 2 * H + 2 doubles
+//   LT_PROJ_SECTOR      behind either, the two numbers of the sector -- the yaw of its middle (|.| <= pi) and its width (in
+//                       (0, 2 pi)), radians -- from lt_projector_set_sector / lt_range_projection_set_sector (`sec`, NULL:
+//                       none was set)
+static int model_table(const char* who, const double* beam_angles, int n_beams, unsigned flags, double fov_up_deg,
+                       double fov_down_deg, int H, const double* sec, double* tab) {
+  const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0, sector = (flags & LT_PROJ_SECTOR) != 0;
+  if (rows && ((flags & ~LT_PROJ_SECTOR) != (LT_PROJ_BEAM_ROWS | LT_PROJ_NEW | LT_PROJ_REMOVE) || n_beams != H || !beam_angles ||
+               2 * H + 2 > 1024)) {
     lt_set_error("%s: LT_PROJ_BEAM_ROWS goes with LT_PROJ_NEW | LT_PROJ_REMOVE only (flags=%u) and a table of n_beams == H "
-                 "<= 511 rows (n_beams=%d H=%d)", who, flags, n_beams, H);
-    return 0;
+                 "<= 511 rows (n_beams=%d H=%d)", who, flags & ~LT_PROJ_SECTOR, n_beams, H);
+    return -1;
   }
-  memcpy(tab, beam_angles, 2 * (size_t)H * sizeof(double));
-  tab[2 * H] = fov_down_deg / 180.0 * M_PI;
-  tab[2 * H + 1] = fov_up_deg / 180.0 * M_PI;
-  return 2 * H + 2;
-}
-
-// LT_PROJ_SECTOR: the two numbers of the sector -- the yaw of its middle (|.| <= pi) and its width (in (0, 2 pi)), radians --
-// come from lt_projector_set_sector / lt_range_projection_set_sector (`sec`, NULL: none was set).  They are appended to
-// `tab`: behind the n_tab doubles of the completed table when LT_PROJ_BEAM_ROWS is set as well, else behind a copy of the
-// n_beams angles (n_beams may be 0).  Returns the number of doubles, 0 when the arguments do not fit the flag.
-static int sector_tail(const char* who, const double* sec, const double* beam_angles, int n_beams, unsigned flags, double* tab,
-                       int n_tab) {
-  const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0;
-  if ((flags & ~LT_PROJ_BEAM_ROWS) != (LT_PROJ_SECTOR | LT_PROJ_NEW | LT_PROJ_REMOVE) || !sec || n_beams < 0 ||
-      (n_beams > 0 && !beam_angles) || (rows ? n_tab : n_beams) + 2 > 1024) {
+  const int n_given = rows ? 2 * H : n_beams;      // doubles of the caller's
+  const int n_rows = rows ? 2 * H + 2 : n_beams;   // ... and of the row model that the kernels read
+  if (sector && ((flags & ~LT_PROJ_BEAM_ROWS) != (LT_PROJ_SECTOR | LT_PROJ_NEW | LT_PROJ_REMOVE) || !sec || n_beams < 0 ||
+                 (n_beams > 0 && !beam_angles) || n_rows + 2 > 1024)) {
     lt_set_error("%s: LT_PROJ_SECTOR goes with LT_PROJ_NEW | LT_PROJ_REMOVE only, with or without LT_PROJ_BEAM_ROWS (flags=%u), "
                  "and after the sector was set (%s; n_beams=%d)", who, flags, sec ? "it was" : "it was not", n_beams);
-    return 0;
+    return -1;
   }
-  if (!rows) {
-    if (n_beams > 0) memcpy(tab, beam_angles, (size_t)n_beams * sizeof(double));
-    n_tab = n_beams;
+  if (n_given > 0) memcpy(tab, beam_angles, (size_t)n_given * sizeof(double));
+  if (rows) {
+    tab[2 * H] = fov_down_deg / 180.0 * M_PI;
+    tab[2 * H + 1] = fov_up_deg / 180.0 * M_PI;
   }
-  tab[n_tab] = sec[0];
-  tab[n_tab + 1] = sec[1];
-  return n_tab + 2;
+  if (sector) {
+    tab[n_rows] = sec[0];
+    tab[n_rows + 1] = sec[1];
+  }
+  return n_rows + (sector ? 2 : 0);
 }
 
 static bool sector_ok(const char* who, double yaw_center, double span) {
@@ -456,23 +392,16 @@ int run_projection(proj_ws& w, const T* pts, const float* rem, const unsigned* l
   w.armed = false;
   const int round_key = (flags & LT_PROJ_NEW) ? 1 : 0;
   if (n > 0) {
-    if ((flags & LT_PROJ_BEAM_ROWS) && (flags & LT_PROJ_SECTOR))
-      hipLaunchKernelGGL((k_project<T, 1, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
-                         (const double*)w.beams, n_beams, 1, 1, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
-                         w.blockcount);
-    else if (flags & LT_PROJ_SECTOR)
-      hipLaunchKernelGGL((k_project<T, 0, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
-                         (const double*)w.beams, n_beams, 1, 1, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
-                         w.blockcount);
-    else if (flags & LT_PROJ_BEAM_ROWS)
-      hipLaunchKernelGGL((k_project<T, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
-                         (const double*)w.beams, n_beams, 1, 1, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
-                         w.blockcount);
-    else
-      hipLaunchKernelGGL(k_project<T>, dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
-                         (const double*)w.beams, n_beams, (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW)) ? 1 : 0,
-                         (flags & LT_PROJ_REMOVE) ? 1 : 0, round_key, w.cell, w.depth_d, (T*)w.xf, (T*)w.yf, w.cellmin,
-                         w.blockcount);
+    const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0, sector = (flags & LT_PROJ_SECTOR) != 0;
+    // rows and sector go with LT_PROJ_NEW | LT_PROJ_REMOVE only: both drops
+    const int drop_zero = (rows || sector || (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW))) ? 1 : 0;
+    const int drop_outside = (rows || sector || (flags & LT_PROJ_REMOVE)) ? 1 : 0;
+#define LT_PROJECT(B, S)                                                                                                   \
+  hipLaunchKernelGGL((k_project<T, B, S>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,          \
+                     (const double*)w.beams, n_beams, drop_zero, drop_outside, round_key, w.cell, w.depth_d, (T*)w.xf,      \
+                     (T*)w.yf, w.cellmin, w.blockcount)
+    LT_FOR_MODEL(rows, sector, LT_PROJECT);
+#undef LT_PROJECT
     hipLaunchKernelGGL(k_assign<T>, dim3(nb), dim3(256), 0, st, pts, rem, label, n, W, (const int*)w.cell,
                        (const double*)w.depth_d, (const T*)w.xf, (const T*)w.yf,
                        (const unsigned long long*)w.cellmin, w.blockcount, round_key, w.idxmin,
@@ -518,24 +447,16 @@ extern "C" int lt_range_projection_dev(const void* points, int is_f64, const flo
     return LT_ERR_INVALID_ARG;
   }
   double tab[1024];
-  int n_tab = 0;
-  if (flags & LT_PROJ_BEAM_ROWS) {
-    n_tab = beam_rows_table("lt_range_projection", beam_angles, n_beams, flags & ~LT_PROJ_SECTOR, H, fov_up, fov_down, tab);
-    if (!n_tab) return LT_ERR_INVALID_ARG;
-  }
   std::lock_guard<std::mutex> lock(g_pmu);
-  if (flags & LT_PROJ_SECTOR) {
-    n_tab = sector_tail("lt_range_projection", g_sector_set ? g_sector : nullptr, beam_angles, n_beams, flags, tab, n_tab);
-    if (!n_tab) return LT_ERR_INVALID_ARG;
-  }
+  const int n_tab = model_table("lt_range_projection", beam_angles, n_beams, flags, fov_up, fov_down, H,
+                                g_sector_set ? g_sector : nullptr, tab);
+  if (n_tab < 0) return LT_ERR_INVALID_ARG;
   int dev = 0;
   LT_HIP(hipGetDevice(&dev));
   LT_CHECK(pws_reserve(g_pws, dev, (size_t)n, (size_t)H * W));
   hipStream_t st = (hipStream_t)stream;
   if (n_tab > 0)  // (run_projection waits for the stream before `tab` goes out of scope)
     LT_HIP(hipMemcpyAsync(g_pws.beams, tab, n_tab * sizeof(double), hipMemcpyHostToDevice, st));
-  else if (n_beams > 0)
-    LT_HIP(hipMemcpyAsync(g_pws.beams, beam_angles, n_beams * sizeof(double), hipMemcpyHostToDevice, st));
   if (is_f64)
     return run_projection<double>(g_pws, (const double*)points, rem, label, n, fov_up, fov_down, H, W, n_beams, flags,
                                   color_lut, lut_len, (double*)points_kept, rem_kept, label_kept, (double*)depth_kept,
@@ -602,9 +523,8 @@ __device__ __forceinline__ double pb_unord(unsigned long long k) {
 }
 
 // MODE 0: the single-key variants (NEW on any dtype, OLD on float32).  MODE 1: OLD on float64 -- depth minimum only.
-// BEAMS: the rows of a beam table (project_point_beams; `beams` is then its table), MODE 0 only.  SECTOR: the columns of a
-// horizontal sector (project_sector_column; its two numbers follow the table or the n_beams angles), MODE 0 only.
-template <typename T, int MODE, int BEAMS = 0, int SECTOR = 0>
+// BEAMS, SECTOR and `beams`: project_model; MODE 0 only.
+template <typename T, int MODE, int BEAMS, int SECTOR>
 __global__ __launch_bounds__(256) void k_pb_project(pb_args A, T pi_t, T abs_fov_down, T fov, int H, int W,
                                                     const double* __restrict__ beams, int n_beams, int drop_zero,
                                                     int drop_outside) {
@@ -615,10 +535,8 @@ __global__ __launch_bounds__(256) void k_pb_project(pb_args A, T pi_t, T abs_fov
   if (i < c.n) {
     const T* pts = (const T*)c.pts;
     const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-    proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
-                          : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
-                                             drop_outside);
-    if (SECTOR) project_sector_column<T>(o, x, y, pi_t, W, beams + (BEAMS ? 2 * H + 2 : n_beams));
+    const proj_out<T> o = project_model<T, BEAMS, SECTOR>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
+                                                          drop_outside);
     keep = o.cell >= 0;
     if (keep) {
       if (MODE == 0) atomicMin(&c.key[o.cell], pb_key<T>(o.depth, i));
@@ -743,7 +661,7 @@ __global__ __launch_bounds__(64) void k_pb_bnds(pb_args A) {
   if (c.bacc) pb_fold_bounds(c, threadIdx.x);
 }
 
-template <typename T, int MODE, int BEAMS = 0, int SECTOR = 0>
+template <typename T, int MODE, int BEAMS, int SECTOR>
 __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cloud, T pi_t, T abs_fov_down, T fov, int H,
                                                     int W, const double* __restrict__ beams, int n_beams, int drop_zero,
                                                     int drop_outside, const float* __restrict__ lut, int lut_len,
@@ -766,11 +684,8 @@ __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cl
   o.depth = (T)0; o.xf = (T)0; o.yf = (T)0; o.px = 0; o.py = 0; o.cell = -1;
   if (i >= 0) {
     x = pts[3 * (size_t)i]; y = pts[3 * (size_t)i + 1]; z = pts[3 * (size_t)i + 2];
-    if (has ? (want_xy || c.range_img) : true) {
-      o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, beams)
-                : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
-      if (SECTOR) project_sector_column<T>(o, x, y, pi_t, W, beams + (BEAMS ? 2 * H + 2 : n_beams));
-    }
+    if (has ? (want_xy || c.range_img) : true)
+      o = project_model<T, BEAMS, SECTOR>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
   }
   int k = -1;
   if (has && have_prefix) k = c.wprefix[i >> 6] + __popcll(c.keep[i >> 6] & ((1ull << (i & 63)) - 1ull));
@@ -871,49 +786,33 @@ int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool nee
   const int cells = H * W, bpc = (cells + 255) / 256;
   const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0;  // (never with old_f64: the flag goes with LT_PROJ_NEW)
   const bool sector = (flags & LT_PROJ_SECTOR) != 0;   // (the same)
+  // MODE 1 (old_f64) has neither rows nor a sector; the other instantiations are MODE 0
+#define LT_PB_PROJECT(MODE, B, S)                                                                                          \
+  hipLaunchKernelGGL((k_pb_project<T, MODE, B, S>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, \
+                     H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside)
+#define LT_PB_RESOLVE(MODE, B, S)                                                                                          \
+  hipLaunchKernelGGL((k_pb_resolve<T, MODE, B, S>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI,             \
+                     (T)fabs(fd), (T)fov, H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len,   \
+                     range_init, rem_init, xyz_init, need_prefix ? 1 : 0)
+#define LT_PB_PROJECT0(B, S) LT_PB_PROJECT(0, B, S)
+#define LT_PB_RESOLVE0(B, S) LT_PB_RESOLVE(0, B, S)
   if (total_blocks > 0) {
-    if (sector) {
-      if (rows)
-        hipLaunchKernelGGL((k_pb_project<T, 0, 1, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H,
-                           W, (const double*)p->beams, n_beams, drop_zero, drop_outside);
-      else
-        hipLaunchKernelGGL((k_pb_project<T, 0, 0, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H,
-                           W, (const double*)p->beams, n_beams, drop_zero, drop_outside);
-    } else if (rows) {
-      hipLaunchKernelGGL((k_pb_project<T, 0, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
-                         (const double*)p->beams, n_beams, drop_zero, drop_outside);
-    } else if (old_f64) {
-      hipLaunchKernelGGL((k_pb_project<T, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
-                         (const double*)p->beams, n_beams, drop_zero, drop_outside);
+    if (old_f64) {
+      LT_PB_PROJECT(1, 0, 0);
       hipLaunchKernelGGL(k_pb_assign, dim3(total_blocks), dim3(256), 0, st, A, M_PI, fabs(fd), fov, H, W,
                          (const double*)p->beams, n_beams, drop_zero, drop_outside);
     } else {
-      hipLaunchKernelGGL((k_pb_project<T, 0>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, H, W,
-                         (const double*)p->beams, n_beams, drop_zero, drop_outside);
+      LT_FOR_MODEL(rows, sector, LT_PB_PROJECT0);
     }
   }
   if (need_prefix) hipLaunchKernelGGL(k_pb_prefix, dim3(A.n_clouds), dim3(256), 0, st, A);
   else if (bnds_only) hipLaunchKernelGGL(k_pb_bnds, dim3(A.n_clouds), dim3(64), 0, st, A);
-  if (sector && rows)
-    hipLaunchKernelGGL((k_pb_resolve<T, 0, 1, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd),
-                       (T)fov, H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init,
-                       rem_init, xyz_init, need_prefix ? 1 : 0);
-  else if (sector)
-    hipLaunchKernelGGL((k_pb_resolve<T, 0, 0, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd),
-                       (T)fov, H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init,
-                       rem_init, xyz_init, need_prefix ? 1 : 0);
-  else if (rows)
-    hipLaunchKernelGGL((k_pb_resolve<T, 0, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd), (T)fov,
-                       H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init, rem_init,
-                       xyz_init, need_prefix ? 1 : 0);
-  else if (old_f64)
-    hipLaunchKernelGGL((k_pb_resolve<T, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd), (T)fov,
-                       H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init, rem_init,
-                       xyz_init, need_prefix ? 1 : 0);
-  else
-    hipLaunchKernelGGL((k_pb_resolve<T, 0>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI, (T)fabs(fd), (T)fov,
-                       H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len, range_init, rem_init,
-                       xyz_init, need_prefix ? 1 : 0);
+  if (old_f64) LT_PB_RESOLVE(1, 0, 0);
+  else LT_FOR_MODEL(rows, sector, LT_PB_RESOLVE0);
+#undef LT_PB_PROJECT
+#undef LT_PB_RESOLVE
+#undef LT_PB_PROJECT0
+#undef LT_PB_RESOLVE0
   LT_HIP(hipGetLastError());
   return LT_OK;
 }
@@ -983,16 +882,6 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
     lt_set_error("lt_range_projection_batch_dev: invalid argument (n_clouds=%d H=%d W=%d n_beams=%d)", n_clouds, H, W, n_beams);
     return LT_ERR_INVALID_ARG;
   }
-  double tab[1024];
-  const double* given = beam_angles;
-  const int n_given = n_beams;
-  if (flags & LT_PROJ_BEAM_ROWS) {  // from here on `beam_angles` / `n_beams` are the completed table
-    n_beams = beam_rows_table("lt_range_projection_batch_dev", beam_angles, n_beams, flags & ~LT_PROJ_SECTOR, H, fov_up,
-                              fov_down, tab);
-    if (!n_beams) return LT_ERR_INVALID_ARG;
-    beam_angles = tab;
-  }
-  int n_dev = n_beams;  // doubles of `beam_angles` that the kernels read: with a sector, two more than n_beams
   size_t n_max = 0;
   for (int k = 0; k < n_clouds; ++k) {
     if (clouds[k].n < 0 || (clouds[k].n > 0 && !clouds[k].points)) {
@@ -1002,12 +891,10 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
     n_max = std::max(n_max, (size_t)clouds[k].n);
   }
   std::lock_guard<std::mutex> lock(p->mu);
-  if (flags & LT_PROJ_SECTOR) {
-    n_dev = sector_tail("lt_range_projection_batch_dev", p->sector_set ? p->sector : nullptr, given, n_given, flags, tab,
-                        (flags & LT_PROJ_BEAM_ROWS) ? n_beams : 0);
-    if (!n_dev) return LT_ERR_INVALID_ARG;
-    beam_angles = tab;
-  }
+  double tab[1024];
+  const int n_dev = model_table("lt_range_projection_batch_dev", beam_angles, n_beams, flags, fov_up, fov_down, H,
+                                p->sector_set ? p->sector : nullptr, tab);
+  if (n_dev < 0) return LT_ERR_INVALID_ARG;
   LT_HIP(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
   const bool old_f64 = is_f64 && !(flags & LT_PROJ_NEW);
@@ -1025,10 +912,10 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
   }
   p->armed = false;  // (until the resolve pass of this call has been queued)
   if (old_f64) p->dmin_armed = false;
-  if (n_dev > 0 && (n_dev != p->n_beams_cached || memcmp(p->beams_host, beam_angles, n_dev * sizeof(double)) != 0)) {
+  if (n_dev > 0 && (n_dev != p->n_beams_cached || memcmp(p->beams_host, tab, n_dev * sizeof(double)) != 0)) {
     // the table is read by kernels of EARLIER calls on this stream: the copy is stream-ordered behind them; a pageable
     // source is staged by the runtime before the call returns, so beams_host may be overwritten by the next call
-    memcpy(p->beams_host, beam_angles, n_dev * sizeof(double));
+    memcpy(p->beams_host, tab, n_dev * sizeof(double));
     LT_HIP(hipMemcpyAsync(p->beams, p->beams_host, n_dev * sizeof(double), hipMemcpyHostToDevice, st));
     p->n_beams_cached = n_dev;
   }

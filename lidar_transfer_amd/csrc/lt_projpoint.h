@@ -169,6 +169,20 @@ __device__ __forceinline__ void project_sector_column(proj_out<T>& o, T x, T y, 
   o.cell = (o.cell >= 0 && in) ? o.py * W + o.px : -1;
 }
 
+// One point through the sensor model of a projection kernel -- the one entry point of k_project, k_pb_project and
+// k_pb_resolve.  BEAMS: the rows of a beam table (project_point_beams; `tab` is then the completed table of 2 H + 2 doubles),
+// else the linear rows (project_point; `tab` holds the n_beams hard-coded angles, n_beams may be 0).  SECTOR: the columns of
+// a horizontal sector on top; its two numbers follow the table or the angles in `tab` -- only this function knows where.
+template <typename T, int BEAMS, int SECTOR>
+__device__ __forceinline__ proj_out<T> project_model(T x, T y, T z, T pi_t, T abs_fov_down, T fov, int H, int W,
+                                                     const double* __restrict__ tab, int n_beams, bool drop_zero,
+                                                     bool drop_outside) {
+  proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, tab)
+                        : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, tab, n_beams, drop_zero, drop_outside);
+  if (SECTOR) project_sector_column<T>(o, x, y, pi_t, W, tab + (BEAMS ? 2 * H + 2 : n_beams));
+  return o;
+}
+
 // The z-min key of one point (see the batched projection in lt_project.hip): hi word = float32 bits of the depth (positive
 // floats order like unsigned integers); lo word = 0x7fffffff - index for a point whose depth lies BELOW its float32 value
 // (they beat the others, the highest index first), 0x80000000 | index otherwise (lowest index first).  float32 clouds never

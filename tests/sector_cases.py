@@ -11,7 +11,7 @@ import beam_cases as bc
 #: (centre, span, W): W * 360 / span an integer; not an integer; straddling the seam behind the sensor; tiny
 SECTORS = ((0.0, 120.0, 256), (35.0, 70.4, 301), (170.0, 100.0, 200), (-90.0, 30.0, 7))
 #: the sectors of the ulp rule on the rays: (-90, 30, 7) has a cell centre exactly on -90 degrees
-RAY_SECTORS = SECTORS[:3]
+RAY_SECTORS = SECTORS[:3] + ((35.0, 70.4, 1),)
 LT_BIN_SLACK = 4e-3
 
 

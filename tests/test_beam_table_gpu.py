@@ -45,7 +45,9 @@ def _differs(a, b):
 
 # ---- rays -----------------------------------------------------------------------------------------------------------------------
 LINSPACE_SENSORS = ((3.0, -25.0, 64, 1024), (10.0, -30.0, 32, 2048), (15.0, -15.0, 16, 301), (0.0, -10.0, 1, 720),
-                    (10.0, -30.0, 32, 1)) + tm.RAY_SENSORS
+                    (10.0, -30.0, 32, 1), (3.0, -25.0, 1, 1), (3.0, -25.0, 3, 171)) + tm.RAY_SENSORS
+#: the tables of the ray tests: the two sensors and a table of one row (at W = 1 a single ray)
+RAY_TABLES = bc.TABLES + (bc.TINY[0] + (1,),)
 
 
 def test_device_rays_of_the_linspace_table_are_create_rays_bit_for_bit():
@@ -67,20 +69,21 @@ def test_device_rays_of_the_linspace_table_are_create_rays_bit_for_bit():
 @pytest.mark.parametrize("W", [1, 301, 1024])
 def test_device_rays_of_the_two_tables_equal_the_restatement(W):
     from lidar_transfer_amd.laserscan import create_rays_device
-    for name, table, fov, _ in bc.TABLES:
+    for name, table, fov, _ in RAY_TABLES:
         dev = create_rays_device(fov[0], fov[1], len(table), W, beam_table=table).cpu().numpy()
         n = tm._rays_rule(dev, bc.table_rays(table, W), (name, W))
         assert np.abs(np.linalg.norm(dev.astype(np.float64), axis=1) - 1).max() < 1e-6
         print(f"\n{name} x {W}: {n} of {dev.size} elements not bit-equal to the restatement")
 
 
-@pytest.mark.parametrize("W", [1023, 1025])
+@pytest.mark.parametrize("W", [1, 1023, 1025])
 @pytest.mark.parametrize("pose", ["example", "general"])
 def test_posed_device_rays_of_the_two_tables_equal_the_restatement(pose, W):
-    """W - 1 no multiple of 4: no ray ON a zero of a rotated component (tests/test_mount_gpu.py, RAY_SENSORS)"""
+    """W - 1 no multiple of 4: no ray ON a zero of a rotated component (tests/test_mount_gpu.py, RAY_SENSORS); W = 1: the one ray
+    at the seam, which every W has, and with the table of one row a launch of a single ray"""
     from lidar_transfer_amd.laserscan import create_rays_device
     rot = dict(mc.RENDER_POSES)[pose][:3, :3]
-    for name, table, fov, _ in bc.TABLES:
+    for name, table, fov, _ in RAY_TABLES:
         dev = create_rays_device(fov[0], fov[1], len(table), W, rot=rot, beam_table=table).cpu().numpy()
         n = tm._rays_rule(dev, bc.table_rays(table, W, rot), (name, pose, W))
         print(f"\n{name} x {W} at the {pose} pose: {n} of {dev.size} elements not bit-equal to the restatement")

@@ -72,7 +72,7 @@ def test_rays_without_a_rotation_and_with_the_identity_are_create_rays():
                                       ("general", mc.POSE_GENERAL[:3, :3])])
 def test_posed_rays_equal_the_float64_restatement(name, rot):
     from lidar_transfer_amd.laserscan import create_rays_device
-    for fu, fd, H, W in RAY_SENSORS:
+    for fu, fd, H, W in RAY_SENSORS + ((3.0, -25.0, 1, 1), (3.0, -25.0, 3, 171)):
         dev = create_rays_device(fu, fd, H, W, rot=rot).cpu().numpy()
         host = mc.posed_rays(fu, fd, H, W, rot)
         n = _rays_rule(dev, host, (name, H, W))

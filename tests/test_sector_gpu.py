@@ -48,7 +48,8 @@ def test_device_rays_of_a_sector_equal_the_restatement(si, posed):
     from lidar_transfer_amd.laserscan import create_rays_device
     c, s, W = sc.RAY_SECTORS[si]
     rot = mc.POSE_GENERAL[:3, :3] if posed else None
-    for table, fov, H in ((None, LINEAR_FOV, 1), (None, LINEAR_FOV, 16), (bc.VLP32C, bc.VLP32C_FOV, 32)):
+    for table, fov, H in ((None, LINEAR_FOV, 1), (None, LINEAR_FOV, 16), (bc.VLP32C, bc.VLP32C_FOV, 32),
+                          (bc.TINY[0][1], bc.TINY[0][2], 1)):
         dev = create_rays_device(fov[0], fov[1], H, W, rot=rot, beam_table=table, sector=(c, s)).cpu().numpy()
         assert dev.shape == (H * W, 3) and dev.dtype == np.float32
         n = tm._rays_rule(dev, sc.sector_rays((c, s), W, fov, H, table, rot), (c, s, W, H, posed))
