@@ -254,6 +254,17 @@ int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, const double
 int lt_create_rays_sector_dev(const double* beams_deg, double fov_up, double fov_down, int H, int W, double center_deg,
                               double span_deg, const double* rot, float* rays, void* stream);
 
+/* The rays of a sensor with a BEAM TABLE whose beams carry AZIMUTH OFFSETS: the lasers of one firing do not share an azimuth.
+ * az_deg[h] (HOST, [H] float64, degrees, |.| <= 90, in the table's row order; NULL = none) is measured like `center_deg`:
+ * atan2(y, x) in the sensor's frame, positive to the left -- beam h of column w looks az_deg[h] to the LEFT of the column's
+ * nominal direction: yaw_deg = nominal(w) - az_deg[h] in float64, nominal(w) being lt_create_rays_dev's column (linspace(0,
+ * 360, W) + 180, wrapped) or, with `sec` (HOST [2]: center_deg, span_deg as in lt_create_rays_sector_dev; NULL = the full
+ * circle), the centre of the sector's cell w; no further wrap.  The rest is lt_create_rays_beams_dev's: beams_deg (HOST [H],
+ * mandatory), `rot` (HOST [9], NULL = none), one cast to float32.  A row whose offset is 0 gets the bits it has without
+ * offsets.  The call waits for `stream`. */
+int lt_create_rays_beams_az_dev(const double* beams_deg, const double* az_deg, int H, int W, const double* sec,
+                                const double* rot, float* rays, void* stream);
+
 #define LT_PROJ_REMOVE 1u /* `remove=True`: drop depth == 0 and points whose proj_y is outside [0, 1]   */
 #define LT_PROJ_NEW 2u    /* do_range_projection_new: depth == 0 is always dropped (laserscan.py:306-309) */
 /* LT_PROJ_BEAM_ROWS -- the image rows are the beams of a TABLE (a target sensor whose beams are not evenly spaced), defined
@@ -281,6 +292,22 @@ int lt_create_rays_sector_dev(const double* beams_deg, double fov_up, double fov
 /* The sector that LT_PROJ_SECTOR reads in lt_range_projection_dev / lt_range_projection (one per process, kept until set
  * again; span == 0 clears it).  LT_ERR_INVALID_ARG unless |yaw_center| <= pi and 0 < span < 2 pi (radians). */
 int lt_range_projection_set_sector(double yaw_center, double span);
+/* LT_PROJ_BEAM_AZIMUTH -- the beams of the table carry AZIMUTH OFFSETS (lt_create_rays_beams_az_dev), defined together with
+ * LT_PROJ_BEAM_ROWS | LT_PROJ_NEW | LT_PROJ_REMOVE only, with or without LT_PROJ_SECTOR (any other combination:
+ * LT_ERR_INVALID_ARG), for the same three calls.  The offsets -- az[H] in radians, az = az_deg / 180 * pi, in the table's row
+ * order -- are set beforehand: lt_projector_set_beam_azimuth for lt_range_projection_batch_dev,
+ * lt_range_projection_set_beam_azimuth for the two single-cloud calls; the flag without offsets set for exactly H rows is
+ * LT_ERR_INVALID_ARG, so no existing signature, struct or argument changes its meaning.  Per point, in the cloud's dtype T: the
+ * row and every keep condition are LT_PROJ_BEAM_ROWS'; then, with a = (T)az[row], the point's NOMINAL yaw is
+ * y' = -atan2(y, x) + a -- the column whose beam `row` looks at the point.  Full circle: y' - 2 pi if y' > pi, y' + 2 pi if
+ * y' < -pi (only strictly outside: the closed interval of the plain rule stays), proj_xf = 0.5 * (y' / pi + 1) * W, proj_x =
+ * floor clamped to [0, W - 1].  With LT_PROJ_SECTOR: d = y' - yc, then that flag's wrap, u, keep rule and column.  proj_xf
+ * is the nominal coordinate.  The z-min rule and the empty cells are LT_PROJ_BEAM_ROWS'. */
+#define LT_PROJ_BEAM_AZIMUTH 16u
+/* The offsets that LT_PROJ_BEAM_AZIMUTH reads in lt_range_projection_dev / lt_range_projection (one set per process, kept
+ * until set again; NULL or H == 0 clears them): az_rad HOST [H], copied.  LT_ERR_INVALID_ARG unless 1 <= H <= 511 and every
+ * offset is finite with |az| <= pi / 2. */
+int lt_range_projection_set_beam_azimuth(const double* az_rad, int H);
 
 /*
  * lt_range_projection_dev -- point cloud -> H x W spherical image, closest point per cell (atomic
@@ -373,6 +400,10 @@ int lt_projector_destroy(lt_projector* projector);
  * span == 0 clears it): yaw_center = -center / 180 * pi, span the width, radians.  LT_ERR_INVALID_ARG unless
  * |yaw_center| <= pi and 0 < span < 2 pi.  Host side only: it takes effect with the next call. */
 int lt_projector_set_sector(lt_projector* projector, double yaw_center, double span);
+/* The offsets that LT_PROJ_BEAM_AZIMUTH reads in this projector's lt_range_projection_batch_dev calls (kept until set again;
+ * NULL or H == 0 clears them): az_rad HOST [H] radians in the table's row order, copied.  LT_ERR_INVALID_ARG unless
+ * 1 <= H <= 511 and every offset is finite with |az| <= pi / 2.  Host side only: it takes effect with the next call. */
+int lt_projector_set_beam_azimuth(lt_projector* projector, const double* az_rad, int H);
 int lt_range_projection_batch_dev(lt_projector* projector, int n_clouds, const lt_cloud* clouds, int is_f64,
                                   double fov_up, double fov_down, int H, int W, const double* beam_angles, int n_beams,
                                   unsigned flags, const float* color_lut, int lut_len, const lt_proj_images* out,
@@ -609,6 +640,16 @@ int lt_reverse_projection_beams_dev(const float* range_img, const void* proj_x, 
 int lt_reverse_projection_sector_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
                                      int preserve_float, int beam_rows, const double* Brad, double fov_up, double fov_down,
                                      int H, int W, double yaw_center, double span, double* back_points, void* stream);
+
+/* The same for a sensor with a beam table whose beams carry AZIMUTH OFFSETS (what LT_PROJ_BEAM_AZIMUTH projected): the yaw
+ * of lt_reverse_projection_beams_dev or -- `sector` (HOST [2]: yaw_center, span in radians; NULL = the full circle) -- of
+ * lt_reverse_projection_sector_dev is the NOMINAL one, and yaw = nominal - az_rad[row] (az_rad: DEVICE [H] float64, radians)
+ * in float64.  The row is proj_y clamped to [0, H - 1] like the Brad read (int32 coordinates), or the cell's own row i / W
+ * with preserve_float, where the second image holds the pitch.  The elevation is lt_reverse_projection_beams_dev's (Brad:
+ * DEVICE [H]; may be NULL with preserve_float).  Asynchronous on `stream`. */
+int lt_reverse_projection_beams_az_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
+                                       int preserve_float, const double* Brad, const double* az_rad, const double* sector,
+                                       int H, int W, double* back_points, void* stream);
 
 /* Points into another frame: out[i] = float32(((m0*x + m1*y) + m2*z) + m3) per row of T, in float64 from the float32
  * point.  points / out [n,3] f32 DEVICE (out may be points), tri [n] i32 DEVICE or NULL: rows with tri < 0 (rays

@@ -9,7 +9,9 @@ target YAML with ``beam_model: table`` (config/vlp32c_table_1024.yaml) switches 
 image rows at the angles of its ``beam_angles``; no metrics are printed and every row of ``--log`` carries
 ``"beam_model": "table"``.  A target YAML with ``azimuth_model: sector`` (config/front120_64x1024.yaml) gives the target a
 horizontal field of view of ``fov_hor`` degrees around ``azimuth_center``: rays and image columns cover that sector alone; no
-metrics are printed and every row of ``--log`` carries ``"azimuth_model": "sector"``.  The tool
+metrics are printed and every row of ``--log`` carries ``"azimuth_model": "sector"``.  A table target with
+``beam_azimuth_offsets`` (config/vlp32c_table_az_1024.yaml) shears rays and columns row by row by its beams' azimuth offsets;
+every row of ``--log`` then carries ``"beam_azimuth": true`` as well.  The tool
 is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
 ``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  A missing dataset, labels or output
 folder ends with a message and exit status 1."""
@@ -68,9 +70,10 @@ def main(argv=None):
     try:
         approach, source, target = load_approach(args.config), load_sensor(source_path), load_sensor(target_path)
         approach.mount()   # (a transformation that is not a rigid motion: said here, not half way into the run)
-        from .config import refuse_source_sector, refuse_source_table
+        from .config import refuse_source_beam_azimuth, refuse_source_sector, refuse_source_table
         refuse_source_table(source)
         refuse_source_sector(source)
+        refuse_source_beam_azimuth(source)
     except Exception as e:  # noqa: BLE001  (a YAML that cannot be read: message and status, as the reference's quit())
         print(e)
         print("Error opening yaml file.")
@@ -95,6 +98,8 @@ def main(argv=None):
                         row["beam_model"] = tr.beam_model
                     if tr.azimuth_model != "full":
                         row["azimuth_model"] = tr.azimuth_model
+                    if tr.beam_azimuth is not None:
+                        row["beam_azimuth"] = True
                     log.write(json.dumps(row) + "\n")
             if log is not None:
                 log.write(json.dumps(dict(summary=tr.summary)) + "\n")

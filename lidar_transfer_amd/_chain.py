@@ -72,6 +72,17 @@ def sector_pair(sector):
     return np.array(sector_radians(check_sector(sector)), dtype=np.float64)
 
 
+def beam_azimuth_rad(beam_azimuth):
+    """A target sensor's per-beam AZIMUTH OFFSETS (``SensorModel.beam_azimuth()``, degrees, the table's row order) as
+    ``LT_PROJ_BEAM_AZIMUTH`` and ``lt_reverse_projection_beams_az_dev`` read them: float64 [H] radians
+    (``config.beam_azimuth_radians``)."""
+    import numpy as np
+
+    from .config import beam_azimuth_radians, check_beam_azimuth
+    a = np.asarray(beam_azimuth, dtype=np.float64)
+    return beam_azimuth_radians(check_beam_azimuth(a, a.size))
+
+
 def origin3(origin):
     return (C.c_float * 3)(*[float(x) for x in origin])
 

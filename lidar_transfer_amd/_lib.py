@@ -21,6 +21,7 @@ LT_PROJ_REMOVE = 1
 LT_PROJ_NEW = 2
 LT_PROJ_BEAM_ROWS = 4
 LT_PROJ_SECTOR = 8
+LT_PROJ_BEAM_AZIMUTH = 16
 LT_TSDF_MERGE = 1
 LT_TSDF_HOST_MODE = 2
 LT_INGEST_MERGED = 1
@@ -45,7 +46,9 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_evaluator_create", "lt_evaluator_destroy", "lt_source_scan_dev", "lt_compare_record_dev",
            "lt_create_rays_pose_dev", "lt_points_to_frame_dev", "lt_create_rays_beams_dev",
            "lt_reverse_projection_beams_dev", "lt_create_rays_sector_dev", "lt_reverse_projection_sector_dev",
-           "lt_rayset_create_grid_dev", "lt_projector_set_sector", "lt_range_projection_set_sector"]
+           "lt_rayset_create_grid_dev", "lt_projector_set_sector", "lt_range_projection_set_sector",
+           "lt_create_rays_beams_az_dev", "lt_projector_set_beam_azimuth", "lt_range_projection_set_beam_azimuth",
+           "lt_reverse_projection_beams_az_dev"]
 LT_ABI_VERSION = 8   # include/lidarhip.h: layout version of the structs mirrored below
 
 
@@ -269,6 +272,15 @@ def load():
     lib.lt_projector_set_sector.restype = C.c_int
     lib.lt_range_projection_set_sector.argtypes = [C.c_double, C.c_double]
     lib.lt_range_projection_set_sector.restype = C.c_int
+    dp = C.POINTER(C.c_double)
+    lib.lt_create_rays_beams_az_dev.argtypes = [dp, dp, C.c_int, C.c_int, dp, dp, vp, vp]
+    lib.lt_create_rays_beams_az_dev.restype = C.c_int
+    lib.lt_projector_set_beam_azimuth.argtypes = [vp, dp, C.c_int]
+    lib.lt_projector_set_beam_azimuth.restype = C.c_int
+    lib.lt_range_projection_set_beam_azimuth.argtypes = [dp, C.c_int]
+    lib.lt_range_projection_set_beam_azimuth.restype = C.c_int
+    lib.lt_reverse_projection_beams_az_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, dp, C.c_int, C.c_int, vp, vp]
+    lib.lt_reverse_projection_beams_az_dev.restype = C.c_int
     lib.lt_abi_version.argtypes = []
     lib.lt_tsdf_volume_stride.argtypes = []
     if lib.lt_abi_version() != LT_ABI_VERSION:  # a stale prebuilt library: its structs are laid out differently

@@ -22,6 +22,12 @@ beam (:meth:`SensorModel.beam_table`).  Without the key ``beam_angles
 keys as well, for a TARGET sensor: ``fov_hor`` is then the width of the sensor's horizontal field of view around the
 direction ``azimuth_center`` and the ``W`` columns span that sector alone (:meth:`SensorModel.sector`).  Without
 the key ``fov_hor`` only sets ``W`` and the columns go round the whole circle, as in the reference.
+
+``beam_azimuth_offsets`` (optional) is this project's own key too, for a TARGET sensor with ``beam_model: table``: one number
+per beam in degrees, in the order in which the file lists ``beam_angles`` -- the lasers of one firing do not share an
+azimuth, beam ``h`` of a column looks ``offset[h]`` to the LEFT of the column's nominal direction (measured like
+``azimuth_center``; :meth:`SensorModel.beam_azimuth`).  The loader pairs offsets and angles before it sorts the
+angles.  Without the key, or with offsets that are all zero, nothing changes.
 """
 from __future__ import annotations
 
@@ -45,6 +51,8 @@ class SensorModel:
     beam_model: str = "linear"
     azimuth_model: str = "full"
     azimuth_center: float = 0.0
+    #: per-beam azimuth offsets in degrees, paired with ``beam_angles`` index by index (the loader sorts the two together)
+    beam_azimuth_offsets: Optional[List[float]] = None
 
     @property
     def H(self) -> int:
@@ -63,7 +71,8 @@ class SensorModel:
         """Host mirror of ``MultiSemLaserScan.create_rays(fov_up, fov_down, H, W)`` for this model:
         ``[H*W, 3]`` float32 (beam_angles are ignored there, as in the reference)."""
         from .laserscan import create_rays
-        return create_rays(self.fov_up, self.fov_down, self.H, self.W, beam_table=self.beam_table(), sector=self.sector())
+        return create_rays(self.fov_up, self.fov_down, self.H, self.W, beam_table=self.beam_table(), sector=self.sector(),
+                           beam_azimuth=self.beam_azimuth())
 
     def sector(self):
         """``None`` for ``azimuth_model: full``; for ``sector`` ``(center_deg, span_deg)`` as floats: the ``W`` columns span
@@ -92,6 +101,45 @@ class SensorModel:
         except (TypeError, ValueError):
             raise ValueError(f"sensor {self.name!r}: beam_model table needs beam_angles, a list of numbers") from None
         return check_beam_table(b, self.H, self.fov_up, self.fov_down, f"sensor {self.name!r}")
+
+    def beam_azimuth(self):
+        """``None`` without ``beam_azimuth_offsets`` or when all of them are zero; else the beams' azimuth offsets in degrees,
+        float64 [H], in the row order of :meth:`beam_table` (descending elevation) -- ``beam_azimuth_offsets[k]`` belongs to
+        ``beam_angles[k]`` and travels with it.  Beam ``h`` of a column looks ``offset[h]`` to the left of the column's nominal
+        direction.  ``ValueError`` unless the sensor has ``beam_model: table`` and there is one finite number per beam with
+        ``|offset| <= 90``."""
+        if self.beam_azimuth_offsets is None:
+            return None
+        who = f"sensor {self.name!r}"
+        table = self.beam_table()
+        if table is None:
+            raise ValueError(f"{who}: beam_azimuth_offsets needs beam_model: table (the offsets belong to the table's beams)")
+        try:
+            a = np.array([float(v) for v in self.beam_azimuth_offsets], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: beam_azimuth_offsets must be a list of numbers") from None
+        angles = np.array([float(v) for v in self.beam_angles], dtype=np.float64)
+        a = check_beam_azimuth(a, len(angles), who)
+        a = a[np.argsort(-angles, kind="stable")]   # (the table's angles are distinct: one order)
+        return a if np.any(a != 0.0) else None
+
+
+def check_beam_azimuth(a, H, who="beam azimuth offsets"):
+    """the conditions of :meth:`SensorModel.beam_azimuth` on a float64 array of offsets in degrees; returns it"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 1 or len(a) != int(H):
+        raise ValueError(f"{who}: {a.size} beam_azimuth_offsets for {int(H)} beams")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{who}: beam_azimuth_offsets must be finite")
+    if not np.all(np.abs(a) <= 90.0):
+        raise ValueError(f"{who}: beam_azimuth_offsets must lie within +-90 degrees")
+    return a
+
+
+def beam_azimuth_radians(az):
+    """What the column rule of the offsets reads (``LT_PROJ_BEAM_AZIMUTH``, ``lt_reverse_projection_beams_az_dev``), float64
+    [H]: ``az / 180 * pi``."""
+    return np.ascontiguousarray(np.asarray(az, dtype=np.float64) / 180. * np.pi)
 
 
 def check_beam_table(b, H, fov_up, fov_down, who="beam table"):
@@ -171,11 +219,22 @@ def load_sensor(path_or_dict) -> SensorModel:
         beam_angles.sort()
     except Exception:
         beam_angles = None
+    offsets = cfg.get("beam_azimuth_offsets")
+    if offsets is not None:
+        try:   # pair with the angles in the FILE's order, then carry along into the sorted one
+            offsets, listed = list(offsets), list(cfg["beam_angles"])
+            if len(offsets) == len(listed):
+                offsets = [offsets[k] for k in sorted(range(len(listed)), key=lambda k: listed[k])]
+        except Exception:
+            raise ValueError(f"sensor {name!r}: beam_azimuth_offsets needs beam_model: table and its beam_angles, "
+                             "one number per beam") from None
     model = SensorModel(name, fov_up, fov_down, beams, angle_res_hor, fov_hor, beam_angles, raw=cfg,
                         beam_model=str(cfg.get("beam_model", "linear")),
-                        azimuth_model=str(cfg.get("azimuth_model", "full")), azimuth_center=cfg.get("azimuth_center", 0.0))
+                        azimuth_model=str(cfg.get("azimuth_model", "full")), azimuth_center=cfg.get("azimuth_center", 0.0),
+                        beam_azimuth_offsets=offsets)
     model.beam_table()   # (a table that cannot be used: said at load time)
     model.sector()       # (the same for a sector)
+    model.beam_azimuth() # (and for the beams' azimuth offsets)
     return model
 
 
@@ -191,6 +250,14 @@ def refuse_source_sector(source):
     if getattr(source, "azimuth_model", "full") != "full":
         raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: azimuth_model {source.azimuth_model!r} is for target "
                          "sensors only (the source scan is fused by the reference's full-circle pixel model)")
+
+
+def refuse_source_beam_azimuth(source):
+    """Azimuth offsets are a property of the TARGET's table as well: the source scan is fused by the reference's pixel model,
+    whose rows share one azimuth per column."""
+    if getattr(source, "beam_azimuth_offsets", None) is not None:
+        raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: beam_azimuth_offsets is for target sensors only (the "
+                         "source scan is fused by the reference's pixel model: one azimuth per column)")
 
 
 @dataclass

@@ -32,6 +32,16 @@ int lt_cu_count(int device);
     if (rows) { if (sector) LAUNCH(1, 1); else LAUNCH(1, 0); }     \
     else { if (sector) LAUNCH(0, 1); else LAUNCH(0, 0); }          \
   } while (0)
+// The same with per-beam azimuth offsets (`az`; they come with a beam table only): LAUNCH_AZ(SECTOR) holds the launch of the
+// kernel's <BEAMS = 1, SECTOR, AZ = 1> instantiation; without offsets the models above, from the launch they had.
+#define LT_FOR_MODEL_AZ(rows, sector, az, LAUNCH, LAUNCH_AZ)       \
+  do {                                                             \
+    if (az) { if (sector) LAUNCH_AZ(1); else LAUNCH_AZ(0); }       \
+    else LT_FOR_MODEL(rows, sector, LAUNCH);                       \
+  } while (0)
+// doubles of the sensor model a projection uploads, at most: a table of 511 rows (Brad, halfw, the field of view), its
+// azimuth offsets and a sector
+#define LT_MODEL_DOUBLES 1540
 
 // ---- device data layout -----------------------------------------------------------------------
 // Sorted triangle record, 48 B = 3 x float4 (one 16-B-aligned dwordx4 load each):

@@ -118,6 +118,61 @@ extern "C" int lt_reverse_projection_sector_dev(const float* range_img, const vo
                         back_points, (hipStream_t)stream);
 }
 
+// The same for a beam table whose beams carry AZIMUTH OFFSETS (what LT_PROJ_BEAM_AZIMUTH projected), a kernel of its own so
+// that k_reverse keeps its operands: the column's yaw as above (SECTOR or the full circle) is the NOMINAL one, and the beam of
+// the cell's row looks az[row] to its left -- yaw = nominal - az[row].  The row is proj_y clamped like the Brad read, or --
+// float64 coordinates, where py holds the pitch -- the cell's own row i / W.  The pitch is the table's rule.
+template <typename P, int SECTOR>
+__global__ __launch_bounds__(256) void k_reverse_az(const float* __restrict__ range, const P* __restrict__ px,
+                                                    const P* __restrict__ py, int H, int W, const double* __restrict__ Brad,
+                                                    const double* __restrict__ az, double yc, double span,
+                                                    double* __restrict__ out) {
+  constexpr bool is_float = std::is_same<P, double>::value;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= H * W) return;
+  const double depth = (double)range[i];
+  double yaw;
+  if (SECTOR) {
+    const double x = is_float ? (double)px[i] / (double)W : ((double)px[i] + 0.5) / (double)W;
+    yaw = yc + (x - 0.5) * span;
+  } else {
+    const double x = (double)px[i] / (double)W;
+    yaw = (x * 2 - 1.0) * M_PI;
+  }
+  int r = is_float ? i / W : (int)py[i];
+  r = r < 0 ? 0 : (r > H - 1 ? H - 1 : r);
+  yaw = yaw - az[r];
+  const double e = is_float ? (double)py[i] : Brad[r];
+  const double pitch = M_PI / 2 - e;
+  const double sp = sin(pitch);
+  out[3 * (size_t)i] = depth * sp * cos(-yaw);
+  out[3 * (size_t)i + 1] = depth * sp * sin(-yaw);
+  out[3 * (size_t)i + 2] = depth * cos(pitch);
+}
+
+extern "C" int lt_reverse_projection_beams_az_dev(const float* range_img, const void* proj_x, const void* proj_y_or_pitch,
+                                                  int preserve_float, const double* Brad, const double* az_rad,
+                                                  const double* sector, int H, int W, double* back_points, void* stream) {
+  bool ok = H > 0 && W > 0 && range_img && proj_x && proj_y_or_pitch && back_points && (preserve_float || Brad) && az_rad;
+  if (ok && sector) ok = fabs(sector[0]) <= M_PI && sector[1] > 0.0 && sector[1] < 2 * M_PI;
+  if (!ok) {
+    lt_set_error("lt_reverse_projection_beams_az_dev: invalid argument (H=%d W=%d; the table, the offsets, a sector with "
+                 "|yaw_center| <= pi and 0 < span < 2 pi)", H, W);
+    return LT_ERR_INVALID_ARG;
+  }
+  const double yc = sector ? sector[0] : 0.0, span = sector ? sector[1] : 0.0;
+  const dim3 grid((H * W + 255) / 256), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define LT_REVERSE_AZ(P, S)                                                                                         \
+  hipLaunchKernelGGL((k_reverse_az<P, S>), grid, block, 0, st, range_img, (const P*)proj_x, (const P*)proj_y_or_pitch, \
+                     H, W, Brad, az_rad, yc, span, back_points)
+  if (preserve_float) { if (sector) LT_REVERSE_AZ(double, 1); else LT_REVERSE_AZ(double, 0); }
+  else { if (sector) LT_REVERSE_AZ(int, 1); else LT_REVERSE_AZ(int, 0); }
+#undef LT_REVERSE_AZ
+  LT_HIP(hipGetLastError());
+  return LT_OK;
+}
+
 // ---- rendered points into another frame (the target sensor's, when it is mounted at a pose of its own) ----------
 // float32 point widened to float64, ((m0 * x + m1 * y) + m2 * z) + m3 per row of T (lt_ingest_scans_dev's row form; every
 // product and sum rounded on its own), rounded to float32.  Rows with tri < 0 (misses) are copied as they are: (0, 0, 0)

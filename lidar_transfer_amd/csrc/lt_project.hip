@@ -25,8 +25,8 @@
 
 #define LT_EMPTY_IDX 0x7F7F7F7F  // hipMemset(0x7F) pattern: larger than any point index
 
-// pass 1: project, z-min of the depth bits, per-workgroup count of kept points (BEAMS, SECTOR and `beams`: project_model)
-template <typename T, int BEAMS, int SECTOR>
+// pass 1: project, z-min of the depth bits, per-workgroup count of kept points (BEAMS, SECTOR, AZ and `beams`: project_model)
+template <typename T, int BEAMS, int SECTOR, int AZ = 0>
 __global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int n, T pi_t, T abs_fov_down, T fov,
                                                  int H, int W, const double* __restrict__ beams, int n_beams,
                                                  int drop_zero, int drop_outside, int round_key,
@@ -39,8 +39,8 @@ __global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int 
   bool keep = false;
   if (i < n) {
     const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-    const proj_out<T> o = project_model<T, BEAMS, SECTOR>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
-                                                          drop_outside);
+    const proj_out<T> o = project_model<T, BEAMS, SECTOR, AZ>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams,
+                                                              drop_zero, drop_outside);
     cell[i] = o.cell;
     depth_d[i] = (double)o.depth;
     xf[i] = o.xf;
@@ -165,12 +165,14 @@ __global__ __launch_bounds__(256) void k_resolve(const T* __restrict__ pts, cons
 //           counted clockwise from the sector's left edge, and its ray leaves through the cell's CENTRE -- not wrapped (sin
 //           and cos are periodic)
 //   row     np.linspace(fov_up, fov_down, H), or -- BEAMS: `beams_deg` (device, [H]) -- the table's angle (degrees) of row h
+//           AZ (with BEAMS): beam h looks beams_deg[H + h] degrees to the LEFT of its column's nominal direction (the
+//           per-beam azimuth offsets, behind the table in the same buffer): yaw_deg = nominal(w) - offset, no further wrap
 //   pose    POSED: the direction, still in float64, turned by the row-major rotation R of the sensor's pose --
 //           ((r0 * x + r1 * y) + r2 * z) per component, every product and sum rounded on its own (-ffp-contract=off).
 //           Unposed rays are cast as they are, not turned by the identity: -0.0 + 0.0 is +0.0
 struct lt_rot9 { double m[9]; };
 
-template <int BEAMS, int SECTOR, int POSED>
+template <int BEAMS, int SECTOR, int POSED, int AZ = 0>
 __global__ __launch_bounds__(256) void k_create_rays(const double* __restrict__ beams_deg, double fov_up, double fov_down,
                                                      int H, int W, double center_deg, double span_deg, lt_rot9 R,
                                                      float* __restrict__ rays) {
@@ -186,6 +188,7 @@ __global__ __launch_bounds__(256) void k_create_rays(const double* __restrict__ 
     yaw_deg += 180.0;
     if (yaw_deg > 360.0) yaw_deg -= 360.0;
   }
+  if (BEAMS && AZ) yaw_deg = yaw_deg - beams_deg[H + h];
   const double yaw = yaw_deg / 180. * M_PI;
   const double pd = BEAMS ? beams_deg[h]
                         : (H > 1 ? (h == H - 1 ? fov_down : fov_up + h * ((fov_down - fov_up) / (H - 1))) : fov_up);
@@ -203,11 +206,11 @@ __global__ __launch_bounds__(256) void k_create_rays(const double* __restrict__ 
   }
 }
 
-// `beams_deg` (host, [H]) or NULL, `sec` = (center, span) in degrees or NULL, `rot` (host, [9]) or NULL.  Without a table the
-// launch is asynchronous.  With one (once per sensor model) the table goes to the device in a buffer of this call, which
-// waits for its kernel.
-static int create_rays_launch(const double* beams_deg, double fov_up, double fov_down, int H, int W, const double* sec,
-                              const double* rot, float* rays, hipStream_t st) {
+// `beams_deg` (host, [H]) or NULL, `az_deg` (host, [H]; with a table only) or NULL, `sec` = (center, span) in degrees or
+// NULL, `rot` (host, [9]) or NULL.  Without a table the launch is asynchronous.  With one (once per sensor model) the table
+// -- and the offsets behind it -- go to the device in a buffer of this call, which waits for its kernel.
+static int create_rays_launch(const double* beams_deg, const double* az_deg, double fov_up, double fov_down, int H, int W,
+                              const double* sec, const double* rot, float* rays, hipStream_t st) {
   lt_rot9 R;
   for (int k = 0; k < 9; ++k) R.m[k] = rot ? rot[k] : 0.0;  // (read by the POSED kernels only)
   const dim3 grid((H * W + 255) / 256), block(256);
@@ -215,8 +218,10 @@ static int create_rays_launch(const double* beams_deg, double fov_up, double fov
   double* d_beams = nullptr;
   hipError_t e = hipSuccess;
   if (beams_deg) {
-    LT_HIP(hipMalloc((void**)&d_beams, (size_t)H * sizeof(double)));
+    LT_HIP(hipMalloc((void**)&d_beams, (size_t)H * (az_deg ? 2 : 1) * sizeof(double)));
     e = hipMemcpyAsync(d_beams, beams_deg, (size_t)H * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && az_deg)
+      e = hipMemcpyAsync(d_beams + H, az_deg, (size_t)H * sizeof(double), hipMemcpyHostToDevice, st);
   }
   if (e == hipSuccess) {
 #define LT_RAYS(B, S, P)                                                                                              \
@@ -224,11 +229,20 @@ static int create_rays_launch(const double* beams_deg, double fov_up, double fov
                      span_deg, R, rays)
 #define LT_RAYS_POSED(B, S) LT_RAYS(B, S, 1)
 #define LT_RAYS_UNPOSED(B, S) LT_RAYS(B, S, 0)
-    if (rot) LT_FOR_MODEL(beams_deg != nullptr, sec != nullptr, LT_RAYS_POSED);
-    else LT_FOR_MODEL(beams_deg != nullptr, sec != nullptr, LT_RAYS_UNPOSED);
+#define LT_RAYS_AZ(S, P)                                                                                       \
+  hipLaunchKernelGGL((k_create_rays<1, S, P, 1>), grid, block, 0, st, (const double*)d_beams, fov_up, fov_down, H, W, \
+                     center_deg, span_deg, R, rays)
+#define LT_RAYS_AZ_POSED(S) LT_RAYS_AZ(S, 1)
+#define LT_RAYS_AZ_UNPOSED(S) LT_RAYS_AZ(S, 0)
+    const bool az = beams_deg && az_deg;
+    if (rot) LT_FOR_MODEL_AZ(beams_deg != nullptr, sec != nullptr, az, LT_RAYS_POSED, LT_RAYS_AZ_POSED);
+    else LT_FOR_MODEL_AZ(beams_deg != nullptr, sec != nullptr, az, LT_RAYS_UNPOSED, LT_RAYS_AZ_UNPOSED);
 #undef LT_RAYS
 #undef LT_RAYS_POSED
 #undef LT_RAYS_UNPOSED
+#undef LT_RAYS_AZ
+#undef LT_RAYS_AZ_POSED
+#undef LT_RAYS_AZ_UNPOSED
     e = hipGetLastError();
   }
   if (beams_deg) {
@@ -244,7 +258,7 @@ extern "C" int lt_create_rays_dev(double fov_up, double fov_down, int H, int W, 
     lt_set_error("lt_create_rays_dev: invalid argument (H=%d W=%d)", H, W);
     return LT_ERR_INVALID_ARG;
   }
-  return create_rays_launch(nullptr, fov_up, fov_down, H, W, nullptr, nullptr, rays, (hipStream_t)stream);
+  return create_rays_launch(nullptr, nullptr, fov_up, fov_down, H, W, nullptr, nullptr, rays, (hipStream_t)stream);
 }
 
 extern "C" int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, int W, const double* rot, float* rays,
@@ -254,7 +268,7 @@ extern "C" int lt_create_rays_pose_dev(double fov_up, double fov_down, int H, in
     lt_set_error("lt_create_rays_pose_dev: invalid argument (H=%d W=%d)", H, W);
     return LT_ERR_INVALID_ARG;
   }
-  return create_rays_launch(nullptr, fov_up, fov_down, H, W, nullptr, rot, rays, (hipStream_t)stream);
+  return create_rays_launch(nullptr, nullptr, fov_up, fov_down, H, W, nullptr, rot, rays, (hipStream_t)stream);
 }
 
 extern "C" int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, const double* rot, float* rays,
@@ -263,7 +277,7 @@ extern "C" int lt_create_rays_beams_dev(const double* beams_deg, int H, int W, c
     lt_set_error("lt_create_rays_beams_dev: invalid argument (H=%d W=%d)", H, W);
     return LT_ERR_INVALID_ARG;
   }
-  return create_rays_launch(beams_deg, 0.0, 0.0, H, W, nullptr, rot, rays, (hipStream_t)stream);
+  return create_rays_launch(beams_deg, nullptr, 0.0, 0.0, H, W, nullptr, rot, rays, (hipStream_t)stream);
 }
 
 extern "C" int lt_create_rays_sector_dev(const double* beams_deg, double fov_up, double fov_down, int H, int W,
@@ -273,20 +287,46 @@ extern "C" int lt_create_rays_sector_dev(const double* beams_deg, double fov_up,
     return LT_ERR_INVALID_ARG;
   }
   const double sec[2] = {center_deg, span_deg};
-  return create_rays_launch(beams_deg, fov_up, fov_down, H, W, sec, rot, rays, (hipStream_t)stream);
+  return create_rays_launch(beams_deg, nullptr, fov_up, fov_down, H, W, sec, rot, rays, (hipStream_t)stream);
 }
 
-// The doubles a projection uploads for its sensor model, into `tab` [1024]; returns their number (0: none), -1 when the
-// arguments do not fit the flags.  Layout (project_model reads it):
-//   neither flag        the caller's n_beams hard-coded angles (n_beams may be 0)
-//   LT_PROJ_BEAM_ROWS   the caller's table (Brad[H], halfw[H]) checked and completed by the field of view in radians, which
-//                       the H == 1 keep rule reads: 2 * H + 2 doubles
-//   LT_PROJ_SECTOR      behind either, the two numbers of the sector -- the yaw of its middle (|.| <= pi) and its width (in
-//                       (0, 2 pi)), radians -- from lt_projector_set_sector / lt_range_projection_set_sector (`sec`, NULL:
-//                       none was set)
+extern "C" int lt_create_rays_beams_az_dev(const double* beams_deg, const double* az_deg, int H, int W, const double* sec,
+                                           const double* rot, float* rays, void* stream) {
+  bool ok = beams_deg && H > 0 && W > 0 && rays;
+  if (ok && sec) ok = fabs(sec[0]) <= 360.0 && sec[1] > 0.0 && sec[1] < 360.0;
+  if (ok && az_deg)
+    for (int h = 0; h < H; ++h) ok = ok && fabs(az_deg[h]) <= 90.0;  // (NaN: not)
+  if (!ok) {
+    lt_set_error("lt_create_rays_beams_az_dev: invalid argument (H=%d W=%d; a table, offsets within +-90 degrees, a sector "
+                 "with |center| <= 360 and 0 < span < 360)", H, W);
+    return LT_ERR_INVALID_ARG;
+  }
+  return create_rays_launch(beams_deg, az_deg, 0.0, 0.0, H, W, sec, rot, rays, (hipStream_t)stream);
+}
+
+// The doubles a projection uploads for its sensor model, into `tab` [LT_MODEL_DOUBLES]; returns their number (0: none), -1
+// when the arguments do not fit the flags.  Layout (project_model reads it):
+//   neither flag          the caller's n_beams hard-coded angles (n_beams may be 0)
+//   LT_PROJ_BEAM_ROWS     the caller's table (Brad[H], halfw[H]) checked and completed by the field of view in radians,
+//                         which the H == 1 keep rule reads: 2 * H + 2 doubles
+//   LT_PROJ_BEAM_AZIMUTH  behind the completed table, the H azimuth offsets of its rows in radians -- from
+//                         lt_projector_set_beam_azimuth / lt_range_projection_set_beam_azimuth (`az`, `n_az` of them; NULL:
+//                         none were set)
+//   LT_PROJ_SECTOR        behind either (and the offsets), the two numbers of the sector -- the yaw of its middle (|.| <= pi)
+//                         and its width (in (0, 2 pi)), radians -- from lt_projector_set_sector /
+//                         lt_range_projection_set_sector (`sec`, NULL: none was set)
 static int model_table(const char* who, const double* beam_angles, int n_beams, unsigned flags, double fov_up_deg,
-                       double fov_down_deg, int H, const double* sec, double* tab) {
+                       double fov_down_deg, int H, const double* sec, const double* az, int n_az, double* tab) {
   const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0, sector = (flags & LT_PROJ_SECTOR) != 0;
+  const bool azimuth = (flags & LT_PROJ_BEAM_AZIMUTH) != 0;
+  const unsigned with_az = LT_PROJ_BEAM_AZIMUTH | LT_PROJ_BEAM_ROWS | LT_PROJ_NEW | LT_PROJ_REMOVE;
+  if (azimuth && ((flags & ~LT_PROJ_SECTOR) != with_az || !az || n_az != H)) {
+    lt_set_error("%s: LT_PROJ_BEAM_AZIMUTH goes with LT_PROJ_BEAM_ROWS | LT_PROJ_NEW | LT_PROJ_REMOVE only, with or without "
+                 "LT_PROJ_SECTOR (flags=%u), and after the offsets of exactly H rows were set (%d were; H=%d)", who, flags,
+                 az ? n_az : 0, H);
+    return -1;
+  }
+  flags &= ~LT_PROJ_BEAM_AZIMUTH;  // (checked; the two rules below are what they were)
   if (rows && ((flags & ~LT_PROJ_SECTOR) != (LT_PROJ_BEAM_ROWS | LT_PROJ_NEW | LT_PROJ_REMOVE) || n_beams != H || !beam_angles ||
                2 * H + 2 > 1024)) {
     lt_set_error("%s: LT_PROJ_BEAM_ROWS goes with LT_PROJ_NEW | LT_PROJ_REMOVE only (flags=%u) and a table of n_beams == H "
@@ -294,7 +334,7 @@ static int model_table(const char* who, const double* beam_angles, int n_beams, 
     return -1;
   }
   const int n_given = rows ? 2 * H : n_beams;      // doubles of the caller's
-  const int n_rows = rows ? 2 * H + 2 : n_beams;   // ... and of the row model that the kernels read
+  int n_rows = rows ? 2 * H + 2 : n_beams;         // ... and of the row model that the kernels read
   if (sector && ((flags & ~LT_PROJ_BEAM_ROWS) != (LT_PROJ_SECTOR | LT_PROJ_NEW | LT_PROJ_REMOVE) || !sec || n_beams < 0 ||
                  (n_beams > 0 && !beam_angles) || n_rows + 2 > 1024)) {
     lt_set_error("%s: LT_PROJ_SECTOR goes with LT_PROJ_NEW | LT_PROJ_REMOVE only, with or without LT_PROJ_BEAM_ROWS (flags=%u), "
@@ -305,6 +345,10 @@ static int model_table(const char* who, const double* beam_angles, int n_beams, 
   if (rows) {
     tab[2 * H] = fov_down_deg / 180.0 * M_PI;
     tab[2 * H + 1] = fov_up_deg / 180.0 * M_PI;
+  }
+  if (azimuth) {  // (H <= 511: 3 H + 2 + 2 <= LT_MODEL_DOUBLES)
+    memcpy(tab + n_rows, az, (size_t)H * sizeof(double));
+    n_rows += H;
   }
   if (sector) {
     tab[n_rows] = sec[0];
@@ -319,6 +363,15 @@ static bool sector_ok(const char* who, double yaw_center, double span) {
     return false;
   }
   return true;
+}
+
+// the offsets of LT_PROJ_BEAM_AZIMUTH: `az` [n] radians, finite and within +-pi/2, for 1 .. 511 rows; NULL or n == 0 clears
+static bool beam_azimuth_ok(const char* who, const double* az, int n) {
+  bool ok = (!az || n == 0) || (n > 0 && n <= 511);
+  if (ok && az)
+    for (int h = 0; h < n; ++h) ok = ok && fabs(az[h]) <= M_PI / 2;  // (NaN: not)
+  if (!ok) lt_set_error("%s: the azimuth offsets of 1 .. 511 rows, radians, each finite and within +-pi/2 (n=%d)", who, n);
+  return ok;
 }
 
 // ---- host orchestration -------------------------------------------------------------------------------------
@@ -342,6 +395,8 @@ std::mutex g_pmu;
 proj_ws g_pws;
 double g_sector[2] = {0.0, 0.0};  // lt_range_projection_set_sector
 bool g_sector_set = false;
+double g_az[511];                 // lt_range_projection_set_beam_azimuth
+int g_az_n = 0;
 
 void pws_free(proj_ws& w) {
   void* ps[] = {w.cell, w.depth_d, w.xf, w.yf, w.blockcount, w.orig_of, w.cellmin, w.idxmin, w.idxlast, w.beams};
@@ -366,7 +421,7 @@ int pws_reserve(proj_ws& w, int device, size_t n, size_t cells) {
   LT_HIP(hipMalloc((void**)&w.cellmin, cc * sizeof(unsigned long long)));
   LT_HIP(hipMalloc((void**)&w.idxmin, cc * sizeof(int)));
   LT_HIP(hipMalloc((void**)&w.idxlast, cc * sizeof(int)));
-  LT_HIP(hipMalloc((void**)&w.beams, 1024 * sizeof(double)));
+  LT_HIP(hipMalloc((void**)&w.beams, LT_MODEL_DOUBLES * sizeof(double)));
   w.device = device;
   w.cap_n = cn;
   w.cap_cells = cc;
@@ -393,6 +448,7 @@ int run_projection(proj_ws& w, const T* pts, const float* rem, const unsigned* l
   const int round_key = (flags & LT_PROJ_NEW) ? 1 : 0;
   if (n > 0) {
     const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0, sector = (flags & LT_PROJ_SECTOR) != 0;
+    const bool azimuth = (flags & LT_PROJ_BEAM_AZIMUTH) != 0;
     // rows and sector go with LT_PROJ_NEW | LT_PROJ_REMOVE only: both drops
     const int drop_zero = (rows || sector || (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW))) ? 1 : 0;
     const int drop_outside = (rows || sector || (flags & LT_PROJ_REMOVE)) ? 1 : 0;
@@ -400,8 +456,13 @@ int run_projection(proj_ws& w, const T* pts, const float* rem, const unsigned* l
   hipLaunchKernelGGL((k_project<T, B, S>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,          \
                      (const double*)w.beams, n_beams, drop_zero, drop_outside, round_key, w.cell, w.depth_d, (T*)w.xf,      \
                      (T*)w.yf, w.cellmin, w.blockcount)
-    LT_FOR_MODEL(rows, sector, LT_PROJECT);
+#define LT_PROJECT_AZ(S)                                                                                                   \
+  hipLaunchKernelGGL((k_project<T, 1, S, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,       \
+                     (const double*)w.beams, n_beams, drop_zero, drop_outside, round_key, w.cell, w.depth_d, (T*)w.xf,      \
+                     (T*)w.yf, w.cellmin, w.blockcount)
+    LT_FOR_MODEL_AZ(rows, sector, azimuth, LT_PROJECT, LT_PROJECT_AZ);
 #undef LT_PROJECT
+#undef LT_PROJECT_AZ
     hipLaunchKernelGGL(k_assign<T>, dim3(nb), dim3(256), 0, st, pts, rem, label, n, W, (const int*)w.cell,
                        (const double*)w.depth_d, (const T*)w.xf, (const T*)w.yf,
                        (const unsigned long long*)w.cellmin, w.blockcount, round_key, w.idxmin,
@@ -432,6 +493,14 @@ extern "C" int lt_range_projection_set_sector(double yaw_center, double span) {
   return LT_OK;
 }
 
+extern "C" int lt_range_projection_set_beam_azimuth(const double* az_rad, int H) {
+  if (!beam_azimuth_ok("lt_range_projection_set_beam_azimuth", az_rad, H)) return LT_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(g_pmu);
+  g_az_n = az_rad ? H : 0;
+  if (g_az_n > 0) memcpy(g_az, az_rad, (size_t)H * sizeof(double));
+  return LT_OK;
+}
+
 extern "C" int lt_range_projection_dev(const void* points, int is_f64, const float* rem, const unsigned* label,
                                        int n, double fov_up, double fov_down, int H, int W,
                                        const double* beam_angles, int n_beams, unsigned flags,
@@ -446,10 +515,10 @@ extern "C" int lt_range_projection_dev(const void* points, int is_f64, const flo
     lt_set_error("lt_range_projection: invalid argument (n=%d H=%d W=%d n_beams=%d)", n, H, W, n_beams);
     return LT_ERR_INVALID_ARG;
   }
-  double tab[1024];
+  double tab[LT_MODEL_DOUBLES];
   std::lock_guard<std::mutex> lock(g_pmu);
   const int n_tab = model_table("lt_range_projection", beam_angles, n_beams, flags, fov_up, fov_down, H,
-                                g_sector_set ? g_sector : nullptr, tab);
+                                g_sector_set ? g_sector : nullptr, g_az_n > 0 ? g_az : nullptr, g_az_n, tab);
   if (n_tab < 0) return LT_ERR_INVALID_ARG;
   int dev = 0;
   LT_HIP(hipGetDevice(&dev));
@@ -523,8 +592,8 @@ __device__ __forceinline__ double pb_unord(unsigned long long k) {
 }
 
 // MODE 0: the single-key variants (NEW on any dtype, OLD on float32).  MODE 1: OLD on float64 -- depth minimum only.
-// BEAMS, SECTOR and `beams`: project_model; MODE 0 only.
-template <typename T, int MODE, int BEAMS, int SECTOR>
+// BEAMS, SECTOR, AZ and `beams`: project_model; MODE 0 only.
+template <typename T, int MODE, int BEAMS, int SECTOR, int AZ = 0>
 __global__ __launch_bounds__(256) void k_pb_project(pb_args A, T pi_t, T abs_fov_down, T fov, int H, int W,
                                                     const double* __restrict__ beams, int n_beams, int drop_zero,
                                                     int drop_outside) {
@@ -535,8 +604,8 @@ __global__ __launch_bounds__(256) void k_pb_project(pb_args A, T pi_t, T abs_fov
   if (i < c.n) {
     const T* pts = (const T*)c.pts;
     const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-    const proj_out<T> o = project_model<T, BEAMS, SECTOR>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero,
-                                                          drop_outside);
+    const proj_out<T> o = project_model<T, BEAMS, SECTOR, AZ>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams,
+                                                              drop_zero, drop_outside);
     keep = o.cell >= 0;
     if (keep) {
       if (MODE == 0) atomicMin(&c.key[o.cell], pb_key<T>(o.depth, i));
@@ -661,7 +730,7 @@ __global__ __launch_bounds__(64) void k_pb_bnds(pb_args A) {
   if (c.bacc) pb_fold_bounds(c, threadIdx.x);
 }
 
-template <typename T, int MODE, int BEAMS, int SECTOR>
+template <typename T, int MODE, int BEAMS, int SECTOR, int AZ = 0>
 __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cloud, T pi_t, T abs_fov_down, T fov, int H,
                                                     int W, const double* __restrict__ beams, int n_beams, int drop_zero,
                                                     int drop_outside, const float* __restrict__ lut, int lut_len,
@@ -685,7 +754,7 @@ __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cl
   if (i >= 0) {
     x = pts[3 * (size_t)i]; y = pts[3 * (size_t)i + 1]; z = pts[3 * (size_t)i + 2];
     if (has ? (want_xy || c.range_img) : true)
-      o = project_model<T, BEAMS, SECTOR>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
+      o = project_model<T, BEAMS, SECTOR, AZ>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams, drop_zero, drop_outside);
   }
   int k = -1;
   if (has && have_prefix) k = c.wprefix[i >> 6] + __popcll(c.keep[i >> 6] & ((1ull << (i & 63)) - 1ull));
@@ -724,11 +793,13 @@ struct lt_projector {
   unsigned long long* keep[LT_PB_MAX] = {};
   int* wprefix[LT_PB_MAX] = {};
   int* meta = nullptr;                      // [LT_PB_MAX][2]
-  double* beams = nullptr;                  // [1024]
-  double beams_host[1024];
+  double* beams = nullptr;                  // [LT_MODEL_DOUBLES]
+  double beams_host[LT_MODEL_DOUBLES];
   int n_beams_cached = -1;
   double sector[2] = {0.0, 0.0};            // lt_projector_set_sector
   bool sector_set = false;
+  double az[511];                           // lt_projector_set_beam_azimuth
+  int az_n = 0;
   unsigned long long* bacc = nullptr;       // [LT_PB_MAX][bacc_blocks][6] per-workgroup partial bounds of the clouds (no arming: every
   size_t bacc_blocks = 0;                   // workgroup of k_pb_project writes its six words)
   float* img = nullptr;                     // lt_deform_scan_dev: [n][3][H * W] source images (range, remission, folded label)
@@ -786,6 +857,7 @@ int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool nee
   const int cells = H * W, bpc = (cells + 255) / 256;
   const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0;  // (never with old_f64: the flag goes with LT_PROJ_NEW)
   const bool sector = (flags & LT_PROJ_SECTOR) != 0;   // (the same)
+  const bool azimuth = (flags & LT_PROJ_BEAM_AZIMUTH) != 0;  // (the same; with rows)
   // MODE 1 (old_f64) has neither rows nor a sector; the other instantiations are MODE 0
 #define LT_PB_PROJECT(MODE, B, S)                                                                                          \
   hipLaunchKernelGGL((k_pb_project<T, MODE, B, S>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, \
@@ -796,23 +868,32 @@ int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool nee
                      range_init, rem_init, xyz_init, need_prefix ? 1 : 0)
 #define LT_PB_PROJECT0(B, S) LT_PB_PROJECT(0, B, S)
 #define LT_PB_RESOLVE0(B, S) LT_PB_RESOLVE(0, B, S)
+#define LT_PB_PROJECT_AZ(S)                                                                                                \
+  hipLaunchKernelGGL((k_pb_project<T, 0, 1, S, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, \
+                     H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside)
+#define LT_PB_RESOLVE_AZ(S)                                                                                                \
+  hipLaunchKernelGGL((k_pb_resolve<T, 0, 1, S, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI,             \
+                     (T)fabs(fd), (T)fov, H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len,   \
+                     range_init, rem_init, xyz_init, need_prefix ? 1 : 0)
   if (total_blocks > 0) {
     if (old_f64) {
       LT_PB_PROJECT(1, 0, 0);
       hipLaunchKernelGGL(k_pb_assign, dim3(total_blocks), dim3(256), 0, st, A, M_PI, fabs(fd), fov, H, W,
                          (const double*)p->beams, n_beams, drop_zero, drop_outside);
     } else {
-      LT_FOR_MODEL(rows, sector, LT_PB_PROJECT0);
+      LT_FOR_MODEL_AZ(rows, sector, azimuth, LT_PB_PROJECT0, LT_PB_PROJECT_AZ);
     }
   }
   if (need_prefix) hipLaunchKernelGGL(k_pb_prefix, dim3(A.n_clouds), dim3(256), 0, st, A);
   else if (bnds_only) hipLaunchKernelGGL(k_pb_bnds, dim3(A.n_clouds), dim3(64), 0, st, A);
   if (old_f64) LT_PB_RESOLVE(1, 0, 0);
-  else LT_FOR_MODEL(rows, sector, LT_PB_RESOLVE0);
+  else LT_FOR_MODEL_AZ(rows, sector, azimuth, LT_PB_RESOLVE0, LT_PB_RESOLVE_AZ);
 #undef LT_PB_PROJECT
 #undef LT_PB_RESOLVE
 #undef LT_PB_PROJECT0
 #undef LT_PB_RESOLVE0
+#undef LT_PB_PROJECT_AZ
+#undef LT_PB_RESOLVE_AZ
   LT_HIP(hipGetLastError());
   return LT_OK;
 }
@@ -834,7 +915,7 @@ extern "C" int lt_projector_create(lt_projector** pj, int device) {
   }
   p->device = dev;
   if (hipMalloc((void**)&p->meta, LT_PB_MAX * 2 * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&p->beams, 1024 * sizeof(double)) != hipSuccess) {
+      hipMalloc((void**)&p->beams, LT_MODEL_DOUBLES * sizeof(double)) != hipSuccess) {
     if (p->meta) (void)hipFree(p->meta);
     if (p->beams) (void)hipFree(p->beams);
     delete p;
@@ -855,6 +936,17 @@ extern "C" int lt_projector_set_sector(lt_projector* p, double yaw_center, doubl
   p->sector[0] = yaw_center;
   p->sector[1] = span;
   p->sector_set = span != 0.0;
+  return LT_OK;
+}
+
+extern "C" int lt_projector_set_beam_azimuth(lt_projector* p, const double* az_rad, int H) {
+  if (!p || !beam_azimuth_ok("lt_projector_set_beam_azimuth", az_rad, H)) {
+    if (!p) lt_set_error("lt_projector_set_beam_azimuth: NULL projector");
+    return LT_ERR_INVALID_ARG;
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  p->az_n = az_rad ? H : 0;
+  if (p->az_n > 0) memcpy(p->az, az_rad, (size_t)H * sizeof(double));
   return LT_OK;
 }
 
@@ -891,9 +983,9 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
     n_max = std::max(n_max, (size_t)clouds[k].n);
   }
   std::lock_guard<std::mutex> lock(p->mu);
-  double tab[1024];
+  double tab[LT_MODEL_DOUBLES];
   const int n_dev = model_table("lt_range_projection_batch_dev", beam_angles, n_beams, flags, fov_up, fov_down, H,
-                                p->sector_set ? p->sector : nullptr, tab);
+                                p->sector_set ? p->sector : nullptr, p->az_n > 0 ? p->az : nullptr, p->az_n, tab);
   if (n_dev < 0) return LT_ERR_INVALID_ARG;
   LT_HIP(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;

@@ -152,9 +152,8 @@ __device__ __forceinline__ proj_out<T> project_point_beams(T x, T y, T z, T pi_t
 // is the position across the sector: kept iff 0 <= u < 1 as well, px = u * W, column = floor(px) clamped -- column w is the
 // cell [w, w + 1) * span / W, whose centre is the ray of that column (lt_create_rays_sector_dev).
 template <typename T>
-__device__ __forceinline__ void project_sector_column(proj_out<T>& o, T x, T y, T pi_t, int W, const double* __restrict__ sec) {
+__device__ __forceinline__ void project_sector_yaw(proj_out<T>& o, T yaw, T pi_t, int W, const double* __restrict__ sec) {
   const T yc = (T)sec[0], span_t = (T)sec[1], twopi_t = (T)2 * pi_t;
-  const T yaw = -lt_atan2(y, x);
   T d = yaw - yc;
   if (d < -pi_t) d += twopi_t;
   if (d >= pi_t) d -= twopi_t;
@@ -168,17 +167,54 @@ __device__ __forceinline__ void project_sector_column(proj_out<T>& o, T x, T y, 
   o.px = (int)fx;
   o.cell = (o.cell >= 0 && in) ? o.py * W + o.px : -1;
 }
+template <typename T>
+__device__ __forceinline__ void project_sector_column(proj_out<T>& o, T x, T y, T pi_t, int W, const double* __restrict__ sec) {
+  project_sector_yaw<T>(o, -lt_atan2(y, x), pi_t, W, sec);
+}
+
+// The column of a beam-table sensor whose beams carry AZIMUTH OFFSETS (LT_PROJ_BEAM_AZIMUTH), on top of a point projected by
+// project_point_beams -- its row, depth, pitch and keep conditions stay.  `az` (device, float64 [H]): the offset of every row
+// in radians, positive to the left (measured like atan2(y, x)); beam `row` of a column looks az[row] to the left of the
+// column's nominal direction, so the point's NOMINAL yaw is y' = -atan2(y, x) + a with a = (T)az[row] (|a| <= pi / 2).  Returns
+// y' for a sector (whose own wrap follows, project_sector_yaw); on the full circle one wrap back into [-pi, pi], only when
+// strictly outside -- the reference's closed interval stays what it is -- then the column as without offsets:
+// px = 0.5 (y' / pi + 1) W, floor, clamp.  xf is the nominal coordinate.
+template <typename T, int SECTOR>
+__device__ __forceinline__ T project_azimuth_column(proj_out<T>& o, T x, T y, T pi_t, int W, const double* __restrict__ az) {
+  T yaw = -lt_atan2(y, x) + (T)az[o.py];
+  if (!SECTOR) {
+    const T twopi_t = (T)2 * pi_t;
+    if (yaw > pi_t) yaw -= twopi_t;
+    else if (yaw < -pi_t) yaw += twopi_t;
+    T px = (T)0.5 * (yaw / pi_t + (T)1.0);
+    px *= (T)W;
+    o.xf = px;
+    T fx = lt_floor(px);
+    fx = fx < (T)(W - 1) ? fx : (T)(W - 1);
+    fx = fx > (T)0 ? fx : (T)0;
+    o.px = (int)fx;
+    o.cell = o.cell >= 0 ? o.py * W + o.px : -1;  // (a NaN yaw was dropped with the plain column already)
+  }
+  return yaw;
+}
 
 // One point through the sensor model of a projection kernel -- the one entry point of k_project, k_pb_project and
 // k_pb_resolve.  BEAMS: the rows of a beam table (project_point_beams; `tab` is then the completed table of 2 H + 2 doubles),
-// else the linear rows (project_point; `tab` holds the n_beams hard-coded angles, n_beams may be 0).  SECTOR: the columns of
-// a horizontal sector on top; its two numbers follow the table or the angles in `tab` -- only this function knows where.
-template <typename T, int BEAMS, int SECTOR>
+// else the linear rows (project_point; `tab` holds the n_beams hard-coded angles, n_beams may be 0).  AZ (with BEAMS only):
+// the per-row azimuth offsets, H doubles in radians behind the completed table (project_azimuth_column).  SECTOR: the columns
+// of a horizontal sector on top; its two numbers follow the table (and the offsets) or the angles in `tab` -- only this
+// function knows where.
+template <typename T, int BEAMS, int SECTOR, int AZ = 0>
 __device__ __forceinline__ proj_out<T> project_model(T x, T y, T z, T pi_t, T abs_fov_down, T fov, int H, int W,
                                                      const double* __restrict__ tab, int n_beams, bool drop_zero,
                                                      bool drop_outside) {
   proj_out<T> o = BEAMS ? project_point_beams<T>(x, y, z, pi_t, H, W, tab)
                         : project_point<T>(x, y, z, pi_t, abs_fov_down, fov, H, W, tab, n_beams, drop_zero, drop_outside);
+  if (BEAMS && AZ) {
+    const T yaw = project_azimuth_column<T, SECTOR>(o, x, y, pi_t, W, tab + 2 * H + 2);
+    if (SECTOR) project_sector_yaw<T>(o, yaw, pi_t, W, tab + 3 * H + 2);
+    return o;
+  }
   if (SECTOR) project_sector_column<T>(o, x, y, pi_t, W, tab + (BEAMS ? 2 * H + 2 : n_beams));
   return o;
 }

@@ -135,7 +135,7 @@ class DeviceDeform:
 
     def __init__(self, source, target, vol_bnds=None, voxel_size=0.1, beam_angles=None, t_beam_angles=None,
                  preserve_float=False, device=None, merge=True, fusion="cuda", mesh_volume=True, rayset=None, mm_state=None,
-                 transformation=None, t_beam_table=None, t_sector=None):
+                 transformation=None, t_beam_table=None, t_sector=None, t_beam_azimuth=None):
         """``fusion``: ``"cuda"`` -- the arithmetic of the reference's CUDA kernel (class-aware with ``merge``), or ``"numpy"`` --
         that of its numpy branch (``FUSION_GPU_MODE == 0``, fusion_lidar.py:290-388; what goldens F13 / F14 are made by).
         ``vol_bnds``: [3,2]; for :meth:`mergemesh` it is STATE, clipped in place call after call exactly as the reference
@@ -162,7 +162,14 @@ class DeviceDeform:
         (``mergemesh`` still fuses what the source origin sees inside the target's vertical field of view); ``cp`` puts a
         point into the column whose ray is nearest, drops what lies outside the sector (``LT_PROJ_SECTOR``) and re-projects
         it along that ray (``lt_reverse_projection_sector_dev``).  A shared ``rayset`` must have been built for the same
-        sector (``RaySet(..., sector=...)``)."""
+        sector (``RaySet(..., sector=...)``).
+        ``t_beam_azimuth``: the azimuth offsets of the TARGET's beams (``SensorModel.beam_azimuth()``: [t_H] degrees in the
+        table's row order, with ``t_beam_table`` only; ``None`` or all zero: nothing of this runs) -- beam ``h`` of a column
+        looks ``t_beam_azimuth[h]`` to the left of the column's nominal direction: the target's rays are sheared row by row
+        (with a sector and a pose as above), so ``mesh`` and ``mergemesh`` change by their rays alone; ``cp`` puts a point into
+        the column whose beam of the point's row looks at it (``LT_PROJ_BEAM_AZIMUTH``) and re-projects it along that beam
+        (``lt_reverse_projection_beams_az_dev``).  A shared ``rayset`` must have been built for the same offsets
+        (``RaySet(..., beam_azimuth=...)``)."""
         import numpy as np
         import torch
 
@@ -199,6 +206,16 @@ class DeviceDeform:
             from .config import check_sector
             self.t_sector = check_sector(t_sector, "DeviceDeform: t_sector")
             self._t_sec = _chain.sector_pair(self.t_sector)              # marshalled once: yaw of the middle, width (radians)
+        self.t_beam_azimuth = self._t_az = self._t_az_dev = None
+        if t_beam_azimuth is not None:
+            from .config import check_beam_azimuth
+            if self.t_beam_table is None:
+                raise ValueError("DeviceDeform: t_beam_azimuth belongs to the beams of `t_beam_table`")
+            az = check_beam_azimuth(np.array(t_beam_azimuth, dtype=np.float64), self.t_H, "DeviceDeform: t_beam_azimuth")
+            if np.any(az != 0.0):                                        # (all zero: the table alone)
+                self.t_beam_azimuth = az
+                self._t_az = _chain.beam_azimuth_rad(az)                 # marshalled once: radians
+                self._t_az_dev = torch.from_numpy(self._t_az.copy()).to(self.device)
         # ``origin``: the target sensor in the scene, where mesh / mergemesh cast from by default
         self.mount, self.origin = self._mounting.pair, self._mounting.origin
         if mm_state is not None and vol_bnds is None:
@@ -217,9 +234,10 @@ class DeviceDeform:
             if rayset is None:
                 rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=idx,
                                           rot=pose[:3, :3] if pose is not None else None, beam_table=self.t_beam_table,
-                                          sector=self.t_sector)
+                                          sector=self.t_sector, beam_azimuth=self.t_beam_azimuth)
                 self.rayset = RaySet(rays, self.t_H, pose=pose, beam_table=self.t_beam_table, sector=self.t_sector,
-                                     grid=None if self.t_sector is None else sector_grid(self.t_W, self.t_sector))
+                                     grid=None if self.t_sector is None else sector_grid(self.t_W, self.t_sector),
+                                     beam_azimuth=self.t_beam_azimuth)
                 self._rays = rays
             else:
                 theirs = getattr(rayset, "pose", None)
@@ -231,6 +249,11 @@ class DeviceDeform:
                     raise ValueError("DeviceDeform: the shared rayset was built for another beam table than `t_beam_table`")
                 if getattr(rayset, "sector", None) != self.t_sector:
                     raise ValueError("DeviceDeform: the shared rayset was built for another sector than `t_sector`")
+                theirs = getattr(rayset, "beam_azimuth", None)
+                if (theirs is None) != (self.t_beam_azimuth is None) or \
+                        (theirs is not None and not np.array_equal(theirs, self.t_beam_azimuth)):
+                    raise ValueError("DeviceDeform: the shared rayset was built for other beam azimuth offsets than "
+                                     "`t_beam_azimuth`")
                 self.rayset = rayset
         self.n_rays = self.t_H * self.t_W
 
@@ -502,13 +525,19 @@ class DeviceDeform:
         rows = self._t_rows
         o = self.projector.project([_chain.merged_cloud(clouds)], self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, new=True,
                                    remove=True, beam_angles=self.t_beam_angles if rows is None else None, outputs=outs,
-                                   stream=st, beam_table=rows, sector=self._t_sec)[0]
+                                   stream=st, beam_table=rows, sector=self._t_sec, beam_azimuth=self.t_beam_azimuth)[0]
         px, py = (o["proj_xf"], o["proj_yf"]) if pf else (o["proj_x"], o["proj_y"])
         if pf and px.dtype != torch.float64:
             px, py = px.double(), py.double()
         back = torch.empty((self.n_rays, 3), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            if self._t_sec is not None:   # along the ray of the winner's column (or its own yaw with preserve_float)
+            if self._t_az is not None:    # along the winner's beam, the row's offset beside its column's nominal direction
+                _lib.check(lib.lt_reverse_projection_beams_az_dev(
+                    o["range"].data_ptr(), px.data_ptr(), py.data_ptr(), int(pf), self._t_brad.data_ptr(),
+                    self._t_az_dev.data_ptr(),
+                    self._t_sec.ctypes.data_as(C.POINTER(C.c_double)) if self._t_sec is not None else None, self.t_H, self.t_W,
+                    back.data_ptr(), C.c_void_p(st.cuda_stream)), "lt_reverse_projection_beams_az_dev")
+            elif self._t_sec is not None: # along the ray of the winner's column (or its own yaw with preserve_float)
                 _lib.check(lib.lt_reverse_projection_sector_dev(
                     o["range"].data_ptr(), px.data_ptr(), py.data_ptr(), int(pf), int(rows is not None),
                     self._t_brad.data_ptr() if rows is not None else None, self.t_fov_up, self.t_fov_down, self.t_H, self.t_W,

@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 
 
-def create_rays(fov_up, fov_down, H, W, beam_table=None, sector=None):
+def create_rays(fov_up, fov_down, H, W, beam_table=None, sector=None, beam_azimuth=None):
     """Unit ray direction per (beam, azimuth) cell, ``float32 [H*W, 3]``, row-major ``h*W + w``.
 
     Restatement of ``MultiSemLaserScan.create_rays`` (auxiliary/laserscan.py:1092-1119), quirks
@@ -16,6 +16,9 @@ def create_rays(fov_up, fov_down, H, W, beam_table=None, sector=None):
     ``sector`` (``SensorModel.sector()``: ``(center_deg, span_deg)``): the W columns span that sector alone --
     column w is the cell ``[w, w + 1) * span / W`` from the sector's left edge, clockwise seen from above, and its ray
     leaves through the cell's centre (no closed-``linspace`` quirk: a sector does not close).
+    ``beam_azimuth`` (``SensorModel.beam_azimuth()``: [H] degrees in the table's row order; with a ``beam_table`` only): beam
+    ``h`` of a column looks ``beam_azimuth[h]`` to the left of the column's nominal direction, ``yaw_deg = nominal(w) -
+    beam_azimuth[h]``, no further wrap.
     """
     if sector is None:
         yaw = np.linspace(0, 360, W) + 180
@@ -23,12 +26,13 @@ def create_rays(fov_up, fov_down, H, W, beam_table=None, sector=None):
     else:
         c, s = (float(v) for v in sector)
         yaw = (-c - s / 2) + (np.arange(W, dtype=np.float64) + 0.5) * (s / W)   # not wrapped: sin and cos are periodic
-    yaw = yaw / 180. * np.pi
+    az = _beam_azimuth(beam_azimuth, beam_table, H)
+    yaw = (yaw[None, :] if az is None else yaw[None, :] - az[:, None]) / 180. * np.pi   # [1 or H, W]
     pitch = np.pi / 2 - _beam_degrees(beam_table, fov_up, fov_down, H) / 180. * np.pi
     sp, cp = np.sin(pitch), np.cos(pitch)
     beams = np.empty((H, W, 3), dtype=np.float64)
-    beams[:, :, 0] = sp[:, None] * np.cos(-yaw)[None, :]
-    beams[:, :, 1] = sp[:, None] * np.sin(-yaw)[None, :]
+    beams[:, :, 0] = sp[:, None] * np.cos(-yaw)
+    beams[:, :, 1] = sp[:, None] * np.sin(-yaw)
     beams[:, :, 2] = cp[:, None] * np.ones(W)[None, :]
     return np.ascontiguousarray(beams.reshape(H * W, 3).astype(np.float32))
 
@@ -42,12 +46,24 @@ def _beam_degrees(beam_table, fov_up, fov_down, H):
     return b
 
 
-def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=None, beam_table=None, sector=None):
+def _beam_azimuth(beam_azimuth, beam_table, H):
+    """the offsets as float64 [H] degrees, ``None`` for none; they come with a table only"""
+    if beam_azimuth is None:
+        return None
+    if beam_table is None:
+        raise ValueError("beam_azimuth: the offsets belong to the beams of a beam_table")
+    from .config import check_beam_azimuth
+    return np.ascontiguousarray(check_beam_azimuth(beam_azimuth, H, "beam_azimuth"))
+
+
+def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=None, beam_table=None, sector=None,
+                       beam_azimuth=None):
     """:func:`create_rays` computed by the HIP kernel into a ``torch`` tensor ``[H*W, 3] f32`` on the GPU.  ``rot``: the
     rotation [3, 3] of the sensor's pose (``Approach.mount()[1][:3, :3]``) -- every direction is turned by it in float64,
     ``(r0 * x + r1 * y) + r2 * z`` per component, before the cast to float32; ``None``: the sensor's own frame.
     ``beam_table``: as for :func:`create_rays` (``lt_create_rays_beams_dev``; the call waits for ``stream``).
-    ``sector``: as for :func:`create_rays` (``lt_create_rays_sector_dev``, with or without a table and a rotation)."""
+    ``sector``: as for :func:`create_rays` (``lt_create_rays_sector_dev``, with or without a table and a rotation).
+    ``beam_azimuth``: as for :func:`create_rays` (``lt_create_rays_beams_az_dev``, with or without a sector and a rotation)."""
     import ctypes as C
 
     import torch
@@ -62,8 +78,20 @@ def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=Non
         r = np.ascontiguousarray(rot, dtype=np.float64)
         if r.shape != (3, 3):
             raise ValueError("rot: a 3x3 rotation")
+    az = _beam_azimuth(beam_azimuth, beam_table, H)
     with torch.cuda.device(dev):
-        if sector is not None:
+        if az is not None:
+            dp = C.POINTER(C.c_double)
+            b = _beam_degrees(beam_table, fov_up, fov_down, H)
+            sec = None
+            if sector is not None:
+                from .config import check_sector
+                sec = np.array(check_sector(sector, "create_rays_device: sector"), dtype=np.float64)
+            _lib.check(lib.lt_create_rays_beams_az_dev(b.ctypes.data_as(dp), az.ctypes.data_as(dp), int(H), int(W),
+                                                       sec.ctypes.data_as(dp) if sec is not None else None,
+                                                       r.ctypes.data_as(dp) if r is not None else None, out.data_ptr(),
+                                                       C.c_void_p(st.cuda_stream)), "lt_create_rays_beams_az_dev")
+        elif sector is not None:
             from .config import check_sector
             c, s = check_sector(sector, "create_rays_device: sector")
             dp = C.POINTER(C.c_double)
@@ -110,7 +138,10 @@ class Projector:
     winner's pitch in radians, empty cells hold 0 in ``proj_x`` / ``proj_y`` / ``proj_xf`` / ``proj_yf``.  ``sector``
     (``SensorModel.sector()``, ``(center_deg, span_deg)``; with ``new`` and ``remove`` only, with or without a table): the
     columns are those of the sector (``LT_PROJ_SECTOR``) -- a point outside it is dropped, ``proj_xf`` is its position
-    across the sector times ``W``, ``proj_x`` the column whose ray is nearest."""
+    across the sector times ``W``, ``proj_x`` the column whose ray is nearest.  ``beam_azimuth``
+    (``SensorModel.beam_azimuth()``, [H] degrees in the table's row order; with a ``beam_table`` only, with or without a
+    sector): the beams of the table carry azimuth offsets (``LT_PROJ_BEAM_AZIMUTH``) -- a point goes to the column whose beam
+    of the point's row looks at it, ``proj_xf`` is that nominal coordinate."""
 
     _IMG = {"idx": ("int32", 1), "range": ("float32", 1), "xyz": ("float32", 3), "rem": ("float32", 1), "label": ("int32", 1),
             "color": ("float32", 3), "mask": ("float32", 1), "label_folded": ("float32", 1), "proj_x": ("int32", 1),
@@ -131,7 +162,7 @@ class Projector:
         self._h = h
 
     def project(self, clouds, fov_up, fov_down, H, W, new=True, remove=False, beam_angles=None, color_lut=None,
-                outputs=("range", "rem", "label"), out=None, stream=None, beam_table=None, sector=None):
+                outputs=("range", "rem", "label"), out=None, stream=None, beam_table=None, sector=None, beam_azimuth=None):
         import ctypes as C
 
         from . import _lib
@@ -176,7 +207,6 @@ class Projector:
         lut = color_lut.to(torch.float32).contiguous() if color_lut is not None else None
         beams = None
         if beam_angles is not None and len(beam_angles):
-            import numpy as np
             beams = np.ascontiguousarray(beam_angles, dtype=np.float64)
         st = torch.cuda.current_stream(self.device) if stream is None else stream
         flags = (_lib.LT_PROJ_NEW if new else 0) | (_lib.LT_PROJ_REMOVE if remove else 0)
@@ -192,6 +222,16 @@ class Projector:
             if sec != getattr(self, "_sector", None):
                 _lib.check(self._lib.lt_projector_set_sector(self._h, sec[0], sec[1]), "lt_projector_set_sector")
                 self._sector = sec
+        if beam_azimuth is not None:  # set when they change; the flag reads them
+            from ._chain import beam_azimuth_rad
+            if beam_table is None:
+                raise ValueError("Projector.project: beam_azimuth belongs to the beams of a beam_table")
+            flags |= _lib.LT_PROJ_BEAM_AZIMUTH
+            az = beam_azimuth_rad(beam_azimuth)
+            if getattr(self, "_beam_az", None) is None or not np.array_equal(az, self._beam_az):
+                _lib.check(self._lib.lt_projector_set_beam_azimuth(self._h, az.ctypes.data_as(C.POINTER(C.c_double)), len(az)),
+                           "lt_projector_set_beam_azimuth")
+                self._beam_az = az.copy()
         init = (0.0, -1.0, 0.0) if new else (-1.0, -1.0, -1.0)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.lt_range_projection_batch_dev(

@@ -314,7 +314,9 @@ class FusionScanPipeline:
     Empty, ``None`` or the identity: nothing changes.
 
     A target sensor with a beam table (``SensorModel.beam_table()``) needs nothing but its rays: pass
-    ``create_rays_device(..., beam_table=table)`` (with ``rot`` when it is mounted as well) as ``rays``.
+    ``create_rays_device(..., beam_table=table)`` (with ``rot`` when it is mounted as well) as ``rays``.  The same holds for
+    a table whose beams carry azimuth offsets (``SensorModel.beam_azimuth()``): ``create_rays_device(..., beam_table=table,
+    beam_azimuth=offsets)``.
 
     A target sensor with a horizontal sector (``SensorModel.sector()``) needs its rays,
     ``create_rays_device(..., sector=sector)``, and -- for speed alone -- a bin grid at the sector's resolution:

@@ -275,13 +275,16 @@ class RaySet:
     normalised like the reference (Vector3.h:73-89) and binned by azimuth x elevation.  One per sensor
     model; reuse it for every scan.  ``pose``: the [4, 4] pose of the sensor the rays were generated for (``None``: its own
     frame), ``beam_table``: the beam table the rays were generated from (``None``: evenly spaced beams) and ``sector``: the
-    ``(center_deg, span_deg)`` the columns span (``None``: the full circle) -- only remembered, so that a chain handed a
+    ``(center_deg, span_deg)`` the columns span (``None``: the full circle), ``beam_azimuth``: the per-beam azimuth offsets the
+    rays were generated with (``None``: none) -- only remembered, so that a chain handed a
     shared ray set can tell whether it was built for its sensor.  ``grid``: ``(nb_az, nb_el)``, the size of the bin grid
     (``lt_rayset_create_grid_dev``; 0 = the image's own rule for that axis, ``None`` = ``(0, 0)``) -- any grid renders the same
     image, the fastest is the one whose bin centres the rays sit on: :func:`sector_grid` for a sector."""
 
-    def __init__(self, rays, H, exact_normalize=False, stream=None, pose=None, beam_table=None, sector=None, grid=None):
+    def __init__(self, rays, H, exact_normalize=False, stream=None, pose=None, beam_table=None, sector=None, grid=None,
+                 beam_azimuth=None):
         import torch
+        self.beam_azimuth = None if beam_azimuth is None else np.array(beam_azimuth, dtype=np.float64).reshape(-1)
         self.sector = None if sector is None else (float(sector[0]), float(sector[1]))
         self.grid = None if grid is None else (int(grid[0]), int(grid[1]))
         if self.grid is not None and min(self.grid) < 0:

@@ -112,7 +112,9 @@ class SequenceTransfer:
     for row, so ``evaluate`` behaves as for a mounted target; ``beam_model`` tells.  A source sensor with a table is
     refused.  A target ``SensorModel`` with ``azimuth_model: sector`` brings its sector (``DeviceDeform(t_sector=...)``): its
     columns are not the source scan's full-circle columns, so ``evaluate`` behaves the same way; ``azimuth_model`` tells.  A
-    source sensor with a sector is refused."""
+    source sensor with a sector is refused.  A target table with ``beam_azimuth_offsets`` brings them
+    (``DeviceDeform(t_beam_azimuth=...)``); ``beam_azimuth`` holds them (``None``: none) and a source sensor with the key is
+    refused."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -123,15 +125,17 @@ class SequenceTransfer:
         if int(chains) < 1:
             raise ValueError("chains: at least one")
         self.approach, self.adaption = approach, approach.adaption
-        from .config import refuse_source_sector, refuse_source_table
+        from .config import refuse_source_beam_azimuth, refuse_source_sector, refuse_source_table
         refuse_source_table(source_sensor)
         refuse_source_sector(source_sensor)
+        refuse_source_beam_azimuth(source_sensor)
         self.source_sensor, self.target_sensor = sensor_tuple(source_sensor), sensor_tuple(target_sensor)
         # (sensor_tuple drops the table; ValueError on one that cannot be used)
         self.beam_table = target_sensor.beam_table() if hasattr(target_sensor, "beam_table") else None
         self.beam_model = "linear" if self.beam_table is None else "table"
         self.sector = target_sensor.sector() if hasattr(target_sensor, "sector") else None
         self.azimuth_model = "full" if self.sector is None else "sector"
+        self.beam_azimuth = target_sensor.beam_azimuth() if hasattr(target_sensor, "beam_azimuth") else None
         self.chains = 1 if self.adaption == "cp" else int(chains)     # `cp` always runs on one chain
         self.fusion, self.out_dir = fusion, out_dir
         self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
@@ -181,14 +185,14 @@ class SequenceTransfer:
                     dd = DeviceDeform(self.source_sensor, self.target_sensor, None, beam_angles=beams,
                                       preserve_float=approach.preserve_float, device=idx, fusion=fusion,
                                       transformation=self.mount, t_beam_table=self.beam_table,
-                                      t_sector=self.sector)
+                                      t_sector=self.sector, t_beam_azimuth=self.beam_azimuth)
                 else:
                     dd = DeviceDeform(self.source_sensor, self.target_sensor,
                                       None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
                                       beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
                                       mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm,
                                       transformation=self.mount, t_beam_table=self.beam_table,
-                                      t_sector=self.sector)
+                                      t_sector=self.sector, t_beam_azimuth=self.beam_azimuth)
                     rayset = dd.rayset
                 ch = dict(dd=dd, ev=None, q=None, thread=None,
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
@@ -336,6 +340,7 @@ class SequenceTransfer:
                 job["written"].wait()
             self.summary = dict(scans=n_done, chains=self.chains, adaption=self.adaption, fusion=self.fusion,
                                 mounted=self.mounted, beam_model=self.beam_model, azimuth_model=self.azimuth_model,
+                                beam_azimuth=self.beam_azimuth is not None,
                                 mm_stats=dict(self._mm.stats) if self._mm is not None else None,
                                 source_stats=dict(self.source.stats))
 

@@ -44,6 +44,81 @@ def grid(rs):
     return dict(nb_az=int(nb[0]), nb_el=int(nb[1]), dev_az=float(p[4]), dev_el=float(p[5]))
 
 
+def render_cases(rays, H, tris, reps, renders):
+    """`rays`: name -> [H * W, 3] device rays of one image height.  The render part of the docstring: returns the `render` record"""
+    import torch
+    from lidar_transfer_amd.raytracer import RaySet, Scene
+    from lidar_transfer_amd.synth import synth_scene
+    dev = torch.device("cuda", 0)
+    scn = Scene(0)
+    mesh = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in synth_scene(0, tris)]
+    scn.set_mesh(*mesh)
+    sets, outs, counters = {}, {}, {}
+    for name, r in rays.items():
+        h = H[name] if isinstance(H, dict) else H
+        sets[name] = RaySet(r, h)
+        outs[name] = scn.alloc_outputs(r.shape[0])
+    for name, rs in sets.items():          # warm-up, counters
+        for _ in range(3):
+            o = scn.render(rs, (0.0, 0.0, 0.0), out=outs[name], count=True)
+        s = o["stats"]
+        counters[name] = dict(grid(rs), n_rays=int(s["n_rays"]), n_hits=int(s["n_hits"]), candidate_bins=int(s["nodes_visited"]),
+                              tris_tested=int(s["tris_tested"]), tris_tested_per_ray=float(s["tris_tested"]) / max(int(s["n_rays"]), 1),
+                              entries_culled=int(s["entries_culled"]))
+    ms = {k: [] for k in sets}
+    for _ in range(reps):
+        for name, rs in sets.items():
+            acc = 0.0
+            for _ in range(renders):
+                acc += scn.render(rs, (0.0, 0.0, 0.0), out=outs[name], stats=True)["stats"]["ms_trace"]
+            ms[name].append(acc / renders)
+    doc = dict(tris=int(mesh[1].shape[0]), renders_per_rep=renders, reps=reps, ms_trace={k: stat(v) for k, v in ms.items()},
+               counters=counters)
+    for rs in sets.values():
+        rs.close()
+    scn.close()
+    return doc
+
+
+def sequence_targets(root, targets, raw_scans, window, reps):
+    """`targets`: name -> target SensorModel.  The sequence part of the docstring: returns the `sequence` record"""
+    import bench_ingest as bi
+    import torch
+    from lidar_transfer_amd.config import load_approach
+    from lidar_transfer_amd.ingest import SequenceSource
+    from lidar_transfer_amd.sequence import SequenceTransfer
+    sensor = (bi.H, bi.W, bi.FOV_UP, bi.FOV_DOWN)
+    scans, poses = bi.make_sequence(raw_scans, 7)
+    a = load_approach(os.path.join(root, "config", "approach_mergemesh.yaml"))
+    runners = {}
+    for name, t in targets.items():
+        src = SequenceSource(scans=[s for s, _ in scans], labels=[l for _, l in scans], poses=poses, cache_scans=32)
+        runners[name] = SequenceTransfer(src, a, sensor, t, out_dir=None, chains=1, evaluate=False)
+
+    def one_pass(tr):
+        n = sum(1 for _ in tr.run())
+        torch.cuda.synchronize()
+        return n
+
+    for tr in runners.values():
+        one_pass(tr)
+    times = {k: [] for k in runners}
+    for _ in range(reps):
+        for name, tr in runners.items():
+            n, t0 = 0, time.perf_counter()
+            while time.perf_counter() - t0 < window:
+                n += one_pass(tr)
+            times[name].append((time.perf_counter() - t0) * 1e3 / n)
+    doc = dict(workload=dict(raw_scans=len(scans), source=list(sensor), adaption="mergemesh", chains=1,
+                             number_of_scans=a.number_of_scans, window_s=window, reps=reps),
+               ms_per_output_scan={k: stat(v) for k, v in times.items()},
+               mm_stats={k: tr.summary.get("mm_stats") for k, tr in runners.items()})
+    for tr in runners.values():
+        tr.source.close()
+        tr.close()
+    return doc
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -60,85 +135,24 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_beam_table.py needs a GPU")
-    import bench_ingest as bi
     import lidar_transfer_amd
-    from lidar_transfer_amd.config import load_approach, load_sensor
-    from lidar_transfer_amd.ingest import SequenceSource
+    from lidar_transfer_amd.config import load_sensor
     from lidar_transfer_amd.laserscan import create_rays_device
-    from lidar_transfer_amd.raytracer import RaySet, Scene
-    from lidar_transfer_amd.sequence import SequenceTransfer
-    from lidar_transfer_amd.synth import WORKLOADS, synth_scene
+    from lidar_transfer_amd.synth import WORKLOADS
     assert os.path.abspath(lidar_transfer_amd.__file__).startswith(root + os.sep), lidar_transfer_amd.__file__
-    dev = torch.device("cuda", 0)
     doc = dict(root=os.path.relpath(root), linear_only=bool(args.linear_only))
-
-    # ---- the render alone ----------------------------------------------------------------------------------------------------
     cases = {"linear 64x2048": (2.0, -24.8, 64, 2048, None), "linear 32x1024": (15.0, -25.0, 32, 1024, None)}
     if not args.linear_only:
         cases["two_block 64x2048"] = (2.0, -24.8, 64, 2048, np.array(TWO_BLOCK))
         cases["vlp32c 32x1024"] = (15.0, -25.0, 32, 1024, np.array(VLP32C))
-    scn = Scene(0)
-    mesh = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in synth_scene(0, WORKLOADS["C2"]["tris"])]
-    scn.set_mesh(*mesh)
-    sets, outs, counters = {}, {}, {}
-    for name, (fu, fd, H, W, table) in cases.items():
-        rays = create_rays_device(fu, fd, H, W) if table is None else create_rays_device(fu, fd, H, W, beam_table=table)
-        sets[name] = (RaySet(rays, H), rays)
-        outs[name] = scn.alloc_outputs(H * W)
-    for name, (rs, _) in sets.items():          # warm-up, counters
-        for _ in range(3):
-            o = scn.render(rs, (0.0, 0.0, 0.0), out=outs[name], count=True)
-        s = o["stats"]
-        counters[name] = dict(grid(rs), n_rays=int(s["n_rays"]), n_hits=int(s["n_hits"]), candidate_bins=int(s["nodes_visited"]),
-                              tris_tested=int(s["tris_tested"]), tris_tested_per_ray=float(s["tris_tested"]) / max(int(s["n_rays"]), 1),
-                              entries_culled=int(s["entries_culled"]))
-    ms = {k: [] for k in sets}
-    for _ in range(args.reps):
-        for name, (rs, _) in sets.items():
-            acc = 0.0
-            for _ in range(args.renders):
-                acc += scn.render(rs, (0.0, 0.0, 0.0), out=outs[name], stats=True)["stats"]["ms_trace"]
-            ms[name].append(acc / args.renders)
-    doc["render"] = dict(tris=int(mesh[1].shape[0]), renders_per_rep=args.renders, reps=args.reps,
-                         ms_trace={k: stat(v) for k, v in ms.items()}, counters=counters)
-    for rs, _ in sets.values():
-        rs.close()
-    scn.close()
-    del mesh, outs
-
-    # ---- a whole sequence ------------------------------------------------------------------------------------------------------
-    sensor = (bi.H, bi.W, bi.FOV_UP, bi.FOV_DOWN)
-    scans, poses = bi.make_sequence(args.raw_scans, 7)
-    a = load_approach(os.path.join(root, "config", "approach_mergemesh.yaml"))
+    rays = {name: (create_rays_device(fu, fd, H, W) if table is None else create_rays_device(fu, fd, H, W, beam_table=table))
+            for name, (fu, fd, H, W, table) in cases.items()}
+    doc["render"] = render_cases(rays, {name: c[2] for name, c in cases.items()}, WORKLOADS["C2"]["tris"], args.reps, args.renders)
+    del rays
     targets = {"vlp32_1024.yaml": load_sensor(os.path.join(root, "config", "vlp32_1024.yaml"))}
     if not args.linear_only:
         targets["vlp32c_table_1024.yaml"] = load_sensor(os.path.join(root, "config", "vlp32c_table_1024.yaml"))
-    runners = {}
-    for name, t in targets.items():
-        src = SequenceSource(scans=[s for s, _ in scans], labels=[l for _, l in scans], poses=poses, cache_scans=32)
-        runners[name] = SequenceTransfer(src, a, sensor, t, out_dir=None, chains=1, evaluate=False)
-
-    def one_pass(tr):
-        n = sum(1 for _ in tr.run())
-        torch.cuda.synchronize()
-        return n
-
-    for tr in runners.values():
-        one_pass(tr)
-    times = {k: [] for k in runners}
-    for _ in range(args.reps):
-        for name, tr in runners.items():
-            n, t0 = 0, time.perf_counter()
-            while time.perf_counter() - t0 < args.window:
-                n += one_pass(tr)
-            times[name].append((time.perf_counter() - t0) * 1e3 / n)
-    doc["sequence"] = dict(workload=dict(raw_scans=len(scans), source=list(sensor), adaption="mergemesh", chains=1,
-                                         number_of_scans=a.number_of_scans, window_s=args.window, reps=args.reps),
-                           ms_per_output_scan={k: stat(v) for k, v in times.items()},
-                           mm_stats={k: tr.summary.get("mm_stats") for k, tr in runners.items()})
-    for tr in runners.values():
-        tr.source.close()
-        tr.close()
+    doc["sequence"] = sequence_targets(root, targets, args.raw_scans, args.window, args.reps)
     print(json.dumps(doc))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
