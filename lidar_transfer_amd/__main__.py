@@ -64,16 +64,13 @@ def main(argv=None):
     if problem:
         print(problem)
         return 1
-    from .config import load_approach, load_sensor
+    from .config import load_approach, load_sensor, refuse_source_models
     source_path = os.path.join(args.dataset, "config.yaml")
     target_path = args.target or source_path
     try:
         approach, source, target = load_approach(args.config), load_sensor(source_path), load_sensor(target_path)
         approach.mount()   # (a transformation that is not a rigid motion: said here, not half way into the run)
-        from .config import refuse_source_beam_azimuth, refuse_source_sector, refuse_source_table
-        refuse_source_table(source)
-        refuse_source_sector(source)
-        refuse_source_beam_azimuth(source)
+        refuse_source_models(source)
     except Exception as e:  # noqa: BLE001  (a YAML that cannot be read: message and status, as the reference's quit())
         print(e)
         print("Error opening yaml file.")

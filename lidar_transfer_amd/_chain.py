@@ -48,41 +48,6 @@ def beam_table(beam_angles):
     return beams.ctypes.data_as(C.c_void_p), len(beams), beams
 
 
-def beam_rows_table(table):
-    """``(pointer, H, array to keep alive)`` of a target sensor's beam TABLE (``SensorModel.beam_table()``, degrees,
-    descending) as ``LT_PROJ_BEAM_ROWS`` reads it: ``Brad`` followed by ``halfw`` (``config.beam_rows``), float64 [2 H].
-    A table that already is such a marshalled triple is returned as it is."""
-    if isinstance(table, tuple):
-        return table
-    import numpy as np
-
-    from .config import beam_rows
-    t = np.ascontiguousarray(np.concatenate(beam_rows(table)), dtype=np.float64)
-    return t.ctypes.data_as(C.c_void_p), len(t) // 2, t
-
-
-def sector_pair(sector):
-    """A target sensor's SECTOR (``SensorModel.sector()``, ``(center_deg, span_deg)``) as ``LT_PROJ_SECTOR`` and
-    ``lt_reverse_projection_sector_dev`` read it: float64 [2], the yaw of its middle and its width in radians
-    (``config.sector_radians``).  A float64 array of two is taken as already marshalled."""
-    import numpy as np
-    if isinstance(sector, np.ndarray):
-        return sector
-    from .config import check_sector, sector_radians
-    return np.array(sector_radians(check_sector(sector)), dtype=np.float64)
-
-
-def beam_azimuth_rad(beam_azimuth):
-    """A target sensor's per-beam AZIMUTH OFFSETS (``SensorModel.beam_azimuth()``, degrees, the table's row order) as
-    ``LT_PROJ_BEAM_AZIMUTH`` and ``lt_reverse_projection_beams_az_dev`` read them: float64 [H] radians
-    (``config.beam_azimuth_radians``)."""
-    import numpy as np
-
-    from .config import beam_azimuth_radians, check_beam_azimuth
-    a = np.asarray(beam_azimuth, dtype=np.float64)
-    return beam_azimuth_radians(check_beam_azimuth(a, a.size))
-
-
 def origin3(origin):
     return (C.c_float * 3)(*[float(x) for x in origin])
 

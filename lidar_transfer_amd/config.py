@@ -14,24 +14,23 @@ Host logic only: what the files say is turned into the arguments of the device p
 is ``None`` when absent; ``create_rays`` ignores it (``laserscan.py:1092-1119``), the projection uses it
 (``laserscan.py:233-238``).
 
-``beam_model: table`` (optional, default ``linear``) is this project's own key, for a TARGET sensor: its ``beam_angles`` are
-then the real elevation of every beam in degrees -- its rays leave at these angles and a point's image row is its nearest
-beam (:meth:`SensorModel.beam_table`).  Without the key ``beam_angles`` keeps the meaning above.
+Three optional keys are this project's own, for a TARGET sensor; :class:`TargetModel` carries what they say to the device path
+(``SensorModel.target_model()``), and without them nothing changes:
 
-``azimuth_model: sector`` (optional, default ``full``) and ``azimuth_center`` (degrees, default 0) are this project's own
-keys as well, for a TARGET sensor: ``fov_hor`` is then the width of the sensor's horizontal field of view around the
-direction ``azimuth_center`` and the ``W`` columns span that sector alone (:meth:`SensorModel.sector`).  Without
-the key ``fov_hor`` only sets ``W`` and the columns go round the whole circle, as in the reference.
-
-``beam_azimuth_offsets`` (optional) is this project's own key too, for a TARGET sensor with ``beam_model: table``: one number
-per beam in degrees, in the order in which the file lists ``beam_angles`` -- the lasers of one firing do not share an
-azimuth, beam ``h`` of a column looks ``offset[h]`` to the LEFT of the column's nominal direction (measured like
-``azimuth_center``; :meth:`SensorModel.beam_azimuth`).  The loader pairs offsets and angles before it sorts the
-angles.  Without the key, or with offsets that are all zero, nothing changes.
+* ``beam_model: table`` (default ``linear``): ``beam_angles`` are the real elevation of every beam in degrees -- its rays leave
+  at these angles and a point's image row is its nearest beam (:meth:`SensorModel.beam_table`, DESIGN 7b);
+* ``azimuth_model: sector`` (default ``full``) and ``azimuth_center`` (degrees, default 0): ``fov_hor`` is the width of the
+  sensor's horizontal field of view around the direction ``azimuth_center`` and the ``W`` columns span that sector alone, not
+  the whole circle (:meth:`SensorModel.sector`, DESIGN 7c);
+* ``beam_azimuth_offsets``, with ``beam_model: table``: one number per beam in degrees, in the order in which the file lists
+  ``beam_angles`` (the loader pairs the two before it sorts the angles) -- the lasers of one firing do not share an azimuth,
+  beam ``h`` of a column looks ``offset[h]`` to the LEFT of the column's nominal direction, measured like ``azimuth_center``
+  (:meth:`SensorModel.beam_azimuth`); offsets that are all zero are none.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from functools import cached_property
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -71,8 +70,34 @@ class SensorModel:
         """Host mirror of ``MultiSemLaserScan.create_rays(fov_up, fov_down, H, W)`` for this model:
         ``[H*W, 3]`` float32 (beam_angles are ignored there, as in the reference)."""
         from .laserscan import create_rays
-        return create_rays(self.fov_up, self.fov_down, self.H, self.W, beam_table=self.beam_table(), sector=self.sector(),
-                           beam_azimuth=self.beam_azimuth())
+        m = self.target_model()
+        return create_rays(self.fov_up, self.fov_down, self.H, self.W, m.beam_table, m.sector, m.beam_azimuth)
+
+    def target_model(self):
+        """What this sensor has beyond the reference's evenly spaced full circle as ONE :class:`TargetModel`, validated against
+        the sensor: what the device path is handed for a TARGET.  Its fields: :meth:`beam_table`, :meth:`sector`, :meth:`beam_azimuth`."""
+        who = f"sensor {self.name!r}"
+        if self.beam_model not in ("linear", "table"):
+            raise ValueError(f"{who}: beam_model {self.beam_model!r} (linear or table)")
+        if self.azimuth_model not in ("full", "sector"):
+            raise ValueError(f"{who}: azimuth_model {self.azimuth_model!r} (full or sector)")
+
+        def numbers(values, else_say):
+            try:
+                return np.array([float(v) for v in values], dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: {else_say}") from None
+        table = az = None
+        if self.beam_model == "table":
+            angles = numbers(self.beam_angles or (), "beam_model table needs beam_angles, a list of numbers")
+            order = np.argsort(-angles, kind="stable")   # (a table's angles are distinct: one order)
+            table = angles[order]
+        if self.beam_azimuth_offsets is not None:
+            az = numbers(self.beam_azimuth_offsets, "beam_azimuth_offsets must be a list of numbers")
+            if table is not None and len(az) == len(table):   # (another count: refused below)
+                az = az[order]
+        sector = (self.azimuth_center, self.fov_hor) if self.azimuth_model == "sector" else None
+        return TargetModel(table, sector, az, who).validate(self.H, (self.fov_up, self.fov_down), who)
 
     def sector(self):
         """``None`` for ``azimuth_model: full``; for ``sector`` ``(center_deg, span_deg)`` as floats: the ``W`` columns span
@@ -80,11 +105,7 @@ class SensorModel:
         frame: 0 is straight ahead, positive to the left), column 0 at the left edge, clockwise seen from above.  A centre
         beyond +-180 comes back reduced by a full turn.  ``ValueError`` for another model, a ``fov_hor`` outside (0, 360),
         or a centre that is not finite or beyond +-360."""
-        if self.azimuth_model == "full":
-            return None
-        if self.azimuth_model != "sector":
-            raise ValueError(f"sensor {self.name!r}: azimuth_model {self.azimuth_model!r} (full or sector)")
-        return check_sector((self.azimuth_center, self.fov_hor), f"sensor {self.name!r}")
+        return self.target_model().sector
 
     def beam_table(self):
         """``None`` for ``beam_model: linear``; for ``table`` the beams' elevations in degrees, float64 [H], sorted
@@ -92,15 +113,7 @@ class SensorModel:
         one angle per beam, all are finite with |angle| < 90, neighbours differ by at least 1e-6 degrees and every angle
         lies in ``[fov_down, fov_up]`` (``mergemesh`` fuses only what the target's field of view holds, laserscan.py:952,
         :968: a beam outside it would look at nothing)."""
-        if self.beam_model == "linear":
-            return None
-        if self.beam_model != "table":
-            raise ValueError(f"sensor {self.name!r}: beam_model {self.beam_model!r} (linear or table)")
-        try:
-            b = np.array(sorted((float(a) for a in (self.beam_angles or ())), reverse=True), dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"sensor {self.name!r}: beam_model table needs beam_angles, a list of numbers") from None
-        return check_beam_table(b, self.H, self.fov_up, self.fov_down, f"sensor {self.name!r}")
+        return self.target_model().beam_table
 
     def beam_azimuth(self):
         """``None`` without ``beam_azimuth_offsets`` or when all of them are zero; else the beams' azimuth offsets in degrees,
@@ -108,20 +121,7 @@ class SensorModel:
         ``beam_angles[k]`` and travels with it.  Beam ``h`` of a column looks ``offset[h]`` to the left of the column's nominal
         direction.  ``ValueError`` unless the sensor has ``beam_model: table`` and there is one finite number per beam with
         ``|offset| <= 90``."""
-        if self.beam_azimuth_offsets is None:
-            return None
-        who = f"sensor {self.name!r}"
-        table = self.beam_table()
-        if table is None:
-            raise ValueError(f"{who}: beam_azimuth_offsets needs beam_model: table (the offsets belong to the table's beams)")
-        try:
-            a = np.array([float(v) for v in self.beam_azimuth_offsets], dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: beam_azimuth_offsets must be a list of numbers") from None
-        angles = np.array([float(v) for v in self.beam_angles], dtype=np.float64)
-        a = check_beam_azimuth(a, len(angles), who)
-        a = a[np.argsort(-angles, kind="stable")]   # (the table's angles are distinct: one order)
-        return a if np.any(a != 0.0) else None
+        return self.target_model().beam_azimuth
 
 
 def check_beam_azimuth(a, H, who="beam azimuth offsets"):
@@ -194,6 +194,102 @@ def beam_rows(table):
     return Brad, halfw
 
 
+def _same(a, b):
+    return (a is None) == (b is None) and (a is None or np.array_equal(a, b))
+
+
+class TargetModel:
+    """What distinguishes a TARGET sensor's rows and columns from the reference's evenly spaced full circle, as one immutable
+    value -- the ONE thing the device path passes around (``create_rays``, ``RaySet``, ``Projector``, ``DeviceDeform``).  Its
+    fields ``beam_table``, ``sector`` and ``beam_azimuth`` are what :meth:`SensorModel.beam_table`, :meth:`SensorModel.sector` and
+    :meth:`SensorModel.beam_azimuth` return, each ``None`` where the sensor is the reference's.  The
+    constructor normalises and nothing else does: dtype, the centre reduced by a full turn (:func:`check_sector`, whose
+    conditions no sensor enters), offsets that are all zero become ``None``; offsets without a table are a ``ValueError``.
+    :meth:`validate` holds the model against a sensor; ``who`` leads the messages of both.  What the library reads --
+    :attr:`rows`, :attr:`sector_rad`, :attr:`azimuth_rad`, :attr:`proj_flags`, :meth:`grid` -- is derived from the fields on
+    first use and kept.  Two models are equal when their fields are, arrays by value."""
+
+    def __init__(self, beam_table=None, sector=None, beam_azimuth=None, who="target model"):
+        def frozen(v):
+            a = np.array(v, dtype=np.float64)
+            a.setflags(write=False)
+            return a
+        if beam_table is not None:
+            beam_table = frozen(beam_table)
+        if sector is not None:
+            sector = check_sector(sector, who)   # (no sensor enters its conditions, and the reduction needs them)
+        if beam_azimuth is not None:
+            if beam_table is None:
+                raise ValueError(f"{who}: beam_azimuth_offsets needs beam_model: table (the offsets belong to the beams of a "
+                                 "beam table)")
+            beam_azimuth = frozen(beam_azimuth)
+            if not np.any(beam_azimuth != 0.0):   # (all zero: the table alone)
+                beam_azimuth = None
+        self.__dict__.update(beam_table=beam_table, sector=sector, beam_azimuth=beam_azimuth)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a TargetModel does not change: make another")
+
+    def validate(self, H, fov=None, who="target model"):
+        """``ValueError``, its message led by ``who``, unless the model fits a sensor of ``H`` beams: one table entry and one
+        offset per beam, the conditions of :func:`check_beam_azimuth`, and -- given the sensor's ``fov = (fov_up, fov_down)``
+        -- those of :func:`check_beam_table`.  Returns the model."""
+        if self.beam_table is not None:
+            if fov is not None:
+                check_beam_table(self.beam_table, H, fov[0], fov[1], who)
+            elif self.beam_table.shape != (int(H),):
+                raise ValueError(f"{who}: {self.beam_table.size} beam_angles for {int(H)} beams")
+        if self.beam_azimuth is not None:
+            check_beam_azimuth(self.beam_azimuth, H, who)
+        return self
+
+    def difference(self, other):
+        """the first field in which two models differ -- ``"beam_table"``, ``"sector"``, ``"beam_azimuth"`` -- or ``None``"""
+        if not _same(self.beam_table, other.beam_table):
+            return "beam_table"
+        if self.sector != other.sector:
+            return "sector"
+        return None if _same(self.beam_azimuth, other.beam_azimuth) else "beam_azimuth"
+
+    def __eq__(self, other):
+        return isinstance(other, TargetModel) and self.difference(other) is None
+
+    @cached_property
+    def rows(self):
+        """the table as ``LT_PROJ_BEAM_ROWS`` reads it, float64 [2 H]: ``Brad`` followed by ``halfw`` (:func:`beam_rows`)"""
+        return None if self.beam_table is None else np.ascontiguousarray(np.concatenate(beam_rows(self.beam_table)))
+
+    @property
+    def rows_ptr(self):
+        """``void *`` to :attr:`rows` (which the model keeps alive), ``None`` without a table"""
+        import ctypes as C
+        return None if self.rows is None else self.rows.ctypes.data_as(C.c_void_p)
+
+    @cached_property
+    def sector_rad(self):
+        """the sector as ``LT_PROJ_SECTOR`` reads it, float64 [2]: :func:`sector_radians`"""
+        return None if self.sector is None else np.array(sector_radians(self.sector), dtype=np.float64)
+
+    @cached_property
+    def azimuth_rad(self):
+        """the offsets as ``LT_PROJ_BEAM_AZIMUTH`` reads them, float64 [H]: :func:`beam_azimuth_radians`"""
+        return None if self.beam_azimuth is None else beam_azimuth_radians(self.beam_azimuth)
+
+    @property
+    def proj_flags(self):
+        """the ``LT_PROJ_*`` bits of the three fields"""
+        from . import _lib
+        return (_lib.LT_PROJ_BEAM_ROWS if self.beam_table is not None else 0) | \
+            (_lib.LT_PROJ_SECTOR if self.sector is not None else 0) | \
+            (_lib.LT_PROJ_BEAM_AZIMUTH if self.beam_azimuth is not None else 0)
+
+    def grid(self, W):
+        """the bin grid of this sensor's ray set at image width ``W`` (``RaySet(..., grid=...)``): ``raytracer.sector_grid``
+        for a sector, ``None`` (the image's own rule) without one"""
+        from .raytracer import sector_grid
+        return None if self.sector is None else sector_grid(W, self.sector)
+
+
 def _load_yaml(path_or_dict):
     if isinstance(path_or_dict, dict):
         return path_or_dict
@@ -232,9 +328,7 @@ def load_sensor(path_or_dict) -> SensorModel:
                         beam_model=str(cfg.get("beam_model", "linear")),
                         azimuth_model=str(cfg.get("azimuth_model", "full")), azimuth_center=cfg.get("azimuth_center", 0.0),
                         beam_azimuth_offsets=offsets)
-    model.beam_table()   # (a table that cannot be used: said at load time)
-    model.sector()       # (the same for a sector)
-    model.beam_azimuth() # (and for the beams' azimuth offsets)
+    model.target_model()   # (a table, a sector or offsets that cannot be used: said at load time)
     return model
 
 
@@ -258,6 +352,13 @@ def refuse_source_beam_azimuth(source):
     if getattr(source, "beam_azimuth_offsets", None) is not None:
         raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: beam_azimuth_offsets is for target sensors only (the "
                          "source scan is fused by the reference's pixel model: one azimuth per column)")
+
+
+def refuse_source_models(source):
+    """everything a :class:`TargetModel` holds is a property of the TARGET: the three refusals, the table's first"""
+    refuse_source_table(source)
+    refuse_source_sector(source)
+    refuse_source_beam_azimuth(source)
 
 
 @dataclass

@@ -20,15 +20,17 @@ def create_rays(fov_up, fov_down, H, W, beam_table=None, sector=None, beam_azimu
     ``h`` of a column looks ``beam_azimuth[h]`` to the left of the column's nominal direction, ``yaw_deg = nominal(w) -
     beam_azimuth[h]``, no further wrap.
     """
-    if sector is None:
+    from .config import TargetModel
+    m = TargetModel(beam_table, sector, beam_azimuth, "create_rays").validate(H, who="create_rays")
+    if m.sector is None:
         yaw = np.linspace(0, 360, W) + 180
         yaw[yaw > 360] -= 360
     else:
-        c, s = (float(v) for v in sector)
+        c, s = m.sector
         yaw = (-c - s / 2) + (np.arange(W, dtype=np.float64) + 0.5) * (s / W)   # not wrapped: sin and cos are periodic
-    az = _beam_azimuth(beam_azimuth, beam_table, H)
+    az = m.beam_azimuth
     yaw = (yaw[None, :] if az is None else yaw[None, :] - az[:, None]) / 180. * np.pi   # [1 or H, W]
-    pitch = np.pi / 2 - _beam_degrees(beam_table, fov_up, fov_down, H) / 180. * np.pi
+    pitch = np.pi / 2 - (np.linspace(fov_up, fov_down, H) if m.beam_table is None else m.beam_table) / 180. * np.pi
     sp, cp = np.sin(pitch), np.cos(pitch)
     beams = np.empty((H, W, 3), dtype=np.float64)
     beams[:, :, 0] = sp[:, None] * np.cos(-yaw)
@@ -37,23 +39,22 @@ def create_rays(fov_up, fov_down, H, W, beam_table=None, sector=None, beam_azimu
     return np.ascontiguousarray(beams.reshape(H * W, 3).astype(np.float32))
 
 
-def _beam_degrees(beam_table, fov_up, fov_down, H):
-    if beam_table is None:
-        return np.linspace(fov_up, fov_down, H)
-    b = np.ascontiguousarray(beam_table, dtype=np.float64)
-    if b.shape != (int(H),):
-        raise ValueError(f"beam_table: {b.size} angles for H = {H} rows")
-    return b
-
-
-def _beam_azimuth(beam_azimuth, beam_table, H):
-    """the offsets as float64 [H] degrees, ``None`` for none; they come with a table only"""
-    if beam_azimuth is None:
-        return None
-    if beam_table is None:
-        raise ValueError("beam_azimuth: the offsets belong to the beams of a beam_table")
-    from .config import check_beam_azimuth
-    return np.ascontiguousarray(check_beam_azimuth(beam_azimuth, H, "beam_azimuth"))
+def _rays_entry(m, fov_up, fov_down, H, W, r):
+    """which of the five ``lt_create_rays*_dev`` entry points makes the rays of model ``m`` (turned by ``r`` or not), and its
+    arguments in front of ``out, stream``"""
+    import ctypes as C
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+    fov, hw = (float(fov_up), float(fov_down)), (int(H), int(W))
+    if m.beam_azimuth is not None:
+        sec = None if m.sector is None else np.array(m.sector, dtype=np.float64)
+        return "lt_create_rays_beams_az_dev", (dp(m.beam_table), dp(m.beam_azimuth)) + hw + (dp(sec), dp(r))
+    if m.sector is not None:
+        return "lt_create_rays_sector_dev", (dp(m.beam_table),) + fov + hw + m.sector + (dp(r),)
+    if m.beam_table is not None:
+        return "lt_create_rays_beams_dev", (dp(m.beam_table),) + hw + (dp(r),)
+    if r is None:
+        return "lt_create_rays_dev", fov + hw
+    return "lt_create_rays_pose_dev", fov + hw + (dp(r),)
 
 
 def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=None, beam_table=None, sector=None,
@@ -61,14 +62,16 @@ def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=Non
     """:func:`create_rays` computed by the HIP kernel into a ``torch`` tensor ``[H*W, 3] f32`` on the GPU.  ``rot``: the
     rotation [3, 3] of the sensor's pose (``Approach.mount()[1][:3, :3]``) -- every direction is turned by it in float64,
     ``(r0 * x + r1 * y) + r2 * z`` per component, before the cast to float32; ``None``: the sensor's own frame.
-    ``beam_table``: as for :func:`create_rays` (``lt_create_rays_beams_dev``; the call waits for ``stream``).
-    ``sector``: as for :func:`create_rays` (``lt_create_rays_sector_dev``, with or without a table and a rotation).
-    ``beam_azimuth``: as for :func:`create_rays` (``lt_create_rays_beams_az_dev``, with or without a sector and a rotation)."""
+    ``beam_table``, ``sector``, ``beam_azimuth``: as for :func:`create_rays`, in any combination a
+    :class:`~lidar_transfer_amd.config.TargetModel` allows, with or without a rotation (with a table the call waits for
+    ``stream``)."""
     import ctypes as C
 
     import torch
 
     from . import _lib
+    from .config import TargetModel
+    m = TargetModel(beam_table, sector, beam_azimuth, "create_rays_device").validate(H, who="create_rays_device")
     lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
     out = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
@@ -78,41 +81,9 @@ def create_rays_device(fov_up, fov_down, H, W, device=None, stream=None, rot=Non
         r = np.ascontiguousarray(rot, dtype=np.float64)
         if r.shape != (3, 3):
             raise ValueError("rot: a 3x3 rotation")
-    az = _beam_azimuth(beam_azimuth, beam_table, H)
+    name, args = _rays_entry(m, fov_up, fov_down, H, W, r)
     with torch.cuda.device(dev):
-        if az is not None:
-            dp = C.POINTER(C.c_double)
-            b = _beam_degrees(beam_table, fov_up, fov_down, H)
-            sec = None
-            if sector is not None:
-                from .config import check_sector
-                sec = np.array(check_sector(sector, "create_rays_device: sector"), dtype=np.float64)
-            _lib.check(lib.lt_create_rays_beams_az_dev(b.ctypes.data_as(dp), az.ctypes.data_as(dp), int(H), int(W),
-                                                       sec.ctypes.data_as(dp) if sec is not None else None,
-                                                       r.ctypes.data_as(dp) if r is not None else None, out.data_ptr(),
-                                                       C.c_void_p(st.cuda_stream)), "lt_create_rays_beams_az_dev")
-        elif sector is not None:
-            from .config import check_sector
-            c, s = check_sector(sector, "create_rays_device: sector")
-            dp = C.POINTER(C.c_double)
-            b = _beam_degrees(beam_table, fov_up, fov_down, H) if beam_table is not None else None
-            _lib.check(lib.lt_create_rays_sector_dev(b.ctypes.data_as(dp) if b is not None else None, float(fov_up),
-                                                     float(fov_down), int(H), int(W), c, s,
-                                                     r.ctypes.data_as(dp) if r is not None else None, out.data_ptr(),
-                                                     C.c_void_p(st.cuda_stream)), "lt_create_rays_sector_dev")
-        elif beam_table is not None:
-            b = _beam_degrees(beam_table, fov_up, fov_down, H)
-            dp = C.POINTER(C.c_double)
-            _lib.check(lib.lt_create_rays_beams_dev(b.ctypes.data_as(dp), int(H), int(W),
-                                                    r.ctypes.data_as(dp) if r is not None else None, out.data_ptr(),
-                                                    C.c_void_p(st.cuda_stream)), "lt_create_rays_beams_dev")
-        elif rot is None:
-            _lib.check(lib.lt_create_rays_dev(float(fov_up), float(fov_down), int(H), int(W), out.data_ptr(),
-                                              C.c_void_p(st.cuda_stream)), "lt_create_rays_dev")
-        else:
-            _lib.check(lib.lt_create_rays_pose_dev(float(fov_up), float(fov_down), int(H), int(W),
-                                                   r.ctypes.data_as(C.POINTER(C.c_double)), out.data_ptr(),
-                                                   C.c_void_p(st.cuda_stream)), "lt_create_rays_pose_dev")
+        _lib.check(getattr(lib, name)(*args, out.data_ptr(), C.c_void_p(st.cuda_stream)), name)
     return out
 
 
@@ -132,16 +103,14 @@ class Projector:
     ``TSDFVolume.integrate`` folds from ``proj_label3``), ``proj_x`` / ``proj_y`` / ``proj_xf`` / ``proj_yf``, ``n_kept``
     (a 1-element int32 tensor), ``bnds`` (a [3,2] float64 tensor: ``get_bnds()`` of the kept points, laserscan.py:678-681).
     Empty cells: 0 / -1 / 0 for range / rem / xyz with ``new`` (laserscan.py:362-368), -1
-    everywhere for the old variant (:37-53).  ``beam_table`` (``SensorModel.beam_table()``, [H] degrees descending; with
-    ``new`` and ``remove`` only): the rows are the beams of the table (``LT_PROJ_BEAM_ROWS``) -- a point goes to its nearest
-    beam and is kept only within half the gap to that beam's nearer neighbour; ``proj_y`` is the row, ``proj_yf`` the
-    winner's pitch in radians, empty cells hold 0 in ``proj_x`` / ``proj_y`` / ``proj_xf`` / ``proj_yf``.  ``sector``
-    (``SensorModel.sector()``, ``(center_deg, span_deg)``; with ``new`` and ``remove`` only, with or without a table): the
-    columns are those of the sector (``LT_PROJ_SECTOR``) -- a point outside it is dropped, ``proj_xf`` is its position
-    across the sector times ``W``, ``proj_x`` the column whose ray is nearest.  ``beam_azimuth``
-    (``SensorModel.beam_azimuth()``, [H] degrees in the table's row order; with a ``beam_table`` only, with or without a
-    sector): the beams of the table carry azimuth offsets (``LT_PROJ_BEAM_AZIMUTH``) -- a point goes to the column whose beam
-    of the point's row looks at it, ``proj_xf`` is that nominal coordinate."""
+    everywhere for the old variant (:37-53).  ``beam_table``, ``sector``, ``beam_azimuth``: the fields of a target sensor's
+    :class:`~lidar_transfer_amd.config.TargetModel` (with ``new`` and ``remove`` only).  With a table the rows are its beams
+    (``LT_PROJ_BEAM_ROWS``) -- a point goes to its nearest beam and is kept only within half the gap to that beam's nearer
+    neighbour; ``proj_y`` is the row, ``proj_yf`` the winner's pitch in radians, empty cells hold 0 in ``proj_x`` /
+    ``proj_y`` / ``proj_xf`` / ``proj_yf``.  With a sector the columns are the sector's (``LT_PROJ_SECTOR``) -- a point outside
+    it is dropped, ``proj_xf`` is its position across the sector times ``W``, ``proj_x`` the column whose ray is nearest.
+    With offsets (``LT_PROJ_BEAM_AZIMUTH``) a point goes to the column whose beam of the point's row looks at it, ``proj_xf``
+    is that nominal coordinate.  The projector is told a sector and offsets when they differ from the model it applied last."""
 
     _IMG = {"idx": ("int32", 1), "range": ("float32", 1), "xyz": ("float32", 3), "rem": ("float32", 1), "label": ("int32", 1),
             "color": ("float32", 3), "mask": ("float32", 1), "label_folded": ("float32", 1), "proj_x": ("int32", 1),
@@ -160,9 +129,17 @@ class Projector:
         h = C.c_void_p()
         _lib.check(self._lib.lt_projector_create(C.byref(h), idx), "lt_projector_create")
         self._h = h
+        self._applied = (None, None)   # (model, H) of the last call: what was held valid and told to lt_projector_set_*
 
     def project(self, clouds, fov_up, fov_down, H, W, new=True, remove=False, beam_angles=None, color_lut=None,
                 outputs=("range", "rem", "label"), out=None, stream=None, beam_table=None, sector=None, beam_azimuth=None):
+        from .config import TargetModel
+        return self._project(clouds, fov_up, fov_down, H, W, TargetModel(beam_table, sector, beam_azimuth, "Projector.project"),
+                             new, remove, beam_angles, color_lut, outputs, out, stream)
+
+    def _project(self, clouds, fov_up, fov_down, H, W, model, new=True, remove=False, beam_angles=None, color_lut=None,
+                 outputs=("range", "rem", "label"), out=None, stream=None):
+        """:meth:`project` for a :class:`~lidar_transfer_amd.config.TargetModel`"""
         import ctypes as C
 
         from . import _lib
@@ -205,42 +182,42 @@ class Projector:
                 setattr(im[k], name, t.data_ptr())
             res.append(o)
         lut = color_lut.to(torch.float32).contiguous() if color_lut is not None else None
-        beams = None
-        if beam_angles is not None and len(beam_angles):
-            beams = np.ascontiguousarray(beam_angles, dtype=np.float64)
+        beams, n_beams = None, 0
+        if model.rows is not None:   # Brad followed by halfw, n_beams == H
+            beams, n_beams = model.rows_ptr, int(H)
+        elif beam_angles is not None and len(beam_angles):
+            angles = np.ascontiguousarray(beam_angles, dtype=np.float64)
+            beams, n_beams = angles.ctypes.data_as(C.c_void_p), len(angles)
         st = torch.cuda.current_stream(self.device) if stream is None else stream
-        flags = (_lib.LT_PROJ_NEW if new else 0) | (_lib.LT_PROJ_REMOVE if remove else 0)
-        if beam_table is not None:   # Brad followed by halfw, n_beams == H
-            from ._chain import beam_rows_table
-            flags |= _lib.LT_PROJ_BEAM_ROWS
-            beams = beam_rows_table(beam_table)[2]
-        n_beams = 0 if beams is None else (int(H) if beam_table is not None else len(beams))
-        if sector is not None:       # set when it changes; the flag reads it
-            from ._chain import sector_pair
-            flags |= _lib.LT_PROJ_SECTOR
-            sec = tuple(float(v) for v in sector_pair(sector))
-            if sec != getattr(self, "_sector", None):
-                _lib.check(self._lib.lt_projector_set_sector(self._h, sec[0], sec[1]), "lt_projector_set_sector")
-                self._sector = sec
-        if beam_azimuth is not None:  # set when they change; the flag reads them
-            from ._chain import beam_azimuth_rad
-            if beam_table is None:
-                raise ValueError("Projector.project: beam_azimuth belongs to the beams of a beam_table")
-            flags |= _lib.LT_PROJ_BEAM_AZIMUTH
-            az = beam_azimuth_rad(beam_azimuth)
-            if getattr(self, "_beam_az", None) is None or not np.array_equal(az, self._beam_az):
-                _lib.check(self._lib.lt_projector_set_beam_azimuth(self._h, az.ctypes.data_as(C.POINTER(C.c_double)), len(az)),
-                           "lt_projector_set_beam_azimuth")
-                self._beam_az = az.copy()
+        flags = (_lib.LT_PROJ_NEW if new else 0) | (_lib.LT_PROJ_REMOVE if remove else 0) | model.proj_flags
+        self._apply(model, int(H))
         init = (0.0, -1.0, 0.0) if new else (-1.0, -1.0, -1.0)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.lt_range_projection_batch_dev(
                 self._h, n, cl, int(dt == torch.float64), float(fov_up), float(fov_down), int(H), int(W),
-                beams.ctypes.data_as(C.c_void_p) if beams is not None else None, n_beams, flags,
+                beams, n_beams, flags,
                 lut.data_ptr() if lut is not None else None, 0 if lut is None else int(lut.shape[0]), im, *init,
                 C.c_void_p(st.cuda_stream)), "lt_range_projection_batch_dev")
         self._keep = (keep, lut)  # inputs stay referenced until the next call (the kernels are queued, not finished)
         return res
+
+    def _apply(self, model, H):
+        """a model that is not the last call's: held against ``H``; its sector and its offsets set where they changed (the
+        flags read them)"""
+        import ctypes as C
+
+        from . import _lib
+        last, last_H = self._applied
+        if model is last and H == last_H:
+            return
+        model.validate(H, who="Projector.project")
+        if model.sector is not None and (last is None or model.sector != last.sector):
+            _lib.check(self._lib.lt_projector_set_sector(self._h, *model.sector_rad.tolist()), "lt_projector_set_sector")
+        az = model.azimuth_rad
+        if az is not None and (last is None or last.azimuth_rad is None or not np.array_equal(az, last.azimuth_rad)):
+            _lib.check(self._lib.lt_projector_set_beam_azimuth(self._h, az.ctypes.data_as(C.POINTER(C.c_double)), len(az)),
+                       "lt_projector_set_beam_azimuth")
+        self._applied = (model, H)
 
     def close(self):
         if getattr(self, "_h", None):

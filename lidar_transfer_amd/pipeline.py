@@ -313,14 +313,11 @@ class FusionScanPipeline:
     the target's frame (``lt_points_to_frame_dev`` on the chain's stream, hits only), ``endpoints_scene`` as rendered.
     Empty, ``None`` or the identity: nothing changes.
 
-    A target sensor with a beam table (``SensorModel.beam_table()``) needs nothing but its rays: pass
-    ``create_rays_device(..., beam_table=table)`` (with ``rot`` when it is mounted as well) as ``rays``.  The same holds for
-    a table whose beams carry azimuth offsets (``SensorModel.beam_azimuth()``): ``create_rays_device(..., beam_table=table,
-    beam_azimuth=offsets)``.
-
-    A target sensor with a horizontal sector (``SensorModel.sector()``) needs its rays,
-    ``create_rays_device(..., sector=sector)``, and -- for speed alone -- a bin grid at the sector's resolution:
-    ``grid=sector_grid(W, sector)`` (``raytracer.sector_grid``; ``grid`` goes to the ``RaySet``, ``None``: the image's rule)."""
+    A target sensor with a model of its own (``m = SensorModel.target_model()``: a beam table, a sector, azimuth offsets)
+    needs nothing but its rays -- pass ``create_rays_device(..., beam_table=m.beam_table, sector=m.sector,
+    beam_azimuth=m.beam_azimuth)`` (with ``rot`` when it is mounted as well) as ``rays`` -- and, for a sector and for speed
+    alone, a bin grid at the sector's resolution: ``grid=m.grid(W)`` (``grid`` goes to the ``RaySet``, ``None``: the image's
+    rule)."""
 
     def __init__(self, vol_bnds, voxel_size, fov_up, fov_down, rays, H, chains=3, device=None, merge=True,
                  label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None, grid=None):

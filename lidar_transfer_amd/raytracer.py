@@ -274,9 +274,8 @@ class RaySet:
     """A ray batch prepared for :meth:`Scene.render` (``lt_rayset`` in include/lidarhip.h): directions
     normalised like the reference (Vector3.h:73-89) and binned by azimuth x elevation.  One per sensor
     model; reuse it for every scan.  ``pose``: the [4, 4] pose of the sensor the rays were generated for (``None``: its own
-    frame), ``beam_table``: the beam table the rays were generated from (``None``: evenly spaced beams) and ``sector``: the
-    ``(center_deg, span_deg)`` the columns span (``None``: the full circle), ``beam_azimuth``: the per-beam azimuth offsets the
-    rays were generated with (``None``: none) -- only remembered, so that a chain handed a
+    frame), ``beam_table`` / ``sector`` / ``beam_azimuth``: the :class:`~lidar_transfer_amd.config.TargetModel` the rays were
+    generated from (``model``; its fields read as attributes) -- only remembered, so that a chain handed a
     shared ray set can tell whether it was built for its sensor.  ``grid``: ``(nb_az, nb_el)``, the size of the bin grid
     (``lt_rayset_create_grid_dev``; 0 = the image's own rule for that axis, ``None`` = ``(0, 0)``) -- any grid renders the same
     image, the fastest is the one whose bin centres the rays sit on: :func:`sector_grid` for a sector."""
@@ -284,13 +283,13 @@ class RaySet:
     def __init__(self, rays, H, exact_normalize=False, stream=None, pose=None, beam_table=None, sector=None, grid=None,
                  beam_azimuth=None):
         import torch
-        self.beam_azimuth = None if beam_azimuth is None else np.array(beam_azimuth, dtype=np.float64).reshape(-1)
-        self.sector = None if sector is None else (float(sector[0]), float(sector[1]))
+
+        from .config import TargetModel
+        self.model = TargetModel(beam_table, sector, beam_azimuth, "RaySet")
         self.grid = None if grid is None else (int(grid[0]), int(grid[1]))
         if self.grid is not None and min(self.grid) < 0:
             raise ValueError("grid: (nb_az, nb_el), both >= 0")
         self.pose = None if pose is None else np.array(pose, dtype=np.float64).reshape(4, 4)
-        self.beam_table = None if beam_table is None else np.array(beam_table, dtype=np.float64).reshape(-1)
         if not isinstance(rays, torch.Tensor) or rays.dtype != torch.float32 or not rays.is_contiguous() \
                 or not rays.is_cuda:
             raise ValueError("rays: contiguous float32 CUDA tensor [R, 3] expected")
@@ -310,6 +309,10 @@ class RaySet:
                                                                C.c_void_p(st.cuda_stream)), "lt_rayset_create_grid_dev")
             st.synchronize()
         self._h = h
+
+    beam_table = property(lambda self: self.model.beam_table)
+    sector = property(lambda self: self.model.sector)
+    beam_azimuth = property(lambda self: self.model.beam_azimuth)
 
     def close(self):
         if getattr(self, "_h", None):

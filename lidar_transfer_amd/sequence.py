@@ -107,14 +107,11 @@ class SequenceTransfer:
     YAML) copied next to the output once (lidar_deform.py:446-452).  A non-identity ``approach.transformation`` mounts the
     target sensor at a pose of its own (``Approach.mount()``; ``DeviceDeform(transformation=...)``): the output is in the
     target's frame, ``compare()`` against the source scan would mean nothing, so ``evaluate=None`` resolves to ``False`` and
-    ``evaluate=True`` raises; ``mounted`` tells.  A target ``SensorModel`` with ``beam_model: table`` brings its beam table
-    (``DeviceDeform(t_beam_table=...)``): the source scan is projected by the evenly spaced model and cannot be compared row
-    for row, so ``evaluate`` behaves as for a mounted target; ``beam_model`` tells.  A source sensor with a table is
-    refused.  A target ``SensorModel`` with ``azimuth_model: sector`` brings its sector (``DeviceDeform(t_sector=...)``): its
-    columns are not the source scan's full-circle columns, so ``evaluate`` behaves the same way; ``azimuth_model`` tells.  A
-    source sensor with a sector is refused.  A target table with ``beam_azimuth_offsets`` brings them
-    (``DeviceDeform(t_beam_azimuth=...)``); ``beam_azimuth`` holds them (``None``: none) and a source sensor with the key is
-    refused."""
+    ``evaluate=True`` raises; ``mounted`` tells.  A target ``SensorModel`` brings its ``TargetModel``
+    (``SensorModel.target_model()``, kept as ``target_model``; its fields ``beam_table``, ``sector`` and ``beam_azimuth`` are
+    attributes here too, ``None``: none) to every chain's ``DeviceDeform``.  With a beam table (``beam_model`` tells) the source
+    scan, projected by the evenly spaced model, cannot be compared row for row, with a sector (``azimuth_model`` tells) not
+    column for column: ``evaluate`` then behaves as for a mounted target.  A source sensor with any of the three is refused."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -125,17 +122,14 @@ class SequenceTransfer:
         if int(chains) < 1:
             raise ValueError("chains: at least one")
         self.approach, self.adaption = approach, approach.adaption
-        from .config import refuse_source_beam_azimuth, refuse_source_sector, refuse_source_table
-        refuse_source_table(source_sensor)
-        refuse_source_sector(source_sensor)
-        refuse_source_beam_azimuth(source_sensor)
+        from .config import TargetModel, refuse_source_models
+        refuse_source_models(source_sensor)
         self.source_sensor, self.target_sensor = sensor_tuple(source_sensor), sensor_tuple(target_sensor)
-        # (sensor_tuple drops the table; ValueError on one that cannot be used)
-        self.beam_table = target_sensor.beam_table() if hasattr(target_sensor, "beam_table") else None
-        self.beam_model = "linear" if self.beam_table is None else "table"
-        self.sector = target_sensor.sector() if hasattr(target_sensor, "sector") else None
-        self.azimuth_model = "full" if self.sector is None else "sector"
-        self.beam_azimuth = target_sensor.beam_azimuth() if hasattr(target_sensor, "beam_azimuth") else None
+        # (sensor_tuple drops the model; ValueError on one that cannot be used; a plain tuple has none: the empty model)
+        m = self.target_model = getattr(target_sensor, "target_model", TargetModel)()
+        self.beam_table, self.sector, self.beam_azimuth = m.beam_table, m.sector, m.beam_azimuth
+        self.beam_model = "linear" if m.beam_table is None else "table"
+        self.azimuth_model = "full" if m.sector is None else "sector"
         self.chains = 1 if self.adaption == "cp" else int(chains)     # `cp` always runs on one chain
         self.fusion, self.out_dir = fusion, out_dir
         self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
@@ -180,19 +174,15 @@ class SequenceTransfer:
                 self.vol_bnds = self._configured_bnds.copy()   # the ONE array of the sequence, kept current
                 self._mm = MergeMeshState(self.vol_bnds, approach.voxel_size, idx)
             rayset = None
+            every = dict(beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
+                         transformation=self.mount, t_beam_table=m.beam_table, t_sector=m.sector, t_beam_azimuth=m.beam_azimuth)
             for c in range(self.chains):
                 if self.adaption == "cp":
-                    dd = DeviceDeform(self.source_sensor, self.target_sensor, None, beam_angles=beams,
-                                      preserve_float=approach.preserve_float, device=idx, fusion=fusion,
-                                      transformation=self.mount, t_beam_table=self.beam_table,
-                                      t_sector=self.sector, t_beam_azimuth=self.beam_azimuth)
+                    dd = DeviceDeform(self.source_sensor, self.target_sensor, None, **every)
                 else:
                     dd = DeviceDeform(self.source_sensor, self.target_sensor,
                                       None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
-                                      beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
-                                      mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm,
-                                      transformation=self.mount, t_beam_table=self.beam_table,
-                                      t_sector=self.sector, t_beam_azimuth=self.beam_azimuth)
+                                      mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm, **every)
                     rayset = dd.rayset
                 ch = dict(dd=dd, ev=None, q=None, thread=None,
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))

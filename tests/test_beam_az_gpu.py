@@ -641,7 +641,8 @@ def test_a_table_target_without_the_key_and_with_zero_offsets_change_nothing(ada
                dict(t_beam_azimuth=np.zeros(32))):
         bnds = None if adaption == "cp" else a.voxel_bounds.copy()
         with DeviceDeform(ev.SOURCE, SEQ_TARGET, bnds, a.voxel_size, mesh_volume=adaption == "mesh", t_beam_table=bc.VLP32C, **kw) as dd:
-            assert dd.t_beam_azimuth is None and dd._t_az is None and dd._t_az_dev is None
+            assert dd.t_beam_azimuth is None and dd.t_model.beam_azimuth is None and dd.t_model.azimuth_rad is None \
+                and dd._t_az_dev is None
             assert dd.rayset is None or dd.rayset.beam_azimuth is None
             assert getattr(dd.projector, "_beam_az", None) is None
             params.append(None if dd.rayset is None else btg._rayset_params(dd.rayset))
