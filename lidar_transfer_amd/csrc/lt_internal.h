@@ -26,18 +26,16 @@ int lt_cu_count(int device);
   } while (0)
 
 // The instantiation of a sensor-model kernel (projection, reverse projection) for a beam table (`rows`) and a horizontal
-// sector: LAUNCH(BEAMS, SECTOR) is a macro that holds the kernel's one launch statement, expanded with the two as literals.
-#define LT_FOR_MODEL(rows, sector, LAUNCH)                         \
-  do {                                                             \
-    if (rows) { if (sector) LAUNCH(1, 1); else LAUNCH(1, 0); }     \
-    else { if (sector) LAUNCH(0, 1); else LAUNCH(0, 0); }          \
-  } while (0)
-// The same with per-beam azimuth offsets (`az`; they come with a beam table only): LAUNCH_AZ(SECTOR) holds the launch of the
-// kernel's <BEAMS = 1, SECTOR, AZ = 1> instantiation; without offsets the models above, from the launch they had.
-#define LT_FOR_MODEL_AZ(rows, sector, az, LAUNCH, LAUNCH_AZ)       \
-  do {                                                             \
-    if (az) { if (sector) LAUNCH_AZ(1); else LAUNCH_AZ(0); }       \
-    else LT_FOR_MODEL(rows, sector, LAUNCH);                       \
+// sector, with or without per-beam azimuth offsets (`az`; they come with a beam table only): LAUNCH(BEAMS, SECTOR, AZ) is a
+// macro that holds the kernel's one launch statement, expanded with the three as literals -- (1, S, 1) with a table and
+// offsets, else (B, S, 0): six instantiations per kernel.  `az` without `rows` is ignored (no caller passes it: model_table
+// and create_rays_launch admit offsets with a table only).  A kernel without offsets (the reverse projection) passes `false`
+// and ignores AZ.
+#define LT_FOR_MODEL(rows, sector, az, LAUNCH)                           \
+  do {                                                                   \
+    if ((rows) && (az)) { if (sector) LAUNCH(1, 1, 1); else LAUNCH(1, 0, 1); } \
+    else if (rows) { if (sector) LAUNCH(1, 1, 0); else LAUNCH(1, 0, 0); } \
+    else { if (sector) LAUNCH(0, 1, 0); else LAUNCH(0, 0, 0); }          \
   } while (0)
 // doubles of the sensor model a projection uploads, at most: a table of 511 rows (Brad, halfw, the field of view), its
 // azimuth offsets and a sector

@@ -71,10 +71,10 @@ static int reverse_launch(const float* range_img, const void* proj_x, const void
 #define LT_REVERSE(P, B, S)                                                                                                  \
   hipLaunchKernelGGL((k_reverse<P, B, S>), dim3((n + 255) / 256), dim3(256), 0, st, range_img, (const P*)proj_x,             \
                      (const P*)proj_y, n, (double)W, (double)H, fov, fabs(fd), Brad, yc, span, back_points)
-#define LT_REVERSE_F64(B, S) LT_REVERSE(double, B, S)
-#define LT_REVERSE_I32(B, S) LT_REVERSE(int, B, S)
-  if (coords_are_f64) LT_FOR_MODEL(rows, sector, LT_REVERSE_F64);
-  else LT_FOR_MODEL(rows, sector, LT_REVERSE_I32);
+#define LT_REVERSE_F64(B, S, AZ) LT_REVERSE(double, B, S)  // (offsets: k_reverse_az, below)
+#define LT_REVERSE_I32(B, S, AZ) LT_REVERSE(int, B, S)
+  if (coords_are_f64) LT_FOR_MODEL(rows, sector, false, LT_REVERSE_F64);
+  else LT_FOR_MODEL(rows, sector, false, LT_REVERSE_I32);
 #undef LT_REVERSE
 #undef LT_REVERSE_F64
 #undef LT_REVERSE_I32

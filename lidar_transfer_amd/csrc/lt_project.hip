@@ -7,10 +7,10 @@
 // and create_rays (auxiliary/laserscan.py:1092-1119) as a device kernel.
 //
 // Semantics: the closest point of a cell wins; among equal depths the LOWEST point index wins --
-// exactly the `_new` loop (`depth[i] < range_image[...]`, laserscan.py:376) and one valid outcome of
-// the unstable argsort of the old variant.  Implemented as two order-independent atomic passes:
-// atomicMin of the depth bits per cell (positive IEEE doubles order like unsigned integers), then
-// atomicMin of the point index among the points that equal the cell minimum.
+// the `_new` loop (`depth[i] < range_image[...]`, laserscan.py:376) and one valid outcome of the
+// unstable argsort of the old variant.  Implemented as ONE order-independent atomicMin per kept point
+// of a 64-bit key per cell that holds the depth and the index (`The key`, below); every entry point
+// -- one cloud or a batch -- runs the same kernels.
 //
 // Arithmetic follows numpy's dtype rules for the array the reference holds: float32 when the scan
 // was read from file (laserscan.py:131-136), float64 after a pose was applied (laserscan.py:98-104).
@@ -22,141 +22,6 @@
 #include <algorithm>
 #include <mutex>
 #include <new>
-
-#define LT_EMPTY_IDX 0x7F7F7F7F  // hipMemset(0x7F) pattern: larger than any point index
-
-// pass 1: project, z-min of the depth bits, per-workgroup count of kept points (BEAMS, SECTOR, AZ and `beams`: project_model)
-template <typename T, int BEAMS, int SECTOR, int AZ = 0>
-__global__ __launch_bounds__(256) void k_project(const T* __restrict__ pts, int n, T pi_t, T abs_fov_down, T fov,
-                                                 int H, int W, const double* __restrict__ beams, int n_beams,
-                                                 int drop_zero, int drop_outside, int round_key,
-                                                 int* __restrict__ cell,
-                                                 double* __restrict__ depth_d, T* __restrict__ xf,
-                                                 T* __restrict__ yf, unsigned long long* __restrict__ cellmin,
-                                                 int* __restrict__ blockcount) {
-  __shared__ int wcnt[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  bool keep = false;
-  if (i < n) {
-    const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-    const proj_out<T> o = project_model<T, BEAMS, SECTOR, AZ>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams,
-                                                              drop_zero, drop_outside);
-    cell[i] = o.cell;
-    depth_d[i] = (double)o.depth;
-    xf[i] = o.xf;
-    yf[i] = o.yf;
-    keep = o.cell >= 0;
-    // `_new` keeps its running minimum in a float32 image (laserscan.py:366, :376): the cell minimum is
-    // taken over the float32-ROUNDED depths there
-    const double key = round_key ? (double)(float)o.depth : (double)o.depth;
-    if (keep) atomicMin(&cellmin[o.cell], (unsigned long long)__double_as_longlong(key));
-  }
-  const unsigned long long m = __ballot(keep);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) blockcount[blockIdx.x] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-}
-
-// pass 2: compacted index of every kept point (stable), compacted per-point outputs, index z-min.
-// Every workgroup sums the kept-counts of the workgroups before it itself (n / 256 integers from L2: cheaper
-// than a scan kernel between the two passes); the last one also leaves the total in blockcount[gridDim.x].
-template <typename T>
-__global__ __launch_bounds__(256) void k_assign(const T* __restrict__ pts, const float* __restrict__ rem,
-                                                const unsigned* __restrict__ label, int n, int W,
-                                                const int* __restrict__ cell, const double* __restrict__ depth_d,
-                                                const T* __restrict__ xf, const T* __restrict__ yf,
-                                                const unsigned long long* __restrict__ cellmin,
-                                                int* __restrict__ blockcount, int round_key,
-                                                int* __restrict__ idxmin, int* __restrict__ idxlast,
-                                                int* __restrict__ orig_of, T* __restrict__ pts_k,
-                                                float* __restrict__ rem_k, unsigned* __restrict__ label_k,
-                                                T* __restrict__ depth_k, int* __restrict__ px_k,
-                                                int* __restrict__ py_k, T* __restrict__ xf_k, T* __restrict__ yf_k) {
-  __shared__ int wcnt[4], wbefore[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = i < n ? cell[i] : -1;
-  const bool keep = c >= 0;
-  const unsigned long long m = __ballot(keep);
-  int before = 0;
-  for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) before += blockcount[b];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-  if (lane == 0) { wcnt[wave] = __popcll(m); wbefore[wave] = before; }
-  __syncthreads();
-  int off = (wbefore[0] + wbefore[1]) + (wbefore[2] + wbefore[3]);
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
-    blockcount[gridDim.x] = off + (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);  // number of kept points
-  for (int w = 0; w < wave; ++w) off += wcnt[w];
-  if (!keep) return;
-  const int k = off + __popcll(m & ((1ull << lane) - 1ull));
-  orig_of[k] = i;
-  const double d = depth_d[i];
-  if (pts_k) {
-    pts_k[3 * (size_t)k] = pts[3 * (size_t)i];
-    pts_k[3 * (size_t)k + 1] = pts[3 * (size_t)i + 1];
-    pts_k[3 * (size_t)k + 2] = pts[3 * (size_t)i + 2];
-  }
-  if (rem_k && rem) rem_k[k] = rem[i];
-  if (label_k && label) label_k[k] = label[i];
-  if (depth_k) depth_k[k] = (T)d;
-  if (px_k) px_k[k] = c % W;
-  if (py_k) py_k[k] = c / W;
-  if (xf_k) xf_k[k] = xf[i];
-  if (yf_k) yf_k[k] = yf[i];
-  const double key = round_key ? (double)(float)d : d;
-  const unsigned long long mbits = cellmin[c];
-  if ((unsigned long long)__double_as_longlong(key) == mbits) {
-    atomicMin(&idxmin[c], k);
-    // `depth[i] < range_image[cell]` compares a float64 depth with the float32-rounded minimum: every
-    // later point of the minimum's float32 bucket that rounded UP replaces the incumbent (see k_resolve)
-    if (round_key && d < __longlong_as_double((long long)mbits)) atomicMax(&idxlast[c], k);
-  }
-}
-
-// pass 3: one thread per cell gathers the winner (laserscan.py:283-292, :376-382, :645-649) and re-arms the
-// cell's three z-min words for the next projection (no memsets between calls)
-template <typename T>
-__global__ __launch_bounds__(256) void k_resolve(const T* __restrict__ pts, const float* __restrict__ rem,
-                                                 const unsigned* __restrict__ label, const double* __restrict__ depth_d,
-                                                 unsigned long long* __restrict__ cellmin,
-                                                 int* __restrict__ idxmin, int* __restrict__ idxlast,
-                                                 const int* __restrict__ orig_of, int ncells, const float* __restrict__ lut, int lut_len,
-                                                 float range_init, float rem_init, float xyz_init,
-                                                 int* __restrict__ idx_img, float* __restrict__ range_img,
-                                                 float* __restrict__ xyz_img, float* __restrict__ rem_img,
-                                                 int* __restrict__ label_img, float* __restrict__ color_img,
-                                                 float* __restrict__ mask_img) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncells) return;
-  // winner of the reference's sequential loop: the first point of the minimum bucket, unless later points
-  // of that bucket lie below the float32 minimum -- then the last of those (idxlast is -1 otherwise and
-  // always for float32 input, where rounding is the identity)
-  const int first = idxmin[c], last = idxlast[c];
-  cellmin[c] = ~0ull;
-  idxmin[c] = LT_EMPTY_IDX;
-  idxlast[c] = -1;
-  const int k = (last >= 0 && last != first) ? last : first;
-  const bool has = first != LT_EMPTY_IDX;
-  const int i = has ? orig_of[k] : 0;
-  if (idx_img) idx_img[c] = has ? k : -1;
-  if (range_img) range_img[c] = has ? (float)depth_d[i] : range_init;
-  if (xyz_img) {
-    xyz_img[3 * (size_t)c] = has ? (float)pts[3 * (size_t)i] : xyz_init;
-    xyz_img[3 * (size_t)c + 1] = has ? (float)pts[3 * (size_t)i + 1] : xyz_init;
-    xyz_img[3 * (size_t)c + 2] = has ? (float)pts[3 * (size_t)i + 2] : xyz_init;
-  }
-  if (rem_img) rem_img[c] = (has && rem) ? rem[i] : rem_init;
-  const unsigned lab = (has && label) ? label[i] : 0u;
-  if (label_img) label_img[c] = (int)lab;
-  if (color_img) {
-    const bool ok = has && lut && lab < (unsigned)lut_len;
-    color_img[3 * (size_t)c] = ok ? lut[3 * (size_t)lab] : 0.f;
-    color_img[3 * (size_t)c + 1] = ok ? lut[3 * (size_t)lab + 1] : 0.f;
-    color_img[3 * (size_t)c + 2] = ok ? lut[3 * (size_t)lab + 2] : 0.f;
-  }
-  if (mask_img) mask_img[c] = (has && k > 0) ? 1.f : 0.f;  // proj_idx > 0 (sic, laserscan.py:292)
-}
 
 // ---- create_rays (laserscan.py:1092-1119): float64 trigonometry, cast to float32 last ---------------------
 // One body for every target sensor.  The three choices are template arguments: as flags read at run time they cost the plain
@@ -224,25 +89,16 @@ static int create_rays_launch(const double* beams_deg, const double* az_deg, dou
       e = hipMemcpyAsync(d_beams + H, az_deg, (size_t)H * sizeof(double), hipMemcpyHostToDevice, st);
   }
   if (e == hipSuccess) {
-#define LT_RAYS(B, S, P)                                                                                              \
-  hipLaunchKernelGGL((k_create_rays<B, S, P>), grid, block, 0, st, (const double*)d_beams, fov_up, fov_down, H, W, center_deg, \
-                     span_deg, R, rays)
-#define LT_RAYS_POSED(B, S) LT_RAYS(B, S, 1)
-#define LT_RAYS_UNPOSED(B, S) LT_RAYS(B, S, 0)
-#define LT_RAYS_AZ(S, P)                                                                                       \
-  hipLaunchKernelGGL((k_create_rays<1, S, P, 1>), grid, block, 0, st, (const double*)d_beams, fov_up, fov_down, H, W, \
+#define LT_RAYS(B, S, P, AZ)                                                                                          \
+  hipLaunchKernelGGL((k_create_rays<B, S, P, AZ>), grid, block, 0, st, (const double*)d_beams, fov_up, fov_down, H, W, \
                      center_deg, span_deg, R, rays)
-#define LT_RAYS_AZ_POSED(S) LT_RAYS_AZ(S, 1)
-#define LT_RAYS_AZ_UNPOSED(S) LT_RAYS_AZ(S, 0)
-    const bool az = beams_deg && az_deg;
-    if (rot) LT_FOR_MODEL_AZ(beams_deg != nullptr, sec != nullptr, az, LT_RAYS_POSED, LT_RAYS_AZ_POSED);
-    else LT_FOR_MODEL_AZ(beams_deg != nullptr, sec != nullptr, az, LT_RAYS_UNPOSED, LT_RAYS_AZ_UNPOSED);
+#define LT_RAYS_POSED(B, S, AZ) LT_RAYS(B, S, 1, AZ)
+#define LT_RAYS_UNPOSED(B, S, AZ) LT_RAYS(B, S, 0, AZ)
+    if (rot) LT_FOR_MODEL(beams_deg != nullptr, sec != nullptr, az_deg != nullptr, LT_RAYS_POSED);
+    else LT_FOR_MODEL(beams_deg != nullptr, sec != nullptr, az_deg != nullptr, LT_RAYS_UNPOSED);
 #undef LT_RAYS
 #undef LT_RAYS_POSED
 #undef LT_RAYS_UNPOSED
-#undef LT_RAYS_AZ
-#undef LT_RAYS_AZ_POSED
-#undef LT_RAYS_AZ_UNPOSED
     e = hipGetLastError();
   }
   if (beams_deg) {
@@ -374,188 +230,25 @@ static bool beam_azimuth_ok(const char* who, const double* az, int n) {
   return ok;
 }
 
-// ---- host orchestration -------------------------------------------------------------------------------------
-namespace {
-struct proj_ws {
-  int device = -1;
-  size_t cap_n = 0, cap_cells = 0;
-  int* cell = nullptr;
-  double* depth_d = nullptr;
-  void* xf = nullptr;
-  void* yf = nullptr;
-  int* blockcount = nullptr;
-  int* orig_of = nullptr;
-  unsigned long long* cellmin = nullptr;
-  int* idxmin = nullptr;
-  int* idxlast = nullptr;
-  double* beams = nullptr;
-  bool armed = false;  // cellmin / idxmin / idxlast hold their empty patterns (k_resolve leaves them so)
-};
-std::mutex g_pmu;
-proj_ws g_pws;
-double g_sector[2] = {0.0, 0.0};  // lt_range_projection_set_sector
-bool g_sector_set = false;
-double g_az[511];                 // lt_range_projection_set_beam_azimuth
-int g_az_n = 0;
-
-void pws_free(proj_ws& w) {
-  void* ps[] = {w.cell, w.depth_d, w.xf, w.yf, w.blockcount, w.orig_of, w.cellmin, w.idxmin, w.idxlast, w.beams};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  w = proj_ws();
-}
-
-int pws_reserve(proj_ws& w, int device, size_t n, size_t cells) {
-  if (w.device == device && n <= w.cap_n && cells <= w.cap_cells) return LT_OK;
-  if (w.device >= 0) {
-    LT_HIP(hipDeviceSynchronize());
-    pws_free(w);
-  }
-  const size_t cn = n + n / 4 + 1024, cc = cells + 1024;
-  LT_HIP(hipMalloc((void**)&w.cell, cn * sizeof(int)));
-  LT_HIP(hipMalloc((void**)&w.depth_d, cn * sizeof(double)));
-  LT_HIP(hipMalloc(&w.xf, cn * sizeof(double)));
-  LT_HIP(hipMalloc(&w.yf, cn * sizeof(double)));
-  LT_HIP(hipMalloc((void**)&w.blockcount, (cn / 256 + 2) * sizeof(int)));
-  LT_HIP(hipMalloc((void**)&w.orig_of, cn * sizeof(int)));
-  LT_HIP(hipMalloc((void**)&w.cellmin, cc * sizeof(unsigned long long)));
-  LT_HIP(hipMalloc((void**)&w.idxmin, cc * sizeof(int)));
-  LT_HIP(hipMalloc((void**)&w.idxlast, cc * sizeof(int)));
-  LT_HIP(hipMalloc((void**)&w.beams, LT_MODEL_DOUBLES * sizeof(double)));
-  w.device = device;
-  w.cap_n = cn;
-  w.cap_cells = cc;
-  return LT_OK;
-}
-
-template <typename T>
-int run_projection(proj_ws& w, const T* pts, const float* rem, const unsigned* label, int n, double fov_up_deg,
-                   double fov_down_deg, int H, int W, int n_beams, unsigned flags, const float* lut, int lut_len,
-                   T* pts_k, float* rem_k, unsigned* label_k, T* depth_k, int* px_k, int* py_k, T* xf_k, T* yf_k,
-                   int* idx_img, float* range_img, float* xyz_img, float* rem_img, int* label_img, float* color_img,
-                   float* mask_img, float range_init, float rem_init, float xyz_init, int* n_kept, hipStream_t st) {
-  // laser parameters exactly as laserscan.py:207-209 (python floats), then rounded once to the array dtype
-  const double fu = fov_up_deg / 180.0 * M_PI, fd = fov_down_deg / 180.0 * M_PI;
-  const double fov = fabs(fd) + fabs(fu);
-  const int cells = H * W;
-  const int nb = (n + 255) / 256;
-  if (!w.armed) {  // first use of the workspace, or the previous call failed half way
-    LT_HIP(hipMemsetAsync(w.cellmin, 0xFF, w.cap_cells * sizeof(unsigned long long), st));
-    LT_HIP(hipMemsetAsync(w.idxmin, 0x7F, w.cap_cells * sizeof(int), st));
-    LT_HIP(hipMemsetAsync(w.idxlast, 0xFF, w.cap_cells * sizeof(int), st));
-  }
-  w.armed = false;
-  const int round_key = (flags & LT_PROJ_NEW) ? 1 : 0;
-  if (n > 0) {
-    const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0, sector = (flags & LT_PROJ_SECTOR) != 0;
-    const bool azimuth = (flags & LT_PROJ_BEAM_AZIMUTH) != 0;
-    // rows and sector go with LT_PROJ_NEW | LT_PROJ_REMOVE only: both drops
-    const int drop_zero = (rows || sector || (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW))) ? 1 : 0;
-    const int drop_outside = (rows || sector || (flags & LT_PROJ_REMOVE)) ? 1 : 0;
-#define LT_PROJECT(B, S)                                                                                                   \
-  hipLaunchKernelGGL((k_project<T, B, S>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,          \
-                     (const double*)w.beams, n_beams, drop_zero, drop_outside, round_key, w.cell, w.depth_d, (T*)w.xf,      \
-                     (T*)w.yf, w.cellmin, w.blockcount)
-#define LT_PROJECT_AZ(S)                                                                                                   \
-  hipLaunchKernelGGL((k_project<T, 1, S, 1>), dim3(nb), dim3(256), 0, st, pts, n, (T)M_PI, (T)fabs(fd), (T)fov, H, W,       \
-                     (const double*)w.beams, n_beams, drop_zero, drop_outside, round_key, w.cell, w.depth_d, (T*)w.xf,      \
-                     (T*)w.yf, w.cellmin, w.blockcount)
-    LT_FOR_MODEL_AZ(rows, sector, azimuth, LT_PROJECT, LT_PROJECT_AZ);
-#undef LT_PROJECT
-#undef LT_PROJECT_AZ
-    hipLaunchKernelGGL(k_assign<T>, dim3(nb), dim3(256), 0, st, pts, rem, label, n, W, (const int*)w.cell,
-                       (const double*)w.depth_d, (const T*)w.xf, (const T*)w.yf,
-                       (const unsigned long long*)w.cellmin, w.blockcount, round_key, w.idxmin,
-                       w.idxlast, w.orig_of, pts_k,
-                       rem_k, label_k, depth_k, px_k, py_k, xf_k, yf_k);
-  }
-  hipLaunchKernelGGL(k_resolve<T>, dim3((cells + 255) / 256), dim3(256), 0, st, pts, rem, label,
-                     (const double*)w.depth_d, w.cellmin, w.idxmin, w.idxlast, (const int*)w.orig_of,
-                     cells, lut, lut_len,
-                     range_init, rem_init, xyz_init, idx_img, range_img, xyz_img, rem_img, label_img, color_img,
-                     mask_img);
-  LT_HIP(hipGetLastError());
-  int kept = 0;
-  if (n > 0) LT_HIP(hipMemcpyAsync(&kept, w.blockcount + nb, sizeof(int), hipMemcpyDeviceToHost, st));
-  LT_HIP(hipStreamSynchronize(st));
-  w.armed = true;
-  if (n_kept) *n_kept = kept;
-  return LT_OK;
-}
-}  // namespace
-
-extern "C" int lt_range_projection_set_sector(double yaw_center, double span) {
-  if (span != 0.0 && !sector_ok("lt_range_projection_set_sector", yaw_center, span)) return LT_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lock(g_pmu);
-  g_sector[0] = yaw_center;
-  g_sector[1] = span;
-  g_sector_set = span != 0.0;
-  return LT_OK;
-}
-
-extern "C" int lt_range_projection_set_beam_azimuth(const double* az_rad, int H) {
-  if (!beam_azimuth_ok("lt_range_projection_set_beam_azimuth", az_rad, H)) return LT_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lock(g_pmu);
-  g_az_n = az_rad ? H : 0;
-  if (g_az_n > 0) memcpy(g_az, az_rad, (size_t)H * sizeof(double));
-  return LT_OK;
-}
-
-extern "C" int lt_range_projection_dev(const void* points, int is_f64, const float* rem, const unsigned* label,
-                                       int n, double fov_up, double fov_down, int H, int W,
-                                       const double* beam_angles, int n_beams, unsigned flags,
-                                       const float* color_lut, int lut_len, void* points_kept, float* rem_kept,
-                                       unsigned* label_kept, void* depth_kept, int* proj_x_kept, int* proj_y_kept,
-                                       void* proj_xf_kept, void* proj_yf_kept, int* idx_img, float* range_img,
-                                       float* xyz_img, float* rem_img, int* label_img, float* color_img,
-                                       float* mask_img, float range_init, float rem_init, float xyz_init,
-                                       int* n_kept, void* stream) {
-  if (n < 0 || H <= 0 || W <= 0 || (n > 0 && !points) || n_beams < 0 || n_beams > 1024 ||
-      (n_beams > 0 && !beam_angles)) {
-    lt_set_error("lt_range_projection: invalid argument (n=%d H=%d W=%d n_beams=%d)", n, H, W, n_beams);
-    return LT_ERR_INVALID_ARG;
-  }
-  double tab[LT_MODEL_DOUBLES];
-  std::lock_guard<std::mutex> lock(g_pmu);
-  const int n_tab = model_table("lt_range_projection", beam_angles, n_beams, flags, fov_up, fov_down, H,
-                                g_sector_set ? g_sector : nullptr, g_az_n > 0 ? g_az : nullptr, g_az_n, tab);
-  if (n_tab < 0) return LT_ERR_INVALID_ARG;
-  int dev = 0;
-  LT_HIP(hipGetDevice(&dev));
-  LT_CHECK(pws_reserve(g_pws, dev, (size_t)n, (size_t)H * W));
-  hipStream_t st = (hipStream_t)stream;
-  if (n_tab > 0)  // (run_projection waits for the stream before `tab` goes out of scope)
-    LT_HIP(hipMemcpyAsync(g_pws.beams, tab, n_tab * sizeof(double), hipMemcpyHostToDevice, st));
-  if (is_f64)
-    return run_projection<double>(g_pws, (const double*)points, rem, label, n, fov_up, fov_down, H, W, n_beams, flags,
-                                  color_lut, lut_len, (double*)points_kept, rem_kept, label_kept, (double*)depth_kept,
-                                  proj_x_kept, proj_y_kept, (double*)proj_xf_kept, (double*)proj_yf_kept, idx_img,
-                                  range_img, xyz_img, rem_img, label_img, color_img, mask_img, range_init, rem_init,
-                                  xyz_init, n_kept, st);
-  return run_projection<float>(g_pws, (const float*)points, rem, label, n, fov_up, fov_down, H, W, n_beams, flags,
-                               color_lut, lut_len, (float*)points_kept, rem_kept, label_kept, (float*)depth_kept,
-                               proj_x_kept, proj_y_kept, (float*)proj_xf_kept, (float*)proj_yf_kept, idx_img,
-                               range_img, xyz_img, rem_img, label_img, color_img, mask_img, range_init, rem_init,
-                               xyz_init, n_kept, st);
-}
-
-// ---- batched, synchronisation-free projection (lt_range_projection_batch_dev) ------------------------------------------
-// The `number_of_scans` clouds of one output scan (laserscan.py:874-881: do_range_projection_new + do_label_projection_new
-// per scan) in ONE launch sequence on the caller's stream, nothing read back by the host:
-//   k_pb_project   a thread per point of every cloud: the reference's per-point expressions (project_point, above) and ONE
-//                  64-bit atomicMin per kept point -- no per-point temporaries are written (the single-cloud call stores
-//                  cell / depth / xf / yf per point: 28 B written and read again per point);
+// ---- the projection: up to LT_PB_MAX clouds per launch sequence, nothing read back by the host ---------------------------
+// lt_range_projection_batch_dev projects the `number_of_scans` clouds of one output scan (laserscan.py:874-881:
+// do_range_projection_new + do_label_projection_new per scan) in ONE launch sequence on the caller's stream;
+// lt_range_projection_dev is the same sequence for one cloud, plus the compaction of its kept points:
+//   k_pb_project   a thread per point of every cloud: the reference's per-point expressions (project_model, lt_projpoint.h)
+//                  and ONE 64-bit atomicMin per kept point -- no per-point temporaries are written;
 //   [k_pb_assign]  only for the OLD variant on float64 clouds, whose order key (a float64 depth) leaves no room for the index
-//   [k_pb_prefix]  only when an output needs the numbering of the KEPT points (idx / mask images, proj_x .. images, n_kept)
+//   [k_pb_prefix]  only when an output needs the numbering of the KEPT points (idx / mask images, proj_x .. images, n_kept,
+//                  the compaction)
 //   k_pb_resolve   a thread per cell of every image: decodes the winner, RE-COMPUTES its projection from the point itself
 //                  (the same deterministic function), gathers remission / label / colour, writes the images and re-arms the
-//                  cell's key for the next call (no memsets between calls).
+//                  cell's key for the next call (no memsets between calls)
+//   [k_pb_compact] lt_range_projection_dev only: a thread per point writes the kept points' rows, in input order.
 // The key.  `_new` keeps its running minimum in a float32 image and replaces when `depth[i] < image` (laserscan.py:366, :376):
 // the winner is the first point of the minimum's float32 bucket unless points of that bucket lie BELOW the float32 value
 // (rounded up) -- then the last of those.  hi word = float32 bits of the depth (positive floats order like unsigned
 // integers); lo word = 0x7fffffff - index for a rounded-up point (they beat the others, the highest index first),
 // 0x80000000 | index otherwise (lowest index first): one atomicMin yields exactly that point.  float32 clouds never round.
-// The OLD variant on float32 clouds: closest point, lowest index among equal depths (k_project's rule) -- the same key.
+// The OLD variant on float32 clouds: closest point, lowest index among equal depths -- the same key.
 #define LT_PB_MAX 8
 
 struct pb_cloud {
@@ -784,6 +477,46 @@ __global__ __launch_bounds__(256) void k_pb_resolve(pb_args A, int blocks_per_cl
   if (c.yf_img) ((T*)c.yf_img)[cell] = o.yf;
 }
 
+// The per-point outputs of lt_range_projection_dev, each [n_kept] rows or NULL.  The kernel's own argument: pb_args is the
+// hot path's (every scan of a sequence) and stays as small as it is.
+template <typename T>
+struct pb_kept { T* pts; float* rem; unsigned* label; T* depth; int* px; int* py; T* xf; T* yf; };
+
+// One cloud's kept points, compacted in input order (laserscan.py:265-281: points, remissions, labels, depth, proj_x / proj_y
+// and their float forms after remove_points), a thread per input point, after k_pb_prefix.  Kept point i goes to row
+// k = kept points before its wave + kept points before it in its wave (k_pb_resolve's numbering); its depth and pixel are
+// computed again from the point itself, like the winner's in k_pb_resolve.  Rows at and beyond n_kept are not written.
+template <typename T, int BEAMS, int SECTOR, int AZ>
+__global__ __launch_bounds__(256) void k_pb_compact(const T* __restrict__ pts, const float* __restrict__ rem,
+                                                    const unsigned* __restrict__ label, int n,
+                                                    const unsigned long long* __restrict__ keep, const int* __restrict__ wprefix,
+                                                    pb_kept<T> out, T pi_t, T abs_fov_down, T fov, int H, int W,
+                                                    const double* __restrict__ beams, int n_beams, int drop_zero,
+                                                    int drop_outside) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long m = keep[i >> 6];
+  if (!((m >> (i & 63)) & 1ull)) return;
+  const int k = wprefix[i >> 6] + __popcll(m & ((1ull << (i & 63)) - 1ull));
+  const T x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+  if (out.pts) {
+    out.pts[3 * (size_t)k] = x;
+    out.pts[3 * (size_t)k + 1] = y;
+    out.pts[3 * (size_t)k + 2] = z;
+  }
+  if (out.rem && rem) out.rem[k] = rem[i];
+  if (out.label && label) out.label[k] = label[i];
+  if (out.depth || out.px || out.py || out.xf || out.yf) {
+    const proj_out<T> o = project_model<T, BEAMS, SECTOR, AZ>(x, y, z, pi_t, abs_fov_down, fov, H, W, beams, n_beams,
+                                                              drop_zero, drop_outside);
+    if (out.depth) out.depth[k] = o.depth;
+    if (out.px) out.px[k] = o.cell % W;
+    if (out.py) out.py[k] = o.cell / W;
+    if (out.xf) out.xf[k] = o.xf;
+    if (out.yf) out.yf[k] = o.yf;
+  }
+}
+
 struct lt_projector {
   int device = 0;
   size_t cap_n = 0, cap_cells = 0;          // per cloud slot
@@ -847,56 +580,86 @@ int pj_reserve(lt_projector* p, size_t n_max, size_t cells, bool need_dmin, hipS
   return LT_OK;
 }
 
-template <typename T>
-int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool need_prefix, bool bnds_only, double fov_up_deg,
-           double fov_down_deg, int H, int W, int n_beams, unsigned flags, const float* lut, int lut_len, float range_init,
-           float rem_init, float xyz_init, hipStream_t st) {
+// The sensor model of one call, checked: what the kernels are handed of it and the doubles they read from the projector's
+// `beams` (model_table).  An entry point makes it ONCE, before it allocates or launches anything.  Laser parameters exactly
+// as laserscan.py:207-209 (python floats; rounded once to the array dtype at the launch).  The rows, the sector and the
+// offsets go with LT_PROJ_NEW | LT_PROJ_REMOVE only (model_table): both drops, and never MODE 1.
+struct pj_model {
+  int H, W, n_beams;
+  double abs_fov_down, fov;
+  int drop_zero, drop_outside;
+  bool is_new, rows, sector, azimuth;  // LT_PROJ_NEW, _BEAM_ROWS, _SECTOR, _BEAM_AZIMUTH
+  int n_tab;                    // doubles of `tab` in use (0: none)
+  double tab[LT_MODEL_DOUBLES];
+};
+
+// false: the arguments do not fit the flags (the message is set).  `sec`, `az`, `n_az`: model_table
+bool pj_model_of(const char* who, const double* beam_angles, int n_beams, unsigned flags, double fov_up_deg,
+                 double fov_down_deg, int H, int W, const double* sec, const double* az, int n_az, pj_model& m) {
+  m.n_tab = model_table(who, beam_angles, n_beams, flags, fov_up_deg, fov_down_deg, H, sec, az, n_az, m.tab);
+  if (m.n_tab < 0) return false;
   const double fu = fov_up_deg / 180.0 * M_PI, fd = fov_down_deg / 180.0 * M_PI;
-  const double fov = fabs(fd) + fabs(fu);
-  const int drop_zero = (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW)) ? 1 : 0, drop_outside = (flags & LT_PROJ_REMOVE) ? 1 : 0;
-  const int cells = H * W, bpc = (cells + 255) / 256;
-  const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0;  // (never with old_f64: the flag goes with LT_PROJ_NEW)
-  const bool sector = (flags & LT_PROJ_SECTOR) != 0;   // (the same)
-  const bool azimuth = (flags & LT_PROJ_BEAM_AZIMUTH) != 0;  // (the same; with rows)
+  m.H = H; m.W = W; m.n_beams = n_beams;
+  m.abs_fov_down = fabs(fd);
+  m.fov = fabs(fd) + fabs(fu);
+  m.drop_zero = (flags & (LT_PROJ_REMOVE | LT_PROJ_NEW)) ? 1 : 0;
+  m.drop_outside = (flags & LT_PROJ_REMOVE) ? 1 : 0;
+  m.is_new = (flags & LT_PROJ_NEW) != 0;
+  m.rows = (flags & LT_PROJ_BEAM_ROWS) != 0;
+  m.sector = (flags & LT_PROJ_SECTOR) != 0;
+  m.azimuth = (flags & LT_PROJ_BEAM_AZIMUTH) != 0;
+  return true;
+}
+
+// The sensor-model arguments of every kernel that calls project_model, in their order; for pj_run and pj_compact alone
+// (undefined behind them), it reads their `m` (the pj_model) and `p` (the projector).
+#define LT_PB_MODEL_ARGS(T) \
+  (T)M_PI, (T)m.abs_fov_down, (T)m.fov, m.H, m.W, (const double*)p->beams, m.n_beams, m.drop_zero, m.drop_outside
+
+template <typename T>
+int pj_run(lt_projector* p, pb_args& A, int total_blocks, bool old_f64, bool need_prefix, bool bnds_only, const pj_model& m,
+           const float* lut, int lut_len, float range_init, float rem_init, float xyz_init, hipStream_t st) {
+  const int cells = m.H * m.W, bpc = (cells + 255) / 256;
   // MODE 1 (old_f64) has neither rows nor a sector; the other instantiations are MODE 0
-#define LT_PB_PROJECT(MODE, B, S)                                                                                          \
-  hipLaunchKernelGGL((k_pb_project<T, MODE, B, S>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, \
-                     H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside)
-#define LT_PB_RESOLVE(MODE, B, S)                                                                                          \
-  hipLaunchKernelGGL((k_pb_resolve<T, MODE, B, S>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI,             \
-                     (T)fabs(fd), (T)fov, H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len,   \
-                     range_init, rem_init, xyz_init, need_prefix ? 1 : 0)
-#define LT_PB_PROJECT0(B, S) LT_PB_PROJECT(0, B, S)
-#define LT_PB_RESOLVE0(B, S) LT_PB_RESOLVE(0, B, S)
-#define LT_PB_PROJECT_AZ(S)                                                                                                \
-  hipLaunchKernelGGL((k_pb_project<T, 0, 1, S, 1>), dim3(total_blocks), dim3(256), 0, st, A, (T)M_PI, (T)fabs(fd), (T)fov, \
-                     H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside)
-#define LT_PB_RESOLVE_AZ(S)                                                                                                \
-  hipLaunchKernelGGL((k_pb_resolve<T, 0, 1, S, 1>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc, (T)M_PI,             \
-                     (T)fabs(fd), (T)fov, H, W, (const double*)p->beams, n_beams, drop_zero, drop_outside, lut, lut_len,   \
-                     range_init, rem_init, xyz_init, need_prefix ? 1 : 0)
+#define LT_PB_PROJECT(MODE, B, S, AZ)                                                                                      \
+  hipLaunchKernelGGL((k_pb_project<T, MODE, B, S, AZ>), dim3(total_blocks), dim3(256), 0, st, A, LT_PB_MODEL_ARGS(T))
+#define LT_PB_RESOLVE(MODE, B, S, AZ)                                                                                      \
+  hipLaunchKernelGGL((k_pb_resolve<T, MODE, B, S, AZ>), dim3(bpc * A.n_clouds), dim3(256), 0, st, A, bpc,                  \
+                     LT_PB_MODEL_ARGS(T), lut, lut_len, range_init, rem_init, xyz_init, need_prefix ? 1 : 0)
+#define LT_PB_PROJECT0(B, S, AZ) LT_PB_PROJECT(0, B, S, AZ)
+#define LT_PB_RESOLVE0(B, S, AZ) LT_PB_RESOLVE(0, B, S, AZ)
   if (total_blocks > 0) {
     if (old_f64) {
-      LT_PB_PROJECT(1, 0, 0);
-      hipLaunchKernelGGL(k_pb_assign, dim3(total_blocks), dim3(256), 0, st, A, M_PI, fabs(fd), fov, H, W,
-                         (const double*)p->beams, n_beams, drop_zero, drop_outside);
+      LT_PB_PROJECT(1, 0, 0, 0);
+      hipLaunchKernelGGL(k_pb_assign, dim3(total_blocks), dim3(256), 0, st, A, LT_PB_MODEL_ARGS(double));
     } else {
-      LT_FOR_MODEL_AZ(rows, sector, azimuth, LT_PB_PROJECT0, LT_PB_PROJECT_AZ);
+      LT_FOR_MODEL(m.rows, m.sector, m.azimuth, LT_PB_PROJECT0);
     }
   }
   if (need_prefix) hipLaunchKernelGGL(k_pb_prefix, dim3(A.n_clouds), dim3(256), 0, st, A);
   else if (bnds_only) hipLaunchKernelGGL(k_pb_bnds, dim3(A.n_clouds), dim3(64), 0, st, A);
-  if (old_f64) LT_PB_RESOLVE(1, 0, 0);
-  else LT_FOR_MODEL_AZ(rows, sector, azimuth, LT_PB_RESOLVE0, LT_PB_RESOLVE_AZ);
+  if (old_f64) LT_PB_RESOLVE(1, 0, 0, 0);
+  else LT_FOR_MODEL(m.rows, m.sector, m.azimuth, LT_PB_RESOLVE0);
 #undef LT_PB_PROJECT
 #undef LT_PB_RESOLVE
 #undef LT_PB_PROJECT0
 #undef LT_PB_RESOLVE0
-#undef LT_PB_PROJECT_AZ
-#undef LT_PB_RESOLVE_AZ
   LT_HIP(hipGetLastError());
   return LT_OK;
 }
+
+// the kept points of slot 0's cloud, after a pj_run with the prefix (lt_range_projection_dev)
+template <typename T>
+int pj_compact(lt_projector* p, const lt_cloud& c, const pb_kept<T>& out, const pj_model& m, hipStream_t st) {
+#define LT_PB_COMPACT(B, S, AZ)                                                                                            \
+  hipLaunchKernelGGL((k_pb_compact<T, B, S, AZ>), dim3((c.n + 255) / 256), dim3(256), 0, st, (const T*)c.points, c.rem,    \
+                     c.label, c.n, (const unsigned long long*)p->keep[0], (const int*)p->wprefix[0], out, LT_PB_MODEL_ARGS(T))
+  LT_FOR_MODEL(m.rows, m.sector, m.azimuth, LT_PB_COMPACT);
+#undef LT_PB_COMPACT
+  LT_HIP(hipGetLastError());
+  return LT_OK;
+}
+#undef LT_PB_MODEL_ARGS
 }  // namespace
 
 extern "C" int lt_projector_create(lt_projector** pj, int device) {
@@ -964,33 +727,19 @@ extern "C" int lt_projector_destroy(lt_projector* p) {
   return LT_OK;
 }
 
-extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, const lt_cloud* clouds, int is_f64,
-                                             double fov_up, double fov_down, int H, int W, const double* beam_angles,
-                                             int n_beams, unsigned flags, const float* color_lut, int lut_len,
-                                             const lt_proj_images* out, float range_init, float rem_init, float xyz_init,
-                                             void* stream) {
-  if (!p || n_clouds < 0 || (n_clouds > 0 && (!clouds || !out)) || H <= 0 || W <= 0 || n_beams < 0 || n_beams > 1024 ||
-      (n_beams > 0 && !beam_angles)) {
-    lt_set_error("lt_range_projection_batch_dev: invalid argument (n_clouds=%d H=%d W=%d n_beams=%d)", n_clouds, H, W, n_beams);
-    return LT_ERR_INVALID_ARG;
-  }
+// The projection of checked clouds (n >= 0, points unless n == 0) on a projector that the caller holds locked, queued on
+// `st`.  `model` is the caller's, with the sector and the offsets the caller chose: a projector's own, or the process-wide
+// ones of the single-cloud call -- p->sector and p->az are not read here.
+static int project_clouds(lt_projector* p, const pj_model& model, int n_clouds, const lt_cloud* clouds, int is_f64,
+                          const float* color_lut, int lut_len, const lt_proj_images* out, float range_init, float rem_init,
+                          float xyz_init, hipStream_t st) {
   size_t n_max = 0;
-  for (int k = 0; k < n_clouds; ++k) {
-    if (clouds[k].n < 0 || (clouds[k].n > 0 && !clouds[k].points)) {
-      lt_set_error("lt_range_projection_batch_dev: cloud %d: n=%d points=%p", k, clouds[k].n, clouds[k].points);
-      return LT_ERR_INVALID_ARG;
-    }
-    n_max = std::max(n_max, (size_t)clouds[k].n);
-  }
-  std::lock_guard<std::mutex> lock(p->mu);
-  double tab[LT_MODEL_DOUBLES];
-  const int n_dev = model_table("lt_range_projection_batch_dev", beam_angles, n_beams, flags, fov_up, fov_down, H,
-                                p->sector_set ? p->sector : nullptr, p->az_n > 0 ? p->az : nullptr, p->az_n, tab);
-  if (n_dev < 0) return LT_ERR_INVALID_ARG;
+  for (int k = 0; k < n_clouds; ++k) n_max = std::max(n_max, (size_t)clouds[k].n);
+  const double* tab = model.tab;
+  const int n_dev = model.n_tab;
   LT_HIP(hipSetDevice(p->device));
-  hipStream_t st = (hipStream_t)stream;
-  const bool old_f64 = is_f64 && !(flags & LT_PROJ_NEW);
-  LT_CHECK(pj_reserve(p, n_max, (size_t)H * W, old_f64, st));
+  const bool old_f64 = is_f64 && !model.is_new;
+  LT_CHECK(pj_reserve(p, n_max, (size_t)model.H * model.W, old_f64, st));
   {  // the per-workgroup partial bounds of the clouds that want get_bnds()
     bool want = false;
     for (int k = 0; k < n_clouds; ++k) want = want || out[k].bnds;
@@ -1032,14 +781,125 @@ extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, cons
     for (int k = A.n_clouds; k < LT_PB_MAX; ++k) { A.c[k] = A.c[0]; A.c[k].n = 0; A.c[k].block0 = 0x7fffffff; }
     bool wants_bnds = false;
     for (int k = 0; k < A.n_clouds; ++k) wants_bnds = wants_bnds || A.c[k].bacc;
-    const int rc = is_f64 ? pj_run<double>(p, A, blocks, old_f64, need_prefix, wants_bnds, fov_up, fov_down, H, W, n_beams, flags,
-                                           color_lut, lut_len, range_init, rem_init, xyz_init, st)
-                          : pj_run<float>(p, A, blocks, false, need_prefix, wants_bnds, fov_up, fov_down, H, W, n_beams, flags,
-                                          color_lut, lut_len, range_init, rem_init, xyz_init, st);
+    const int rc = is_f64 ? pj_run<double>(p, A, blocks, old_f64, need_prefix, wants_bnds, model, color_lut, lut_len,
+                                           range_init, rem_init, xyz_init, st)
+                          : pj_run<float>(p, A, blocks, false, need_prefix, wants_bnds, model, color_lut, lut_len,
+                                          range_init, rem_init, xyz_init, st);
     if (rc != LT_OK) return rc;
   }
   p->armed = true;  // k_pb_resolve re-armed every cell it looked at
   if (old_f64) p->dmin_armed = true;
+  return LT_OK;
+}
+
+extern "C" int lt_range_projection_batch_dev(lt_projector* p, int n_clouds, const lt_cloud* clouds, int is_f64,
+                                             double fov_up, double fov_down, int H, int W, const double* beam_angles,
+                                             int n_beams, unsigned flags, const float* color_lut, int lut_len,
+                                             const lt_proj_images* out, float range_init, float rem_init, float xyz_init,
+                                             void* stream) {
+  if (!p || n_clouds < 0 || (n_clouds > 0 && (!clouds || !out)) || H <= 0 || W <= 0 || n_beams < 0 || n_beams > 1024 ||
+      (n_beams > 0 && !beam_angles)) {
+    lt_set_error("lt_range_projection_batch_dev: invalid argument (n_clouds=%d H=%d W=%d n_beams=%d)", n_clouds, H, W, n_beams);
+    return LT_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < n_clouds; ++k)
+    if (clouds[k].n < 0 || (clouds[k].n > 0 && !clouds[k].points)) {
+      lt_set_error("lt_range_projection_batch_dev: cloud %d: n=%d points=%p", k, clouds[k].n, clouds[k].points);
+      return LT_ERR_INVALID_ARG;
+    }
+  std::lock_guard<std::mutex> lock(p->mu);
+  pj_model model;
+  if (!pj_model_of("lt_range_projection_batch_dev", beam_angles, n_beams, flags, fov_up, fov_down, H, W,
+                   p->sector_set ? p->sector : nullptr, p->az_n > 0 ? p->az : nullptr, p->az_n, model))
+    return LT_ERR_INVALID_ARG;
+  return project_clouds(p, model, n_clouds, clouds, is_f64, color_lut, lut_len, out, range_init, rem_init, xyz_init,
+                        (hipStream_t)stream);
+}
+
+// ---- one cloud, with its kept points compacted and their number on the host (lt_range_projection_dev) -----------------
+namespace {
+std::mutex g_pmu;
+lt_projector* g_pj = nullptr;     // the workspace of lt_range_projection_dev, on the device of its last call
+double g_sector[2] = {0.0, 0.0};  // lt_range_projection_set_sector
+bool g_sector_set = false;
+double g_az[511];                 // lt_range_projection_set_beam_azimuth
+int g_az_n = 0;
+}  // namespace
+
+extern "C" int lt_range_projection_set_sector(double yaw_center, double span) {
+  if (span != 0.0 && !sector_ok("lt_range_projection_set_sector", yaw_center, span)) return LT_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(g_pmu);
+  g_sector[0] = yaw_center;
+  g_sector[1] = span;
+  g_sector_set = span != 0.0;
+  return LT_OK;
+}
+
+extern "C" int lt_range_projection_set_beam_azimuth(const double* az_rad, int H) {
+  if (!beam_azimuth_ok("lt_range_projection_set_beam_azimuth", az_rad, H)) return LT_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(g_pmu);
+  g_az_n = az_rad ? H : 0;
+  if (g_az_n > 0) memcpy(g_az, az_rad, (size_t)H * sizeof(double));
+  return LT_OK;
+}
+
+// The batch's kernels for one cloud on a hidden, process-wide projector (g_pj; g_pmu stands in for its mutex), then
+// k_pb_compact.  g_pmu is held for the WHOLE call, the final wait for the stream included: the projector is shared by every
+// thread of the process, whatever stream each one passes, and a thread that has to regrow it (pj_reserve, which waits for
+// its own stream only) may free the buffers only because no other thread's kernels can still be in flight on them.
+extern "C" int lt_range_projection_dev(const void* points, int is_f64, const float* rem, const unsigned* label,
+                                       int n, double fov_up, double fov_down, int H, int W,
+                                       const double* beam_angles, int n_beams, unsigned flags,
+                                       const float* color_lut, int lut_len, void* points_kept, float* rem_kept,
+                                       unsigned* label_kept, void* depth_kept, int* proj_x_kept, int* proj_y_kept,
+                                       void* proj_xf_kept, void* proj_yf_kept, int* idx_img, float* range_img,
+                                       float* xyz_img, float* rem_img, int* label_img, float* color_img,
+                                       float* mask_img, float range_init, float rem_init, float xyz_init,
+                                       int* n_kept, void* stream) {
+  if (n < 0 || H <= 0 || W <= 0 || (n > 0 && !points) || n_beams < 0 || n_beams > 1024 ||
+      (n_beams > 0 && !beam_angles)) {
+    lt_set_error("lt_range_projection: invalid argument (n=%d H=%d W=%d n_beams=%d)", n, H, W, n_beams);
+    return LT_ERR_INVALID_ARG;
+  }
+  std::lock_guard<std::mutex> lock(g_pmu);
+  pj_model model;  // (the flags and the table are checked before anything is allocated)
+  if (!pj_model_of("lt_range_projection", beam_angles, n_beams, flags, fov_up, fov_down, H, W,
+                   g_sector_set ? g_sector : nullptr, g_az_n > 0 ? g_az : nullptr, g_az_n, model))
+    return LT_ERR_INVALID_ARG;
+  int dev = 0;
+  LT_HIP(hipGetDevice(&dev));
+  if (g_pj && g_pj->device != dev) {  // (destroy waits for the old device and leaves it current; create makes `dev` current again)
+    (void)lt_projector_destroy(g_pj);
+    g_pj = nullptr;
+  }
+  if (!g_pj) LT_CHECK(lt_projector_create(&g_pj, dev));
+  lt_projector* p = g_pj;
+  hipStream_t st = (hipStream_t)stream;
+  lt_cloud cloud;
+  cloud.points = points; cloud.rem = rem; cloud.label = label; cloud.n = n;
+  lt_proj_images img;
+  memset(&img, 0, sizeof(img));
+  img.idx = idx_img; img.range = range_img; img.xyz = xyz_img; img.rem = rem_img; img.label = label_img;
+  img.color = color_img; img.mask = mask_img;
+  img.n_kept = p->meta;  // always: the number of kept points goes where k_pb_prefix leaves it anyway, and asking for it asks
+                         // for the prefix, which the compaction and the host's n_kept need whatever images are wanted
+  LT_CHECK(project_clouds(p, model, 1, &cloud, is_f64, color_lut, lut_len, &img, range_init, rem_init, xyz_init, st));
+  if (n > 0 && (points_kept || rem_kept || label_kept || depth_kept || proj_x_kept || proj_y_kept || proj_xf_kept ||
+                proj_yf_kept)) {
+    if (is_f64) {
+      const pb_kept<double> out = {(double*)points_kept, rem_kept, label_kept, (double*)depth_kept, proj_x_kept, proj_y_kept,
+                                   (double*)proj_xf_kept, (double*)proj_yf_kept};
+      LT_CHECK(pj_compact<double>(p, cloud, out, model, st));
+    } else {
+      const pb_kept<float> out = {(float*)points_kept, rem_kept, label_kept, (float*)depth_kept, proj_x_kept, proj_y_kept,
+                                  (float*)proj_xf_kept, (float*)proj_yf_kept};
+      LT_CHECK(pj_compact<float>(p, cloud, out, model, st));
+    }
+  }
+  int kept = 0;
+  LT_HIP(hipMemcpyAsync(&kept, p->meta, sizeof(int), hipMemcpyDeviceToHost, st));
+  LT_HIP(hipStreamSynchronize(st));
+  if (n_kept) *n_kept = kept;
   return LT_OK;
 }
 

@@ -198,8 +198,8 @@ __device__ __forceinline__ T project_azimuth_column(proj_out<T>& o, T x, T y, T 
   return yaw;
 }
 
-// One point through the sensor model of a projection kernel -- the one entry point of k_project, k_pb_project and
-// k_pb_resolve.  BEAMS: the rows of a beam table (project_point_beams; `tab` is then the completed table of 2 H + 2 doubles),
+// One point through the sensor model of a projection kernel -- the one entry point of k_pb_project, k_pb_resolve and
+// k_pb_compact.  BEAMS: the rows of a beam table (project_point_beams; `tab` is then the completed table of 2 H + 2 doubles),
 // else the linear rows (project_point; `tab` holds the n_beams hard-coded angles, n_beams may be 0).  AZ (with BEAMS only):
 // the per-row azimuth offsets, H doubles in radians behind the completed table (project_azimuth_column).  SECTOR: the columns
 // of a horizontal sector on top; its two numbers follow the table (and the offsets) or the angles in `tab` -- only this

@@ -266,7 +266,14 @@ def test_single_sizes_with_keep_patterns_at_every_seam(dtype, new, remove, strea
             if n > s + 1:
                 seen[s].add(bool(keep[s]))
     assert all(v == {True, False} for v in seen.values()), seen   # both ends and both sides of a wave and a block seam, in and out
-    assert {65535, 65536, 65537} <= set(pc.SIZES)                 # k_assign's sum over the preceding blocks: 255 | 256 | 257 blocks
+    assert {65535, 65536, 65537} <= set(pc.SIZES)                 # 255 | 256 | 257 blocks of the per-point kernels
+    # the compaction numbers the kept points with k_pb_prefix, whose share per thread goes from one wave to two at 256 waves:
+    # the clouds of test_batch_sizes_across_the_prefix_and_fold_seams (and their restatements), one call each
+    big = pc.big_batch_case(dtype, remove)[:4]
+    assert [len(c[0]) for c in big] == [16383, 16384, 16385, 16448]
+    for k, (pts, rem, lab) in enumerate(big):
+        got, _ = run_single((("big", dtype, remove), k), pts, rem, lab, H, W, new, remove, None, stream)
+        assert 0 < got["n_kept"] < len(pts)
 
 
 @pytest.mark.parametrize("new,remove", pc.VARIANTS)

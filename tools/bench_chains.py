@@ -423,8 +423,9 @@ def main():
         do_label_projection_new per cloud (ONE lt_range_projection_batch_dev call) -> fresh 2000x2000x200 volume, integrate
         x nscans -> marching cubes -> ray cast of the target sensor -> write(): filter + pack the .bin / .label bytes
         (lt_pack_scan_dev).  Nothing leaves HBM but the mesh sizes and the number of packed points.  `verified`: the source
-        images equal the single-cloud call's (lt_range_projection_dev, pinned to the reference's goldens), and the target
-        images + packed bytes equal the step-by-step API run from those images."""
+        images equal the single-cloud call's (lt_range_projection_dev: the same kernels, one cloud at a time -- a check of the
+        batching, not an independent pin; those are the tests: the numpy restatement and the reference's goldens), and the
+        target images + packed bytes equal the step-by-step API run from those images."""
         import ctypes as C
         from lidar_transfer_amd import _lib
         from lidar_transfer_amd.deform import DeviceDeform
@@ -536,7 +537,7 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         proj_ms = e0.elapsed_time(e1) / reps
-        # the single-cloud device call for comparison (four kernels + a host synchronisation per cloud)
+        # the single-cloud device call for comparison (the same kernels for one cloud + a host synchronisation per cloud)
         kept = C.c_int(0)
         t_single = []
         for rep_ in range(6):
