@@ -51,9 +51,45 @@
 // The volume is ONE array of float4 per voxel -- (tsdf, weight, colour, remission), [x][y][z] -- not the reference's four
 // arrays: an update is one 16-byte read-modify-write instead of four 4-byte ones in four places (a z run of ~10 written
 // voxels was 2-3 32-byte sectors in each of four arrays: 3.3 x the bytes of the voxels), and marching cubes finds a
-// vertex's field samples and its attributes in the two lines it reads anyway.  The kernels keep their four pointer
-// arguments (base, base + 1, base + 2, base + 3: what lt_tsdf_volumes hands out, stride 4); only LT_VOX touches memory.
+// vertex's field samples and its attributes in the two lines it reads anyway.  The kernels take that one base pointer
+// (tsdf_volume::vox); the four field pointers at stride 4 (lt_tsdf::tsdf / weight / color / rem) are what lt_tsdf_volumes
+// hands out and what marching cubes reads.
 #define LT_VOX(tsdf_base, idx) (reinterpret_cast<float4*>(tsdf_base) + (idx))
+
+// What the kernels below are told, as four PODs by value (helpers: by const reference) -- built on the host by
+// tsdf_vol_of / tsdf_view_of / tsdf_marks_of / tsdf_wedge_of.  A call's images, dct, obs4, zw_snap and the debug pointers
+// stay arguments of their own.
+struct tsdf_volume {  // the voxel grid
+  float4* vox;  // [dim_x][dim_y][dim_z] (tsdf, weight, colour, remission)
+  int dim_x, dim_y, dim_z;
+  float ox, oy, oz, voxel_size;
+};
+struct tsdf_view {  // one integrate call: the image shape and the reference kernel's other_params
+  int im_h, im_w;
+  float trunc_margin, obs_weight, fov_up, fov_down;
+  float sin_up_hi, sin_down_lo;  // the conservative sine test of the vertical field of view (tsdf_fov_of)
+};
+struct tsdf_marks {  // the column bookkeeping every writer updates (lt_internal.h, lt_tsdf)
+  unsigned* col_epoch;
+  unsigned epoch;
+  unsigned long long* sign_bits;
+  int words_z;
+  unsigned* col_zw;
+  unsigned* chunk_epoch;
+};
+// the tables of the pixel pass (tsdf_pix_tables); the other kernels of its path read wd_px only.  wd_start is NOT in here: the
+// pixel kernels read it at workgroup-uniform indices, and only as a `const __restrict__` kernel argument is that a scalar
+// load (a pointer inside a struct cannot say that no store of the kernel reaches it: two vector loads + readfirstlane)
+struct tsdf_wedge {
+  const int* wd_px;
+  const int2* wd_ent;
+  const uint32_t* wd_key;
+  int rho_bits;
+  float qscale;
+  const float4* rowtab;
+  float inv_vs;  // 1 / voxel_size
+};
+
 __global__ __launch_bounds__(256) void k_tsdf_fill(float4* __restrict__ vol, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
     vol[i] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);  // np.ones / np.zeros (fusion_lidar.py:47-51)
@@ -65,9 +101,9 @@ __global__ __launch_bounds__(256) void k_tsdf_fill(float4* __restrict__ vol, siz
 // `fresh`: the voxel's column has not been written since the last reset, so the old values are the initial ones
 // (tsdf 1, weight 0, colour 0, remission 0) and need not be loaded
 template <bool MERGE>
-__device__ __forceinline__ int tsdf_update(float* __restrict__ tsdf_vol, int voxel_idx, float dist, float obs_weight,
+__device__ __forceinline__ int tsdf_update(float4* __restrict__ vol, int voxel_idx, float dist, float obs_weight,
                                             float new_color, float new_rem, bool fresh = false) {
-  float4* const vox = LT_VOX(tsdf_vol, voxel_idx);
+  float4* const vox = vol + voxel_idx;
   const float4 o = fresh ? make_float4(1.0f, 0.0f, 0.0f, 0.0f) : *vox;  // (tsdf, weight, colour, remission)
   if (!MERGE) {
     const float w_old = o.y;
@@ -163,26 +199,26 @@ struct col_plain {  // (as declared: not plain -- every voxel by the reference's
   int col = 0;     // cx * dim_y + cy: the exact evaluation takes pt_x, pt_y from it (col_xy)
 };
 // (pt_x, pt_y) of table column `col` -- the kernel's `vol_origin + voxel * voxel_size` on voxel_x = cx, voxel_y = cy (:101-103)
-__device__ __forceinline__ void col_xy(int col, int dim_y, float voxel_size, float ox, float oy, float& pt_x, float& pt_y) {
-  int cx = (int)((float)col * __builtin_amdgcn_rcpf((float)dim_y));  // (within one of col / dim_y for dim_x < 2^21)
-  int cy = col - cx * dim_y;
-  if (cy < 0) { cx -= 1; cy += dim_y; }
-  if (cy >= dim_y) { cx += 1; cy -= dim_y; }
-  pt_x = __fmaf_rn((float)cx, voxel_size, ox);
-  pt_y = __fmaf_rn((float)cy, voxel_size, oy);
+__device__ __forceinline__ void col_xy(int col, const tsdf_volume& Vol, float& pt_x, float& pt_y) {
+  int cx = (int)((float)col * __builtin_amdgcn_rcpf((float)Vol.dim_y));  // (within one of col / dim_y for dim_x < 2^21)
+  int cy = col - cx * Vol.dim_y;
+  if (cy < 0) { cx -= 1; cy += Vol.dim_y; }
+  if (cy >= Vol.dim_y) { cx += 1; cy -= Vol.dim_y; }
+  pt_x = __fmaf_rn((float)cx, Vol.voxel_size, Vol.ox);
+  pt_y = __fmaf_rn((float)cy, Vol.voxel_size, Vol.oy);
 }
-__device__ __forceinline__ col_plain col_plain_of(int cx, int cy, int z0, int z1, int vol_dim_y, int vol_dim_z, float ox,
-                                                  float oy, float voxel_size, const int* __restrict__ colinfo) {
+__device__ __forceinline__ col_plain col_plain_of(int cx, int cy, int z0, int z1, const tsdf_volume& Vol,
+                                                  const int* __restrict__ colinfo) {
   col_plain C;
   if (z1 <= z0) return C;
-  const int cc = cx * vol_dim_y + cy;
-  const int i0 = cc * vol_dim_z + z0, i1 = cc * vol_dim_z + z1 - 1;
-  const float dyz = (float)(vol_dim_y * vol_dim_z);
+  const int cc = cx * Vol.dim_y + cy;
+  const int i0 = cc * Vol.dim_z + z0, i1 = cc * Vol.dim_z + z1 - 1;
+  const float dyz = (float)(Vol.dim_y * Vol.dim_z);
   const float x0 = floorf(((float)i0) / dyz), x1 = floorf(((float)i1) / dyz);
   if (x0 != (float)cx || x1 != (float)cx) return C;
   const int px = colinfo[cc];
   if (px < 0) return C;  // (a dead column walked because cy == dim_y - 1: the general path sorts its voxels out)
-  const float pt_x = __fmaf_rn((float)cx, voxel_size, ox), pt_y = __fmaf_rn((float)cy, voxel_size, oy);
+  const float pt_x = __fmaf_rn((float)cx, Vol.voxel_size, Vol.ox), pt_y = __fmaf_rn((float)cy, Vol.voxel_size, Vol.oy);
   C.plain = true;
   C.px = px;
   C.rho2 = __fmaf_rn(pt_y, pt_y, pt_x * pt_x);
@@ -195,18 +231,19 @@ __device__ __forceinline__ col_plain col_plain_of(int cx, int cy, int z0, int z1
 // column, outside the vertical field of view, or not in row want_py (>= 0: the pixel-centric integrate, where a voxel is
 // evaluated by the visitor of ITS OWN pixel only -- the conservative candidate sets of neighbouring rows overlap, and
 // the update is not idempotent).  The image reads and the update are the callers': tsdf_voxel, tsdf_voxel_multi.
-__device__ __forceinline__ bool tsdf_project(int voxel_idx, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy,
-                                             float oz, float voxel_size, int im_h, int im_w, float fov_up, float fov_down,
-                                             float sin_up_hi, float sin_down_lo, const int* __restrict__ colinfo,
-                                             const col_plain& C, int z_plain, int want_py, int& px_out, int& py_out, float& depth_out) {
+__device__ __forceinline__ bool tsdf_project(int voxel_idx, const tsdf_volume& Vol, const tsdf_view& Vw,
+                                             const int* __restrict__ colinfo, const col_plain& C, int z_plain, int want_py,
+                                             int& px_out, int& py_out, float& depth_out) {
+  const int vol_dim_y = Vol.dim_y, vol_dim_z = Vol.dim_z, im_h = Vw.im_h, im_w = Vw.im_w;
+  const float voxel_size = Vol.voxel_size, fov_up = Vw.fov_up, fov_down = Vw.fov_down;
   int px = -2;
   float pt_x, pt_y, pt_z;
   if (C.plain) {
     // the reference's float decomposition of every voxel index of this walk gives (cx, cy, z) (see col_plain): the
     // column's share of the expressions below comes from the caller
     px = C.px;
-    col_xy(C.col, vol_dim_y, voxel_size, ox, oy, pt_x, pt_y);
-    pt_z = __fmaf_rn((float)z_plain, voxel_size, oz);
+    col_xy(C.col, Vol, pt_x, pt_y);
+    pt_z = __fmaf_rn((float)z_plain, voxel_size, Vol.oz);
   } else {
     // voxel grid coordinates -- float division exactly as the reference (:95-98); beyond 2^24 voxels (float)voxel_idx
     // is rounded, which moves a few voxels next to an x boundary to (x + 1, -1, z): those are not a column of the table
@@ -214,15 +251,15 @@ __device__ __forceinline__ bool tsdf_project(int voxel_idx, int vol_dim_x, int v
     const float voxel_y = floorf(((float)(voxel_idx - ((int)voxel_x) * vol_dim_y * vol_dim_z)) / ((float)vol_dim_z));
     const float voxel_z = (float)(voxel_idx - ((int)voxel_x) * vol_dim_y * vol_dim_z - ((int)voxel_y) * vol_dim_z);
     const int ix = (int)voxel_x, iy = (int)voxel_y;
-    const bool in_table = ix >= 0 && ix < vol_dim_x && iy >= 0 && iy < vol_dim_y;
+    const bool in_table = ix >= 0 && ix < Vol.dim_x && iy >= 0 && iy < vol_dim_y;
     if (in_table) {
       px = colinfo[ix * vol_dim_y + iy];
       if (px == -1) return false;
       if (px >= 0) px &= 0x3FFFFFFF;  // (the wedge table's per-column image column carries a flag bit: LT_WD_QUIRK_FLAG)
     }
-    pt_x = __fmaf_rn(voxel_x, voxel_size, ox);
-    pt_y = __fmaf_rn(voxel_y, voxel_size, oy);
-    pt_z = __fmaf_rn(voxel_z, voxel_size, oz);
+    pt_x = __fmaf_rn(voxel_x, voxel_size, Vol.ox);
+    pt_y = __fmaf_rn(voxel_y, voxel_size, Vol.oy);
+    pt_z = __fmaf_rn(voxel_z, voxel_size, Vol.oz);
     if (px < 0) {
       const float yaw = -atan2f(pt_y, pt_x);
       float proj_x = (float)(0.5 * ((double)yaw / LT_PI_D + 1.0));
@@ -238,7 +275,7 @@ __device__ __forceinline__ bool tsdf_project(int voxel_idx, int vol_dim_x, int v
   // clearly outside the vertical field of view (NaN passes on -- and so does |s| > 1: on the sensor's axis the device
   // library's norm3df, a 1-ulp square root, can return less than |pt_z|; asinf is then NaN, no comparison of the
   // reference holds and the voxel IS written through pixel row 0 -- LT_AXIS_RHO)
-  if ((s > sin_up_hi || s < sin_down_lo) && fabsf(s) <= 1.0f) return false;
+  if ((s > Vw.sin_up_hi || s < Vw.sin_down_lo) && fabsf(s) <= 1.0f) return false;
   const float pitch = asinf(s);
   if (pitch > fov_up || pitch < fov_down) return false;
   float proj_y = (float)(1.0 - (double)((pitch + fabsf(fov_down)) / fov));
@@ -253,24 +290,20 @@ __device__ __forceinline__ bool tsdf_project(int voxel_idx, int vol_dim_x, int v
 
 // one observation: tsdf_project, the voxel's pixel, tsdf_update
 template <bool MERGE>
-__device__ __forceinline__ int tsdf_voxel(
-    int voxel_idx, float* __restrict__ tsdf_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
-    float sin_up_hi, float sin_down_lo, const float* __restrict__ rem_im, const int* __restrict__ colinfo, bool fresh,
-    const col_plain& C, int z_plain, const float2* __restrict__ dct, int want_py = -1) {
+__device__ __forceinline__ int tsdf_voxel(int voxel_idx, const tsdf_volume& Vol, const tsdf_view& Vw,
+                                           const float* __restrict__ rem_im, const int* __restrict__ colinfo, bool fresh,
+                                           const col_plain& C, int z_plain, const float2* __restrict__ dct, int want_py = -1) {
   int px, py;
   float depth;
-  if (!tsdf_project(voxel_idx, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, fov_up, fov_down,
-                    sin_up_hi, sin_down_lo, colinfo, C, z_plain, want_py, px, py, depth))
-    return 0;
-  const float2 dc = dct[px * im_h + py];  // (depth_im, color_im)[py * im_w + px], transposed copy (lt_tsdf::dct)
-  const float new_rem = rem_im[py * im_w + px];  // (issued with it: one round trip, not two)
+  if (!tsdf_project(voxel_idx, Vol, Vw, colinfo, C, z_plain, want_py, px, py, depth)) return 0;
+  const float2 dc = dct[px * Vw.im_h + py];  // (depth_im, color_im)[py * im_w + px], transposed copy (lt_tsdf::dct)
+  const float new_rem = rem_im[py * Vw.im_w + px];  // (issued with it: one round trip, not two)
   const float depth_value = dc.x;
   if (depth_value == 0.f) return 0;
   const float depth_diff = depth_value - depth;
-  if (depth_diff < -trunc_margin) return 0;
-  const float dist = fminf(1.0f, depth_diff / trunc_margin);
-  return tsdf_update<MERGE>(tsdf_vol, voxel_idx, dist, obs_weight, dc.y, new_rem, fresh);
+  if (depth_diff < -Vw.trunc_margin) return 0;
+  const float dist = fminf(1.0f, depth_diff / Vw.trunc_margin);
+  return tsdf_update<MERGE>(Vol.vox, voxel_idx, dist, Vw.obs_weight, dc.y, new_rem, fresh);
 }
 
 // Can voxel z of a FRESH plain column be written by the class-aware update?  On a fresh volume (the reference builds one
@@ -282,18 +315,19 @@ __device__ __forceinline__ int tsdf_voxel(
 // exact projection can choose (+-0.25 row against an error below 0.01) -> their depth / colour with a margin far above
 // the approximation errors.  CONSERVATIVE: it may only say yes too often; every candidate then runs the reference's
 // expressions (tsdf_voxel), which decide.
-__device__ __forceinline__ bool tsdf_band_candidate(int z, const col_plain& C, float oz, float voxel_size, int im_h,
-                                                    int im_w, float trunc_margin, float kA, float kB, float sin_up_hi,
-                                                    float sin_down_lo, const float2* __restrict__ dct) {
+__device__ __forceinline__ bool tsdf_band_candidate(int z, const col_plain& C, const tsdf_volume& Vol, const tsdf_view& Vw,
+                                                    float kA, float kB, const float2* __restrict__ dct) {
+  const int im_h = Vw.im_h;
+  const float trunc_margin = Vw.trunc_margin;
   // (branch-free, loads unconditional at clamped indices: the caller evaluates three voxels per lane at once and wants
   // their loads in flight together)
-  const float pt_z = __fmaf_rn((float)z, voxel_size, oz);
+  const float pt_z = __fmaf_rn((float)z, Vol.voxel_size, Vol.oz);
   const float d2 = __fmaf_rn(pt_z, pt_z, C.rho2);
   // the voxel at the sensor, NaN, overflow, a voxel on the sensor's axis (rho < 2e-3 |z|, LT_AXIS_RHO): the exact path decides
   const bool odd = !(d2 > 0.f && d2 < 1e30f) || C.rho2 <= 4e-6f * d2;
   const float rinv = __builtin_amdgcn_rsqf(d2);
   const float s = pt_z * rinv, depth = d2 * rinv;
-  const bool in_fov = !(s > sin_up_hi + 1e-4f || s < sin_down_lo - 1e-4f);  // (with margin)
+  const bool in_fov = !(s > Vw.sin_up_hi + 1e-4f || s < Vw.sin_down_lo - 1e-4f);  // (with margin)
   const float q = s * s;
   const float pitch = s * (1.0f + q * (0.16666667f + q * (0.075f + q * (0.044642857f + q * 0.030381944f))));
   const float py = __fmaf_rn(pitch, kA, kB);  // ~ proj_y * im_h
@@ -317,20 +351,19 @@ __device__ __forceinline__ bool tsdf_band_candidate(int z, const col_plain& C, f
 // whole column for y = dim_y - 1 (its voxels may belong to another (x, y) by the reference's float index) and when the
 // field of view is too steep for tangents.
 struct col_geom {
-  int dim_y, dim_z;
-  float ox, oy, oz, voxel_size, tan_up, tan_down;
+  float tan_up, tan_down;
   int tan_ok;
 };
-__device__ __forceinline__ void col_zrange(const col_geom& G, int cx, int cy, int& z0, int& z1) {
+__device__ __forceinline__ void col_zrange(const col_geom& G, const tsdf_volume& Vol, int cx, int cy, int& z0, int& z1) {
   z0 = 0;
-  z1 = G.dim_z;
-  const float pt_x = __fmaf_rn((float)cx, G.voxel_size, G.ox), pt_y = __fmaf_rn((float)cy, G.voxel_size, G.oy);
+  z1 = Vol.dim_z;
+  const float pt_x = __fmaf_rn((float)cx, Vol.voxel_size, Vol.ox), pt_y = __fmaf_rn((float)cy, Vol.voxel_size, Vol.oy);
   const float rho = sqrtf(pt_x * pt_x + pt_y * pt_y);
-  if (cy != G.dim_y - 1 && G.tan_ok && rho > axis_rho_limit(G.oz, G.voxel_size, G.dim_z)) {  // (LT_AXIS_RHO: whole column)
-    const float pad = 2.0f * G.voxel_size + 1e-3f * rho;
-    const float zl = (rho * G.tan_down - pad - G.oz) / G.voxel_size, zh = (rho * G.tan_up + pad - G.oz) / G.voxel_size;
-    z0 = max(0, (int)floorf(fminf(fmaxf(zl, -1.0f), (float)G.dim_z)));
-    z1 = min(G.dim_z, (int)ceilf(fminf(fmaxf(zh, -1.0f), (float)G.dim_z)) + 1);
+  if (cy != Vol.dim_y - 1 && G.tan_ok && rho > axis_rho_limit(Vol.oz, Vol.voxel_size, Vol.dim_z)) {  // (LT_AXIS_RHO: whole column)
+    const float pad = 2.0f * Vol.voxel_size + 1e-3f * rho;
+    const float zl = (rho * G.tan_down - pad - Vol.oz) / Vol.voxel_size, zh = (rho * G.tan_up + pad - Vol.oz) / Vol.voxel_size;
+    z0 = max(0, (int)floorf(fminf(fmaxf(zl, -1.0f), (float)Vol.dim_z)));
+    z1 = min(Vol.dim_z, (int)ceilf(fminf(fmaxf(zh, -1.0f), (float)Vol.dim_z)) + 1);
   }
 }
 
@@ -375,21 +408,20 @@ __device__ __forceinline__ void sign_run_merge(unsigned long long* __restrict__ 
 
 // per voxel column (x, y): its image column px -- the kernel's own expressions on voxel_x = x, voxel_y = y -- or -1
 // when no voxel of the column can pass the truncation test
-__global__ __launch_bounds__(256) void k_tsdf_columns(int vol_dim_x, int vol_dim_y, float ox, float oy, float voxel_size,
-                                                      int im_w, float trunc_margin, const float* __restrict__ colmax,
-                                                      int* __restrict__ colinfo, int* __restrict__ chunk_live, col_geom G,
-                                                      int vol_dim_z, unsigned* __restrict__ colz,
+__global__ __launch_bounds__(256) void k_tsdf_columns(tsdf_volume Vol, tsdf_view Vw, col_geom G,
+                                                      const float* __restrict__ colmax, int* __restrict__ colinfo,
+                                                      int* __restrict__ chunk_live, unsigned* __restrict__ colz,
                                                       float* __restrict__ colrho2) {
   const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= vol_dim_x * vol_dim_y) return;
-  const int x = c / vol_dim_y, y = c - x * vol_dim_y;
-  const float pt_x = __fmaf_rn((float)x, voxel_size, ox);
-  const float pt_y = __fmaf_rn((float)y, voxel_size, oy);
+  if (c >= Vol.dim_x * Vol.dim_y) return;
+  const int x = c / Vol.dim_y, y = c - x * Vol.dim_y;
+  const float pt_x = __fmaf_rn((float)x, Vol.voxel_size, Vol.ox);
+  const float pt_y = __fmaf_rn((float)y, Vol.voxel_size, Vol.oy);
   const float yaw = -atan2f(pt_y, pt_x);
   float proj_x = (float)(0.5 * ((double)yaw / LT_PI_D + 1.0));
-  proj_x *= (float)im_w;
+  proj_x *= (float)Vw.im_w;
   int px = (int)floorf(proj_x);
-  px = min(im_w - 1, px);
+  px = min(Vw.im_w - 1, px);
   px = max(0, px);
   // every voxel of the column has depth = norm3df(x, y, z) >= rho_lo: the true norm is >= the true sqrt(x^2 + y^2), the
   // device library's norm3df is within an ulp of the one and rho within an ulp of the other, and rho_lo sits four ulp
@@ -399,19 +431,19 @@ __global__ __launch_bounds__(256) void k_tsdf_columns(int vol_dim_x, int vol_dim
   const float rho = sqrtf(__fmaf_rn(pt_y, pt_y, pt_x * pt_x));
   const float rho_lo = rho * 0.9999995f;
   const float cm = colmax[px];
-  const bool dead = (cm - rho_lo) < -trunc_margin;
+  const bool dead = (cm - rho_lo) < -Vw.trunc_margin;
   // -2: a dead column with y = dim_y - 1 -- walked all the same, voxel by voxel (the reference's float index can put
   // voxels of the (x + 1, -1) "column" there), each finding its own px
-  const int info = dead ? (y == vol_dim_y - 1 ? -2 : -1) : px;
+  const int info = dead ? (y == Vol.dim_y - 1 ? -2 : -1) : px;
   colinfo[c] = info;
   // the walk the integrate kernel will do in this column -- its z range, whether it is plain (col_plain_of), the
   // column's fma(pt_y, pt_y, pt_x^2) -- computed HERE, one lane per column, instead of by the 16 lanes that walk the
   // column there (two square roots and four IEEE divisions per column: a sixth of that kernel's vector instructions)
   if (info != -1) {
     int z0, z1;
-    col_zrange(G, x, y, z0, z1);
+    col_zrange(G, Vol, x, y, z0, z1);
     colinfo[c] = info;  // (col_plain_of reads it)
-    const col_plain C = col_plain_of(x, y, z0, z1, vol_dim_y, vol_dim_z, ox, oy, voxel_size, colinfo);
+    const col_plain C = col_plain_of(x, y, z0, z1, Vol, colinfo);
     colz[c] = (unsigned)z0 | ((unsigned)z1 << 15) | (C.plain ? 0x80000000u : 0u);  // z < 2^15 (lt_tsdf_create)
     colrho2[c] = C.rho2;
   }
@@ -433,22 +465,16 @@ __global__ __launch_bounds__(256) void k_tsdf_columns(int vol_dim_x, int vol_dim
 // only this quarter wave works on this column, so the read-modify-write needs no atomic.
 template <bool MERGE>
 __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
-    float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
-    float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
-    float sin_up_hi, float sin_down_lo, const float* __restrict__ color_im, const float* __restrict__ depth_im,
-    const float* __restrict__ rem_im, const int* __restrict__ colinfo, unsigned* __restrict__ col_epoch,
-    unsigned epoch, col_geom G, unsigned long long* __restrict__ sign_bits, int words_z,
-    unsigned* __restrict__ col_zw, const float2* __restrict__ dct, float kA, float kB,
-    const int* __restrict__ chunk_live, const unsigned* __restrict__ colz, const float* __restrict__ colrho2,
-    int all_written, unsigned long long* __restrict__ dbg, unsigned* __restrict__ chunk_epoch) {
+    tsdf_volume Vol, tsdf_view Vw, tsdf_marks Mk, const float* __restrict__ rem_im, const float2* __restrict__ dct,
+    const int* __restrict__ colinfo, const int* __restrict__ chunk_live, const unsigned* __restrict__ colz,
+    const float* __restrict__ colrho2, float kA, float kB, int all_written, unsigned long long* __restrict__ dbg) {
   const unsigned long long t_dbg = dbg ? (unsigned long long)wall_clock64() : 0ull;  // (LIDARHIP_DEBUG_TSDF: per-wave stamps)
   // candidates of the band test (fresh plain columns, class-aware update) wait here, per wave, until 64 are together:
   // then lane j evaluates candidate j exactly
   __shared__ int q_col[4][128], q_z[4][128], q_px[4][128];
   __shared__ float q_rho2[4][128];
   const int lane = threadIdx.x & 63, grp = lane >> 4, gl = lane & 15, wv = threadIdx.x >> 6;
-  const int n_cols = vol_dim_x * vol_dim_y;
+  const int n_cols = Vol.dim_x * Vol.dim_y;
   const int n_chunks = (n_cols + 63) / 64;
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
   // (kA, kB: the band test's row = pitch * kA + kB, from the host: a quarter of a million waves need not divide for them)
@@ -459,11 +485,9 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
       const int e = qn - n + lane;
       const int col = q_col[wv][e], z = q_z[wv][e];
       const col_plain Cq = {true, q_px[wv][e], q_rho2[wv][e], col};
-      const int code = tsdf_voxel<MERGE>(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz,
-                                         voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
-                                         sin_down_lo, rem_im, colinfo, true, Cq, z, dct);
+      const int code = tsdf_voxel<MERGE>(col * Vol.dim_z + z, Vol, Vw, rem_im, colinfo, true, Cq, z, dct);
       if (code) {  // the sign of the value written -> the column's sign bit (other lanes may hold voxels of the same word)
-        unsigned long long* w = sign_bits + (size_t)col * words_z + (z >> 6);
+        unsigned long long* w = Mk.sign_bits + (size_t)col * Mk.words_z + (z >> 6);
         const unsigned long long bit = 1ull << (z & 63);
         if (code == 2) atomicOr(w, bit);
         else atomicAnd(w, ~bit);
@@ -483,7 +507,7 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
       live = colinfo[c] != -1;  // (-2: the dead columns with y = dim_y - 1, see k_tsdf_columns)
       // before this launch: its voxels hold something else than the initial values (all_written: the caller wrote into
       // the volumes through the raw pointers, lt_tsdf_touch, or a kernel without stamps did: nothing may be folded)
-      written = all_written != 0 || col_epoch[c] == epoch;
+      written = all_written != 0 || Mk.col_epoch[c] == Mk.epoch;
     }
     unsigned long long m = __ballot(live);
     const unsigned long long wm = __ballot(written);
@@ -523,8 +547,7 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
 #pragma unroll
           for (int u = 0; u < 3; ++u) {
             const int z = (z0 & ~15) + 16 * (k0 + u) + gl;
-            const bool c1 = tsdf_band_candidate(min(z, vol_dim_z - 1), C, oz, voxel_size, im_h, im_w, trunc_margin, kA, kB,
-                                                sin_up_hi, sin_down_lo, dct);
+            const bool c1 = tsdf_band_candidate(min(z, Vol.dim_z - 1), C, Vol, Vw, kA, kB, dct);
             cd[u] = c1 && z >= z0 && z < z1;
           }
         }
@@ -538,9 +561,7 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
           if (any_direct) {
             int code = 0;
             if (!band && z >= z0 && z < z1)
-              code = tsdf_voxel<MERGE>(cc * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz,
-                                       voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
-                                       sin_down_lo, rem_im, colinfo, fresh, C, z, dct);
+              code = tsdf_voxel<MERGE>(cc * Vol.dim_z + z, Vol, Vw, rem_im, colinfo, fresh, C, z, dct);
             const unsigned long long wrote_w = __ballot(code != 0), neg_w = __ballot(code == 2);
             wrote = (wrote_w >> (16 * grp)) & 0xFFFFull;
             neg = (neg_w >> (16 * grp)) & 0xFFFFull;
@@ -551,7 +572,7 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
             wz_lo = min(wz_lo, zc + (__ffsll((long long)(wrote | cands)) - 1));
             wz_hi = max(wz_hi, zc + 63 - __clzll((long long)(wrote | cands)));
             if (wrote && gl == 0) {
-              unsigned long long* w = sign_bits + (size_t)cc * words_z + (zc >> 6);
+              unsigned long long* w = Mk.sign_bits + (size_t)cc * Mk.words_z + (zc >> 6);
               const int sh = zc & 63;
               *w = (*w & ~(wrote << sh)) | (neg << sh);
             }
@@ -570,13 +591,13 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
       // reset has to re-initialise); this quarter wave owns the column, no atomics
       if (bit >= 0 && wz_hi >= 0 && gl == 0) {
         if (!fresh) {
-          wz_lo = min(wz_lo, LT_ZW_LO(col_zw[cc]));
-          wz_hi = max(wz_hi, LT_ZW_HI(col_zw[n_cols + cc]));
+          wz_lo = min(wz_lo, LT_ZW_LO(Mk.col_zw[cc]));
+          wz_hi = max(wz_hi, LT_ZW_HI(Mk.col_zw[n_cols + cc]));
         }
-        col_zw[cc] = (unsigned)(0x7FFF - wz_lo);
-        col_zw[n_cols + cc] = (unsigned)(wz_hi + 1);
-        col_epoch[cc] = epoch;
-        chunk_epoch[cc >> 6] = epoch;  // (what reset and marching cubes look at first)
+        Mk.col_zw[cc] = (unsigned)(0x7FFF - wz_lo);
+        Mk.col_zw[n_cols + cc] = (unsigned)(wz_hi + 1);
+        Mk.col_epoch[cc] = Mk.epoch;
+        Mk.chunk_epoch[cc >> 6] = Mk.epoch;  // (what reset and marching cubes look at first)
       }
     }
   }
@@ -598,33 +619,28 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
 #ifndef LT_RESET_CHUNKS_PER_WAVE
 #define LT_RESET_CHUNKS_PER_WAVE 8
 #endif
-__global__ __launch_bounds__(256) void k_tsdf_reset_cols(float* __restrict__ tsdf, float* __restrict__ weight,
-                                                         float* __restrict__ color, float* __restrict__ rem,
-                                                         int n_cols, int dim_z, const unsigned* __restrict__ col_epoch,
-                                                         unsigned epoch, unsigned long long* __restrict__ sign_bits,
-                                                         unsigned* __restrict__ col_zw,
-                                                         const unsigned* __restrict__ chunk_epoch) {
+__global__ __launch_bounds__(256) void k_tsdf_reset_cols(tsdf_volume Vol, tsdf_marks Mk) {
   const int lane = threadIdx.x & 63, grp = lane >> 4, gl = lane & 15;
+  const int n_cols = Vol.dim_x * Vol.dim_y, dim_z = Vol.dim_z;
   const int n_chunks = (n_cols + 63) / 64;
-  const int words_z = (dim_z + 63) / 64;
   const int n_waves = gridDim.x * 4, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
   unsigned long long live;
   {
     const int ch = lane * n_waves + wave;
-    live = __ballot(lane < LT_RESET_CHUNKS_PER_WAVE && ch < n_chunks && chunk_epoch[min(ch, n_chunks - 1)] == epoch);
+    live = __ballot(lane < LT_RESET_CHUNKS_PER_WAVE && ch < n_chunks && Mk.chunk_epoch[min(ch, n_chunks - 1)] == Mk.epoch);
   }
   while (live) {
     const int chunk = (__ffsll((long long)live) - 1) * n_waves + wave;  // (wave-uniform)
     live &= live - 1;
     const int c = chunk * 64 + lane;
-    const bool dirty = c < n_cols && col_epoch[c] == epoch;
+    const bool dirty = c < n_cols && Mk.col_epoch[c] == Mk.epoch;
     unsigned zw = 0x7FFFu;  // (lo | hi << 16; empty)
     if (dirty) {
-      const int hi = LT_ZW_HI(col_zw[n_cols + c]);
-      if (hi >= 0) zw = (unsigned)LT_ZW_LO(col_zw[c]) | ((unsigned)hi << 16);
-      for (int k = 0; k < words_z; ++k) sign_bits[(size_t)c * words_z + k] = 0ull;
-      col_zw[c] = 0u;  // (a clean column holds the empty range)
-      col_zw[n_cols + c] = 0u;
+      const int hi = LT_ZW_HI(Mk.col_zw[n_cols + c]);
+      if (hi >= 0) zw = (unsigned)LT_ZW_LO(Mk.col_zw[c]) | ((unsigned)hi << 16);
+      for (int k = 0; k < Mk.words_z; ++k) Mk.sign_bits[(size_t)c * Mk.words_z + k] = 0ull;
+      Mk.col_zw[c] = 0u;  // (a clean column holds the empty range)
+      Mk.col_zw[n_cols + c] = 0u;
     }
     unsigned long long m = __ballot(dirty);
     while (m) {
@@ -635,7 +651,7 @@ __global__ __launch_bounds__(256) void k_tsdf_reset_cols(float* __restrict__ tsd
       const int z0 = (int)(r & 0xFFFFu), z1 = min((int)(r >> 16), dim_z - 1);
       const size_t base = (size_t)(chunk * 64 + bit) * dim_z;
       for (int z = z0 + gl; z <= z1; z += 16) {
-        *LT_VOX(tsdf, base + z) = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+        Vol.vox[base + z] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
       }
     }
   }
@@ -729,13 +745,11 @@ __global__ __launch_bounds__(256) void k_wd_finish(wd_geom G, const uint32_t* __
 }
 
 // merge z into the written range of column c (lo | hi << 16), stamp the column; any number of concurrent writers
-__device__ __forceinline__ void col_mark_written(unsigned* __restrict__ col_zw, unsigned* __restrict__ col_epoch,
-                                                 unsigned* __restrict__ chunk_epoch, unsigned epoch, int n_cols, int c,
-                                                 int z, int z_last) {
-  atomicMax(&col_zw[c], (unsigned)(0x7FFF - z));       // (results unused: fire and forget)
-  atomicMax(&col_zw[n_cols + c], (unsigned)(z_last + 1));
-  col_epoch[c] = epoch;
-  chunk_epoch[c >> 6] = epoch;
+__device__ __forceinline__ void col_mark_written(const tsdf_marks& Mk, int n_cols, int c, int z, int z_last) {
+  atomicMax(&Mk.col_zw[c], (unsigned)(0x7FFF - z));       // (results unused: fire and forget)
+  atomicMax(&Mk.col_zw[n_cols + c], (unsigned)(z_last + 1));
+  Mk.col_epoch[c] = Mk.epoch;
+  Mk.chunk_epoch[c >> 6] = Mk.epoch;
 }
 
 // ---- several observations of a FRESH volume in ONE pass (lt_tsdf_integrate_multi_dev) --------------------------------------
@@ -771,7 +785,7 @@ __global__ __launch_bounds__(256) void k_tsdf_dct4(tsdf_obs_ptrs O, int n_obs, i
 
 // the n class-aware updates of one voxel of a FRESH volume (fusion_lidar.py:177, :191-228; tsdf_update<true> above, on
 // registers): returns 0 untouched, 1 written (> 0), 2 written not > 0 (the sign bit, as tsdf_update)
-__device__ __forceinline__ int tsdf_updates_fresh(float* __restrict__ tsdf_vol, int voxel_idx, float depth, float trunc_margin,
+__device__ __forceinline__ int tsdf_updates_fresh(float4* __restrict__ vol, int voxel_idx, float depth, float trunc_margin,
                                                    float obs_weight, const float4* __restrict__ obs4, size_t pix, size_t n_pix,
                                                    int n_obs) {
   float tv = 1.0f, wv = 0.0f, cv = 0.0f, rv = 0.0f;  // the initial volume (fusion_lidar.py:47-63)
@@ -802,23 +816,19 @@ __device__ __forceinline__ int tsdf_updates_fresh(float* __restrict__ tsdf_vol, 
     }
   }
   if (!written) return 0;
-  *LT_VOX(tsdf_vol, voxel_idx) = make_float4(tv, wv, cv, rv);
+  vol[voxel_idx] = make_float4(tv, wv, cv, rv);
   return !(tv > 0.0f) ? 2 : 1;
 }
 
 // n observations of a fresh volume: tsdf_project, then the n updates; want_py as in tsdf_voxel
-__device__ __forceinline__ int tsdf_voxel_multi(
-    int voxel_idx, float* __restrict__ tsdf_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
-    float sin_up_hi, float sin_down_lo, const int* __restrict__ colinfo, const col_plain& C, int z_plain,
-    const float4* __restrict__ obs4, int n_obs, int want_py = -1) {
+__device__ __forceinline__ int tsdf_voxel_multi(int voxel_idx, const tsdf_volume& Vol, const tsdf_view& Vw,
+                                                 const int* __restrict__ colinfo, const col_plain& C, int z_plain,
+                                                 const float4* __restrict__ obs4, int n_obs, int want_py = -1) {
   int px, py;
   float depth;
-  if (!tsdf_project(voxel_idx, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, im_h, im_w, fov_up, fov_down,
-                    sin_up_hi, sin_down_lo, colinfo, C, z_plain, want_py, px, py, depth))
-    return 0;
-  return tsdf_updates_fresh(tsdf_vol, voxel_idx, depth, trunc_margin, obs_weight, obs4, (size_t)px * im_h + py,
-                            (size_t)im_h * im_w, n_obs);
+  if (!tsdf_project(voxel_idx, Vol, Vw, colinfo, C, z_plain, want_py, px, py, depth)) return 0;
+  return tsdf_updates_fresh(Vol.vox, voxel_idx, depth, Vw.trunc_margin, Vw.obs_weight, obs4, (size_t)px * Vw.im_h + py,
+                            (size_t)Vw.im_h * Vw.im_w, n_obs);
 }
 
 // One workgroup = 64 consecutive pixels of the transposed image (rows of one image column: they walk the same wedge), its
@@ -849,16 +859,13 @@ __device__ __forceinline__ int tsdf_voxel_multi(
 // voxels inside them may hold anything -- k_tsdf_integrate_written has evaluated every one of them -- and are skipped here;
 // everything else still holds the initial values, so the superset argument (and `fresh` = true) stands.
 template <bool MULTI, bool VCOUNT>
-__device__ __forceinline__ void pix_body(
-    float* __restrict__ tsdf_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz, float voxel_size,
-    float inv_vs, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down, float sin_up_hi,
-    float sin_down_lo, const float* __restrict__ rem_im, const float4* __restrict__ obs4, int n_obs,
-    const int* __restrict__ wd_px, unsigned* __restrict__ col_epoch, unsigned epoch,
-    unsigned long long* __restrict__ sign_bits, int words_z, unsigned* __restrict__ col_zw,
-    unsigned* __restrict__ chunk_epoch, const float2* __restrict__ dct, const float4* __restrict__ rowtab,
-    const int* __restrict__ wd_start, const int2* __restrict__ wd_ent, const uint32_t* __restrict__ wd_key, int rho_bits,
-    float qscale, const unsigned* __restrict__ zw_snap, unsigned long long* __restrict__ dbg) {
-  const int n_cols_all = vol_dim_x * vol_dim_y;
+__device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view& Vw, const tsdf_marks& Mk,
+                                         const tsdf_wedge& Wd, const int* __restrict__ wd_start,
+                                         const float* __restrict__ rem_im, const float2* __restrict__ dct,
+                                         const float4* __restrict__ obs4, int n_obs, const unsigned* __restrict__ zw_snap,
+                                         unsigned long long* __restrict__ dbg) {
+  const int n_cols_all = Vol.dim_x * Vol.dim_y, im_h = Vw.im_h, im_w = Vw.im_w;
+  const float trunc_margin = Vw.trunc_margin, qscale = Wd.qscale;
   // per pixel of the workgroup
   __shared__ int p_k0[64], p_pre[65], p_r[64], p_px[64];
   __shared__ float p_tlo[64], p_thi[64], p_dlo[64], p_dhi[64];
@@ -877,7 +884,7 @@ __device__ __forceinline__ void pix_body(
   __shared__ unsigned a_lo[LT_PIX_AGG], a_hi[LT_PIX_AGG];
   __shared__ int a_k0, a_span;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t qmax = (1u << rho_bits) - 2u;
+  const uint32_t qmax = (1u << Wd.rho_bits) - 2u;
   const int n_pix = im_h * im_w;
   const uint32_t* const skey = (const uint32_t*)c_buf;  // staged quanta of [stage0, stage0 + n_stage)
   int stage0 = 0, n_stage = 0;
@@ -892,7 +899,7 @@ __device__ __forceinline__ void pix_body(
     }
     return a;
   };
-  auto lower = [&](int a, int b, uint32_t q) { return staged ? lower_in(skey, stage0, a, b, q) : lower_in(wd_key, 0, a, b, q); };
+  auto lower = [&](int a, int b, uint32_t q) { return staged ? lower_in(skey, stage0, a, b, q) : lower_in(Wd.wd_key, 0, a, b, q); };
   // (An item's chunks dealt to several workgroups, each repeating phase A, were measured: 2 parts 88 us, 4 parts 129 against
   // 65 -- an item is 6 us of phase A, 3 of its first chunk's pairs and 9 of voxel rounds: tools/tsdf_written_times.py --pix.)
   for (int p0 = blockIdx.x * 64; p0 < n_pix; p0 += gridDim.x * 64) {  // (workgroup-uniform)
@@ -907,7 +914,7 @@ __device__ __forceinline__ void pix_body(
     float4 row;
     auto locate = [&](bool in_) {
       in = in_; px = in ? p / im_h : 0; r = in ? p - px * im_h : 0;
-      row = rowtab[r]; s0 = wd_start[px]; s1 = wd_start[px + 1];
+      row = Wd.rowtab[r]; s0 = wd_start[px]; s1 = wd_start[px + 1];
     };
     [[maybe_unused]] float2 dcA;
     if constexpr (!MULTI) {
@@ -930,7 +937,7 @@ __device__ __forceinline__ void pix_body(
         constexpr int NS = (LT_PIX_STAGE + 255) / 256;
         uint32_t sv[NS];
 #pragma unroll
-        for (int k = 0; k < NS; ++k) sv[k] = tid + 256 * k < n_stage ? wd_key[stage0 + tid + 256 * k] : 0u;
+        for (int k = 0; k < NS; ++k) sv[k] = tid + 256 * k < n_stage ? Wd.wd_key[stage0 + tid + 256 * k] : 0u;
 #pragma unroll
         for (int k = 0; k < NS; ++k)
           if (tid + 256 * k < n_stage) c_buf[tid + 256 * k] = (int)sv[k];
@@ -1021,7 +1028,7 @@ __device__ __forceinline__ void pix_body(
           for (int st = 32; st >= 1; st >>= 1)
             if (p_pre[sidx + st] <= i) sidx += st;
           const int kk = p_k0[sidx] + (i - p_pre[sidx]);
-          const int2 e = wd_ent[kk];
+          const int2 e = Wd.wd_ent[kk];
           int z = 1, zend = 0;
           if (e.x >= 0) {  // (the quirk tail of the last wedge carries column -1)
             const float rho2 = __int_as_float(e.y), rho = sqrtf(rho2);
@@ -1037,9 +1044,9 @@ __device__ __forceinline__ void pix_body(
               else if (zb <= 0.f) { lo = fmaxf(za, -zmax); hi = fminf(zb, -zmin); }
               else { lo = fmaxf(za, -zmax); hi = fminf(zb, zmax); }
               if (lo <= hi) {
-                const float fz0 = ceilf((lo - oz) * inv_vs - 0.02f), fz1 = floorf((hi - oz) * inv_vs + 0.02f);
+                const float fz0 = ceilf((lo - Vol.oz) * Wd.inv_vs - 0.02f), fz1 = floorf((hi - Vol.oz) * Wd.inv_vs + 0.02f);
                 z = (int)fmaxf(fz0, 0.f);
-                zend = (int)fminf(fz1, (float)(vol_dim_z - 1));
+                zend = (int)fminf(fz1, (float)(Vol.dim_z - 1));
               }
             }
           }
@@ -1064,7 +1071,7 @@ __device__ __forceinline__ void pix_body(
               atomicMax(&a_lo[kk - agg_k0], (unsigned)(0x7FFF - z));
               atomicMax(&a_hi[kk - agg_k0], (unsigned)(zend + 1));
             } else {
-              col_mark_written(col_zw, col_epoch, chunk_epoch, epoch, n_cols_all, e.x, z, zend);
+              col_mark_written(Mk, n_cols_all, e.x, z, zend);
             }
           }
 #endif
@@ -1110,19 +1117,15 @@ __device__ __forceinline__ void pix_body(
 #endif
           if (mine) {
             if constexpr (MULTI)
-              code = tsdf_voxel_multi(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz,
-                                      voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
-                                      sin_down_lo, wd_px, Cq, z, obs4, n_obs, p_r[sidx]);
+              code = tsdf_voxel_multi(col * Vol.dim_z + z, Vol, Vw, Wd.wd_px, Cq, z, obs4, n_obs, p_r[sidx]);
             else
-              code = tsdf_voxel<true>(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz,
-                                      voxel_size, im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi,
-                                      sin_down_lo, rem_im, wd_px, true, Cq, z, dct, p_r[sidx]);
+              code = tsdf_voxel<true>(col * Vol.dim_z + z, Vol, Vw, rem_im, Wd.wd_px, true, Cq, z, dct, p_r[sidx]);
           }
         }
 #ifdef LT_PIX_NO_BITS  // timing experiment: no sign bits (marching cubes would see nothing)
         code = 0;
 #endif
-        sign_run_merge<false>(sign_bits, code, col, z, words_z, lane);
+        sign_run_merge<false>(Mk.sign_bits, code, col, z, Mk.words_z, lane);
         if (VCOUNT) {  // (one atomic per wave and round: a per-voxel atomic on one address would be the whole kernel)
           const unsigned long long wr = __ballot(code != 0);
           if (lane == 0 && wr) atomicAdd(&dbg[2], (unsigned long long)__popcll(wr));
@@ -1141,11 +1144,11 @@ __device__ __forceinline__ void pix_body(
       for (int i = tid; i < agg_span; i += 256) {
         const unsigned hi1 = a_hi[i];
         if (hi1) {
-          const int c = wd_ent[agg_k0 + i].x;
-          atomicMax(&col_zw[c], a_lo[i]);  // (atomic: with an image height that does not divide 64 two workgroups share a wedge)
-          atomicMax(&col_zw[n_cols_all + c], hi1);
-          col_epoch[c] = epoch;
-          chunk_epoch[c >> 6] = epoch;
+          const int c = Wd.wd_ent[agg_k0 + i].x;
+          atomicMax(&Mk.col_zw[c], a_lo[i]);  // (atomic: with an image height that does not divide 64 two workgroups share a wedge)
+          atomicMax(&Mk.col_zw[n_cols_all + c], hi1);
+          Mk.col_epoch[c] = Mk.epoch;
+          Mk.chunk_epoch[c >> 6] = Mk.epoch;
         }
       }
     LT_PIX_MARK(4);
@@ -1153,58 +1156,42 @@ __device__ __forceinline__ void pix_body(
   }
 }
 
-template <bool MERGE, bool VCOUNT>
+template <bool VCOUNT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_PIX_WPE, 8))) void k_tsdf_integrate_pix(
-    float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
-    float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, float inv_vs, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up,
-    float fov_down, float sin_up_hi, float sin_down_lo, const float* __restrict__ color_im,
-    const float* __restrict__ depth_im, const float* __restrict__ rem_im, const int* __restrict__ wd_px,
-    unsigned* __restrict__ col_epoch, unsigned epoch, unsigned long long* __restrict__ sign_bits, int words_z,
-    unsigned* __restrict__ col_zw, unsigned* __restrict__ chunk_epoch, const float2* __restrict__ dct,
-    const float4* __restrict__ rowtab, const int* __restrict__ wd_start, const int2* __restrict__ wd_ent, const uint32_t* __restrict__ wd_key, int rho_bits,
-    float qscale, const unsigned* __restrict__ zw_snap, unsigned long long* __restrict__ dbg) {
-  pix_body<false, VCOUNT>(tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, inv_vs, im_h, im_w, trunc_margin,
-                          obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, rem_im, nullptr, 1, wd_px, col_epoch, epoch,
-                          sign_bits, words_z, col_zw, chunk_epoch, dct, rowtab, wd_start, wd_ent, wd_key, rho_bits, qscale,
-                          zw_snap, dbg);
+    tsdf_volume Vol, tsdf_view Vw, tsdf_marks Mk, tsdf_wedge Wd, const int* __restrict__ wd_start,
+    const float* __restrict__ rem_im, const float2* __restrict__ dct, const unsigned* __restrict__ zw_snap,
+    unsigned long long* __restrict__ dbg) {
+  pix_body<false, VCOUNT>(Vol, Vw, Mk, Wd, wd_start, rem_im, dct, nullptr, 1, zw_snap, dbg);
 }
 
 template <bool VCOUNT>
-__global__ __launch_bounds__(256) void k_tsdf_integrate_pix_multi(
-    float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
-    float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, float inv_vs, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up,
-    float fov_down, float sin_up_hi, float sin_down_lo, const float4* __restrict__ obs4, int n_obs,
-    const int* __restrict__ wd_px,
-    unsigned* __restrict__ col_epoch, unsigned epoch, unsigned long long* __restrict__ sign_bits, int words_z,
-    unsigned* __restrict__ col_zw, unsigned* __restrict__ chunk_epoch,
-    const float4* __restrict__ rowtab, const int* __restrict__ wd_start, const int2* __restrict__ wd_ent, const uint32_t* __restrict__ wd_key, int rho_bits,
-    float qscale, unsigned long long* __restrict__ dbg) {
-  pix_body<true, VCOUNT>(tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size, inv_vs, im_h, im_w, trunc_margin,
-                         obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, nullptr, obs4, n_obs, wd_px, col_epoch, epoch,
-                         sign_bits, words_z, col_zw, chunk_epoch, nullptr, rowtab, wd_start, wd_ent, wd_key, rho_bits, qscale,
-                         nullptr, dbg);
+__global__ __launch_bounds__(256) void k_tsdf_integrate_pix_multi(tsdf_volume Vol, tsdf_view Vw, tsdf_marks Mk, tsdf_wedge Wd,
+                                                                  const int* __restrict__ wd_start,
+                                                                  const float4* __restrict__ obs4, int n_obs,
+                                                                  unsigned long long* __restrict__ dbg) {
+  pix_body<true, VCOUNT>(Vol, Vw, Mk, Wd, wd_start, nullptr, nullptr, obs4, n_obs, nullptr, dbg);
 }
 
 // the quirk columns (not in the wedge table) for the n observations at once, one thread per voxel
+// (Scalars at its boundary, the structs inside: with the structs as arguments this 5.5 us kernel was 0.3 us slower in two
+// series of kernel traces, profiles/tsdf_kernel_args/README.md)
 __global__ __launch_bounds__(256) void k_tsdf_integrate_quirk_multi(
-    float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
-    float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
-    float sin_up_hi, float sin_down_lo, const float4* __restrict__ obs4, int n_obs, const int* __restrict__ wd_px,
+    float4* __restrict__ vox, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz, float voxel_size,
+    int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down, float sin_up_hi,
+    float sin_down_lo, const float4* __restrict__ obs4, int n_obs, const int* __restrict__ wd_px,
     unsigned* __restrict__ col_epoch, unsigned epoch, unsigned long long* __restrict__ sign_bits, int words_z,
     unsigned* __restrict__ col_zw, unsigned* __restrict__ chunk_epoch, const uint32_t* __restrict__ qcols, int n_q) {
+  const tsdf_volume Vol = {vox, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size};
+  const tsdf_view Vw = {im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo};
+  const tsdf_marks Mk = {col_epoch, epoch, sign_bits, words_z, col_zw, chunk_epoch};
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)n_q * vol_dim_z) return;
-  const int col = (int)qcols[i / vol_dim_z], z = (int)(i % vol_dim_z);
+  if (i >= (long long)n_q * Vol.dim_z) return;
+  const int col = (int)qcols[i / Vol.dim_z], z = (int)(i % Vol.dim_z);
   col_plain C;
-  const int code = tsdf_voxel_multi(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size,
-                                    im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, wd_px,
-                                    C, z, obs4, n_obs);
+  const int code = tsdf_voxel_multi(col * Vol.dim_z + z, Vol, Vw, wd_px, C, z, obs4, n_obs);
   if (code) {
-    if (code == 2) atomicOr(sign_bits + (size_t)col * words_z + (z >> 6), 1ull << (z & 63));  // (fresh volume: the bit is 0)
-    col_mark_written(col_zw, col_epoch, chunk_epoch, epoch, vol_dim_x * vol_dim_y, col, z, z);
+    if (code == 2) atomicOr(Mk.sign_bits + (size_t)col * Mk.words_z + (z >> 6), 1ull << (z & 63));  // (fresh volume: the bit is 0)
+    col_mark_written(Mk, Vol.dim_x * Vol.dim_y, col, z, z);
   }
 }
 
@@ -1227,20 +1214,16 @@ extern "C" int lt_debug_tsdf_stamps(unsigned long long* out, int n_wgs) {
 #ifndef LT_WRITTEN_CHUNKS_PER_WG
 #define LT_WRITTEN_CHUNKS_PER_WG 8  // (swept 4 .. 32 on the default volume: 62 / 58 / 70 / 71 us)
 #endif
-template <bool MERGE>
-__global__ __launch_bounds__(256) void k_tsdf_integrate_written(
-    float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
-    float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
-    float sin_up_hi, float sin_down_lo, const float* __restrict__ color_im, const float* __restrict__ depth_im,
-    const float* __restrict__ rem_im, const int* __restrict__ wd_px, unsigned* __restrict__ col_epoch, unsigned epoch,
-    unsigned long long* __restrict__ sign_bits, int words_z, const unsigned* __restrict__ zw_snap,
-    const float2* __restrict__ dct, const unsigned* __restrict__ chunk_epoch) {
+__global__ __launch_bounds__(256) void k_tsdf_integrate_written(tsdf_volume Vol, tsdf_view Vw, tsdf_marks Mk,
+                                                                const int* __restrict__ wd_px,
+                                                                const float* __restrict__ rem_im,
+                                                                const float2* __restrict__ dct,
+                                                                const unsigned* __restrict__ zw_snap) {
   __shared__ int w_lo[64], w_px[64], w_pre[65];
   __shared__ float w_rho2[64];
   __shared__ unsigned long long w_live;
   const int tid = threadIdx.x, lane = tid & 63;
-  const int n_cols = vol_dim_x * vol_dim_y, n_chunks = (n_cols + 63) / 64;
+  const int n_cols = Vol.dim_x * Vol.dim_y, n_chunks = (n_cols + 63) / 64;
   // a workgroup takes LT_WRITTEN_CHUNKS_PER_WG chunks, a stride apart (lt_deal_count); its first lanes read one stamp each
   // (a workgroup per chunk was 250 000 waves on the default volume, most of which read a stamp and left: 72 -> 58-64 us.
   // Per-workgroup stamps, tools/tsdf_written_times.py: a written chunk holds ~114 voxels in its columns' ranges and costs
@@ -1252,7 +1235,7 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_written(
   if (tid < 64) {
     const int ch = lane * (int)gridDim.x + (int)blockIdx.x;
     const unsigned long long m =
-        __ballot(lane < LT_WRITTEN_CHUNKS_PER_WG && ch < n_chunks && chunk_epoch[min(ch, n_chunks - 1)] == epoch);
+        __ballot(lane < LT_WRITTEN_CHUNKS_PER_WG && ch < n_chunks && Mk.chunk_epoch[min(ch, n_chunks - 1)] == Mk.epoch);
     if (lane == 0) w_live = m;
   }
   __syncthreads();
@@ -1271,10 +1254,10 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_written(
           const int pxq = wd_px[c];
           if (!(pxq & LT_WD_QUIRK_FLAG)) {  // (k_tsdf_integrate_quirk evaluates those columns whole)
             lo = LT_ZW_LO(zw_snap[c]);
-            len = max(min(hi, vol_dim_z - 1) - lo + 1, 0);
+            len = max(min(hi, Vol.dim_z - 1) - lo + 1, 0);
             px = pxq;
-            const int cx = c / vol_dim_y, cy = c - cx * vol_dim_y;
-            const float pt_x = __fmaf_rn((float)cx, voxel_size, ox), pt_y = __fmaf_rn((float)cy, voxel_size, oy);
+            const int cx = c / Vol.dim_y, cy = c - cx * Vol.dim_y;
+            const float pt_x = __fmaf_rn((float)cx, Vol.voxel_size, Vol.ox), pt_y = __fmaf_rn((float)cy, Vol.voxel_size, Vol.oy);
             rho2 = __fmaf_rn(pt_y, pt_y, pt_x * pt_x);
           }
         }
@@ -1300,12 +1283,10 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_written(
         cc = chunk * 64 + sidx;
         z = w_lo[sidx] + (j - w_pre[sidx]);
         const col_plain C = {true, w_px[sidx], w_rho2[sidx], cc};
-        code = tsdf_voxel<MERGE>(cc * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size,
-                                 im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, rem_im,
-                                 wd_px, false, C, z, dct);
+        code = tsdf_voxel<true>(cc * Vol.dim_z + z, Vol, Vw, rem_im, wd_px, false, C, z, dct);
       }
       // the sign of every value written: set the bit (negative) or clear it (a column's range is consecutive in j)
-      sign_run_merge<true>(sign_bits, code, cc, z, words_z, lane);
+      sign_run_merge<true>(Mk.sign_bits, code, cc, z, Mk.words_z, lane);
     }
     __syncthreads();  // the chunk's arrays are reused
 #ifdef LT_TSDF_STAMP
@@ -1324,29 +1305,22 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_written(
 // the columns that are not in the wedge table (k_wd_keys: quirk), one thread per voxel, by the reference's own
 // decomposition of the voxel index (tsdf_voxel's general path; a decomposed (x, y) inside the table finds its image
 // column in wd_px, one outside -- the "(x + 1, -1)" voxels -- computes it)
-template <bool MERGE>
-__global__ __launch_bounds__(256) void k_tsdf_integrate_quirk(
-    float* __restrict__ tsdf_vol, float* __restrict__ weight_vol, float* __restrict__ color_vol,
-    float* __restrict__ rem_vol, int vol_dim_x, int vol_dim_y, int vol_dim_z, float ox, float oy, float oz,
-    float voxel_size, int im_h, int im_w, float trunc_margin, float obs_weight, float fov_up, float fov_down,
-    float sin_up_hi, float sin_down_lo, const float* __restrict__ color_im, const float* __restrict__ depth_im,
-    const float* __restrict__ rem_im, const int* __restrict__ wd_px, unsigned* __restrict__ col_epoch, unsigned epoch,
-    unsigned long long* __restrict__ sign_bits, int words_z, unsigned* __restrict__ col_zw,
-    unsigned* __restrict__ chunk_epoch, const float2* __restrict__ dct, const uint32_t* __restrict__ qcols, int n_q,
-    int fresh) {
+__global__ __launch_bounds__(256) void k_tsdf_integrate_quirk(tsdf_volume Vol, tsdf_view Vw, tsdf_marks Mk,
+                                                              const int* __restrict__ wd_px,
+                                                              const float* __restrict__ rem_im,
+                                                              const float2* __restrict__ dct,
+                                                              const uint32_t* __restrict__ qcols, int n_q, int fresh) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)n_q * vol_dim_z) return;
-  const int col = (int)qcols[i / vol_dim_z], z = (int)(i % vol_dim_z);
+  if (i >= (long long)n_q * Vol.dim_z) return;
+  const int col = (int)qcols[i / Vol.dim_z], z = (int)(i % Vol.dim_z);
   col_plain C;
-  const int code = tsdf_voxel<MERGE>(col * vol_dim_z + z, tsdf_vol, vol_dim_x, vol_dim_y, vol_dim_z, ox, oy, oz, voxel_size,
-                                     im_h, im_w, trunc_margin, obs_weight, fov_up, fov_down, sin_up_hi, sin_down_lo, rem_im,
-                                     wd_px, fresh != 0, C, z, dct);
+  const int code = tsdf_voxel<true>(col * Vol.dim_z + z, Vol, Vw, rem_im, wd_px, fresh != 0, C, z, dct);
   if (code) {
-    unsigned long long* w = sign_bits + (size_t)col * words_z + (z >> 6);
+    unsigned long long* w = Mk.sign_bits + (size_t)col * Mk.words_z + (z >> 6);
     const unsigned long long bit = 1ull << (z & 63);
     if (code == 2) atomicOr(w, bit);
     else atomicAnd(w, ~bit);
-    col_mark_written(col_zw, col_epoch, chunk_epoch, epoch, vol_dim_x * vol_dim_y, col, z, z);
+    col_mark_written(Mk, Vol.dim_x * Vol.dim_y, col, z, z);
   }
 }
 
@@ -1379,13 +1353,25 @@ static tsdf_fov tsdf_fov_of(const lt_tsdf* t) {
 // geometry of the per-column z range: slopes of the field of view with the 1e-5 margin of the sine test on the angles
 static col_geom tsdf_geom(const lt_tsdf* t, const tsdf_fov& F) {
   col_geom G;
-  G.dim_y = t->dim[1]; G.dim_z = t->dim[2];
-  G.ox = t->origin[0]; G.oy = t->origin[1]; G.oz = t->origin[2];
-  G.voxel_size = t->voxel_size;
   G.tan_ok = F.tan_ok;
   G.tan_up = G.tan_ok ? (float)tan((double)F.fu + 1e-5) : 0.f;
   G.tan_down = G.tan_ok ? (float)tan((double)F.fd - 1e-5) : 0.f;
   return G;
+}
+
+// the kernels' argument structs of a volume (and, for the view, of one integrate call)
+static tsdf_volume tsdf_vol_of(const lt_tsdf* t) {
+  return {reinterpret_cast<float4*>(t->tsdf), t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2],
+          t->voxel_size};
+}
+static tsdf_view tsdf_view_of(const lt_tsdf* t, const tsdf_fov& F, int im_h, int im_w, float obs_weight) {
+  return {im_h, im_w, t->trunc_margin, obs_weight, F.fu, F.fd, F.su, F.sd};
+}
+static tsdf_marks tsdf_marks_of(const lt_tsdf* t) {
+  return {t->col_epoch, t->epoch, t->bits, (t->dim[2] + 63) / 64, t->col_zw, t->chunk_epoch};
+}
+static tsdf_wedge tsdf_wedge_of(const lt_tsdf* t) {  // (after tsdf_pix_tables)
+  return {t->wd_px, t->wd_ent, t->wd_key, t->wd_rho_bits, t->wd_qscale, t->rowtab, 1.0f / t->voxel_size};
 }
 
 // a per-call device buffer of `cap` elements that must hold `need`: re-allocated with `alloc` elements when it does not.
@@ -1426,9 +1412,7 @@ extern "C" int lt_tsdf_reset(lt_tsdf* t, void* stream) {
   const int n_cols = t->dim[0] * t->dim[1];
   const int n_chunks = (n_cols + 63) / 64;
   hipLaunchKernelGGL(k_tsdf_reset_cols, dim3((unsigned)(lt_deal_count(n_chunks, LT_RESET_CHUNKS_PER_WAVE, t->dim[1], 4) / 4)),
-                     dim3(256), 0, (hipStream_t)stream,
-                     t->tsdf, t->weight, t->color, t->rem, n_cols, t->dim[2], t->col_epoch, t->epoch, t->bits, t->col_zw,
-                     t->chunk_epoch);
+                     dim3(256), 0, (hipStream_t)stream, tsdf_vol_of(t), tsdf_marks_of(t));
   LT_HIP(hipGetLastError());
   t->epoch += 1;  // every stamp is stale now: nothing to clear
   t->n_obs = 0;
@@ -1668,10 +1652,6 @@ static unsigned tsdf_pix_grid(const lt_tsdf* t, size_t n_pix, int waves_per_eu) 
 // k_tsdf_integrate_pix_multi carries no waves_per_eu attribute: this is its compiler-reported occupancy (96 VGPRs, 27.5 KB
 // of LDS), not LT_PIX_WPE, which a -D can change
 #define LT_PIX_MULTI_WPE 5
-// what the argument list of every integrate kernel starts with: the volume, and (after inv_vs, where there is one) the view
-#define LT_VOL_ARGS \
-  t->tsdf, t->weight, t->color, t->rem, t->dim[0], t->dim[1], t->dim[2], t->origin[0], t->origin[1], t->origin[2], t->voxel_size
-#define LT_VIEW_ARGS im_h, im_w, t->trunc_margin, obs_weight, F.fu, F.fd, F.su, F.sd
 
 static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* depth_im, const float* rem_im, int im_h,
                               int im_w, float obs_weight, const tsdf_fov& F, int rho_bits, bool fresh_volume,
@@ -1680,7 +1660,10 @@ static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* de
   const size_t n_pix = (size_t)im_w * im_h;
   LT_CHECK(tsdf_grow(t->dct, t->cap_dct, n_pix, n_pix));
   hipLaunchKernelGGL(k_tsdf_dct, dim3((im_h * im_w + 255) / 256), dim3(256), 0, stream, depth_im, color_im, im_h, im_w, t->dct);
-  const int words_z = (t->dim[2] + 63) / 64;
+  const tsdf_volume Vol = tsdf_vol_of(t);
+  const tsdf_view Vw = tsdf_view_of(t, F, im_h, im_w, obs_weight);
+  const tsdf_marks Mk = tsdf_marks_of(t);
+  const tsdf_wedge Wd = tsdf_wedge_of(t);
   const unsigned nb = tsdf_pix_grid(t, n_pix, LT_PIX_WPE);
   const unsigned* zw_snap = nullptr;
   if (!fresh_volume) {
@@ -1690,27 +1673,24 @@ static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* de
     if (!t->zw_snap) LT_HIP(hipMalloc((void**)&t->zw_snap, 2 * n_cols * sizeof(unsigned)));
     LT_HIP(hipMemcpyAsync(t->zw_snap, t->col_zw, 2 * n_cols * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
     zw_snap = t->zw_snap;
-    hipLaunchKernelGGL(k_tsdf_integrate_written<true>,
+    hipLaunchKernelGGL(k_tsdf_integrate_written,
                        dim3((unsigned)lt_deal_count((int)((n_cols + 63) / 64), LT_WRITTEN_CHUNKS_PER_WG, t->dim[1], 1)), dim3(256), 0,
-                       stream, LT_VOL_ARGS, LT_VIEW_ARGS, color_im, depth_im, rem_im, t->wd_px, t->col_epoch, t->epoch, t->bits,
-                       words_z, zw_snap, t->dct, t->chunk_epoch);
+                       stream, Vol, Vw, Mk, Wd.wd_px, rem_im, t->dct, zw_snap);
   }
   // LIDARHIP_DEBUG_TSDF=1: pairs / candidate voxels / written voxels of the launch (lt_debug_tsdf_pix_counts)
   static const bool want_cnt = getenv("LIDARHIP_DEBUG_TSDF") != nullptr;
   if (want_cnt && !g_pix_dbg) LT_HIP(hipMalloc((void**)&g_pix_dbg, 8 * sizeof(unsigned long long)));
   if (want_cnt) LT_HIP(hipMemsetAsync(g_pix_dbg, 0, 8 * sizeof(unsigned long long), stream));
-#define LT_PIX_ARGS                                                                                                         \
-  LT_VOL_ARGS, 1.0f / t->voxel_size, LT_VIEW_ARGS, color_im, depth_im, rem_im, t->wd_px, t->col_epoch, t->epoch, t->bits,   \
-      words_z, t->col_zw, t->chunk_epoch, t->dct, t->rowtab, t->wd_start, t->wd_ent, t->wd_key, t->wd_rho_bits, t->wd_qscale, \
-      zw_snap, g_pix_dbg
-  if (want_cnt) hipLaunchKernelGGL((k_tsdf_integrate_pix<true, true>), dim3(nb), dim3(256), 0, stream, LT_PIX_ARGS);
-  else hipLaunchKernelGGL((k_tsdf_integrate_pix<true, false>), dim3(nb), dim3(256), 0, stream, LT_PIX_ARGS);
-#undef LT_PIX_ARGS
+  if (want_cnt)
+    hipLaunchKernelGGL(k_tsdf_integrate_pix<true>, dim3(nb), dim3(256), 0, stream, Vol, Vw, Mk, Wd, t->wd_start, rem_im, t->dct,
+                       zw_snap, g_pix_dbg);
+  else
+    hipLaunchKernelGGL(k_tsdf_integrate_pix<false>, dim3(nb), dim3(256), 0, stream, Vol, Vw, Mk, Wd, t->wd_start, rem_im, t->dct,
+                       zw_snap, g_pix_dbg);
   if (t->wd_n_quirk > 0) {
     const long long nv = (long long)t->wd_n_quirk * t->dim[2];
-    hipLaunchKernelGGL(k_tsdf_integrate_quirk<true>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, LT_VOL_ARGS,
-                       LT_VIEW_ARGS, color_im, depth_im, rem_im, t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, t->col_zw,
-                       t->chunk_epoch, t->dct, t->wd_qcols, t->wd_n_quirk, fresh_volume ? 1 : 0);
+    hipLaunchKernelGGL(k_tsdf_integrate_quirk, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, Vol, Vw, Mk, Wd.wd_px,
+                       rem_im, t->dct, t->wd_qcols, t->wd_n_quirk, fresh_volume ? 1 : 0);
   }
   LT_HIP(hipGetLastError());
   return LT_OK;
@@ -1807,16 +1787,18 @@ extern "C" int lt_tsdf_integrate_dev(lt_tsdf* t, const float* color_im, const fl
   LT_CHECK(tsdf_grow(t->colmax, t->cap_w, (size_t)im_w, (size_t)im_w));
   LT_CHECK(tsdf_grow(t->dct, t->cap_dct, (size_t)im_w * im_h, (size_t)im_w * im_h));
   const int n_cols = t->dim[0] * t->dim[1];
-  const col_geom G = tsdf_geom(t, F);
   // behind the table: one flag per chunk of 64 columns, then the walks' z ranges and the columns' rho^2
   const size_t n_flags = ((size_t)n_cols + 63) / 64 + 64;
+  int* chunk_live = t->colinfo + n_cols;
   unsigned* colz = (unsigned*)(t->colinfo + n_cols + n_flags);
   float* colrho2 = (float*)(t->colinfo + n_cols + n_flags + n_cols);
   hipLaunchKernelGGL(k_tsdf_colmax, dim3((im_w + 63) / 64), dim3(256), 0, stream, depth_im, color_im, im_h, im_w, t->colmax,
                      t->dct);
-  hipLaunchKernelGGL(k_tsdf_columns, dim3((n_cols + 255) / 256), dim3(256), 0, stream, t->dim[0], t->dim[1], t->origin[0],
-                     t->origin[1], t->voxel_size, im_w, t->trunc_margin, t->colmax, t->colinfo, t->colinfo + n_cols, G,
-                     t->dim[2], colz, colrho2);
+  const tsdf_volume Vol = tsdf_vol_of(t);
+  const tsdf_view Vw = tsdf_view_of(t, F, im_h, im_w, obs_weight);
+  const tsdf_marks Mk = tsdf_marks_of(t);
+  hipLaunchKernelGGL(k_tsdf_columns, dim3((n_cols + 255) / 256), dim3(256), 0, stream, Vol, Vw, tsdf_geom(t, F), t->colmax,
+                     t->colinfo, chunk_live, colz, colrho2);
   static const int env_blocks = []() { const char* e = getenv("LIDARHIP_TSDF_BLOCKS"); return e ? atoi(e) : 0; }();
   const unsigned nbc = (unsigned)min((n_cols + 63) / 64, env_blocks > 0 ? env_blocks : (1 << 20));  // a chunk of 64 columns each
   // debug (LIDARHIP_DEBUG_TSDF=1, tools/tsdf_wave_times.py): start / duration of every wave at 100 MHz
@@ -1829,12 +1811,12 @@ extern "C" int lt_tsdf_integrate_dev(lt_tsdf* t, const float* color_im, const fl
   // kA = NaN switches it off and every voxel takes the exact evaluation
   const bool band_ok = fabsf(F.su) <= 0.5f && fabsf(F.sd) <= 0.5f && fov_abs / (float)im_h >= 2e-4f;
   const float kA = band_ok ? -(float)im_h / fov_abs : NAN, kB = (float)im_h * (1.0f - fabsf(F.fd) / fov_abs);
-#define LT_COLS_ARGS                                                                                                     \
-  LT_VOL_ARGS, LT_VIEW_ARGS, color_im, depth_im, rem_im, t->colinfo, t->col_epoch, t->epoch, G, t->bits,                 \
-      (t->dim[2] + 63) / 64, t->col_zw, t->dct, kA, kB, t->colinfo + n_cols, colz, colrho2, t->all_dirty, dbg, t->chunk_epoch
-  if (flags & LT_TSDF_MERGE) hipLaunchKernelGGL(k_tsdf_integrate_cols<true>, dim3(nbc), dim3(256), 0, stream, LT_COLS_ARGS);
-  else hipLaunchKernelGGL(k_tsdf_integrate_cols<false>, dim3(nbc), dim3(256), 0, stream, LT_COLS_ARGS);
-#undef LT_COLS_ARGS
+  if (flags & LT_TSDF_MERGE)
+    hipLaunchKernelGGL(k_tsdf_integrate_cols<true>, dim3(nbc), dim3(256), 0, stream, Vol, Vw, Mk, rem_im, t->dct, t->colinfo,
+                       chunk_live, colz, colrho2, kA, kB, t->all_dirty, dbg);
+  else
+    hipLaunchKernelGGL(k_tsdf_integrate_cols<false>, dim3(nbc), dim3(256), 0, stream, Vol, Vw, Mk, rem_im, t->dct, t->colinfo,
+                       chunk_live, colz, colrho2, kA, kB, t->all_dirty, dbg);
   LT_HIP(hipGetLastError());
   return LT_OK;
 }
@@ -1871,16 +1853,19 @@ extern "C" int lt_tsdf_integrate_multi_dev(lt_tsdf* t, int n_obs, const float* c
       O.color[k] = color_ims[q]; O.depth[k] = depth_ims[q]; O.rem[k] = rem_ims[q];
     }
     hipLaunchKernelGGL(k_tsdf_dct4, dim3((unsigned)((n * n_pix + 255) / 256)), dim3(256), 0, stream, O, n, im_h, im_w, t->obs4);
-    const int words_z = (t->dim[2] + 63) / 64;
-    hipLaunchKernelGGL((k_tsdf_integrate_pix_multi<false>), dim3(tsdf_pix_grid(t, n_pix, LT_PIX_MULTI_WPE)), dim3(256), 0, stream,
-                       LT_VOL_ARGS, 1.0f / t->voxel_size, LT_VIEW_ARGS, (const float4*)t->obs4, n, t->wd_px, t->col_epoch,
-                       t->epoch, t->bits, words_z, t->col_zw, t->chunk_epoch, t->rowtab, t->wd_start, t->wd_ent, t->wd_key,
-                       t->wd_rho_bits, t->wd_qscale, (unsigned long long*)nullptr);
+    const tsdf_volume Vol = tsdf_vol_of(t);
+    const tsdf_view Vw = tsdf_view_of(t, F, im_h, im_w, obs_weight);
+    const tsdf_marks Mk = tsdf_marks_of(t);
+    const tsdf_wedge Wd = tsdf_wedge_of(t);
+    hipLaunchKernelGGL(k_tsdf_integrate_pix_multi<false>, dim3(tsdf_pix_grid(t, n_pix, LT_PIX_MULTI_WPE)), dim3(256), 0, stream,
+                       Vol, Vw, Mk, Wd, t->wd_start, t->obs4, n, (unsigned long long*)nullptr);
     if (t->wd_n_quirk > 0) {
       const long long nv = (long long)t->wd_n_quirk * t->dim[2];
-      hipLaunchKernelGGL(k_tsdf_integrate_quirk_multi, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, LT_VOL_ARGS,
-                         LT_VIEW_ARGS, (const float4*)t->obs4, n, t->wd_px, t->col_epoch, t->epoch, t->bits, words_z, t->col_zw,
-                         t->chunk_epoch, t->wd_qcols, t->wd_n_quirk);
+      hipLaunchKernelGGL(k_tsdf_integrate_quirk_multi, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, Vol.vox,
+                         Vol.dim_x, Vol.dim_y, Vol.dim_z, Vol.ox, Vol.oy, Vol.oz, Vol.voxel_size, Vw.im_h, Vw.im_w,
+                         Vw.trunc_margin, Vw.obs_weight, Vw.fov_up, Vw.fov_down, Vw.sin_up_hi, Vw.sin_down_lo, t->obs4, n,
+                         Wd.wd_px, Mk.col_epoch, Mk.epoch, Mk.sign_bits, Mk.words_z, Mk.col_zw, Mk.chunk_epoch, t->wd_qcols,
+                         t->wd_n_quirk);
     }
     LT_HIP(hipGetLastError());
     t->n_obs += n;

@@ -178,7 +178,10 @@ H, W = (int(sys.argv[6]), int(sys.argv[7])) if len(sys.argv) > 7 else (32, 256)
 rng = np.random.default_rng(5)
 yaw = np.linspace(-np.pi, np.pi, W)
 half = 15.0 if voxel < 0.1 else 20.0
-vol = TSDFVolume(np.array([[-half, half], [-half, half], [-5.0, 5.0]]), voxel, fu, fd, merge=merge)   # 0.05: 600 x 600 x 200 = 72 M voxels
+bnds = [[-half, half], [-half, half], [-5.0, 5.0]]   # 0.05: 600 x 600 x 200 = 72 M voxels
+if len(sys.argv) > 8:
+    bnds = np.array([float(x) for x in sys.argv[8].split(",")]).reshape(3, 2)
+vol = TSDFVolume(np.array(bnds), voxel, fu, fd, merge=merge)
 if os.environ.get("LT_TEST_TSDF") == "dense":
     # the A/B partner: the one-thread-per-voxel restatement of the reference kernel (oracle/lt_tsdf_dense.hip, an
     # ORACLE library) writes the volume's fields through their raw pointers; the product only allocates and resets them
@@ -238,12 +241,25 @@ np.savez(sys.argv[1], **{f"{k}{i}": a for k, v in out.items() for i, a in enumer
 """
 
 
-@pytest.mark.parametrize("merge,fu,fd,voxel,hw", [(True, 10.0, -25.0, 0.05, (32, 256)), (False, 10.0, -25.0, 0.05, (32, 256)),
-                                                   (True, 40.0, -50.0, 0.05, (32, 256)), (True, 2.0, -24.8, 0.05, (32, 256)),
-                                                   (True, 10.0, -25.0, 0.25, (32, 256)), (False, 10.0, -25.0, 0.25, (32, 256)),
-                                                   (True, 15.0, -20.0, 0.25, (25, 301)), (True, 5.0, -30.0, 0.25, (70, 97)),
-                                                   (True, 10.0, -25.0, 0.05, (32, 64))])
-def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge, fu, fd, voxel, hw):
+# 161 x 163 x 37 voxels at 0.25: 26 243 columns = 410 * 64 + 3 -- the last chunk of 64 columns is partial -- and a dim_z that
+# is neither a multiple of 16 (a quarter wave's z step) nor of 64 (a sign word)
+_ODD_BNDS = ((-20.0, 20.25), (-20.0, 20.75), (-5.0, 4.25))
+
+
+def _cases_with_bnds(cases, odd):
+    """`cases` with bnds = None (the symmetric volume) under the ids they had before the bounds argument, then `odd`."""
+    def old_id(i, c):
+        return "-".join(f"hw{i}" if isinstance(v, tuple) else str(v) for v in c)
+    return [pytest.param(*c, None, id=old_id(i, c)) for i, c in enumerate(cases)] + [pytest.param(*odd, id="odd-volume")]
+
+
+@pytest.mark.parametrize("merge,fu,fd,voxel,hw,bnds", _cases_with_bnds(
+    [(True, 10.0, -25.0, 0.05, (32, 256)), (False, 10.0, -25.0, 0.05, (32, 256)),
+     (True, 40.0, -50.0, 0.05, (32, 256)), (True, 2.0, -24.8, 0.05, (32, 256)),
+     (True, 10.0, -25.0, 0.25, (32, 256)), (False, 10.0, -25.0, 0.25, (32, 256)),
+     (True, 15.0, -20.0, 0.25, (25, 301)), (True, 5.0, -30.0, 0.25, (70, 97)),
+     (True, 10.0, -25.0, 0.05, (32, 64))], (True, 5.0, -30.0, 0.25, (70, 97), _ODD_BNDS)))
+def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge, fu, fd, voxel, hw, bnds):
     """The work-saving integrate (per-column image column and dead-column test, conservative sine test, dirty-column
     reset) against the plain one-thread-per-voxel restatement of the reference kernel (oracle/lt_tsdf_dense.hip: an ORACLE
     library, not in liblidarhip.so) on a 72 M-voxel volume -- beyond 2^24
@@ -263,10 +279,12 @@ def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge,
     of 64 pixels spans two image columns -- every workgroup's search range exceeds LT_PIX_STAGE (3840) and takes the
     unstaged search in global memory; and its pairs fall on two wedges (a colour-0 pixel at 9 m alone on 0.5 * 0.098 * 81 /
     0.0025 ~ 1600 entries): more than LT_PIX_AGG (1024) table entries, so the workgroups mark the columns' written ranges
-    directly (col_mark_written) instead of merging them in LDS."""
+    directly (col_mark_written) instead of merging them in LDS.  bnds (optional; _ODD_BNDS): a volume whose last chunk of 64
+    columns holds 3 -- what the column walk, the pass over the written ranges and the reset do per chunk."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bnds_arg = [",".join(str(x) for lo_hi in bnds for x in lo_hi)] if bnds is not None else []
     res = {}
     for mode in ("cols", "walk", "pix1", "dense"):
         env = dict(os.environ)
@@ -280,7 +298,7 @@ def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge,
             env["LIDARHIP_TSDF_PIX"] = "1"
         path = str(tmp_path / f"{mode}.npz")
         r = subprocess.run([sys.executable, "-c", _AB_SCRIPT % root, path, "1" if merge else "0", str(fu), str(fd), str(voxel),
-                            str(hw[0]), str(hw[1])],
+                            str(hw[0]), str(hw[1])] + bnds_arg,
                            env=env,
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -294,15 +312,18 @@ def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge,
     rx, ry = (slice(60, 160), slice(380, 520)) if voxel < 0.1 else (slice(20, 60), slice(100, 140))
     assert (res["cols"]["third0"][rx, ry, :] != 0.25).any()   # the touched region was observed
     t = res["cols"]["first0"]
+    if bnds is _ODD_BNDS:
+        assert t.shape == (161, 163, 37), t.shape
     assert (t < 0).sum() > (10000 if voxel < 0.1 else 1000) and (t != 1).mean() < 0.5
     if voxel > 0.2:   # voxels next to the sensor written through the all -1 image columns (trunc_margin 1.25 m > 1)
         assert (res["dense"]["first1"] != 0).sum() > 0
 
 
-@pytest.mark.parametrize("fu,fd,voxel,hw,n_obs", [(10.0, -25.0, 0.05, (32, 256), 4), (5.0, -30.0, 0.25, (70, 97), 3),
-                                                    (10.0, -25.0, 0.05, (32, 256), 11), (40.0, -50.0, 0.05, (32, 256), 2),
-                                                    (10.0, -25.0, 0.05, (32, 64), 3), (5.0, -30.0, 0.25, (70, 97), 9)])
-def test_fused_observations_equal_one_integrate_per_observation(fu, fd, voxel, hw, n_obs):
+@pytest.mark.parametrize("fu,fd,voxel,hw,n_obs,bnds", _cases_with_bnds(
+    [(10.0, -25.0, 0.05, (32, 256), 4), (5.0, -30.0, 0.25, (70, 97), 3),
+     (10.0, -25.0, 0.05, (32, 256), 11), (40.0, -50.0, 0.05, (32, 256), 2),
+     (10.0, -25.0, 0.05, (32, 64), 3), (5.0, -30.0, 0.25, (70, 97), 9)], (5.0, -30.0, 0.25, (70, 97), 3, _ODD_BNDS)))
+def test_fused_observations_equal_one_integrate_per_observation(fu, fd, voxel, hw, n_obs, bnds):
     """lt_tsdf_integrate_multi_dev -- all observations of a fresh volume in ONE pixel pass, the updates applied in order on
     the voxel's state in registers -- against one lt_tsdf_integrate_dev per observation (itself bit-identical to the
     one-thread-per-voxel restatement of the reference kernel, test above): the four fields bit for bit, the mesh extracted
@@ -314,14 +335,16 @@ def test_fused_observations_equal_one_integrate_per_observation(fu, fd, voxel, h
     LT_TSDF_MULTI_MAX, then one observation through zw_snap.  Image 32 x 64 at voxel 0.05: a wedge of the 600 x 600 columns
     is a 5.6 degree sector of at least 0.5 * 0.098 * 15^2 / 0.0025 ~ 4400 columns and a group of 64 pixels spans two image
     columns, so the fused kernel's searches are unstaged (more than LT_PIX_STAGE = 3840 quanta) and a workgroup's pairs, on
-    two wedges, span more than LT_PIX_AGG = 1024 entries (written ranges marked directly), as in the test above."""
+    two wedges, span more than LT_PIX_AGG = 1024 entries (written ranges marked directly), as in the test above.  bnds
+    (optional; _ODD_BNDS): 161 x 163 x 37 voxels, the last chunk of 64 columns partial."""
     import torch
     from lidar_transfer_amd.fusion import TSDFVolume
     H, W = hw
     rng = np.random.default_rng(17)
     yaw = np.linspace(-np.pi, np.pi, W)
     half = 15.0 if voxel < 0.1 else 20.0
-    bnds = np.array([[-half, half], [-half, half], [-5.0, 5.0]])
+    odd = bnds is _ODD_BNDS
+    bnds = np.array([[-half, half], [-half, half], [-5.0, 5.0]] if bnds is None else bnds)
     base = (6.0 + 3.0 * np.sin(3 * yaw)[None, :] + 0.2 * rng.random((H, W))).astype(np.float32)
     lab0 = rng.choice(np.array([0.0, 40.0, 50.0]), (H, W), p=[0.1, 0.6, 0.3]).astype(np.float32)
     obs = []
@@ -349,6 +372,7 @@ def test_fused_observations_equal_one_integrate_per_observation(fu, fd, voxel, h
         fused.integrate_multi(obs)
         torch.cuda.synchronize()
         a, b = seq.get_volume_tensors(), fused.get_volume_tensors()
+        assert not odd or tuple(a[0].shape) == (161, 163, 37), a[0].shape
         for name, x, y in zip(("tsdf", "weight", "color", "rem"), a, b):
             same = torch.equal(x.view(torch.int32), y.view(torch.int32))
             assert same, f"round {rnd}: {name} differs in {int((x.view(torch.int32) != y.view(torch.int32)).sum())} voxels"
