@@ -27,6 +27,7 @@
 //   (the z-min cells and the two queues are the state of a render in flight: they belong to the scene)
 #include "lt_internal.h"
 #include <math.h>
+#include <type_traits>
 #include <stdlib.h>
 #include <string.h>
 #include "lt_normalize.h"
@@ -616,12 +617,38 @@ __device__ __forceinline__ void sc_prefix(sc_shared& S, const sc_one rA, const s
 // lanes of a wave hold 64 consecutive candidates = consecutive bins of a few neighbouring triangles, so the
 // grid loads and the atomics of a wave fall into a handful of cache lines, and every lane runs the same
 // number of Moller-Trumbore tests no matter how unevenly the triangles cover the image.  (A contiguous chunk
-// per thread needs no search but made every lane touch its own lines: L2 bound.)  The loop is
-// software-pipelined: the search and the grid load of the NEXT candidate are issued before the triangle test
-// of the current one.
+// per thread needs no search but made every lane touch its own lines: L2 bound.)
+// A lane takes its candidates in BLOCKS of LT_SC_PB rounds (c, c + NT, ..., c + (LT_SC_PB - 1) NT), three stages a block:
+//   1 locate + load: the searches of the block run in lockstep (step loop outside, candidates inside: LT_SC_PB independent
+//     LDS chains, the latency of one), then the grid loads are issued back to back -- the block pays ONE round trip;
+//   2 test: Moller-Trumbore for each, the accepted hit (t, ray, slot) stays in registers;
+//   3 hits last: the block's atomicMins.
+// Why: vmcnt counts loads, stores and atomics together and retires them IN ORDER, so a load issued after an atomic cannot
+// be consumed before that memory-side atomic has come back.  The earlier loop (prefetch of the next candidate before the
+// test of the current one, atomic right after the test) compiled to an s_waitcnt vmcnt(0) in every round that waited
+// for the prefetch just issued AND for the previous round's atomic: search -> load -> wait -> test -> atomic -> wait, per
+// round.  Now a wave meets its own atomics once per 256 x LT_SC_PB candidates (profiles/sc_phaseb/README.md).
+// A sub-round that NO lane of the wave has (round-robin dealing makes that wave-uniform up to the one wave holding c_end)
+// is not searched at all: the block is instantiated for 1 .. LT_SC_PB live sub-rounds -- the search + bin arithmetic of
+// candidates nobody has were 9 % of the kernel's vector instructions once.  A lane without a
+// candidate in a live sub-round searches and loads the clamped index c_end - 1 (no lane-level branch around the loads) and
+// neither counts nor tests it.  Bins with several rays (LT_GRID_MULTI, irregular ray sets) keep their loop over the bin's
+// rays and their immediate atomics, in stage 2 right after their candidate's own test: a pass of their own behind the
+// three tests kept all three grid entries alive across them (71 - 77 VGPRs instead of 55 - 62).
+#ifndef LT_SC_PB
+#define LT_SC_PB 3  // rounds per block: 2, 3, 4 measured (profiles/sc_phaseb/README.md); -DLT_SC_PB=1 is one round at a time
+#endif
+static_assert(LT_SC_PB >= 1 && LT_SC_PB <= 4, "LT_SC_PB: 1 .. 4");
+// k_sc_rest runs its slices (LT_SC_SLICE / 256 = 2 rounds of a workgroup) one round per block: holding a hit back across
+// the second test costs it 4 registers (66 - 72 instead of 62 - 68 VGPRs: 7 instead of 8 waves per SIMD for the variant
+// that ships), and one round per block allocates exactly what the earlier loop did.  -DLT_SC_PB_REST=2 for A/B.
+#ifndef LT_SC_PB_REST
+#define LT_SC_PB_REST 1
+#endif
+static_assert(LT_SC_PB_REST >= 1 && LT_SC_PB_REST <= 4, "LT_SC_PB_REST: 1 .. 4");
 // NT = lanes sharing the candidates (256: a workgroup; 64: one wave of k_sc_rest), NE = entries of the prefix array the
 // descent covers (a power of two; the array has NE + 1 entries, all-ones beyond the slots in use), tix = this lane's index
-template <bool COUNT, bool WIDE, int NT, int NE>
+template <bool COUNT, bool WIDE, int NT, int NE, int PB>
 __device__ __forceinline__ void sc_round_robin(const unsigned* s_pre, const float4* s_q0, const float4* s_q1,
                                                const float2* s_q2, const rs_params& P, const float4* __restrict__ grid,
                                                const float4* __restrict__ sdirs, unsigned long long* __restrict__ cell,
@@ -633,20 +660,10 @@ __device__ __forceinline__ void sc_round_robin(const unsigned* s_pre, const floa
   auto ld2 = [](const float2* arr, unsigned j4) { return *(const float2*)((const char*)arr + 2u * j4); };
   const unsigned pre0 = s_pre[0];
   // slot j = largest j with prefix[j] <= c (pre = prefix << 13 | a0: compare against c << 13 | all-ones); the entry found is
-  // carried along, so the descent needs no read of pre[j] afterwards; returns the bin and the record's third word
-  auto locate = [&](int c, unsigned& j4, float2& q2) -> int {
-    const unsigned ck = ((unsigned)c << 13) | 0x1FFFu;
-    j4 = 0;
-    unsigned base = pre0;
-#pragma unroll
-    for (unsigned step4 = 2u * NE; step4 >= 4; step4 >>= 1) {
-      const unsigned v = ldu(s_pre, j4 + step4);
-      const bool take = v <= ck;
-      j4 = take ? j4 + step4 : j4;
-      base = take ? v : base;
-    }
+  // carried along, so the descent needs no read of pre[j] afterwards.  bin_of: the candidate's bin from the entry found
+  // and the record's third word
+  auto bin_of = [&](int c, unsigned base, const float2 q2) -> int {
     const int local = c - (int)(base >> 13);
-    q2 = ld2(s_q2, j4);
     const int pk = __float_as_int(q2.y);
     const int na = (pk & 511) + 1;
     // local / na: (local + 0.5) / na is >= 0.5 / na away from an integer and local / na <= LT_SC_BIG / na, so
@@ -657,31 +674,71 @@ __device__ __forceinline__ void sc_round_robin(const unsigned* s_pre, const floa
     if (az >= P.nb_az) az -= P.nb_az;
     return __mul24((pk >> 9) + row, P.nb_az) + az;
   };
-  int c = c_begin + tix;
-  if (c < c_end) {
-    unsigned j4;
-    float2 q2;
-    float4 g = *at<false>(grid, (unsigned)locate(c, j4, q2));  // <= 8192 x 4096 bins x 16 B: always < 4 GB
-    for (;;) {
-      // prefetch of the next candidate (index clamped to the last one: no lane-level branch, the load stays in flight
-      // across the test) -- unless NO lane of the wave has one: round-robin dealing makes that wave-uniform up to the
-      // one wave holding c_end, and the search + bin arithmetic of a prefetch nobody uses were 9 % of the kernel's
-      // vector instructions
-      const int cn = c + NT;
-      unsigned jn4 = 0;
-      float2 q2n = make_float2(0.f, 0.f);
-      float4 gn = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (__ballot(cn < c_end) != 0ull) gn = *at<false>(grid, (unsigned)locate(min(cn, c_end - 1), jn4, q2n));
-      const float4 q0 = ldq(s_q0, j4), q1 = ldq(s_q1, j4);
+  // one block of N live sub-rounds; this lane's candidates are cb + u NT (the first one exists: cb < c_end)
+  auto block = [&](auto n_tag, const int cb) {
+    constexpr int N = decltype(n_tag)::value;
+    // stage 1: N descents in lockstep, then N grid loads with nothing to wait for between them
+    int cc[N];
+    unsigned ck[N], j4[N], base[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      cc[u] = min(cb + u * NT, c_end - 1);
+      ck[u] = ((unsigned)cc[u] << 13) | 0x1FFFu;
+      j4[u] = 0;
+      base[u] = pre0;
+    }
+#pragma unroll
+    for (unsigned step4 = 2u * NE; step4 >= 4; step4 >>= 1) {
+#pragma unroll
+      for (int u = 0; u < N; ++u) {
+        const unsigned v = ldu(s_pre, j4[u] + step4);
+        const bool take = v <= ck[u];
+        j4[u] = take ? j4[u] + step4 : j4[u];
+        base[u] = take ? v : base[u];
+      }
+    }
+    float2 q2[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) q2[u] = ld2(s_q2, j4[u]);
+    float4 g[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) g[u] = *at<false>(grid, (unsigned)bin_of(cc[u], base[u], q2[u]));  // <= 8192 x 4096 bins x 16 B: always < 4 GB
+    // stage 2: the tests; th = the accepted t of a single-ray bin, NaN otherwise (no candidate, no hit, empty or multi bin)
+    float th[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      const bool act = cb + u * NT < c_end;
+      const float4 q0 = ldq(s_q0, j4[u]), q1 = ldq(s_q1, j4[u]);
       tri_rec T;
       T.v0x = q0.x; T.v0y = q0.y; T.v0z = q0.z;
       T.e1x = q0.w; T.e1y = q1.x; T.e1z = q1.y;
-      T.e2x = q1.z; T.e2y = q1.w; T.e2z = q2.x;
-      if (COUNT) ++n_cand;
-      sc_test_cell<WIDE>(T, first_face + (int)(j4 >> 2), g, sdirs, ox, oy, oz, cell, n_tests);
-      if (cn >= c_end) break;
-      c = cn; j4 = jn4; g = gn; q2 = q2n;
+      T.e2x = q1.z; T.e2y = q1.w; T.e2z = q2[u].x;
+      const int w = __float_as_int(g[u].w);
+      if (COUNT) n_cand += act ? 1u : 0u;
+      n_tests += act && w >= 0 ? 1u : 0u;
+      const float t = sc_mt(T, ox, oy, oz, g[u].x, g[u].y, g[u].z);
+      th[u] = act && w != LT_GRID_MULTI ? t : NAN;
+      // (irregular ray sets) the bin's rays one after the other, atomics at once
+      if (act && w == LT_GRID_MULTI) sc_test_cell<WIDE>(T, first_face + (int)(j4[u] >> 2), g[u], sdirs, ox, oy, oz, cell, n_tests);
     }
+    // stage 3: hits last -- nothing this block loaded is waited for behind these
+#pragma unroll
+    for (int u = 0; u < N; ++u) sc_hit<WIDE>(th[u], __float_as_int(g[u].w), first_face + (int)(j4[u] >> 2), cell);
+  };
+  for (int cb = c_begin + tix; cb < c_end; cb += PB * NT) {
+    int live = 1;  // sub-rounds in which a lane of this wave has a candidate (they end together: c grows with u)
+#pragma unroll
+    for (int u = 1; u < PB; ++u) live += __ballot(cb + u * NT < c_end) != 0ull ? 1 : 0;
+    if constexpr (PB >= 4) {
+      if (live == 4) { block(std::integral_constant<int, 4>{}, cb); continue; }
+    }
+    if constexpr (PB >= 3) {
+      if (live == 3) { block(std::integral_constant<int, 3>{}, cb); continue; }
+    }
+    if constexpr (PB >= 2) {
+      if (live == 2) { block(std::integral_constant<int, 2>{}, cb); continue; }
+    }
+    block(std::integral_constant<int, 1>{}, cb);
   }
 }
 
@@ -776,8 +833,8 @@ __global__ __launch_bounds__(256) void k_sc_tris(const sc_batch B) {
   __syncthreads();
   const int kept = S.kept;
   unsigned n_tests = 0, n_cand = 0;
-  sc_round_robin<COUNT, WIDE, 256, (LT_SC_T > 256 ? 512 : 256)>(S.pre, S.q0, S.q1, S.q2, P, J.grid, J.sdirs, J.cell, first, 0,
-                                                                kept, tid, ox, oy, oz, n_tests, n_cand);
+  sc_round_robin<COUNT, WIDE, 256, (LT_SC_T > 256 ? 512 : 256), LT_SC_PB>(S.pre, S.q0, S.q1, S.q2, P, J.grid, J.sdirs, J.cell,
+                                                                          first, 0, kept, tid, ox, oy, oz, n_tests, n_cand);
   sc_count<COUNT>(n_tests, n_cand, J.counters);
 }
 
@@ -819,9 +876,9 @@ __global__ __launch_bounds__(256) void k_sc_rest(const sc_batch B) {
     int total, preA, preB;
     sc_prefix(S, rA, rB, preA, preB, total);
     __syncthreads();
-    sc_round_robin<COUNT, WIDE, 256, (LT_SC_T > 256 ? 512 : 256)>(S.pre, S.q0, S.q1, S.q2, P, grid, sdirs, cell, first, sl.y,
-                                                                  min(sl.y + LT_SC_SLICE, total), (int)threadIdx.x, ox, oy,
-                                                                  oz, n_tests, n_cand);
+    sc_round_robin<COUNT, WIDE, 256, (LT_SC_T > 256 ? 512 : 256), LT_SC_PB_REST>(S.pre, S.q0, S.q1, S.q2, P, grid, sdirs, cell,
+                                                                               first, sl.y, min(sl.y + LT_SC_SLICE, total),
+                                                                               (int)threadIdx.x, ox, oy, oz, n_tests, n_cand);
     __syncthreads();  // LDS is reused by the next slice
   }
   const int lane = threadIdx.x & 63;
