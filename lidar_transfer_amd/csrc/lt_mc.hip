@@ -207,11 +207,15 @@ extern "C" int lt_debug_mc_stamps(unsigned long long* out, int n_waves) {
 #define LT_MC_STAMP_AT(which, w, i, v) do { if (LT_MC_STAMP == (which) && (threadIdx.x & 63) == 0 && (w) < (1 << 16)) g_mc_stamp[(w) * 4 + (i)] = (v); } while (0)
 // =3: k_mc_emit_batch by section -- g_mc_stamp[8 b + i]: the wall clock between marks i - 1 and i of batch b (plain stores:
 // atomics on eight shared words serialise the waves behind them and measure themselves)
-#define LT_MC_SECTION(i) do { if (LT_MC_STAMP == 3) { const unsigned long long t_ = wall_clock64(); if ((threadIdx.x & 63) == 0 && bi < (1 << 15)) g_mc_stamp[bi * 8 + (i)] = t_ - st_last; st_last = t_; } } while (0)
+// (st: the batch's mc_stamp -- its number and its last mark)
+#define LT_MC_SECTION(st, i) do { if (LT_MC_STAMP == 3) { const unsigned long long t_ = wall_clock64(); if ((threadIdx.x & 63) == 0 && (st).bi < (1 << 15)) g_mc_stamp[(st).bi * 8 + (i)] = t_ - (st).last; (st).last = t_; } } while (0)
+#define LT_MC_SECTION_START(bi) {(bi), (unsigned long long)wall_clock64()}
 #else
 #define LT_MC_STAMP_AT(which, w, i, v) do { } while (0)
-#define LT_MC_SECTION(i) do { } while (0)
+#define LT_MC_SECTION(st, i) do { } while (0)
+#define LT_MC_SECTION_START(bi) {(bi), 0ull}
 #endif
+struct mc_stamp { int bi; unsigned long long last; };
 
 typedef unsigned long long u64;
 
@@ -457,144 +461,145 @@ __global__ __launch_bounds__(256) void k_mc_words(mc_amb A, const u64* __restric
   LT_MC_STAMP_AT(1, wave, 1, wall_clock64());
   LT_MC_STAMP_AT(1, wave, 3, (unsigned long long)__popcll(live));
   while (live) {
-  const int blkid = (__ffsll((long long)live) - 1) * n_waves + wave;  // (wave-uniform)
-  live &= live - 1;
-  const int row = blkid * 64 + lane;
-  unsigned na = 0, nv = 0, nt = 0;
-  if (lane == 0) s_qn[wv] = 0;
-  __builtin_amdgcn_wave_barrier();
-  // (a clean row writes nothing: its words hold 0 -- no active word of the last extraction is left, k_mc_clear)
-  const bool rowlive = row < n_rows && mc_rows_dirty(col_epoch, epoch, D, row);
-  const int rowc = min(row, n_rows - 1);
-  const int x = mc_x_of(D, rowc), y = rowc - x * D.ny;
-  // Triangles of a word = sum over its active cells of the case's count.  A lane walking its own cells is a chain of
-  // ~60 instructions and an LDS look-up per cell, and a row through a wall along z has 60 active cells a word: its wave
-  // waits for that one lane, and the launch for its slowest waves.  Words with more than LT_MC_HEAVY cells are therefore
-  // counted by the WAVE, a lane per cell: the owner's eight corner masks are broadcast (v_readlane), every lane looks up
-  // its cell, three ballots add the counts up (42 -> 32 us on the default volume, with the threshold swept and the lanes'
-  // own loops on 32-bit half words).
+    const int blkid = (__ffsll((long long)live) - 1) * n_waves + wave;  // (wave-uniform)
+    live &= live - 1;
+    const int row = blkid * 64 + lane;
+    unsigned na = 0, nv = 0, nt = 0;
+    if (lane == 0) s_qn[wv] = 0;
+    __builtin_amdgcn_wave_barrier();
+    // (a clean row writes nothing: its words hold 0 -- no active word of the last extraction is left, k_mc_clear)
+    const bool rowlive = row < n_rows && mc_rows_dirty(col_epoch, epoch, D, row);
+    const int rowc = min(row, n_rows - 1);
+    const int x = mc_x_of(D, rowc), y = rowc - x * D.ny;
+    // Triangles of a word = sum over its active cells of the case's count.  A lane walking its own cells is a chain of
+    // ~60 instructions and an LDS look-up per cell, and a row through a wall along z has 60 active cells a word: its wave
+    // waits for that one lane, and the launch for its slowest waves.  Words with more than LT_MC_HEAVY cells are therefore
+    // counted by the WAVE, a lane per cell: the owner's eight corner masks are broadcast (v_readlane), every lane looks up
+    // its cell, three ballots add the counts up (42 -> 32 us on the default volume, with the threshold swept and the lanes'
+    // own loops on 32-bit half words).
 #ifndef LT_MC_HEAVY_LANES
 #define LT_MC_HEAVY_LANES 8   // (swept: 4 .. 12: 31.5 us, 20 .. 32: 32.4, 64 = never walked: 37.5)
 #endif
 #ifndef LT_MC_HEAVY
 #define LT_MC_HEAVY 16  // (swept on the default volume: 2: 50 us, 4: 39, 6: 38, 10 .. 24: 32-33, 40: 35, never: 39)
 #endif
-  // -> triangles | centre vertices << 16 of the word k of this lane's row
-  auto count_tris = [&](const mc_masks& M, int k) -> unsigned {  // (called by all 64 lanes)
-    unsigned t = 0;
-    auto ambiguous = [&](int xx, int yy, int b, unsigned cs) -> unsigned {  // queued for k_mc_amb; counts 0 here
-      const uint2 e = make_uint2((unsigned)((xx * D.ny + yy) * D.nz + k * 64 + b), cs | ((unsigned)blkid << 8));
-      const int slot = atomicAdd(&s_qn[wv], 1);  // (LDS)
-      if (slot < LT_MC_QW) s_q[wv][slot] = e;
-      else {  // (more than the buffer holds in one block of rows: straight to the queue)
-        const unsigned sh = (unsigned)blkid & (LT_MC_SHARDS - 1);
-        const unsigned pos = (unsigned)atomicAdd(A.counter + sh * LT_MC_CTR_STRIDE, 1);
-        if (pos < A.cap) A.queue[(size_t)sh * A.cap + pos] = e;
-      }
-      return 0u;
-    };
-    // ... unless MANY lanes hold such a word (a wall across the block's rows): the wave's turn costs ~90 instructions
-    // per heavy word, the lanes' own loops ~25 per cell of the fullest lane -- 64 heavy words at once are cheaper walked
-    bool heavy = __popcll(M.ac) > LT_MC_HEAVY;
-    if (__popcll(__ballot(heavy)) > LT_MC_HEAVY_LANES) heavy = false;
-    if (!heavy) {
-      // the word's halves one after the other: with 32-bit masks a cell is 8 x (v_bfe_u32, v_lshl_or_b32) + a 32-bit
-      // find-first / clear-lowest, a third of the instructions of the 64-bit shifts of mc_case
+    // -> triangles | centre vertices << 16 of the word k of this lane's row
+    auto count_tris = [&](const mc_masks& M, int k) -> unsigned {  // (called by all 64 lanes)
+      unsigned t = 0;
+      auto ambiguous = [&](int xx, int yy, int b, unsigned cs) -> unsigned {  // queued for k_mc_amb; counts 0 here
+        const uint2 e = make_uint2((unsigned)((xx * D.ny + yy) * D.nz + k * 64 + b), cs | ((unsigned)blkid << 8));
+        const int slot = atomicAdd(&s_qn[wv], 1);  // (LDS)
+        if (slot < LT_MC_QW) s_q[wv][slot] = e;
+        else {  // (more than the buffer holds in one block of rows: straight to the queue)
+          const unsigned sh = (unsigned)blkid & (LT_MC_SHARDS - 1);
+          const unsigned pos = (unsigned)atomicAdd(A.counter + sh * LT_MC_CTR_STRIDE, 1);
+          if (pos < A.cap) A.queue[(size_t)sh * A.cap + pos] = e;
+        }
+        return 0u;
+      };
+      // ... unless MANY lanes hold such a word (a wall across the block's rows): the wave's turn costs ~90 instructions
+      // per heavy word, the lanes' own loops ~25 per cell of the fullest lane -- 64 heavy words at once are cheaper walked
+      bool heavy = __popcll(M.ac) > LT_MC_HEAVY;
+      if (__popcll(__ballot(heavy)) > LT_MC_HEAVY_LANES) heavy = false;
+      if (!heavy) {
+        // the word's halves one after the other: with 32-bit masks a cell is 8 x (v_bfe_u32, v_lshl_or_b32) + a 32-bit
+        // find-first / clear-lowest, a third of the instructions of the 64-bit shifts of mc_case
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        unsigned a = (unsigned)(M.ac >> (32 * h));
-        if (a == 0u) continue;
-        unsigned m[8];
+        for (int h = 0; h < 2; ++h) {
+          unsigned a = (unsigned)(M.ac >> (32 * h));
+          if (a == 0u) continue;
+          unsigned m[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-          m[i] = (unsigned)(((i & 4) ? M.s[i & 1][(i >> 1) & 1] : M.m[i & 1][(i >> 1) & 1]) >> (32 * h));
-        for (; a; a &= a - 1) {
-          const int b = __ffs((int)a) - 1;
-          unsigned cs = 0;
+          for (int i = 0; i < 8; ++i)
+            m[i] = (unsigned)(((i & 4) ? M.s[i & 1][(i >> 1) & 1] : M.m[i & 1][(i >> 1) & 1]) >> (32 * h));
+          for (; a; a &= a - 1) {
+            const int b = __ffs((int)a) - 1;
+            unsigned cs = 0;
 #pragma unroll
-          for (int i = 0; i < 8; ++i) cs |= ((m[i] >> b) & 1u) << i;
-          const unsigned n = s_nt[cs];
-          t += (n & 0x80u) ? ambiguous(x, y, 32 * h + b, cs) : n;
+            for (int i = 0; i < 8; ++i) cs |= ((m[i] >> b) & 1u) << i;
+            const unsigned n = s_nt[cs];
+            t += (n & 0x80u) ? ambiguous(x, y, 32 * h + b, cs) : n;
+          }
         }
       }
-    }
-    for (u64 hm = __ballot(heavy); hm; hm &= hm - 1) {
-      const int r = __ffsll((long long)hm) - 1;  // (wave-uniform)
-      int cs = 0;
+      for (u64 hm = __ballot(heavy); hm; hm &= hm - 1) {
+        const int r = __ffsll((long long)hm) - 1;  // (wave-uniform)
+        int cs = 0;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const u64 m = (i & 4) ? M.s[i & 1][(i >> 1) & 1] : M.m[i & 1][(i >> 1) & 1];
-        const u64 mr = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)m, r) |
-                       ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(m >> 32), r) << 32);
-        cs |= (int)((mr >> lane) & 1ull) << i;
+        for (int i = 0; i < 8; ++i) {
+          const u64 m = (i & 4) ? M.s[i & 1][(i >> 1) & 1] : M.m[i & 1][(i >> 1) & 1];
+          const u64 mr = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)m, r) |
+                         ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(m >> 32), r) << 32);
+          cs |= (int)((mr >> lane) & 1ull) << i;
+        }
+        const u64 ac = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)M.ac, r) |
+                       ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(M.ac >> 32), r) << 32);
+        unsigned n = ((ac >> lane) & 1ull) ? s_nt[cs] : 0u;  // (<= 12, or the marker)
+        if (n & 0x80u)  // (the OWNER's x, y: broadcast like its masks)
+          n = ambiguous(__builtin_amdgcn_readlane(x, r), __builtin_amdgcn_readlane(y, r), lane, (unsigned)cs);
+        const unsigned tot = __popcll(__ballot(n & 1u)) + 2u * __popcll(__ballot(n & 2u)) + 4u * __popcll(__ballot(n & 4u)) +
+                             8u * __popcll(__ballot(n & 8u)) + ((unsigned)__popcll(__ballot(n >> 16)) << 16);
+        if (lane == r) t = tot;
       }
-      const u64 ac = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)M.ac, r) |
-                     ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(M.ac >> 32), r) << 32);
-      unsigned n = ((ac >> lane) & 1ull) ? s_nt[cs] : 0u;  // (<= 12, or the marker)
-      if (n & 0x80u)  // (the OWNER's x, y: broadcast like its masks)
-        n = ambiguous(__builtin_amdgcn_readlane(x, r), __builtin_amdgcn_readlane(y, r), lane, (unsigned)cs);
-      const unsigned tot = __popcll(__ballot(n & 1u)) + 2u * __popcll(__ballot(n & 2u)) + 4u * __popcll(__ballot(n & 4u)) +
-                           8u * __popcll(__ballot(n & 8u)) + ((unsigned)__popcll(__ballot(n >> 16)) << 16);
-      if (lane == r) t = tot;
-    }
-    return t;
-  };
-  if (D.wz <= 4) {
-    // the sign words of the four rows (x + dx, y + dy), ALL loaded before the first is used -- a word's masks need
-    // its row neighbours' words at k and k + 1, so a loop over k loaded every word twice, in wz dependent rounds
-    const bool hx = x + 1 < D.nx, hy = y + 1 < D.ny;
-    u64 w[4][5];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int dx = q & 1, dy = q >> 1;
-      const bool have = rowlive && (dx == 0 || hx) && (dy == 0 || hy);
-      const size_t base = (size_t)(rowc + (have ? dx * D.ny + dy : 0)) * D.wz;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) w[q][k] = (have && k < D.wz) ? bits[base + k] : 0ull;
-      w[q][4] = 0ull;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k >= D.wz) break;  // (wave-uniform)
-      u64 w8[8];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { w8[q] = w[q][k]; w8[q | 4] = w[q][k + 1]; }
-      const mc_masks M = mc_build(w8, D, x, y, k);  // (a row that is not live holds zeros: no edge, no cell)
+      return t;
+    };
+    // word k of this lane's row is done: its count (vertices | triangles << 16) stored, the row's three sums kept
+    auto word_done = [&](const mc_masks& M, int k) {  // (called by all 64 lanes: count_tris)
       const unsigned tc = count_tris(M, k), t = tc & 0xFFFFu;
       const unsigned v = __popcll(M.ex) + __popcll(M.ey) + __popcll(M.ez) + (tc >> 16);
       if (rowlive) cnt[(size_t)row * D.wz + k] = v | (t << 16);
       na += (v | t) ? 1u : 0u; nv += v; nt += t;
-    }
-  } else
-  for (int k = 0; k < D.wz; ++k) {
-    mc_masks M = mc_load(bits, D, x, y, k);
-    if (!rowlive) { M.ex = M.ey = M.ez = M.ac = 0ull; }
-    const unsigned tc = count_tris(M, k), t = tc & 0xFFFFu;
-    const unsigned v = __popcll(M.ex) + __popcll(M.ey) + __popcll(M.ez) + (tc >> 16);
-    if (rowlive) cnt[(size_t)row * D.wz + k] = v | (t << 16);
-    na += (v | t) ? 1u : 0u; nv += v; nt += t;
-  }
-  {  // the block's ambiguous cells -> the queue
-    __builtin_amdgcn_wave_barrier();
-    const int nq = min(s_qn[wv], LT_MC_QW);  // (wave-uniform)
-    if (nq > 0) {
-      unsigned base = 0;
-      const unsigned sh = (unsigned)blkid & (LT_MC_SHARDS - 1);
-      if (lane == 0) base = (unsigned)atomicAdd(A.counter + sh * LT_MC_CTR_STRIDE, nq);
-      base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-      for (int j = lane; j < nq; j += 64)
-        if (base + (unsigned)j < A.cap) A.queue[(size_t)sh * A.cap + base + j] = s_q[wv][j];
-    }
-  }
-  u64 p = pack3(na, nv, nt);  // (20 bits each: 64 rows x wz words x <= 768 triangles -- the host checks wz)
+    };
+    if (D.wz <= 4) {
+      // the sign words of the four rows (x + dx, y + dy), ALL loaded before the first is used -- a word's masks need
+      // its row neighbours' words at k and k + 1, so a loop over k loaded every word twice, in wz dependent rounds
+      const bool hx = x + 1 < D.nx, hy = y + 1 < D.ny;
+      u64 w[4][5];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
-  if (lane == 0) {
-    blk[3 * blkid] = (int)(p & 0xFFFFF);
-    blk[3 * blkid + 1] = (int)((p >> 20) & 0xFFFFF);
-    blk[3 * blkid + 2] = (int)((p >> 40) & 0xFFFFF);
-    wave_na[blkid] = (int)(p & 0xFFFFF);
-  }
+      for (int q = 0; q < 4; ++q) {
+        const int dx = q & 1, dy = q >> 1;
+        const bool have = rowlive && (dx == 0 || hx) && (dy == 0 || hy);
+        const size_t base = (size_t)(rowc + (have ? dx * D.ny + dy : 0)) * D.wz;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[q][k] = (have && k < D.wz) ? bits[base + k] : 0ull;
+        w[q][4] = 0ull;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k >= D.wz) break;  // (wave-uniform)
+        u64 w8[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { w8[q] = w[q][k]; w8[q | 4] = w[q][k + 1]; }
+        word_done(mc_build(w8, D, x, y, k), k);  // (a row that is not live holds zeros: no edge, no cell)
+      }
+    } else {
+      for (int k = 0; k < D.wz; ++k) {
+        mc_masks M = mc_load(bits, D, x, y, k);
+        if (!rowlive) { M.ex = M.ey = M.ez = M.ac = 0ull; }
+        word_done(M, k);
+      }
+    }
+    {  // the block's ambiguous cells -> the queue
+      __builtin_amdgcn_wave_barrier();
+      const int nq = min(s_qn[wv], LT_MC_QW);  // (wave-uniform)
+      if (nq > 0) {
+        unsigned base = 0;
+        const unsigned sh = (unsigned)blkid & (LT_MC_SHARDS - 1);
+        if (lane == 0) base = (unsigned)atomicAdd(A.counter + sh * LT_MC_CTR_STRIDE, nq);
+        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+        for (int j = lane; j < nq; j += 64)
+          if (base + (unsigned)j < A.cap) A.queue[(size_t)sh * A.cap + base + j] = s_q[wv][j];
+      }
+    }
+    u64 p = pack3(na, nv, nt);  // (20 bits each: 64 rows x wz words x <= 768 triangles -- the host checks wz)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+    if (lane == 0) {
+      blk[3 * blkid] = (int)(p & 0xFFFFF);
+      blk[3 * blkid + 1] = (int)((p >> 20) & 0xFFFFF);
+      blk[3 * blkid + 2] = (int)((p >> 40) & 0xFFFFF);
+      wave_na[blkid] = (int)(p & 0xFFFFF);
+    }
   }
   LT_MC_STAMP_AT(1, wave, 2, wall_clock64());
 }
@@ -746,56 +751,56 @@ __global__ __launch_bounds__(256) void k_mc_compact(const u64* __restrict__ bits
   LT_MC_STAMP_AT(2, wave, 1, wall_clock64());
   LT_MC_STAMP_AT(2, wave, 3, (unsigned long long)__popcll(live));
   while (live) {
-  const int blkid = (__ffsll((long long)live) - 1) * n_waves + wave;  // (wave-uniform)
-  live &= live - 1;
-  const int row = blkid * 64 + lane;
-  unsigned na = 0, nv = 0, nt = 0;
-  // the row's counts: up to four words ALL loaded before the first is used and kept for the loop below (a rolled loop
-  // waited for every load before it issued the next, twice: eight dependent round trips per block of rows)
-  const bool few = D.wz <= 4;  // (wave-uniform)
-  unsigned c4[4] = {0u, 0u, 0u, 0u};
-  if (row < n_rows) {
-    if (few) {
+    const int blkid = (__ffsll((long long)live) - 1) * n_waves + wave;  // (wave-uniform)
+    live &= live - 1;
+    const int row = blkid * 64 + lane;
+    unsigned na = 0, nv = 0, nt = 0;
+    // the row's counts: up to four words ALL loaded before the first is used and kept for the loop below (a rolled loop
+    // waited for every load before it issued the next, twice: eight dependent round trips per block of rows)
+    const bool few = D.wz <= 4;  // (wave-uniform)
+    unsigned c4[4] = {0u, 0u, 0u, 0u};
+    if (row < n_rows) {
+      if (few) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) c4[k] = k < D.wz ? cnt[(size_t)row * D.wz + k] : 0u;
+        for (int k = 0; k < 4; ++k) c4[k] = k < D.wz ? cnt[(size_t)row * D.wz + k] : 0u;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { na += c4[k] ? 1u : 0u; nv += c4[k] & 0xFFFFu; nt += c4[k] >> 16; }
-    } else {
-      for (int k = 0; k < D.wz; ++k) {
-        const unsigned c = cnt[(size_t)row * D.wz + k];
-        na += c ? 1u : 0u; nv += c & 0xFFFFu; nt += c >> 16;
+        for (int k = 0; k < 4; ++k) { na += c4[k] ? 1u : 0u; nv += c4[k] & 0xFFFFu; nt += c4[k] >> 16; }
+      } else {
+        for (int k = 0; k < D.wz; ++k) {
+          const unsigned c = cnt[(size_t)row * D.wz + k];
+          na += c ? 1u : 0u; nv += c & 0xFFFFu; nt += c >> 16;
+        }
       }
     }
-  }
-  const u64 mine = pack3(na, nv, nt);
-  const u64 ex = wave_incl_scan(mine) - mine;
-  if (row >= n_rows) continue;
-  const int* sg = seg + 3 * (blkid >> 8);
-  int ci = sg[0] + blk[3 * blkid] + (int)(ex & 0xFFFFF);
-  int vb = sg[1] + blk[3 * blkid + 1] + (int)((ex >> 20) & 0xFFFFF);
-  int tb = sg[2] + blk[3 * blkid + 2] + (int)((ex >> 40) & 0xFFFFF);
-  const int x = mc_x_of(D, row), y = row - x * D.ny;
-  for (int k = 0; k < D.wz; ++k) {
-    const int w = row * D.wz + k;
-    const unsigned c = few ? (k == 0 ? c4[0] : k == 1 ? c4[1] : k == 2 ? c4[2] : c4[3]) : cnt[w];
-    int mine_ci = -1;
-    if (c) {
-      if (ci < cap_rec) {
-        const mc_masks M = mc_load(bits, D, x, y, k);
-        mc_rec r;
-        r.w = w;
-        r.vbase = vb;
-        r.tbase = tb;
-        r.ex = M.ex; r.ey = M.ey; r.ez = M.ez;
-        // triangles of the word (k_mc_emit_batch: the extent of a batch) | its centre vertices << 16
-        r.pad = (int)((c >> 16) | (((c & 0xFFFFu) - (unsigned)(__popcll(M.ex) + __popcll(M.ey) + __popcll(M.ez))) << 16));
-        rec[ci] = r;
-        mine_ci = ci;
+    const u64 mine = pack3(na, nv, nt);
+    const u64 ex = wave_incl_scan(mine) - mine;
+    if (row >= n_rows) continue;
+    const int* sg = seg + 3 * (blkid >> 8);
+    int ci = sg[0] + blk[3 * blkid] + (int)(ex & 0xFFFFF);
+    int vb = sg[1] + blk[3 * blkid + 1] + (int)((ex >> 20) & 0xFFFFF);
+    int tb = sg[2] + blk[3 * blkid + 2] + (int)((ex >> 40) & 0xFFFFF);
+    const int x = mc_x_of(D, row), y = row - x * D.ny;
+    for (int k = 0; k < D.wz; ++k) {
+      const int w = row * D.wz + k;
+      const unsigned c = few ? (k == 0 ? c4[0] : k == 1 ? c4[1] : k == 2 ? c4[2] : c4[3]) : cnt[w];
+      int mine_ci = -1;
+      if (c) {
+        if (ci < cap_rec) {
+          const mc_masks M = mc_load(bits, D, x, y, k);
+          mc_rec r;
+          r.w = w;
+          r.vbase = vb;
+          r.tbase = tb;
+          r.ex = M.ex; r.ey = M.ey; r.ez = M.ez;
+          // triangles of the word (k_mc_emit_batch: the extent of a batch) | its centre vertices << 16
+          r.pad = (int)((c >> 16) | (((c & 0xFFFFu) - (unsigned)(__popcll(M.ex) + __popcll(M.ey) + __popcll(M.ez))) << 16));
+          rec[ci] = r;
+          mine_ci = ci;
+        }
+        ++ci; vb += (int)(c & 0xFFFFu); tb += (int)(c >> 16);
       }
-      ++ci; vb += (int)(c & 0xFFFFu); tb += (int)(c >> 16);
+      cmap[w] = mine_ci;
     }
-    cmap[w] = mine_ci;
-  }
   }
   LT_MC_STAMP_AT(2, wave, 2, wall_clock64());
 }
@@ -813,7 +818,7 @@ __device__ __forceinline__ float mc_edge_coord(int c, float v1, float v2) {
   return (float)((double)c + w2 / (w1 + w2));
 }
 
-// ---- k_mc_emit_batch: one wave per K consecutive active words, one lane per VERTEX / per TRIANGLE ----------------------------
+// ---- k_mc_emit_batch: one wave per K = LT_MC_K consecutive active words, one lane per VERTEX / per TRIANGLE ------------------
 // A wave per active word with a lane per voxel (rounds 1-2) spent its time issuing instructions for idle lanes: on the default volume's street scene an active word owns
 // 3.6 vertices and 7.3 triangles, so the double-precision vertex rule (three IEEE divisions), unrolled over the three edge
 // axes, and the 5 x 3 unrolled index computations run with 2-4 of 64 lanes live -- 252 000 waves x ~3 300 cycles = the
@@ -832,229 +837,230 @@ __device__ __forceinline__ float mc_edge_coord(int c, float v1, float v2) {
 #define LT_MC_EW 4  // waves per workgroup of the emission
 #define LT_MC_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
                           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-// AOS: the three field pointers are one array of (tsdf, weight, colour, remission) records (a TSDF volume, D.vs == 4): an
-// edge vertex's two field samples and its attributes -- which are those of one of the edge's two ends -- come with TWO
-// 16-byte loads, nothing waits for the vertex rule (separate arrays: four loads, the last two behind the rule)
-template <int K, bool AOS>
-__global__ __launch_bounds__(64 * LT_MC_EW) void k_mc_emit_batch(const float* __restrict__ tsdf, const float* __restrict__ color_vol,
-                                                      const float* __restrict__ rem_vol, const u64* __restrict__ bits,
-                                                      mc_dims D, const int* __restrict__ cmap,
-                                                      const mc_rec* __restrict__ rec, int n_active, float voxel_size,
-                                                      float ox, float oy, float oz, float* __restrict__ verts,
-                                                      int* __restrict__ faces, int* __restrict__ colors,
-                                                      float* __restrict__ rem, int cap_v, int cap_f, mc_amb A, int xcd_map) {
-  static_assert(K <= 16, "list entries hold the word in 4 bits");
-  static_assert(64 * LT_MC_EW == 256, "the tiling table is staged by 256 threads");
-  // LT_MC_EW waves per workgroup, each with arrays of its own and no business with the others: what would be a workgroup
-  // barrier orders ONE wave's LDS accesses, which the hardware executes in order anyway -- LT_MC_WSYNC only keeps the
-  // compiler from moving them.  (Four waves instead of one per workgroup change nothing by themselves -- 82.7 us both;
-  // they share the tiling table below, 256 B of LDS per wave instead of 1 KB: 80 us; 75 on a volume of records, AOS.)
-  __shared__ mc_rec S_rec[LT_MC_EW][K];
-  __shared__ int S_xyz[LT_MC_EW][K][3];       // x, y, wz of the words
-  __shared__ size_t S_base[LT_MC_EW][K];      // ... and the voxel index of their first voxel
-  __shared__ mc_nb S_nb[LT_MC_EW][K][8];      // records of the 8 words a cell's triangles can reference
-  __shared__ u64 S_cm[LT_MC_EW][K][9];        // corner masks m[dx][dy], s[dx][dy] (mc_masks) and the active-cell mask of the words
-  // sg: sign words of the cell corners, [dx | dy << 1 | dw << 2] -- dead once the corner masks are built, where
-  // vl: vertex j of the window: k | b << 4 | axis << 10 (12 bits; axis 3 = the cell's centre vertex) begins its life
-  union sg_vl { u64 sg[K][8]; unsigned short vl[LT_MC_VCAP]; };
-  __shared__ sg_vl S_sv[LT_MC_EW];
-  __shared__ unsigned short S_tl[LT_MC_EW][LT_MC_TCAP];  // triangle j of the window: index into s_cl | t << 10
-  __shared__ unsigned S_cl[LT_MC_EW][K * 64];      // active cells of the batch in order: k | b << 4 | triangles << 10 | centre << 14 | tiling offset << 15
-  __shared__ unsigned short S_ct[LT_MC_EW][K * 64];  // ... and the (batch-relative) index of their first triangle (< 16 x 64 x 12)
-  __shared__ u64 S_ccm[LT_MC_EW][K];               // the words' cells that own a centre vertex
-  __shared__ int S_cpre[LT_MC_EW][K + 1];          // active cells before word k
-  __shared__ unsigned s_lwc[256];  // LT_LWC_FIXED, once per workgroup: a cell's tiling without a global round trip
-  s_lwc[threadIdx.x & 255u] = LT_LWC_FIXED[threadIdx.x & 255u];
-  __syncthreads();  // (the only workgroup barrier: before any wave's first batch)
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  auto& s_rec = S_rec[wv]; auto& s_xyz = S_xyz[wv]; auto& s_base = S_base[wv]; auto& s_sg = S_sv[wv].sg; auto& s_nb = S_nb[wv]; auto& s_cm = S_cm[wv];
-  auto& s_vl = S_sv[wv].vl; auto& s_tl = S_tl[wv]; auto& s_cl = S_cl[wv]; auto& s_ct = S_ct[wv]; auto& s_ccm = S_ccm[wv];
-  auto& s_cpre = S_cpre[wv];
-  const int lane = (int)(threadIdx.x & 63u);
-  // (a wave takes batches until none is left; by default the grid has a wave per batch -- see the launch)
-  const int n_batches = (n_active + K - 1) / K;
-  // Batch order: active words are numbered x-major, so the batch list walks the volume plane by plane.  Workgroups are dealt
-  // to the eight XCDs round-robin (workgroup id % 8) and the L2s are private: with `xcd_map` XCD q takes the q-th EIGHTH of
-  // the batch list (its waves in turn within it), so that the columns (x + 1, y) / (x, y + 1) a batch samples are the OWN
-  // columns of batches the same L2 serves moments later -- instead of every plane's lines being pulled into all eight L2s.
-  // xcd_map = C > 0: the list is cut into CHUNKS of C batches (a few planes), chunk c belongs to XCD c % 8, and the waves of
-  // an XCD take the batches of its chunks in turn -- eight contiguous eighths (one per XCD) moved the fewest bytes but the
-  // XCDs finished at different times (a batch costs 1.5 - 42 us depending on where in the scene it lies).
-  const int per_xcd = (int)(gridDim.x >> 3) * LT_MC_EW, xq = blockIdx.x & 7, xslot = (int)(blockIdx.x >> 3) * LT_MC_EW + wv;
-  if (xcd_map && xslot >= per_xcd) return;  // (a grid that is not a multiple of eight: the tail waves have no share)
-  for (int it = xcd_map ? xslot : (int)blockIdx.x * LT_MC_EW + wv;; it += xcd_map ? per_xcd : (int)gridDim.x * LT_MC_EW) {
-    int bi = it;
-    if (xcd_map) bi = ((it / xcd_map) * 8 + xq) * xcd_map + it % xcd_map;
-    if (xcd_map ? (it / xcd_map) * 8 * xcd_map >= n_batches : bi >= n_batches) break;
-    if (bi >= n_batches) continue;
-#ifdef LT_MC_STAMP
-  unsigned long long st_last = wall_clock64();
+#ifndef LT_MC_K
+#define LT_MC_K 8  // active words per batch (swept 2 / 4 / 8 / 16: profiles/r04/DESIGN_rounds_1_to_4.md; 16 halves the occupancy)
 #endif
-  const int ci0 = bi * K;
-  const int nw = min(K, n_active - ci0);
+static_assert(LT_MC_K >= 1 && LT_MC_K <= 16, "list entries hold the word in 4 bits");
+static_assert(64 * LT_MC_EW == 256, "the tiling table is staged by 256 threads");
+
+// what the host hands over (mc_emit_args_of); by value into the kernel, by const& into its phases
+struct mc_emit_args {
+  const float* tsdf; const float* color_vol; const float* rem_vol;  // (AOS: all three the one array of records)
+  const u64* bits; mc_dims D; const int* cmap;
+  const mc_rec* rec; int n_active;
+  float voxel_size, ox, oy, oz;
+  float* verts; int* faces; int* colors; float* rem;
+  int cap_v, cap_f;
+  mc_amb A;
+  int xcd_map;
+};
+
+// ONE wave's working set in LDS.  LT_MC_EW waves per workgroup, each with a set of its own and no business with the others:
+// what would be a workgroup barrier orders ONE wave's LDS accesses, which the hardware executes in order anyway --
+// LT_MC_WSYNC only keeps the compiler from moving them.  (Four waves instead of one per workgroup change nothing by
+// themselves -- 82.7 us both; they share the tiling table s_lwc, 256 B of LDS per wave instead of 1 KB: 80 us; 75 on a
+// volume of records, AOS.)  Size for K = 8: 7 300 B of members, 7 312 B with the 16-byte alignment that lets the compiler read
+// the 40-byte records with ds_read_b128 (8-byte alignment: 7 304 B and pairs of ds_read2_b64) -- 30 272 B per workgroup with
+// s_lwc, 24 granules of 1 280 B like the 30 224 B of twelve separate arrays.
+struct alignas(16) mc_batch {
+  mc_rec rec[LT_MC_K];
+  int xyz[LT_MC_K][3];       // x, y, wz of the words
+  size_t base[LT_MC_K];      // ... and the voxel index of their first voxel
+  mc_nb nb[LT_MC_K][8];      // records of the 8 words a cell's triangles can reference
+  u64 cm[LT_MC_K][9];        // corner masks m[dx][dy], s[dx][dy] (mc_masks) and the active-cell mask of the words
+  union {
+    u64 sg[LT_MC_K][8];      // sign words of the cell corners, [dx | dy << 1 | dw << 2] -- dead once the corner masks are built, where
+    unsigned short vl[LT_MC_VCAP];  // vertex j of the window: k | b << 4 | axis << 10 (12 bits; axis 3 = the cell's centre vertex) begins its life
+  };
+  unsigned short tl[LT_MC_TCAP];    // triangle j of the window: index into cl | t << 10
+  unsigned cl[LT_MC_K * 64];        // active cells of the batch in order: k | b << 4 | triangles << 10 | centre << 14 | tiling offset << 15
+  unsigned short ct[LT_MC_K * 64];  // ... and the (batch-relative) index of their first triangle (< 16 x 64 x 12)
+  u64 ccm[LT_MC_K];                 // the words' cells that own a centre vertex
+  int cpre[LT_MC_K + 1];            // active cells before word k
+};
+struct mc_extent {  // of one batch, wave-uniform (emit_stage)
+  int nw;              // words
+  int ncell;           // active cells
+  int vbase0, tbase0;  // its first vertex / triangle in the output
+  int nvt, ntt;        // its vertices / triangles
+};
+constexpr int LT_MC_NPV = (8 * LT_MC_K + 63) / 64;  // (word, segment of 8 voxels) pairs per lane
+
+// ---- staging: records and word coordinates; sign words, compact indices, neighbour records; corner masks; the prefix of
+// active cells per word
+__device__ __forceinline__ mc_extent emit_stage(const mc_emit_args& a, mc_batch& s, int lane, int ci0, mc_stamp& st) {
+  const mc_dims& D = a.D;
+  mc_extent e;
+  e.nw = min(LT_MC_K, a.n_active - ci0);
+  const int nw = e.nw;
   const size_t sy = (size_t)D.nz, sx = (size_t)D.ny * D.nz;
   if (lane < nw) {
-    const mc_rec r = rec[ci0 + lane];
-    s_rec[lane] = r;
+    const mc_rec r = a.rec[ci0 + lane];
+    s.rec[lane] = r;
     const int row = mc_row_of(D, r.w), x = mc_x_of(D, row);
-    s_xyz[lane][2] = r.w - row * D.wz;
-    s_xyz[lane][0] = x;
-    s_xyz[lane][1] = row - x * D.ny;
-    s_base[lane] = (size_t)x * sx + (size_t)(row - x * D.ny) * sy + (size_t)(r.w - row * D.wz) * 64;
+    s.xyz[lane][2] = r.w - row * D.wz;
+    s.xyz[lane][0] = x;
+    s.xyz[lane][1] = row - x * D.ny;
+    s.base[lane] = (size_t)x * sx + (size_t)(row - x * D.ny) * sy + (size_t)(r.w - row * D.wz) * 64;
   }
   LT_MC_WSYNC();
-  LT_MC_SECTION(0);  // records
+  LT_MC_SECTION(st, 0);  // records
   for (int p = lane; p < 8 * nw; p += 64) {  // (k, slot): sign word and record of the word (x + dx, y + dy, wz + dw)
     const int k = p >> 3, slot = p & 7;
-    const int x = s_xyz[k][0], y = s_xyz[k][1], wz = s_xyz[k][2];
+    const int x = s.xyz[k][0], y = s.xyz[k][1], wz = s.xyz[k][2];
     const int dx = slot & 1, dy = (slot >> 1) & 1, dw = slot >> 2;
     const bool have = x + dx < D.nx && y + dy < D.ny && wz + dw < D.wz;
     const int w2 = ((x + dx) * D.ny + (y + dy)) * D.wz + wz + dw;
     u64 sg = 0ull;
     int c2 = -1;
     if (have) {
-      sg = bits[w2];
-      c2 = slot == 0 ? ci0 + k : cmap[w2];
+      sg = a.bits[w2];
+      c2 = slot == 0 ? ci0 + k : a.cmap[w2];
     }
-    mc_nb e;
-    e.ex = e.ey = e.ez = 0; e.vbase = 0; e.have = 0;
+    mc_nb nb;
+    nb.ex = nb.ey = nb.ez = 0; nb.vbase = 0; nb.have = 0;
     if (c2 >= 0) {
-      const mc_rec r2 = rec[c2];
-      e.ex = r2.ex; e.ey = r2.ey; e.ez = r2.ez; e.vbase = r2.vbase; e.have = 1;
+      const mc_rec r2 = a.rec[c2];
+      nb.ex = r2.ex; nb.ey = r2.ey; nb.ez = r2.ez; nb.vbase = r2.vbase; nb.have = 1;
     }
-    s_sg[k][slot] = sg;
-    s_nb[k][slot] = e;
+    s.sg[k][slot] = sg;
+    s.nb[k][slot] = nb;
   }
   LT_MC_WSYNC();
-  LT_MC_SECTION(1);  // sign words, compact indices, neighbour records
+  LT_MC_SECTION(st, 1);  // sign words, compact indices, neighbour records
   if (lane < nw) {  // the cell masks of word `lane`, once
     u64 w8[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) w8[q] = s_sg[lane][q];
-    const mc_masks M = mc_build(w8, D, s_xyz[lane][0], s_xyz[lane][1], s_xyz[lane][2]);
+    for (int q = 0; q < 8; ++q) w8[q] = s.sg[lane][q];
+    const mc_masks M = mc_build(w8, D, s.xyz[lane][0], s.xyz[lane][1], s.xyz[lane][2]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      s_cm[lane][q] = M.m[q & 1][q >> 1];
-      s_cm[lane][4 + q] = M.s[q & 1][q >> 1];
+      s.cm[lane][q] = M.m[q & 1][q >> 1];
+      s.cm[lane][4 + q] = M.s[q & 1][q >> 1];
     }
-    s_cm[lane][8] = M.ac;
+    s.cm[lane][8] = M.ac;
   }
   {  // active cells before each word (lanes 0 .. nw - 1 hold the words' counts)
-    int c = lane < nw ? __popcll(s_cm[lane][8]) : 0;  // (own write: same lane)
-    const int mine = c;
+    int c = lane < nw ? __popcll(s.cm[lane][8]) : 0;  // (own write: same lane)
 #pragma unroll
-    for (int o = 1; o < K; o <<= 1) {
+    for (int o = 1; o < LT_MC_K; o <<= 1) {
       const int q = __shfl_up(c, o, 64);
       if (lane >= o) c += q;
     }
-    if (lane < nw) s_cpre[lane + 1] = c;
-    if (lane == 0) s_cpre[0] = 0;
-    if (lane < K) s_ccm[lane] = 0ull;
-    (void)mine;
+    if (lane < nw) s.cpre[lane + 1] = c;
+    if (lane == 0) s.cpre[0] = 0;
+    if (lane < LT_MC_K) s.ccm[lane] = 0ull;
   }
   LT_MC_WSYNC();
-  const mc_rec first = s_rec[0], last = s_rec[nw - 1];
-  const int vbase0 = first.vbase, tbase0 = first.tbase;
-  const int nvt = last.vbase + __popcll(last.ex) + __popcll(last.ey) + __popcll(last.ez) + (last.pad >> 16) - vbase0;
-  const int ntt = last.tbase + (last.pad & 0xFFFF) - tbase0;
-#if defined(LT_MC_STOP) && LT_MC_STOP == 1  // instruction-count experiment (tools/mc_sections.sh): staging only
-  continue;
-#endif
-  // ---- the batch's active cells in order (word, z) with their TILING, and the (batch-relative) index of every cell's first
-  // triangle: a lane takes one (word, SEGMENT of 8 voxels) pair, lists the cells of its 8 voxels (the word's cell base + a
-  // popcount below the segment) -- case index from the corner masks, tiling from the table or, for Lewiner's ambiguous cases,
-  // from k_mc_amb's side table (the tests on the cell's eight values ran there) -- and adds up their triangle counts; ONE wave scan over the lanes
-  // turns the sums into offsets, and the lane hands them to its cells.  The cells whose tiling has a centre vertex are
-  // collected per word (s_ccm): their vertices follow the word's edge vertices in the output.
-  const int ncell = s_cpre[nw];  // (wave-uniform)
-  constexpr int NPV = (8 * K + 63) / 64;
-  {
-    int run = 0;  // triangles of the pairs before this round of 64
+  const mc_rec first = s.rec[0], last = s.rec[nw - 1];
+  e.vbase0 = first.vbase;
+  e.tbase0 = first.tbase;
+  e.nvt = last.vbase + __popcll(last.ex) + __popcll(last.ey) + __popcll(last.ez) + (last.pad >> 16) - e.vbase0;
+  e.ntt = last.tbase + (last.pad & 0xFFFF) - e.tbase0;
+  e.ncell = s.cpre[nw];
+  return e;
+}
+
+// ---- the batch's active cells in order (word, z) with their TILING, and the (batch-relative) index of every cell's first
+// triangle: a lane takes one (word, SEGMENT of 8 voxels) pair, lists the cells of its 8 voxels (the word's cell base + a
+// popcount below the segment) -- case index from the corner masks, tiling from the table or, for Lewiner's ambiguous cases,
+// from k_mc_amb's side table (the tests on the cell's eight values ran there) -- and adds up their triangle counts; ONE wave scan over the lanes
+// turns the sums into offsets, and the lane hands them to its cells.  The cells whose tiling has a centre vertex are
+// collected per word (ccm): their vertices follow the word's edge vertices in the output.
+// (s_lwc: LT_LWC_FIXED in LDS, once per workgroup: a cell's tiling without a global round trip)
+__device__ __forceinline__ void emit_cells(const mc_emit_args& a, mc_batch& s, const unsigned* s_lwc, int lane, int nw) {
+  const mc_dims& D = a.D;
+  int run = 0;  // triangles of the pairs before this round of 64
 #pragma unroll
-    for (int i = 0; i < NPV; ++i) {
-      const int p = lane + 64 * i, k = p >> 3, seg = p & 7;
-      unsigned ac8 = 0, ntp = 0;  // ntp: the triangle counts of the segment's cells, 4 bits each, in cell order
-      int c0 = 0, tsum = 0;
-      if (k < nw) {
-        const u64 ac = s_cm[k][8];
-        ac8 = (unsigned)(ac >> (8 * seg)) & 255u;
-        if (ac8) {
-          c0 = s_cpre[k] + __popcll(ac & ((1ull << (8 * seg)) - 1ull));
-          unsigned m8[8];  // the corner masks' bits of this segment
+  for (int i = 0; i < LT_MC_NPV; ++i) {
+    const int p = lane + 64 * i, k = p >> 3, seg = p & 7;
+    unsigned ac8 = 0, ntp = 0;  // ntp: the triangle counts of the segment's cells, 4 bits each, in cell order
+    int c0 = 0, tsum = 0;
+    if (k < nw) {
+      const u64 ac = s.cm[k][8];
+      ac8 = (unsigned)(ac >> (8 * seg)) & 255u;
+      if (ac8) {
+        c0 = s.cpre[k] + __popcll(ac & ((1ull << (8 * seg)) - 1ull));
+        unsigned m8[8];  // the corner masks' bits of this segment
 #pragma unroll
-          for (int q = 0; q < 8; ++q) m8[q] = (unsigned)(s_cm[k][q] >> (8 * seg)) & 255u;
-          int c = c0, sh = 0;
-          unsigned cm8 = 0;
-          // the tilings of the segment's (up to eight) cells: ALL table look-ups first, independent of one another -- a loop
-          // over the set bits with the look-up inside was a chain of dependent global loads, one per cell of the fullest lane
-          // (the section's 3.0 of a batch's 9.4 us, tools/mc_wave_times.py)
-          // case index of voxel bb: bit q = bit bb of corner mask q (mc_case: corner q = dx | dy << 1 | dz << 2) -- the
-          // transpose of an 8 x 8 bit matrix (rows = the masks' bytes), three swap steps on a 64-bit word instead of 64
-          // single-bit moves
-          u64 tm = 0ull;
+        for (int q = 0; q < 8; ++q) m8[q] = (unsigned)(s.cm[k][q] >> (8 * seg)) & 255u;
+        int c = c0, sh = 0;
+        unsigned cm8 = 0;
+        // the tilings of the segment's (up to eight) cells: ALL table look-ups first, independent of one another -- a loop
+        // over the set bits with the look-up inside was a chain of dependent global loads, one per cell of the fullest lane
+        // (the section's 3.0 of a batch's 9.4 us, tools/mc_wave_times.py)
+        // case index of voxel bb: bit q = bit bb of corner mask q (mc_case: corner q = dx | dy << 1 | dz << 2) -- the
+        // transpose of an 8 x 8 bit matrix (rows = the masks' bytes), three swap steps on a 64-bit word instead of 64
+        // single-bit moves
+        u64 tm = 0ull;
 #pragma unroll
-          for (int q = 0; q < 8; ++q) tm |= (u64)m8[q] << (8 * q);
-          u64 tt = (tm ^ (tm >> 7)) & 0x00AA00AA00AA00AAull;
-          tm ^= tt ^ (tt << 7);
-          tt = (tm ^ (tm >> 14)) & 0x0000CCCC0000CCCCull;
-          tm ^= tt ^ (tt << 14);
-          tt = (tm ^ (tm >> 28)) & 0x00000000F0F0F0F0ull;
-          tm ^= tt ^ (tt << 28);
-          unsigned selv[8];
+        for (int q = 0; q < 8; ++q) tm |= (u64)m8[q] << (8 * q);
+        u64 tt = (tm ^ (tm >> 7)) & 0x00AA00AA00AA00AAull;
+        tm ^= tt ^ (tt << 7);
+        tt = (tm ^ (tm >> 14)) & 0x0000CCCC0000CCCCull;
+        tm ^= tt ^ (tt << 14);
+        tt = (tm ^ (tm >> 28)) & 0x00000000F0F0F0F0ull;
+        tm ^= tt ^ (tt << 28);
+        unsigned selv[8];
 #pragma unroll
-          for (int bb = 0; bb < 8; ++bb) {
-            const unsigned cs = (unsigned)(tm >> (8 * bb)) & 255u;
-            selv[bb] = ((ac8 >> bb) & 1u) ? s_lwc[cs] : 0u;
-          }
-#pragma unroll
-          for (int bb = 0; bb < 8; ++bb) {
-            if (!((ac8 >> bb) & 1u)) continue;
-            unsigned sel = selv[bb];
-            if (sel == 0xFFFFFFFFu)  // an ambiguous case: the tiling k_mc_amb filed under the cell's voxel index
-              sel = amb_lookup(A, (unsigned)((s_xyz[k][0] * D.ny + s_xyz[k][1]) * D.nz + s_xyz[k][2] * 64 + 8 * seg + bb));
-            const unsigned nt = LW_NT(sel);
-            s_cl[c] = (unsigned)k | ((unsigned)(8 * seg + bb) << 4) | (nt << 10) | (LW_C(sel) << 14) | (LW_OFF(sel) << 15);
-            cm8 |= LW_C(sel) << bb;
-            ntp |= nt << sh;
-            tsum += (int)nt;
-            ++c; sh += 4;
-          }
-          if (cm8) atomicOr((unsigned long long*)&s_ccm[k], (unsigned long long)cm8 << (8 * seg));
+        for (int bb = 0; bb < 8; ++bb) {
+          const unsigned cs = (unsigned)(tm >> (8 * bb)) & 255u;
+          selv[bb] = ((ac8 >> bb) & 1u) ? s_lwc[cs] : 0u;
         }
-      }
-      int inc = tsum;
 #pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int q = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += q;
+        for (int bb = 0; bb < 8; ++bb) {
+          if (!((ac8 >> bb) & 1u)) continue;
+          unsigned sel = selv[bb];
+          if (sel == 0xFFFFFFFFu)  // an ambiguous case: the tiling k_mc_amb filed under the cell's voxel index
+            sel = amb_lookup(a.A, (unsigned)((s.xyz[k][0] * D.ny + s.xyz[k][1]) * D.nz + s.xyz[k][2] * 64 + 8 * seg + bb));
+          const unsigned nt = LW_NT(sel);
+          s.cl[c] = (unsigned)k | ((unsigned)(8 * seg + bb) << 4) | (nt << 10) | (LW_C(sel) << 14) | (LW_OFF(sel) << 15);
+          cm8 |= LW_C(sel) << bb;
+          ntp |= nt << sh;
+          tsum += (int)nt;
+          ++c; sh += 4;
+        }
+        if (cm8) atomicOr((unsigned long long*)&s.ccm[k], (unsigned long long)cm8 << (8 * seg));
       }
-      int t0 = run + inc - tsum;
-      int c = c0;
-      for (unsigned a8 = ac8; a8; a8 &= a8 - 1u, ++c, ntp >>= 4) {
-        s_ct[c] = (unsigned short)t0;
-        t0 += (int)(ntp & 15u);
-      }
-      run += __shfl(inc, 63, 64);
     }
+    int inc = tsum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int q = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += q;
+    }
+    int t0 = run + inc - tsum;
+    int c = c0;
+    for (unsigned a8 = ac8; a8; a8 &= a8 - 1u, ++c, ntp >>= 4) {
+      s.ct[c] = (unsigned short)t0;
+      t0 += (int)(ntp & 15u);
+    }
+    run += __shfl(inc, 63, 64);
   }
   LT_MC_WSYNC();
-  LT_MC_SECTION(5);  // cell masks, cell list, triangle offsets
-#if defined(LT_MC_STOP) && LT_MC_STOP == 4  // ... + cell list and scan
-  continue;
-#endif
-  // ---- vertices
-  // Listing: a lane takes one (word, SEGMENT of 8 voxels) pair -- 8 K pairs, one per lane for K = 8 --, finds where its
-  // segment's vertices start in the batch's output range (the word's base + three popcounts below the segment: no search,
-  // no scan) and walks its own voxels.  A street scene's segment holds 0.45 vertices on average and 24 at most: the walk
-  // is short where the batch is sparse and costs what a lane-per-voxel pass costs where it is dense (walls along z), so one
-  // path serves both -- the lane-per-ITEM search it replaces (word by the bases, voxel by a 6-step binary search over
-  // three 64-bit popcounts) was 277 vector instructions per batch.
+}
+
+// ---- vertices, a window of LT_MC_VCAP at a time: listed, then a lane per vertex
+// Listing: a lane takes one (word, SEGMENT of 8 voxels) pair -- 8 K pairs, one per lane for K = 8 --, finds where its
+// segment's vertices start in the batch's output range (the word's base + three popcounts below the segment: no search,
+// no scan) and walks its own voxels.  A street scene's segment holds 0.45 vertices on average and 24 at most: the walk
+// is short where the batch is sparse and costs what a lane-per-voxel pass costs where it is dense (walls along z), so one
+// path serves both -- the lane-per-ITEM search it replaces (word by the bases, voxel by a 6-step binary search over
+// three 64-bit popcounts) was 277 vector instructions per batch.
+// AOS: the three field pointers are one array of (tsdf, weight, colour, remission) records (a TSDF volume, D.vs == 4): an
+// edge vertex's two field samples and its attributes -- which are those of one of the edge's two ends -- come with TWO
+// 16-byte loads, nothing waits for the vertex rule (separate arrays: four loads, the last two behind the rule)
+template <bool AOS>
+__device__ __forceinline__ void emit_vertices(const mc_emit_args& a, mc_batch& s, int lane, const mc_extent& e, mc_stamp& st) {
+  const mc_dims& D = a.D;
+  const int nw = e.nw, vbase0 = e.vbase0, nvt = e.nvt;
+  const size_t sy = (size_t)D.nz, sx = (size_t)D.ny * D.nz;
   for (int vb = 0; vb < nvt; vb += LT_MC_VCAP) {
 #pragma unroll
-    for (int i = 0; i < NPV; ++i) {
+    for (int i = 0; i < LT_MC_NPV; ++i) {
       const int p = lane + 64 * i, k = p >> 3, seg = p & 7;
       if (k < nw) {
-        const mc_rec R = s_rec[k];
+        const mc_rec R = s.rec[k];
         const unsigned ex8 = (unsigned)(R.ex >> (8 * seg)) & 255u, ey8 = (unsigned)(R.ey >> (8 * seg)) & 255u,
                        ez8 = (unsigned)(R.ez >> (8 * seg)) & 255u;
         unsigned any = ex8 | ey8 | ez8;
@@ -1064,42 +1070,42 @@ __global__ __launch_bounds__(64 * LT_MC_EW) void k_mc_emit_batch(const float* __
           const unsigned e0 = (unsigned)k | ((unsigned)(8 * seg) << 4);
           for (; any; any &= any - 1u) {
             const int bb = __ffs((int)any) - 1;
-            const unsigned e = e0 + ((unsigned)bb << 4);
-            if ((ex8 >> bb) & 1u) { if ((unsigned)j < LT_MC_VCAP) s_vl[j] = (unsigned short)e; ++j; }
-            if ((ey8 >> bb) & 1u) { if ((unsigned)j < LT_MC_VCAP) s_vl[j] = (unsigned short)(e | (1u << 10)); ++j; }
-            if ((ez8 >> bb) & 1u) { if ((unsigned)j < LT_MC_VCAP) s_vl[j] = (unsigned short)(e | (2u << 10)); ++j; }
+            const unsigned en = e0 + ((unsigned)bb << 4);
+            if ((ex8 >> bb) & 1u) { if ((unsigned)j < LT_MC_VCAP) s.vl[j] = (unsigned short)en; ++j; }
+            if ((ey8 >> bb) & 1u) { if ((unsigned)j < LT_MC_VCAP) s.vl[j] = (unsigned short)(en | (1u << 10)); ++j; }
+            if ((ez8 >> bb) & 1u) { if ((unsigned)j < LT_MC_VCAP) s.vl[j] = (unsigned short)(en | (2u << 10)); ++j; }
           }
         }
         // the centre vertices of the segment's cells: after all edge vertices of the word, in cell order
-        const u64 ccm = s_ccm[k];
+        const u64 ccm = s.ccm[k];
         unsigned cm8 = (unsigned)(ccm >> (8 * seg)) & 255u;
         if (cm8) {
           int j = R.vbase - vbase0 - vb + __popcll(R.ex) + __popcll(R.ey) + __popcll(R.ez) + __popcll(ccm & ((1ull << (8 * seg)) - 1ull));
           for (; cm8; cm8 &= cm8 - 1u, ++j) {
             const int bb = __ffs((int)cm8) - 1;
-            if ((unsigned)j < LT_MC_VCAP) s_vl[j] = (unsigned short)((unsigned)k | ((unsigned)(8 * seg + bb) << 4) | (3u << 10));
+            if ((unsigned)j < LT_MC_VCAP) s.vl[j] = (unsigned short)((unsigned)k | ((unsigned)(8 * seg + bb) << 4) | (3u << 10));
           }
         }
       }
     }
     LT_MC_WSYNC();
-    LT_MC_SECTION(3);  // vertex list
+    LT_MC_SECTION(st, 3);  // vertex list
 #if defined(LT_MC_STOP) && LT_MC_STOP == 2  // ... + vertex list
     continue;
 #endif
     const int nwin = min(LT_MC_VCAP, nvt - vb);
     for (int j = lane; j < nwin; j += 64) {
-      const unsigned e = s_vl[j];
-      const int k = e & 15, b = (e >> 4) & 63, a = (e >> 10) & 3;
-      const int x = s_xyz[k][0], y = s_xyz[k][1], z = s_xyz[k][2] * 64 + b;
-      const size_t i = s_base[k] + (size_t)b;  // (64-bit multiplications are quarter rate: once per word, not per vertex)
+      const unsigned en = s.vl[j];
+      const int k = en & 15, b = (en >> 4) & 63, ax = (en >> 10) & 3;
+      const int x = s.xyz[k][0], y = s.xyz[k][1], z = s.xyz[k][2] * 64 + b;
+      const size_t i = s.base[k] + (size_t)b;  // (64-bit multiplications are quarter rate: once per word, not per vertex)
       float p0 = (float)x, p1 = (float)y, p2 = (float)z;
       constexpr size_t VS = AOS ? 4 : 1;
       float rgb, rm;
-      if (a == 3) {
+      if (ax == 3) {
         // the cell's centre vertex (Cell.calculate_center_vertex): the centre of mass of the eight corners with weights
         // 1 / (eps + |v|), summed in Lewiner's corner order (0 .. 7) in double, stored as float32
-        const float* c = tsdf + i * VS;
+        const float* c = a.tsdf + i * VS;
         double ff = 0.0, f0 = 0.0, f1 = 0.0, f2 = 0.0;
 #pragma unroll 1  // (rare: a rolled loop keeps the kernel's registers where they were without the centre vertex)
         for (int q = 0; q < 8; ++q) {  // Lewiner's corner q sits at (a0, a1, a2) = (q >> 2, q >> 1 & 1, (q ^ q >> 1) & 1)
@@ -1117,93 +1123,147 @@ __global__ __launch_bounds__(64 * LT_MC_EW) void k_mc_emit_batch(const float* __
         // field value, on which numpy would raise -- counts as "the next one": never a wild address.)
         const size_t jj = i + ((int)rintf(p0) == x ? (size_t)0 : sx) + ((int)rintf(p1) == y ? (size_t)0 : sy) +
                           ((int)rintf(p2) == z ? (size_t)0 : (size_t)1);
-        rgb = color_vol[jj * VS];
-        rm = rem_vol[jj * VS];
+        rgb = a.color_vol[jj * VS];
+        rm = a.rem_vol[jj * VS];
       } else {
-        const size_t i1 = i + (a == 0 ? sx : (a == 1 ? sy : (size_t)1));
-        const int ce = a == 0 ? x : (a == 1 ? y : z);
+        const size_t i1 = i + (ax == 0 ? sx : (ax == 1 ? sy : (size_t)1));
+        const int ce = ax == 0 ? x : (ax == 1 ? y : z);
         if (AOS) {
-          const float4 q0 = reinterpret_cast<const float4*>(tsdf)[i], q1 = reinterpret_cast<const float4*>(tsdf)[i1];
+          const float4 q0 = reinterpret_cast<const float4*>(a.tsdf)[i], q1 = reinterpret_cast<const float4*>(a.tsdf)[i1];
           const float pe = mc_edge_coord(ce, q0.x, q1.x);
-          if (a == 0) p0 = pe; else if (a == 1) p1 = pe; else p2 = pe;
+          if (ax == 0) p0 = pe; else if (ax == 1) p1 = pe; else p2 = pe;
           const bool far_end = (int)rintf(pe) != ce;
           rgb = far_end ? q1.z : q0.z;
           rm = far_end ? q1.w : q0.w;
         } else {
-          const float pe = mc_edge_coord(ce, tsdf[i], tsdf[i1]);
-          if (a == 0) p0 = pe; else if (a == 1) p1 = pe; else p2 = pe;
+          const float pe = mc_edge_coord(ce, a.tsdf[i], a.tsdf[i1]);
+          if (ax == 0) p0 = pe; else if (ax == 1) p1 = pe; else p2 = pe;
           const size_t jj = (int)rintf(pe) != ce ? i1 : i;
-          rgb = color_vol[jj];
-          rm = rem_vol[jj];
+          rgb = a.color_vol[jj];
+          rm = a.rem_vol[jj];
         }
       }
       const int vid = vbase0 + vb + j;
-      if (vid < cap_v) {
-        verts[3 * (size_t)vid] = p0 * voxel_size + ox;  // verts * voxel_size + vol_origin in float32 (:412)
-        verts[3 * (size_t)vid + 1] = p1 * voxel_size + oy;
-        verts[3 * (size_t)vid + 2] = p2 * voxel_size + oz;
+      if (vid < a.cap_v) {
+        a.verts[3 * (size_t)vid] = p0 * a.voxel_size + a.ox;  // verts * voxel_size + vol_origin in float32 (:412)
+        a.verts[3 * (size_t)vid + 1] = p1 * a.voxel_size + a.oy;
+        a.verts[3 * (size_t)vid + 2] = p2 * a.voxel_size + a.oz;
         // colour unfolding (:419-423) in float32, .astype(np.uint8) = truncation to 8 bits
         const float cb = floorf(rgb / (float)(256 * 256));
         const float cg = floorf((rgb - cb * 256.0f * 256.0f) / 256.0f);
         const float cr = rgb - cb * 256.0f * 256.0f - cg * 256.0f;
-        colors[3 * (size_t)vid] = (int)floorf(cr) & 255;
-        colors[3 * (size_t)vid + 1] = (int)floorf(cg) & 255;
-        colors[3 * (size_t)vid + 2] = (int)floorf(cb) & 255;
-        rem[vid] = rm;
+        a.colors[3 * (size_t)vid] = (int)floorf(cr) & 255;
+        a.colors[3 * (size_t)vid + 1] = (int)floorf(cg) & 255;
+        a.colors[3 * (size_t)vid + 2] = (int)floorf(cb) & 255;
+        a.rem[vid] = rm;
       }
     }
     LT_MC_WSYNC();
   }
-  LT_MC_SECTION(4);  // vertex pass (field samples, attributes, stores drained)
-#if defined(LT_MC_STOP) && LT_MC_STOP == 3  // ... + vertex pass
-  continue;
-#endif
-  // ---- triangles (cells exist where x + 1 < nx, y + 1 < ny, z + 1 < nz): their cells were listed above
+}
+
+// ---- triangles (cells exist where x + 1 < nx, y + 1 < ny, z + 1 < nz), a window of LT_MC_TCAP at a time: the cells listed
+// by emit_cells put their triangles into the window's list, then a lane per triangle computes its three indices
+__device__ __forceinline__ void emit_triangles(const mc_emit_args& a, mc_batch& s, int lane, const mc_extent& e) {
+  const int ncell = e.ncell, tbase0 = e.tbase0, ntt = e.ntt;
   for (int tb = 0; tb < ntt; tb += LT_MC_TCAP) {
     for (int c = lane; c < ncell; c += 64) {  // a cell's (up to twelve) triangles into the window's list
-      const int nt = (int)((s_cl[c] >> 10) & 15u);
-      const int j0 = (int)s_ct[c] - tb;
+      const int nt = (int)((s.cl[c] >> 10) & 15u);
+      const int j0 = (int)s.ct[c] - tb;
       for (int t = 0; t < nt; ++t)
-        if ((unsigned)(j0 + t) < LT_MC_TCAP) s_tl[j0 + t] = (unsigned short)((unsigned)c | ((unsigned)t << 10));
+        if ((unsigned)(j0 + t) < LT_MC_TCAP) s.tl[j0 + t] = (unsigned short)((unsigned)c | ((unsigned)t << 10));
     }
     LT_MC_WSYNC();
     const int nwin = min(LT_MC_TCAP, ntt - tb);
     for (int j = lane; j < nwin; j += 64) {
-      const unsigned tl = s_tl[j];
-      const unsigned e = s_cl[tl & 1023u];
-      const int k = e & 15, b = (e >> 4) & 63, t = (int)(tl >> 10);
+      const unsigned tl = s.tl[j];
+      const unsigned en = s.cl[tl & 1023u];
+      const int k = en & 15, b = (en >> 4) & 63, t = (int)(tl >> 10);
       // the triangle's three codes in one 16-bit word (already in the reference's order: np.fliplr(faces)); three byte loads
       // with a branch on each were three dependent round trips per triangle window
-      const unsigned codes = LT_LWF3[(e >> 15) / 3u + (unsigned)t];
+      const unsigned codes = LT_LWF3[(en >> 15) / 3u + (unsigned)t];
       const int tid = tbase0 + tb + j;
       int id[3];
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         const int code = (int)((codes >> (5 * q)) & 31u);
         if (code == 31) {  // the cell's centre vertex: behind the word's edge vertices, ranked among the word's centre cells
-          const mc_rec& Rk = s_rec[k];
-          id[q] = Rk.vbase + __popcll(Rk.ex) + __popcll(Rk.ey) + __popcll(Rk.ez) + __popcll(s_ccm[k] & ((1ull << b) - 1ull));
+          const mc_rec& Rk = s.rec[k];
+          id[q] = Rk.vbase + __popcll(Rk.ex) + __popcll(Rk.ey) + __popcll(Rk.ez) + __popcll(s.ccm[k] & ((1ull << b) - 1ull));
           continue;
         }
         const int c0 = code & 7, ax = code >> 3;
         int b2 = b + ((c0 >> 2) & 1), slot = c0 & 3;
         if (b2 == 64) { b2 = 0; slot |= 4; }
-        const mc_nb nbe = s_nb[k][slot];
+        const mc_nb nbe = s.nb[k][slot];
         const u64 l2 = (1ull << b2) - 1ull;
         int v = nbe.vbase + __popcll(nbe.ex & l2) + __popcll(nbe.ey & l2) + __popcll(nbe.ez & l2);
         if (ax > 0) v += (int)((nbe.ex >> b2) & 1ull);
         if (ax > 1) v += (int)((nbe.ey >> b2) & 1ull);
         id[q] = v;
       }
-      if (tid < cap_f) {
-        faces[3 * (size_t)tid] = id[0];
-        faces[3 * (size_t)tid + 1] = id[1];
-        faces[3 * (size_t)tid + 2] = id[2];
+      if (tid < a.cap_f) {
+        a.faces[3 * (size_t)tid] = id[0];
+        a.faces[3 * (size_t)tid + 1] = id[1];
+        a.faces[3 * (size_t)tid + 2] = id[2];
       }
     }
     LT_MC_WSYNC();
   }
-    LT_MC_SECTION(6);  // triangle list + pass (stores drained)
+}
+
+// Batch order: active words are numbered x-major, so the batch list walks the volume plane by plane.  Workgroups are dealt
+// to the eight XCDs round-robin (workgroup id % 8) and the L2s are private: with `xcd_map` XCD q takes the q-th EIGHTH of
+// the batch list (its waves in turn within it), so that the columns (x + 1, y) / (x, y + 1) a batch samples are the OWN
+// columns of batches the same L2 serves moments later -- instead of every plane's lines being pulled into all eight L2s.
+// xcd_map = C > 0: the list is cut into CHUNKS of C batches (a few planes), chunk c belongs to XCD c % 8, and the waves of
+// an XCD take the batches of its chunks in turn -- eight contiguous eighths (one per XCD) moved the fewest bytes but the
+// XCDs finished at different times (a batch costs 1.5 - 42 us depending on where in the scene it lies).
+// -> the batch of a wave's turn `it` (xcd_map: a turn of XCD xq's waves); -1: the list is exhausted.  With xcd_map the
+// batch may lie behind the list's end -- the last round of eight chunks is partial: nothing to do in this turn
+__device__ __forceinline__ int mc_batch_of(int it, int xcd_map, int xq, int n_batches) {
+  if (!xcd_map) return it < n_batches ? it : -1;
+  const int round = it / xcd_map;  // (of eight chunks)
+  return round * 8 * xcd_map < n_batches ? (round * 8 + xq) * xcd_map + it % xcd_map : -1;
+}
+
+// the kernel: a wave takes batches until none is left (by default the grid has a wave per batch -- see the launch).
+// (launch bounds: the five workgroups per CU that LDS admits -- five waves per SIMD -- are the register budget; left to
+// itself the allocator took 102 registers with the working set in one struct, four waves, and 83 when told)
+template <bool AOS>
+__global__ __launch_bounds__(64 * LT_MC_EW, 5) void k_mc_emit_batch(const mc_emit_args a) {
+  __shared__ mc_batch S[LT_MC_EW];
+  __shared__ unsigned s_lwc[256];  // LT_LWC_FIXED, once per workgroup: a cell's tiling without a global round trip
+  s_lwc[threadIdx.x & 255u] = LT_LWC_FIXED[threadIdx.x & 255u];
+  __syncthreads();  // (the only workgroup barrier: before any wave's first batch)
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)(threadIdx.x & 63u);
+  mc_batch& s = S[wv];
+  const int n_batches = (a.n_active + LT_MC_K - 1) / LT_MC_K;
+  const int xcd_map = a.xcd_map;
+  const int per_xcd = (int)(gridDim.x >> 3) * LT_MC_EW, xq = blockIdx.x & 7, xslot = (int)(blockIdx.x >> 3) * LT_MC_EW + wv;
+  if (xcd_map && xslot >= per_xcd) return;  // (a grid that is not a multiple of eight: the tail waves have no share)
+  for (int it = xcd_map ? xslot : (int)blockIdx.x * LT_MC_EW + wv;; it += xcd_map ? per_xcd : (int)gridDim.x * LT_MC_EW) {
+    const int bi = mc_batch_of(it, xcd_map, xq, n_batches);
+    if (bi < 0) break;
+    if (bi >= n_batches) continue;
+    mc_stamp st = LT_MC_SECTION_START(bi);
+    const mc_extent e = emit_stage(a, s, lane, bi * LT_MC_K, st);
+#if defined(LT_MC_STOP) && LT_MC_STOP == 1  // instruction-count experiment (tools/mc_sections.sh): staging only
+    continue;
+#endif
+    emit_cells(a, s, s_lwc, lane, e.nw);
+    LT_MC_SECTION(st, 5);  // cell masks, cell list, triangle offsets
+#if defined(LT_MC_STOP) && LT_MC_STOP == 4  // ... + cell list and scan
+    continue;
+#endif
+    emit_vertices<AOS>(a, s, lane, e, st);
+    LT_MC_SECTION(st, 4);  // vertex pass (field samples, attributes, stores drained)
+#if defined(LT_MC_STOP) && LT_MC_STOP == 3  // ... + vertex pass
+    continue;
+#endif
+    emit_triangles(a, s, lane, e);
+    LT_MC_SECTION(st, 6);  // triangle list + pass (stores drained)
     LT_MC_WSYNC();  // the batch's arrays are reused
   }
 }
@@ -1260,19 +1320,45 @@ extern "C" int lt_mesh_get(lt_mesh* m, int* n_verts, int* n_faces, float** verts
   return LT_OK;
 }
 
+// A group of device arrays that share one capacity is replaced: the old arrays freed (after the device has finished with
+// them), the new ones allocated, *cap = new_cap.  On failure nothing of the group is left and *cap is 0.
+struct mc_array { void** p; size_t bytes; };
+template <class C, size_t N>
+static hipError_t mc_realloc(C* cap, C new_cap, const mc_array (&group)[N]) {
+  auto drop = [&]() {
+    for (const mc_array& g : group) { (void)hipFree(*g.p); *g.p = nullptr; }
+    *cap = 0;
+  };
+  bool any = false;
+  for (const mc_array& g : group) any = any || *g.p;
+  hipError_t e = any ? hipDeviceSynchronize() : hipSuccess;
+  if (e != hipSuccess) return e;
+  drop();
+  for (const mc_array& g : group)
+    if (e == hipSuccess) e = hipMalloc(g.p, g.bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    drop();
+    return e;
+  }
+  *cap = new_cap;
+  return hipSuccess;
+}
+
 template <class T>
 static int mc_grow(T** p, size_t* cap, size_t need) {
   if (need <= *cap && *p) return LT_OK;
-  if (*p) {
-    LT_HIP(hipDeviceSynchronize());
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-  }
   const size_t n = need + need / 4 + 1024;
-  LT_HIP(hipMalloc((void**)p, n * sizeof(T)));
-  *cap = n;
+  const mc_array one[] = {{(void**)p, n * sizeof(T)}};
+  LT_HIP(mc_realloc(cap, n, one));
   return LT_OK;
+}
+
+static mc_emit_args mc_emit_args_of(const float* tsdf, const float* color_vol, const float* rem_vol, const u64* bits,
+                                    const mc_dims& D, const lt_mesh* m, int n_active, float voxel_size, const float* origin,
+                                    int xcd_map) {
+  return {tsdf, color_vol, rem_vol, bits, D, m->cmap, m->rec, n_active, voxel_size, origin[0], origin[1], origin[2],
+          m->verts, m->faces, m->colors, m->rem, m->cap_v, m->cap_f, m->amb, xcd_map};  // (in mc_emit_args' order)
 }
 
 static int mc_extract(const float* tsdf, const float* color_vol, const float* rem_vol, int vs, int nx, int ny, int nz,
@@ -1312,90 +1398,83 @@ static int mc_extract(const float* tsdf, const float* color_vol, const float* re
     return LT_ERR_TOO_LARGE;
   }
   if (n_words > m->cap_words || !m->bits) {
-    if (m->bits) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(m->bits); (void)hipFree(m->cnt); (void)hipFree(m->cmap);
-      m->bits = nullptr; m->cnt = nullptr; m->cmap = nullptr;
-      m->cap_words = 0;
-    }
-    LT_HIP(hipMalloc((void**)&m->bits, (n_words + 1) * sizeof(u64)));
-    LT_HIP(hipMalloc((void**)&m->cnt, n_words * sizeof(unsigned)));
-    LT_HIP(hipMalloc((void**)&m->cmap, n_words * sizeof(int)));
-    m->cap_words = n_words;
+    const mc_array words[] = {{(void**)&m->bits, (n_words + 1) * sizeof(u64)}, {(void**)&m->cnt, n_words * sizeof(unsigned)},
+                              {(void**)&m->cmap, n_words * sizeof(int)}};
+    LT_HIP(mc_realloc(&m->cap_words, n_words, words));
     m->state_dirty = 1;  // (fresh buffers: swept below)
   }
-  // the ambiguous cells' queue and tiling table: grown when an extraction queued more cells than fit (below)
-  if (!m->amb.queue) {
-    const size_t cap = m->amb_cap ? m->amb_cap : (size_t)1 << 10;   // per shard
-    size_t tcap = 1;
-    while (tcap < 4 * LT_MC_SHARDS * cap) tcap <<= 1;
-    const size_t n_ctr = LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS;
-    if (hipMalloc((void**)&m->amb.queue, LT_MC_SHARDS * cap * sizeof(uint2)) != hipSuccess || hipMalloc((void**)&m->amb.table, tcap * sizeof(uint2)) != hipSuccess ||
-        (!m->amb.counter && hipMalloc((void**)&m->amb.counter, n_ctr * sizeof(int)) != hipSuccess)) {
-      (void)hipGetLastError();
-      (void)hipFree(m->amb.queue); (void)hipFree(m->amb.table);
-      m->amb.queue = nullptr; m->amb.table = nullptr;
-      lt_set_error("lt_marching_cubes_dev: hipMalloc of the ambiguous cells' buffers (%zu cells) failed", cap);
-      return LT_ERR_NO_MEMORY;
-    }
-    m->amb_cap = cap;
-    m->amb.cap = (unsigned)cap;
-    m->amb.tmask = (unsigned)(tcap - 1);
-    LT_HIP(hipMemsetAsync(m->amb.counter, 0, n_ctr * sizeof(int), stream));
-    LT_HIP(hipMemsetAsync(m->amb.table, 0, tcap * sizeof(uint2), stream));
-    m->n_amb_prev = 0;
-  }
-  if (m->state_dirty) {  // new buffers, or an extraction that did not finish: cnt = 0, cmap = -1 everywhere, once
-    LT_HIP(hipMemsetAsync(m->cnt, 0, m->cap_words * sizeof(unsigned), stream));
-    LT_HIP(hipMemsetAsync(m->cmap, 0xFF, m->cap_words * sizeof(int), stream));
-    LT_HIP(hipMemsetAsync(m->amb.counter, 0, (LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS) * sizeof(int), stream));
-    LT_HIP(hipMemsetAsync(m->amb.table, 0, ((size_t)m->amb.tmask + 1) * sizeof(uint2), stream));
-    m->n_prev = 0;
-    m->n_amb_prev = 0;
-  } else if (m->n_prev > 0) {
-    hipLaunchKernelGGL(k_mc_clear, dim3((max(m->n_prev, LT_MC_SHARDS * m->n_amb_prev) + 255) / 256), dim3(256), 0, stream, m->rec,
-                       m->n_prev, m->cnt, m->cmap, m->amb, m->n_amb_prev);
-  }
-  m->state_dirty = 1;  // until this extraction has finished
-  m->n_prev = 0;
-  m->n_amb_prev = 0;
-  LT_CHECK(mc_grow(&m->wave_na, &m->cap_wave_na, (size_t)n_blocks));
   const int n_seg = (n_blocks + 255) / 256;
-  if (n_seg > 1024) {
-    lt_set_error("lt_marching_cubes_dev: volume too large (%d words)", D.n_words);
-    return LT_ERR_TOO_LARGE;
-  }
-  LT_CHECK(mc_grow(&m->blk, &m->cap_blocks, (size_t)3 * n_blocks + 3 * (size_t)n_seg + 4));
-  int* seg_dev = m->blk + 3 * (size_t)n_blocks;
-  int* totals_dev = seg_dev + 3 * (size_t)n_seg;
-  if (ms) LT_HIP(hipEventRecord(m->ev[0], stream));
+  int* seg_dev = nullptr;
   // sign bits: the volume's own (kept current by integrate / reset, lt_tsdf.hip) or one pass over the float field
   const u64* bits = ext_bits ? ext_bits : m->bits;
-  if (!ext_bits)
-    hipLaunchKernelGGL(k_mc_signs, dim3((unsigned)min((size_t)16384, ((size_t)nx * ny + 255) / 256)), dim3(256), 0, stream,
-                       tsdf, D, m->bits, col_epoch, epoch);
-  if (ms) LT_HIP(hipEventRecord(m->ev[1], stream));
   // (a wave takes LT_MC_BLOCKS_PER_WAVE blocks, see k_mc_words)
   const int sweep_wgs = lt_deal_count(n_blocks, LT_MC_BLOCKS_PER_WAVE, ny, 4) / 4;
-  hipLaunchKernelGGL(k_mc_words, dim3(sweep_wgs), dim3(256), 0, stream, m->amb, bits, D, m->cnt, m->blk, ext_bits ? col_epoch : nullptr,
-                     epoch, ext_bits ? chunk_epoch : nullptr, m->wave_na, n_blocks);
-  // Lewiner's ambiguous cells (1-2 % of a street scene's): tests on their eight values, counts added, tilings filed
-  hipLaunchKernelGGL(k_mc_amb, dim3(2 * LT_MC_SHARDS), dim3(256), 0, stream, tsdf, D, m->amb, m->cnt, m->blk, m->wave_na);
-  hipLaunchKernelGGL(k_mc_scan1, dim3(n_seg), dim3(256), 0, stream, m->blk, n_blocks, seg_dev);
-  hipLaunchKernelGGL(k_mc_scan2, dim3(1), dim3(1024), 0, stream, seg_dev, n_seg, totals_dev, m->amb.counter, (int)m->amb.cap);
-  LT_HIP(hipMemcpyAsync(m->totals_host, totals_dev, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-  LT_HIP(hipStreamSynchronize(stream));  // the one synchronisation: the sizes of the mesh
-  if ((size_t)(unsigned)m->totals_host[3] > m->amb_cap) {
-    // more ambiguous cells in a shard than its segment holds (white noise: a third of all cells): the counts above are incomplete --
-    // larger buffers, and the extraction once more from the start (cnt / cmap are swept: state_dirty is still set)
+  // The counting part, up to the one synchronisation.  It runs a second time when it queued more ambiguous cells than the
+  // side buffers held: the second run's buffers hold them.
+  for (;;) {
+    // the ambiguous cells' queue and tiling table: m->amb_cap cells per shard, the counters allocated once
+    if (!m->amb.queue || !m->amb.counter || m->amb.cap != m->amb_cap) {
+      const size_t cap = m->amb_cap ? m->amb_cap : (size_t)1 << 10;   // per shard
+      size_t tcap = 1;
+      while (tcap < 4 * LT_MC_SHARDS * cap) tcap <<= 1;
+      const size_t n_ctr = LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS;
+      const mc_array amb[] = {{(void**)&m->amb.queue, LT_MC_SHARDS * cap * sizeof(uint2)}, {(void**)&m->amb.table, tcap * sizeof(uint2)}};
+      if (mc_realloc(&m->amb.cap, (unsigned)cap, amb) != hipSuccess ||
+          (!m->amb.counter && hipMalloc((void**)&m->amb.counter, n_ctr * sizeof(int)) != hipSuccess)) {
+        (void)hipGetLastError();
+        lt_set_error("lt_marching_cubes_dev: hipMalloc of the ambiguous cells' buffers (%zu cells) failed", cap);
+        return LT_ERR_NO_MEMORY;
+      }
+      m->amb_cap = cap;
+      m->amb.tmask = (unsigned)(tcap - 1);
+      LT_HIP(hipMemsetAsync(m->amb.counter, 0, n_ctr * sizeof(int), stream));
+      LT_HIP(hipMemsetAsync(m->amb.table, 0, tcap * sizeof(uint2), stream));
+      m->n_amb_prev = 0;
+    }
+    if (m->state_dirty) {  // new buffers, or an extraction that did not finish: cnt = 0, cmap = -1 everywhere, once
+      LT_HIP(hipMemsetAsync(m->cnt, 0, m->cap_words * sizeof(unsigned), stream));
+      LT_HIP(hipMemsetAsync(m->cmap, 0xFF, m->cap_words * sizeof(int), stream));
+      LT_HIP(hipMemsetAsync(m->amb.counter, 0, (LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS) * sizeof(int), stream));
+      LT_HIP(hipMemsetAsync(m->amb.table, 0, ((size_t)m->amb.tmask + 1) * sizeof(uint2), stream));
+      m->n_prev = 0;
+      m->n_amb_prev = 0;
+    } else if (m->n_prev > 0) {
+      hipLaunchKernelGGL(k_mc_clear, dim3((max(m->n_prev, LT_MC_SHARDS * m->n_amb_prev) + 255) / 256), dim3(256), 0, stream, m->rec,
+                         m->n_prev, m->cnt, m->cmap, m->amb, m->n_amb_prev);
+    }
+    m->state_dirty = 1;  // until this extraction has finished
+    m->n_prev = 0;
+    m->n_amb_prev = 0;
+    LT_CHECK(mc_grow(&m->wave_na, &m->cap_wave_na, (size_t)n_blocks));
+    if (n_seg > 1024) {
+      lt_set_error("lt_marching_cubes_dev: volume too large (%d words)", D.n_words);
+      return LT_ERR_TOO_LARGE;
+    }
+    LT_CHECK(mc_grow(&m->blk, &m->cap_blocks, (size_t)3 * n_blocks + 3 * (size_t)n_seg + 4));
+    seg_dev = m->blk + 3 * (size_t)n_blocks;
+    int* totals_dev = seg_dev + 3 * (size_t)n_seg;
+    if (ms) LT_HIP(hipEventRecord(m->ev[0], stream));
+    if (!ext_bits)
+      hipLaunchKernelGGL(k_mc_signs, dim3((unsigned)min((size_t)16384, ((size_t)nx * ny + 255) / 256)), dim3(256), 0, stream,
+                         tsdf, D, m->bits, col_epoch, epoch);
+    if (ms) LT_HIP(hipEventRecord(m->ev[1], stream));
+    hipLaunchKernelGGL(k_mc_words, dim3(sweep_wgs), dim3(256), 0, stream, m->amb, bits, D, m->cnt, m->blk, ext_bits ? col_epoch : nullptr,
+                       epoch, ext_bits ? chunk_epoch : nullptr, m->wave_na, n_blocks);
+    // Lewiner's ambiguous cells (1-2 % of a street scene's): tests on their eight values, counts added, tilings filed
+    hipLaunchKernelGGL(k_mc_amb, dim3(2 * LT_MC_SHARDS), dim3(256), 0, stream, tsdf, D, m->amb, m->cnt, m->blk, m->wave_na);
+    hipLaunchKernelGGL(k_mc_scan1, dim3(n_seg), dim3(256), 0, stream, m->blk, n_blocks, seg_dev);
+    hipLaunchKernelGGL(k_mc_scan2, dim3(1), dim3(1024), 0, stream, seg_dev, n_seg, totals_dev, m->amb.counter, (int)m->amb.cap);
+    LT_HIP(hipMemcpyAsync(m->totals_host, totals_dev, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    LT_HIP(hipStreamSynchronize(stream));  // the one synchronisation: the sizes of the mesh
     const size_t need = (size_t)(unsigned)m->totals_host[3];
-    (void)hipFree(m->amb.queue); (void)hipFree(m->amb.table);
-    m->amb.queue = nullptr; m->amb.table = nullptr;
+    if (need <= m->amb_cap) break;
+    // more ambiguous cells in a shard than its segment holds (white noise: a third of all cells): the counts above are incomplete --
+    // larger buffers, and the counting once more from the start (cnt / cmap are swept: state_dirty is still set)
     m->amb_cap = need + need / 4 + 1024;
-    return mc_extract(tsdf, color_vol, rem_vol, vs, nx, ny, nz, voxel_size, origin, m, stream_, ms, col_epoch, epoch, ext_bits, chunk_epoch);
   }
   const int n_active = m->totals_host[0], nv = m->totals_host[1], nf = m->totals_host[2];
   static const bool dbg_mc = getenv("LIDARHIP_DEBUG_MC") != nullptr;
+  // (tests/test_mc_gpu.py reads this line: keep its wording)
   if (dbg_mc) fprintf(stderr, "marching cubes: %d active words, %d vertices, %d triangles\n", n_active, nv, nf);
   if (nv == 2147483647 || nf == 2147483647) {
     lt_set_error("lt_marching_cubes_dev: mesh exceeds 2^31 - 1 vertices / faces");
@@ -1407,40 +1486,21 @@ static int mc_extract(const float* tsdf, const float* color_vol, const float* re
   }
   LT_CHECK(mc_grow(&m->rec, &m->cap_rec, (size_t)n_active));
   if (nv > m->cap_v || !m->verts) {
-    if (m->verts) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(m->verts); (void)hipFree(m->colors); (void)hipFree(m->rem);
-      m->verts = nullptr; m->colors = nullptr; m->rem = nullptr;
-    }
     const size_t cap = (size_t)nv + nv / 4 + 1024;
-    m->cap_v = 0;  // (a failure below must not leave the old capacity standing over freed / missing buffers)
-    if (hipMalloc((void**)&m->verts, cap * 12) != hipSuccess || hipMalloc((void**)&m->colors, cap * 12) != hipSuccess ||
-        hipMalloc((void**)&m->rem, cap * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(m->verts); (void)hipFree(m->colors); (void)hipFree(m->rem);
-      m->verts = nullptr; m->colors = nullptr; m->rem = nullptr;
+    const mc_array vertex[] = {{(void**)&m->verts, cap * 12}, {(void**)&m->colors, cap * 12}, {(void**)&m->rem, cap * 4}};
+    if (mc_realloc(&m->cap_v, (int)min(cap, (size_t)2147483647), vertex) != hipSuccess) {
       lt_set_error("lt_marching_cubes_dev: hipMalloc of the vertex arrays (%zu vertices) failed", cap);
       return LT_ERR_NO_MEMORY;
     }
-    m->cap_v = (int)min(cap, (size_t)2147483647);
   }
   if (nf > m->cap_f || !m->faces) {
-    if (m->faces) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(m->faces);
-      m->faces = nullptr;
-    }
     const size_t cap = (size_t)nf + nf / 4 + 1024;
-    m->cap_f = 0;
-    LT_HIP(hipMalloc((void**)&m->faces, cap * 12));
-    m->cap_f = (int)min(cap, (size_t)2147483647);
+    const mc_array face[] = {{(void**)&m->faces, cap * 12}};
+    LT_HIP(mc_realloc(&m->cap_f, (int)min(cap, (size_t)2147483647), face));
   }
   hipLaunchKernelGGL(k_mc_compact, dim3(sweep_wgs), dim3(256), 0, stream, bits, D, m->cnt, m->blk, seg_dev, m->cmap, m->rec,
                      (int)min(m->cap_rec, (size_t)2147483647), m->wave_na, n_blocks);
-#define LT_MC_EMIT_ARGS tsdf, color_vol, rem_vol, bits, D, m->cmap, m->rec, n_active, voxel_size, origin[0], origin[1], origin[2], \
-                        m->verts, m->faces, m->colors, m->rem, m->cap_v, m->cap_f, m->amb, xcd_map
   if (n_active > 0) {
-    static const int kk = []() { const char* e = getenv("LIDARHIP_MC_EMIT_K"); return e ? atoi(e) : 8; }();
     // The grid: persistent waves taking batches in turn (bi += gridDim), 36 per CU -- 1.8 x the resident capacity (20 waves
     // per CU, see LT_MC_VCAP; swept again with four-wave workgroups on the six-workgroup variant: 24 / 36 / 48 / 72 / 96 per
     // CU = 118 / 90 / 100 / 92 / 102 us).  On the default volume's street scene (31 500 batches; a batch lives 8.3 us on
@@ -1454,15 +1514,13 @@ static int mc_extract(const float* tsdf, const float* color_vol, const float* re
     const int max_waves = env_waves > 0 ? env_waves : (env_waves == 0 ? (1 << 24) : dflt_waves);
     // LIDARHIP_MC_EMIT_XCD=0: batches dealt to the waves round-robin over the whole list (rounds 3-4)
     static const int env_xcd = []() { const char* e = getenv("LIDARHIP_MC_EMIT_XCD"); return e ? atoi(e) : 64; }();
-    auto grid = [&](int k) { return dim3((unsigned)((min((n_active + k - 1) / k, max_waves) + LT_MC_EW - 1) / LT_MC_EW)); };
-    const int xcd_map = (env_xcd > 0 && (int)grid(vs == 4 ? 8 : kk >= 16 ? 16 : kk >= 8 ? 8 : kk >= 4 ? 4 : 2).x * LT_MC_EW >= 64) ? env_xcd : 0;
-    if (vs == 4) hipLaunchKernelGGL((k_mc_emit_batch<8, true>), grid(8), dim3(64 * LT_MC_EW), 0, stream, LT_MC_EMIT_ARGS);
-    else if (kk >= 16) hipLaunchKernelGGL((k_mc_emit_batch<16, false>), grid(16), dim3(64 * LT_MC_EW), 0, stream, LT_MC_EMIT_ARGS);
-    else if (kk >= 8) hipLaunchKernelGGL((k_mc_emit_batch<8, false>), grid(8), dim3(64 * LT_MC_EW), 0, stream, LT_MC_EMIT_ARGS);
-    else if (kk >= 4) hipLaunchKernelGGL((k_mc_emit_batch<4, false>), grid(4), dim3(64 * LT_MC_EW), 0, stream, LT_MC_EMIT_ARGS);
-    else hipLaunchKernelGGL((k_mc_emit_batch<2, false>), grid(2), dim3(64 * LT_MC_EW), 0, stream, LT_MC_EMIT_ARGS);
+    const int n_batches = (n_active + LT_MC_K - 1) / LT_MC_K;
+    const int n_wgs = (min(n_batches, max_waves) + LT_MC_EW - 1) / LT_MC_EW;
+    const int xcd_map = (env_xcd > 0 && n_wgs * LT_MC_EW >= 64) ? env_xcd : 0;
+    const mc_emit_args args = mc_emit_args_of(tsdf, color_vol, rem_vol, bits, D, m, n_active, voxel_size, origin, xcd_map);
+    hipLaunchKernelGGL(vs == 4 ? k_mc_emit_batch<true> : k_mc_emit_batch<false>, dim3((unsigned)n_wgs), dim3(64 * LT_MC_EW), 0,
+                       stream, args);
   }
-#undef LT_MC_EMIT_ARGS
   LT_HIP(hipGetLastError());
   m->n_verts = nv;
   m->n_faces = nf;

@@ -99,9 +99,9 @@ def test_more_ambiguous_cells_than_the_queue_holds_grow_the_buffers_and_start_ov
 
 @pytest.mark.parametrize("p_neg", [0.0005, 0.004, 0.02, 0.08, 0.3])
 def test_speckled_fields_cross_the_sparse_and_dense_emission_paths(oracle, p_neg):
-    """The emission kernel lists a batch of 8 active words with a lane per vertex / cell when the batch holds <= 128 of them
-    and with a pass per word otherwise (k_mc_emit_batch): fields that are +1 with isolated negative voxels at five
-    densities put batches on both sides of both thresholds, next to each other in one volume."""
+    """The emission kernel lists the vertices and the triangles of a batch of 8 active words in windows of LT_MC_VCAP /
+    LT_MC_TCAP = 256 and runs several passes over a batch that holds more (k_mc_emit_batch): fields that are +1 with
+    isolated negative voxels at five densities put batches of one pass and of several next to each other in one volume."""
     shape = (24, 20, 200)
     rng = np.random.default_rng(int(p_neg * 1e4))
     t = np.ones(shape, np.float32)
@@ -377,3 +377,133 @@ def test_bare_lt_fusion_scan_dev_symbol_edge_cases():
     assert mesh.n_faces == 0 and int((out["range"] != 0).sum()) == 0
     del none
     mesh.close(); sc.close(); vol.close(); rs.close()
+
+# ---- the AOS emission on dense data, and waves that take several batches ------------------------------------------------
+_DENSE_BOUNDS = {(33, 17, 129): [[0, 3.3], [0, 1.7], [0, 12.9]],   # three words per row, the last of one voxel
+                 (9, 8, 70): [[0, 0.9], [0, 0.8], [0, 7.0]]}      # a 6-voxel word next to a full one
+_DENSE = {}
+
+
+def _dense_fields(oracle, shape):
+    """White noise with 5 % exact zeros, labels 0 .. 259 (256 .. 259 wrap) and random remissions on `shape`, with the
+    oracle's mesh at voxel size 0.1 and origin 0 -- computed once per shape."""
+    if shape not in _DENSE:
+        rng = np.random.default_rng(7002 + sum(shape))
+        t = rng.normal(size=shape).astype(np.float32)
+        t[rng.random(shape) < 0.05] = 0.0
+        col = (rng.integers(0, 260, shape) * 65536 + rng.integers(0, 256, shape) * 256 + rng.integers(0, 256, shape))
+        col = col.astype(np.float32)
+        rem = rng.random(shape).astype(np.float32)
+        want = oracle.marching_cubes(t, col, rem, np.float32(0.1), np.zeros(3, np.float32))
+        _DENSE[shape] = (t, col, rem, want)
+    return _DENSE[shape]
+
+
+@pytest.mark.parametrize("shape", sorted(_DENSE_BOUNDS), ids=lambda s: "x".join(map(str, s)))
+def test_dense_volume_of_records_equals_oracle(oracle, shape):
+    """The variant of k_mc_emit_batch that every chain runs -- a TSDF volume's interleaved records (AOS) -- on dense
+    data: white noise gives ~1.5 vertices per voxel, so a batch of eight words holds well over LT_MC_VCAP = 256 vertices
+    and LT_MC_TCAP = 256 triangles and both window loops run several passes; ambiguous cells and centre vertices occur."""
+    import torch
+    from lidar_transfer_amd.fusion import TSDFVolume
+    vol = TSDFVolume(np.array(_DENSE_BOUNDS[shape], np.float64), 0.1, 3.0, -25.0)
+    t, w, c, r = vol.get_volume_tensors()
+    assert tuple(t.shape) == shape
+    tsdf, col, rem, want = _dense_fields(oracle, shape)
+    for view, a in ((t, tsdf), (c, col), (r, rem)):
+        view.copy_(torch.from_numpy(a))
+    vol.touch()
+    mesh = vol.extract_mesh()
+    got = [a.cpu().numpy() for a in mesh.tensors()]
+    # the oracle's mesh of the downloaded fields: they are, bit for bit, the fields the shared mesh was computed from
+    for view, a in zip(vol.get_volume_tensors(), (tsdf, None, col, rem)):
+        assert a is None or np.array_equal(view.cpu().numpy().view(np.int32), a.view(np.int32))
+    assert not vol._vol_origin.any()
+    assert mesh.n_verts > 8 * 256 and mesh.n_faces > 8 * 256
+    _assert_same_mesh(got, want)
+    vol.close()
+
+
+def _active_words(t):
+    """Words of 64 voxels along z that own a vertex (a sign change along the edge from one of their voxels towards +x, +y
+    or +z) or a triangle (a cell at one of their voxels whose eight corners are not all on one side): the sign of a voxel
+    is "not above 0" (lt_mc.hip, k_mc_signs / mc_build)."""
+    s = ~(t > 0)
+    nx, ny, nz = s.shape
+    own = np.zeros(s.shape, bool)
+    own[:-1] |= s[:-1] ^ s[1:]
+    own[:, :-1] |= s[:, :-1] ^ s[:, 1:]
+    own[:, :, :-1] |= s[:, :, :-1] ^ s[:, :, 1:]
+    c = [s[dx:nx - 1 + dx, dy:ny - 1 + dy, dz:nz - 1 + dz] for dx in (0, 1) for dy in (0, 1) for dz in (0, 1)]
+    own[:-1, :-1, :-1] |= np.logical_or.reduce(c) & ~np.logical_and.reduce(c)
+    own = np.pad(own, ((0, 0), (0, 0), (0, (-nz) % 64)))
+    return int(own.reshape(nx, ny, -1, 64).any(axis=3).sum())
+
+
+_BATCH_CHILD = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, {root!r})
+from lidar_transfer_amd.fusion import DeviceMesh, TSDFVolume
+g = np.load({npz!r})
+dev = torch.device("cuda", 0)
+out = {{}}
+m = DeviceMesh(0)
+m.extract(*[torch.from_numpy(g[k]).to(dev) for k in ("tsdf", "col", "rem")], np.float32(0.1), (0.0, 0.0, 0.0))
+for k, a in zip("vfcr", m.tensors()):
+    out["soa_" + k] = a.cpu().numpy()
+m.close()
+vol = TSDFVolume(g["bounds"], 0.1, 3.0, -25.0)
+t, w, c, r = vol.get_volume_tensors()
+assert tuple(t.shape) == g["tsdf"].shape
+for view, k in ((t, "tsdf"), (c, "col"), (r, "rem")):
+    view.copy_(torch.from_numpy(g[k]))
+vol.touch()
+for k, a in zip("vfcr", vol.extract_mesh().tensors()):
+    out["aos_" + k] = a.cpu().numpy()
+vol.close()
+np.savez({out!r}, **out)
+print("BATCHES_OK")
+"""
+
+
+def test_waves_that_take_several_batches_with_and_without_the_xcd_dealing(oracle, tmp_path):
+    """By default the emission has a wave per batch on volumes of test size and deals them round-robin (`xcd_map` needs 64
+    waves).  LIDARHIP_MC_EMIT_WAVES (read once per process: fresh children, one after the other) makes waves take several
+    batches.  Of the 33 x 17 x 3 = 1 683 words of the (33, 17, 129) white-noise volume 1 515 are active (the third word of a row
+    is one voxel and owns a vertex seven times in ten; counted here in numpy and asserted against the library's own count):
+    190 batches of 8 words = three chunks of 64, the last partial.
+      64 waves: 16 workgroups, xcd_map = 64, 8 waves per XCD.  Chunk c belongs to XCD c: the waves of XCDs 0 and 1 take 8
+        batches each, those of XCD 2 the 62 batches of the partial chunk and skip its last two turns (`continue`), those
+        of XCDs 3 .. 7 skip every turn of the first round; the second round is past the list (`break`).
+      72 waves: 18 workgroups, not a multiple of eight: the waves of workgroups 16 and 17 have no share and return.
+      8 waves, LIDARHIP_MC_EMIT_XCD=0: two workgroups, round-robin, 23 or 24 batches per wave.
+    Both field layouts in every child; every mesh equals the oracle's."""
+    import os
+    import re
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    shape = (33, 17, 129)
+    tsdf, col, rem, want = _dense_fields(oracle, shape)
+    np.savez(tmp_path / "fields.npz", tsdf=tsdf, col=col, rem=rem, bounds=np.array(_DENSE_BOUNDS[shape], np.float64))
+    n_active_want = _active_words(tsdf)
+    n_batches = (n_active_want + 7) // 8
+    assert 2 * 64 < n_batches < 3 * 64, n_batches     # three chunks of 64 batches, the last partial
+    assert "LIDARHIP_MC_EMIT_WAVES" not in os.environ and "LIDARHIP_MC_EMIT_XCD" not in os.environ
+    for name, env in (("w64", dict(LIDARHIP_MC_EMIT_WAVES="64")), ("w72", dict(LIDARHIP_MC_EMIT_WAVES="72")),
+                      ("w8", dict(LIDARHIP_MC_EMIT_WAVES="8", LIDARHIP_MC_EMIT_XCD="0"))):
+        out = str(tmp_path / (name + ".npz"))
+        code = _BATCH_CHILD.format(root=root, npz=str(tmp_path / "fields.npz"), out=out)
+        res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True,
+                             env=dict(os.environ, LIDARHIP_DEBUG_MC="1", **env), timeout=300)
+        assert res.returncode == 0 and "BATCHES_OK" in res.stdout, name + ": " + res.stdout + res.stderr
+        counts = re.findall(r"marching cubes: (\d+) active words, (\d+) vertices, (\d+) triangles", res.stderr)
+        assert len(counts) == 2, res.stderr
+        for n_active, nv, nf in counts:
+            assert int(n_active) == n_active_want
+            assert int(nv) == want[0].shape[0] and int(nf) == want[1].shape[0]
+        got = np.load(out)
+        for layout in ("soa", "aos"):
+            mesh = [got[layout + "_" + k] for k in "vfcr"]
+            assert mesh[0].shape[0] == want[0].shape[0] and mesh[1].shape[0] == want[1].shape[0], (name, layout)
+            _assert_same_mesh(mesh, want)
