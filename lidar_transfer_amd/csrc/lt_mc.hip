@@ -255,7 +255,7 @@ struct lt_mesh {
   float* verts; int* faces; int* colors; float* rem;
   int cap_v, cap_f, n_verts, n_faces;
   u64* bits; unsigned* cnt; int* cmap; size_t cap_words;
-  int* blk; size_t cap_blocks;          // 3 ints per workgroup of 256 words, then 4 totals
+  int* blk; size_t cap_blocks;          // 3 ints per block of 64 rows (mc_triple), then 3 per segment of 256 blocks, then 4 totals
   int* totals_host;                     // pinned: {active words, vertices, triangles, -}
   mc_rec* rec; size_t cap_rec;
   // cnt / cmap hold 0 / -1 for every word that is not an active word of the LAST extraction (k_mc_clear undoes those
@@ -374,8 +374,33 @@ __device__ __forceinline__ int mc_case(const mc_masks& M, int b) {
   return cs;
 }
 
-// block-wide sum / exclusive scan of three small counters packed into one 64-bit word (20 bits each)
+// ---- the packed triple ------------------------------------------------------------------------------------------------
+// (active words, vertices, triangles) of a row, a block of 64 rows or a prefix of either, summed / scanned across a wave as
+// ONE 64-bit word of 20 bits a field.  The largest value a field takes is a block's triangles: 64 rows x wz words x <= 768
+// triangles a word (64 cells of <= 12) < 2^20 for wz <= 21 -- mc_dims_of refuses nz > 21 x 64 = 1344 for this reason.  In
+// memory a block's triple is three ints, blk[3 b ..] (lt_mesh::blk).
+struct mc_triple { unsigned a, v, t; };
 __device__ __forceinline__ u64 pack3(unsigned a, unsigned v, unsigned t) { return (u64)a | ((u64)v << 20) | ((u64)t << 40); }
+__device__ __forceinline__ mc_triple unpack3(u64 p) {
+  return {(unsigned)(p & 0xFFFFF), (unsigned)((p >> 20) & 0xFFFFF), (unsigned)((p >> 40) & 0xFFFFF)};
+}
+__device__ __forceinline__ u64 wave_sum3(u64 p) {  // the wave's total, in every lane
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+  return p;
+}
+__device__ __forceinline__ mc_triple blk_load3(const int* __restrict__ blk, int b) {
+  return {(unsigned)blk[3 * b], (unsigned)blk[3 * b + 1], (unsigned)blk[3 * b + 2]};
+}
+__device__ __forceinline__ void blk_store3(int* __restrict__ blk, int b, const mc_triple& s) {
+  blk[3 * b] = (int)s.a; blk[3 * b + 1] = (int)s.v; blk[3 * b + 2] = (int)s.t;
+}
+// (k_mc_amb: a cell's late triangles / centre vertex / newly active word; fields that are 0 cost no atomic)
+__device__ __forceinline__ void blk_add3(int* __restrict__ blk, int b, const mc_triple& s) {
+  if (s.v) atomicAdd(&blk[3 * b + 1], (int)s.v);
+  if (s.t) atomicAdd(&blk[3 * b + 2], (int)s.t);
+  if (s.a) atomicAdd(&blk[3 * b], (int)s.a);
+}
 
 __device__ __forceinline__ u64 wave_incl_scan(u64 p) {
   const int lane = threadIdx.x & 63;
@@ -386,6 +411,19 @@ __device__ __forceinline__ u64 wave_incl_scan(u64 p) {
   }
   return p;
 }
+
+// What the pieces of k_mc_words share, by const&.  The kernel puts it together from its arguments: as ONE kernel argument by
+// value (tried for k_mc_words, k_mc_amb and k_mc_compact, no load changed kind) the three kernels together were about 1 us
+// slower than with separate arguments (profiles/mc_count_phases/README.md, series A to C), so they keep those.
+struct mc_sweep_args {
+  mc_dims D;
+  const u64* bits;
+  unsigned* cnt;   // per word: vertices | triangles << 16
+  int* blk;        // per block of 64 rows: its triple (blk_load3)
+  int* wave_na;    // per block: its active words (k_mc_words -> k_mc_compact)
+  int n_blocks;
+  mc_amb A;
+};
 
 // ---- k_mc_words -----------------------------------------------------------------------------------------------------
 // a word can only own a crossing edge or an active cell if its row (x, y) or one of the rows (x, y + 1), (x + 1, y),
@@ -415,6 +453,36 @@ __device__ __forceinline__ bool mc_rows_dirty(const unsigned* __restrict__ col_e
 #ifndef LT_MC_BLOCKS_PER_WAVE
 #define LT_MC_BLOCKS_PER_WAVE 8
 #endif
+// a word with more cells than this is counted by the wave (count_cells_wave) ...
+#ifndef LT_MC_HEAVY
+#define LT_MC_HEAVY 16  // (swept on the default volume: 2: 50 us, 4: 39, 6: 38, 10 .. 24: 32-33, 40: 35, never: 39)
+#endif
+// ... unless more lanes than this hold such a word (word_by_wave)
+#ifndef LT_MC_HEAVY_LANES
+#define LT_MC_HEAVY_LANES 8   // (swept: 4 .. 12: 31.5 us, 20 .. 32: 32.4, 64 = never walked: 37.5)
+#endif
+#define LT_MC_QW 96  // ambiguous cells a wave buffers in LDS per block of 64 rows (amb_buffer)
+
+// A wave's blocks, for k_mc_words and k_mc_compact alike: the kernels differ in what makes a block live.
+struct sweep_deal {
+  int n_waves, wave;  // waves of the launch, this one's number
+  u64 live;           // bit l: block l * n_waves + wave is still to be walked (the ballot of the kernel's predicate)
+};
+__device__ __forceinline__ sweep_deal sweep_deal_of() {
+  const int n_waves = gridDim.x * 4, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  return {n_waves, wave, 0ull};
+}
+__device__ __forceinline__ int sweep_block(const sweep_deal& d, int l) { return l * d.n_waves + d.wave; }
+// lane `lane` looks at a block of its own
+__device__ __forceinline__ bool sweep_mine(const sweep_deal& d, int lane, int n_blocks) {
+  return lane < LT_MC_BLOCKS_PER_WAVE && sweep_block(d, lane) < n_blocks;
+}
+__device__ __forceinline__ int sweep_next(sweep_deal& d) {  // the next live block (wave-uniform), taken off the mask
+  const int b = sweep_block(d, __ffsll((long long)d.live) - 1);
+  d.live &= d.live - 1;
+  return b;
+}
+
 __device__ __forceinline__ bool mc_block_live(const unsigned* __restrict__ chunk_epoch, unsigned epoch, const mc_dims& D,
                                               int b, int n_chunks) {
   if (!chunk_epoch) return true;
@@ -426,182 +494,241 @@ __device__ __forceinline__ bool mc_block_live(const unsigned* __restrict__ chunk
   return any;
 }
 
+// one block of 64 rows as a lane of its wave sees it: the lane's row and what the row has summed up so far
+struct mc_block {
+  int id, lane;    // the block (wave-uniform) and the lane: row = 64 id + lane
+  int row, rowc;   // rowc: the row, or the volume's last where the block reaches beyond it
+  int x, y;        // of rowc
+  bool rowlive;    // the row exists and it or a neighbour was written (a clean row writes nothing: its words hold 0 -- no
+                   // active word of the last extraction is left, k_mc_clear)
+  unsigned na, nv, nt;  // the row's active words, vertices, triangles
+};
+__device__ __forceinline__ mc_block mc_block_of(const mc_dims& D, int id, int lane, const unsigned* __restrict__ col_epoch,
+                                                unsigned epoch) {
+  mc_block B;
+  const int n_rows = D.nx * D.ny;
+  B.id = id;
+  B.lane = lane;
+  B.row = id * 64 + lane;
+  B.na = B.nv = B.nt = 0;
+  B.rowlive = B.row < n_rows && mc_rows_dirty(col_epoch, epoch, D, B.row);
+  B.rowc = min(B.row, n_rows - 1);
+  B.x = mc_x_of(D, B.rowc);
+  B.y = B.rowc - B.x * D.ny;
+  return B;
+}
+
+// ---- a row's sign words ----
+// Two loaders.  Up to four words a row (D.wz <= 4, the default volume): the sign words of the four rows (x + dx, y + dy),
+// ALL loaded before the first is used -- a word's masks need its row neighbours' words at k and k + 1, so a loop over k
+// loaded every word twice, in wz dependent rounds.  That takes 16 words in registers under constant indices (an unrolled
+// loop); longer rows load the eight words of word k when its turn comes (mc_load).
+struct mc_row_words { u64 w[4][5]; };
+__device__ __forceinline__ mc_row_words row_words_load(const mc_sweep_args& a, const mc_block& B) {
+  const mc_dims& D = a.D;
+  const bool hx = B.x + 1 < D.nx, hy = B.y + 1 < D.ny;
+  mc_row_words R;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int dx = q & 1, dy = q >> 1;
+    const bool have = B.rowlive && (dx == 0 || hx) && (dy == 0 || hy);
+    const size_t base = (size_t)(B.rowc + (have ? dx * D.ny + dy : 0)) * D.wz;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) R.w[q][k] = (have && k < D.wz) ? a.bits[base + k] : 0ull;
+    R.w[q][4] = 0ull;
+  }
+  return R;
+}
+// the masks of word k of the lane's row: from the words loaded ahead (R; k a constant then) or, without them, from memory
+__device__ __forceinline__ mc_masks row_masks(const mc_sweep_args& a, const mc_block& B, const mc_row_words* R, int k) {
+  if (R) {
+    u64 w8[8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { w8[q] = R->w[q][k]; w8[q | 4] = R->w[q][k + 1]; }
+    return mc_build(w8, a.D, B.x, B.y, k);  // (a row that is not live holds zeros: no edge, no cell)
+  }
+  mc_masks M = mc_load(a.bits, a.D, B.x, B.y, k);
+  if (!B.rowlive) { M.ex = M.ey = M.ez = M.ac = 0ull; }
+  return M;
+}
+
+// ---- the ambiguous cells' queue ----
+// the ambiguous cells a wave meets in one block of 64 rows, collected in LDS and appended to the queue with ONE global
+// atomic (a returning atomic per cell on the one counter -- 14 500 of them on a street scene -- doubled the kernel's time)
+// One per wave; n may exceed LT_MC_QW (amb_push).  An entry is the queue's uint2 as ONE word, x | y << 32, written with one
+// store: as a uint2 its halves are stored apart, and the compiler merges the second half's store with that of the queue's own
+// entry in amb_push -- one store through a FLAT pointer that is either LDS or global (seen in the assembly).
+struct amb_buffer { u64 e[LT_MC_QW]; int n; };
+__device__ __forceinline__ void amb_begin(amb_buffer& Q, int lane) {
+  if (lane == 0) Q.n = 0;
+  __builtin_amdgcn_wave_barrier();
+}
+// the cell at voxel (xx, yy, z) with case cs, met in block `blkid`: queued for k_mc_amb; counts 0 here
+__device__ __forceinline__ unsigned amb_push(amb_buffer& Q, const mc_sweep_args& a, int blkid, int xx, int yy, int z, unsigned cs) {
+  const mc_amb& A = a.A;
+  const uint2 e = make_uint2((unsigned)((xx * a.D.ny + yy) * a.D.nz + z), cs | ((unsigned)blkid << 8));
+  const int slot = atomicAdd(&Q.n, 1);  // (LDS)
+  if (slot < LT_MC_QW) Q.e[slot] = (u64)e.x | ((u64)e.y << 32);
+  else {  // (more than the buffer holds in one block of rows: straight to the queue)
+    const unsigned sh = (unsigned)blkid & (LT_MC_SHARDS - 1);
+    const unsigned pos = (unsigned)atomicAdd(A.counter + sh * LT_MC_CTR_STRIDE, 1);
+    if (pos < A.cap) A.queue[(size_t)sh * A.cap + pos] = e;
+  }
+  return 0u;
+}
+// the block's ambiguous cells -> the queue
+__device__ __forceinline__ void amb_flush(amb_buffer& Q, const mc_amb& A, int blkid, int lane) {
+  __builtin_amdgcn_wave_barrier();
+  const int nq = min(Q.n, LT_MC_QW);  // (wave-uniform)
+  if (nq > 0) {
+    unsigned base = 0;
+    const unsigned sh = (unsigned)blkid & (LT_MC_SHARDS - 1);
+    if (lane == 0) base = (unsigned)atomicAdd(A.counter + sh * LT_MC_CTR_STRIDE, nq);
+    base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+    for (int j = lane; j < nq; j += 64)
+      if (base + (unsigned)j < A.cap) A.queue[(size_t)sh * A.cap + base + j] = make_uint2((unsigned)Q.e[j], (unsigned)(Q.e[j] >> 32));
+  }
+}
+
+// ---- counting one word ----
+// triangles per case: the loops below look it up once per active cell, a chain of dependent loads that is three times
+// shorter through LDS.  0x80: an ambiguous case of Lewiner's (3, 4, 6, 7, 10, 12, 13) -- the cell's eight VALUES decide
+// (k_mc_amb; 1-2 % of a street scene's cells).  256 threads, one case each; the caller's barrier follows.
+__device__ __forceinline__ void case_counts_stage(unsigned char* s_nt) {
+  const unsigned fx = LT_LWC_FIXED[threadIdx.x];
+  s_nt[threadIdx.x] = fx == 0xFFFFFFFFu ? 0x80 : (unsigned char)LW_NT(fx);
+}
+
+// Triangles of a word = sum over its active cells of the case's count.  A lane walking its own cells is a chain of
+// ~60 instructions and an LDS look-up per cell, and a row through a wall along z has 60 active cells a word: its wave
+// waits for that one lane, and the launch for its slowest waves.  Words with more than LT_MC_HEAVY cells are therefore
+// counted by the WAVE, a lane per cell: the owner's eight corner masks are broadcast (v_readlane), every lane looks up
+// its cell, three ballots add the counts up (42 -> 32 us on the default volume, with the threshold swept and the lanes'
+// own loops on 32-bit half words).
+// ... unless MANY lanes hold such a word (a wall across the block's rows): the wave's turn costs ~90 instructions
+// per heavy word, the lanes' own loops ~25 per cell of the fullest lane -- 64 heavy words at once are cheaper walked
+__device__ __forceinline__ bool word_by_wave(const mc_masks& M) {  // (called by all 64 lanes)
+  bool heavy = __popcll(M.ac) > LT_MC_HEAVY;
+  if (__popcll(__ballot(heavy)) > LT_MC_HEAVY_LANES) heavy = false;
+  return heavy;
+}
+// the lane's own loop -> triangles of word k of its row (ambiguous cells: queued, 0)
+__device__ __forceinline__ unsigned count_cells_lane(const mc_sweep_args& a, const mc_block& B, amb_buffer& Q,
+                                                     const unsigned char* s_nt, const mc_masks& M, int k) {
+  unsigned t = 0;
+  // the word's halves one after the other: with 32-bit masks a cell is 8 x (v_bfe_u32, v_lshl_or_b32) + a 32-bit
+  // find-first / clear-lowest, a third of the instructions of the 64-bit shifts of mc_case
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    unsigned ac = (unsigned)(M.ac >> (32 * h));
+    if (ac == 0u) continue;
+    unsigned m[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      m[i] = (unsigned)(((i & 4) ? M.s[i & 1][(i >> 1) & 1] : M.m[i & 1][(i >> 1) & 1]) >> (32 * h));
+    for (; ac; ac &= ac - 1) {
+      const int b = __ffs((int)ac) - 1;
+      unsigned cs = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) cs |= ((m[i] >> b) & 1u) << i;
+      const unsigned n = s_nt[cs];
+      t += (n & 0x80u) ? amb_push(Q, a, B.id, B.x, B.y, k * 64 + 32 * h + b, cs) : n;
+    }
+  }
+  return t;
+}
+// the wave's turns: every lane whose word is `heavy` has it counted by all 64, a lane per cell, and receives the sum
+// (triangles | centre vertices << 16) in t; the other lanes keep theirs.  (Called by all 64 lanes.)
+__device__ __forceinline__ unsigned count_cells_wave(const mc_sweep_args& a, const mc_block& B, amb_buffer& Q,
+                                                     const unsigned char* s_nt, const mc_masks& M, int k, bool heavy, unsigned t) {
+  const int lane = B.lane;
+  for (u64 hm = __ballot(heavy); hm; hm &= hm - 1) {
+    const int r = __ffsll((long long)hm) - 1;  // (wave-uniform)
+    int cs = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const u64 m = (i & 4) ? M.s[i & 1][(i >> 1) & 1] : M.m[i & 1][(i >> 1) & 1];
+      const u64 mr = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)m, r) |
+                     ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(m >> 32), r) << 32);
+      cs |= (int)((mr >> lane) & 1ull) << i;
+    }
+    const u64 ac = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)M.ac, r) |
+                   ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(M.ac >> 32), r) << 32);
+    unsigned n = ((ac >> lane) & 1ull) ? s_nt[cs] : 0u;  // (<= 12, or the marker)
+    if (n & 0x80u)  // (the OWNER's x, y: broadcast like its masks)
+      n = amb_push(Q, a, B.id, __builtin_amdgcn_readlane(B.x, r), __builtin_amdgcn_readlane(B.y, r), k * 64 + lane, (unsigned)cs);
+    const unsigned tot = __popcll(__ballot(n & 1u)) + 2u * __popcll(__ballot(n & 2u)) + 4u * __popcll(__ballot(n & 4u)) +
+                         8u * __popcll(__ballot(n & 8u)) + ((unsigned)__popcll(__ballot(n >> 16)) << 16);
+    if (lane == r) t = tot;
+  }
+  return t;
+}
+// word k of this lane's row is done: its count (vertices | triangles << 16) stored, the row's three sums kept
+__device__ __forceinline__ void sweep_word(const mc_sweep_args& a, mc_block& B, amb_buffer& Q, const unsigned char* s_nt,
+                                           const mc_masks& M, int k) {  // (called by all 64 lanes)
+  const bool heavy = word_by_wave(M);
+  const unsigned own = heavy ? 0u : count_cells_lane(a, B, Q, s_nt, M, k);
+  const unsigned tc = count_cells_wave(a, B, Q, s_nt, M, k, heavy, own), t = tc & 0xFFFFu;
+  const unsigned v = __popcll(M.ex) + __popcll(M.ey) + __popcll(M.ez) + (tc >> 16);
+  if (B.rowlive) a.cnt[(size_t)B.row * a.D.wz + k] = v | (t << 16);
+  B.na += (v | t) ? 1u : 0u; B.nv += v; B.nt += t;
+}
+
+// ---- the block's totals ----
+// the wave sum of the rows' triples (20 bits each: the host checks wz, see pack3) and the four stores
+__device__ __forceinline__ void block_totals_store(const mc_sweep_args& a, const mc_block& B) {
+  const mc_triple s = unpack3(wave_sum3(pack3(B.na, B.nv, B.nt)));
+  if (B.lane == 0) {
+    blk_store3(a.blk, B.id, s);
+    a.wave_na[B.id] = (int)s.a;
+  }
+}
+__device__ __forceinline__ void block_totals_clean(const mc_sweep_args& a, int b) {  // (cnt already holds 0 for the words of a clean block)
+  blk_store3(a.blk, b, {0u, 0u, 0u});
+  a.wave_na[b] = 0;
+}
+
 __global__ __launch_bounds__(256) void k_mc_words(mc_amb A, const u64* __restrict__ bits, mc_dims D, unsigned* __restrict__ cnt,
                                                   int* __restrict__ blk, const unsigned* __restrict__ col_epoch,
                                                   unsigned epoch, const unsigned* __restrict__ chunk_epoch,
                                                   int* __restrict__ wave_na, int n_blocks) {
-  const int n_rows = D.nx * D.ny;
-  const int n_chunks = (n_rows + 63) / 64;
-  __shared__ unsigned char s_nt[256];  // triangles per case: the loops below look it up once per active cell, a chain of
-  {                                    // dependent loads that is three times shorter through LDS.  0x80: an ambiguous case of
-    const unsigned fx = LT_LWC_FIXED[threadIdx.x];  // Lewiner's (3, 4, 6, 7, 10, 12, 13) -- the cell's eight VALUES decide
-    s_nt[threadIdx.x] = fx == 0xFFFFFFFFu ? 0x80 : (unsigned char)LW_NT(fx);  // (k_mc_amb; 1-2 % of a street scene's cells)
-  }
-  // the ambiguous cells a wave meets in one block of 64 rows, collected in LDS and appended to the queue with ONE global
-  // atomic (a returning atomic per cell on the one counter -- 14 500 of them on a street scene -- doubled the kernel's time)
-#define LT_MC_QW 96
-  __shared__ uint2 s_q[4][LT_MC_QW];
-  __shared__ int s_qn[4];
-  const int wv = threadIdx.x >> 6;
+  const mc_sweep_args a = {D, bits, cnt, blk, wave_na, n_blocks, A};  // (in mc_sweep_args' order)
+  const int n_chunks = (D.nx * D.ny + 63) / 64;
+  __shared__ unsigned char s_nt[256];
+  __shared__ amb_buffer s_q[4];
+  case_counts_stage(s_nt);
+  amb_buffer& Q = s_q[threadIdx.x >> 6];
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int n_waves = gridDim.x * 4, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-  LT_MC_STAMP_AT(1, wave, 0, wall_clock64());
-  u64 live;
+  sweep_deal dl = sweep_deal_of();
+  LT_MC_STAMP_AT(1, dl.wave, 0, wall_clock64());
   {
-    const int b = lane * n_waves + wave;
-    const bool mine = lane < LT_MC_BLOCKS_PER_WAVE && b < n_blocks;
+    const int b = sweep_block(dl, lane);
+    const bool mine = sweep_mine(dl, lane, a.n_blocks);
     const bool act = mine && mc_block_live(chunk_epoch, epoch, D, b, n_chunks);
-    if (mine && !act) {  // (cnt already holds 0 for the words of a clean block)
-      blk[3 * b] = 0; blk[3 * b + 1] = 0; blk[3 * b + 2] = 0;
-      wave_na[b] = 0;
-    }
-    live = __ballot(act);
+    if (mine && !act) block_totals_clean(a, b);
+    dl.live = __ballot(act);
   }
-  LT_MC_STAMP_AT(1, wave, 1, wall_clock64());
-  LT_MC_STAMP_AT(1, wave, 3, (unsigned long long)__popcll(live));
-  while (live) {
-    const int blkid = (__ffsll((long long)live) - 1) * n_waves + wave;  // (wave-uniform)
-    live &= live - 1;
-    const int row = blkid * 64 + lane;
-    unsigned na = 0, nv = 0, nt = 0;
-    if (lane == 0) s_qn[wv] = 0;
-    __builtin_amdgcn_wave_barrier();
-    // (a clean row writes nothing: its words hold 0 -- no active word of the last extraction is left, k_mc_clear)
-    const bool rowlive = row < n_rows && mc_rows_dirty(col_epoch, epoch, D, row);
-    const int rowc = min(row, n_rows - 1);
-    const int x = mc_x_of(D, rowc), y = rowc - x * D.ny;
-    // Triangles of a word = sum over its active cells of the case's count.  A lane walking its own cells is a chain of
-    // ~60 instructions and an LDS look-up per cell, and a row through a wall along z has 60 active cells a word: its wave
-    // waits for that one lane, and the launch for its slowest waves.  Words with more than LT_MC_HEAVY cells are therefore
-    // counted by the WAVE, a lane per cell: the owner's eight corner masks are broadcast (v_readlane), every lane looks up
-    // its cell, three ballots add the counts up (42 -> 32 us on the default volume, with the threshold swept and the lanes'
-    // own loops on 32-bit half words).
-#ifndef LT_MC_HEAVY_LANES
-#define LT_MC_HEAVY_LANES 8   // (swept: 4 .. 12: 31.5 us, 20 .. 32: 32.4, 64 = never walked: 37.5)
-#endif
-#ifndef LT_MC_HEAVY
-#define LT_MC_HEAVY 16  // (swept on the default volume: 2: 50 us, 4: 39, 6: 38, 10 .. 24: 32-33, 40: 35, never: 39)
-#endif
-    // -> triangles | centre vertices << 16 of the word k of this lane's row
-    auto count_tris = [&](const mc_masks& M, int k) -> unsigned {  // (called by all 64 lanes)
-      unsigned t = 0;
-      auto ambiguous = [&](int xx, int yy, int b, unsigned cs) -> unsigned {  // queued for k_mc_amb; counts 0 here
-        const uint2 e = make_uint2((unsigned)((xx * D.ny + yy) * D.nz + k * 64 + b), cs | ((unsigned)blkid << 8));
-        const int slot = atomicAdd(&s_qn[wv], 1);  // (LDS)
-        if (slot < LT_MC_QW) s_q[wv][slot] = e;
-        else {  // (more than the buffer holds in one block of rows: straight to the queue)
-          const unsigned sh = (unsigned)blkid & (LT_MC_SHARDS - 1);
-          const unsigned pos = (unsigned)atomicAdd(A.counter + sh * LT_MC_CTR_STRIDE, 1);
-          if (pos < A.cap) A.queue[(size_t)sh * A.cap + pos] = e;
-        }
-        return 0u;
-      };
-      // ... unless MANY lanes hold such a word (a wall across the block's rows): the wave's turn costs ~90 instructions
-      // per heavy word, the lanes' own loops ~25 per cell of the fullest lane -- 64 heavy words at once are cheaper walked
-      bool heavy = __popcll(M.ac) > LT_MC_HEAVY;
-      if (__popcll(__ballot(heavy)) > LT_MC_HEAVY_LANES) heavy = false;
-      if (!heavy) {
-        // the word's halves one after the other: with 32-bit masks a cell is 8 x (v_bfe_u32, v_lshl_or_b32) + a 32-bit
-        // find-first / clear-lowest, a third of the instructions of the 64-bit shifts of mc_case
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          unsigned a = (unsigned)(M.ac >> (32 * h));
-          if (a == 0u) continue;
-          unsigned m[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-            m[i] = (unsigned)(((i & 4) ? M.s[i & 1][(i >> 1) & 1] : M.m[i & 1][(i >> 1) & 1]) >> (32 * h));
-          for (; a; a &= a - 1) {
-            const int b = __ffs((int)a) - 1;
-            unsigned cs = 0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) cs |= ((m[i] >> b) & 1u) << i;
-            const unsigned n = s_nt[cs];
-            t += (n & 0x80u) ? ambiguous(x, y, 32 * h + b, cs) : n;
-          }
-        }
-      }
-      for (u64 hm = __ballot(heavy); hm; hm &= hm - 1) {
-        const int r = __ffsll((long long)hm) - 1;  // (wave-uniform)
-        int cs = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const u64 m = (i & 4) ? M.s[i & 1][(i >> 1) & 1] : M.m[i & 1][(i >> 1) & 1];
-          const u64 mr = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)m, r) |
-                         ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(m >> 32), r) << 32);
-          cs |= (int)((mr >> lane) & 1ull) << i;
-        }
-        const u64 ac = (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)M.ac, r) |
-                       ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(M.ac >> 32), r) << 32);
-        unsigned n = ((ac >> lane) & 1ull) ? s_nt[cs] : 0u;  // (<= 12, or the marker)
-        if (n & 0x80u)  // (the OWNER's x, y: broadcast like its masks)
-          n = ambiguous(__builtin_amdgcn_readlane(x, r), __builtin_amdgcn_readlane(y, r), lane, (unsigned)cs);
-        const unsigned tot = __popcll(__ballot(n & 1u)) + 2u * __popcll(__ballot(n & 2u)) + 4u * __popcll(__ballot(n & 4u)) +
-                             8u * __popcll(__ballot(n & 8u)) + ((unsigned)__popcll(__ballot(n >> 16)) << 16);
-        if (lane == r) t = tot;
-      }
-      return t;
-    };
-    // word k of this lane's row is done: its count (vertices | triangles << 16) stored, the row's three sums kept
-    auto word_done = [&](const mc_masks& M, int k) {  // (called by all 64 lanes: count_tris)
-      const unsigned tc = count_tris(M, k), t = tc & 0xFFFFu;
-      const unsigned v = __popcll(M.ex) + __popcll(M.ey) + __popcll(M.ez) + (tc >> 16);
-      if (rowlive) cnt[(size_t)row * D.wz + k] = v | (t << 16);
-      na += (v | t) ? 1u : 0u; nv += v; nt += t;
-    };
-    if (D.wz <= 4) {
-      // the sign words of the four rows (x + dx, y + dy), ALL loaded before the first is used -- a word's masks need
-      // its row neighbours' words at k and k + 1, so a loop over k loaded every word twice, in wz dependent rounds
-      const bool hx = x + 1 < D.nx, hy = y + 1 < D.ny;
-      u64 w[4][5];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int dx = q & 1, dy = q >> 1;
-        const bool have = rowlive && (dx == 0 || hx) && (dy == 0 || hy);
-        const size_t base = (size_t)(rowc + (have ? dx * D.ny + dy : 0)) * D.wz;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[q][k] = (have && k < D.wz) ? bits[base + k] : 0ull;
-        w[q][4] = 0ull;
-      }
+  LT_MC_STAMP_AT(1, dl.wave, 1, wall_clock64());
+  LT_MC_STAMP_AT(1, dl.wave, 3, (unsigned long long)__popcll(dl.live));
+  while (dl.live) {
+    const int id = sweep_next(dl);
+    amb_begin(Q, lane);
+    mc_block B = mc_block_of(D, id, lane, col_epoch, epoch);
+    if (D.wz <= 4) {  // (wave-uniform; the two loaders: row_words_load)
+      const mc_row_words R = row_words_load(a, B);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (k >= D.wz) break;  // (wave-uniform)
-        u64 w8[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { w8[q] = w[q][k]; w8[q | 4] = w[q][k + 1]; }
-        word_done(mc_build(w8, D, x, y, k), k);  // (a row that is not live holds zeros: no edge, no cell)
+        sweep_word(a, B, Q, s_nt, row_masks(a, B, &R, k), k);
       }
     } else {
-      for (int k = 0; k < D.wz; ++k) {
-        mc_masks M = mc_load(bits, D, x, y, k);
-        if (!rowlive) { M.ex = M.ey = M.ez = M.ac = 0ull; }
-        word_done(M, k);
-      }
+      for (int k = 0; k < D.wz; ++k) sweep_word(a, B, Q, s_nt, row_masks(a, B, nullptr, k), k);
     }
-    {  // the block's ambiguous cells -> the queue
-      __builtin_amdgcn_wave_barrier();
-      const int nq = min(s_qn[wv], LT_MC_QW);  // (wave-uniform)
-      if (nq > 0) {
-        unsigned base = 0;
-        const unsigned sh = (unsigned)blkid & (LT_MC_SHARDS - 1);
-        if (lane == 0) base = (unsigned)atomicAdd(A.counter + sh * LT_MC_CTR_STRIDE, nq);
-        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-        for (int j = lane; j < nq; j += 64)
-          if (base + (unsigned)j < A.cap) A.queue[(size_t)sh * A.cap + base + j] = s_q[wv][j];
-      }
-    }
-    u64 p = pack3(na, nv, nt);  // (20 bits each: 64 rows x wz words x <= 768 triangles -- the host checks wz)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
-    if (lane == 0) {
-      blk[3 * blkid] = (int)(p & 0xFFFFF);
-      blk[3 * blkid + 1] = (int)((p >> 20) & 0xFFFFF);
-      blk[3 * blkid + 2] = (int)((p >> 40) & 0xFFFFF);
-      wave_na[blkid] = (int)(p & 0xFFFFF);
-    }
+    amb_flush(Q, a.A, id, lane);
+    block_totals_store(a, B);
   }
-  LT_MC_STAMP_AT(1, wave, 2, wall_clock64());
+  LT_MC_STAMP_AT(1, dl.wave, 2, wall_clock64());
 }
 
 // ---- k_mc_amb: the queued ambiguous cells, one lane each ------------------------------------------------------------
@@ -647,9 +774,8 @@ __global__ __launch_bounds__(256) void k_mc_amb(const float* __restrict__ tsdf, 
     if (nt) {
       const unsigned row = i / (unsigned)D.nz, z = i - row * (unsigned)D.nz;
       const unsigned old = atomicAdd(&cnt[(size_t)row * D.wz + (z >> 6)], c | (nt << 16));
-      if (c) atomicAdd(&blk[3 * b + 1], (int)c);
-      atomicAdd(&blk[3 * b + 2], (int)nt);
-      if (old == 0u) { atomicAdd(&blk[3 * b], 1); atomicAdd(&wave_na[b], 1); }  // the word becomes an active word
+      blk_add3(blk, b, {0u, c, nt});
+      if (old == 0u) { blk_add3(blk, b, {1u, 0u, 0u}); atomicAdd(&wave_na[b], 1); }  // the word becomes an active word
     }
   }
 }
@@ -680,10 +806,10 @@ __global__ __launch_bounds__(256) void k_mc_clear(const mc_rec* __restrict__ rec
 // default volume took 143 us: one CU's L2 bandwidth.)
 __global__ __launch_bounds__(256) void k_mc_scan1(int* __restrict__ blk, int n_blocks, int* __restrict__ seg) {
   const int b = blockIdx.x * 256 + threadIdx.x;
-  unsigned a = 0, v = 0, t = 0;
-  if (b < n_blocks) { a = (unsigned)blk[3 * b]; v = (unsigned)blk[3 * b + 1]; t = (unsigned)blk[3 * b + 2]; }
+  mc_triple mine = {0u, 0u, 0u};
+  if (b < n_blocks) mine = blk_load3(blk, b);
   // (the 20-bit packing of pack3 would overflow here -- 256 x 81 920 triangles: three 64-bit scans)
-  u64 p[3] = {a, v, t}, inc[3];
+  u64 p[3] = {mine.a, mine.v, mine.t}, inc[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) inc[k] = wave_incl_scan(p[k]);
   __shared__ u64 ws[3][4];
@@ -695,9 +821,13 @@ __global__ __launch_bounds__(256) void k_mc_scan1(int* __restrict__ blk, int n_b
     for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off[k] += ws[k][w];
     tot[k] = (ws[k][0] + ws[k][1]) + (ws[k][2] + ws[k][3]);
   }
-  if (b < n_blocks)
-    for (int k = 0; k < 3; ++k) blk[3 * b + k] = (int)min(off[k] + inc[k] - p[k], (u64)2147483647);
-  if (threadIdx.x == 0)
+  // (saturated: the host refuses a mesh of 2^31 - 1 vertices / faces)
+  if (b < n_blocks) {
+    unsigned ex[3];
+    for (int k = 0; k < 3; ++k) ex[k] = (unsigned)min(off[k] + inc[k] - p[k], (u64)2147483647);
+    blk_store3(blk, b, {ex[0], ex[1], ex[2]});
+  }
+  if (threadIdx.x == 0)  // (the segment's triple, laid out like a block's: k_mc_compact reads it with blk_load3)
     for (int k = 0; k < 3; ++k) seg[3 * blockIdx.x + k] = (int)min(tot[k], (u64)2147483647);
 }
 
@@ -733,76 +863,84 @@ __global__ __launch_bounds__(1024) void k_mc_scan2(int* __restrict__ seg, int n_
 }
 
 // ---- k_mc_compact ----------------------------------------------------------------------------------------------------
+// the row's counts: up to four words ALL loaded before the first is used and kept for row_records_store (a rolled loop
+// waited for every load before it issued the next, twice: eight dependent round trips per block of rows)
+struct mc_row_counts {
+  unsigned c4[4];  // the words' counts when there are `few` (D.wz <= 4)
+  mc_triple sum;   // the row's triple
+};
+__device__ __forceinline__ mc_row_counts row_counts_load(const unsigned* __restrict__ cnt, const mc_dims& D, int row, bool few) {
+  unsigned na = 0, nv = 0, nt = 0, c4[4] = {0u, 0u, 0u, 0u};
+  if (few) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c4[k] = k < D.wz ? cnt[(size_t)row * D.wz + k] : 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { na += c4[k] ? 1u : 0u; nv += c4[k] & 0xFFFFu; nt += c4[k] >> 16; }
+  } else {
+    for (int k = 0; k < D.wz; ++k) {
+      const unsigned c = cnt[(size_t)row * D.wz + k];
+      na += c ? 1u : 0u; nv += c & 0xFFFFu; nt += c >> 16;
+    }
+  }
+  return {{c4[0], c4[1], c4[2], c4[3]}, {na, nv, nt}};
+}
+// the records of the row's active words and the cmap entries of all its words; at: (compact index, vertex base, triangle
+// base) of the row's first active word
+__device__ __forceinline__ void row_records_store(const u64* __restrict__ bits, const mc_dims& D, const unsigned* __restrict__ cnt,
+                                                  int row, bool few, const mc_row_counts R, const mc_triple& at,
+                                                  int* __restrict__ cmap, mc_rec* __restrict__ rec, int cap_rec) {
+  int ci = (int)at.a, vb = (int)at.v, tb = (int)at.t;
+  const int x = mc_x_of(D, row), y = row - x * D.ny;
+  for (int k = 0; k < D.wz; ++k) {
+    const int w = row * D.wz + k;
+    const unsigned c = few ? (k == 0 ? R.c4[0] : k == 1 ? R.c4[1] : k == 2 ? R.c4[2] : R.c4[3]) : cnt[w];
+    int mine_ci = -1;
+    if (c) {
+      if (ci < cap_rec) {
+        const mc_masks M = mc_load(bits, D, x, y, k);
+        mc_rec r;
+        r.w = w;
+        r.vbase = vb;
+        r.tbase = tb;
+        r.ex = M.ex; r.ey = M.ey; r.ez = M.ez;
+        // triangles of the word (k_mc_emit_batch: the extent of a batch) | its centre vertices << 16
+        r.pad = (int)((c >> 16) | (((c & 0xFFFFu) - (unsigned)(__popcll(M.ex) + __popcll(M.ey) + __popcll(M.ez))) << 16));
+        rec[ci] = r;
+        mine_ci = ci;
+      }
+      ++ci; vb += (int)(c & 0xFFFFu); tb += (int)(c >> 16);
+    }
+    cmap[w] = mine_ci;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_mc_compact(const u64* __restrict__ bits, mc_dims D,
                                                     const unsigned* __restrict__ cnt, const int* __restrict__ blk,
                                                     const int* __restrict__ seg, int* __restrict__ cmap,
                                                     mc_rec* __restrict__ rec, int cap_rec,
                                                     const int* __restrict__ wave_na, int n_blocks) {
-  // thread = row, scan block = a wave's turn (as in k_mc_words, and dealt the same way); compact order = word order
+  // thread = row, scan block = a wave's turn (as in k_mc_words, and dealt the same way: sweep_deal); compact order = word order
   const int n_rows = D.nx * D.ny;
   const int lane = threadIdx.x & 63;
-  const int n_waves = gridDim.x * 4, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-  LT_MC_STAMP_AT(2, wave, 0, wall_clock64());
-  u64 live;
-  {  // no active word in a block's 64 rows (most): nothing to rank, and their cmap entries are -1 already (lt_mesh)
-    const int b = lane * n_waves + wave;
-    live = __ballot(lane < LT_MC_BLOCKS_PER_WAVE && b < n_blocks && wave_na[min(b, n_blocks - 1)] != 0);
-  }
-  LT_MC_STAMP_AT(2, wave, 1, wall_clock64());
-  LT_MC_STAMP_AT(2, wave, 3, (unsigned long long)__popcll(live));
-  while (live) {
-    const int blkid = (__ffsll((long long)live) - 1) * n_waves + wave;  // (wave-uniform)
-    live &= live - 1;
-    const int row = blkid * 64 + lane;
-    unsigned na = 0, nv = 0, nt = 0;
-    // the row's counts: up to four words ALL loaded before the first is used and kept for the loop below (a rolled loop
-    // waited for every load before it issued the next, twice: eight dependent round trips per block of rows)
+  sweep_deal dl = sweep_deal_of();
+  LT_MC_STAMP_AT(2, dl.wave, 0, wall_clock64());
+  // no active word in a block's 64 rows (most): nothing to rank, and their cmap entries are -1 already (lt_mesh)
+  dl.live = __ballot(sweep_mine(dl, lane, n_blocks) && wave_na[min(sweep_block(dl, lane), n_blocks - 1)] != 0);
+  LT_MC_STAMP_AT(2, dl.wave, 1, wall_clock64());
+  LT_MC_STAMP_AT(2, dl.wave, 3, (unsigned long long)__popcll(dl.live));
+  while (dl.live) {
+    const int id = sweep_next(dl), row = id * 64 + lane;
     const bool few = D.wz <= 4;  // (wave-uniform)
-    unsigned c4[4] = {0u, 0u, 0u, 0u};
-    if (row < n_rows) {
-      if (few) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c4[k] = k < D.wz ? cnt[(size_t)row * D.wz + k] : 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { na += c4[k] ? 1u : 0u; nv += c4[k] & 0xFFFFu; nt += c4[k] >> 16; }
-      } else {
-        for (int k = 0; k < D.wz; ++k) {
-          const unsigned c = cnt[(size_t)row * D.wz + k];
-          na += c ? 1u : 0u; nv += c & 0xFFFFu; nt += c >> 16;
-        }
-      }
-    }
-    const u64 mine = pack3(na, nv, nt);
-    const u64 ex = wave_incl_scan(mine) - mine;
+    mc_row_counts R = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u}};
+    if (row < n_rows) R = row_counts_load(cnt, D, row, few);
+    const u64 p = pack3(R.sum.a, R.sum.v, R.sum.t);
+    const mc_triple in_blk = unpack3(wave_incl_scan(p) - p);  // the rows before this one in the block
     if (row >= n_rows) continue;
-    const int* sg = seg + 3 * (blkid >> 8);
-    int ci = sg[0] + blk[3 * blkid] + (int)(ex & 0xFFFFF);
-    int vb = sg[1] + blk[3 * blkid + 1] + (int)((ex >> 20) & 0xFFFFF);
-    int tb = sg[2] + blk[3 * blkid + 2] + (int)((ex >> 40) & 0xFFFFF);
-    const int x = mc_x_of(D, row), y = row - x * D.ny;
-    for (int k = 0; k < D.wz; ++k) {
-      const int w = row * D.wz + k;
-      const unsigned c = few ? (k == 0 ? c4[0] : k == 1 ? c4[1] : k == 2 ? c4[2] : c4[3]) : cnt[w];
-      int mine_ci = -1;
-      if (c) {
-        if (ci < cap_rec) {
-          const mc_masks M = mc_load(bits, D, x, y, k);
-          mc_rec r;
-          r.w = w;
-          r.vbase = vb;
-          r.tbase = tb;
-          r.ex = M.ex; r.ey = M.ey; r.ez = M.ez;
-          // triangles of the word (k_mc_emit_batch: the extent of a batch) | its centre vertices << 16
-          r.pad = (int)((c >> 16) | (((c & 0xFFFFu) - (unsigned)(__popcll(M.ex) + __popcll(M.ey) + __popcll(M.ez))) << 16));
-          rec[ci] = r;
-          mine_ci = ci;
-        }
-        ++ci; vb += (int)(c & 0xFFFFu); tb += (int)(c >> 16);
-      }
-      cmap[w] = mine_ci;
-    }
+    const mc_triple sg = blk_load3(seg, id >> 8), in_seg = blk_load3(blk, id);
+    row_records_store(bits, D, cnt, row, few, R, {sg.a + in_seg.a + in_blk.a, sg.v + in_seg.v + in_blk.v, sg.t + in_seg.t + in_blk.t},
+                      cmap, rec, cap_rec);
   }
-  LT_MC_STAMP_AT(2, wave, 2, wall_clock64());
+  LT_MC_STAMP_AT(2, dl.wave, 2, wall_clock64());
 }
 
 // ---- emission ----------------------------------------------------------------------------------------------------------
@@ -1361,26 +1499,33 @@ static mc_emit_args mc_emit_args_of(const float* tsdf, const float* color_vol, c
           m->verts, m->faces, m->colors, m->rem, m->cap_v, m->cap_f, m->amb, xcd_map};  // (in mc_emit_args' order)
 }
 
-static int mc_extract(const float* tsdf, const float* color_vol, const float* rem_vol, int vs, int nx, int ny, int nz,
-                      float voxel_size, const float* origin, lt_mesh* m, void* stream_, float* ms,
-                      const unsigned* col_epoch, unsigned epoch, const u64* ext_bits, const unsigned* chunk_epoch) {
-  if (!tsdf || !color_vol || !rem_vol || !origin || !m || nx <= 0 || ny <= 0 || nz <= 0) {
-    lt_set_error("lt_marching_cubes_dev: invalid argument");
-    return LT_ERR_INVALID_ARG;
-  }
+// ---- mc_extract: one extraction, step by step --------------------------------------------------------------------------
+// what the steps share
+struct mc_job {
+  const float* tsdf; const float* color_vol; const float* rem_vol;
+  float voxel_size; const float* origin;
+  lt_mesh* m; hipStream_t stream; bool timed;
+  // the volume's own stamps and sign bits (lt_tsdf_extract_mesh_dev), or NULL
+  const unsigned* col_epoch; unsigned epoch; const u64* ext_bits; const unsigned* chunk_epoch;
+  mc_dims D;
+  int n_blocks;   // one block of the scan per wave of 64 rows
+  int n_seg;      // segments of 256 blocks (k_mc_scan1 / 2)
+  int sweep_wgs;  // workgroups of k_mc_words and k_mc_compact (a wave takes LT_MC_BLOCKS_PER_WAVE blocks, see k_mc_words)
+};
+// sign bits: the volume's own (kept current by integrate / reset, lt_tsdf.hip) or one pass over the float field
+static const u64* mc_bits_of(const mc_job& J) { return J.ext_bits ? J.ext_bits : J.m->bits; }
+static int* mc_seg_of(const mc_job& J) { return J.m->blk + 3 * (size_t)J.n_blocks; }  // (lt_mesh::blk)
+
+// the volume's sizes checked, mc_dims and the sizes of the launches; *empty: no cell, nothing to extract
+static int mc_dims_of(int vs, int nx, int ny, int nz, mc_job* J, bool* empty) {
   if ((double)nx * ny * nz >= 2147483647.0) {
     lt_set_error("lt_marching_cubes_dev: more than 2^31 - 1 voxels");
     return LT_ERR_TOO_LARGE;
   }
-  hipStream_t stream = (hipStream_t)stream_;
-  LT_HIP(hipSetDevice(m->device));
-  if (nx < 2 || ny < 2 || nz < 2) {  // no cell (scikit-image: "Input array must be at least 2x2x2"): the empty mesh
-    m->n_verts = 0;
-    m->n_faces = 0;
-    if (ms) ms[0] = ms[1] = 0.f;
-    return LT_OK;
-  }
-  mc_dims D;
+  LT_HIP(hipSetDevice(J->m->device));
+  *empty = nx < 2 || ny < 2 || nz < 2;  // no cell (scikit-image: "Input array must be at least 2x2x2"): the empty mesh
+  if (*empty) return LT_OK;
+  mc_dims& D = J->D;
   D.nx = nx; D.ny = ny; D.nz = nz; D.vs = vs;
   D.wz = (nz + 63) / 64;
   mc_magic((unsigned)D.wz, &D.wz_m, &D.wz_s);
@@ -1391,87 +1536,109 @@ static int mc_extract(const float* tsdf, const float* color_vol, const float* re
     return LT_ERR_TOO_LARGE;
   }
   D.n_words = (int)n_words;
-  const int n_rows = nx * ny;
-  const int n_blocks = ((n_rows + 255) / 256) * 4;  // one block of the scan per wave of 64 rows
-  if (D.wz > 21) {  // (the packed per-block totals hold 20 bits a field: 64 rows x wz words x 768 triangles)
+  if (D.wz > 21) {  // (the packed per-block totals hold 20 bits a field, see pack3)
     lt_set_error("lt_marching_cubes_dev: nz = %d exceeds 1344", nz);
     return LT_ERR_TOO_LARGE;
   }
+  J->n_blocks = ((nx * ny + 255) / 256) * 4;
+  J->n_seg = (J->n_blocks + 255) / 256;
+  J->sweep_wgs = lt_deal_count(J->n_blocks, LT_MC_BLOCKS_PER_WAVE, ny, 4) / 4;
+  return LT_OK;
+}
+
+static int mc_reserve_words(const mc_job& J) {  // bits / cnt / cmap
+  lt_mesh* m = J.m;
+  const size_t n_words = (size_t)J.D.n_words;
   if (n_words > m->cap_words || !m->bits) {
     const mc_array words[] = {{(void**)&m->bits, (n_words + 1) * sizeof(u64)}, {(void**)&m->cnt, n_words * sizeof(unsigned)},
                               {(void**)&m->cmap, n_words * sizeof(int)}};
     LT_HIP(mc_realloc(&m->cap_words, n_words, words));
-    m->state_dirty = 1;  // (fresh buffers: swept below)
+    m->state_dirty = 1;  // (fresh buffers: swept by mc_restore_state)
   }
-  const int n_seg = (n_blocks + 255) / 256;
-  int* seg_dev = nullptr;
-  // sign bits: the volume's own (kept current by integrate / reset, lt_tsdf.hip) or one pass over the float field
-  const u64* bits = ext_bits ? ext_bits : m->bits;
-  // (a wave takes LT_MC_BLOCKS_PER_WAVE blocks, see k_mc_words)
-  const int sweep_wgs = lt_deal_count(n_blocks, LT_MC_BLOCKS_PER_WAVE, ny, 4) / 4;
-  // The counting part, up to the one synchronisation.  It runs a second time when it queued more ambiguous cells than the
-  // side buffers held: the second run's buffers hold them.
-  for (;;) {
-    // the ambiguous cells' queue and tiling table: m->amb_cap cells per shard, the counters allocated once
-    if (!m->amb.queue || !m->amb.counter || m->amb.cap != m->amb_cap) {
-      const size_t cap = m->amb_cap ? m->amb_cap : (size_t)1 << 10;   // per shard
-      size_t tcap = 1;
-      while (tcap < 4 * LT_MC_SHARDS * cap) tcap <<= 1;
-      const size_t n_ctr = LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS;
-      const mc_array amb[] = {{(void**)&m->amb.queue, LT_MC_SHARDS * cap * sizeof(uint2)}, {(void**)&m->amb.table, tcap * sizeof(uint2)}};
-      if (mc_realloc(&m->amb.cap, (unsigned)cap, amb) != hipSuccess ||
-          (!m->amb.counter && hipMalloc((void**)&m->amb.counter, n_ctr * sizeof(int)) != hipSuccess)) {
-        (void)hipGetLastError();
-        lt_set_error("lt_marching_cubes_dev: hipMalloc of the ambiguous cells' buffers (%zu cells) failed", cap);
-        return LT_ERR_NO_MEMORY;
-      }
-      m->amb_cap = cap;
-      m->amb.tmask = (unsigned)(tcap - 1);
-      LT_HIP(hipMemsetAsync(m->amb.counter, 0, n_ctr * sizeof(int), stream));
-      LT_HIP(hipMemsetAsync(m->amb.table, 0, tcap * sizeof(uint2), stream));
-      m->n_amb_prev = 0;
-    }
-    if (m->state_dirty) {  // new buffers, or an extraction that did not finish: cnt = 0, cmap = -1 everywhere, once
-      LT_HIP(hipMemsetAsync(m->cnt, 0, m->cap_words * sizeof(unsigned), stream));
-      LT_HIP(hipMemsetAsync(m->cmap, 0xFF, m->cap_words * sizeof(int), stream));
-      LT_HIP(hipMemsetAsync(m->amb.counter, 0, (LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS) * sizeof(int), stream));
-      LT_HIP(hipMemsetAsync(m->amb.table, 0, ((size_t)m->amb.tmask + 1) * sizeof(uint2), stream));
-      m->n_prev = 0;
-      m->n_amb_prev = 0;
-    } else if (m->n_prev > 0) {
-      hipLaunchKernelGGL(k_mc_clear, dim3((max(m->n_prev, LT_MC_SHARDS * m->n_amb_prev) + 255) / 256), dim3(256), 0, stream, m->rec,
-                         m->n_prev, m->cnt, m->cmap, m->amb, m->n_amb_prev);
-    }
-    m->state_dirty = 1;  // until this extraction has finished
-    m->n_prev = 0;
-    m->n_amb_prev = 0;
-    LT_CHECK(mc_grow(&m->wave_na, &m->cap_wave_na, (size_t)n_blocks));
-    if (n_seg > 1024) {
-      lt_set_error("lt_marching_cubes_dev: volume too large (%d words)", D.n_words);
-      return LT_ERR_TOO_LARGE;
-    }
-    LT_CHECK(mc_grow(&m->blk, &m->cap_blocks, (size_t)3 * n_blocks + 3 * (size_t)n_seg + 4));
-    seg_dev = m->blk + 3 * (size_t)n_blocks;
-    int* totals_dev = seg_dev + 3 * (size_t)n_seg;
-    if (ms) LT_HIP(hipEventRecord(m->ev[0], stream));
-    if (!ext_bits)
-      hipLaunchKernelGGL(k_mc_signs, dim3((unsigned)min((size_t)16384, ((size_t)nx * ny + 255) / 256)), dim3(256), 0, stream,
-                         tsdf, D, m->bits, col_epoch, epoch);
-    if (ms) LT_HIP(hipEventRecord(m->ev[1], stream));
-    hipLaunchKernelGGL(k_mc_words, dim3(sweep_wgs), dim3(256), 0, stream, m->amb, bits, D, m->cnt, m->blk, ext_bits ? col_epoch : nullptr,
-                       epoch, ext_bits ? chunk_epoch : nullptr, m->wave_na, n_blocks);
-    // Lewiner's ambiguous cells (1-2 % of a street scene's): tests on their eight values, counts added, tilings filed
-    hipLaunchKernelGGL(k_mc_amb, dim3(2 * LT_MC_SHARDS), dim3(256), 0, stream, tsdf, D, m->amb, m->cnt, m->blk, m->wave_na);
-    hipLaunchKernelGGL(k_mc_scan1, dim3(n_seg), dim3(256), 0, stream, m->blk, n_blocks, seg_dev);
-    hipLaunchKernelGGL(k_mc_scan2, dim3(1), dim3(1024), 0, stream, seg_dev, n_seg, totals_dev, m->amb.counter, (int)m->amb.cap);
-    LT_HIP(hipMemcpyAsync(m->totals_host, totals_dev, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    LT_HIP(hipStreamSynchronize(stream));  // the one synchronisation: the sizes of the mesh
-    const size_t need = (size_t)(unsigned)m->totals_host[3];
-    if (need <= m->amb_cap) break;
-    // more ambiguous cells in a shard than its segment holds (white noise: a third of all cells): the counts above are incomplete --
-    // larger buffers, and the counting once more from the start (cnt / cmap are swept: state_dirty is still set)
-    m->amb_cap = need + need / 4 + 1024;
+  return LT_OK;
+}
+
+// the ambiguous cells' queue and tiling table: m->amb_cap cells per shard, the counters allocated once
+static int mc_reserve_amb(const mc_job& J) {
+  lt_mesh* m = J.m;
+  hipStream_t stream = J.stream;
+  if (m->amb.queue && m->amb.counter && m->amb.cap == m->amb_cap) return LT_OK;
+  const size_t cap = m->amb_cap ? m->amb_cap : (size_t)1 << 10;   // per shard
+  size_t tcap = 1;
+  while (tcap < 4 * LT_MC_SHARDS * cap) tcap <<= 1;
+  const size_t n_ctr = LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS;
+  const mc_array amb[] = {{(void**)&m->amb.queue, LT_MC_SHARDS * cap * sizeof(uint2)}, {(void**)&m->amb.table, tcap * sizeof(uint2)}};
+  if (mc_realloc(&m->amb.cap, (unsigned)cap, amb) != hipSuccess ||
+      (!m->amb.counter && hipMalloc((void**)&m->amb.counter, n_ctr * sizeof(int)) != hipSuccess)) {
+    (void)hipGetLastError();
+    lt_set_error("lt_marching_cubes_dev: hipMalloc of the ambiguous cells' buffers (%zu cells) failed", cap);
+    return LT_ERR_NO_MEMORY;
   }
+  m->amb_cap = cap;
+  m->amb.tmask = (unsigned)(tcap - 1);
+  LT_HIP(hipMemsetAsync(m->amb.counter, 0, n_ctr * sizeof(int), stream));
+  LT_HIP(hipMemsetAsync(m->amb.table, 0, tcap * sizeof(uint2), stream));
+  m->n_amb_prev = 0;
+  return LT_OK;
+}
+
+// cnt = 0, cmap = -1, the tiling table empty: by undoing the last extraction's entries (k_mc_clear) or, with new buffers or
+// after an extraction that did not finish, by sweeping everything once.  state_dirty stays set until mc_finish.
+static int mc_restore_state(const mc_job& J) {
+  lt_mesh* m = J.m;
+  hipStream_t stream = J.stream;
+  if (m->state_dirty) {
+    LT_HIP(hipMemsetAsync(m->cnt, 0, m->cap_words * sizeof(unsigned), stream));
+    LT_HIP(hipMemsetAsync(m->cmap, 0xFF, m->cap_words * sizeof(int), stream));
+    LT_HIP(hipMemsetAsync(m->amb.counter, 0, (LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS) * sizeof(int), stream));
+    LT_HIP(hipMemsetAsync(m->amb.table, 0, ((size_t)m->amb.tmask + 1) * sizeof(uint2), stream));
+  } else if (m->n_prev > 0) {
+    hipLaunchKernelGGL(k_mc_clear, dim3((max(m->n_prev, LT_MC_SHARDS * m->n_amb_prev) + 255) / 256), dim3(256), 0, stream, m->rec,
+                       m->n_prev, m->cnt, m->cmap, m->amb, m->n_amb_prev);
+  }
+  m->state_dirty = 1;  // until this extraction has finished
+  m->n_prev = 0;
+  m->n_amb_prev = 0;
+  return LT_OK;
+}
+
+static int mc_reserve_blocks(const mc_job& J) {  // wave_na and blk (the blocks' triples, the segment sums, four totals)
+  lt_mesh* m = J.m;
+  LT_CHECK(mc_grow(&m->wave_na, &m->cap_wave_na, (size_t)J.n_blocks));
+  if (J.n_seg > 1024) {
+    lt_set_error("lt_marching_cubes_dev: volume too large (%d words)", J.D.n_words);
+    return LT_ERR_TOO_LARGE;
+  }
+  return mc_grow(&m->blk, &m->cap_blocks, (size_t)3 * J.n_blocks + 3 * (size_t)J.n_seg + 4);
+}
+
+// The counting part, up to the one synchronisation: m->totals_host holds {active words, vertices, triangles, the fullest
+// shard's ambiguous cells}.  mc_extract runs it a second time when it queued more ambiguous cells than the side buffers held.
+static int mc_count(const mc_job& J) {
+  lt_mesh* m = J.m;
+  hipStream_t stream = J.stream;
+  const mc_dims& D = J.D;
+  int* seg_dev = mc_seg_of(J);
+  int* totals_dev = seg_dev + 3 * (size_t)J.n_seg;
+  if (J.timed) LT_HIP(hipEventRecord(m->ev[0], stream));
+  if (!J.ext_bits)
+    hipLaunchKernelGGL(k_mc_signs, dim3((unsigned)min((size_t)16384, ((size_t)D.nx * D.ny + 255) / 256)), dim3(256), 0, stream,
+                       J.tsdf, D, m->bits, J.col_epoch, J.epoch);
+  if (J.timed) LT_HIP(hipEventRecord(m->ev[1], stream));
+  hipLaunchKernelGGL(k_mc_words, dim3(J.sweep_wgs), dim3(256), 0, stream, m->amb, mc_bits_of(J), D, m->cnt, m->blk,
+                     J.ext_bits ? J.col_epoch : nullptr, J.epoch, J.ext_bits ? J.chunk_epoch : nullptr, m->wave_na, J.n_blocks);
+  // Lewiner's ambiguous cells (1-2 % of a street scene's): tests on their eight values, counts added, tilings filed
+  hipLaunchKernelGGL(k_mc_amb, dim3(2 * LT_MC_SHARDS), dim3(256), 0, stream, J.tsdf, D, m->amb, m->cnt, m->blk, m->wave_na);
+  hipLaunchKernelGGL(k_mc_scan1, dim3(J.n_seg), dim3(256), 0, stream, m->blk, J.n_blocks, seg_dev);
+  hipLaunchKernelGGL(k_mc_scan2, dim3(1), dim3(1024), 0, stream, seg_dev, J.n_seg, totals_dev, m->amb.counter, (int)m->amb.cap);
+  LT_HIP(hipMemcpyAsync(m->totals_host, totals_dev, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+  LT_HIP(hipStreamSynchronize(stream));  // the one synchronisation: the sizes of the mesh
+  return LT_OK;
+}
+
+// the sizes of the mesh checked, its arrays and the records of the active words reserved
+static int mc_reserve_mesh(const mc_job& J) {
+  lt_mesh* m = J.m;
   const int n_active = m->totals_host[0], nv = m->totals_host[1], nf = m->totals_host[2];
   static const bool dbg_mc = getenv("LIDARHIP_DEBUG_MC") != nullptr;
   // (tests/test_mc_gpu.py reads this line: keep its wording)
@@ -1498,8 +1665,16 @@ static int mc_extract(const float* tsdf, const float* color_vol, const float* re
     const mc_array face[] = {{(void**)&m->faces, cap * 12}};
     LT_HIP(mc_realloc(&m->cap_f, (int)min(cap, (size_t)2147483647), face));
   }
-  hipLaunchKernelGGL(k_mc_compact, dim3(sweep_wgs), dim3(256), 0, stream, bits, D, m->cnt, m->blk, seg_dev, m->cmap, m->rec,
-                     (int)min(m->cap_rec, (size_t)2147483647), m->wave_na, n_blocks);
+  return LT_OK;
+}
+
+// k_mc_compact and the emission
+static int mc_emit(const mc_job& J) {
+  lt_mesh* m = J.m;
+  hipStream_t stream = J.stream;
+  const int n_active = m->totals_host[0];
+  hipLaunchKernelGGL(k_mc_compact, dim3(J.sweep_wgs), dim3(256), 0, stream, mc_bits_of(J), J.D, m->cnt, m->blk, mc_seg_of(J), m->cmap, m->rec,
+                     (int)min(m->cap_rec, (size_t)2147483647), m->wave_na, J.n_blocks);
   if (n_active > 0) {
     // The grid: persistent waves taking batches in turn (bi += gridDim), 36 per CU -- 1.8 x the resident capacity (20 waves
     // per CU, see LT_MC_VCAP; swept again with four-wave workgroups on the six-workgroup variant: 24 / 36 / 48 / 72 / 96 per
@@ -1517,14 +1692,22 @@ static int mc_extract(const float* tsdf, const float* color_vol, const float* re
     const int n_batches = (n_active + LT_MC_K - 1) / LT_MC_K;
     const int n_wgs = (min(n_batches, max_waves) + LT_MC_EW - 1) / LT_MC_EW;
     const int xcd_map = (env_xcd > 0 && n_wgs * LT_MC_EW >= 64) ? env_xcd : 0;
-    const mc_emit_args args = mc_emit_args_of(tsdf, color_vol, rem_vol, bits, D, m, n_active, voxel_size, origin, xcd_map);
-    hipLaunchKernelGGL(vs == 4 ? k_mc_emit_batch<true> : k_mc_emit_batch<false>, dim3((unsigned)n_wgs), dim3(64 * LT_MC_EW), 0,
+    const mc_emit_args args = mc_emit_args_of(J.tsdf, J.color_vol, J.rem_vol, mc_bits_of(J), J.D, m, n_active, J.voxel_size, J.origin,
+                                              xcd_map);
+    hipLaunchKernelGGL(J.D.vs == 4 ? k_mc_emit_batch<true> : k_mc_emit_batch<false>, dim3((unsigned)n_wgs), dim3(64 * LT_MC_EW), 0,
                        stream, args);
   }
   LT_HIP(hipGetLastError());
-  m->n_verts = nv;
-  m->n_faces = nf;
-  m->n_prev = n_active;  // (the records k_mc_clear will undo before the next extraction)
+  return LT_OK;
+}
+
+// the extraction has finished: what the next one's mc_restore_state undoes, and the times when asked for
+static int mc_finish(const mc_job& J, float* ms) {
+  lt_mesh* m = J.m;
+  hipStream_t stream = J.stream;
+  m->n_verts = m->totals_host[1];
+  m->n_faces = m->totals_host[2];
+  m->n_prev = m->totals_host[0];  // (the records k_mc_clear will undo before the next extraction)
   m->n_amb_prev = m->totals_host[3];  // (the fullest shard's count: k_mc_clear's extent per shard)
   m->state_dirty = 0;
   if (ms) {
@@ -1536,6 +1719,40 @@ static int mc_extract(const float* tsdf, const float* color_vol, const float* re
     ms[1] = m->ms_rest;
   }
   return LT_OK;
+}
+
+static int mc_extract(const float* tsdf, const float* color_vol, const float* rem_vol, int vs, int nx, int ny, int nz,
+                      float voxel_size, const float* origin, lt_mesh* m, void* stream_, float* ms,
+                      const unsigned* col_epoch, unsigned epoch, const u64* ext_bits, const unsigned* chunk_epoch) {
+  if (!tsdf || !color_vol || !rem_vol || !origin || !m || nx <= 0 || ny <= 0 || nz <= 0) {
+    lt_set_error("lt_marching_cubes_dev: invalid argument");
+    return LT_ERR_INVALID_ARG;
+  }
+  mc_job J = {tsdf, color_vol, rem_vol, voxel_size, origin, m, (hipStream_t)stream_, ms != nullptr,
+              col_epoch, epoch, ext_bits, chunk_epoch};  // (D and the sizes: mc_dims_of)
+  bool empty = false;
+  LT_CHECK(mc_dims_of(vs, nx, ny, nz, &J, &empty));
+  if (empty) {
+    m->n_verts = 0;
+    m->n_faces = 0;
+    if (ms) ms[0] = ms[1] = 0.f;
+    return LT_OK;
+  }
+  LT_CHECK(mc_reserve_words(J));
+  for (;;) {
+    LT_CHECK(mc_reserve_amb(J));
+    LT_CHECK(mc_restore_state(J));
+    LT_CHECK(mc_reserve_blocks(J));
+    LT_CHECK(mc_count(J));
+    const size_t need = (size_t)(unsigned)m->totals_host[3];
+    if (need <= m->amb_cap) break;
+    // more ambiguous cells in a shard than its segment holds (white noise: a third of all cells): the counts above are incomplete --
+    // larger buffers, and the counting once more from the start (cnt / cmap are swept: state_dirty is still set)
+    m->amb_cap = need + need / 4 + 1024;
+  }
+  LT_CHECK(mc_reserve_mesh(J));
+  LT_CHECK(mc_emit(J));
+  return mc_finish(J, ms);
 }
 
 // ---- lt_mesh_renumber_dev: the vertices numbered as scikit-image numbers them ----------------------------------------
