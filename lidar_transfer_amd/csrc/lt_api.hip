@@ -257,6 +257,42 @@ extern "C" int lt_debug_wave_times(lt_scene* s, unsigned long long* out, int n_w
   return LT_OK;
 }
 
+// debug helper (not part of the documented ABI): the hand-over of the last plain (neither counting nor step-image)
+// quad-traversal launch -- how many rays k_trace4 parked for k_trace4_tail, and the largest number of stack entries
+// one of them saved (tail_meta[].z: its stack plus the reference it was about to visit).  Host code only: the counter
+// of a launch keeps its value until the tail kernel of the NEXT launch re-arms it (tests/test_lbvh_paths_gpu.py).
+extern "C" int lt_debug_trace_tail(lt_scene* s, int* n_parked, int* max_saved_sp) {
+  if (!s || !n_parked || !max_saved_sp) return LT_ERR_INVALID_ARG;
+  *n_parked = 0;
+  *max_saved_sp = 0;
+  if (!s->tail_count) return LT_OK;  // no launch yet
+  LT_HIP(hipSetDevice(s->device));
+  LT_HIP(hipDeviceSynchronize());
+  int n = 0;  // lt_trace_launch flipped tail_parity after it chose the counter of that launch
+  LT_HIP(hipMemcpy(&n, s->tail_count + ((s->tail_parity & 1) ^ 1), sizeof(int), hipMemcpyDeviceToHost));
+  if (n < 0 || n > s->cap_rays) {
+    lt_set_error("lt_debug_trace_tail: hand-over counter %d outside [0, %d]", n, s->cap_rays);
+    return LT_ERR_INVALID_ARG;
+  }
+  *n_parked = n;
+  if (n > 0) {
+    float4* meta = (float4*)malloc((size_t)n * sizeof(float4));
+    if (!meta) return LT_ERR_NO_MEMORY;
+    const hipError_t e = hipMemcpy(meta, s->tail_meta, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
+    int m = 0;
+    if (e == hipSuccess)
+      for (int i = 0; i < n; ++i) {
+        int z;
+        memcpy(&z, &meta[i].z, sizeof(z));
+        if (z > m) m = z;
+      }
+    free(meta);
+    LT_HIP(e);
+    *max_saved_sp = m;
+  }
+  return LT_OK;
+}
+
 // debug helper (not part of the documented ABI): compare lt_rcp_ieee with the IEEE division for every one of the
 // 2^32 float bit patterns; returns the number of patterns where the bits differ in *mismatches, and how many
 // patterns took the 5-instruction path in *fast

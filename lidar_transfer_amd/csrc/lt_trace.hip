@@ -7,7 +7,8 @@
 // contiguous azimuth sector.  Traversal is "while-while": lanes descend internal nodes until every
 // lane of the wave holds a leaf, then the leaves are intersected.  The per-ray stack of deferred
 // children lives in LDS ([depth][lane] layout: bank = lane, conflict-free); entries beyond
-// LT_STACK_LDS spill to HBM (never observed on real scenes, kept for adversarial inputs).
+// LT_STACK_LDS spill to HBM (never observed on real scenes, kept for adversarial inputs: tests/test_lbvh_paths_gpu.py
+// drives the spill, the hand-over and the tail of both kernels on the scenes of tests/lbvh_cases.py).
 //
 // Float arithmetic of the triangle test, the normalisation and the write-back is the reference's,
 // operation by operation; the file is compiled with -ffp-contract=off and IEEE division / sqrt.

@@ -161,11 +161,12 @@ class Scene:
         return st.asdict() if stats else None
 
     def trace(self, rays, origin, H, out=None, stream=None, write_misses=True, count=False, stats=False,
-              exact_normalize=False, label_image=False):
+              exact_normalize=False, label_image=False, _extra_flags=0):
         """Cast ``rays [R,3] f32`` (device) from ``origin`` (3 floats, host); returns dict of device tensors.
 
         ``out`` may carry preallocated ``endpoints [R,3] f32, endcolors [R,3] i32, range [R] f32,
-        endrem [R] f32, tri [R] i32`` tensors to reuse.
+        endrem [R] f32, tri [R] i32`` tensors to reuse.  (``_extra_flags``: internal trace flags of lt_internal.h,
+        for the tests and tools that read the kernels' debug outputs.)
         """
         torch = self._torch
         rays = self._t(rays, torch.float32, "rays")
@@ -175,7 +176,7 @@ class Scene:
         org = (C.c_float * 3)(*[float(v) for v in origin])
         flags = ((_lib.LT_TRACE_WRITE_MISSES if write_misses else 0) | (_lib.LT_TRACE_COUNT if count else 0)
                  | _norm_flag(exact_normalize)
-                 | (_lib.LT_TRACE_LABEL_IMAGE if label_image else 0))
+                 | (_lib.LT_TRACE_LABEL_IMAGE if label_image else 0) | int(_extra_flags))
         st = _lib.Stats()
 
         def p(k):

@@ -5,12 +5,16 @@ HIP kernels reproduce the reference's float32 operation order (no FMA), we hold 
 that against our oracle: every output bit-identical to the brute-force closest hit.
 """
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from lidar_transfer_amd.laserscan import create_rays
 from lidar_transfer_amd.synth import synth_scene
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from lbvh_cases import adversarial_soup as _adversarial_soup, cluster_stairs, identical  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -389,28 +393,6 @@ def test_scatter_equals_lbvh_equals_bruteforce_on_adversarial_soup(oracle):
             _assert_bits(a[k], ref[k], f"scatter {k} origin={origin}")
             _assert_bits(b[k], ref[k], f"lbvh {k} origin={origin}")
         assert a["stats"]["n_hits"] == b["stats"]["n_hits"] == int((ref["tri"] >= 0).sum()) > 100
-
-
-def _adversarial_soup(rng, n):
-    cen = rng.normal(size=(n, 3)) * rng.choice([0.05, 0.5, 5.0, 40.0], size=(n, 1))
-    size = rng.choice([0.01, 0.1, 1.0, 20.0], size=(n, 1, 1))
-    tri = cen[:, None, :] + rng.normal(size=(n, 3, 3)) * size
-    k = n // 15
-    tri[:k, :, 1] = 0.0                          # edge-on: in the plane y = 0 through the sensor
-    tri[k:2 * k, :, 2] = tri[k:2 * k, :1, 2]     # horizontal triangles (many contain the vertical axis)
-    tri[2 * k:3 * k, 1, :2] = tri[2 * k:3 * k, 0, :2]   # vertical walls: two vertices above each other
-    tri[3 * k:4 * k, :, 0] = -np.abs(tri[3 * k:4 * k, :, 0])  # behind the sensor: straddle azimuth +-pi
-    tri[3 * k:4 * k, 0, 1] = -np.abs(tri[3 * k:4 * k, 0, 1]) - 1e-3
-    tri[3 * k:4 * k, 1, 1] = np.abs(tri[3 * k:4 * k, 1, 1]) + 1e-3
-    # beyond the reference's initial t = 999999999.f (BVH.cpp:20): must stay misses
-    nf = min(8, n - 4 * k)
-    far = rng.normal(size=(nf, 1, 3)); far /= np.linalg.norm(far, axis=2, keepdims=True)
-    tri[4 * k:4 * k + nf] = far * 3e9 + rng.normal(size=(nf, 3, 3)) * 1e9
-    v = np.ascontiguousarray(tri.reshape(-1, 3).astype(np.float32))
-    f = np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
-    c = rng.integers(0, 256, (3 * n, 3)).astype(np.int32)
-    r = rng.uniform(0, 1, 3 * n).astype(np.float32)
-    return v, f, c, r
 
 
 @pytest.mark.parametrize("H,W,fov_up,fov_down,seed", [(64, 2048, 3.0, -25.0, 1), (16, 301, 15.0, -15.0, 2),
@@ -911,12 +893,8 @@ def test_lbvh_on_degenerate_morton_trees(oracle):
     of identical triangles (one Morton key: the tree is decided by the index tie-break alone and every upper node is
     wide), and a staircase of clusters at x = 2^-k, 600 copies each (a chain of wide nodes, one per key bit)."""
     rng = np.random.default_rng(77)
-    one = np.array([[4.0, -1.0, -1.0], [4.0, 1.0, -1.0], [4.0, 0.0, 1.5]])
-    same = np.repeat(one[None], 5000, axis=0)
-    stairs = []
-    for k in range(14):
-        base = one * [1.0, 0.2, 0.2] + [30.0 * 2.0 ** -k, 0.0, 0.0]
-        stairs.append(np.repeat(base[None], 600, axis=0) + rng.normal(size=(600, 1, 3)) * 1e-4)
+    same = identical(5000)
+    stairs = cluster_stairs(rng, levels=14, copies=600)   # (the generators live in tests/lbvh_cases.py)
     for tri in (same, np.concatenate(stairs), np.concatenate([same] + stairs)):
         n = len(tri)
         v = np.ascontiguousarray(tri.reshape(-1, 3).astype(np.float32))
