@@ -104,9 +104,9 @@ def _ref(name, n_rays, H):
     return _oracle(lc.scene(name)[0], lc.scene_rays(name, n_rays), lc.scene(name)[1], H)
 
 
-def _assert_images(got, ref, what):
+def _assert_images(got, ref, what, keys=KEYS):
     n = ref["tri"].shape[0]
-    for k in KEYS:
+    for k in keys:
         a, b = got[k][:n], ref[k]
         assert a.shape == b.shape, f"{what} {k}"
         bad = np.nonzero(a.view(np.int32).reshape(-1) != b.view(np.int32).reshape(-1))[0]
@@ -168,8 +168,58 @@ def run_case(name, H, W, extra=0):
     return rec
 
 
+WRITEBACK_CASE = ("stairs", 5, 8, 3)   # 16 hits, 24 misses, 3 trailing rays; two ragged tiles of either kernel
+
+
+def run_writeback_variants(name, H, W, extra):
+    """What the write-back does besides the five full images, in THIS process (its kernel): the label image, hits only,
+    two of the five images.  -> record of what ran"""
+    import torch
+    t0 = time.time()
+    mesh, origin = lc.scene(name)
+    n_rays, n = H * W + extra, H * W
+    ref = _ref(name, n_rays, H)
+    hit = ref["tri"] >= 0
+    assert 0 < int(hit.sum()) < n, "the case needs hits and misses"
+    what = f"{name} {H}x{W}+{extra}{' binary' if BINARY else ''}"
+    sc = _built(mesh)
+    try:
+        rays_t = torch.from_numpy(np.ascontiguousarray(lc.scene_rays(name, n_rays))).to(sc.device)
+
+        def cast(out, **kw):
+            for t in out.values():
+                t.fill_(SENTINEL)
+            sc.trace(rays_t, origin, H, out=out, **kw)
+            torch.cuda.synchronize()
+            return {k: t.cpu().numpy() for k, t in out.items()}
+
+        # label_image: endcolors is [R], channel 2 of the colours
+        got = cast(sc.alloc_outputs(n_rays, label_image=True), label_image=True)
+        assert got["endcolors"].shape == (n_rays,)
+        _assert_images(got, dict(ref, endcolors=ref["endcolors"][:, 2]), what + " label_image")
+        # write_misses=False: nothing is written where nothing was hit
+        got = cast(sc.alloc_outputs(n_rays), write_misses=False)
+        for k in KEYS:
+            assert np.array_equal(got[k][:n][hit].view(np.int32), ref[k][hit].view(np.int32)), f"{what} hits only {k}"
+            assert np.all(got[k][:n][~hit] == SENTINEL), f"{what} hits only {k}: a missed cell was written"
+            assert np.all(got[k][n:] == SENTINEL), f"{what} hits only {k}: rays beyond W * H were written"
+        # two images wanted, null pointers for the other three
+        full = sc.alloc_outputs(n_rays)
+        got = cast({k: full[k] for k in ("range", "tri")})
+        _assert_images(got, ref, what + " range and tri only", keys=("range", "tri"))
+    finally:
+        sc.close()
+    return dict(case="writeback " + name, H=H, W=W, extra=extra, binary=BINARY, hits=int(hit.sum()), n_used=n,
+                seconds=round(time.time() - t0, 2))
+
+
+def _run(case):
+    return run_writeback_variants(*case[1:]) if case[0] == "writeback" else run_case(*case)
+
+
 def _children(env, cases):
-    """run_case for every case in a child process with `env` set -> records"""
+    """run_case (a case that begins with "writeback": run_writeback_variants) for every case in a child process with
+    `env` set -> records"""
     e = dict(os.environ)
     for k in ("LIDARHIP_STEP_CAP", "LIDARHIP_TRACE"):
         e.pop(k, None)
@@ -378,5 +428,34 @@ def test_binary_twin_spills_in_subprocess():
         assert rec["binary"] and rec["stack_overflows"] > 0 and rec["parked"] == 0 and rec["hits"] >= 100
 
 
+# k_trace shares its tile mapping and its write-back with the quad kernels: every image shape, ragged against its 4 x 16 tile
+BINARY_EDGE_CASES = [(name, H, W, extra) for name in ("soup", "stairs") for H, W, extra in lc.IMAGE_SHAPES]
+
+
+@functools.lru_cache(maxsize=None)
+def _binary_edge_child():
+    """ONE LIDARHIP_TRACE=binary child for the two tests that follow: the edge shapes, then the write-back variants"""
+    return _children({"LIDARHIP_TRACE": "binary"}, BINARY_EDGE_CASES + [("writeback",) + WRITEBACK_CASE])
+
+
+def test_binary_twin_at_the_edge_shapes_in_subprocess():
+    """LIDARHIP_TRACE=binary on soup and stairs at every entry of lc.IMAGE_SHAPES: all five images of the count=True and
+    of the plain trace equal the oracle, the trailing rays of 5 x 8 + 3 stay untouched (run_case)."""
+    recs = _binary_edge_child()[:len(BINARY_EDGE_CASES)]
+    assert [(r["H"], r["W"], r["extra"]) for r in recs] == 2 * [tuple(s) for s in lc.IMAGE_SHAPES]
+    assert all(r["binary"] and r["parked"] == 0 and r["n_used"] == r["H"] * r["W"] for r in recs)
+    assert any(r["hits"] > 0 for r in recs) and any(r["hits"] < r["n_used"] for r in recs)
+
+
+def test_write_back_variants_of_the_quad_kernels_and_of_the_binary_twin():
+    """run_writeback_variants on WRITEBACK_CASE here (k_trace4, and k_trace4_tail for the rays with more than CAP steps)
+    and in the LIDARHIP_TRACE=binary child (k_trace)."""
+    here = run_writeback_variants(*WRITEBACK_CASE)
+    print(json.dumps(here))
+    twin = _binary_edge_child()[-1]
+    assert twin["case"] == here["case"] and twin["binary"] and not here["binary"]
+    assert twin["hits"] == here["hits"] == 16
+
+
 if __name__ == "__main__":
-    print("LBVH_CASES " + json.dumps([run_case(*case) for case in json.loads(sys.argv[1])]))
+    print("LBVH_CASES " + json.dumps([_run(case) for case in json.loads(sys.argv[1])]))
