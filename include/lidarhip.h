@@ -657,6 +657,43 @@ int lt_reverse_projection_beams_az_dev(const float* range_img, const void* proj_
  * used).  Asynchronous on `stream`. */
 int lt_points_to_frame_dev(const float* points, const int* tri, int n, const double* T, float* out, void* stream);
 
+/* ---- the target sensor's return model (the reference writes every hit) ------------------------
+ *
+ * Applied to a rendered scan cell by cell, in place.  Per cell i: tri[i], range[i], endrem[i]; the ray d = rays[i]; for a
+ * hit the float32 vertices v0, v1, v2 of face tri[i] of the scene's CURRENT mesh.  In float64 from the widened float32
+ * values, every product and sum rounded on its own, in this order:
+ *   e1 = v1 - v0;  e2 = v2 - v0;  n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x)
+ *   dot = (nx*dx + ny*dy) + nz*dz;  nn = (nx*nx + ny*ny) + nz*nz;  dd = (dx*dx + dy*dy) + dz*dz
+ *   q = |dot| / sqrt(nn * dd);  c = (nn == 0 || dd == 0) ? 0 : (q < 1 ? q : 1)        the cosine of the incidence angle
+ * The cell's code is the FIRST rule that applies (all comparisons strict: a cell exactly at a threshold stays):
+ *   1  tri[i] < 0 (no hit)       2  (double)range[i] < min_range      3  (double)range[i] > max_range
+ *   4  c < min_cos               5  hash(seed, scan, i) < drop_threshold                0  the return stands
+ * with  mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16  (uint32, wrapping) and
+ * hash(seed, scan, i) = mix(mix(mix(seed) + scan) + i): a pure function of the three, so a scan's pattern does not depend
+ * on the chain, rank or order it is rendered in.  `scan`: the output scan's index in its sequence (its file's number).
+ * A cell with code 2 - 5 becomes the miss LT_TRACE_WRITE_MISSES writes: end point (0, 0, 0), label / colour 0, remission 0,
+ * range 0, tri -1.  Code 0 keeps everything; with LT_RETURN_LAMBERT endrem[i] = float32((double)endrem[i] * c).  Code 1 is
+ * left as it is.  incidence[i] = float32(c) for code 0, else -1; drop[i] = the code.  No counters: totals are a bincount.
+ * min_cos = cos(max_incidence) and drop_threshold = floor(drop_rate * 2^32) are the HOST's: the kernel has no transcendental. */
+typedef struct lt_return_model {
+  double min_range, max_range; /* metres; 0 <= min_range <= max_range (+inf: no far gate)                              */
+  double min_cos;              /* in [0, 1]; 0 never drops                                                             */
+  unsigned drop_threshold;     /* 0 never drops                                                                        */
+  unsigned seed;
+  unsigned flags;              /* LT_RETURN_LAMBERT or 0                                                               */
+} lt_return_model;
+#define LT_RETURN_LAMBERT 1u
+
+/* rays [n_rays,3] f32 DEVICE: the tensor the ray set was built from (posed, if the sensor is mounted).  model: HOST, read
+ * before the call returns.  tri [n] i32 and range [n] f32 are mandatory; endpoints [n,3] f32, endcolors ([n] i32 with
+ * trace_flags & LT_TRACE_LABEL_IMAGE, else [n,3] i32), endrem [n] f32, incidence [n] f32 and drop [n] u8 may each be NULL --
+ * all DEVICE, read-modify-write.  A tri value outside [-1, n_faces), or a face whose vertices are outside [0, n_verts),
+ * sets the scene's deferred LT_ERR_BAD_INDEX (lt_scene_status); such a cell gets code 1 and nothing beside the mesh is
+ * read.  One thread per cell, asynchronous on `stream`. */
+int lt_return_model_dev(lt_scene* scene, const float* rays, int n_rays, const lt_return_model* model, unsigned scan,
+                        float* endpoints, int* endcolors, float* range, float* endrem, int* tri, float* incidence,
+                        unsigned char* drop, unsigned trace_flags, void* stream);
+
 /* Pack a rendered scan in SemanticKITTI layout; replaces the filtering and the per-point struct.pack loops
  * of MultiSemLaserScan.write (auxiliary/laserscan.py:1133-1178).  Keeps, in order, the cells with
  * (index == NULL or index[i] > 0) and label[i] >= 0 and x + y + z != 0.  points [n,3] f32 or f64,
@@ -754,7 +791,7 @@ const char* lt_version(void);
 
 /* Layout version of the structs this header declares (lt_proj_images, lt_stats, lt_mm_geometry ...): a caller compiled
  * against another header must not pass them.  lt_abi_version() returns the library's; the Python binding compares at load. */
-#define LT_ABI_VERSION 8
+#define LT_ABI_VERSION 9
 int lt_abi_version(void);
 
 #ifdef __cplusplus

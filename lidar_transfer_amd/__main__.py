@@ -11,7 +11,10 @@ image rows at the angles of its ``beam_angles``; no metrics are printed and ever
 horizontal field of view of ``fov_hor`` degrees around ``azimuth_center``: rays and image columns cover that sector alone; no
 metrics are printed and every row of ``--log`` carries ``"azimuth_model": "sector"``.  A table target with
 ``beam_azimuth_offsets`` (config/vlp32c_table_az_1024.yaml) shears rays and columns row by row by its beams' azimuth offsets;
-every row of ``--log`` then carries ``"beam_azimuth": true`` as well.  The tool
+every row of ``--log`` then carries ``"beam_azimuth": true`` as well.  A target YAML with a ``return_model`` block
+(config/vlp32c_table_returns_1024.yaml) applies the sensor's range gate, incidence limit and random dropout to every output scan
+of ``mesh`` / ``mergemesh`` (``cp`` is refused); the run closes with one line ``Returns: kept N, no hit N, ...``, the cells per
+code over all its scans, which the ``--log`` summary carries as ``return_totals``.  The tool
 is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
 ``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  A missing dataset, labels or output
 folder ends with a message and exit status 1."""
@@ -76,6 +79,9 @@ def main(argv=None):
         print("Error opening yaml file.")
         return 1
     from .sequence import SequenceTransfer
+    if target.return_model() is not None and approach.adaption == "cp":
+        print("adaption cp renders no surface: the target sensor's return_model cannot be applied (use mesh or mergemesh).")
+        return 1
     log = open(args.log, "w") if args.log else None
     try:
         with SequenceTransfer((args.dataset, args.sequence), approach, source, target, out_dir=args.output if args.write else None,
@@ -98,6 +104,9 @@ def main(argv=None):
                     if tr.beam_azimuth is not None:
                         row["beam_azimuth"] = True
                     log.write(json.dumps(row) + "\n")
+            if tr.summary.get("return_totals") is not None:
+                from .sequence import format_return_totals
+                print(format_return_totals(tr.summary["return_totals"]), flush=True)
             if log is not None:
                 log.write(json.dumps(dict(summary=tr.summary)) + "\n")
     finally:

@@ -57,6 +57,43 @@ def out_ptrs(out):
     return tuple(out[k].data_ptr() if out.get(k) is not None else None for k in OUT_KEYS)
 
 
+class Returns:
+    """The target sensor's return model on a chain (``config.ReturnModel`` or ``None``).  ``None``, or a model
+    with every field at its default: nothing here allocates or launches.  Applied once per output scan, to the render that
+    stands, behind it on the chain's stream and BEFORE the hits go into the target's frame, evaluation and packing."""
+
+    KEYS = ("incidence", "drop")
+
+    def __init__(self, model, who="return model"):
+        from .config import ReturnModel
+        if model is not None and not isinstance(model, ReturnModel):
+            raise ValueError(f"{who}: returns= takes a lidar_transfer_amd.config.ReturnModel (SensorModel.return_model()) or None")
+        self.model = None if model is None or model.is_default else model
+
+    def __bool__(self):
+        return self.model is not None
+
+    def render_into(self, rout, n_rays, device):
+        """What the render writes for this chain: ``rout`` itself without a model or when it holds ``tri`` already; else a
+        copy with a ``tri`` image (the model reads the hit triangle).  Allocates on the current stream."""
+        if self.model is None or rout.get("tri") is not None:
+            return rout
+        import torch
+        rout = dict(rout)
+        rout["tri"] = torch.empty((n_rays,), dtype=torch.int32, device=device)
+        return rout
+
+    def apply(self, rout, scan, scene, rays, stream, label_image=True):
+        """the model on the rendered images ``rout`` of output scan ``scan`` (its index in its sequence), on ``stream``;
+        returns ``dict(incidence=, drop=)``, or ``{}`` without a model"""
+        if self.model is None:
+            return {}
+        if scan is None:
+            raise ValueError("a return model needs the output scan's index in its sequence (scan_index=)")
+        from . import post
+        return post.return_model(scene, rays, self.model, scan, rout, label_image=label_image, stream=stream)
+
+
 class Mount:
     """The target sensor's mounting from the approach file's ``transformation`` (``config.mount_of``).  ``pair``: ``(T, P)``,
     or ``None`` for no mounting (``None``, empty, the identity) -- then nothing here allocates or launches.  ``T``

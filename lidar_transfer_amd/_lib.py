@@ -30,6 +30,7 @@ LT_COMPARE_MAX_NLABELS = 2048
 LT_COMPARE_MAX_PRESENT = 64
 LT_COMPARE_OVERFLOW = 1
 LT_COMPARE_LABEL_RANGE = 2
+LT_RETURN_LAMBERT = 1
 
 #: every symbol include/lidarhip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_dev", "lt_scene_set_mesh_host",
@@ -48,8 +49,8 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_reverse_projection_beams_dev", "lt_create_rays_sector_dev", "lt_reverse_projection_sector_dev",
            "lt_rayset_create_grid_dev", "lt_projector_set_sector", "lt_range_projection_set_sector",
            "lt_create_rays_beams_az_dev", "lt_projector_set_beam_azimuth", "lt_range_projection_set_beam_azimuth",
-           "lt_reverse_projection_beams_az_dev"]
-LT_ABI_VERSION = 8   # include/lidarhip.h: layout version of the structs mirrored below
+           "lt_reverse_projection_beams_az_dev", "lt_return_model_dev"]
+LT_ABI_VERSION = 9   # include/lidarhip.h: layout version of the structs mirrored below
 
 
 class Stats(C.Structure):
@@ -101,6 +102,12 @@ class CompareRecord(C.Structure):
     _fields_ = [("status", C.c_int), ("n_present", C.c_int), ("n_cells", C.c_int), ("src_bad_labels", C.c_uint),
                 ("sq_sum", C.c_double), ("present", C.c_int * LT_COMPARE_MAX_PRESENT),
                 ("counts", C.c_uint * (LT_COMPARE_MAX_PRESENT * LT_COMPARE_MAX_PRESENT))]
+
+
+class ReturnModelArgs(C.Structure):
+    """Mirror of ``lt_return_model``: the target sensor's return model as ``lt_return_model_dev`` reads it (HOST)."""
+    _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("min_cos", C.c_double), ("drop_threshold", C.c_uint),
+                ("seed", C.c_uint), ("flags", C.c_uint)]
 
 
 def ingest_work_ints(n_total: int, n_scans: int) -> int:
@@ -281,6 +288,9 @@ def load():
     lib.lt_range_projection_set_beam_azimuth.restype = C.c_int
     lib.lt_reverse_projection_beams_az_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, dp, C.c_int, C.c_int, vp, vp]
     lib.lt_reverse_projection_beams_az_dev.restype = C.c_int
+    lib.lt_return_model_dev.argtypes = [vp, vp, C.c_int, C.POINTER(ReturnModelArgs), C.c_uint, vp, vp, vp, vp, vp, vp, vp,
+                                        C.c_uint, vp]
+    lib.lt_return_model_dev.restype = C.c_int
     lib.lt_abi_version.argtypes = []
     lib.lt_tsdf_volume_stride.argtypes = []
     if lib.lt_abi_version() != LT_ABI_VERSION:  # a stale prebuilt library: its structs are laid out differently

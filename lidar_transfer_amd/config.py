@@ -26,6 +26,12 @@ Three optional keys are this project's own, for a TARGET sensor; :class:`TargetM
   ``beam_angles`` (the loader pairs the two before it sorts the angles) -- the lasers of one firing do not share an azimuth,
   beam ``h`` of a column looks ``offset[h]`` to the LEFT of the column's nominal direction, measured like ``azimuth_center``
   (:meth:`SensorModel.beam_azimuth`); offsets that are all zero are none.
+
+A fourth is what the target MEASURES along those rays, :class:`ReturnModel` (``SensorModel.return_model()``):
+
+* ``return_model``: a block of ``min_range``, ``max_range`` (metres), ``max_incidence`` (degrees), ``remission`` (``none`` |
+  ``lambert``), ``drop_rate`` and ``seed`` -- returns outside the range gate, seen too close to edge-on or dropped at random
+  become misses of the rendered scan; a block with every field at its default is none.
 """
 from __future__ import annotations
 
@@ -52,6 +58,8 @@ class SensorModel:
     azimuth_center: float = 0.0
     #: per-beam azimuth offsets in degrees, paired with ``beam_angles`` index by index (the loader sorts the two together)
     beam_azimuth_offsets: Optional[List[float]] = None
+    #: the file's ``return_model`` block as read (a mapping), ``None`` without the key: :meth:`return_model`
+    return_block: Optional[dict] = None
 
     @property
     def H(self) -> int:
@@ -98,6 +106,12 @@ class SensorModel:
                 az = az[order]
         sector = (self.azimuth_center, self.fov_hor) if self.azimuth_model == "sector" else None
         return TargetModel(table, sector, az, who).validate(self.H, (self.fov_up, self.fov_down), who)
+
+    def return_model(self):
+        """The sensor's :class:`ReturnModel` -- what a TARGET measures along its rays: range gate, incidence, dropout (DESIGN
+        7e) -- or ``None`` without the ``return_model`` key or with every field at its default.  ``ValueError`` led by the
+        sensor's name for a block that cannot be used.  :class:`TargetModel` stays rows and columns."""
+        return ReturnModel.of(self.return_block, f"sensor {self.name!r}")
 
     def sector(self):
         """``None`` for ``azimuth_model: full``; for ``sector`` ``(center_deg, span_deg)`` as floats: the ``W`` columns span
@@ -290,6 +304,124 @@ class TargetModel:
         return None if self.sector is None else sector_grid(W, self.sector)
 
 
+def return_hash_mix(x):
+    """``mix`` of the return model's hash (include/lidarhip.h), uint32 with wrapping products, on a Python int"""
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7feb352d) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846ca68b) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x
+
+
+def return_hash(seed, scan, i):
+    """``hash(seed, scan, i) = mix(mix(mix(seed) + scan) + i)`` (uint32 sums wrap): the random rule of :class:`ReturnModel`, a
+    pure function of the three -- a scan's pattern is the same whichever chain, rank or order renders it"""
+    return return_hash_mix(return_hash_mix(return_hash_mix(int(seed)) + int(scan)) + int(i))
+
+
+class ReturnModel:
+    """What a TARGET sensor measures along its rays beyond the reference's "every hit returns" (the sensor file's
+    ``return_model`` block), as one immutable value like :class:`TargetModel`: a range gate ``min_range`` /
+    ``max_range`` (metres), ``max_incidence`` (degrees between ray and surface normal; 90 never drops), ``remission``
+    (``"none"`` or ``"lambert"``: the remission times the cosine of the incidence angle), ``drop_rate`` (probability of a
+    random drop) and its ``seed``.  The constructor is the only place that normalises and validates -- finite numbers,
+    ``0 <= min_range <= max_range`` (``max_range`` may be ``inf``), ``0 < max_incidence <= 90``, ``0 <= drop_rate < 1``,
+    ``seed`` in uint32, else ``ValueError`` led by ``who`` -- and :meth:`of` returns ``None`` for a model in which every field
+    is at its default, as all-zero azimuth offsets are none.  What the library reads is derived here in float64 / Python
+    ints: :attr:`min_cos` ``= cos(max_incidence * pi / 180)`` (exactly 0 for 90), :attr:`drop_threshold`
+    ``= floor(drop_rate * 2^32)``."""
+
+    DEFAULTS = dict(min_range=0.0, max_range=float("inf"), max_incidence=90.0, remission="none", drop_rate=0.0, seed=0)
+
+    def __init__(self, min_range=0.0, max_range=float("inf"), max_incidence=90.0, remission="none", drop_rate=0.0, seed=0,
+                 who="return model"):
+        import math
+
+        def number(name, v):
+            try:
+                if isinstance(v, (bool, str)):
+                    raise TypeError
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: return_model {name} must be a number, not {v!r}") from None
+            if math.isnan(v) or (math.isinf(v) and not (name == "max_range" and v > 0)):
+                raise ValueError(f"{who}: return_model {name} must be finite (max_range may be +inf), not {v}")
+            return v
+        lo, hi = number("min_range", min_range), number("max_range", max_range)
+        inc, rate = number("max_incidence", max_incidence), number("drop_rate", drop_rate)
+        if not 0.0 <= lo <= hi:
+            raise ValueError(f"{who}: return_model needs 0 <= min_range <= max_range (min_range = {lo}, max_range = {hi})")
+        if not 0.0 < inc <= 90.0:
+            raise ValueError(f"{who}: return_model needs 0 < max_incidence <= 90 degrees (max_incidence = {inc})")
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"{who}: return_model needs 0 <= drop_rate < 1 (drop_rate = {rate})")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= 0xFFFFFFFF:
+            raise ValueError(f"{who}: return_model seed must be an integer in [0, 2^32), not {seed!r}")
+        if remission not in ("none", "lambert"):
+            raise ValueError(f"{who}: return_model remission {remission!r} (none or lambert)")
+        self.__dict__.update(min_range=lo, max_range=hi, max_incidence=inc, remission=str(remission), drop_rate=rate,
+                             seed=int(seed))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a ReturnModel does not change: make another")
+
+    @classmethod
+    def of(cls, block, who="return model"):
+        """The model of a sensor file's ``return_model`` block (a mapping, or ``None``: no key), or ``None`` when every field
+        is at its default; an unknown key and a block that is no mapping are ``ValueError``.  A :class:`ReturnModel` passes
+        through (``None`` if all-default)."""
+        if block is None:
+            return None
+        if isinstance(block, cls):
+            return None if block.is_default else block
+        if not isinstance(block, dict):
+            raise ValueError(f"{who}: return_model must be a mapping of {', '.join(cls.DEFAULTS)}")
+        unknown = sorted(set(map(str, block)) - set(cls.DEFAULTS))
+        if unknown:
+            raise ValueError(f"{who}: return_model has unknown key(s) {', '.join(unknown)} (known: {', '.join(cls.DEFAULTS)})")
+        m = cls(who=who, **block)
+        return None if m.is_default else m
+
+    def fields(self):
+        return {k: getattr(self, k) for k in self.DEFAULTS}
+
+    @property
+    def is_default(self):
+        return self.fields() == self.DEFAULTS
+
+    def __eq__(self, other):
+        return isinstance(other, ReturnModel) and self.fields() == other.fields()
+
+    def __hash__(self):
+        return hash(tuple(self.fields().values()))
+
+    def __repr__(self):
+        return "ReturnModel(" + ", ".join(f"{k}={v!r}" for k, v in self.fields().items()) + ")"
+
+    @cached_property
+    def min_cos(self):
+        """``cos(max_incidence * pi / 180)`` in float64; exactly 0 for 90 degrees (where the float64 cosine is 6e-17)"""
+        import math
+        return 0.0 if self.max_incidence == 90.0 else math.cos(self.max_incidence * math.pi / 180.0)
+
+    @property
+    def drop_threshold(self):
+        """``floor(drop_rate * 2^32)`` as a Python int (below 2^32: ``drop_rate < 1``)"""
+        return min(int(self.drop_rate * 4294967296.0), 0xFFFFFFFF)
+
+    @property
+    def lambert(self):
+        return self.remission == "lambert"
+
+    def args(self):
+        """the model as ``lt_return_model_dev`` reads it (``_lib.ReturnModelArgs``)"""
+        from . import _lib
+        return _lib.ReturnModelArgs(self.min_range, self.max_range, self.min_cos, self.drop_threshold, self.seed,
+                                    _lib.LT_RETURN_LAMBERT if self.lambert else 0)
+
+
 def _load_yaml(path_or_dict):
     if isinstance(path_or_dict, dict):
         return path_or_dict
@@ -327,8 +459,9 @@ def load_sensor(path_or_dict) -> SensorModel:
     model = SensorModel(name, fov_up, fov_down, beams, angle_res_hor, fov_hor, beam_angles, raw=cfg,
                         beam_model=str(cfg.get("beam_model", "linear")),
                         azimuth_model=str(cfg.get("azimuth_model", "full")), azimuth_center=cfg.get("azimuth_center", 0.0),
-                        beam_azimuth_offsets=offsets)
+                        beam_azimuth_offsets=offsets, return_block=cfg.get("return_model"))
     model.target_model()   # (a table, a sector or offsets that cannot be used: said at load time)
+    model.return_model()   # (and a return model that cannot be)
     return model
 
 
@@ -354,11 +487,20 @@ def refuse_source_beam_azimuth(source):
                          "source scan is fused by the reference's pixel model: one azimuth per column)")
 
 
+def refuse_source_return_model(source):
+    """A return model is a property of the TARGET as well: the source scan is what its sensor recorded."""
+    if getattr(source, "return_block", None) is not None:
+        raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: return_model is for target sensors only (the source "
+                         "scan holds the returns its sensor recorded)")
+
+
 def refuse_source_models(source):
-    """everything a :class:`TargetModel` holds is a property of the TARGET: the three refusals, the table's first"""
+    """everything a :class:`TargetModel` or a :class:`ReturnModel` holds is a property of the TARGET: the four refusals, the
+    table's first"""
     refuse_source_table(source)
     refuse_source_sector(source)
     refuse_source_beam_azimuth(source)
+    refuse_source_return_model(source)
 
 
 @dataclass

@@ -135,7 +135,7 @@ class DeviceDeform:
 
     def __init__(self, source, target, vol_bnds=None, voxel_size=0.1, beam_angles=None, t_beam_angles=None,
                  preserve_float=False, device=None, merge=True, fusion="cuda", mesh_volume=True, rayset=None, mm_state=None,
-                 transformation=None, t_beam_table=None, t_sector=None, t_beam_azimuth=None):
+                 transformation=None, t_beam_table=None, t_sector=None, t_beam_azimuth=None, returns=None):
         """``fusion``: ``"cuda"`` -- the arithmetic of the reference's CUDA kernel (class-aware with ``merge``), or ``"numpy"`` --
         that of its numpy branch (``FUSION_GPU_MODE == 0``, fusion_lidar.py:290-388; what goldens F13 / F14 are made by).
         ``vol_bnds``: [3,2]; for :meth:`mergemesh` it is STATE, clipped in place call after call exactly as the reference
@@ -155,7 +155,12 @@ class DeviceDeform:
         ``transformation``), so ``mesh`` and ``mergemesh`` change by their rays alone -- and, for a sector, by the ray set's bin
         grid (``TargetModel.grid``; ``mergemesh`` still fuses what the source origin sees inside the target's vertical field of
         view).  ``cp`` projects into the model's rows and columns (``Projector``) and re-projects along the winner's ray (the
-        ``lt_reverse_projection*_dev`` entry point of the model).  A shared ``rayset`` must have been built for an equal model."""
+        ``lt_reverse_projection*_dev`` entry point of the model).  A shared ``rayset`` must have been built for an equal model.
+        ``returns``: the TARGET sensor's :class:`~lidar_transfer_amd.config.ReturnModel` (``SensorModel.return_model()``;
+        ``None`` or all-default: nothing of it runs) -- ``mesh`` and ``mergemesh`` then take ``scan_index``, the output scan's
+        index in its sequence, apply the model once to the render that stands (range gate, incidence, dropout: such cells
+        become misses) before the hits go into the target's frame and before packing, and return ``incidence`` and ``drop``
+        as well; ``cp`` renders no surface and raises."""
         import numpy as np
         import torch
 
@@ -181,6 +186,8 @@ class DeviceDeform:
         self._mm_state, self._mm_own = mm_state, mm_state is None
         self._rayset_own = rayset is None
         self._mounting = _chain.Mount(transformation)
+        self._returns = _chain.Returns(returns, "DeviceDeform")
+        self.returns = self._returns.model
         m = self.t_model = TargetModel(t_beam_table, t_sector, t_beam_azimuth, "DeviceDeform").validate(
             self.t_H, (self.t_fov_up, self.t_fov_down), "DeviceDeform")
         # what the reverse projection reads on the device: the table and the offsets in radians
@@ -275,7 +282,7 @@ class DeviceDeform:
                     n_faces=self.mesh_obj.n_faces, **more)
 
     # ---- deform('mesh') + write ---------------------------------------------------------------------------------------
-    def mesh(self, clouds, origin=None, pack=True, timing=None):
+    def mesh(self, clouds, origin=None, pack=True, timing=None, scan_index=None):
         """``clouds``: one (points [n,3] f32|f64, remissions [n] f32, label [n] i32) triple of CUDA tensors per source scan,
         already in the primary scan's frame (laserscan.py:876-879).  Returns the target scan: ``range`` / ``rem`` [t_H,t_W]
         f32, ``label`` [t_H,t_W] i32 (``label_image``, :912), ``endpoints`` [t_H*t_W,3] f32 (``back_points``), ``tri``, the
@@ -283,9 +290,12 @@ class DeviceDeform:
         bytes ``write`` puts into ``velodyne/N.bin`` and ``labels/N.label``.  ``timing``: a list that receives CUDA events
         (start, projected, rendered, packed) when given.  ``origin``: where the rays start in the scene (default: the target
         sensor's position, (0, 0, 0) unless it is mounted elsewhere); ``endpoints`` are in the target sensor's frame,
-        ``endpoints_scene`` as rendered."""
+        ``endpoints_scene`` as rendered.  ``scan_index``: the output scan's index in its sequence, needed with a return
+        model (``returns=``): the result is what the target sensor sees, with ``incidence`` and ``drop`` [n] beside it."""
         if origin is None:
             origin = self.origin
+        if self._returns and scan_index is None:
+            raise ValueError("DeviceDeform.mesh: a return model needs scan_index, the output scan's index in its sequence")
         if self.vol is None:
             raise RuntimeError("DeviceDeform.mesh: constructed without vol_bnds")
         torch, lib = self._torch, self._lib
@@ -303,15 +313,16 @@ class DeviceDeform:
         for k, o in enumerate(src):
             cp[k], dp[k], rp[k] = o["label_folded"].data_ptr(), o["range"].data_ptr(), o["rem"].data_ptr()
         out = self.scene.alloc_outputs(self.n_rays, label_image=True)
-        rout = self._mounting.render_into(out, self.n_rays, self.device)
+        rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays, self.device)
         with torch.cuda.device(self.device):
             _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, n, cp, dp, rp,
                                               self.H, self.W, 1.0, self._merge, _chain.origin3(origin), *_chain.out_ptrs(rout),
                                               _chain.TRACE_FLAGS, vp(st.cuda_stream), 0), "lt_fusion_scan_dev")
+            seen = self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st)
             self._mounting.to_target(rout, out, st)
             if ev:
                 ev[2].record(st)
-            res = self._result(out, rout, source=src)
+            res = self._result(out, rout, source=src, **seen)
             if pack:
                 res["bin"], res["label_file"] = self.pack_result(res, st)
             if ev:
@@ -370,7 +381,7 @@ class DeviceDeform:
         self._mm_vols[key] = vol
         return vol
 
-    def mergemesh(self, clouds, origin=None, pack=True, out=None, seq=None, source_images=False):
+    def mergemesh(self, clouds, origin=None, pack=True, out=None, seq=None, source_images=False, scan_index=None):
         """``clouds``: the (points, remissions, label) CUDA triples of the source scans, already in the primary scan's frame
         (``apply_inv_pose``, laserscan.py:949: pose handling is out of scope).  Returns what :meth:`mesh` returns -- the
         target scan's ``range`` / ``rem`` / ``label`` images, ``endpoints``, ``tri``, the merged cloud's source image under
@@ -381,7 +392,8 @@ class DeviceDeform:
         scan's number in its sequence when several chains share the state.  By default the whole scan is ONE native call
         (``lt_mergemesh_scan_dev``; the source image stays inside the projector); ``source_images=True`` composes it from
         the public steps instead and returns the merged cloud's images under ``source``.  ``origin`` / ``endpoints`` /
-        ``endpoints_scene``: as for :meth:`mesh`."""
+        ``endpoints_scene`` / ``scan_index``: as for :meth:`mesh`; a return model is applied to the render that stands -- after
+        a re-run, never to the speculative one."""
         if origin is None:
             origin = self.origin
         if self.vol_bnds is None:
@@ -393,7 +405,9 @@ class DeviceDeform:
             cloud = _chain.merged_cloud(clouds)
             if out is None:
                 out = self.scene.alloc_outputs(self.n_rays, label_image=True)
-            rout = self._mounting.render_into(out, self.n_rays, self.device)
+            if self._returns and scan_index is None:
+                raise ValueError("DeviceDeform.mergemesh: a return model needs scan_index, the output scan's index in its sequence")
+            rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays, self.device)
             first, again, more = (self._mm_composed if source_images else self._mm_native)(
                 mm, cloud, seq, _chain.origin3(origin), _chain.out_ptrs(rout), st)
             pred, vol = mm.pred, None
@@ -420,6 +434,7 @@ class DeviceDeform:
                 mm.stats["waited" if vol is None else "rerun"] += 1
                 vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
                 again(vol)
+            more.update(self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st))
             self._mounting.to_target(rout, out, st)
             res = self._result(out, rout, vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
                                vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol, **more)
@@ -483,7 +498,11 @@ class DeviceDeform:
         (:841-843), re-projected to points (:844-845) and written (:1133-1160).  Returns ``range``, ``rem``, ``label``,
         ``index`` images, ``back_points`` [t_H*t_W,3] f64 and -- with ``pack`` -- ``bin`` / ``label_file``.
         The reference's ``cp`` path always holds float64 points (``apply_pose``, laserscan.py:98-104) and goldens F12 / F12b pin
-        that; float32 clouds with ``preserve_float`` are re-projected in float64 here as well (numpy would stay in float32)."""
+        that; float32 clouds with ``preserve_float`` are re-projected in float64 here as well (numpy would stay in float32).
+        ``cp`` renders no surface, so there is no incidence angle: with a return model it raises ``ValueError``."""
+        if self._returns:
+            raise ValueError("DeviceDeform.cp: the target sensor has a return_model, but cp renders no surface (no hit triangle, "
+                             "no incidence angle): use mesh or mergemesh, or a target file without the key")
         torch = self._torch
         st = self._stream()
         pf = self.preserve_float

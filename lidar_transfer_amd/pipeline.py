@@ -317,10 +317,17 @@ class FusionScanPipeline:
     needs nothing but its rays -- pass ``create_rays_device(..., beam_table=m.beam_table, sector=m.sector,
     beam_azimuth=m.beam_azimuth)`` (with ``rot`` when it is mounted as well) as ``rays`` -- and, for a sector and for speed
     alone, a bin grid at the sector's resolution: ``grid=m.grid(W)`` (``grid`` goes to the ``RaySet``, ``None``: the image's
-    rule)."""
+    rule).
+
+    ``returns``: the target sensor's :class:`~lidar_transfer_amd.config.ReturnModel` (``SensorModel.return_model()``;
+    ``None`` or all-default: nothing changes).  Every ``submit*`` then needs ``scan_index``, the output scan's index in its
+    sequence -- the random drops are a function of it, not of the ticket or the chain --; the model is applied once on the
+    chain's stream behind the render that stands and before the hits go into the target's frame (no host wait is added),
+    and a result carries ``incidence`` and ``drop`` [n] as well (``post.return_model``)."""
 
     def __init__(self, vol_bnds, voxel_size, fov_up, fov_down, rays, H, chains=3, device=None, merge=True,
-                 label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None, grid=None):
+                 label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None, grid=None,
+                 returns=None):
         import queue
         import threading
         import weakref
@@ -337,6 +344,8 @@ class FusionScanPipeline:
         self.device = torch.device("cuda", idx)
         self._mounting = _chain.Mount(transformation)
         self.mount, self.origin = self._mounting.pair, self._mounting.origin
+        self._returns = _chain.Returns(returns, "FusionScanPipeline")
+        self.returns = self._returns.model
         self.rayset = RaySet(rays, H, pose=self._mounting.P, grid=grid)  # one read-only ray set for all chains
         self.n_rays = self.rayset.n_rays
         self.label_image = bool(label_image)
@@ -373,7 +382,7 @@ class FusionScanPipeline:
             ch["thread"].start()
 
     # ---- a chain's thread ---------------------------------------------------------------------------------------------
-    def _scan(self, ch, kind, items, origin, out, seq):
+    def _scan(self, ch, kind, items, origin, out, seq, scan_index):
         """one job on its chain's stream: ``kind`` is ``"images"`` (:meth:`submit`), ``"clouds"`` or ``"mergemesh"``"""
         torch = self._torch
         try:
@@ -381,13 +390,15 @@ class FusionScanPipeline:
                 if out is None:
                     out = ch["scene"].alloc_outputs(self.n_rays, label_image=self.label_image)
                 if kind == "mergemesh":
-                    return self._scan_mergemesh(ch, items, origin, out, seq)
+                    return self._scan_mergemesh(ch, items, origin, out, seq, scan_index)
                 if ch["vol"] is None:
                     raise RuntimeError("FusionScanPipeline: constructed with fixed_volume=False (submit_mergemesh only)")
-                rout = self._mounting.render_into(out, self.n_rays, self.device)
+                rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays,
+                                                 self.device)
                 scan = self._scan_clouds if kind == "clouds" else self._scan_images
                 keep = scan(ch, items, _chain.origin3(origin), _chain.out_ptrs(rout))
-                return self._finish(ch, out, rout, ch["mesh"], keep, items)
+                seen = self._returns.apply(rout, scan_index, ch["scene"], self.rayset.rays, ch["stream"], self.label_image)
+                return self._finish(ch, out, rout, ch["mesh"], keep, items, **seen)
         except BaseException:
             if kind == "mergemesh":
                 self._mm_state.skip(seq)  # (a failed scan -- its outputs included -- must not hold up the later scans)
@@ -398,7 +409,7 @@ class FusionScanPipeline:
         event behind the render on the chain's stream -- what wait() waits for, so the chain's next scan is queued while this
         one still renders -- and the result; temporaries and inputs stay referenced until the event has passed."""
         res = dict(out, n_verts=mesh.n_verts, n_faces=mesh.n_faces, **more)
-        if rout is not out:
+        if rout.get("endpoints") is not out.get("endpoints"):
             self._mounting.to_target(rout, out, ch["stream"])
             res["endpoints_scene"] = rout["endpoints"]
         done = self._torch.cuda.Event()
@@ -445,7 +456,7 @@ class FusionScanPipeline:
                                                 C.c_void_p(ch["stream"].cuda_stream), 0), "lt_deform_scan_dev")
         return keep
 
-    def _scan_mergemesh(self, ch, clouds, origin, out, seq):
+    def _scan_mergemesh(self, ch, clouds, origin, out, seq, scan_index):
         """deform('mergemesh') of one output scan on this chain (DeviceDeform.mergemesh on the chain's stream): projection
         with the target field of view -> the bounds statements on the shared device state, in sequence order -> fusion
         chain on the predicted geometry -> verified against the record"""
@@ -457,10 +468,10 @@ class FusionScanPipeline:
             sensor_t = (a["H"], self.n_rays // a["H"], self._src_fov[0], self._src_fov[1])
             dd = DeviceDeform(sensor_s, sensor_t, None, a["voxel_size"], beam_angles=self._beam_angles, device=self.device.index,
                               merge=a["merge"], mesh_volume=False, rayset=self.rayset, mm_state=self._mm_state,
-                              transformation=self.mount)
+                              transformation=self.mount, returns=self.returns)
             ch["deform"] = dd
-        got = dd.mergemesh(clouds, origin, pack=False, out=out, seq=seq)
-        more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after")}
+        got = dd.mergemesh(clouds, origin, pack=False, out=out, seq=seq, scan_index=scan_index)
+        more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after") + (_chain.Returns.KEYS if self._returns else ())}
         if self.mount is not None:   # (the chain's DeviceDeform has taken the hits into the target's frame)
             more["endpoints_scene"] = got["endpoints_scene"]
         return self._finish(ch, out, out, dd.mesh_obj, [got.get("source"), got.get("_keep")], clouds, **more)
@@ -477,7 +488,7 @@ class FusionScanPipeline:
         ev.set()
 
     # ---- caller's side --------------------------------------------------------------------------------------------------
-    def submit(self, observations, origin=None, out=None, inputs_ready=False):
+    def submit(self, observations, origin=None, out=None, inputs_ready=False, scan_index=None):
         """Queue one output scan: ``observations`` = the (color_im, depth_im, rem_im) CUDA tensors fused into its volume,
         in order.  Returns the ticket.  ``out``: a dict like ``Scene.alloc_outputs`` returns (missing keys are not written).
         ``inputs_ready``: the caller guarantees that the observation tensors are complete (no wait for its stream)."""
@@ -488,11 +499,13 @@ class FusionScanPipeline:
         for o in obs:
             if len(o) != 3 or not all(isinstance(a, torch.Tensor) and a.is_cuda for a in o):
                 raise ValueError("observations: (color_im, depth_im, rem_im) CUDA tensors")
-        return self._submit("images", obs, origin, out, inputs_ready)
+        return self._submit("images", obs, origin, out, inputs_ready, scan_index=scan_index)
 
-    def _submit(self, kind, items, origin, out, inputs_ready, seq=None):
+    def _submit(self, kind, items, origin, out, inputs_ready, seq=None, scan_index=None):
         import threading
         torch = self._torch
+        if self._returns and scan_index is None:
+            raise ValueError("FusionScanPipeline: a return model needs scan_index, the output scan's index in its sequence")
         if not inputs_ready:
             torch.cuda.current_stream(self.device).synchronize()  # (see the class docstring)
         with self._lock:
@@ -501,10 +514,10 @@ class FusionScanPipeline:
             self._done[t] = threading.Event()
         if origin is None:   # the target sensor's own position: (0, 0, 0) unless it is mounted elsewhere
             origin = self.origin
-        self._chains[t % len(self._chains)]["q"].put((t, kind, items, tuple(origin), out, seq))
+        self._chains[t % len(self._chains)]["q"].put((t, kind, items, tuple(origin), out, seq, scan_index))
         return t
 
-    def submit_clouds(self, clouds, origin=None, out=None, inputs_ready=False):
+    def submit_clouds(self, clouds, origin=None, out=None, inputs_ready=False, scan_index=None):
         """Queue one output scan from the POINT CLOUDS of its source scans: ``clouds`` = ``(points [n,3] f32|f64, remissions
         [n] f32, label [n] i32)`` CUDA tensors per source scan, in the primary scan's frame (laserscan.py:876-879).  The
         chain projects them (``lt_range_projection_batch_dev``, one launch sequence, nothing read back) and runs the fusion
@@ -518,9 +531,9 @@ class FusionScanPipeline:
                 raise ValueError("clouds: (points, remissions, label) CUDA tensors")
             items.append((c[0], c[1], c[2]))
         # (no source scan at all: the empty volume of ``submit([])``)
-        return self._submit("clouds" if items else "images", items, origin, out, inputs_ready)
+        return self._submit("clouds" if items else "images", items, origin, out, inputs_ready, scan_index=scan_index)
 
-    def submit_mergemesh(self, clouds, origin=None, out=None, inputs_ready=False):
+    def submit_mergemesh(self, clouds, origin=None, out=None, inputs_ready=False, scan_index=None):
         """Queue one output scan of the reference's DEFAULT adaption (config/lidar_transfer.yaml:3; laserscan.py:921-1012): the
         source scans' clouds merged, projected with the TARGET field of view (this pipeline's ``fov_up`` / ``fov_down``) onto the
         SOURCE image (``source_hw``), ``vol_bnds`` clipped by the kept points' rounded bounds -- the statements run on the
@@ -545,8 +558,10 @@ class FusionScanPipeline:
             items.append((c[0], c[1], c[2]))
         if not items:   # (before the sequence number moves: no scan would ever take it, and every later one would wait for it)
             raise ValueError("FusionScanPipeline.submit_mergemesh: no clouds")
+        if self._returns and scan_index is None:   # (before the sequence number moves, like the empty list)
+            raise ValueError("FusionScanPipeline.submit_mergemesh: a return model needs scan_index")
         seq, self._mm_seq = self._mm_seq, self._mm_seq + 1
-        return self._submit("mergemesh", items, origin, out, inputs_ready, seq=seq)
+        return self._submit("mergemesh", items, origin, out, inputs_ready, seq=seq, scan_index=scan_index)
 
     def reset_bounds(self, vol_bnds):
         """A new sequence for :meth:`submit_mergemesh`: every submitted scan is completed, then the bounds state goes back to

@@ -72,6 +72,60 @@ def points_to_frame(points, T, tri=None, out=None, stream=None):
     return out
 
 
+def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label_image=True, stream=None):
+    """The target sensor's return model (``lt_return_model_dev``) on a rendered scan, in place and asynchronous
+    on ``stream`` (default the current one): a return outside the range gate, seen beyond ``max_incidence`` or dropped at
+    random (``hash(seed, scan, cell)``) becomes the miss the render writes -- end point (0, 0, 0), label 0, remission 0,
+    range 0, ``tri`` -1 --, and with ``remission: lambert`` the remission of one that stands is multiplied by the cosine of
+    its incidence angle.  ``scene``: the :class:`~lidar_transfer_amd.raytracer.Scene` that rendered (its CURRENT mesh is
+    read); ``rays``: the [n, 3] float32 CUDA tensor the ray set was built from; ``model``: a
+    :class:`~lidar_transfer_amd.config.ReturnModel`; ``scan``: the output scan's index in its sequence; ``out``: the render's
+    images (``Scene.alloc_outputs``' keys; ``tri`` and ``range`` are needed, the others may be absent or ``None``);
+    ``label_image``: whether ``endcolors`` is the [n] label image or [n, 3].  ``incidence`` / ``drop``: ``True`` -- a fresh
+    [n] float32 / uint8 tensor, a tensor -- that one, ``None`` -- not wanted.  Returns ``dict(incidence=..., drop=...)``:
+    the cosine of every standing return (-1 elsewhere) and every cell's code (0 stands, 1 no hit, 2 too near, 3 too far,
+    4 incidence, 5 random)."""
+    import torch
+
+    from .config import ReturnModel
+    if not isinstance(model, ReturnModel):
+        raise ValueError("model: a lidar_transfer_amd.config.ReturnModel")
+    tri, rng = out.get("tri"), out.get("range")
+    if tri is None or rng is None:
+        raise ValueError("out: the render's `tri` and `range` images are needed")
+    n = tri.numel()
+    dev = tri.device
+    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() \
+            or rays.numel() < 3 * n or rays.device != dev:
+        raise ValueError("rays: contiguous float32 CUDA tensor [n, 3] on the images' device")
+    want = dict(endpoints=(torch.float32, 3 * n), endcolors=(torch.int32, n if label_image else 3 * n),
+                range=(torch.float32, n), endrem=(torch.float32, n), tri=(torch.int32, n))
+    ptr = {}
+    for key, (dt, numel) in want.items():
+        t = out.get(key)
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != numel or t.device != dev):
+            raise ValueError(f"out[{key!r}]: contiguous {dt} CUDA tensor with {numel} elements on the device of `tri`")
+        ptr[key] = t.data_ptr() if t is not None else None
+    extra = {}
+    for key, t, dt in (("incidence", incidence, torch.float32), ("drop", drop, torch.uint8)):
+        if t is True:
+            t = torch.empty((n,), dtype=dt, device=dev)
+        elif t is False:
+            t = None
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != dev):
+            raise ValueError(f"{key}: contiguous {dt} CUDA tensor [n] on the device of `tri`")
+        extra[key] = t
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    args = model.args()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lt_return_model_dev(
+            scene._h, rays.data_ptr(), n, C.byref(args), int(scan) & 0xFFFFFFFF, ptr["endpoints"], ptr["endcolors"], ptr["range"],
+            ptr["endrem"], ptr["tri"], extra["incidence"].data_ptr() if extra["incidence"] is not None else None,
+            extra["drop"].data_ptr() if extra["drop"] is not None else None,
+            _lib.LT_TRACE_LABEL_IMAGE if label_image else 0, C.c_void_p(st.cuda_stream)), "lt_return_model_dev")
+    return extra
+
+
 def pack_scan(back_points, label_image, remissions, index=None):
     """Filtering + packing of ``MultiSemLaserScan.write`` (auxiliary/laserscan.py:1133-1160): returns
     ``(bin [N,4] float32, label [N] uint32)`` -- byte-for-byte what the reference writes to

@@ -297,6 +297,7 @@ class RaySet:
         self._lib = _lib.load()
         self.n_rays = (rays.numel() // 3 // int(H)) * int(H)
         self.H = int(H)
+        self.rays = rays   # (the tensor the set was built from: what a return model reads its directions from)
         st = torch.cuda.current_stream(rays.device) if stream is None else stream
         h = C.c_void_p()
         with torch.cuda.device(rays.device):

@@ -30,6 +30,13 @@ from .evaluate import Evaluator
 from .ingest import ScanIngest, SequenceSource
 
 ADAPTIONS = ("cp", "mesh", "mergemesh")
+#: what the codes of a return model's ``drop`` image mean, in code order (``return_totals``, the CLI's closing line)
+RETURN_CODES = ("kept", "no hit", "below min_range", "beyond max_range", "beyond max_incidence", "dropped at random")
+
+
+def format_return_totals(totals):
+    """the CLI's closing line of a run with a return model: ``Returns: kept N, no hit N, ...`` in code order"""
+    return "Returns: " + ", ".join(f"{name} {int(n)}" for name, n in zip(RETURN_CODES, totals))
 
 
 def sensor_tuple(s):
@@ -111,7 +118,12 @@ class SequenceTransfer:
     (``SensorModel.target_model()``, kept as ``target_model``; its fields ``beam_table``, ``sector`` and ``beam_azimuth`` are
     attributes here too, ``None``: none) to every chain's ``DeviceDeform``.  With a beam table (``beam_model`` tells) the source
     scan, projected by the evenly spaced model, cannot be compared row for row, with a sector (``azimuth_model`` tells) not
-    column for column: ``evaluate`` then behaves as for a mounted target.  A source sensor with any of the three is refused."""
+    column for column: ``evaluate`` then behaves as for a mounted target.  A source sensor with any of the three is refused.
+    A target ``SensorModel`` with a ``return_model`` block (kept as ``returns``; ``None``: none) has it applied to every
+    output scan of ``mesh`` / ``mergemesh`` behind its render, with the scan's FILE index as the random rule's ``scan`` --
+    evaluation and the written files see what the target sensor sees --; the cells per code are summed on the device and
+    read once at the end of :meth:`run` (``summary["return_totals"]``, six numbers in :data:`RETURN_CODES`' order).  ``cp``
+    renders no surface: with such a target it raises ``ValueError``; so does a source sensor with the key."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -130,6 +142,10 @@ class SequenceTransfer:
         self.beam_table, self.sector, self.beam_azimuth = m.beam_table, m.sector, m.beam_azimuth
         self.beam_model = "linear" if m.beam_table is None else "table"
         self.azimuth_model = "full" if m.sector is None else "sector"
+        self.returns = getattr(target_sensor, "return_model", lambda: None)()
+        if self.returns is not None and self.adaption == "cp":
+            raise ValueError("adaption cp renders no surface (no hit triangle, no incidence angle): the target sensor's "
+                             "return_model cannot be applied -- use mesh or mergemesh, or a target file without the key")
         self.chains = 1 if self.adaption == "cp" else int(chains)     # `cp` always runs on one chain
         self.fusion, self.out_dir = fusion, out_dir
         self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
@@ -175,7 +191,8 @@ class SequenceTransfer:
                 self._mm = MergeMeshState(self.vol_bnds, approach.voxel_size, idx)
             rayset = None
             every = dict(beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
-                         transformation=self.mount, t_beam_table=m.beam_table, t_sector=m.sector, t_beam_azimuth=m.beam_azimuth)
+                         transformation=self.mount, t_beam_table=m.beam_table, t_sector=m.sector, t_beam_azimuth=m.beam_azimuth,
+                         returns=self.returns)
             for c in range(self.chains):
                 if self.adaption == "cp":
                     dd = DeviceDeform(self.source_sensor, self.target_sensor, None, **every)
@@ -184,7 +201,7 @@ class SequenceTransfer:
                                       None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
                                       mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm, **every)
                     rayset = dd.rayset
-                ch = dict(dd=dd, ev=None, q=None, thread=None,
+                ch = dict(dd=dd, ev=None, q=None, thread=None, totals=None, codes=None,
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
                 if self.evaluate:
                     ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx)
@@ -219,10 +236,15 @@ class SequenceTransfer:
                 if self.adaption == "cp":
                     out = dd.cp(clouds, pack=False)
                 elif self.adaption == "mesh":
-                    out = dd.mesh(clouds, pack=False)
+                    out = dd.mesh(clouds, pack=False, scan_index=job["idx"])
                 else:
-                    out = dd.mergemesh(clouds, pack=False, seq=job["k"])
+                    out = dd.mergemesh(clouds, pack=False, seq=job["k"], scan_index=job["idx"])
                     job["bnds_after"] = np.array(out["vol_bnds_after"]).reshape(3, 2)
+                if self.returns is not None:         # cells per code, summed on the chain's stream: read once, in run()
+                    if ch["totals"] is None:
+                        ch["codes"] = torch.arange(len(RETURN_CODES), dtype=torch.uint8, device=self.device)
+                        ch["totals"] = torch.zeros(len(RETURN_CODES), dtype=torch.int64, device=self.device)
+                    ch["totals"] += (out["drop"].unsqueeze(1) == ch["codes"]).sum(0)
                 if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
                     src = ch["ev"].source_scan(*job["raw"], stream=st)
                     job["record"] = ch["ev"].compare(src, out["label"], out["range"], stream=st)
@@ -328,7 +350,15 @@ class SequenceTransfer:
             for job in pending:                          # (a failure or an abandoned generator: let what is queued finish)
                 job["done"].wait()
                 job["written"].wait()
-            self.summary = dict(scans=n_done, chains=self.chains, adaption=self.adaption, fusion=self.fusion,
+            totals = None
+            if self.returns is not None:
+                totals = [0] * len(RETURN_CODES)
+                for ch in self._chains:
+                    if ch["totals"] is not None:
+                        ch["stream"].synchronize()
+                        totals = [a + int(b) for a, b in zip(totals, ch["totals"].cpu().tolist())]
+                        ch["totals"] = None          # (the next run starts its own)
+            self.summary = dict(return_totals=totals, scans=n_done, chains=self.chains, adaption=self.adaption, fusion=self.fusion,
                                 mounted=self.mounted, beam_model=self.beam_model, azimuth_model=self.azimuth_model,
                                 beam_azimuth=self.beam_azimuth is not None,
                                 mm_stats=dict(self._mm.stats) if self._mm is not None else None,
