@@ -860,6 +860,7 @@ int lt_build_launch(lt_scene* s, hipStream_t stream, lt_stats* stats) {
     int cur = 0;
     lt_sort_pairs(s->keys, s->vals, s->hist, n, 30, stream, &cur);
     // sorted data is in buffer `cur`
+    s->sorted_buf = cur;
     LT_MARK();  // 3
     hipLaunchKernelGGL(k_gather, dim3(cdiv(np, 256)), dim3(256), 0, stream, s->verts, s->faces, s->n_verts, n, np,
                        s->vals[cur], s->params, s->tris, s->seg);
@@ -922,5 +923,68 @@ extern "C" int lt_debug_nodes4_get(lt_scene* s, void* out, int n_nodes) {
   LT_HIP(hipSetDevice(s->device));
   LT_HIP(hipDeviceSynchronize());
   LT_HIP(hipMemcpy(out, s->nodes4, (size_t)n_nodes * 128, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+// debug helper: lt_sort_pairs on host arrays.  keys_out / vals_out receive the n pairs in the stable order of the low
+// `key_bits` bits of the keys (the whole 32-bit key is carried along).  Workspace of its own, default stream.
+struct sort_ws {
+  uint32_t* keys[2];
+  uint32_t* vals[2];
+  uint32_t* hist;
+};
+static int debug_sort_run(sort_ws& w, const uint32_t* keys, const uint32_t* vals, int n, int key_bits,
+                          uint32_t* keys_out, uint32_t* vals_out) {
+  const size_t bytes = (size_t)n * sizeof(uint32_t);
+  for (int k = 0; k < 2; ++k) {
+    LT_HIP(hipMalloc((void**)&w.keys[k], bytes));
+    LT_HIP(hipMalloc((void**)&w.vals[k], bytes));
+  }
+  LT_HIP(hipMalloc((void**)&w.hist, ((size_t)LT_RD * cdiv(n, LT_SORT_TILE) + LT_RD) * sizeof(uint32_t)));
+  LT_HIP(hipMemcpy(w.keys[0], keys, bytes, hipMemcpyHostToDevice));
+  LT_HIP(hipMemcpy(w.vals[0], vals, bytes, hipMemcpyHostToDevice));
+  int cur = 0;
+  lt_sort_pairs(w.keys, w.vals, w.hist, n, key_bits, (hipStream_t)0, &cur);
+  LT_HIP(hipGetLastError());
+  LT_HIP(hipDeviceSynchronize());
+  LT_HIP(hipMemcpy(keys_out, w.keys[cur], bytes, hipMemcpyDeviceToHost));
+  LT_HIP(hipMemcpy(vals_out, w.vals[cur], bytes, hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+extern "C" int lt_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, int n, int key_bits, uint32_t* keys_out,
+                                   uint32_t* vals_out) {
+  if (n < 0 || key_bits < 1 || key_bits > 32 || (n > 0 && (!keys || !vals || !keys_out || !vals_out))) {
+    lt_set_error("lt_debug_sort_pairs: n >= 0, 1 <= key_bits <= 32 and non-NULL arrays are required");
+    return LT_ERR_INVALID_ARG;
+  }
+  if (n == 0) return LT_OK;
+  sort_ws w = {{nullptr, nullptr}, {nullptr, nullptr}, nullptr};
+  const int rc = debug_sort_run(w, keys, vals, n, key_bits, keys_out, vals_out);
+  for (int k = 0; k < 2; ++k) {
+    if (w.keys[k]) (void)hipFree(w.keys[k]);
+    if (w.vals[k]) (void)hipFree(w.vals[k]);
+  }
+  if (w.hist) (void)hipFree(w.hist);
+  return rc;
+}
+
+// debug helper: one product of the scene's last build.  what = 0: the n sorted keys; 1: the sorted triangle records (3 n
+// float4); 2: params (5 floats); 3: the n binary nodes (64 B each; written by the LIDARHIP_TRACE=binary build only); 4: the
+// counter of the nodes k_hierarchy4 queued for k_hierarchy4_big (one word).
+extern "C" int lt_debug_build_get(lt_scene* s, int what, void* out, int n) {
+  if (!s || !out || !s->built || n < 0 || n > s->cap_faces || what < 0 || what > 4) return LT_ERR_INVALID_ARG;
+  LT_HIP(hipSetDevice(s->device));
+  LT_HIP(hipDeviceSynchronize());
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (what) {
+    case 0: src = s->keys[s->sorted_buf]; bytes = (size_t)n * sizeof(uint32_t); break;
+    case 1: src = s->tris; bytes = (size_t)n * 3 * sizeof(float4); break;
+    case 2: src = s->params; bytes = 5 * sizeof(float); break;
+    case 3: src = s->nodes; bytes = (size_t)n * 4 * sizeof(float4); break;
+    default: src = s->flags + 2; bytes = sizeof(unsigned); break;
+  }
+  if (!src) return LT_ERR_INVALID_ARG;  // (a scene built with no face has no workspace)
+  if (bytes) LT_HIP(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
   return LT_OK;
 }

@@ -112,6 +112,7 @@ struct lt_scene {
   int* sc_large_count;          // [4]: [0] queued big triangles, [1] queued slices; reset by k_sc_resolve
   int sc_cap_cells, sc_cap_queue;
   int built;
+  int sorted_buf;        // which of keys[] / vals[] holds the sorted pairs of the last build (lt_sort_pairs' *out_buffer)
   hipStream_t last_stream;
   hipEvent_t probe[2];   // caller's events to record around the dominant kernel of the next cast (one shot)
   hipEvent_t ev[10];
