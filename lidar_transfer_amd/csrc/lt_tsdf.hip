@@ -314,7 +314,9 @@ __device__ __forceinline__ int tsdf_voxel(int voxel_idx, const tsdf_volume& Vol,
 // approximate depth (rsq), approximate pitch (odd polynomial, |s| <= 0.5: error < 1e-6 rad) -> the one or two image rows the
 // exact projection can choose (+-0.25 row against an error below 0.01) -> their depth / colour with a margin far above
 // the approximation errors.  CONSERVATIVE: it may only say yes too often; every candidate then runs the reference's
-// expressions (tsdf_voxel), which decide.
+// expressions (tsdf_voxel), which decide.  For any positive obs_weight: the test is only asked about FRESH voxels (weight 0,
+// colour 0), whose update depends on the pixel's colour and the sign of dist alone -- obs_weight enters the value written, never
+// whether a fresh voxel is written (tests/test_tsdf_update_gpu.py: weights 0.25 .. 2^24 against the dense restatement).
 __device__ __forceinline__ bool tsdf_band_candidate(int z, const col_plain& C, const tsdf_volume& Vol, const tsdf_view& Vw,
                                                     float kA, float kB, const float2* __restrict__ dct) {
   const int im_h = Vw.im_h;
@@ -955,6 +957,9 @@ __device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view
       // can write lies in that observation's interval while it still holds its initial values, and once written (by an
       // earlier observation: inside an earlier interval) anywhere in front of ITS band: a band further out extends the
       // union's upper end, and the voxels in front of it that earlier observations wrote are inside the union already
+      // (any positive obs_weight: it only decides whether `dist < weight` lets a WRITTEN voxel change hands, and a written
+      // voxel lies inside an earlier interval, hence inside the union; a voxel still holding its initial values has weight 0
+      // and is written through colour 0 or dist < 0 whatever the weight -- tests/test_tsdf_update_gpu.py)
       bool any = false;
       float d_lo = 3e38f, d_hi = 0.f;
       if constexpr (MULTI) {

@@ -4,7 +4,11 @@ Parity status: the reference's `integrate` exists only as a CUDA kernel inside a
 (auxiliary/fusion_lidar.py:66-229).  tests/test_tsdf_ref_kernel_gpu.py pins the product to that source compiled for
 gfx950, bit for bit; here the product is checked against our C restatement of it (oracle/lt_tsdf_oracle.c -- libm's
 atan2f / asinf / sqrtf instead of the device library's: boundary voxels and last ulps differ), against the dense HIP
-restatement (bit for bit), and the plain-average branch against golden volumes of the reference's own numpy CPU mode (F8)."""
+restatement (bit for bit), and the plain-average branch against golden volumes of the reference's own numpy CPU mode (F8).
+
+This file owns the SHAPES (wedge tables, staging limits, partial chunks, volumes beyond 2^24 voxels) and feeds obs_weight = 1
+and one colour channel throughout; the VALUES of the update -- other weights, the class-aware comparison where it rejects,
+rounding ties, the clamp, three channels -- are pinned in tests/test_tsdf_update_gpu.py."""
 import os
 
 import numpy as np
