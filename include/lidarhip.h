@@ -754,6 +754,50 @@ int lt_source_scan_dev(lt_evaluator* ev, const lt_raw_scan* scan, const int* ign
                        double fov_down, int H, int W, const float* color_lut, int lut_len, const lt_source_images* out,
                        void* stream);
 
+/* The TARGET sensor's model as lt_target_view_dev reads it (HOST).  The arrays are what lt_range_projection_batch_dev takes
+ * for the same flags: `rows` is its beam_angles under LT_PROJ_BEAM_ROWS, `az_rad` what lt_projector_set_beam_azimuth takes,
+ * yaw_center / span what lt_projector_set_sector takes, with the same ranges (1 <= H <= 511 with a table, |az| <= pi / 2,
+ * |yaw_center| <= pi, 0 < span < 2 pi). */
+typedef struct lt_view_model {
+  double fov_up, fov_down;  /* degrees, the TARGET's                                                     */
+  int H, W;                 /* the TARGET's image                                                         */
+  unsigned flags;           /* 0 or a valid combination of LT_PROJ_BEAM_ROWS | LT_PROJ_SECTOR |          */
+                            /* LT_PROJ_BEAM_AZIMUTH (LT_PROJ_NEW | LT_PROJ_REMOVE are implied)            */
+  const double* rows;       /* HOST: Brad[H] then halfw[H] with LT_PROJ_BEAM_ROWS, else NULL              */
+  const double* az_rad;     /* HOST [H] with LT_PROJ_BEAM_AZIMUTH, else NULL                              */
+  double yaw_center, span;  /* radians, with LT_PROJ_SECTOR                                               */
+} lt_view_model;
+
+/* lt_target_view_dev -- the TARGET VIEW of one resident raw scan: the primary source scan seen through the target sensor's
+ * model from the target's pose, i.e. what `cp` with number_of_scans: 1 and no `moving` list puts into the target image
+ * (lt_ingest_scans_dev of the one scan with poses[0] = T and back = NULL, then lt_range_projection_batch_dev under the
+ * model's flags | LT_PROJ_NEW | LT_PROJ_REMOVE without beam angles), made in one pass from the file bytes, in the shape
+ * lt_compare_record_dev consumes.  On the same lt_evaluator as lt_source_scan_dev (one key workspace, calls in stream
+ * order).  Per raw point i, in file order:
+ *   1. l = label & 0xFFFF; l >= lut_len is counted into bad_labels
+ *   2. dropped if l in ignore (the list-or-bitmap rule of lt_source_scan_dev)
+ *   3. x, y, z are widened from float32 to float64.  With T: every row as ((m0*x + m1*y) + m2*z) + m3, products and sums
+ *      rounded on their own (step 5 of lt_ingest_scans_dev); the last row of T is not read.  T == NULL: the widened values
+ *      themselves, not a product with the identity (a -0.0 keeps its sign)
+ *   4. the float64 projection of the model's flags with both drops (depth 0, NaN; outside the rows' keep rule; outside the
+ *      sector).  Linear rows have NO hard-coded beam angles, as the source reference scan has none (lidar_deform.py:396);
+ *      pi, |fov_down| and fov in radians as lt_range_projection_batch_dev derives them for float64 clouds.  A dropped point
+ *      does not bid
+ *   5. winner per cell: do_range_projection_new's (laserscan.py:366, :376) -- the first point of the minimum's float32
+ *      bucket unless points of that bucket lie below the float32 value, then the last of those.  The raw index stands for
+ *      the kept index because the removals keep the file order
+ *   6. the cell receives the winner's float32 depth, xyzr[3], l, and black = (sum(color_lut[l]) == 0); empty: -1, -1, 0, 1
+ * T: HOST [16] row-major, x_target = T x_source, or NULL.  The model's doubles live in a device buffer of the evaluator and
+ * are uploaded, in stream order, only when they differ from the previous call's: the per-scan calls of a sequence copy
+ * nothing and wait for nothing.  LT_ERR_INVALID_ARG before any device work: NULL handles, n > 0 without buffers, xyzr not
+ * 16-byte aligned, a class outside 0 .. 65535, H or W <= 0 or H * W beyond the key range, flags that do not combine
+ * (LT_PROJ_BEAM_AZIMUTH without LT_PROJ_BEAM_ROWS), a flag without its array, values outside the ranges above.
+ * ignore, color_lut, out: as lt_source_scan_dev.  Asynchronous on `stream`; the host reads nothing back. */
+int lt_target_view_dev(lt_evaluator* ev, const lt_raw_scan* scan, const int* ignore, int n_ignore,
+                       const double* T /* HOST [16] row-major, x_target = T x_source; NULL: none */,
+                       const lt_view_model* model, const float* color_lut, int lut_len, const lt_source_images* out,
+                       void* stream);
+
 /* What compare() + iouEval.addBatch leave of one output scan, compacted on the device. */
 typedef struct lt_compare_record {
   int status;              /* 0, LT_COMPARE_OVERFLOW or LT_COMPARE_LABEL_RANGE: then only sq_sum / n_cells are meaningful */

@@ -16,8 +16,11 @@ every row of ``--log`` then carries ``"beam_azimuth": true`` as well.  A target 
 of ``mesh`` / ``mergemesh`` (``cp`` is refused); the run closes with one line ``Returns: kept N, no hit N, ...``, the cells per
 code over all its scans, which the ``--log`` summary carries as ``return_totals``.  The tool
 is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
-``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  A missing dataset, labels or output
-folder ends with a message and exit status 1."""
+``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  ``--evaluate target`` compares for
+every target -- mounted, with a table, a sector, offsets, a return model, another image size -- against the source scan seen
+through the target's model from its pose: the three lines are printed per scan and every row of ``--log`` carries
+``"evaluate": "target"``, ``n_compared`` and ``MSE_compared``; ``--evaluate off`` compares nothing.  A missing dataset, labels
+or output folder ends with a message and exit status 1."""
 from __future__ import annotations
 
 import argparse
@@ -41,6 +44,10 @@ def build_parser():
     p.add_argument("--fusion", choices=("cuda", "numpy"), default="cuda", help="Arithmetic of the TSDF fusion. Defaults to %(default)s")
     p.add_argument("--resume", action="store_true", help="Skip scans whose two output files exist.")
     p.add_argument("--log", type=str, default="", help="Write one JSON object per scan to this file.")
+    p.add_argument("--evaluate", choices=("auto", "target", "off"), default="auto",
+                   help="auto: compare with the source scan when both images have one size and the target has no model of its "
+                        "own; target: compare with the source scan seen through the target's model, for every target; off: "
+                        "compare nothing. Defaults to %(default)s")
     return p
 
 
@@ -85,7 +92,8 @@ def main(argv=None):
     log = open(args.log, "w") if args.log else None
     try:
         with SequenceTransfer((args.dataset, args.sequence), approach, source, target, out_dir=args.output if args.write else None,
-                              chains=args.chains, fusion=args.fusion, copy_files=(target_path, args.config)) as tr:
+                              chains=args.chains, fusion=args.fusion, copy_files=(target_path, args.config),
+                              evaluate={"auto": None, "target": "target", "off": False}[args.evaluate]) as tr:
             n_files = len(tr.source)
             for rec in tr.run(offset=args.offset, one_scan=args.one_scan, resume=args.resume):
                 if rec["m_iou"] is not None:
@@ -95,6 +103,8 @@ def main(argv=None):
                 print("#" * 30, args.sequence, "-", rec["idx"], "/", n_files, "#" * 30, flush=True)
                 if log is not None:
                     row = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in rec.items()}
+                    if tr.evaluate_mode == "target":
+                        row["evaluate"] = "target"
                     if tr.mounted:
                         row["mounted"] = True
                     if tr.beam_model != "linear":

@@ -49,7 +49,7 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_reverse_projection_beams_dev", "lt_create_rays_sector_dev", "lt_reverse_projection_sector_dev",
            "lt_rayset_create_grid_dev", "lt_projector_set_sector", "lt_range_projection_set_sector",
            "lt_create_rays_beams_az_dev", "lt_projector_set_beam_azimuth", "lt_range_projection_set_beam_azimuth",
-           "lt_reverse_projection_beams_az_dev", "lt_return_model_dev"]
+           "lt_reverse_projection_beams_az_dev", "lt_return_model_dev", "lt_target_view_dev"]
 LT_ABI_VERSION = 9   # include/lidarhip.h: layout version of the structs mirrored below
 
 
@@ -95,6 +95,12 @@ class IngestOut(C.Structure):
 class SourceImages(C.Structure):
     """Mirror of ``lt_source_images``: the [H*W] DEVICE images of the source reference scan; NULL = not wanted."""
     _fields_ = [(k, C.c_void_p) for k in ("range", "rem", "label", "black", "bad_labels")]
+
+
+class ViewModel(C.Structure):
+    """Mirror of ``lt_view_model``: the TARGET sensor's model as ``lt_target_view_dev`` reads it (HOST arrays)."""
+    _fields_ = [("fov_up", C.c_double), ("fov_down", C.c_double), ("H", C.c_int), ("W", C.c_int), ("flags", C.c_uint),
+                ("rows", C.c_void_p), ("az_rad", C.c_void_p), ("yaw_center", C.c_double), ("span", C.c_double)]
 
 
 class CompareRecord(C.Structure):
@@ -257,7 +263,10 @@ def load():
     lib.lt_source_scan_dev.argtypes = [vp, C.POINTER(RawScan), ip, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_int,
                                        C.POINTER(SourceImages), vp]
     lib.lt_compare_record_dev.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
-    for name in ("lt_evaluator_create", "lt_evaluator_destroy", "lt_source_scan_dev", "lt_compare_record_dev"):
+    lib.lt_target_view_dev.argtypes = [vp, C.POINTER(RawScan), ip, C.c_int, C.POINTER(C.c_double), C.POINTER(ViewModel), vp, C.c_int,
+                                       C.POINTER(SourceImages), vp]
+    for name in ("lt_evaluator_create", "lt_evaluator_destroy", "lt_source_scan_dev", "lt_compare_record_dev",
+                 "lt_target_view_dev"):
         getattr(lib, name).restype = C.c_int
     lib.lt_create_rays_pose_dev.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), vp, vp]
     lib.lt_create_rays_pose_dev.restype = C.c_int

@@ -3,6 +3,10 @@
 //                            remove_classes(ignore), do_range_projection(fov, remove=True) on the float32 file points,
 //                            do_label_projection; two kernels (a thread per raw point: ONE 64-bit atomicMin per kept point;
 //                            a thread per cell: decode the winner, gather, re-arm the key)
+//   * lt_target_view_dev     the same raw scan seen through the TARGET sensor's model from the target's pose -- what `cp` with
+//                            one scan would put into the target image: widened to float64, optionally transformed, through
+//                            project_model<double, ...> (every target model), the `_new` variant's z-min key; its own project
+//                            kernel, then k_src_resolve as it is
 //   * lt_compare_record_dev  compare() (auxiliary/laserscan.py:1181-1301) + iouEval.addBatch (np_ioueval.py:31-47) of one
 //                            output scan into a small fixed-size record; two kernels (a thread per cell: masks, squared range
 //                            difference, per-wave pair counting with ballots into an n_labels^2 workspace, one partial sum per
@@ -34,6 +38,9 @@ struct lt_evaluator {
   size_t cap_blocks = 0;
   double* partial = nullptr;            // [cap_blocks] per-workgroup sums of squared range differences
   lt_compare_record* rec = nullptr;     // device staging of the record
+  double* model = nullptr;              // [LT_MODEL_DOUBLES] the target view's sensor model (model_table), allocated by its first call
+  double model_host[LT_MODEL_DOUBLES];  // ... as uploaded last: a call whose model has these bytes copies nothing
+  int n_model = -1;
   std::mutex mu;
 };
 
@@ -66,6 +73,41 @@ __global__ __launch_bounds__(256) void k_src_project(const SrcArgs a, const unsi
       const float4 p = a.xyzr[i];                   // one 16-byte load
       const proj_out<float> o = project_point<float>(p.x, p.y, p.z, pi_t, abs_fov_down, fov, H, W, nullptr, 0, true, true);
       if (o.cell >= 0) atomicMin(&key[o.cell], pb_key<float>(o.depth, i));
+    }
+  }
+  const unsigned long long m = __ballot(outside_lut);
+  if (m && (threadIdx.x & 63) == 0) atomicAdd(bad, (unsigned)__popcll(m));
+}
+
+// The target view's transform: rows 0..2 of T (x_target = T x_source), `on` == 0: none -- the widened values themselves, not
+// a product with the identity (-0.0 keeps its sign).
+struct ViewXf { double m[12]; int on; };
+
+__device__ __forceinline__ double view_row(const double* __restrict__ m, double x, double y, double z) {
+  return ((m[0] * x + m[1] * y) + m[2] * z) + m[3];  // step 5 of lt_ingest_scans_dev: every product and sum rounded on its own
+}
+
+// a thread per raw point, as k_src_project: the point in float64, in the target's frame, through the target's model (`tab`:
+// model_table's doubles, no hard-coded beam angles); the `_new` variant's key (pb_key<double>: the rounded-up bucket)
+template <int BEAMS, int SECTOR, int AZ>
+__global__ __launch_bounds__(256) void k_view_project(const SrcArgs a, const unsigned* __restrict__ bitmap, const ViewXf T,
+                                                      double pi_t, double abs_fov_down, double fov, int H, int W,
+                                                      const double* __restrict__ tab, unsigned long long* __restrict__ key,
+                                                      unsigned* __restrict__ bad) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool outside_lut = false;
+  if (i < a.n) {
+    const unsigned l = a.label[i] & 0xFFFFu;
+    outside_lut = l >= (unsigned)a.lut_len;
+    if (!src_dropped(a, bitmap, l)) {
+      const float4 p = a.xyzr[i];                   // one 16-byte load
+      double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+      if (T.on) {
+        const double tx = view_row(T.m, x, y, z), ty = view_row(T.m + 4, x, y, z), tz = view_row(T.m + 8, x, y, z);
+        x = tx; y = ty; z = tz;
+      }
+      const proj_out<double> o = project_model<double, BEAMS, SECTOR, AZ>(x, y, z, pi_t, abs_fov_down, fov, H, W, tab, 0, true, true);
+      if (o.cell >= 0) atomicMin(&key[o.cell], pb_key<double>(o.depth, i));
     }
   }
   const unsigned long long m = __ballot(outside_lut);
@@ -215,7 +257,7 @@ __global__ __launch_bounds__(256) void k_cmp_record(int NL, unsigned epoch, unsi
 }
 
 void ev_free(lt_evaluator* e) {
-  void* ps[] = {e->key, e->bitmap, e->bad, e->conf, e->seen, e->partial, e->rec};
+  void* ps[] = {e->key, e->bitmap, e->bad, e->conf, e->seen, e->partial, e->rec, e->model};
   for (void* p : ps)
     if (p) (void)hipFree(p);
 }
@@ -324,6 +366,100 @@ extern "C" int lt_source_scan_dev(lt_evaluator* e, const lt_raw_scan* scan, cons
   if (a.n > 0)
     hipLaunchKernelGGL(k_src_project, dim3((a.n + 255) / 256), dim3(256), 0, st, a, (const unsigned*)e->bitmap, pi_t, afd, fov,
                        H, W, e->key, e->bad);
+  hipLaunchKernelGGL(k_src_resolve, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a, H, W, color_lut, e->key,
+                     e->bad, *out);
+  LT_HIP(hipGetLastError());
+  e->armed = true;  // k_src_resolve re-armed every cell it looked at
+  return LT_OK;
+}
+
+extern "C" int lt_target_view_dev(lt_evaluator* e, const lt_raw_scan* scan, const int* ignore, int n_ignore, const double* T,
+                                  const lt_view_model* vm, const float* color_lut, int lut_len, const lt_source_images* out,
+                                  void* stream) {
+  const unsigned model_bits = LT_PROJ_BEAM_ROWS | LT_PROJ_SECTOR | LT_PROJ_BEAM_AZIMUTH;
+  if (!e || !scan || !vm || !out || scan->n < 0 || (scan->n > 0 && (!scan->xyzr || !scan->label)) ||
+      ((uintptr_t)scan->xyzr & 15u) || n_ignore < 0 || (n_ignore > 0 && !ignore) || vm->H <= 0 || vm->W <= 0 ||
+      (long long)vm->H * vm->W > 0x7fffffffLL - 4096 || (vm->flags & ~model_bits) || lut_len < 0 || (lut_len > 0 && !color_lut)) {
+    lt_set_error("lt_target_view_dev: invalid argument (n=%d H=%d W=%d flags=%u n_ignore=%d lut_len=%d; xyzr must be 16-byte "
+                 "aligned)", scan ? scan->n : -1, vm ? vm->H : -1, vm ? vm->W : -1, vm ? vm->flags : 0u, n_ignore, lut_len);
+    return LT_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < n_ignore; ++k)
+    if (ignore[k] < 0 || ignore[k] > 65535) {
+      lt_set_error("lt_target_view_dev: class %d is outside 0..65535 (labels are masked to 16 bits)", ignore[k]);
+      return LT_ERR_INVALID_ARG;
+    }
+  const int H = vm->H, W = vm->W;
+  const bool rows = (vm->flags & LT_PROJ_BEAM_ROWS) != 0, sector = (vm->flags & LT_PROJ_SECTOR) != 0;
+  const bool azimuth = (vm->flags & LT_PROJ_BEAM_AZIMUTH) != 0;
+  if (sector && !sector_ok("lt_target_view_dev", vm->yaw_center, vm->span)) return LT_ERR_INVALID_ARG;
+  if (azimuth && !beam_azimuth_ok("lt_target_view_dev", vm->az_rad, H)) return LT_ERR_INVALID_ARG;
+  // the model's doubles, laid out and held against the flags where the projections' are; no hard-coded beam angles
+  const double sec[2] = {vm->yaw_center, vm->span};
+  double tab[LT_MODEL_DOUBLES];
+  const int n_tab = model_table("lt_target_view_dev", rows ? vm->rows : nullptr, rows ? H : 0,
+                                vm->flags | LT_PROJ_NEW | LT_PROJ_REMOVE, vm->fov_up, vm->fov_down, H, sector ? sec : nullptr,
+                                azimuth ? vm->az_rad : nullptr, H, tab);
+  if (n_tab < 0) return LT_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(e->mu);
+  LT_HIP(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t cells = (size_t)H * W;
+  if (cells > e->cap_cells) {
+    if (e->key) {
+      LT_HIP(hipStreamSynchronize(st));
+      (void)hipFree(e->key);
+      e->key = nullptr;
+      e->cap_cells = 0;
+    }
+    LT_HIP(hipMalloc((void**)&e->key, cells * sizeof(unsigned long long)));
+    e->cap_cells = cells;
+    e->armed = false;
+  }
+  if (!e->model) LT_HIP(hipMalloc((void**)&e->model, LT_MODEL_DOUBLES * sizeof(double)));
+  if (!e->armed) {  // first use, or the previous call failed half way
+    LT_HIP(hipMemsetAsync(e->key, 0xFF, e->cap_cells * sizeof(unsigned long long), st));
+    LT_HIP(hipMemsetAsync(e->bad, 0, sizeof(unsigned), st));
+  }
+  e->armed = false;
+  if (n_tab > 0 && (n_tab != e->n_model || memcmp(e->model_host, tab, (size_t)n_tab * sizeof(double)) != 0)) {
+    // read by the kernels of EARLIER calls on this stream: the copy is stream-ordered behind them; a pageable source is
+    // staged by the runtime before the call returns.  A sequence's calls bring the same bytes and copy nothing.
+    e->n_model = -1;
+    memcpy(e->model_host, tab, (size_t)n_tab * sizeof(double));
+    LT_HIP(hipMemcpyAsync(e->model, e->model_host, (size_t)n_tab * sizeof(double), hipMemcpyHostToDevice, st));
+    e->n_model = n_tab;
+  }
+  SrcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.xyzr = (const float4*)scan->xyzr;
+  a.label = scan->label;
+  a.n = scan->n;
+  a.lut_len = lut_len;
+  a.use_bitmap = n_ignore > LT_INGEST_LIST_ARGS;
+  if (a.use_bitmap) {
+    unsigned bits[LT_EV_BITMAP_WORDS];
+    memset(bits, 0, sizeof(bits));
+    for (int k = 0; k < n_ignore; ++k) bits[ignore[k] >> 5] |= 1u << (ignore[k] & 31);
+    LT_HIP(hipMemcpyAsync(e->bitmap, bits, sizeof(bits), hipMemcpyHostToDevice, st));
+  } else {
+    a.n_ign = n_ignore;
+    for (int k = 0; k < n_ignore; ++k) a.ign[k] = (unsigned short)ignore[k];
+  }
+  ViewXf xf;
+  memset(&xf, 0, sizeof(xf));
+  xf.on = T != nullptr;
+  if (T) memcpy(xf.m, T, sizeof(xf.m));  // (the last row is not read)
+  // laser parameters as lt_range_projection_batch_dev derives them for float64 clouds (laserscan.py:207-209, python floats)
+  const double fd = vm->fov_down / 180.0 * M_PI, fu = vm->fov_up / 180.0 * M_PI;
+  const double afd = fabs(fd), fov = fabs(fd) + fabs(fu);
+  if (a.n > 0) {
+#define LT_VIEW_PROJECT(B, S, AZ)                                                                                     \
+  hipLaunchKernelGGL((k_view_project<B, S, AZ>), dim3((a.n + 255) / 256), dim3(256), 0, st, a, (const unsigned*)e->bitmap, \
+                     xf, (double)M_PI, afd, fov, H, W, (const double*)e->model, e->key, e->bad)
+    LT_FOR_MODEL(rows, sector, azimuth, LT_VIEW_PROJECT);
+#undef LT_VIEW_PROJECT
+  }
   hipLaunchKernelGGL(k_src_resolve, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a, H, W, color_lut, e->key,
                      e->bad, *out);
   LT_HIP(hipGetLastError());

@@ -40,6 +40,13 @@ int lt_cu_count(int device);
 // doubles of the sensor model a projection uploads, at most: a table of 511 rows (Brad, halfw, the field of view), its
 // azimuth offsets and a sector
 #define LT_MODEL_DOUBLES 1540
+// The doubles of a sensor model as project_model reads them, laid out and checked in ONE place (lt_project.hip, where the
+// layout is described): the projections' and the target view's (lt_evaluate.hip).  model_table returns their number, -1 when
+// the arguments do not fit the flags; the other two hold a sector and a set of azimuth offsets against their ranges.
+int model_table(const char* who, const double* beam_angles, int n_beams, unsigned flags, double fov_up_deg,
+                double fov_down_deg, int H, const double* sec, const double* az, int n_az, double* tab);
+bool sector_ok(const char* who, double yaw_center, double span);
+bool beam_azimuth_ok(const char* who, const double* az, int n);
 
 // ---- device data layout -----------------------------------------------------------------------
 // Sorted triangle record, 48 B = 3 x float4 (one 16-B-aligned dwordx4 load each):

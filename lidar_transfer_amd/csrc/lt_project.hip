@@ -171,8 +171,9 @@ extern "C" int lt_create_rays_beams_az_dev(const double* beams_deg, const double
 //   LT_PROJ_SECTOR        behind either (and the offsets), the two numbers of the sector -- the yaw of its middle (|.| <= pi)
 //                         and its width (in (0, 2 pi)), radians -- from lt_projector_set_sector /
 //                         lt_range_projection_set_sector (`sec`, NULL: none was set)
-static int model_table(const char* who, const double* beam_angles, int n_beams, unsigned flags, double fov_up_deg,
-                       double fov_down_deg, int H, const double* sec, const double* az, int n_az, double* tab) {
+// Declared in lt_internal.h with the two checks below: the target view of lt_evaluate.hip lays its model out with them too.
+int model_table(const char* who, const double* beam_angles, int n_beams, unsigned flags, double fov_up_deg,
+                double fov_down_deg, int H, const double* sec, const double* az, int n_az, double* tab) {
   const bool rows = (flags & LT_PROJ_BEAM_ROWS) != 0, sector = (flags & LT_PROJ_SECTOR) != 0;
   const bool azimuth = (flags & LT_PROJ_BEAM_AZIMUTH) != 0;
   const unsigned with_az = LT_PROJ_BEAM_AZIMUTH | LT_PROJ_BEAM_ROWS | LT_PROJ_NEW | LT_PROJ_REMOVE;
@@ -213,7 +214,7 @@ static int model_table(const char* who, const double* beam_angles, int n_beams, 
   return n_rows + (sector ? 2 : 0);
 }
 
-static bool sector_ok(const char* who, double yaw_center, double span) {
+bool sector_ok(const char* who, double yaw_center, double span) {
   if (!(fabs(yaw_center) <= M_PI) || !(span > 0.0 && span < 2 * M_PI)) {
     lt_set_error("%s: yaw of the sector's middle %g (|.| <= pi) and width %g (0 < . < 2 pi), radians", who, yaw_center, span);
     return false;
@@ -222,7 +223,7 @@ static bool sector_ok(const char* who, double yaw_center, double span) {
 }
 
 // the offsets of LT_PROJ_BEAM_AZIMUTH: `az` [n] radians, finite and within +-pi/2, for 1 .. 511 rows; NULL or n == 0 clears
-static bool beam_azimuth_ok(const char* who, const double* az, int n) {
+bool beam_azimuth_ok(const char* who, const double* az, int n) {
   bool ok = (!az || n == 0) || (n > 0 && n <= 511);
   if (ok && az)
     for (int h = 0; h < n; ++h) ok = ok && fabs(az[h]) <= M_PI / 2;  // (NaN: not)

@@ -119,6 +119,12 @@ class SequenceTransfer:
     attributes here too, ``None``: none) to every chain's ``DeviceDeform``.  With a beam table (``beam_model`` tells) the source
     scan, projected by the evenly spaced model, cannot be compared row for row, with a sector (``azimuth_model`` tells) not
     column for column: ``evaluate`` then behaves as for a mounted target.  A source sensor with any of the three is refused.
+    ``evaluate="target"`` compares for EVERY target and adaption instead: each chain's evaluator makes the TARGET VIEW of the
+    primary raw scan -- the scan seen through the target's model from the target's pose (``Evaluator.target_view``, DESIGN
+    7f) -- on the chain's stream and compares it with the chain's ``label`` / ``range``, behind the return model and the
+    frame change; the records then also carry ``n_compared`` (cells that are not background) and ``MSE_compared`` (``sq_sum
+    / n_compared``, ``None`` when 0).  ``evaluate_mode`` tells ``"source"``, ``"target"`` or ``None``; ``evaluate`` is then
+    ``True``.
     A target ``SensorModel`` with a ``return_model`` block (kept as ``returns``; ``None``: none) has it applied to every
     output scan of ``mesh`` / ``mergemesh`` behind its render, with the scan's FILE index as the random rule's ``scan`` --
     evaluation and the written files see what the target sensor sees --; the cells per code are summed on the device and
@@ -151,6 +157,11 @@ class SequenceTransfer:
         self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
         self.copy_files = [p for p in copy_files if p]
         same = self.source_sensor[:2] == self.target_sensor[:2]
+        if isinstance(evaluate, str) and evaluate != "target":
+            raise ValueError(f"evaluate: {evaluate!r} (None, True, False or \"target\")")
+        target_view = isinstance(evaluate, str)
+        if target_view:                              # every target can see the source scan through its own model
+            evaluate = None
         if evaluate and not same:
             raise ValueError("evaluate: source and target images differ in size (lidar_deform.py:416)")
         self.mount = approach.mount()                # (raises ValueError on a transformation that is not rigid)
@@ -166,6 +177,9 @@ class SequenceTransfer:
                              "the source scan's full-circle columns, the two cannot be compared cell by cell")
         self.evaluate = (same and not self.mounted and self.beam_table is None and self.sector is None) \
             if evaluate is None else bool(evaluate)
+        if target_view:
+            self.evaluate = True
+        self.evaluate_mode = "target" if target_view else ("source" if self.evaluate else None)
         need = cache_scans_needed(approach.number_of_scans, self.chains, approach.batch_interval)
         idx = torch.cuda.current_device() if device is None else int(device)
         if isinstance(source_seq, SequenceSource):
@@ -203,7 +217,10 @@ class SequenceTransfer:
                     rayset = dd.rayset
                 ch = dict(dd=dd, ev=None, q=None, thread=None, totals=None, codes=None,
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
-                if self.evaluate:
+                if target_view:
+                    ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx,
+                                         target=self.target_sensor, target_model=m, transformation=self.mount)
+                elif self.evaluate:
                     ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx)
                 if self.chains > 1:
                     ch["q"] = queue.Queue()
@@ -246,7 +263,8 @@ class SequenceTransfer:
                         ch["totals"] = torch.zeros(len(RETURN_CODES), dtype=torch.int64, device=self.device)
                     ch["totals"] += (out["drop"].unsqueeze(1) == ch["codes"]).sum(0)
                 if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
-                    src = ch["ev"].source_scan(*job["raw"], stream=st)
+                    scan = ch["ev"].target_view if self.evaluate_mode == "target" else ch["ev"].source_scan
+                    src = scan(*job["raw"], stream=st)
                     job["record"] = ch["ev"].compare(src, out["label"], out["range"], stream=st)
                     job["images"] = (src, out)
                 b, l = dd.pack_result(out, st)
@@ -306,9 +324,12 @@ class SequenceTransfer:
         rec = dict(idx=job["idx"], n_points=job["n_points"], m_iou=None, m_acc=None, MSE=None, iou=None, skipped=job["skipped"])
         if job["bnds_after"] is not None:
             rec["bnds_after"] = job["bnds_after"]
+        compared = self.evaluate_mode == "target"    # a sparse reference image: how many cells were compared at all
+        if compared:
+            rec.update(n_compared=None, MSE_compared=None)
         if job["record"] is not None:
             try:
-                rec.update(job["record"].metrics(self.nclasses))
+                rec.update(job["record"].metrics(self.nclasses, compared=compared))
             except OverflowError:        # more label values than a record holds: this scan through post.compare
                 from .post import compare
                 src, out = job["images"]
@@ -317,6 +338,9 @@ class SequenceTransfer:
                 m = compare(h(src["label"]), color, h(out["label"]), h(src["range"]), h(out["range"]), h(src["rem"]), h(out["rem"]),
                             self.nclasses)
                 rec.update(m_iou=m["m_iou"], m_acc=m["m_acc"], MSE=m["MSE"], iou=m["iou"])
+                if compared:             # (background: black or label 0 in the source image, as the record counts it)
+                    nc = int(((h(src["black"]) == 0) & (h(src["label"]) != 0)).sum())
+                    rec.update(n_compared=nc, MSE_compared=float(m["range_diff"].astype(np.float64).sum()) / nc if nc else None)
         if self.out_dir is not None and not self._copied and not job["skipped"]:
             base = os.path.join(self.out_dir, "sequences", self.sequence)
             for p in self.copy_files:
@@ -329,7 +353,8 @@ class SequenceTransfer:
     def run(self, offset=0, one_scan=False, resume=False):
         """Generator of one record per output scan, in scan order: ``idx``, ``n_points``, ``m_iou`` / ``m_acc`` / ``MSE`` /
         ``iou`` (``None`` when the run does not compare), ``skipped`` (``resume`` found both output files), ``bnds_after``
-        (mergemesh).  A failed scan or a failed write surfaces as that scan's exception; later scans are not started."""
+        (mergemesh), ``n_compared`` / ``MSE_compared`` (``evaluate="target"`` only).  A failed scan or a failed write surfaces
+        as that scan's exception; later scans are not started."""
         indices = self.scan_indices(offset, one_scan)
         if self._mm is not None:
             self._mm.reset(self._configured_bnds)        # a run is one sequence: it starts from the configured bounds
