@@ -853,6 +853,37 @@ __device__ __forceinline__ int tsdf_voxel_multi(int voxel_idx, const tsdf_volume
 #ifndef LT_PIX_WPE
 #define LT_PIX_WPE 5
 #endif
+// Words of g_pix_dbg (LIDARHIP_DEBUG_TSDF; the VCOUNT = true instantiations only).  [0, 8): pairs, candidate voxels, written
+// voxels, -, three section times, chunks (lt_debug_tsdf_pix_counts).  [8, LT_PIXC_N): which PATHS the launch took
+// (lt_debug_tsdf_pix_paths; tests/test_tsdf_pix_paths_gpu.py).  An item = one group of 64 pixels.  Counted, never read by the
+// kernel: what the counted instantiation reports for an input is what the shipped one does on it.
+#define LT_PIXC_ITEMS 8        // items processed
+#define LT_PIXC_STAGED 9       // ... whose searches ran on the quanta staged in LDS
+#define LT_PIXC_UNSTAGED 10    // ... in global memory (n_stage > LT_PIX_STAGE)
+#define LT_PIXC_AGG 11         // items with pairs whose written ranges were merged in LDS
+#define LT_PIXC_DIRECT 12      // ... marked directly (agg_span > LT_PIX_AGG)
+#define LT_PIXC_T0 13          // items without a pair
+#define LT_PIXC_CHUNKS_N 14    // items of several chunks (T > LT_PIX_CHUNK)
+#define LT_PIXC_CHUNKS_1 15    // items of one chunk
+#define LT_PIXC_THREAD0 16     // first of the LT_PIXC_NPT words summed over the threads:
+#define LT_PIXT_EMPTY 0        //   pairs with an empty z interval (before any clipping)
+#define LT_PIXT_CLIP_ALL 1     //   zw_snap clipping: the interval was done already
+#define LT_PIXT_CLIP_LO 2      //   its lower end cut
+#define LT_PIXT_CLIP_HI 3      //   its upper end cut
+#define LT_PIXT_CLIP_HOLE 4    //   a hole in the middle
+#define LT_PIXT_CLIP_DISJ 5    //   nothing cut (clean columns included)
+#define LT_PIXT_CLIP_CLEAN 6   //   ... of which: the column had no written range
+#define LT_PIXT_HOLE_SKIP 7    //   voxels skipped through a hole
+#define LT_PIXT_SIGN_POS 8     //   pairs by the sign case of the row's z span: za >= 0
+#define LT_PIXT_SIGN_NEG 9     //   zb <= 0
+#define LT_PIXT_SIGN_BOTH 10   //   straddling
+#define LT_PIXC_NPT 11
+#define LT_PIXC_TWO_COLS 27    // items whose 64 pixels span two or more image columns
+#define LT_PIXC_V0 28          // chunks without a candidate voxel
+#define LT_PIXC_ROUNDS 29      // voxel rounds
+#define LT_PIXC_MAX_ITEMS 30   // the largest number of items one workgroup took
+#define LT_PIXC_ROUNDS_N 31    // chunks of several voxel rounds (V > 256)
+#define LT_PIXC_N 32
 // ONE body for both entry points: k_tsdf_integrate_pix (one observation; MULTI = false) and k_tsdf_integrate_pix_multi (up
 // to LT_TSDF_MULTI_MAX observations of a fresh volume at once; MULTI = true).  They differ at four places, each an
 // `if constexpr`: where a pixel's depth interval comes from (phase A), the zw_snap clipping, the voxel evaluation -- and the
@@ -902,6 +933,10 @@ __device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view
     return a;
   };
   auto lower = [&](int a, int b, uint32_t q) { return staged ? lower_in(skey, stage0, a, b, q) : lower_in(Wd.wd_key, 0, a, b, q); };
+  // the path counters (LT_PIXC_*): per thread in registers, summed at the end; nothing of this exists with VCOUNT = false
+  [[maybe_unused]] unsigned pc[LT_PIXC_NPT] = {};
+  [[maybe_unused]] unsigned n_items = 0;
+  auto tally = [&](int q) { if constexpr (VCOUNT) pc[q] += 1u; };
   // (An item's chunks dealt to several workgroups, each repeating phase A, were measured: 2 parts 88 us, 4 parts 129 against
   // 65 -- an item is 6 us of phase A, 3 of its first chunk's pairs and 9 of voxel rounds: tools/tsdf_written_times.py --pix.)
   for (int p0 = blockIdx.x * 64; p0 < n_pix; p0 += gridDim.x * 64) {  // (workgroup-uniform)
@@ -1018,6 +1053,19 @@ __device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view
     const int agg_k0 = a_k0, agg_span = a_span;
     const bool agg = agg_span <= LT_PIX_AGG;  // (workgroup-uniform)
     if (VCOUNT && tid == 0) atomicAdd(&dbg[4], (unsigned long long)wall_clock64() - tm0);  // phase A
+    if constexpr (VCOUNT) {
+      n_items += 1u;
+      if (tid == 0) {
+        atomicAdd(&dbg[LT_PIXC_ITEMS], 1ull);
+        atomicAdd(&dbg[staged ? LT_PIXC_STAGED : LT_PIXC_UNSTAGED], 1ull);
+        if (T == 0) atomicAdd(&dbg[LT_PIXC_T0], 1ull);
+        else {
+          atomicAdd(&dbg[agg ? LT_PIXC_AGG : LT_PIXC_DIRECT], 1ull);
+          atomicAdd(&dbg[T > LT_PIX_CHUNK ? LT_PIXC_CHUNKS_N : LT_PIXC_CHUNKS_1], 1ull);
+        }
+        if (p0 / im_h != min(p0 + 63, n_pix - 1) / im_h) atomicAdd(&dbg[LT_PIXC_TWO_COLS], 1ull);
+      }
+    }
     LT_PIX_MARK(1);
     // ---- B: chunks of pairs ---------------------------------------------------------------------------------------------
     for (int base = 0; base < T; base += LT_PIX_CHUNK) {
@@ -1048,6 +1096,11 @@ __device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view
               if (za >= 0.f) { lo = fmaxf(za, zmin); hi = fminf(zb, zmax); }
               else if (zb <= 0.f) { lo = fmaxf(za, -zmax); hi = fminf(zb, -zmin); }
               else { lo = fmaxf(za, -zmax); hi = fminf(zb, zmax); }
+              if constexpr (VCOUNT) {  // (the three arms above, by their conditions)
+                if (za >= 0.f) tally(LT_PIXT_SIGN_POS);
+                else if (zb <= 0.f) tally(LT_PIXT_SIGN_NEG);
+                else tally(LT_PIXT_SIGN_BOTH);
+              }
               if (lo <= hi) {
                 const float fz0 = ceilf((lo - Vol.oz) * Wd.inv_vs - 0.02f), fz1 = floorf((hi - Vol.oz) * Wd.inv_vs + 0.02f);
                 z = (int)fmaxf(fz0, 0.f);
@@ -1055,15 +1108,19 @@ __device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view
               }
             }
           }
+          if (e.x >= 0 && zend < z) tally(LT_PIXT_EMPTY);
           int partial = 0;
           if constexpr (!MULTI)
             if (zw_snap && zend >= z) {  // the part of the interval the column pass has done already
               const int olo = LT_ZW_LO(zw_snap[e.x]), ohi = LT_ZW_HI(zw_snap[n_cols_all + e.x]);
               if (ohi >= olo) {
-                if (z >= olo && zend <= ohi) zend = z - 1;      // all of it (the usual case of a repeated observation)
-                else if (z >= olo && z <= ohi) z = ohi + 1;     // its lower end
-                else if (zend >= olo && zend <= ohi) zend = olo - 1;  // its upper end
-                else if (z < olo && zend > ohi) partial = 0x40000000;  // a hole in the middle: decided per voxel
+                if (z >= olo && zend <= ohi) { zend = z - 1; tally(LT_PIXT_CLIP_ALL); }  // all of it (the usual case of a repeated observation)
+                else if (z >= olo && z <= ohi) { z = ohi + 1; tally(LT_PIXT_CLIP_LO); }  // its lower end
+                else if (zend >= olo && zend <= ohi) { zend = olo - 1; tally(LT_PIXT_CLIP_HI); }  // its upper end
+                else if (z < olo && zend > ohi) { partial = 0x40000000; tally(LT_PIXT_CLIP_HOLE); }  // a hole in the middle: decided per voxel
+                else tally(LT_PIXT_CLIP_DISJ);
+              } else {
+                tally(LT_PIXT_CLIP_DISJ); tally(LT_PIXT_CLIP_CLEAN);
               }
             }
           len[u] = max(zend - z + 1, 0);
@@ -1116,6 +1173,7 @@ __device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view
           bool mine = true;
           if constexpr (!MULTI)
             if (sflag & 0x40000000) mine = z < LT_ZW_LO(zw_snap[col]) || z > LT_ZW_HI(zw_snap[n_cols_all + col]);
+          if (!mine) tally(LT_PIXT_HOLE_SKIP);
           const col_plain Cq = {true, p_px[sidx], c_rho2[sl], col};
 #ifdef LT_PIX_NO_EVAL  // timing experiment: everything but the evaluation (nothing is written)
           mine = false;
@@ -1140,6 +1198,9 @@ __device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view
         atomicAdd(&dbg[0], (unsigned long long)n_slots); atomicAdd(&dbg[1], (unsigned long long)V);
         atomicAdd(&dbg[6], (unsigned long long)wall_clock64() - tm1);  // the voxel rounds
         atomicAdd(&dbg[7], 1ull);
+        atomicAdd(&dbg[LT_PIXC_ROUNDS], (unsigned long long)((V + 255) / 256));
+        if (V == 0) atomicAdd(&dbg[LT_PIXC_V0], 1ull);
+        if (V > 256) atomicAdd(&dbg[LT_PIXC_ROUNDS_N], 1ull);
       }
       __syncthreads();  // the chunk's arrays are reused
     }
@@ -1158,6 +1219,16 @@ __device__ __forceinline__ void pix_body(const tsdf_volume& Vol, const tsdf_view
       }
     LT_PIX_MARK(4);
     __syncthreads();  // ... and the pixels'
+  }
+  if constexpr (VCOUNT) {  // every thread is here (the loops above are workgroup-uniform)
+#pragma unroll
+    for (int q = 0; q < LT_PIXC_NPT; ++q) {
+      unsigned v = pc[q];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if (lane == 0 && v) atomicAdd(&dbg[LT_PIXC_THREAD0 + q], (unsigned long long)v);
+    }
+    if (tid == 0) atomicMax(&dbg[LT_PIXC_MAX_ITEMS], (unsigned long long)n_items);
   }
 }
 
@@ -1658,6 +1729,17 @@ static unsigned tsdf_pix_grid(const lt_tsdf* t, size_t n_pix, int waves_per_eu) 
 // of LDS), not LT_PIX_WPE, which a -D can change
 #define LT_PIX_MULTI_WPE 5
 
+// LIDARHIP_DEBUG_TSDF=1 (read once): the pixel pass runs its counted instantiation -- pairs / candidate voxels / written
+// voxels (lt_debug_tsdf_pix_counts) and the paths it took (LT_PIXC_*, lt_debug_tsdf_pix_paths) of the LAST launch
+static int tsdf_pix_dbg_begin(hipStream_t stream, bool* want) {
+  static const bool want_cnt = getenv("LIDARHIP_DEBUG_TSDF") != nullptr;
+  *want = want_cnt;
+  if (!want_cnt) return LT_OK;
+  if (!g_pix_dbg) LT_HIP(hipMalloc((void**)&g_pix_dbg, LT_PIXC_N * sizeof(unsigned long long)));
+  LT_HIP(hipMemsetAsync(g_pix_dbg, 0, LT_PIXC_N * sizeof(unsigned long long), stream));
+  return LT_OK;
+}
+
 static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* depth_im, const float* rem_im, int im_h,
                               int im_w, float obs_weight, const tsdf_fov& F, int rho_bits, bool fresh_volume,
                               hipStream_t stream) {
@@ -1682,10 +1764,8 @@ static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* de
                        dim3((unsigned)lt_deal_count((int)((n_cols + 63) / 64), LT_WRITTEN_CHUNKS_PER_WG, t->dim[1], 1)), dim3(256), 0,
                        stream, Vol, Vw, Mk, Wd.wd_px, rem_im, t->dct, zw_snap);
   }
-  // LIDARHIP_DEBUG_TSDF=1: pairs / candidate voxels / written voxels of the launch (lt_debug_tsdf_pix_counts)
-  static const bool want_cnt = getenv("LIDARHIP_DEBUG_TSDF") != nullptr;
-  if (want_cnt && !g_pix_dbg) LT_HIP(hipMalloc((void**)&g_pix_dbg, 8 * sizeof(unsigned long long)));
-  if (want_cnt) LT_HIP(hipMemsetAsync(g_pix_dbg, 0, 8 * sizeof(unsigned long long), stream));
+  bool want_cnt = false;
+  LT_CHECK(tsdf_pix_dbg_begin(stream, &want_cnt));
   if (want_cnt)
     hipLaunchKernelGGL(k_tsdf_integrate_pix<true>, dim3(nb), dim3(256), 0, stream, Vol, Vw, Mk, Wd, t->wd_start, rem_im, t->dct,
                        zw_snap, g_pix_dbg);
@@ -1862,8 +1942,14 @@ extern "C" int lt_tsdf_integrate_multi_dev(lt_tsdf* t, int n_obs, const float* c
     const tsdf_view Vw = tsdf_view_of(t, F, im_h, im_w, obs_weight);
     const tsdf_marks Mk = tsdf_marks_of(t);
     const tsdf_wedge Wd = tsdf_wedge_of(t);
-    hipLaunchKernelGGL(k_tsdf_integrate_pix_multi<false>, dim3(tsdf_pix_grid(t, n_pix, LT_PIX_MULTI_WPE)), dim3(256), 0, stream,
-                       Vol, Vw, Mk, Wd, t->wd_start, t->obs4, n, (unsigned long long*)nullptr);
+    bool want_cnt = false;
+    LT_CHECK(tsdf_pix_dbg_begin(stream, &want_cnt));
+    if (want_cnt)
+      hipLaunchKernelGGL(k_tsdf_integrate_pix_multi<true>, dim3(tsdf_pix_grid(t, n_pix, LT_PIX_MULTI_WPE)), dim3(256), 0, stream,
+                         Vol, Vw, Mk, Wd, t->wd_start, t->obs4, n, g_pix_dbg);
+    else
+      hipLaunchKernelGGL(k_tsdf_integrate_pix_multi<false>, dim3(tsdf_pix_grid(t, n_pix, LT_PIX_MULTI_WPE)), dim3(256), 0, stream,
+                         Vol, Vw, Mk, Wd, t->wd_start, t->obs4, n, (unsigned long long*)nullptr);
     if (t->wd_n_quirk > 0) {
       const long long nv = (long long)t->wd_n_quirk * t->dim[2];
       hipLaunchKernelGGL(k_tsdf_integrate_quirk_multi, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, stream, Vol.vox,
@@ -1917,6 +2003,28 @@ extern "C" int lt_debug_tsdf_pix_counts(unsigned long long* out8) {
   if (!out8 || !g_pix_dbg) return LT_ERR_INVALID_ARG;
   LT_HIP(hipDeviceSynchronize());
   LT_HIP(hipMemcpy(out8, g_pix_dbg, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+// debug helper (not part of the documented ABI): the first n (<= LT_PIXC_N = 32) words of the last pixel pass's counters --
+// [0, 8) as lt_debug_tsdf_pix_counts, from 8 on the paths taken (LT_PIXC_*) -- of k_tsdf_integrate_pix or, after a fused
+// integrate, k_tsdf_integrate_pix_multi (LIDARHIP_DEBUG_TSDF=1)
+extern "C" int lt_debug_tsdf_pix_paths(unsigned long long* out, int n) {
+  if (!out || n < 0 || n > LT_PIXC_N || !g_pix_dbg) return LT_ERR_INVALID_ARG;
+  LT_HIP(hipDeviceSynchronize());
+  LT_HIP(hipMemcpy(out, g_pix_dbg, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+// debug helper (not part of the documented ABI): the first n (<= image width + 1) words of wd_start -- the first table entry
+// of every image column's wedge, [width] = the number of table columns -- and the number of quirk columns, of the wedge
+// table the volume holds (built by its first pixel pass)
+extern "C" int lt_debug_tsdf_wedge(lt_tsdf* t, int* wd_start_out, int n, int* n_quirk) {
+  if (!t || !t->wd_start || t->wd_w <= 0 || n < 0 || n > t->wd_w + 1 || (n > 0 && !wd_start_out)) return LT_ERR_INVALID_ARG;
+  LT_HIP(hipSetDevice(t->device));
+  LT_HIP(hipDeviceSynchronize());
+  if (n > 0) LT_HIP(hipMemcpy(wd_start_out, t->wd_start, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  if (n_quirk) *n_quirk = t->wd_n_quirk;
   return LT_OK;
 }
 

@@ -278,12 +278,11 @@ def test_column_aware_integrate_equals_dense_kernel_bit_for_bit(tmp_path, merge,
     columns holding only the reference's "no data" depth -1 -- with voxel_size 0.25 the truncation margin is 1.25 m, so the
     voxels within 0.25 m of the sensor ARE written through such pixels (depth_diff = -1 - depth >= -trunc_margin).  Image
     shapes 25 x 301 and 70 x 97: the pixel kernel's workgroups of 64 pixels then straddle image columns, and the wedge table
-    is built for a width that is not a power of two.  Image 32 x 64 at voxel 0.05 (600 x 600 columns): a wedge is a
-    5.6 degree sector (2 pi / 64 = 0.098 rad) that holds at least 0.5 * 0.098 * 15^2 / 0.0025 ~ 4400 columns, and a group
-    of 64 pixels spans two image columns -- every workgroup's search range exceeds LT_PIX_STAGE (3840) and takes the
-    unstaged search in global memory; and its pairs fall on two wedges (a colour-0 pixel at 9 m alone on 0.5 * 0.098 * 81 /
-    0.0025 ~ 1600 entries): more than LT_PIX_AGG (1024) table entries, so the workgroups mark the columns' written ranges
-    directly (col_mark_written) instead of merging them in LDS.  bnds (optional; _ODD_BNDS): a volume whose last chunk of 64
+    is built for a width that is not a power of two.  Image 32 x 64 at voxel 0.05 (600 x 600 columns): wide wedges and a
+    group of 64 pixels on two image columns, at deployment-like size -- which branch of the pixel pass an input takes
+    (staged or unstaged search, written ranges merged in LDS or marked directly, and every other one) is not argued here
+    but driven on small inputs, proven and read from the kernel's counters in tests/test_tsdf_pix_paths_gpu.py
+    (cases: tests/tsdf_pix_cases.py).  bnds (optional; _ODD_BNDS): a volume whose last chunk of 64
     columns holds 3 -- what the column walk, the pass over the written ranges and the reset do per chunk."""
     import subprocess
     import sys
@@ -336,10 +335,9 @@ def test_fused_observations_equal_one_integrate_per_observation(fu, fd, voxel, h
     own class: long runs), no-data columns, NaN / infinite pixels -- plus one observation whose surface lies a metre in front
     of the others' and one a metre behind (bands that do not overlap).  11 observations: more than one fused pass holds
     (8), the rest take the single-observation path on the then non-fresh volume; 9: one full fused pass of exactly
-    LT_TSDF_MULTI_MAX, then one observation through zw_snap.  Image 32 x 64 at voxel 0.05: a wedge of the 600 x 600 columns
-    is a 5.6 degree sector of at least 0.5 * 0.098 * 15^2 / 0.0025 ~ 4400 columns and a group of 64 pixels spans two image
-    columns, so the fused kernel's searches are unstaged (more than LT_PIX_STAGE = 3840 quanta) and a workgroup's pairs, on
-    two wedges, span more than LT_PIX_AGG = 1024 entries (written ranges marked directly), as in the test above.  bnds
+    LT_TSDF_MULTI_MAX, then one observation through zw_snap.  Image 32 x 64 at voxel 0.05: wide wedges of the 600 x 600
+    columns and a group of 64 pixels on two image columns, as in the test above (the fused kernel's unstaged search and
+    direct marking are driven on purpose and read from its counters in tests/test_tsdf_pix_paths_gpu.py).  bnds
     (optional; _ODD_BNDS): 161 x 163 x 37 voxels, the last chunk of 64 columns partial."""
     import torch
     from lidar_transfer_amd.fusion import TSDFVolume
