@@ -694,6 +694,49 @@ int lt_return_model_dev(lt_scene* scene, const float* rays, int n_rays, const lt
                         float* endpoints, int* endcolors, float* range, float* endrem, int* tri, float* incidence,
                         unsigned char* drop, unsigned trace_flags, void* stream);
 
+/* ---- the target sensor's noise model (the reference leaves it as a TODO, laserscan.py:1094-1096) ---
+ *
+ * Applied to a rendered scan cell by cell, in place, behind the return model.  Cell i is a RETURN when tri[i] >= 0 and
+ * range[i] > 0; any other cell is left untouched, byte for byte.  With mix(x) as above (uint32, products and sums wrap):
+ *   g   = mix(mix(mix(seed ^ 0x6e6f6973) + scan) + i)          a stream of its own: independent of the dropout hash
+ *   w_k = mix(g + k)                                           k = 1..6: the range draw;  k = 7..12: the remission draw
+ *   S   = the sum over the draw's six words of (w_k & 0xffff) + (w_k >> 16)            twelve 16-bit uniforms, an integer
+ *   z   = (double)(S - 393210) / 65536.0                       mean 0, variance 1 - 2^-32, |z| < 6, exact in float64
+ * a pure function of (seed, scan, i), so a scan's pattern does not depend on the chain, rank or order it is rendered in.
+ * In float64 from the widened float32 values, every product, sum and quotient rounded on its own, in this order:
+ *   r  = (double)range[i]
+ *   r1 = r + (range_sigma + range_sigma_rel * r) * z_range
+ *   r2 = range_resolution > 0 ? rint(r1 / range_resolution) * range_resolution : r1            rint: ties to even
+ * State 2, the return is LOST, if !(r2 > 0) or r2 < min_range or r2 > max_range (strict: a cell exactly at the gate stays):
+ * the cell becomes the miss LT_TRACE_WRITE_MISSES writes -- end point (0, 0, 0), label / colour 0, remission 0, range 0,
+ * tri -1.  Else state 1, the return is NOISED:
+ *   range[i] = float32(r2);   s = r2 / r
+ *   endpoints[i][k] = float32(o[k] + ((double)endpoints[i][k] - o[k]) * s)      o = (double)origin, k = x, y, z
+ *   e = (double)endrem[i] + remission_sigma * z_rem;   e = e < 0 ? 0 : (e > 1 ? 1 : e)
+ *   e = remission_levels ? rint(e * (L - 1)) / (L - 1) : e                      L = remission_levels as a double
+ *   endrem[i] = float32(e)
+ * State 0 is a cell left untouched.  range_error[i] = float32(r2 - r) for state 1, else 0; state[i] = the state.  Both are
+ * written for EVERY cell.  No counters and no atomics: totals are a bincount.  The kernel has no transcendental. */
+typedef struct lt_noise_model {
+  double range_sigma;      /* metres, finite, >= 0: the constant part of the range jitter's standard deviation        */
+  double range_sigma_rel;  /* finite, >= 0: the part proportional to the range (metres per metre)                     */
+  double range_resolution; /* metres, finite, >= 0; 0: ranges are not put on a grid                                   */
+  double remission_sigma;  /* finite, >= 0 (remission is in [0, 1])                                                   */
+  double min_range, max_range; /* the sensor's range gate (its return model's; 0 and +inf: none), 0 <= min <= max     */
+  unsigned remission_levels;   /* 0: off, else >= 2: remission is reported on this many levels                        */
+  unsigned seed;
+} lt_noise_model;
+
+/* origin [3] f32 HOST: where the scan's rays start (the target sensor's position in the scene), finite.  model: HOST; both
+ * are read before the call returns.  tri [n] i32 and range [n] f32 are mandatory; endpoints [n,3] f32, endcolors ([n] i32
+ * with trace_flags & LT_TRACE_LABEL_IMAGE, else [n,3] i32), endrem [n] f32, range_error [n] f32 and state [n] u8 may each
+ * be NULL -- all DEVICE; the five images are read-modify-write, so the call is made ONCE per rendered scan.  No scene: no
+ * mesh is read.  One thread per cell, one launch, asynchronous on `stream`, on the calling thread's current device (the
+ * buffers' and the stream's).  n == 0 is LT_OK; a bad argument is LT_ERR_INVALID_ARG with a message. */
+int lt_noise_model_dev(const float* origin, int n, const lt_noise_model* model, unsigned scan, float* endpoints,
+                       int* endcolors, float* range, float* endrem, int* tri, float* range_error, unsigned char* state,
+                       unsigned trace_flags, void* stream);
+
 /* Pack a rendered scan in SemanticKITTI layout; replaces the filtering and the per-point struct.pack loops
  * of MultiSemLaserScan.write (auxiliary/laserscan.py:1133-1178).  Keeps, in order, the cells with
  * (index == NULL or index[i] > 0) and label[i] >= 0 and x + y + z != 0.  points [n,3] f32 or f64,
@@ -835,7 +878,7 @@ const char* lt_version(void);
 
 /* Layout version of the structs this header declares (lt_proj_images, lt_stats, lt_mm_geometry ...): a caller compiled
  * against another header must not pass them.  lt_abi_version() returns the library's; the Python binding compares at load. */
-#define LT_ABI_VERSION 9
+#define LT_ABI_VERSION 10
 int lt_abi_version(void);
 
 #ifdef __cplusplus

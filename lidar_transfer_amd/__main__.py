@@ -14,7 +14,12 @@ metrics are printed and every row of ``--log`` carries ``"azimuth_model": "secto
 every row of ``--log`` then carries ``"beam_azimuth": true`` as well.  A target YAML with a ``return_model`` block
 (config/vlp32c_table_returns_1024.yaml) applies the sensor's range gate, incidence limit and random dropout to every output scan
 of ``mesh`` / ``mergemesh`` (``cp`` is refused); the run closes with one line ``Returns: kept N, no hit N, ...``, the cells per
-code over all its scans, which the ``--log`` summary carries as ``return_totals``.  The tool
+code over all its scans, which the ``--log`` summary carries as ``return_totals``.  A target YAML with a ``noise_model`` block
+(config/vlp32c_table_noise_1024.yaml) gives every output scan of ``mesh`` / ``mergemesh`` (``cp`` is refused) the sensor's
+measurement error -- range jitter and grid, remission jitter and levels --; the run closes with one line ``Noise: untouched N,
+noised N, lost N, range error RMS X m``, which the ``--log`` summary carries as ``noise_totals`` and ``range_error_rms``.  The
+metrics of such a run, under ``--evaluate auto`` and under ``--evaluate target`` alike, compare the NOISY output with a
+reference that has no noise: their MSE contains the noise.  The tool
 is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
 ``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  ``--evaluate target`` compares for
 every target -- mounted, with a table, a sector, offsets, a return model, another image size -- against the source scan seen
@@ -89,6 +94,9 @@ def main(argv=None):
     if target.return_model() is not None and approach.adaption == "cp":
         print("adaption cp renders no surface: the target sensor's return_model cannot be applied (use mesh or mergemesh).")
         return 1
+    if target.noise_model() is not None and approach.adaption == "cp":
+        print("adaption cp renders no ray: the target sensor's noise_model cannot be applied (use mesh or mergemesh).")
+        return 1
     log = open(args.log, "w") if args.log else None
     try:
         with SequenceTransfer((args.dataset, args.sequence), approach, source, target, out_dir=args.output if args.write else None,
@@ -117,6 +125,9 @@ def main(argv=None):
             if tr.summary.get("return_totals") is not None:
                 from .sequence import format_return_totals
                 print(format_return_totals(tr.summary["return_totals"]), flush=True)
+            if tr.summary.get("noise_totals") is not None:
+                from .sequence import format_noise_totals
+                print(format_noise_totals(tr.summary["noise_totals"], tr.summary["range_error_rms"]), flush=True)
             if log is not None:
                 log.write(json.dumps(dict(summary=tr.summary)) + "\n")
     finally:

@@ -57,6 +57,17 @@ def out_ptrs(out):
     return tuple(out[k].data_ptr() if out.get(k) is not None else None for k in OUT_KEYS)
 
 
+def with_tri(rout, n_rays, device):
+    """``rout`` itself when it holds a ``tri`` image already, else a copy with one (the models behind the render tell a return
+    from a miss by it).  Allocates on the current stream."""
+    if rout.get("tri") is not None:
+        return rout
+    import torch
+    rout = dict(rout)
+    rout["tri"] = torch.empty((n_rays,), dtype=torch.int32, device=device)
+    return rout
+
+
 class Returns:
     """The target sensor's return model on a chain (``config.ReturnModel`` or ``None``).  ``None``, or a model
     with every field at its default: nothing here allocates or launches.  Applied once per output scan, to the render that
@@ -76,12 +87,7 @@ class Returns:
     def render_into(self, rout, n_rays, device):
         """What the render writes for this chain: ``rout`` itself without a model or when it holds ``tri`` already; else a
         copy with a ``tri`` image (the model reads the hit triangle).  Allocates on the current stream."""
-        if self.model is None or rout.get("tri") is not None:
-            return rout
-        import torch
-        rout = dict(rout)
-        rout["tri"] = torch.empty((n_rays,), dtype=torch.int32, device=device)
-        return rout
+        return rout if self.model is None else with_tri(rout, n_rays, device)
 
     def apply(self, rout, scan, scene, rays, stream, label_image=True):
         """the model on the rendered images ``rout`` of output scan ``scan`` (its index in its sequence), on ``stream``;
@@ -92,6 +98,41 @@ class Returns:
             raise ValueError("a return model needs the output scan's index in its sequence (scan_index=)")
         from . import post
         return post.return_model(scene, rays, self.model, scan, rout, label_image=label_image, stream=stream)
+
+
+class Noise:
+    """The target sensor's noise model on a chain (``config.NoiseModel`` or ``None``), beside :class:`Returns`
+    and shaped like it.  ``None``, or a model with every field at its default: nothing here allocates or launches.
+    ``gate``: the chain's return model (``config.ReturnModel`` or ``None``), whose range gate a measured range must stay
+    inside.  Applied once per output scan, to the render that stands, BEHIND the return model on the chain's stream and
+    BEFORE the hits go into the target's frame, evaluation and packing: the kernel is read-modify-write, a second
+    application would jitter the jittered scan."""
+
+    KEYS = ("range_error", "noise_state")
+
+    def __init__(self, model, gate=None, who="noise model"):
+        from .config import NoiseModel
+        if model is not None and not isinstance(model, NoiseModel):
+            raise ValueError(f"{who}: noise= takes a lidar_transfer_amd.config.NoiseModel (SensorModel.noise_model()) or None")
+        self.model = None if model is None or model.is_default else model
+        self.gate = gate
+
+    def __bool__(self):
+        return self.model is not None
+
+    def render_into(self, rout, n_rays, device):
+        """as ``Returns.render_into``: the model reads ``tri`` to tell a return from a miss"""
+        return rout if self.model is None else with_tri(rout, n_rays, device)
+
+    def apply(self, rout, scan, origin, stream, label_image=True):
+        """the model on the rendered images ``rout`` of output scan ``scan`` (its index in its sequence) whose rays start at
+        ``origin``, on ``stream``; returns ``dict(range_error=, noise_state=)``, or ``{}`` without a model"""
+        if self.model is None:
+            return {}
+        if scan is None:
+            raise ValueError("a noise model needs the output scan's index in its sequence (scan_index=)")
+        from . import post
+        return post.noise_model(origin, self.model, scan, rout, gate=self.gate, label_image=label_image, stream=stream)
 
 
 class Mount:

@@ -49,8 +49,8 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_reverse_projection_beams_dev", "lt_create_rays_sector_dev", "lt_reverse_projection_sector_dev",
            "lt_rayset_create_grid_dev", "lt_projector_set_sector", "lt_range_projection_set_sector",
            "lt_create_rays_beams_az_dev", "lt_projector_set_beam_azimuth", "lt_range_projection_set_beam_azimuth",
-           "lt_reverse_projection_beams_az_dev", "lt_return_model_dev", "lt_target_view_dev"]
-LT_ABI_VERSION = 9   # include/lidarhip.h: layout version of the structs mirrored below
+           "lt_reverse_projection_beams_az_dev", "lt_return_model_dev", "lt_target_view_dev", "lt_noise_model_dev"]
+LT_ABI_VERSION = 10   # include/lidarhip.h: layout version of the structs mirrored below
 
 
 class Stats(C.Structure):
@@ -114,6 +114,13 @@ class ReturnModelArgs(C.Structure):
     """Mirror of ``lt_return_model``: the target sensor's return model as ``lt_return_model_dev`` reads it (HOST)."""
     _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("min_cos", C.c_double), ("drop_threshold", C.c_uint),
                 ("seed", C.c_uint), ("flags", C.c_uint)]
+
+
+class NoiseModelArgs(C.Structure):
+    """Mirror of ``lt_noise_model``: the target sensor's noise model as ``lt_noise_model_dev`` reads it (HOST)."""
+    _fields_ = [("range_sigma", C.c_double), ("range_sigma_rel", C.c_double), ("range_resolution", C.c_double),
+                ("remission_sigma", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double),
+                ("remission_levels", C.c_uint), ("seed", C.c_uint)]
 
 
 def ingest_work_ints(n_total: int, n_scans: int) -> int:
@@ -300,6 +307,9 @@ def load():
     lib.lt_return_model_dev.argtypes = [vp, vp, C.c_int, C.POINTER(ReturnModelArgs), C.c_uint, vp, vp, vp, vp, vp, vp, vp,
                                         C.c_uint, vp]
     lib.lt_return_model_dev.restype = C.c_int
+    lib.lt_noise_model_dev.argtypes = [C.POINTER(C.c_float), C.c_int, C.POINTER(NoiseModelArgs), C.c_uint, vp, vp, vp, vp, vp,
+                                       vp, vp, C.c_uint, vp]
+    lib.lt_noise_model_dev.restype = C.c_int
     lib.lt_abi_version.argtypes = []
     lib.lt_tsdf_volume_stride.argtypes = []
     if lib.lt_abi_version() != LT_ABI_VERSION:  # a stale prebuilt library: its structs are laid out differently

@@ -32,6 +32,14 @@ A fourth is what the target MEASURES along those rays, :class:`ReturnModel` (``S
 * ``return_model``: a block of ``min_range``, ``max_range`` (metres), ``max_incidence`` (degrees), ``remission`` (``none`` |
   ``lambert``), ``drop_rate`` and ``seed`` -- returns outside the range gate, seen too close to edge-on or dropped at random
   become misses of the rendered scan; a block with every field at its default is none.
+
+A fifth is the ERROR of what it measures, :class:`NoiseModel` (``SensorModel.noise_model()``), beside the fourth,
+not inside it:
+
+* ``noise_model``: a block of ``range_sigma`` (metres), ``range_sigma_rel`` (metres per metre), ``range_resolution`` (metres),
+  ``remission_sigma``, ``remission_levels`` and ``seed`` -- the range of a return is jittered along its ray and reported on a
+  grid, its remission is jittered, clamped to [0, 1] and reported on ``remission_levels`` levels; a block with every field at
+  its default is none.
 """
 from __future__ import annotations
 
@@ -60,6 +68,8 @@ class SensorModel:
     beam_azimuth_offsets: Optional[List[float]] = None
     #: the file's ``return_model`` block as read (a mapping), ``None`` without the key: :meth:`return_model`
     return_block: Optional[dict] = None
+    #: the file's ``noise_model`` block as read (a mapping), ``None`` without the key: :meth:`noise_model`
+    noise_block: Optional[dict] = None
 
     @property
     def H(self) -> int:
@@ -112,6 +122,12 @@ class SensorModel:
         7e) -- or ``None`` without the ``return_model`` key or with every field at its default.  ``ValueError`` led by the
         sensor's name for a block that cannot be used.  :class:`TargetModel` stays rows and columns."""
         return ReturnModel.of(self.return_block, f"sensor {self.name!r}")
+
+    def noise_model(self):
+        """The sensor's :class:`NoiseModel` -- the error of what a TARGET measures: range jitter and grid, remission jitter
+        and levels -- or ``None`` without the ``noise_model`` key or with every field at its default.
+        ``ValueError`` led by the sensor's name for a block that cannot be used."""
+        return NoiseModel.of(self.noise_block, f"sensor {self.name!r}")
 
     def sector(self):
         """``None`` for ``azimuth_model: full``; for ``sector`` ``(center_deg, span_deg)`` as floats: the ``W`` columns span
@@ -422,6 +438,90 @@ class ReturnModel:
                                     _lib.LT_RETURN_LAMBERT if self.lambert else 0)
 
 
+class NoiseModel:
+    """The error of what a TARGET sensor measures (the sensor file's ``noise_model`` block), one immutable value
+    like :class:`ReturnModel` and beside it: the standard deviation of the range jitter ``range_sigma + range_sigma_rel *
+    range`` (metres; metres per metre), the grid ``range_resolution`` ranges are reported on (metres, 0: none), the standard
+    deviation ``remission_sigma`` of the remission jitter, the number ``remission_levels`` of levels remission is reported on
+    (0: off, else at least 2) and the ``seed`` of the draws.  The constructor is the only place that normalises and
+    validates -- finite numbers that are not negative, ``remission_levels`` 0 or an integer in [2, 2^32), ``seed`` in uint32,
+    else ``ValueError`` led by ``who`` -- and :meth:`of` returns ``None`` for a model in which every field is at its
+    default.  The draws are a pure function of ``(seed, scan, cell)``: :func:`return_hash_mix` in a stream of its own."""
+
+    DEFAULTS = dict(range_sigma=0.0, range_sigma_rel=0.0, range_resolution=0.0, remission_sigma=0.0, remission_levels=0, seed=0)
+
+    def __init__(self, range_sigma=0.0, range_sigma_rel=0.0, range_resolution=0.0, remission_sigma=0.0, remission_levels=0,
+                 seed=0, who="noise model"):
+        import math
+
+        def number(name, v):
+            try:
+                if isinstance(v, (bool, str)):
+                    raise TypeError
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: noise_model {name} must be a number, not {v!r}") from None
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{who}: noise_model {name} must be finite and not negative, not {v}")
+            return v
+
+        def integer(name, v):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{who}: noise_model {name} must be an integer in [0, 2^32), not {v!r}")
+            return int(v)
+        fields = dict(range_sigma=number("range_sigma", range_sigma), range_sigma_rel=number("range_sigma_rel", range_sigma_rel),
+                      range_resolution=number("range_resolution", range_resolution),
+                      remission_sigma=number("remission_sigma", remission_sigma),
+                      remission_levels=integer("remission_levels", remission_levels), seed=integer("seed", seed))
+        if fields["remission_levels"] == 1:
+            raise ValueError(f"{who}: noise_model remission_levels must be 0 (off) or at least 2, not 1")
+        self.__dict__.update(fields)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a NoiseModel does not change: make another")
+
+    @classmethod
+    def of(cls, block, who="noise model"):
+        """The model of a sensor file's ``noise_model`` block (a mapping, or ``None``: no key), or ``None`` when every field is
+        at its default; an unknown key and a block that is no mapping are ``ValueError``.  A :class:`NoiseModel` passes
+        through (``None`` if all-default)."""
+        if block is None:
+            return None
+        if isinstance(block, cls):
+            return None if block.is_default else block
+        if not isinstance(block, dict):
+            raise ValueError(f"{who}: noise_model must be a mapping of {', '.join(cls.DEFAULTS)}")
+        unknown = sorted(set(map(str, block)) - set(cls.DEFAULTS))
+        if unknown:
+            raise ValueError(f"{who}: noise_model has unknown key(s) {', '.join(unknown)} (known: {', '.join(cls.DEFAULTS)})")
+        m = cls(who=who, **block)
+        return None if m.is_default else m
+
+    def fields(self):
+        return {k: getattr(self, k) for k in self.DEFAULTS}
+
+    @property
+    def is_default(self):
+        return self.fields() == self.DEFAULTS
+
+    def __eq__(self, other):
+        return isinstance(other, NoiseModel) and self.fields() == other.fields()
+
+    def __hash__(self):
+        return hash(tuple(self.fields().values()))
+
+    def __repr__(self):
+        return "NoiseModel(" + ", ".join(f"{k}={v!r}" for k, v in self.fields().items()) + ")"
+
+    def args(self, gate=None):
+        """the model as ``lt_noise_model_dev`` reads it (``_lib.NoiseModelArgs``); ``gate``: the sensor's :class:`ReturnModel`
+        -- a measured range outside its ``min_range`` .. ``max_range`` is not reported -- or ``None``: 0 and +inf"""
+        from . import _lib
+        lo, hi = (0.0, float("inf")) if gate is None else (gate.min_range, gate.max_range)
+        return _lib.NoiseModelArgs(self.range_sigma, self.range_sigma_rel, self.range_resolution, self.remission_sigma, lo, hi,
+                                   self.remission_levels, self.seed)
+
+
 def _load_yaml(path_or_dict):
     if isinstance(path_or_dict, dict):
         return path_or_dict
@@ -459,9 +559,11 @@ def load_sensor(path_or_dict) -> SensorModel:
     model = SensorModel(name, fov_up, fov_down, beams, angle_res_hor, fov_hor, beam_angles, raw=cfg,
                         beam_model=str(cfg.get("beam_model", "linear")),
                         azimuth_model=str(cfg.get("azimuth_model", "full")), azimuth_center=cfg.get("azimuth_center", 0.0),
-                        beam_azimuth_offsets=offsets, return_block=cfg.get("return_model"))
+                        beam_azimuth_offsets=offsets, return_block=cfg.get("return_model"),
+                        noise_block=cfg.get("noise_model"))
     model.target_model()   # (a table, a sector or offsets that cannot be used: said at load time)
     model.return_model()   # (and a return model that cannot be)
+    model.noise_model()    # (nor a noise model)
     return model
 
 
@@ -494,13 +596,21 @@ def refuse_source_return_model(source):
                          "scan holds the returns its sensor recorded)")
 
 
+def refuse_source_noise_model(source):
+    """So is its noise model: the source scan holds the error its sensor made."""
+    if getattr(source, "noise_block", None) is not None:
+        raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: noise_model is for target sensors only (the source "
+                         "scan holds the measurement error of its own sensor)")
+
+
 def refuse_source_models(source):
-    """everything a :class:`TargetModel` or a :class:`ReturnModel` holds is a property of the TARGET: the four refusals, the
-    table's first"""
+    """everything a :class:`TargetModel`, a :class:`ReturnModel` or a :class:`NoiseModel` holds is a property of the TARGET:
+    the five refusals, the table's first"""
     refuse_source_table(source)
     refuse_source_sector(source)
     refuse_source_beam_azimuth(source)
     refuse_source_return_model(source)
+    refuse_source_noise_model(source)
 
 
 @dataclass

@@ -135,7 +135,7 @@ class DeviceDeform:
 
     def __init__(self, source, target, vol_bnds=None, voxel_size=0.1, beam_angles=None, t_beam_angles=None,
                  preserve_float=False, device=None, merge=True, fusion="cuda", mesh_volume=True, rayset=None, mm_state=None,
-                 transformation=None, t_beam_table=None, t_sector=None, t_beam_azimuth=None, returns=None):
+                 transformation=None, t_beam_table=None, t_sector=None, t_beam_azimuth=None, returns=None, noise=None):
         """``fusion``: ``"cuda"`` -- the arithmetic of the reference's CUDA kernel (class-aware with ``merge``), or ``"numpy"`` --
         that of its numpy branch (``FUSION_GPU_MODE == 0``, fusion_lidar.py:290-388; what goldens F13 / F14 are made by).
         ``vol_bnds``: [3,2]; for :meth:`mergemesh` it is STATE, clipped in place call after call exactly as the reference
@@ -160,7 +160,13 @@ class DeviceDeform:
         ``None`` or all-default: nothing of it runs) -- ``mesh`` and ``mergemesh`` then take ``scan_index``, the output scan's
         index in its sequence, apply the model once to the render that stands (range gate, incidence, dropout: such cells
         become misses) before the hits go into the target's frame and before packing, and return ``incidence`` and ``drop``
-        as well; ``cp`` renders no surface and raises."""
+        as well; ``cp`` renders no surface and raises.
+        ``noise``: the TARGET sensor's :class:`~lidar_transfer_amd.config.NoiseModel` (``SensorModel.noise_model()``; ``None``
+        or all-default: nothing of it runs) -- ``mesh`` and ``mergemesh`` take ``scan_index`` for it too and apply it once to
+        the render that stands, BEHIND the return model (whose range gate a measured range must stay inside) and before the
+        frame change and packing: ranges are jittered and put on a grid, the end points follow along their rays about the
+        ray origin, remission is jittered and put on levels; the result holds ``range_error`` and
+        ``noise_state`` [n] as well.  ``cp`` renders no ray and has no origin: it raises."""
         import numpy as np
         import torch
 
@@ -188,6 +194,8 @@ class DeviceDeform:
         self._mounting = _chain.Mount(transformation)
         self._returns = _chain.Returns(returns, "DeviceDeform")
         self.returns = self._returns.model
+        self._noise = _chain.Noise(noise, self.returns, "DeviceDeform")
+        self.noise = self._noise.model
         m = self.t_model = TargetModel(t_beam_table, t_sector, t_beam_azimuth, "DeviceDeform").validate(
             self.t_H, (self.t_fov_up, self.t_fov_down), "DeviceDeform")
         # what the reverse projection reads on the device: the table and the offsets in radians
@@ -291,11 +299,14 @@ class DeviceDeform:
         (start, projected, rendered, packed) when given.  ``origin``: where the rays start in the scene (default: the target
         sensor's position, (0, 0, 0) unless it is mounted elsewhere); ``endpoints`` are in the target sensor's frame,
         ``endpoints_scene`` as rendered.  ``scan_index``: the output scan's index in its sequence, needed with a return
-        model (``returns=``): the result is what the target sensor sees, with ``incidence`` and ``drop`` [n] beside it."""
+        model (``returns=``): the result is what the target sensor sees, with ``incidence`` and ``drop`` [n] beside it; and
+        with a noise model (``noise=``): what it reports, with ``range_error`` and ``noise_state`` [n]."""
         if origin is None:
             origin = self.origin
         if self._returns and scan_index is None:
             raise ValueError("DeviceDeform.mesh: a return model needs scan_index, the output scan's index in its sequence")
+        if self._noise and scan_index is None:
+            raise ValueError("DeviceDeform.mesh: a noise model needs scan_index, the output scan's index in its sequence")
         if self.vol is None:
             raise RuntimeError("DeviceDeform.mesh: constructed without vol_bnds")
         torch, lib = self._torch, self._lib
@@ -314,11 +325,13 @@ class DeviceDeform:
             cp[k], dp[k], rp[k] = o["label_folded"].data_ptr(), o["range"].data_ptr(), o["rem"].data_ptr()
         out = self.scene.alloc_outputs(self.n_rays, label_image=True)
         rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays, self.device)
+        rout = self._noise.render_into(rout, self.n_rays, self.device)
         with torch.cuda.device(self.device):
             _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, n, cp, dp, rp,
                                               self.H, self.W, 1.0, self._merge, _chain.origin3(origin), *_chain.out_ptrs(rout),
                                               _chain.TRACE_FLAGS, vp(st.cuda_stream), 0), "lt_fusion_scan_dev")
             seen = self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st)
+            seen.update(self._noise.apply(rout, scan_index, origin, st))
             self._mounting.to_target(rout, out, st)
             if ev:
                 ev[2].record(st)
@@ -392,8 +405,8 @@ class DeviceDeform:
         scan's number in its sequence when several chains share the state.  By default the whole scan is ONE native call
         (``lt_mergemesh_scan_dev``; the source image stays inside the projector); ``source_images=True`` composes it from
         the public steps instead and returns the merged cloud's images under ``source``.  ``origin`` / ``endpoints`` /
-        ``endpoints_scene`` / ``scan_index``: as for :meth:`mesh`; a return model is applied to the render that stands -- after
-        a re-run, never to the speculative one."""
+        ``endpoints_scene`` / ``scan_index``: as for :meth:`mesh`; a return model and a noise model are applied to the render
+        that stands -- after a re-run, never to the speculative one."""
         if origin is None:
             origin = self.origin
         if self.vol_bnds is None:
@@ -407,7 +420,10 @@ class DeviceDeform:
                 out = self.scene.alloc_outputs(self.n_rays, label_image=True)
             if self._returns and scan_index is None:
                 raise ValueError("DeviceDeform.mergemesh: a return model needs scan_index, the output scan's index in its sequence")
+            if self._noise and scan_index is None:
+                raise ValueError("DeviceDeform.mergemesh: a noise model needs scan_index, the output scan's index in its sequence")
             rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays, self.device)
+            rout = self._noise.render_into(rout, self.n_rays, self.device)
             first, again, more = (self._mm_composed if source_images else self._mm_native)(
                 mm, cloud, seq, _chain.origin3(origin), _chain.out_ptrs(rout), st)
             pred, vol = mm.pred, None
@@ -435,6 +451,7 @@ class DeviceDeform:
                 vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
                 again(vol)
             more.update(self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st))
+            more.update(self._noise.apply(rout, scan_index, origin, st))
             self._mounting.to_target(rout, out, st)
             res = self._result(out, rout, vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
                                vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol, **more)
@@ -499,7 +516,11 @@ class DeviceDeform:
         ``index`` images, ``back_points`` [t_H*t_W,3] f64 and -- with ``pack`` -- ``bin`` / ``label_file``.
         The reference's ``cp`` path always holds float64 points (``apply_pose``, laserscan.py:98-104) and goldens F12 / F12b pin
         that; float32 clouds with ``preserve_float`` are re-projected in float64 here as well (numpy would stay in float32).
-        ``cp`` renders no surface, so there is no incidence angle: with a return model it raises ``ValueError``."""
+        ``cp`` renders no surface, so there is no incidence angle: with a return model it raises ``ValueError``; it renders
+        no ray either, so there is no origin to jitter a range about: with a noise model it raises as well."""
+        if self._noise:
+            raise ValueError("DeviceDeform.cp: the target sensor has a noise_model, but cp renders no ray (no origin to jitter "
+                             "a range about): use mesh or mergemesh, or a target file without the key")
         if self._returns:
             raise ValueError("DeviceDeform.cp: the target sensor has a return_model, but cp renders no surface (no hit triangle, "
                              "no incidence angle): use mesh or mergemesh, or a target file without the key")

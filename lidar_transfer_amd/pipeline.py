@@ -323,11 +323,16 @@ class FusionScanPipeline:
     ``None`` or all-default: nothing changes).  Every ``submit*`` then needs ``scan_index``, the output scan's index in its
     sequence -- the random drops are a function of it, not of the ticket or the chain --; the model is applied once on the
     chain's stream behind the render that stands and before the hits go into the target's frame (no host wait is added),
-    and a result carries ``incidence`` and ``drop`` [n] as well (``post.return_model``)."""
+    and a result carries ``incidence`` and ``drop`` [n] as well (``post.return_model``).
+
+    ``noise``: the target sensor's :class:`~lidar_transfer_amd.config.NoiseModel` (``SensorModel.noise_model()``; ``None`` or
+    all-default: nothing changes).  It needs ``scan_index`` in the same way and is applied once, behind the return model --
+    whose range gate a measured range must stay inside -- on the chain's stream, about the scan's ray origin and before the
+    frame change; a result carries ``range_error`` and ``noise_state`` [n] as well (``post.noise_model``)."""
 
     def __init__(self, vol_bnds, voxel_size, fov_up, fov_down, rays, H, chains=3, device=None, merge=True,
                  label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None, grid=None,
-                 returns=None):
+                 returns=None, noise=None):
         import queue
         import threading
         import weakref
@@ -346,6 +351,8 @@ class FusionScanPipeline:
         self.mount, self.origin = self._mounting.pair, self._mounting.origin
         self._returns = _chain.Returns(returns, "FusionScanPipeline")
         self.returns = self._returns.model
+        self._noise = _chain.Noise(noise, self.returns, "FusionScanPipeline")
+        self.noise = self._noise.model
         self.rayset = RaySet(rays, H, pose=self._mounting.P, grid=grid)  # one read-only ray set for all chains
         self.n_rays = self.rayset.n_rays
         self.label_image = bool(label_image)
@@ -395,9 +402,11 @@ class FusionScanPipeline:
                     raise RuntimeError("FusionScanPipeline: constructed with fixed_volume=False (submit_mergemesh only)")
                 rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays,
                                                  self.device)
+                rout = self._noise.render_into(rout, self.n_rays, self.device)
                 scan = self._scan_clouds if kind == "clouds" else self._scan_images
                 keep = scan(ch, items, _chain.origin3(origin), _chain.out_ptrs(rout))
                 seen = self._returns.apply(rout, scan_index, ch["scene"], self.rayset.rays, ch["stream"], self.label_image)
+                seen.update(self._noise.apply(rout, scan_index, origin, ch["stream"], self.label_image))
                 return self._finish(ch, out, rout, ch["mesh"], keep, items, **seen)
         except BaseException:
             if kind == "mergemesh":
@@ -468,10 +477,11 @@ class FusionScanPipeline:
             sensor_t = (a["H"], self.n_rays // a["H"], self._src_fov[0], self._src_fov[1])
             dd = DeviceDeform(sensor_s, sensor_t, None, a["voxel_size"], beam_angles=self._beam_angles, device=self.device.index,
                               merge=a["merge"], mesh_volume=False, rayset=self.rayset, mm_state=self._mm_state,
-                              transformation=self.mount, returns=self.returns)
+                              transformation=self.mount, returns=self.returns, noise=self.noise)
             ch["deform"] = dd
         got = dd.mergemesh(clouds, origin, pack=False, out=out, seq=seq, scan_index=scan_index)
-        more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after") + (_chain.Returns.KEYS if self._returns else ())}
+        more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after") + (_chain.Returns.KEYS if self._returns else ())
+                + (_chain.Noise.KEYS if self._noise else ())}
         if self.mount is not None:   # (the chain's DeviceDeform has taken the hits into the target's frame)
             more["endpoints_scene"] = got["endpoints_scene"]
         return self._finish(ch, out, out, dd.mesh_obj, [got.get("source"), got.get("_keep")], clouds, **more)
@@ -504,8 +514,9 @@ class FusionScanPipeline:
     def _submit(self, kind, items, origin, out, inputs_ready, seq=None, scan_index=None):
         import threading
         torch = self._torch
-        if self._returns and scan_index is None:
-            raise ValueError("FusionScanPipeline: a return model needs scan_index, the output scan's index in its sequence")
+        if (self._returns or self._noise) and scan_index is None:
+            raise ValueError("FusionScanPipeline: a return model or a noise model needs scan_index, the output scan's index in "
+                             "its sequence")
         if not inputs_ready:
             torch.cuda.current_stream(self.device).synchronize()  # (see the class docstring)
         with self._lock:
@@ -558,8 +569,8 @@ class FusionScanPipeline:
             items.append((c[0], c[1], c[2]))
         if not items:   # (before the sequence number moves: no scan would ever take it, and every later one would wait for it)
             raise ValueError("FusionScanPipeline.submit_mergemesh: no clouds")
-        if self._returns and scan_index is None:   # (before the sequence number moves, like the empty list)
-            raise ValueError("FusionScanPipeline.submit_mergemesh: a return model needs scan_index")
+        if (self._returns or self._noise) and scan_index is None:   # (before the sequence number moves, like the empty list)
+            raise ValueError("FusionScanPipeline.submit_mergemesh: a return model or a noise model needs scan_index")
         seq, self._mm_seq = self._mm_seq, self._mm_seq + 1
         return self._submit("mergemesh", items, origin, out, inputs_ready, seq=seq, scan_index=scan_index)
 

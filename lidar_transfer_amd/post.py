@@ -126,6 +126,62 @@ def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label
     return extra
 
 
+def noise_model(origin, model, scan, out, gate=None, range_error=True, state=True, label_image=True, stream=None):
+    """The target sensor's noise model (``lt_noise_model_dev``) on a rendered scan, in place and asynchronous on
+    ``stream`` (default the current one).  Per return (``tri >= 0`` and ``range > 0``): the range is jittered by ``(range_sigma
+    + range_sigma_rel * range) * z`` and put on the ``range_resolution`` grid, the end point is scaled about ``origin`` to
+    the new range, the remission is jittered by ``remission_sigma * z'``, clamped to [0, 1] and put on ``remission_levels``
+    levels; ``z``, ``z'``: sums of twelve 16-bit uniforms, a pure function of ``(seed, scan, cell)``.  A return whose new
+    range is not positive or lies outside ``gate`` becomes the miss the render writes; every other cell is not touched.  The
+    call is read-modify-write: ONCE per rendered scan, behind the return model, before the frame change, evaluation and
+    packing.  ``origin``: three numbers, where the scan's rays start in the scene; ``model``: a
+    :class:`~lidar_transfer_amd.config.NoiseModel`; ``scan``: the output scan's index in its sequence; ``out``: the render's
+    images (``Scene.alloc_outputs``' keys; ``tri`` and ``range`` are needed, the others may be absent or ``None``); ``gate``:
+    the sensor's :class:`~lidar_transfer_amd.config.ReturnModel` or ``None``; ``label_image``: whether ``endcolors`` is the
+    [n] label image or [n, 3].  ``range_error`` / ``state``: ``True`` -- a fresh [n] float32 / uint8 tensor, a tensor -- that
+    one, ``None`` -- not wanted.  Returns ``dict(range_error=..., noise_state=...)``: ``float32(new - old)`` of every noised
+    return (0 elsewhere) and every cell's state (0 untouched, 1 noised, 2 lost)."""
+    import torch
+
+    from .config import NoiseModel, ReturnModel
+    if not isinstance(model, NoiseModel):
+        raise ValueError("model: a lidar_transfer_amd.config.NoiseModel")
+    if gate is not None and not isinstance(gate, ReturnModel):
+        raise ValueError("gate: a lidar_transfer_amd.config.ReturnModel or None")
+    tri, rng = out.get("tri"), out.get("range")
+    if tri is None or rng is None:
+        raise ValueError("out: the render's `tri` and `range` images are needed")
+    n = tri.numel()
+    dev = tri.device
+    want = dict(endpoints=(torch.float32, 3 * n), endcolors=(torch.int32, n if label_image else 3 * n),
+                range=(torch.float32, n), endrem=(torch.float32, n), tri=(torch.int32, n))
+    ptr = {}
+    for key, (dt, numel) in want.items():
+        t = out.get(key)
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != numel or t.device != dev):
+            raise ValueError(f"out[{key!r}]: contiguous {dt} CUDA tensor with {numel} elements on the device of `tri`")
+        ptr[key] = t.data_ptr() if t is not None else None
+    extra = {}
+    for key, t, dt in (("range_error", range_error, torch.float32), ("noise_state", state, torch.uint8)):
+        if t is True:
+            t = torch.empty((n,), dtype=dt, device=dev)
+        elif t is False:
+            t = None
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != dev):
+            raise ValueError(f"{key}: contiguous {dt} CUDA tensor [n] on the device of `tri`")
+        extra[key] = t
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    args = model.args(gate)
+    o = (C.c_float * 3)(*[float(x) for x in origin])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lt_noise_model_dev(
+            o, n, C.byref(args), int(scan) & 0xFFFFFFFF, ptr["endpoints"], ptr["endcolors"], ptr["range"], ptr["endrem"],
+            ptr["tri"], extra["range_error"].data_ptr() if extra["range_error"] is not None else None,
+            extra["noise_state"].data_ptr() if extra["noise_state"] is not None else None,
+            _lib.LT_TRACE_LABEL_IMAGE if label_image else 0, C.c_void_p(st.cuda_stream)), "lt_noise_model_dev")
+    return extra
+
+
 def pack_scan(back_points, label_image, remissions, index=None):
     """Filtering + packing of ``MultiSemLaserScan.write`` (auxiliary/laserscan.py:1133-1160): returns
     ``(bin [N,4] float32, label [N] uint32)`` -- byte-for-byte what the reference writes to

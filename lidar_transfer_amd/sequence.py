@@ -39,6 +39,17 @@ def format_return_totals(totals):
     return "Returns: " + ", ".join(f"{name} {int(n)}" for name, n in zip(RETURN_CODES, totals))
 
 
+#: what the states of a noise model's ``noise_state`` image mean, in state order (``noise_totals``, the CLI's closing line)
+NOISE_STATES = ("untouched", "noised", "lost")
+
+
+def format_noise_totals(totals, rms):
+    """the CLI's closing line of a run with a noise model: ``Noise: untouched N, noised N, lost N, range error RMS X m`` (the
+    root mean square of ``range_error`` over the noised cells; ``None``: there was none)"""
+    return "Noise: " + ", ".join(f"{name} {int(n)}" for name, n in zip(NOISE_STATES, totals)) + \
+        ", range error RMS " + ("n/a" if rms is None else f"{float(rms):.6f} m")
+
+
 def sensor_tuple(s):
     """``(H, W, fov_up, fov_down)`` of a :class:`lidar_transfer_amd.config.SensorModel` (or such a tuple itself)"""
     if hasattr(s, "fov_up"):
@@ -129,7 +140,14 @@ class SequenceTransfer:
     output scan of ``mesh`` / ``mergemesh`` behind its render, with the scan's FILE index as the random rule's ``scan`` --
     evaluation and the written files see what the target sensor sees --; the cells per code are summed on the device and
     read once at the end of :meth:`run` (``summary["return_totals"]``, six numbers in :data:`RETURN_CODES`' order).  ``cp``
-    renders no surface: with such a target it raises ``ValueError``; so does a source sensor with the key."""
+    renders no surface: with such a target it raises ``ValueError``; so does a source sensor with the key.
+    A target ``SensorModel`` with a ``noise_model`` block (kept as ``noise``; ``None``: none) has it applied in the same way
+    and with the same ``scan``, behind the return model and about the target's position in the scene: evaluation
+    -- either mode; the target view itself is never noised, so its MSE contains the noise -- and the written files see what
+    the target sensor reports.  The cells per state and the squared ``range_error`` are summed on the device and read once
+    at the end of :meth:`run` (``summary["noise_totals"]``, three numbers in :data:`NOISE_STATES`' order, and
+    ``summary["range_error_rms"]`` over the noised cells).  ``cp`` renders no ray: with such a target it raises
+    ``ValueError``; so does a source sensor with the key."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -152,6 +170,10 @@ class SequenceTransfer:
         if self.returns is not None and self.adaption == "cp":
             raise ValueError("adaption cp renders no surface (no hit triangle, no incidence angle): the target sensor's "
                              "return_model cannot be applied -- use mesh or mergemesh, or a target file without the key")
+        self.noise = getattr(target_sensor, "noise_model", lambda: None)()
+        if self.noise is not None and self.adaption == "cp":
+            raise ValueError("adaption cp renders no ray (no origin to jitter a range about): the target sensor's noise_model "
+                             "cannot be applied -- use mesh or mergemesh, or a target file without the key")
         self.chains = 1 if self.adaption == "cp" else int(chains)     # `cp` always runs on one chain
         self.fusion, self.out_dir = fusion, out_dir
         self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
@@ -206,7 +228,7 @@ class SequenceTransfer:
             rayset = None
             every = dict(beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
                          transformation=self.mount, t_beam_table=m.beam_table, t_sector=m.sector, t_beam_azimuth=m.beam_azimuth,
-                         returns=self.returns)
+                         returns=self.returns, noise=self.noise)
             for c in range(self.chains):
                 if self.adaption == "cp":
                     dd = DeviceDeform(self.source_sensor, self.target_sensor, None, **every)
@@ -215,7 +237,7 @@ class SequenceTransfer:
                                       None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
                                       mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm, **every)
                     rayset = dd.rayset
-                ch = dict(dd=dd, ev=None, q=None, thread=None, totals=None, codes=None,
+                ch = dict(dd=dd, ev=None, q=None, thread=None, totals=None, codes=None, noise_totals=None,
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
                 if target_view:
                     ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx,
@@ -262,6 +284,13 @@ class SequenceTransfer:
                         ch["codes"] = torch.arange(len(RETURN_CODES), dtype=torch.uint8, device=self.device)
                         ch["totals"] = torch.zeros(len(RETURN_CODES), dtype=torch.int64, device=self.device)
                     ch["totals"] += (out["drop"].unsqueeze(1) == ch["codes"]).sum(0)
+                if self.noise is not None:           # cells per state and the squared range error (float64), summed likewise
+                    if ch["noise_totals"] is None:
+                        ch["states"] = torch.arange(len(NOISE_STATES), dtype=torch.uint8, device=self.device)
+                        ch["noise_totals"] = torch.zeros(len(NOISE_STATES), dtype=torch.int64, device=self.device)
+                        ch["noise_sq"] = torch.zeros((), dtype=torch.float64, device=self.device)
+                    ch["noise_totals"] += (out["noise_state"].unsqueeze(1) == ch["states"]).sum(0)
+                    ch["noise_sq"] += torch.linalg.vector_norm(out["range_error"], dtype=torch.float64) ** 2
                 if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
                     scan = ch["ev"].target_view if self.evaluate_mode == "target" else ch["ev"].source_scan
                     src = scan(*job["raw"], stream=st)
@@ -383,7 +412,18 @@ class SequenceTransfer:
                         ch["stream"].synchronize()
                         totals = [a + int(b) for a, b in zip(totals, ch["totals"].cpu().tolist())]
                         ch["totals"] = None          # (the next run starts its own)
-            self.summary = dict(return_totals=totals, scans=n_done, chains=self.chains, adaption=self.adaption, fusion=self.fusion,
+            noise_totals = rms = None
+            if self.noise is not None:
+                noise_totals, sq_sum = [0] * len(NOISE_STATES), 0.0
+                for ch in self._chains:
+                    if ch["noise_totals"] is not None:
+                        ch["stream"].synchronize()
+                        noise_totals = [a + int(b) for a, b in zip(noise_totals, ch["noise_totals"].cpu().tolist())]
+                        sq_sum += float(ch["noise_sq"])
+                        ch["noise_totals"] = ch["noise_sq"] = None       # (the next run starts its own)
+                rms = float(np.sqrt(sq_sum / noise_totals[1])) if noise_totals[1] else None
+            self.summary = dict(return_totals=totals, noise_totals=noise_totals, range_error_rms=rms, scans=n_done,
+                                chains=self.chains, adaption=self.adaption, fusion=self.fusion,
                                 mounted=self.mounted, beam_model=self.beam_model, azimuth_model=self.azimuth_model,
                                 beam_azimuth=self.beam_azimuth is not None,
                                 mm_stats=dict(self._mm.stats) if self._mm is not None else None,
