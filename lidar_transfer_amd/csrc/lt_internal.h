@@ -150,6 +150,7 @@ struct lt_tsdf {
   int* colinfo;         // [dim_x * dim_y] per integrate call: image column px of the voxel column, or -1 = dead
   float* colmax;        // [cap_w] per integrate call: largest depth of every image column
   int cap_w;
+  int walk_w;           // image width of the volume's last column walk (0: none yet; lt_debug_tsdf_walk_table)
   float2* dct;          // [cap_dct] per integrate call: (depth, colour) of pixel (row, px) at [px * im_h + row] -- the voxels of
   size_t cap_dct;       // a column walk read consecutive rows of ONE image column: contiguous here, a line apart in the image
   // the pixel-centric integrate of a fresh volume (k_tsdf_integrate_pix, lt_tsdf.hip)

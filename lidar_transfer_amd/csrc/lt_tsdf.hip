@@ -350,18 +350,19 @@ __device__ __forceinline__ bool tsdf_band_candidate(int z, const col_plain& C, c
 
 // z range [z0, z1) of the voxel column (cx, cy) that can lie inside the vertical field of view -- conservative: the
 // voxels left out would take tsdf_voxel's sine exit -- pt_z in [rho tan(fov_down) - pad, rho tan(fov_up) + pad].  The
-// whole column for y = dim_y - 1 (its voxels may belong to another (x, y) by the reference's float index) and when the
-// field of view is too steep for tangents.
+// whole column where the caller says so (`whole`, k_tsdf_columns: its voxels may belong to another (x, y) by the reference's
+// float index) and when the field of view is too steep for tangents.
 struct col_geom {
   float tan_up, tan_down;
   int tan_ok;
 };
-__device__ __forceinline__ void col_zrange(const col_geom& G, const tsdf_volume& Vol, int cx, int cy, int& z0, int& z1) {
+__device__ __forceinline__ void col_zrange(const col_geom& G, const tsdf_volume& Vol, int cx, int cy, bool whole, int& z0,
+                                           int& z1) {
   z0 = 0;
   z1 = Vol.dim_z;
   const float pt_x = __fmaf_rn((float)cx, Vol.voxel_size, Vol.ox), pt_y = __fmaf_rn((float)cy, Vol.voxel_size, Vol.oy);
   const float rho = sqrtf(pt_x * pt_x + pt_y * pt_y);
-  if (cy != Vol.dim_y - 1 && G.tan_ok && rho > axis_rho_limit(Vol.oz, Vol.voxel_size, Vol.dim_z)) {  // (LT_AXIS_RHO: whole column)
+  if (!whole && G.tan_ok && rho > axis_rho_limit(Vol.oz, Vol.voxel_size, Vol.dim_z)) {  // (LT_AXIS_RHO: whole column)
     const float pad = 2.0f * Vol.voxel_size + 1e-3f * rho;
     const float zl = (rho * G.tan_down - pad - Vol.oz) / Vol.voxel_size, zh = (rho * G.tan_up + pad - Vol.oz) / Vol.voxel_size;
     z0 = max(0, (int)floorf(fminf(fmaxf(zl, -1.0f), (float)Vol.dim_z)));
@@ -434,16 +435,22 @@ __global__ __launch_bounds__(256) void k_tsdf_columns(tsdf_volume Vol, tsdf_view
   const float rho_lo = rho * 0.9999995f;
   const float cm = colmax[px];
   const bool dead = (cm - rho_lo) < -Vw.trunc_margin;
-  // -2: a dead column with y = dim_y - 1 -- walked all the same, voxel by voxel (the reference's float index can put
-  // voxels of the (x + 1, -1) "column" there), each finding its own px
-  const int info = dead ? (y == Vol.dim_y - 1 ? -2 : -1) : px;
+  // -2: a dead column that is walked all the same, whole, voxel by voxel, each voxel finding its own px -- the columns whose
+  // voxel indices the reference's float decomposition (:95-98) can give to another (x, y): y = dim_y - 1 (the (x + 1, -1)
+  // "column") and, by the rule of k_wd_keys, every column one of whose ENDS does not decompose to x.  Beyond 2^24 voxels with
+  // an odd dim_y * dim_z that is a column with y = 0 (its first voxel becomes (x - 1, dim_y, 0)), beyond 2^25 with a small
+  // dim_z one with y = dim_y - 2: a position with another azimuth and range, which this column's own death says nothing about.
+  const float dyz = (float)(Vol.dim_y * Vol.dim_z);
+  const int i0 = c * Vol.dim_z, i1 = c * Vol.dim_z + Vol.dim_z - 1;
+  const bool whole = y == Vol.dim_y - 1 || floorf(((float)i0) / dyz) != (float)x || floorf(((float)i1) / dyz) != (float)x;
+  const int info = dead ? (whole ? -2 : -1) : px;
   colinfo[c] = info;
   // the walk the integrate kernel will do in this column -- its z range, whether it is plain (col_plain_of), the
   // column's fma(pt_y, pt_y, pt_x^2) -- computed HERE, one lane per column, instead of by the 16 lanes that walk the
   // column there (two square roots and four IEEE divisions per column: a sixth of that kernel's vector instructions)
   if (info != -1) {
     int z0, z1;
-    col_zrange(G, Vol, x, y, z0, z1);
+    col_zrange(G, Vol, x, y, whole, z0, z1);
     colinfo[c] = info;  // (col_plain_of reads it)
     const col_plain C = col_plain_of(x, y, z0, z1, Vol, colinfo);
     colz[c] = (unsigned)z0 | ((unsigned)z1 << 15) | (C.plain ? 0x80000000u : 0u);  // z < 2^15 (lt_tsdf_create)
@@ -460,12 +467,46 @@ __global__ __launch_bounds__(256) void k_tsdf_columns(tsdf_volume Vol, tsdf_view
 // FOUR columns at a time, 16 lanes each with z along the lanes (a column's walk is a chain of dependent loads -- table
 // entry, depth pixel, the voxel's fields -- and only the z range inside the field of view, 20 - 60 voxels, has work:
 // one column per wave iteration left the kernel latency-bound at 0.66 ms for the default volume).  Columns with
-// y = dim_y - 1 are always walked, whole: they are where the reference's float voxel index can misplace a voxel into
-// the (x + 1, -1) column, which the table does not describe -- tsdf_voxel() handles every voxel by the reference's own
-// decomposition.  The signs of the values written update the column's sign bits (bit b of word k = voxel z = 64 k + b
-// is NOT above the level 0), which marching cubes reads instead of the float field; a 16-aligned chunk of z lies inside one word and
-// only this quarter wave works on this column, so the read-modify-write needs no atomic.
-template <bool MERGE>
+// y = dim_y - 1 -- and the columns with an end that does not decompose to its x, k_tsdf_columns -- are always walked, whole:
+// they are where the reference's float voxel index can misplace a voxel into a column the table does not describe, (x + 1, -1)
+// or (x - 1, dim_y) -- tsdf_voxel() handles every voxel by the reference's own decomposition.  The signs of the values
+// written update the column's sign bits (bit b of word k = voxel z = 64 k + b is NOT above the level 0), which marching cubes
+// reads instead of the float field; a 16-aligned chunk of z lies inside one word and only this quarter wave works on this
+// column, so the read-modify-write needs no atomic.
+//
+// Words of the walk's counters (LIDARHIP_DEBUG_TSDF; the VCOUNT = true instantiations only): which PATHS the launch took
+// (lt_debug_tsdf_walk_paths; tests/test_tsdf_walk_paths_gpu.py).  They sit behind the per-wave stamps in the debug buffer
+// (LT_WALKC_AT); counted, never read by the kernel.  A chunk = 64 voxel columns, a quad = four of its live columns, one per
+// quarter wave.
+#define LT_WALKC_CHUNKS 0        // chunks walked / left at their chunk_live flag
+#define LT_WALKC_SKIPPED 1
+#define LT_WALKC_COLS 2          // columns walked = M2 + PLAIN + NONPLAIN = FRESH + WRITTEN = BAND + DIRECT
+#define LT_WALKC_COLS_M2 3       // ... dead, walked whole (colinfo -2)
+#define LT_WALKC_COLS_PLAIN 4
+#define LT_WALKC_COLS_NONPLAIN 5
+#define LT_WALKC_COLS_FRESH 6
+#define LT_WALKC_COLS_WRITTEN 7
+#define LT_WALKC_QUADS_IDLE 8    // quads with a quarter wave that has no column
+#define LT_WALKC_COLS_BAND 9
+#define LT_WALKC_COLS_DIRECT 10
+#define LT_WALKC_MIXED 11        // quads with band AND direct quarter waves
+#define LT_WALKC_BAND_VOX 12     // voxels asked of the band test / its candidates
+#define LT_WALKC_BAND_CAND 13
+#define LT_WALKC_FLUSH_FULL 14   // flushes of 64 candidates / of the rest at the end of a wave; the largest rest
+#define LT_WALKC_FLUSH_TAIL 15
+#define LT_WALKC_TAIL_MAX 16
+#define LT_WALKC_DIRECT_VOX 17   // voxels evaluated directly
+#define LT_WALKC_CODE1 18        // voxels written above the level 0 / not above it (either way)
+#define LT_WALKC_CODE2 19
+#define LT_WALKC_STAMP_FRESH 20  // columns stamped: a fresh one / one whose older range is merged
+#define LT_WALKC_STAMP_MERGED 21
+#define LT_WALKC_TRIPS_MAX 22    // the largest trip count of a quad
+#define LT_WALKC_CHUNKS_MAX 23   // the largest number of chunks one workgroup took (dead ones included)
+#define LT_WALKC_SIGN_HI 24      // writes to a sign word of index >= 1
+#define LT_WALKC_N 32
+#define LT_WALKC_AT ((size_t)LT_TSDF_DBG_WAVES * 2)
+
+template <bool MERGE, bool VCOUNT = false>
 __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
     tsdf_volume Vol, tsdf_view Vw, tsdf_marks Mk, const float* __restrict__ rem_im, const float2* __restrict__ dct,
     const int* __restrict__ colinfo, const int* __restrict__ chunk_live, const unsigned* __restrict__ colz,
@@ -481,6 +522,8 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
   // (kA, kB: the band test's row = pitch * kA + kB, from the host: a quarter of a million waves need not divide for them)
   int qn = 0;  // (wave-uniform)
+  unsigned long long* const cnt = VCOUNT ? dbg + LT_WALKC_AT : nullptr;
+  int n_taken = 0;
   auto flush = [&](int n) {  // the exact evaluation + update of the queue's last n (<= 64) candidates, one per lane
     __builtin_amdgcn_wave_barrier();
     if (lane < n) {
@@ -488,11 +531,21 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
       const int col = q_col[wv][e], z = q_z[wv][e];
       const col_plain Cq = {true, q_px[wv][e], q_rho2[wv][e], col};
       const int code = tsdf_voxel<MERGE>(col * Vol.dim_z + z, Vol, Vw, rem_im, colinfo, true, Cq, z, dct);
+      if constexpr (VCOUNT) {
+        if (code) atomicAdd(cnt + (code == 2 ? LT_WALKC_CODE2 : LT_WALKC_CODE1), 1ull);
+        if (code && (z >> 6) >= 1) atomicAdd(cnt + LT_WALKC_SIGN_HI, 1ull);
+      }
       if (code) {  // the sign of the value written -> the column's sign bit (other lanes may hold voxels of the same word)
         unsigned long long* w = Mk.sign_bits + (size_t)col * Mk.words_z + (z >> 6);
         const unsigned long long bit = 1ull << (z & 63);
         if (code == 2) atomicOr(w, bit);
         else atomicAnd(w, ~bit);
+      }
+    }
+    if constexpr (VCOUNT) {
+      if (lane == 0) {
+        atomicAdd(cnt + (n == 64 ? LT_WALKC_FLUSH_FULL : LT_WALKC_FLUSH_TAIL), 1ull);
+        if (n != 64) atomicMax(cnt + LT_WALKC_TAIL_MAX, (unsigned long long)n);
       }
     }
     qn -= n;
@@ -502,6 +555,10 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
   // cost of a chunk ranges from nothing to 200 us (a wall: every voxel of every column a candidate), and with a chunk per
   // wave the launch ended in a 110 us tail of a few such waves (per-wave stamps: tools/tsdf_wave_times.py)
   for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+    if constexpr (VCOUNT) {
+      ++n_taken;
+      if (threadIdx.x == 0) atomicAdd(cnt + (chunk_live[chunk] ? LT_WALKC_CHUNKS : LT_WALKC_SKIPPED), 1ull);
+    }
     if (!chunk_live[chunk]) continue;  // (uniform: a scalar load)
     const int c = chunk * 64 + lane;
     bool live = false, written = false;
@@ -541,6 +598,20 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
       const bool band = MERGE && fresh && C.plain && kA == kA;  // (per quarter wave; kA is NaN when the test is off)
 #endif
       const bool any_direct = __ballot(bit >= 0 && !band) != 0ull;  // (wave-uniform: usually false on a fresh volume)
+      if constexpr (VCOUNT) {
+        const bool any_band = __ballot(bit >= 0 && band) != 0ull, any_idle = __ballot(bit < 0) != 0ull;
+        if (lane == 0) {
+          if (any_idle) atomicAdd(cnt + LT_WALKC_QUADS_IDLE, 1ull);
+          if (any_band && any_direct) atomicAdd(cnt + LT_WALKC_MIXED, 1ull);
+          atomicMax(cnt + LT_WALKC_TRIPS_MAX, (unsigned long long)max(trips, 0));
+        }
+        if (bit >= 0 && gl == 0) {
+          atomicAdd(cnt + LT_WALKC_COLS, 1ull);
+          atomicAdd(cnt + (C.px == -2 ? LT_WALKC_COLS_M2 : (C.plain ? LT_WALKC_COLS_PLAIN : LT_WALKC_COLS_NONPLAIN)), 1ull);
+          atomicAdd(cnt + (fresh ? LT_WALKC_COLS_FRESH : LT_WALKC_COLS_WRITTEN), 1ull);
+          atomicAdd(cnt + (band ? LT_WALKC_COLS_BAND : LT_WALKC_COLS_DIRECT), 1ull);
+        }
+      }
       for (int k0 = 0; k0 < trips; k0 += 3) {
         // band columns: the candidate tests of three chunks of z at once (their loads in flight together: a wave's life
         // is a chain of load round trips, and this makes it a third as long)
@@ -551,6 +622,15 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
             const int z = (z0 & ~15) + 16 * (k0 + u) + gl;
             const bool c1 = tsdf_band_candidate(min(z, Vol.dim_z - 1), C, Vol, Vw, kA, kB, dct);
             cd[u] = c1 && z >= z0 && z < z1;
+          }
+        }
+        if constexpr (VCOUNT) {
+#pragma unroll
+          for (int u = 0; u < 3; ++u) {
+            const int z = (z0 & ~15) + 16 * (k0 + u) + gl;
+            const unsigned long long asked = __ballot(band && z >= z0 && z < z1), yes = __ballot(cd[u]);
+            if (lane == 0 && asked) atomicAdd(cnt + LT_WALKC_BAND_VOX, (unsigned long long)__popcll(asked));
+            if (lane == 0 && yes) atomicAdd(cnt + LT_WALKC_BAND_CAND, (unsigned long long)__popcll(yes));
           }
         }
 #pragma unroll
@@ -567,6 +647,15 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
             const unsigned long long wrote_w = __ballot(code != 0), neg_w = __ballot(code == 2);
             wrote = (wrote_w >> (16 * grp)) & 0xFFFFull;
             neg = (neg_w >> (16 * grp)) & 0xFFFFull;
+            if constexpr (VCOUNT) {
+              const unsigned long long direct_w = __ballot(!band && z >= z0 && z < z1);
+              if (lane == 0) {
+                atomicAdd(cnt + LT_WALKC_DIRECT_VOX, (unsigned long long)__popcll(direct_w));
+                atomicAdd(cnt + LT_WALKC_CODE1, (unsigned long long)(__popcll(wrote_w) - __popcll(neg_w)));
+                atomicAdd(cnt + LT_WALKC_CODE2, (unsigned long long)__popcll(neg_w));
+              }
+              if (wrote && gl == 0 && (zc >> 6) >= 1) atomicAdd(cnt + LT_WALKC_SIGN_HI, 1ull);
+            }
           }
           const unsigned long long cand_w = __ballot(cand);
           const unsigned long long cands = (cand_w >> (16 * grp)) & 0xFFFFull;
@@ -600,10 +689,14 @@ __global__ __launch_bounds__(256) LT_TSDF_WAVES_ATTR void k_tsdf_integrate_cols(
         Mk.col_zw[n_cols + cc] = (unsigned)(wz_hi + 1);
         Mk.col_epoch[cc] = Mk.epoch;
         Mk.chunk_epoch[cc >> 6] = Mk.epoch;  // (what reset and marching cubes look at first)
+        if constexpr (VCOUNT) atomicAdd(cnt + (fresh ? LT_WALKC_STAMP_FRESH : LT_WALKC_STAMP_MERGED), 1ull);
       }
     }
   }
   if (qn > 0) flush(qn);
+  if constexpr (VCOUNT) {
+    if (threadIdx.x == 0) atomicMax(cnt + LT_WALKC_CHUNKS_MAX, (unsigned long long)n_taken);
+  }
   if (dbg && (threadIdx.x & 63) == 0) {
     const size_t w = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) % LT_TSDF_DBG_WAVES;
     dbg[2 * w] = t_dbg;
@@ -1888,7 +1981,9 @@ extern "C" int lt_tsdf_integrate_dev(lt_tsdf* t, const float* color_im, const fl
   const unsigned nbc = (unsigned)min((n_cols + 63) / 64, env_blocks > 0 ? env_blocks : (1 << 20));  // a chunk of 64 columns each
   // debug (LIDARHIP_DEBUG_TSDF=1, tools/tsdf_wave_times.py): start / duration of every wave at 100 MHz
   static const bool want_dbg = getenv("LIDARHIP_DEBUG_TSDF") != nullptr;
-  if (want_dbg && !g_tsdf_dbg) LT_HIP(hipMalloc((void**)&g_tsdf_dbg, (size_t)LT_TSDF_DBG_WAVES * 2 * sizeof(unsigned long long)));
+  // ... and the counted instantiation: the paths the walk took (LT_WALKC_*, lt_debug_tsdf_walk_paths), behind the stamps
+  if (want_dbg && !g_tsdf_dbg) LT_HIP(hipMalloc((void**)&g_tsdf_dbg, (LT_WALKC_AT + LT_WALKC_N) * sizeof(unsigned long long)));
+  if (want_dbg) LT_HIP(hipMemsetAsync(g_tsdf_dbg + LT_WALKC_AT, 0, LT_WALKC_N * sizeof(unsigned long long), stream));
   unsigned long long* dbg = g_tsdf_dbg;
   const float fov_abs = fabsf(F.fu) + fabsf(F.fd);
   // the band test's pitch polynomial is good to 1e-5 rad for |sin| <= 0.5 and its row choice has +-0.25 row of slack: it is
@@ -1896,12 +1991,18 @@ extern "C" int lt_tsdf_integrate_dev(lt_tsdf* t, const float* color_im, const fl
   // kA = NaN switches it off and every voxel takes the exact evaluation
   const bool band_ok = fabsf(F.su) <= 0.5f && fabsf(F.sd) <= 0.5f && fov_abs / (float)im_h >= 2e-4f;
   const float kA = band_ok ? -(float)im_h / fov_abs : NAN, kB = (float)im_h * (1.0f - fabsf(F.fd) / fov_abs);
-  if (flags & LT_TSDF_MERGE)
-    hipLaunchKernelGGL(k_tsdf_integrate_cols<true>, dim3(nbc), dim3(256), 0, stream, Vol, Vw, Mk, rem_im, t->dct, t->colinfo,
-                       chunk_live, colz, colrho2, kA, kB, t->all_dirty, dbg);
-  else
-    hipLaunchKernelGGL(k_tsdf_integrate_cols<false>, dim3(nbc), dim3(256), 0, stream, Vol, Vw, Mk, rem_im, t->dct, t->colinfo,
-                       chunk_live, colz, colrho2, kA, kB, t->all_dirty, dbg);
+  auto walk = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(nbc), dim3(256), 0, stream, Vol, Vw, Mk, rem_im, t->dct, t->colinfo, chunk_live, colz,
+                       colrho2, kA, kB, t->all_dirty, dbg);
+  };
+  if (flags & LT_TSDF_MERGE) {
+    if (want_dbg) walk(k_tsdf_integrate_cols<true, true>);
+    else walk(k_tsdf_integrate_cols<true, false>);
+  } else {
+    if (want_dbg) walk(k_tsdf_integrate_cols<false, true>);
+    else walk(k_tsdf_integrate_cols<false, false>);
+  }
+  t->walk_w = im_w;
   LT_HIP(hipGetLastError());
   return LT_OK;
 }
@@ -2025,6 +2126,38 @@ extern "C" int lt_debug_tsdf_wedge(lt_tsdf* t, int* wd_start_out, int n, int* n_
   LT_HIP(hipDeviceSynchronize());
   if (n > 0) LT_HIP(hipMemcpy(wd_start_out, t->wd_start, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   if (n_quirk) *n_quirk = t->wd_n_quirk;
+  return LT_OK;
+}
+
+// debug helper (not part of the documented ABI): the first n (<= LT_WALKC_N = 32) words of the last column walk's path
+// counters (LT_WALKC_*; LIDARHIP_DEBUG_TSDF=1)
+extern "C" int lt_debug_tsdf_walk_paths(unsigned long long* out, int n) {
+  if (!out || n < 0 || n > LT_WALKC_N || !g_tsdf_dbg) return LT_ERR_INVALID_ARG;
+  LT_HIP(hipDeviceSynchronize());
+  LT_HIP(hipMemcpy(out, g_tsdf_dbg + LT_WALKC_AT, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return LT_OK;
+}
+
+// debug helper (not part of the documented ABI), read-only: the first n 32-bit words of a table of the volume's last column
+// walk -- what = 0: colinfo [n_cols] (int: image column, -1 dead, -2 dead and walked whole), 1: chunk_live [n_chunks] (int),
+// 2: colz [n_cols] (z0 | z1 << 15 | plain << 31; defined where colinfo != -1), 3: colmax [image width] (float).
+// LT_ERR_INVALID_ARG when the volume has not been walked.
+extern "C" int lt_debug_tsdf_walk_table(lt_tsdf* t, int what, void* out, int n) {
+  if (!t || !out || n < 0 || t->walk_w <= 0 || !t->colinfo || !t->colmax) return LT_ERR_INVALID_ARG;
+  const size_t n_cols = (size_t)t->dim[0] * t->dim[1], n_chunks = (n_cols + 63) / 64, n_flags = n_chunks + 64;
+  const void* src = nullptr;
+  size_t have = 0;
+  switch (what) {
+    case 0: src = t->colinfo; have = n_cols; break;
+    case 1: src = t->colinfo + n_cols; have = n_chunks; break;
+    case 2: src = t->colinfo + n_cols + n_flags; have = n_cols; break;
+    case 3: src = t->colmax; have = (size_t)t->walk_w; break;
+    default: return LT_ERR_INVALID_ARG;
+  }
+  if ((size_t)n > have) return LT_ERR_INVALID_ARG;
+  LT_HIP(hipSetDevice(t->device));
+  LT_HIP(hipDeviceSynchronize());
+  if (n > 0) LT_HIP(hipMemcpy(out, src, (size_t)n * 4, hipMemcpyDeviceToHost));
   return LT_OK;
 }
 
