@@ -737,6 +737,69 @@ int lt_noise_model_dev(const float* origin, int n, const lt_noise_model* model, 
                        int* endcolors, float* range, float* endrem, int* tri, float* range_error, unsigned char* state,
                        unsigned trace_flags, void* stream);
 
+/* ---- the target sensor's echo model: a beam with a divergence (the reference has none) -----------
+ *
+ * A beam illuminates a cone, not a line.  Each cell is rendered with S = n_subrays SUB-RAYS -- the central ray and S - 1 on
+ * a ring around it -- into S sub-images, and one kernel resolves them into the cell: the sub-hits are grouped into echoes
+ * along the range, one echo is reported.  Sub-rays and sub-images are laid out PLANE BY PLANE: sub-ray k of cell i is
+ * element k * n + i, so plane 0 is a whole image.
+ *
+ * lt_create_subrays_dev, per cell, in float64 from the widened float32 d = rays[i] = (x, y, z); every product, sum,
+ * quotient and square root rounded on its own (no fused multiply-add, IEEE sqrt and /):
+ *   h2 = x*x + y*y;  dd = h2 + z*z
+ *   if !(dd > 0) or dd is not finite: every sub-ray of the cell is d, copied
+ *   n = sqrt(dd);  hx = x/n, hy = y/n, hz = z/n
+ *   h2 > 0 ? (h = sqrt(h2); ux = -y/h; uy = x/h) : (ux = 1; uy = 0)       u: horizontal, to the LEFT (larger atan2(y, x))
+ *   vx = -(hz*uy);  vy = hz*ux;  vz = hx*uy - hy*ux                        v = h x u: upwards for a level ray
+ *   (a, b) = (off[2k], off[2k+1]);  (a, b) == (0, 0): the three floats of d, COPIED
+ *   else subrays[k*n + i] = float32( (hx + a*ux) + b*vx,  (hy + a*uy) + b*vy,  hz + b*vz )      not normalised
+ *
+ * lt_echo_resolve_dev, per cell i:
+ *   1. sub-ray k is a HIT when sub_tri[k*n+i] >= 0 and sub_range[k*n+i] > 0;
+ *   2. the hits are ordered by (t, k) ascending, t the float32 range;
+ *   3. walked in that order, the first hit opens an echo, and a hit with (double)t - (double)t_first > separation (strict;
+ *      t_first: the open echo's first member) opens the next;
+ *   4. an echo keeps its count c, St and Srem -- float64 sums of the widened float32 values, in walk order, starting from
+ *      the first member's value -- and its representative rep, the member with the smallest k;
+ *   5. an echo is DETECTED when c >= min_subrays; n_echoes[i] = the number of detected echoes;
+ *   6. LT_ECHO_FIRST takes the earliest detected echo in walk order, LT_ECHO_LAST the latest, LT_ECHO_STRONGEST the one
+ *      with the largest Srem, a tie going to the larger c and a remaining tie to the earlier;
+ *   7. range[i] = float32(St / c);  endrem[i] = float32(Srem / S);  fraction[i] = float32((double)c / S);
+ *      endcolors[i] = sub_label[rep*n+i];  tri[i] = sub_tri[rep*n+i];
+ *      endpoints[i][j] = float32(o[j] + h[j] * (double)range[i])          h: the unit direction above of rays[i], o = origin
+ * A cell without a detected echo, or whose central ray has !(dd > 0), becomes the miss LT_TRACE_WRITE_MISSES writes: end
+ * point (0, 0, 0), label 0, remission 0, range 0, tri -1, fraction 0 (n_echoes stays the count).  Every output is written
+ * for every cell.  A spot wholly on a surface of one remission keeps that remission bit for bit: (S*x)/S is exact, S <= 8.
+ * No transcendental on the device: the offsets are made on the host (config.EchoModel.offsets). */
+#define LT_ECHO_MAX_SUBRAYS 8
+#define LT_ECHO_FIRST 0u
+#define LT_ECHO_STRONGEST 1u
+#define LT_ECHO_LAST 2u
+typedef struct lt_echo_model {
+  double off[2 * LT_ECHO_MAX_SUBRAYS]; /* (a_k, b_k), k < n_subrays, finite; the rest is ignored                       */
+  double separation;                   /* metres, finite, > 0                                                         */
+  int n_subrays;                       /* 2 .. LT_ECHO_MAX_SUBRAYS                                                    */
+  int min_subrays;                     /* 1 .. n_subrays: an echo of fewer sub-hits is not detected                   */
+  unsigned mode;                       /* LT_ECHO_FIRST | LT_ECHO_STRONGEST | LT_ECHO_LAST                            */
+  unsigned reserved;
+} lt_echo_model;
+
+/* rays [n,3] f32 DEVICE -> subrays [n_subrays * n, 3] f32 DEVICE, plane by plane.  model: HOST, read before the call
+ * returns.  One launch, asynchronous on `stream`, on the calling thread's current device.  n == 0 is LT_OK; a NULL
+ * pointer, n < 0 (or n_subrays * n past INT_MAX) and a model outside the ranges above are LT_ERR_INVALID_ARG. */
+int lt_create_subrays_dev(const float* rays, int n, const lt_echo_model* model, float* subrays, void* stream);
+
+/* rays [n,3] f32 (the CENTRAL rays), sub_range [S*n] f32, sub_label [S*n] i32 (label-image layout only), sub_rem [S*n]
+ * f32, sub_tri [S*n] i32 in; endpoints [n,3] f32, endcolors [n] i32, range [n] f32, endrem [n] f32, tri [n] i32, n_echoes
+ * [n] u8, fraction [n] f32 out -- all DEVICE, none of the outputs overlapping an input.  rays, sub_range, sub_tri, range
+ * and tri are mandatory; every other output may be NULL, and so may sub_label (reads as label 0) and sub_rem (remission 0).
+ * origin [3] f32 and model: HOST, read before the call returns.  One thread per cell, one launch, asynchronous on `stream`,
+ * on the calling thread's current device.  n == 0 is LT_OK; a bad argument is LT_ERR_INVALID_ARG with a message. */
+int lt_echo_resolve_dev(const float* rays, const float* origin, int n, const lt_echo_model* model,
+                        const float* sub_range, const int* sub_label, const float* sub_rem, const int* sub_tri,
+                        float* endpoints, int* endcolors, float* range, float* endrem, int* tri,
+                        unsigned char* n_echoes, float* fraction, void* stream);
+
 /* Pack a rendered scan in SemanticKITTI layout; replaces the filtering and the per-point struct.pack loops
  * of MultiSemLaserScan.write (auxiliary/laserscan.py:1133-1178).  Keeps, in order, the cells with
  * (index == NULL or index[i] > 0) and label[i] >= 0 and x + y + z != 0.  points [n,3] f32 or f64,

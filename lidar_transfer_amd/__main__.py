@@ -19,7 +19,12 @@ code over all its scans, which the ``--log`` summary carries as ``return_totals`
 measurement error -- range jitter and grid, remission jitter and levels --; the run closes with one line ``Noise: untouched N,
 noised N, lost N, range error RMS X m``, which the ``--log`` summary carries as ``noise_totals`` and ``range_error_rms``.  The
 metrics of such a run, under ``--evaluate auto`` and under ``--evaluate target`` alike, compare the NOISY output with a
-reference that has no noise: their MSE contains the noise.  The tool
+reference that has no noise: their MSE contains the noise.  A target YAML with an ``echo_model`` block
+(config/vlp32c_table_echo_1024.yaml) gives the beams of ``mesh`` / ``mergemesh`` (``cp`` is refused) a divergence: every cell
+is rendered with several sub-rays whose hits are grouped into echoes, one of which is reported -- with a blended range where
+two surfaces lie within one pulse --; the run closes with one line ``Echoes: none N, one N, several N, mean fraction X``,
+which the ``--log`` summary carries as ``echo_totals`` and ``echo_fraction_mean``, and every row of ``--log`` carries
+``"echo_model": true``; ``--evaluate auto`` treats the key as it treats ``return_model``: nothing is switched off.  The tool
 is always headless (``--batch`` is accepted).  Per compared scan it prints the reference's three lines
 ``IoU:  <m_iou>``, ``Acc:  <m_acc>``, ``MSE:  <MSE>`` (laserscan.py:1233-1234, :1262).  ``--evaluate target`` compares for
 every target -- mounted, with a table, a sector, offsets, a return model, another image size -- against the source scan seen
@@ -97,6 +102,9 @@ def main(argv=None):
     if target.noise_model() is not None and approach.adaption == "cp":
         print("adaption cp renders no ray: the target sensor's noise_model cannot be applied (use mesh or mergemesh).")
         return 1
+    if target.echo_model() is not None and approach.adaption == "cp":
+        print("adaption cp renders no ray: the target sensor's echo_model cannot be applied (use mesh or mergemesh).")
+        return 1
     log = open(args.log, "w") if args.log else None
     try:
         with SequenceTransfer((args.dataset, args.sequence), approach, source, target, out_dir=args.output if args.write else None,
@@ -121,6 +129,8 @@ def main(argv=None):
                         row["azimuth_model"] = tr.azimuth_model
                     if tr.beam_azimuth is not None:
                         row["beam_azimuth"] = True
+                    if tr.echoes is not None:
+                        row["echo_model"] = True
                     log.write(json.dumps(row) + "\n")
             if tr.summary.get("return_totals") is not None:
                 from .sequence import format_return_totals
@@ -128,6 +138,9 @@ def main(argv=None):
             if tr.summary.get("noise_totals") is not None:
                 from .sequence import format_noise_totals
                 print(format_noise_totals(tr.summary["noise_totals"], tr.summary["range_error_rms"]), flush=True)
+            if tr.summary.get("echo_totals") is not None:
+                from .sequence import format_echo_totals
+                print(format_echo_totals(tr.summary["echo_totals"], tr.summary["echo_fraction_mean"]), flush=True)
             if log is not None:
                 log.write(json.dumps(dict(summary=tr.summary)) + "\n")
     finally:

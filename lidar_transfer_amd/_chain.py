@@ -135,6 +135,100 @@ class Noise:
         return post.noise_model(origin, self.model, scan, rout, gate=self.gate, label_image=label_image, stream=stream)
 
 
+class Echoes:
+    """The target sensor's echo model on a chain (``config.EchoModel`` or ``None``), beside :class:`Returns` and
+    :class:`Noise`.  ``None``, or a model that is off (no divergence, one sub-ray): nothing here allocates or launches, and
+    :meth:`render_set` / :meth:`render_into` hand back what they were given.  With a model the chain renders ``S`` sub-rays
+    per cell -- :meth:`bind` makes them from the finished ray tensor and ONE read-only ``RaySet`` over them, shared by all
+    chains of a pipeline as the plain ray set is -- into scratch images and :meth:`apply` resolves those into the chain's
+    own images: behind the render that stands, AHEAD of the return model and the noise model, which see the resolved scan.
+    ``model`` may be a bound :class:`Echoes`: its model and its ray set are shared, not owned."""
+
+    KEYS = ("n_echoes", "echo_fraction")
+    SUB_KEYS = ("endcolors", "range", "endrem", "tri")   # what a sub-render writes: no end points
+
+    def __init__(self, model, who="echo model"):
+        from .config import EchoModel
+        self.rayset = self.subrays = None
+        self._own = True
+        if isinstance(model, Echoes):
+            self.model, self.rayset, self.subrays, self._own = model.model, model.rayset, model.subrays, False
+            return
+        if model is not None and not isinstance(model, EchoModel):
+            raise ValueError(f"{who}: echoes= takes a lidar_transfer_amd.config.EchoModel (SensorModel.echo_model()) or None")
+        self.model = None if model is None or model.is_default else model
+
+    def __bool__(self):
+        return self.model is not None
+
+    @staticmethod
+    def grid_of(central, t_H, table=False):
+        """The bin grid of the sub-ray set for a central set's ``grid`` (``None``: the image's rule): the central set's azimuth
+        rule, and the central set's own ``t_H`` elevation rows -- not the ``S * t_H`` rows the image's rule would make of the
+        taller set --, so that the ``S`` sub-rays of a cell share the bin their central ray sits in; with ``table`` (a target
+        whose rows are not evenly spaced: a beam table) the image's rule, whose finer rows separate the beams that crowd near
+        the horizon.  A speed choice only: every grid renders the same image.  Measured (profiles/echo_model/README.md): at
+        64 x 2048 evenly spaced the central rows render in 0.34 of the time of the image's rule, with the VLP-32C table at
+        32 x 1024 the image's rule in 0.64 of the time of the central rows; doubling the azimuth bins is slower in both."""
+        az, el = (0, 0) if central is None else central
+        return int(az), int(el) if el else (0 if table else int(t_H))
+
+    def bind(self, rays, t_H, pose=None, grid=None, table=False, sub_grid=None):
+        """the sub-rays of ``rays`` [n, 3] (the finished central rays of a target of ``t_H`` rows) and the ray set over them:
+        ``S * t_H`` rows of the image's width, plane by plane, binned by ``sub_grid`` or, without one, by :meth:`grid_of` of the
+        central set's ``grid`` and ``table``.  Once per pipeline; waits for the current stream.  Without a model, or when
+        already bound (a shared one), nothing happens."""
+        if self.model is None or self.rayset is not None:
+            return self
+        from . import post
+        from .raytracer import RaySet
+        n = (rays.shape[0] // int(t_H)) * int(t_H)   # (what the plain ray set keeps of them)
+        self.subrays = post.create_subrays(rays if n == rays.shape[0] else rays[:n].contiguous(), self.model)
+        self.rayset = RaySet(self.subrays, self.model.subrays * int(t_H), pose=pose,
+                             grid=sub_grid if sub_grid is not None else self.grid_of(grid, t_H, table))
+        return self
+
+    def render_set(self, rayset):
+        """the ray set the chain renders with: the sub-ray set, or ``rayset`` (the plain one) without a model"""
+        if self.model is None:
+            return rayset
+        if self.rayset is None:
+            raise RuntimeError("an echo model needs its sub-ray set: Echoes.bind(rays, t_H) first")
+        return self.rayset
+
+    def resolve_into(self, rout, n_rays, device):
+        """What the resolve writes for this chain: ``rout`` itself without a model or when it holds ``tri`` already; else a
+        copy with a ``tri`` image (the resolve always writes the representative's triangle)."""
+        return rout if self.model is None else with_tri(rout, n_rays, device)
+
+    def render_into(self, rout, n_rays, device):
+        """What the render writes for this chain: ``rout`` itself without a model; else scratch images of the ``S * n_rays``
+        sub-rays -- the label image, range, remission and triangle, no end points.  Allocates on the current stream."""
+        if self.model is None:
+            return rout
+        import torch
+        m = self.model.subrays * int(n_rays)
+        sub = dict(endpoints=None, endcolors=torch.empty((m,), dtype=torch.int32, device=device),
+                   range=torch.empty((m,), dtype=torch.float32, device=device),
+                   endrem=torch.empty((m,), dtype=torch.float32, device=device),
+                   tri=torch.empty((m,), dtype=torch.int32, device=device))
+        return sub
+
+    def apply(self, sub, rout, rays, origin, stream):
+        """the sub-render ``sub`` resolved into the chain's images ``rout`` (which hold a ``tri`` image: :func:`with_tri`) on
+        ``stream``; ``rays``: the CENTRAL rays, ``origin``: where they start.  Returns ``dict(n_echoes=, echo_fraction=)``, or
+        ``{}`` without a model."""
+        if self.model is None:
+            return {}
+        from . import post
+        return post.echo_resolve(rays, origin, self.model, sub, rout, stream=stream)
+
+    def close(self):
+        if self._own and self.rayset is not None:
+            self.rayset.close()
+        self.rayset = self.subrays = None
+
+
 class Mount:
     """The target sensor's mounting from the approach file's ``transformation`` (``config.mount_of``).  ``pair``: ``(T, P)``,
     or ``None`` for no mounting (``None``, empty, the identity) -- then nothing here allocates or launches.  ``T``

@@ -31,6 +31,8 @@ LT_COMPARE_MAX_PRESENT = 64
 LT_COMPARE_OVERFLOW = 1
 LT_COMPARE_LABEL_RANGE = 2
 LT_RETURN_LAMBERT = 1
+LT_ECHO_MAX_SUBRAYS = 8
+LT_ECHO_FIRST, LT_ECHO_STRONGEST, LT_ECHO_LAST = 0, 1, 2
 
 #: every symbol include/lidarhip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_dev", "lt_scene_set_mesh_host",
@@ -49,7 +51,8 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_reverse_projection_beams_dev", "lt_create_rays_sector_dev", "lt_reverse_projection_sector_dev",
            "lt_rayset_create_grid_dev", "lt_projector_set_sector", "lt_range_projection_set_sector",
            "lt_create_rays_beams_az_dev", "lt_projector_set_beam_azimuth", "lt_range_projection_set_beam_azimuth",
-           "lt_reverse_projection_beams_az_dev", "lt_return_model_dev", "lt_target_view_dev", "lt_noise_model_dev"]
+           "lt_reverse_projection_beams_az_dev", "lt_return_model_dev", "lt_target_view_dev", "lt_noise_model_dev",
+           "lt_create_subrays_dev", "lt_echo_resolve_dev"]
 LT_ABI_VERSION = 10   # include/lidarhip.h: layout version of the structs mirrored below
 
 
@@ -121,6 +124,13 @@ class NoiseModelArgs(C.Structure):
     _fields_ = [("range_sigma", C.c_double), ("range_sigma_rel", C.c_double), ("range_resolution", C.c_double),
                 ("remission_sigma", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double),
                 ("remission_levels", C.c_uint), ("seed", C.c_uint)]
+
+
+class EchoModelArgs(C.Structure):
+    """Mirror of ``lt_echo_model``: the target sensor's echo model as ``lt_create_subrays_dev`` and ``lt_echo_resolve_dev``
+    read it (HOST)."""
+    _fields_ = [("off", C.c_double * (2 * LT_ECHO_MAX_SUBRAYS)), ("separation", C.c_double), ("n_subrays", C.c_int),
+                ("min_subrays", C.c_int), ("mode", C.c_uint), ("reserved", C.c_uint)]
 
 
 def ingest_work_ints(n_total: int, n_scans: int) -> int:
@@ -310,6 +320,11 @@ def load():
     lib.lt_noise_model_dev.argtypes = [C.POINTER(C.c_float), C.c_int, C.POINTER(NoiseModelArgs), C.c_uint, vp, vp, vp, vp, vp,
                                        vp, vp, C.c_uint, vp]
     lib.lt_noise_model_dev.restype = C.c_int
+    lib.lt_create_subrays_dev.argtypes = [vp, C.c_int, C.POINTER(EchoModelArgs), vp, vp]
+    lib.lt_create_subrays_dev.restype = C.c_int
+    lib.lt_echo_resolve_dev.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(EchoModelArgs), vp, vp, vp, vp, vp, vp,
+                                        vp, vp, vp, vp, vp, vp]
+    lib.lt_echo_resolve_dev.restype = C.c_int
     lib.lt_abi_version.argtypes = []
     lib.lt_tsdf_volume_stride.argtypes = []
     if lib.lt_abi_version() != LT_ABI_VERSION:  # a stale prebuilt library: its structs are laid out differently

@@ -40,6 +40,14 @@ not inside it:
   ``remission_sigma``, ``remission_levels`` and ``seed`` -- the range of a return is jittered along its ray and reported on a
   grid, its remission is jittered, clamped to [0, 1] and reported on ``remission_levels`` levels; a block with every field at
   its default is none.
+
+A sixth is the WIDTH of its beams, :class:`EchoModel` (``SensorModel.echo_model()``), beside the two:
+
+* ``echo_model``: a block of ``divergence`` (degrees, the full cone angle), ``subrays`` (1..8: the centre ray and ``subrays -
+  1`` on a ring), ``ring`` (the ring's radius as a fraction of the half angle), ``separation`` (metres), ``min_subrays`` and
+  ``mode`` (``first`` | ``strongest`` | ``last``) -- every cell is rendered with ``subrays`` rays, their hits are grouped into
+  echoes along the range and one echo is reported, with the blended range of what the spot covers; ``divergence`` 0 or
+  ``subrays`` 1 is none.
 """
 from __future__ import annotations
 
@@ -70,6 +78,8 @@ class SensorModel:
     return_block: Optional[dict] = None
     #: the file's ``noise_model`` block as read (a mapping), ``None`` without the key: :meth:`noise_model`
     noise_block: Optional[dict] = None
+    #: the file's ``echo_model`` block as read (a mapping), ``None`` without the key: :meth:`echo_model`
+    echo_block: Optional[dict] = None
 
     @property
     def H(self) -> int:
@@ -128,6 +138,12 @@ class SensorModel:
         and levels -- or ``None`` without the ``noise_model`` key or with every field at its default.
         ``ValueError`` led by the sensor's name for a block that cannot be used."""
         return NoiseModel.of(self.noise_block, f"sensor {self.name!r}")
+
+    def echo_model(self):
+        """The sensor's :class:`EchoModel` -- the width of a TARGET's beams: sub-rays, echoes, mixed cells -- or
+        ``None`` without the ``echo_model`` key, with ``divergence`` 0 or with ``subrays`` 1.  ``ValueError`` led by the
+        sensor's name for a block that cannot be used."""
+        return EchoModel.of(self.echo_block, f"sensor {self.name!r}")
 
     def sector(self):
         """``None`` for ``azimuth_model: full``; for ``sector`` ``(center_deg, span_deg)`` as floats: the ``W`` columns span
@@ -522,6 +538,110 @@ class NoiseModel:
                                    self.remission_levels, self.seed)
 
 
+class EchoModel:
+    """The width of a TARGET sensor's beams (the sensor file's ``echo_model`` block), one immutable value like
+    :class:`ReturnModel` and :class:`NoiseModel` and beside them: the full cone angle ``divergence`` of a beam (degrees, 0:
+    a line), the number ``subrays`` of rays a cell is rendered with (1..8, 1: a line) -- the centre ray and ``subrays - 1``
+    evenly on a ring of radius ``ring`` times the half angle --, the distance ``separation`` (metres) behind an echo's first
+    sub-hit beyond which a sub-hit starts a new echo, the number ``min_subrays`` of sub-hits an echo needs to be detected and
+    the ``mode`` that picks the reported echo.  The constructor is the only place that normalises and validates, else
+    ``ValueError`` led by ``who``; :meth:`of` returns ``None`` for a model that is off (``divergence`` 0 or ``subrays`` 1)."""
+
+    DEFAULTS = dict(divergence=0.0, subrays=1, ring=0.7071, separation=0.5, min_subrays=1, mode="strongest")
+    MODES = ("first", "strongest", "last")   # in the order of LT_ECHO_FIRST, LT_ECHO_STRONGEST, LT_ECHO_LAST
+    MAX_SUBRAYS = 8                          # LT_ECHO_MAX_SUBRAYS
+
+    def __init__(self, divergence=0.0, subrays=1, ring=0.7071, separation=0.5, min_subrays=1, mode="strongest",
+                 who="echo model"):
+        import math
+
+        def number(name, v, ok, say):
+            try:
+                if isinstance(v, (bool, str)):
+                    raise TypeError
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: echo_model {name} must be a number, not {v!r}") from None
+            if not (math.isfinite(v) and ok(v)):
+                raise ValueError(f"{who}: echo_model {name} must be {say}, not {v}")
+            return v
+
+        def integer(name, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{who}: echo_model {name} must be an integer in [{lo}, {hi}], not {v!r}")
+            return int(v)
+        fields = dict(divergence=number("divergence", divergence, lambda v: 0.0 <= v < 180.0, "in [0, 180) degrees"),
+                      subrays=integer("subrays", subrays, 1, self.MAX_SUBRAYS),
+                      ring=number("ring", ring, lambda v: 0.0 < v <= 1.0, "in (0, 1]"),
+                      separation=number("separation", separation, lambda v: v > 0.0, "finite and positive"))
+        fields["min_subrays"] = integer("min_subrays", min_subrays, 1, fields["subrays"])
+        if not isinstance(mode, str) or mode not in self.MODES:
+            raise ValueError(f"{who}: echo_model mode must be one of {', '.join(self.MODES)}, not {mode!r}")
+        fields["mode"] = mode
+        self.__dict__.update(fields)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("an EchoModel does not change: make another")
+
+    @classmethod
+    def of(cls, block, who="echo model"):
+        """The model of a sensor file's ``echo_model`` block (a mapping, or ``None``: no key), or ``None`` when it is off; an
+        unknown key and a block that is no mapping are ``ValueError``.  An :class:`EchoModel` passes through (``None`` if
+        off)."""
+        if block is None:
+            return None
+        if isinstance(block, cls):
+            return None if block.is_default else block
+        if not isinstance(block, dict):
+            raise ValueError(f"{who}: echo_model must be a mapping of {', '.join(cls.DEFAULTS)}")
+        unknown = sorted(set(map(str, block)) - set(cls.DEFAULTS))
+        if unknown:
+            raise ValueError(f"{who}: echo_model has unknown key(s) {', '.join(unknown)} (known: {', '.join(cls.DEFAULTS)})")
+        m = cls(who=who, **block)
+        return None if m.is_default else m
+
+    def fields(self):
+        return {k: getattr(self, k) for k in self.DEFAULTS}
+
+    @property
+    def is_default(self):
+        """off: a beam without a width, or one ray per cell -- the absence of the key"""
+        return self.divergence == 0.0 or self.subrays == 1
+
+    def __eq__(self, other):
+        return isinstance(other, EchoModel) and self.fields() == other.fields()
+
+    def __hash__(self):
+        return hash(tuple(self.fields().values()))
+
+    def __repr__(self):
+        return "EchoModel(" + ", ".join(f"{k}={v!r}" for k, v in self.fields().items()) + ")"
+
+    def offsets(self):
+        """The sub-rays' offsets, float64 ``[subrays, 2]``: row 0 is (0, 0), the centre ray; row ``k >= 1`` is ``tan(rho) *
+        (cos phi_k, sin phi_k)`` with ``rho = radians(divergence / 2 * ring)`` and ``phi_k = 2 pi (k - 1) / (S - 1) + pi / (S -
+        1)``: ``a`` to the left, ``b`` upwards, in units of the central ray's length.  Made here, on the host: the device
+        evaluates no transcendental."""
+        S = self.subrays
+        off = np.zeros((S, 2), dtype=np.float64)
+        if S > 1:
+            rho = np.radians(self.divergence / 2.0 * self.ring)
+            phi = 2.0 * np.pi * np.arange(S - 1, dtype=np.float64) / (S - 1) + np.pi / (S - 1)
+            off[1:, 0] = np.tan(rho) * np.cos(phi)
+            off[1:, 1] = np.tan(rho) * np.sin(phi)
+        return off
+
+    def args(self):
+        """the model as ``lt_create_subrays_dev`` and ``lt_echo_resolve_dev`` read it (``_lib.EchoModelArgs``)"""
+        from . import _lib
+        a = _lib.EchoModelArgs()
+        for k, v in enumerate(self.offsets().ravel()):
+            a.off[k] = float(v)
+        a.separation, a.n_subrays, a.min_subrays = self.separation, self.subrays, self.min_subrays
+        a.mode, a.reserved = self.MODES.index(self.mode), 0
+        return a
+
+
 def _load_yaml(path_or_dict):
     if isinstance(path_or_dict, dict):
         return path_or_dict
@@ -560,10 +680,11 @@ def load_sensor(path_or_dict) -> SensorModel:
                         beam_model=str(cfg.get("beam_model", "linear")),
                         azimuth_model=str(cfg.get("azimuth_model", "full")), azimuth_center=cfg.get("azimuth_center", 0.0),
                         beam_azimuth_offsets=offsets, return_block=cfg.get("return_model"),
-                        noise_block=cfg.get("noise_model"))
+                        noise_block=cfg.get("noise_model"), echo_block=cfg.get("echo_model"))
     model.target_model()   # (a table, a sector or offsets that cannot be used: said at load time)
     model.return_model()   # (and a return model that cannot be)
     model.noise_model()    # (nor a noise model)
+    model.echo_model()     # (nor an echo model)
     return model
 
 
@@ -603,14 +724,22 @@ def refuse_source_noise_model(source):
                          "scan holds the measurement error of its own sensor)")
 
 
+def refuse_source_echo_model(source):
+    """And its echo model: the source scan holds the echoes its own beams produced."""
+    if getattr(source, "echo_block", None) is not None:
+        raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: echo_model is for target sensors only (the source "
+                         "scan holds the echoes of its own sensor's beams)")
+
+
 def refuse_source_models(source):
-    """everything a :class:`TargetModel`, a :class:`ReturnModel` or a :class:`NoiseModel` holds is a property of the TARGET:
-    the five refusals, the table's first"""
+    """everything a :class:`TargetModel`, a :class:`ReturnModel`, a :class:`NoiseModel` or an :class:`EchoModel` holds is a
+    property of the TARGET: the six refusals, the table's first"""
     refuse_source_table(source)
     refuse_source_sector(source)
     refuse_source_beam_azimuth(source)
     refuse_source_return_model(source)
     refuse_source_noise_model(source)
+    refuse_source_echo_model(source)
 
 
 @dataclass

@@ -135,7 +135,8 @@ class DeviceDeform:
 
     def __init__(self, source, target, vol_bnds=None, voxel_size=0.1, beam_angles=None, t_beam_angles=None,
                  preserve_float=False, device=None, merge=True, fusion="cuda", mesh_volume=True, rayset=None, mm_state=None,
-                 transformation=None, t_beam_table=None, t_sector=None, t_beam_azimuth=None, returns=None, noise=None):
+                 transformation=None, t_beam_table=None, t_sector=None, t_beam_azimuth=None, returns=None, noise=None,
+                 echoes=None):
         """``fusion``: ``"cuda"`` -- the arithmetic of the reference's CUDA kernel (class-aware with ``merge``), or ``"numpy"`` --
         that of its numpy branch (``FUSION_GPU_MODE == 0``, fusion_lidar.py:290-388; what goldens F13 / F14 are made by).
         ``vol_bnds``: [3,2]; for :meth:`mergemesh` it is STATE, clipped in place call after call exactly as the reference
@@ -166,7 +167,14 @@ class DeviceDeform:
         the render that stands, BEHIND the return model (whose range gate a measured range must stay inside) and before the
         frame change and packing: ranges are jittered and put on a grid, the end points follow along their rays about the
         ray origin, remission is jittered and put on levels; the result holds ``range_error`` and
-        ``noise_state`` [n] as well.  ``cp`` renders no ray and has no origin: it raises."""
+        ``noise_state`` [n] as well.  ``cp`` renders no ray and has no origin: it raises.
+        ``echoes``: the TARGET sensor's :class:`~lidar_transfer_amd.config.EchoModel` (``SensorModel.echo_model()``; ``None``
+        or off: nothing of it runs) -- a beam with a divergence: ``mesh`` and ``mergemesh`` render ``S`` sub-rays
+        per cell (one read-only ray set over them, made here or shared: a bound ``_chain.Echoes`` of another chain) into
+        scratch images and resolve them into the scan -- echoes along the range, one reported, a blended range where two
+        surfaces are closer than ``separation`` -- on the render that stands, AHEAD of the return and noise models, which see
+        the resolved scan; the result holds ``n_echoes`` [n] uint8 and ``echo_fraction`` [n] as well.  No ``scan_index`` is
+        needed: nothing is drawn.  ``cp`` renders no ray: it raises."""
         import numpy as np
         import torch
 
@@ -196,6 +204,8 @@ class DeviceDeform:
         self.returns = self._returns.model
         self._noise = _chain.Noise(noise, self.returns, "DeviceDeform")
         self.noise = self._noise.model
+        self._echoes = _chain.Echoes(echoes, "DeviceDeform")
+        self.echoes = self._echoes.model
         m = self.t_model = TargetModel(t_beam_table, t_sector, t_beam_azimuth, "DeviceDeform").validate(
             self.t_H, (self.t_fov_up, self.t_fov_down), "DeviceDeform")
         # what the reverse projection reads on the device: the table and the offsets in radians
@@ -232,6 +242,8 @@ class DeviceDeform:
                                 beam_azimuth="other beam azimuth offsets")[differs]
                     raise ValueError(f"DeviceDeform: the shared rayset was built for {what} than `t_{differs}`")
                 self.rayset = rayset
+            # (the central rays stay in ``rayset.rays``: the return model reads its directions from them)
+            self._echoes.bind(self.rayset.rays, self.t_H, pose=pose, grid=self.rayset.grid, table=m.beam_table is not None)
         self.n_rays = self.t_H * self.t_W
 
     t_beam_table = property(lambda self: self.t_model.beam_table)
@@ -325,12 +337,15 @@ class DeviceDeform:
             cp[k], dp[k], rp[k] = o["label_folded"].data_ptr(), o["range"].data_ptr(), o["rem"].data_ptr()
         out = self.scene.alloc_outputs(self.n_rays, label_image=True)
         rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays, self.device)
-        rout = self._noise.render_into(rout, self.n_rays, self.device)
+        rout = self._echoes.resolve_into(self._noise.render_into(rout, self.n_rays, self.device), self.n_rays, self.device)
+        sub = self._echoes.render_into(rout, self.n_rays, self.device)   # (the sub-images, or ``rout`` itself)
         with torch.cuda.device(self.device):
-            _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, n, cp, dp, rp,
-                                              self.H, self.W, 1.0, self._merge, _chain.origin3(origin), *_chain.out_ptrs(rout),
-                                              _chain.TRACE_FLAGS, vp(st.cuda_stream), 0), "lt_fusion_scan_dev")
-            seen = self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st)
+            _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self._echoes.render_set(self.rayset)._h,
+                                              n, cp, dp, rp, self.H, self.W, 1.0, self._merge, _chain.origin3(origin),
+                                              *_chain.out_ptrs(sub), _chain.TRACE_FLAGS, vp(st.cuda_stream), 0),
+                       "lt_fusion_scan_dev")
+            seen = self._echoes.apply(sub, rout, self.rayset.rays, origin, st)
+            seen.update(self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st))
             seen.update(self._noise.apply(rout, scan_index, origin, st))
             self._mounting.to_target(rout, out, st)
             if ev:
@@ -423,9 +438,10 @@ class DeviceDeform:
             if self._noise and scan_index is None:
                 raise ValueError("DeviceDeform.mergemesh: a noise model needs scan_index, the output scan's index in its sequence")
             rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays, self.device)
-            rout = self._noise.render_into(rout, self.n_rays, self.device)
+            rout = self._echoes.resolve_into(self._noise.render_into(rout, self.n_rays, self.device), self.n_rays, self.device)
+            sub = self._echoes.render_into(rout, self.n_rays, self.device)   # (the sub-images, or ``rout`` itself)
             first, again, more = (self._mm_composed if source_images else self._mm_native)(
-                mm, cloud, seq, _chain.origin3(origin), _chain.out_ptrs(rout), st)
+                mm, cloud, seq, _chain.origin3(origin), _chain.out_ptrs(sub), st)
             pred, vol = mm.pred, None
             if pred is not None:
                 vol = self._mm_vols.get(pred)
@@ -450,6 +466,7 @@ class DeviceDeform:
                 mm.stats["waited" if vol is None else "rerun"] += 1
                 vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
                 again(vol)
+            more.update(self._echoes.apply(sub, rout, self.rayset.rays, origin, st))   # (once, on the render that stands)
             more.update(self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st))
             more.update(self._noise.apply(rout, scan_index, origin, st))
             self._mounting.to_target(rout, out, st)
@@ -468,19 +485,20 @@ class DeviceDeform:
         cl, keep, is_f64 = _chain.cloud_table([cloud])
         beams = _chain.beam_table(self.beam_angles)   # (pointer, n, the array: alive as long as the callables)
         p = self.projector._h
+        rs = self._echoes.render_set(self.rayset)
 
         def first(vol):
             tflags = vol._flags if vol is not None else (_lib.LT_TSDF_HOST_MODE if self._fusion == "numpy" else self._merge)
             geo, done = _lib.MMGeometry(), C.c_int(0)
             _lib.check(lib.lt_mergemesh_scan_dev(p, mm._h, -1 if seq is None else int(seq), vol._h if vol is not None else None,
-                                                 self.mesh_obj._h, self.scene._h, self.rayset._h, cl, is_f64, self.t_fov_up,
+                                                 self.mesh_obj._h, self.scene._h, rs._h, cl, is_f64, self.t_fov_up,
                                                  self.t_fov_down, self.H, self.W, beams[0], beams[1], 1.0, tflags, org, *ptrs,
                                                  _chain.TRACE_FLAGS, vp(st.cuda_stream), C.byref(geo), C.byref(done)),
                        "lt_mergemesh_scan_dev")
             return geo, bool(done.value)
 
         def again(vol):
-            _lib.check(lib.lt_mergemesh_rerun_dev(p, vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, self.H, self.W, 1.0,
+            _lib.check(lib.lt_mergemesh_rerun_dev(p, vol._h, self.mesh_obj._h, self.scene._h, rs._h, self.H, self.W, 1.0,
                                                   vol._flags, org, *ptrs, _chain.TRACE_FLAGS, vp(st.cuda_stream)),
                        "lt_mergemesh_rerun_dev")
         return first, again, dict(_keep=tuple(keep))
@@ -490,10 +508,11 @@ class DeviceDeform:
         returned under ``source``"""
         vp = C.c_void_p
         src = {}
+        rs = self._echoes.render_set(self.rayset)
 
         def again(vol):
             cp, dp, rp = (vp * 1)(src["label_folded"].data_ptr()), (vp * 1)(src["range"].data_ptr()), (vp * 1)(src["rem"].data_ptr())
-            _lib.check(self._lib.lt_fusion_scan_dev(vol._h, self.mesh_obj._h, self.scene._h, self.rayset._h, 1, cp, dp, rp, self.H,
+            _lib.check(self._lib.lt_fusion_scan_dev(vol._h, self.mesh_obj._h, self.scene._h, rs._h, 1, cp, dp, rp, self.H,
                                                     self.W, 1.0, vol._flags, org, *ptrs, _chain.TRACE_FLAGS, vp(st.cuda_stream), 0),
                        "lt_fusion_scan_dev")
 
@@ -517,7 +536,11 @@ class DeviceDeform:
         The reference's ``cp`` path always holds float64 points (``apply_pose``, laserscan.py:98-104) and goldens F12 / F12b pin
         that; float32 clouds with ``preserve_float`` are re-projected in float64 here as well (numpy would stay in float32).
         ``cp`` renders no surface, so there is no incidence angle: with a return model it raises ``ValueError``; it renders
-        no ray either, so there is no origin to jitter a range about: with a noise model it raises as well."""
+        no ray either, so there is no origin to jitter a range about: with a noise model it raises as well; and no beam to
+        widen: with an echo model it raises too."""
+        if self._echoes:
+            raise ValueError("DeviceDeform.cp: the target sensor has an echo_model, but cp renders no ray (no beam to widen): "
+                             "use mesh or mergemesh, or a target file without the key")
         if self._noise:
             raise ValueError("DeviceDeform.cp: the target sensor has a noise_model, but cp renders no ray (no origin to jitter "
                              "a range about): use mesh or mergemesh, or a target file without the key")
@@ -602,6 +625,8 @@ class DeviceDeform:
         if getattr(self, "_mm_state", None) is not None and getattr(self, "_mm_own", False):
             self._mm_state.close()
         self._mm_state = None
+        if getattr(self, "_echoes", None) is not None:
+            self._echoes.close()
         for name in ("rayset", "scene", "mesh_obj", "vol", "projector"):
             obj = getattr(self, name, None)
             if obj is not None:

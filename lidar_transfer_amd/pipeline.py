@@ -328,11 +328,19 @@ class FusionScanPipeline:
     ``noise``: the target sensor's :class:`~lidar_transfer_amd.config.NoiseModel` (``SensorModel.noise_model()``; ``None`` or
     all-default: nothing changes).  It needs ``scan_index`` in the same way and is applied once, behind the return model --
     whose range gate a measured range must stay inside -- on the chain's stream, about the scan's ray origin and before the
-    frame change; a result carries ``range_error`` and ``noise_state`` [n] as well (``post.noise_model``)."""
+    frame change; a result carries ``range_error`` and ``noise_state`` [n] as well (``post.noise_model``).
+
+    ``echoes``: the target sensor's :class:`~lidar_transfer_amd.config.EchoModel` (``SensorModel.echo_model()``; ``None`` or
+    off: nothing changes; it needs ``label_image=True``).  The pipeline makes the ``S`` sub-rays of every cell and ONE
+    read-only ray set over them, beside the plain one and shared by all chains in the same way; a chain renders that set into
+    scratch images and resolves them into the scan on its stream, ahead of the return and noise models; a result carries
+    ``n_echoes`` and ``echo_fraction`` [n] as well (``post.echo_resolve``).  No ``scan_index`` is needed for it.
+    ``echo_grid``: the sub-ray set's bin grid, for speed alone (``None``: ``grid``'s azimuth bins and ``H`` elevation rows; for
+    a beam table ``_chain.Echoes.grid_of(grid, H, table=True)``, the image's rule, is the faster one)."""
 
     def __init__(self, vol_bnds, voxel_size, fov_up, fov_down, rays, H, chains=3, device=None, merge=True,
                  label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None, grid=None,
-                 returns=None, noise=None):
+                 returns=None, noise=None, echoes=None, echo_grid=None):
         import queue
         import threading
         import weakref
@@ -353,8 +361,13 @@ class FusionScanPipeline:
         self.returns = self._returns.model
         self._noise = _chain.Noise(noise, self.returns, "FusionScanPipeline")
         self.noise = self._noise.model
+        self._echoes = _chain.Echoes(echoes, "FusionScanPipeline")
+        self.echoes = self._echoes.model
+        if self._echoes and not label_image:
+            raise ValueError("FusionScanPipeline: an echo model resolves the label image (label_image=True), not colours")
         self.rayset = RaySet(rays, H, pose=self._mounting.P, grid=grid)  # one read-only ray set for all chains
         self.n_rays = self.rayset.n_rays
+        self._echoes.bind(rays, H, pose=self._mounting.P, grid=self.rayset.grid, sub_grid=echo_grid)   # and one over the sub-rays
         self.label_image = bool(label_image)
         self._flags = _lib.LT_TRACE_WRITE_MISSES | (_lib.LT_TRACE_LABEL_IMAGE if label_image else 0)
         self._merge = _lib.LT_TSDF_MERGE if merge else 0
@@ -402,10 +415,12 @@ class FusionScanPipeline:
                     raise RuntimeError("FusionScanPipeline: constructed with fixed_volume=False (submit_mergemesh only)")
                 rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays,
                                                  self.device)
-                rout = self._noise.render_into(rout, self.n_rays, self.device)
+                rout = self._echoes.resolve_into(self._noise.render_into(rout, self.n_rays, self.device), self.n_rays, self.device)
+                sub =self._echoes.render_into(rout, self.n_rays, self.device)   # (the sub-images, or ``rout`` itself)
                 scan = self._scan_clouds if kind == "clouds" else self._scan_images
-                keep = scan(ch, items, _chain.origin3(origin), _chain.out_ptrs(rout))
-                seen = self._returns.apply(rout, scan_index, ch["scene"], self.rayset.rays, ch["stream"], self.label_image)
+                keep = scan(ch, items, _chain.origin3(origin), _chain.out_ptrs(sub))
+                seen = self._echoes.apply(sub, rout, self.rayset.rays, origin, ch["stream"])
+                seen.update(self._returns.apply(rout, scan_index, ch["scene"], self.rayset.rays, ch["stream"], self.label_image))
                 seen.update(self._noise.apply(rout, scan_index, origin, ch["stream"], self.label_image))
                 return self._finish(ch, out, rout, ch["mesh"], keep, items, **seen)
         except BaseException:
@@ -450,7 +465,8 @@ class FusionScanPipeline:
             h, w = d.shape[0], d.shape[1]
             keep += [c, d, r]
             cp[k], dp[k], rp[k] = c.data_ptr(), d.data_ptr(), r.data_ptr()
-        _lib.check(self._lib.lt_fusion_scan_dev(ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h, self.rayset._h, n, cp, dp, rp, h, w,
+        _lib.check(self._lib.lt_fusion_scan_dev(ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h,
+                                                self._echoes.render_set(self.rayset)._h, n, cp, dp, rp, h, w,
                                                 1.0, self._merge, org, *ptrs, self._flags, vp(ch["stream"].cuda_stream), 0),
                    "lt_fusion_scan_dev")
         return keep
@@ -459,8 +475,8 @@ class FusionScanPipeline:
         """projection of the source scans + the fusion chain, ONE native call (``lt_deform_scan_dev``)"""
         cl, keep, is_f64 = _chain.cloud_table(clouds)
         beams, n_beams, _ = _chain.beam_table(self._beam_angles)
-        _lib.check(self._lib.lt_deform_scan_dev(ch["projector"]._h, ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h, self.rayset._h,
-                                                len(clouds), cl, is_f64, self._src_fov[0], self._src_fov[1], self._src_hw[0],
+        _lib.check(self._lib.lt_deform_scan_dev(ch["projector"]._h, ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h,
+                                                self._echoes.render_set(self.rayset)._h, len(clouds), cl, is_f64, self._src_fov[0], self._src_fov[1], self._src_hw[0],
                                                 self._src_hw[1], beams, n_beams, 1.0, self._merge, org, *ptrs, self._flags,
                                                 C.c_void_p(ch["stream"].cuda_stream), 0), "lt_deform_scan_dev")
         return keep
@@ -477,11 +493,11 @@ class FusionScanPipeline:
             sensor_t = (a["H"], self.n_rays // a["H"], self._src_fov[0], self._src_fov[1])
             dd = DeviceDeform(sensor_s, sensor_t, None, a["voxel_size"], beam_angles=self._beam_angles, device=self.device.index,
                               merge=a["merge"], mesh_volume=False, rayset=self.rayset, mm_state=self._mm_state,
-                              transformation=self.mount, returns=self.returns, noise=self.noise)
+                              transformation=self.mount, returns=self.returns, noise=self.noise, echoes=self._echoes)
             ch["deform"] = dd
         got = dd.mergemesh(clouds, origin, pack=False, out=out, seq=seq, scan_index=scan_index)
         more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after") + (_chain.Returns.KEYS if self._returns else ())
-                + (_chain.Noise.KEYS if self._noise else ())}
+                + (_chain.Noise.KEYS if self._noise else ()) + (_chain.Echoes.KEYS if self._echoes else ())}
         if self.mount is not None:   # (the chain's DeviceDeform has taken the hits into the target's frame)
             more["endpoints_scene"] = got["endpoints_scene"]
         return self._finish(ch, out, out, dd.mesh_obj, [got.get("source"), got.get("_keep")], clouds, **more)
@@ -634,6 +650,8 @@ class FusionScanPipeline:
             self._mm_state = None
         if getattr(self, "rayset", None) is not None and chains:
             self.rayset.close()
+        if getattr(self, "_echoes", None) is not None and chains:
+            self._echoes.close()
 
     def __enter__(self):
         return self

@@ -182,6 +182,99 @@ def noise_model(origin, model, scan, out, gate=None, range_error=True, state=Tru
     return extra
 
 
+def create_subrays(rays, model, stream=None):
+    """The sub-rays of a target sensor with a beam divergence (``lt_create_subrays_dev``), asynchronous on
+    ``stream`` (default the current one): ``rays`` [n, 3] float32 (CUDA, contiguous; the finished ray tensor, whatever pose,
+    table, sector or offsets made it) -> [S * n, 3] float32, PLANE BY PLANE: sub-ray ``k`` of cell ``i`` is row ``k * n + i``.
+    Plane 0 is ``rays`` byte for byte; plane ``k >= 1`` leaves at ``model.offsets()[k]`` from the central ray, ``a`` to the
+    left and ``b`` upwards in units of its length, not normalised (the ray set does that).  ``model``: a
+    :class:`~lidar_transfer_amd.config.EchoModel`."""
+    import torch
+
+    from .config import EchoModel
+    if not isinstance(model, EchoModel) or model.is_default:
+        raise ValueError("model: a lidar_transfer_amd.config.EchoModel with a divergence and at least two sub-rays")
+    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() \
+            or rays.numel() % 3:
+        raise ValueError("rays: contiguous float32 CUDA tensor [n, 3]")
+    n = rays.numel() // 3
+    dev = rays.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    args = model.args()
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        sub = torch.empty((model.subrays * n, 3), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().lt_create_subrays_dev(rays.data_ptr(), n, C.byref(args), sub.data_ptr(),
+                                                     C.c_void_p(st.cuda_stream)), "lt_create_subrays_dev")
+    return sub
+
+
+def echo_resolve(rays, origin, model, sub, out, n_echoes=True, fraction=True, stream=None):
+    """The target sensor's echo model (``lt_echo_resolve_dev``): the ``S`` sub-images ``sub`` of a render of
+    :func:`create_subrays`' rays resolved into the scan ``out``, asynchronous on ``stream`` (default the current one).  Per
+    cell the sub-hits (``tri >= 0`` and ``range > 0``) are walked in ``(range, k)`` order and grouped into echoes -- a sub-hit
+    more than ``separation`` behind an echo's first one opens the next --; an echo of at least ``min_subrays`` sub-hits is
+    detected; ``mode`` picks one of them; the cell gets the mean range of its sub-hits, ``1 / S`` of the sum of their
+    remissions, the label and triangle of its member with the smallest ``k`` and an end point on the CENTRAL ray at that
+    range.  A cell without a detected echo becomes the miss the render writes.  ``rays``: the central rays [n, 3] float32;
+    ``origin``: three numbers, where they start in the scene; ``model``: a :class:`~lidar_transfer_amd.config.EchoModel`;
+    ``sub``: the sub-render's images, ``range`` and ``tri`` [S * n] (needed), ``endcolors`` (the [S * n] label image) and
+    ``endrem`` (absent or ``None``: read as 0); ``out``: the scan's images (``Scene.alloc_outputs``' keys with the label image;
+    ``range`` and ``tri`` are needed, the others may be absent or ``None``), every cell of each written.  ``n_echoes`` /
+    ``fraction``: ``True`` -- a fresh [n] uint8 / float32 tensor, a tensor -- that one, ``None`` -- not wanted.  Returns
+    ``dict(n_echoes=..., echo_fraction=...)``: the number of detected echoes of every cell and the share ``c / S`` of the
+    beam's sub-rays in the reported one (0 for a miss)."""
+    import torch
+
+    from .config import EchoModel
+    if not isinstance(model, EchoModel) or model.is_default:
+        raise ValueError("model: a lidar_transfer_amd.config.EchoModel with a divergence and at least two sub-rays")
+    tri, rng = out.get("tri"), out.get("range")
+    if tri is None or rng is None:
+        raise ValueError("out: the scan's `tri` and `range` images are needed")
+    if sub.get("tri") is None or sub.get("range") is None:
+        raise ValueError("sub: the sub-render's `tri` and `range` images are needed")
+    n = tri.numel()
+    S = model.subrays
+    dev = tri.device
+
+    def ptrs(images, want, what):
+        ptr = {}
+        for key, (dt, numel) in want.items():
+            t = images.get(key)
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != numel
+                                  or t.device != dev):
+                raise ValueError(f"{what}[{key!r}]: contiguous {dt} CUDA tensor with {numel} elements on the device of `tri`")
+            ptr[key] = t.data_ptr() if t is not None else None
+        return ptr
+    o = ptrs(out, dict(endpoints=(torch.float32, 3 * n), endcolors=(torch.int32, n), range=(torch.float32, n),
+                       endrem=(torch.float32, n), tri=(torch.int32, n)), "out")
+    s = ptrs(sub, dict(endcolors=(torch.int32, S * n), range=(torch.float32, S * n), endrem=(torch.float32, S * n),
+                       tri=(torch.int32, S * n)), "sub")
+    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() \
+            or rays.numel() < 3 * n or rays.device != dev:
+        raise ValueError("rays: contiguous float32 CUDA tensor [n, 3], the central rays, on the device of `tri`")
+    extra = {}
+    for key, t, dt in (("n_echoes", n_echoes, torch.uint8), ("echo_fraction", fraction, torch.float32)):
+        if t is True:
+            t = torch.empty((n,), dtype=dt, device=dev)
+        elif t is False:
+            t = None
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != dev):
+            raise ValueError(f"{key}: contiguous {dt} CUDA tensor [n] on the device of `tri`")
+        extra[key] = t
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    args = model.args()
+    org = (C.c_float * 3)(*[float(x) for x in origin])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lt_echo_resolve_dev(
+            rays.data_ptr(), org, n, C.byref(args), s["range"], s["endcolors"], s["endrem"], s["tri"], o["endpoints"],
+            o["endcolors"], o["range"], o["endrem"], o["tri"],
+            extra["n_echoes"].data_ptr() if extra["n_echoes"] is not None else None,
+            extra["echo_fraction"].data_ptr() if extra["echo_fraction"] is not None else None, C.c_void_p(st.cuda_stream)),
+            "lt_echo_resolve_dev")
+    return extra
+
+
 def pack_scan(back_points, label_image, remissions, index=None):
     """Filtering + packing of ``MultiSemLaserScan.write`` (auxiliary/laserscan.py:1133-1160): returns
     ``(bin [N,4] float32, label [N] uint32)`` -- byte-for-byte what the reference writes to

@@ -50,6 +50,17 @@ def format_noise_totals(totals, rms):
         ", range error RMS " + ("n/a" if rms is None else f"{float(rms):.6f} m")
 
 
+#: how many echoes a cell of an echo model's ``n_echoes`` image detected (``echo_totals``, the CLI's closing line)
+ECHO_COUNTS = ("none", "one", "several")
+
+
+def format_echo_totals(totals, fraction):
+    """the CLI's closing line of a run with an echo model: ``Echoes: none N, one N, several N, mean fraction X`` (the cells per
+    number of detected echoes, and the mean of ``echo_fraction`` over the cells that detected one; ``None``: there was none)"""
+    return "Echoes: " + ", ".join(f"{name} {int(n)}" for name, n in zip(ECHO_COUNTS, totals)) + \
+        ", mean fraction " + ("n/a" if fraction is None else f"{float(fraction):.6f}")
+
+
 def sensor_tuple(s):
     """``(H, W, fov_up, fov_down)`` of a :class:`lidar_transfer_amd.config.SensorModel` (or such a tuple itself)"""
     if hasattr(s, "fov_up"):
@@ -147,7 +158,13 @@ class SequenceTransfer:
     the target sensor reports.  The cells per state and the squared ``range_error`` are summed on the device and read once
     at the end of :meth:`run` (``summary["noise_totals"]``, three numbers in :data:`NOISE_STATES`' order, and
     ``summary["range_error_rms"]`` over the noised cells).  ``cp`` renders no ray: with such a target it raises
-    ``ValueError``; so does a source sensor with the key."""
+    ``ValueError``; so does a source sensor with the key.
+    A target ``SensorModel`` with an ``echo_model`` block (kept as ``echoes``; ``None``: none) has its beams widened (DESIGN
+    7h): every chain renders the one shared sub-ray set and resolves it ahead of the two other models; evaluation and the
+    written files see the resolved scan.  The cells per number of detected echoes and the reported share of the beam are
+    summed on the device and read once at the end of :meth:`run` (``summary["echo_totals"]``, three numbers in
+    :data:`ECHO_COUNTS`' order, and ``summary["echo_fraction_mean"]`` over the cells with an echo).  ``cp`` renders no ray:
+    with such a target it raises ``ValueError``; so does a source sensor with the key."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -174,6 +191,10 @@ class SequenceTransfer:
         if self.noise is not None and self.adaption == "cp":
             raise ValueError("adaption cp renders no ray (no origin to jitter a range about): the target sensor's noise_model "
                              "cannot be applied -- use mesh or mergemesh, or a target file without the key")
+        self.echoes = getattr(target_sensor, "echo_model", lambda: None)()
+        if self.echoes is not None and self.adaption == "cp":
+            raise ValueError("adaption cp renders no ray (no beam to widen): the target sensor's echo_model cannot be applied "
+                             "-- use mesh or mergemesh, or a target file without the key")
         self.chains = 1 if self.adaption == "cp" else int(chains)     # `cp` always runs on one chain
         self.fusion, self.out_dir = fusion, out_dir
         self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
@@ -225,7 +246,7 @@ class SequenceTransfer:
             if self.adaption == "mergemesh":
                 self.vol_bnds = self._configured_bnds.copy()   # the ONE array of the sequence, kept current
                 self._mm = MergeMeshState(self.vol_bnds, approach.voxel_size, idx)
-            rayset = None
+            rayset, echoes = None, self.echoes
             every = dict(beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
                          transformation=self.mount, t_beam_table=m.beam_table, t_sector=m.sector, t_beam_azimuth=m.beam_azimuth,
                          returns=self.returns, noise=self.noise)
@@ -235,9 +256,12 @@ class SequenceTransfer:
                 else:
                     dd = DeviceDeform(self.source_sensor, self.target_sensor,
                                       None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
-                                      mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm, **every)
+                                      mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm, echoes=echoes,
+                                      **every)
                     rayset = dd.rayset
-                ch = dict(dd=dd, ev=None, q=None, thread=None, totals=None, codes=None, noise_totals=None,
+                    if self.echoes is not None:
+                        echoes = dd._echoes          # (the first chain's sub-ray set, shared like the plain one)
+                ch = dict(dd=dd, ev=None, q=None, thread=None, totals=None, codes=None, noise_totals=None, echo_totals=None,
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
                 if target_view:
                     ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx,
@@ -291,6 +315,13 @@ class SequenceTransfer:
                         ch["noise_sq"] = torch.zeros((), dtype=torch.float64, device=self.device)
                     ch["noise_totals"] += (out["noise_state"].unsqueeze(1) == ch["states"]).sum(0)
                     ch["noise_sq"] += torch.linalg.vector_norm(out["range_error"], dtype=torch.float64) ** 2
+                if self.echoes is not None:          # cells per number of echoes and the reported shares, summed likewise
+                    if ch["echo_totals"] is None:
+                        ch["counts"] = torch.arange(len(ECHO_COUNTS), dtype=torch.uint8, device=self.device)
+                        ch["echo_totals"] = torch.zeros(len(ECHO_COUNTS), dtype=torch.int64, device=self.device)
+                        ch["echo_fraction"] = torch.zeros((), dtype=torch.float64, device=self.device)
+                    ch["echo_totals"] += (out["n_echoes"].clamp(max=2).unsqueeze(1) == ch["counts"]).sum(0)
+                    ch["echo_fraction"] += out["echo_fraction"].sum(dtype=torch.float64)
                 if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
                     scan = ch["ev"].target_view if self.evaluate_mode == "target" else ch["ev"].source_scan
                     src = scan(*job["raw"], stream=st)
@@ -422,7 +453,18 @@ class SequenceTransfer:
                         sq_sum += float(ch["noise_sq"])
                         ch["noise_totals"] = ch["noise_sq"] = None       # (the next run starts its own)
                 rms = float(np.sqrt(sq_sum / noise_totals[1])) if noise_totals[1] else None
-            self.summary = dict(return_totals=totals, noise_totals=noise_totals, range_error_rms=rms, scans=n_done,
+            echo_totals = echo_mean = None
+            if self.echoes is not None:
+                echo_totals, share = [0] * len(ECHO_COUNTS), 0.0
+                for ch in self._chains:
+                    if ch["echo_totals"] is not None:
+                        ch["stream"].synchronize()
+                        echo_totals = [a + int(b) for a, b in zip(echo_totals, ch["echo_totals"].cpu().tolist())]
+                        share += float(ch["echo_fraction"])
+                        ch["echo_totals"] = ch["echo_fraction"] = None   # (the next run starts its own)
+                echo_mean = share / (echo_totals[1] + echo_totals[2]) if echo_totals[1] + echo_totals[2] else None
+            self.summary = dict(return_totals=totals, noise_totals=noise_totals, range_error_rms=rms, echo_totals=echo_totals,
+                                echo_fraction_mean=echo_mean, scans=n_done,
                                 chains=self.chains, adaption=self.adaption, fusion=self.fusion,
                                 mounted=self.mounted, beam_model=self.beam_model, azimuth_model=self.azimuth_model,
                                 beam_azimuth=self.beam_azimuth is not None,
