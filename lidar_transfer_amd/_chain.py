@@ -1,5 +1,8 @@
 """What the chain layer (``deform.py``, ``pipeline.py``, ``sequence.py``) hands the library's device entry points, in one
-place: the merged cloud, the ``lt_cloud`` and beam tables, origin and output pointers, and the target sensor's mounting.
+place: the merged cloud, the ``lt_cloud`` and beam tables, origin and output pointers, and -- :class:`Sensing` -- what
+stands between a chain's render and its result: the target sensor's mounting and its echo, return and noise models.  The
+chain layer makes one :class:`Sensing` per chain and calls ``plan``, its native call(s) with ``render_set`` and
+``out_ptrs(sub)``, then ``finish``; the order of the models lives there and nowhere else.
 Private; imports without a GPU and without the library (torch and numpy on first use)."""
 from __future__ import annotations
 
@@ -9,6 +12,11 @@ from . import _lib
 
 TRACE_FLAGS = _lib.LT_TRACE_WRITE_MISSES | _lib.LT_TRACE_LABEL_IMAGE   # every cell written, ``endcolors`` = the label image
 OUT_KEYS = ("endpoints", "endcolors", "range", "endrem", "tri")        # the render's outputs in the entry points' order
+#: why ``cp`` cannot honour a model behind the render, by the chain layer's name of the model: (the sensor file's key, its
+#: article, what ``cp`` does not render, what is missing).  Each site names its own order of precedence.
+CP_REFUSALS = dict(returns=("return_model", "a", "surface", "no hit triangle, no incidence angle"),
+                   noise=("noise_model", "a", "ray", "no origin to jitter a range about"),
+                   echoes=("echo_model", "an", "ray", "no beam to widen"))
 
 
 def merged_cloud(clouds):
@@ -260,8 +268,69 @@ class Mount:
         return rout
 
     def to_target(self, rout, out, stream):
-        """the hits of ``rout["endpoints"]`` (as rendered) into the target's frame in ``out["endpoints"]``, on ``stream``"""
-        if rout is out:
+        """the hits of ``rout["endpoints"]`` (as rendered) into the target's frame in ``out["endpoints"]``, on ``stream``;
+        nothing when the render wrote the caller's end points themselves (no mounting, or no end points wanted)"""
+        if rout.get("endpoints") is out.get("endpoints"):
             return
-        from .post import points_to_frame
-        points_to_frame(rout["endpoints"], self.T, tri=rout["tri"], out=out["endpoints"], stream=stream)
+        from . import post
+        post.points_to_frame(rout["endpoints"], self.T, tri=rout["tri"], out=out["endpoints"], stream=stream)
+
+
+class Sensing:
+    """What stands between a chain's render and its result, one object per chain: the target sensor's :class:`Mount`,
+    :class:`Echoes`, :class:`Returns` and :class:`Noise` (``mounting``, ``echoes``, ``returns``, ``noise``; each may be
+    off), made from the chain's ``transformation=``, ``returns=``, ``noise=`` and ``echoes=`` with the four constructors'
+    messages, led by ``who``.  THE ORDER LIVES HERE: :meth:`finish` resolves the echoes, then runs the return model, then
+    the noise model (gated by the return model's range gate), then takes the hits into the target's frame -- each once,
+    on the render that stands.  A site that did this in another order would still run and write other bytes; no site does
+    it itself.  ``mount``, ``origin``, ``P``: the mounting's pair, ray origin and pose.  With nothing on, nothing here
+    allocates or launches."""
+
+    def __init__(self, transformation, returns, noise, echoes, who):
+        self.mounting = Mount(transformation)
+        self.returns = Returns(returns, who)
+        self.noise = Noise(noise, self.returns.model, who)
+        self.echoes = Echoes(echoes, who)
+        self.mount, self.origin, self.P = self.mounting.pair, self.mounting.origin, self.mounting.P
+
+    @property
+    def keys(self):
+        """the result keys of the models that are on"""
+        return tuple(k for m in (self.returns, self.noise, self.echoes) if m for k in m.KEYS)
+
+    @property
+    def needs_scan_index(self):
+        """a return or a noise model is on: their draws are a function of the output scan's index in its sequence"""
+        return bool(self.returns or self.noise)
+
+    def bind(self, rays, t_H, grid=None, table=False, sub_grid=None):
+        """:meth:`Echoes.bind` with the mounting's pose"""
+        self.echoes.bind(rays, t_H, pose=self.P, grid=grid, table=table, sub_grid=sub_grid)
+        return self
+
+    def render_set(self, rayset):
+        """the ray set the chain renders with: :meth:`Echoes.render_set`"""
+        return self.echoes.render_set(rayset)
+
+    def plan(self, out, n_rays, device):
+        """``(rout, sub)`` for a scan whose result goes to ``out``: ``sub`` is what the native call renders into
+        (``out_ptrs(sub)``), ``rout`` the scan's images as rendered, which :meth:`finish` works on; both are ``out`` itself
+        with nothing on.  Allocates on the current stream."""
+        rout = self.returns.render_into(self.mounting.render_into(out, n_rays, device), n_rays, device)
+        rout = self.echoes.resolve_into(self.noise.render_into(rout, n_rays, device), n_rays, device)
+        return rout, self.echoes.render_into(rout, n_rays, device)
+
+    def finish(self, out, rout, sub, scan_index, scene, rays, origin, stream, label_image=True):
+        """Behind the render that stands, on ``stream``: ``sub`` resolved into ``rout``, the return model, the noise model,
+        the hits into the target's frame in ``out`` (``post.echo_resolve``, ``post.return_model``, ``post.noise_model``,
+        ``post.points_to_frame``, each only when it is on).  ``rays``: the CENTRAL rays, ``origin``: where they start,
+        ``scene``: what rendered.  Returns what the models add to the result (:attr:`keys`)."""
+        seen = self.echoes.apply(sub, rout, rays, origin, stream)
+        seen.update(self.returns.apply(rout, scan_index, scene, rays, stream, label_image))
+        seen.update(self.noise.apply(rout, scan_index, origin, stream, label_image))
+        self.mounting.to_target(rout, out, stream)
+        return seen
+
+    def close(self):
+        """closes the sub-ray set when this object owns it (a bound :class:`Echoes` handed in is shared)"""
+        self.echoes.close()

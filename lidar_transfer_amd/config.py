@@ -353,66 +353,55 @@ def return_hash(seed, scan, i):
     return return_hash_mix(return_hash_mix(return_hash_mix(int(seed)) + int(scan)) + int(i))
 
 
-class ReturnModel:
-    """What a TARGET sensor measures along its rays beyond the reference's "every hit returns" (the sensor file's
-    ``return_model`` block, DESIGN 7e), as one immutable value like :class:`TargetModel`: a range gate ``min_range`` /
-    ``max_range`` (metres), ``max_incidence`` (degrees between ray and surface normal; 90 never drops), ``remission``
-    (``"none"`` or ``"lambert"``: the remission times the cosine of the incidence angle), ``drop_rate`` (probability of a
-    random drop) and its ``seed``.  The constructor is the only place that normalises and validates -- finite numbers,
-    ``0 <= min_range <= max_range`` (``max_range`` may be ``inf``), ``0 < max_incidence <= 90``, ``0 <= drop_rate < 1``,
-    ``seed`` in uint32, else ``ValueError`` led by ``who`` -- and :meth:`of` returns ``None`` for a model in which every field
-    is at its default, as all-zero azimuth offsets are none.  What the library reads is derived here in float64 / Python
-    ints: :attr:`min_cos` ``= cos(max_incidence * pi / 180)`` (exactly 0 for 90), :attr:`drop_threshold`
-    ``= floor(drop_rate * 2^32)``."""
+class _ModelBlock:
+    """What :class:`ReturnModel`, :class:`NoiseModel` and :class:`EchoModel` share: one immutable value per block of a
+    TARGET sensor's file.  A class names its block's key (``KEY``) and its fields with their defaults (``DEFAULTS``), and its
+    constructor validates with :meth:`_number` / :meth:`_integer`, whose messages are led by ``who`` and the key.  Equality
+    is per block: a model never equals one of another block with the same field values."""
 
-    DEFAULTS = dict(min_range=0.0, max_range=float("inf"), max_incidence=90.0, remission="none", drop_rate=0.0, seed=0)
-
-    def __init__(self, min_range=0.0, max_range=float("inf"), max_incidence=90.0, remission="none", drop_rate=0.0, seed=0,
-                 who="return model"):
-        import math
-
-        def number(name, v):
-            try:
-                if isinstance(v, (bool, str)):
-                    raise TypeError
-                v = float(v)
-            except (TypeError, ValueError):
-                raise ValueError(f"{who}: return_model {name} must be a number, not {v!r}") from None
-            if math.isnan(v) or (math.isinf(v) and not (name == "max_range" and v > 0)):
-                raise ValueError(f"{who}: return_model {name} must be finite (max_range may be +inf), not {v}")
-            return v
-        lo, hi = number("min_range", min_range), number("max_range", max_range)
-        inc, rate = number("max_incidence", max_incidence), number("drop_rate", drop_rate)
-        if not 0.0 <= lo <= hi:
-            raise ValueError(f"{who}: return_model needs 0 <= min_range <= max_range (min_range = {lo}, max_range = {hi})")
-        if not 0.0 < inc <= 90.0:
-            raise ValueError(f"{who}: return_model needs 0 < max_incidence <= 90 degrees (max_incidence = {inc})")
-        if not 0.0 <= rate < 1.0:
-            raise ValueError(f"{who}: return_model needs 0 <= drop_rate < 1 (drop_rate = {rate})")
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= 0xFFFFFFFF:
-            raise ValueError(f"{who}: return_model seed must be an integer in [0, 2^32), not {seed!r}")
-        if remission not in ("none", "lambert"):
-            raise ValueError(f"{who}: return_model remission {remission!r} (none or lambert)")
-        self.__dict__.update(min_range=lo, max_range=hi, max_incidence=inc, remission=str(remission), drop_rate=rate,
-                             seed=int(seed))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("a ReturnModel does not change: make another")
+    KEY = None
+    DEFAULTS = {}
 
     @classmethod
-    def of(cls, block, who="return model"):
-        """The model of a sensor file's ``return_model`` block (a mapping, or ``None``: no key), or ``None`` when every field
-        is at its default; an unknown key and a block that is no mapping are ``ValueError``.  A :class:`ReturnModel` passes
-        through (``None`` if all-default)."""
+    def _number(cls, who, name, v, ok, say):
+        """``v`` as a float: a number (no bool, no string) for which ``ok(v)`` holds, else ``ValueError``: must be ``say``"""
+        try:
+            if isinstance(v, (bool, str)):
+                raise TypeError
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: {cls.KEY} {name} must be a number, not {v!r}") from None
+        if not ok(v):
+            raise ValueError(f"{who}: {cls.KEY} {name} must be {say}, not {v}")
+        return v
+
+    @classmethod
+    def _integer(cls, who, name, v, lo=0, hi=0xFFFFFFFF, say="[0, 2^32)"):
+        """``v`` as an int: an integer (no bool) in ``lo .. hi``, else ``ValueError``: must be an integer in ``say``"""
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{who}: {cls.KEY} {name} must be an integer in {say}, not {v!r}")
+        return int(v)
+
+    def __setattr__(self, name, value):
+        kind = type(self).__name__
+        raise AttributeError(f"{'an' if kind[0] in 'AEIOU' else 'a'} {kind} does not change: make another")
+
+    @classmethod
+    def of(cls, block, who=None):
+        """The model of a sensor file's block (a mapping, or ``None``: no key), or ``None`` when it is at its default (for an
+        :class:`EchoModel`: off); an unknown key and a block that is no mapping are ``ValueError``, led by ``who`` (default:
+        the key in words).  A model of this class passes through (``None`` if at its default)."""
+        if who is None:
+            who = cls.KEY.replace("_", " ")
         if block is None:
             return None
         if isinstance(block, cls):
             return None if block.is_default else block
         if not isinstance(block, dict):
-            raise ValueError(f"{who}: return_model must be a mapping of {', '.join(cls.DEFAULTS)}")
+            raise ValueError(f"{who}: {cls.KEY} must be a mapping of {', '.join(cls.DEFAULTS)}")
         unknown = sorted(set(map(str, block)) - set(cls.DEFAULTS))
         if unknown:
-            raise ValueError(f"{who}: return_model has unknown key(s) {', '.join(unknown)} (known: {', '.join(cls.DEFAULTS)})")
+            raise ValueError(f"{who}: {cls.KEY} has unknown key(s) {', '.join(unknown)} (known: {', '.join(cls.DEFAULTS)})")
         m = cls(who=who, **block)
         return None if m.is_default else m
 
@@ -424,13 +413,50 @@ class ReturnModel:
         return self.fields() == self.DEFAULTS
 
     def __eq__(self, other):
-        return isinstance(other, ReturnModel) and self.fields() == other.fields()
+        return isinstance(other, _ModelBlock) and other.KEY == self.KEY and self.fields() == other.fields()
 
     def __hash__(self):
         return hash(tuple(self.fields().values()))
 
     def __repr__(self):
-        return "ReturnModel(" + ", ".join(f"{k}={v!r}" for k, v in self.fields().items()) + ")"
+        return type(self).__name__ + "(" + ", ".join(f"{k}={v!r}" for k, v in self.fields().items()) + ")"
+
+
+class ReturnModel(_ModelBlock):
+    """What a TARGET sensor measures along its rays beyond the reference's "every hit returns" (the sensor file's
+    ``return_model`` block, DESIGN 7e), as one immutable value like :class:`TargetModel`: a range gate ``min_range`` /
+    ``max_range`` (metres), ``max_incidence`` (degrees between ray and surface normal; 90 never drops), ``remission``
+    (``"none"`` or ``"lambert"``: the remission times the cosine of the incidence angle), ``drop_rate`` (probability of a
+    random drop) and its ``seed``.  The constructor is the only place that normalises and validates -- finite numbers,
+    ``0 <= min_range <= max_range`` (``max_range`` may be ``inf``), ``0 < max_incidence <= 90``, ``0 <= drop_rate < 1``,
+    ``seed`` in uint32, else ``ValueError`` led by ``who`` -- and :meth:`of` returns ``None`` for a model in which every field
+    is at its default, as all-zero azimuth offsets are none.  What the library reads is derived here in float64 / Python
+    ints: :attr:`min_cos` ``= cos(max_incidence * pi / 180)`` (exactly 0 for 90), :attr:`drop_threshold`
+    ``= floor(drop_rate * 2^32)``."""
+
+    KEY = "return_model"
+    DEFAULTS = dict(min_range=0.0, max_range=float("inf"), max_incidence=90.0, remission="none", drop_rate=0.0, seed=0)
+
+    def __init__(self, min_range=0.0, max_range=float("inf"), max_incidence=90.0, remission="none", drop_rate=0.0, seed=0,
+                 who="return model"):
+        import math
+
+        def number(name, v):
+            return self._number(who, name, v, lambda v: math.isfinite(v) or (name == "max_range" and v == math.inf),
+                                "finite (max_range may be +inf)")
+        lo, hi = number("min_range", min_range), number("max_range", max_range)
+        inc, rate = number("max_incidence", max_incidence), number("drop_rate", drop_rate)
+        if not 0.0 <= lo <= hi:
+            raise ValueError(f"{who}: return_model needs 0 <= min_range <= max_range (min_range = {lo}, max_range = {hi})")
+        if not 0.0 < inc <= 90.0:
+            raise ValueError(f"{who}: return_model needs 0 < max_incidence <= 90 degrees (max_incidence = {inc})")
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"{who}: return_model needs 0 <= drop_rate < 1 (drop_rate = {rate})")
+        seed = self._integer(who, "seed", seed)
+        if remission not in ("none", "lambert"):
+            raise ValueError(f"{who}: return_model remission {remission!r} (none or lambert)")
+        self.__dict__.update(min_range=lo, max_range=hi, max_incidence=inc, remission=str(remission), drop_rate=rate,
+                             seed=seed)
 
     @cached_property
     def min_cos(self):
@@ -454,7 +480,7 @@ class ReturnModel:
                                     _lib.LT_RETURN_LAMBERT if self.lambert else 0)
 
 
-class NoiseModel:
+class NoiseModel(_ModelBlock):
     """The error of what a TARGET sensor measures (the sensor file's ``noise_model`` block), one immutable value
     like :class:`ReturnModel` and beside it: the standard deviation of the range jitter ``range_sigma + range_sigma_rel *
     range`` (metres; metres per metre), the grid ``range_resolution`` ranges are reported on (metres, 0: none), the standard
@@ -464,6 +490,7 @@ class NoiseModel:
     else ``ValueError`` led by ``who`` -- and :meth:`of` returns ``None`` for a model in which every field is at its
     default.  The draws are a pure function of ``(seed, scan, cell)``: :func:`return_hash_mix` in a stream of its own."""
 
+    KEY = "noise_model"
     DEFAULTS = dict(range_sigma=0.0, range_sigma_rel=0.0, range_resolution=0.0, remission_sigma=0.0, remission_levels=0, seed=0)
 
     def __init__(self, range_sigma=0.0, range_sigma_rel=0.0, range_resolution=0.0, remission_sigma=0.0, remission_levels=0,
@@ -471,20 +498,10 @@ class NoiseModel:
         import math
 
         def number(name, v):
-            try:
-                if isinstance(v, (bool, str)):
-                    raise TypeError
-                v = float(v)
-            except (TypeError, ValueError):
-                raise ValueError(f"{who}: noise_model {name} must be a number, not {v!r}") from None
-            if not (math.isfinite(v) and v >= 0.0):
-                raise ValueError(f"{who}: noise_model {name} must be finite and not negative, not {v}")
-            return v
+            return self._number(who, name, v, lambda v: math.isfinite(v) and v >= 0.0, "finite and not negative")
 
         def integer(name, v):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFFFFFF:
-                raise ValueError(f"{who}: noise_model {name} must be an integer in [0, 2^32), not {v!r}")
-            return int(v)
+            return self._integer(who, name, v)
         fields = dict(range_sigma=number("range_sigma", range_sigma), range_sigma_rel=number("range_sigma_rel", range_sigma_rel),
                       range_resolution=number("range_resolution", range_resolution),
                       remission_sigma=number("remission_sigma", remission_sigma),
@@ -492,42 +509,6 @@ class NoiseModel:
         if fields["remission_levels"] == 1:
             raise ValueError(f"{who}: noise_model remission_levels must be 0 (off) or at least 2, not 1")
         self.__dict__.update(fields)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("a NoiseModel does not change: make another")
-
-    @classmethod
-    def of(cls, block, who="noise model"):
-        """The model of a sensor file's ``noise_model`` block (a mapping, or ``None``: no key), or ``None`` when every field is
-        at its default; an unknown key and a block that is no mapping are ``ValueError``.  A :class:`NoiseModel` passes
-        through (``None`` if all-default)."""
-        if block is None:
-            return None
-        if isinstance(block, cls):
-            return None if block.is_default else block
-        if not isinstance(block, dict):
-            raise ValueError(f"{who}: noise_model must be a mapping of {', '.join(cls.DEFAULTS)}")
-        unknown = sorted(set(map(str, block)) - set(cls.DEFAULTS))
-        if unknown:
-            raise ValueError(f"{who}: noise_model has unknown key(s) {', '.join(unknown)} (known: {', '.join(cls.DEFAULTS)})")
-        m = cls(who=who, **block)
-        return None if m.is_default else m
-
-    def fields(self):
-        return {k: getattr(self, k) for k in self.DEFAULTS}
-
-    @property
-    def is_default(self):
-        return self.fields() == self.DEFAULTS
-
-    def __eq__(self, other):
-        return isinstance(other, NoiseModel) and self.fields() == other.fields()
-
-    def __hash__(self):
-        return hash(tuple(self.fields().values()))
-
-    def __repr__(self):
-        return "NoiseModel(" + ", ".join(f"{k}={v!r}" for k, v in self.fields().items()) + ")"
 
     def args(self, gate=None):
         """the model as ``lt_noise_model_dev`` reads it (``_lib.NoiseModelArgs``); ``gate``: the sensor's :class:`ReturnModel`
@@ -538,7 +519,7 @@ class NoiseModel:
                                    self.remission_levels, self.seed)
 
 
-class EchoModel:
+class EchoModel(_ModelBlock):
     """The width of a TARGET sensor's beams (the sensor file's ``echo_model`` block), one immutable value like
     :class:`ReturnModel` and :class:`NoiseModel` and beside them: the full cone angle ``divergence`` of a beam (degrees, 0:
     a line), the number ``subrays`` of rays a cell is rendered with (1..8, 1: a line) -- the centre ray and ``subrays - 1``
@@ -547,6 +528,7 @@ class EchoModel:
     the ``mode`` that picks the reported echo.  The constructor is the only place that normalises and validates, else
     ``ValueError`` led by ``who``; :meth:`of` returns ``None`` for a model that is off (``divergence`` 0 or ``subrays`` 1)."""
 
+    KEY = "echo_model"
     DEFAULTS = dict(divergence=0.0, subrays=1, ring=0.7071, separation=0.5, min_subrays=1, mode="strongest")
     MODES = ("first", "strongest", "last")   # in the order of LT_ECHO_FIRST, LT_ECHO_STRONGEST, LT_ECHO_LAST
     MAX_SUBRAYS = 8                          # LT_ECHO_MAX_SUBRAYS
@@ -556,20 +538,10 @@ class EchoModel:
         import math
 
         def number(name, v, ok, say):
-            try:
-                if isinstance(v, (bool, str)):
-                    raise TypeError
-                v = float(v)
-            except (TypeError, ValueError):
-                raise ValueError(f"{who}: echo_model {name} must be a number, not {v!r}") from None
-            if not (math.isfinite(v) and ok(v)):
-                raise ValueError(f"{who}: echo_model {name} must be {say}, not {v}")
-            return v
+            return self._number(who, name, v, lambda v: math.isfinite(v) and ok(v), say)
 
         def integer(name, v, lo, hi):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-                raise ValueError(f"{who}: echo_model {name} must be an integer in [{lo}, {hi}], not {v!r}")
-            return int(v)
+            return self._integer(who, name, v, lo, hi, f"[{lo}, {hi}]")
         fields = dict(divergence=number("divergence", divergence, lambda v: 0.0 <= v < 180.0, "in [0, 180) degrees"),
                       subrays=integer("subrays", subrays, 1, self.MAX_SUBRAYS),
                       ring=number("ring", ring, lambda v: 0.0 < v <= 1.0, "in (0, 1]"),
@@ -580,42 +552,10 @@ class EchoModel:
         fields["mode"] = mode
         self.__dict__.update(fields)
 
-    def __setattr__(self, name, value):
-        raise AttributeError("an EchoModel does not change: make another")
-
-    @classmethod
-    def of(cls, block, who="echo model"):
-        """The model of a sensor file's ``echo_model`` block (a mapping, or ``None``: no key), or ``None`` when it is off; an
-        unknown key and a block that is no mapping are ``ValueError``.  An :class:`EchoModel` passes through (``None`` if
-        off)."""
-        if block is None:
-            return None
-        if isinstance(block, cls):
-            return None if block.is_default else block
-        if not isinstance(block, dict):
-            raise ValueError(f"{who}: echo_model must be a mapping of {', '.join(cls.DEFAULTS)}")
-        unknown = sorted(set(map(str, block)) - set(cls.DEFAULTS))
-        if unknown:
-            raise ValueError(f"{who}: echo_model has unknown key(s) {', '.join(unknown)} (known: {', '.join(cls.DEFAULTS)})")
-        m = cls(who=who, **block)
-        return None if m.is_default else m
-
-    def fields(self):
-        return {k: getattr(self, k) for k in self.DEFAULTS}
-
     @property
     def is_default(self):
         """off: a beam without a width, or one ray per cell -- the absence of the key"""
         return self.divergence == 0.0 or self.subrays == 1
-
-    def __eq__(self, other):
-        return isinstance(other, EchoModel) and self.fields() == other.fields()
-
-    def __hash__(self):
-        return hash(tuple(self.fields().values()))
-
-    def __repr__(self):
-        return "EchoModel(" + ", ".join(f"{k}={v!r}" for k, v in self.fields().items()) + ")"
 
     def offsets(self):
         """The sub-rays' offsets, float64 ``[subrays, 2]``: row 0 is (0, 0), the centre ray; row ``k >= 1`` is ``tan(rho) *

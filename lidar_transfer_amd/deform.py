@@ -199,20 +199,17 @@ class DeviceDeform:
         self.vol_bnds = None
         self._mm_state, self._mm_own = mm_state, mm_state is None
         self._rayset_own = rayset is None
-        self._mounting = _chain.Mount(transformation)
-        self._returns = _chain.Returns(returns, "DeviceDeform")
-        self.returns = self._returns.model
-        self._noise = _chain.Noise(noise, self.returns, "DeviceDeform")
-        self.noise = self._noise.model
-        self._echoes = _chain.Echoes(echoes, "DeviceDeform")
-        self.echoes = self._echoes.model
+        # what stands between the render and the result (and the only place that knows its order)
+        s = self._sensing = _chain.Sensing(transformation, returns, noise, echoes, "DeviceDeform")
+        self._mounting, self._returns, self._noise, self._echoes = s.mounting, s.returns, s.noise, s.echoes
+        self.returns, self.noise, self.echoes = s.returns.model, s.noise.model, s.echoes.model
         m = self.t_model = TargetModel(t_beam_table, t_sector, t_beam_azimuth, "DeviceDeform").validate(
             self.t_H, (self.t_fov_up, self.t_fov_down), "DeviceDeform")
         # what the reverse projection reads on the device: the table and the offsets in radians
         self._t_brad = None if m.rows is None else torch.from_numpy(m.rows[:self.t_H].copy()).to(self.device)
         self._t_az_dev = None if m.azimuth_rad is None else torch.from_numpy(m.azimuth_rad.copy()).to(self.device)
         # ``origin``: the target sensor in the scene, where mesh / mergemesh cast from by default
-        self.mount, self.origin = self._mounting.pair, self._mounting.origin
+        self.mount, self.origin = s.mount, s.origin
         if mm_state is not None and vol_bnds is None:
             vol_bnds = mm_state.vol_bnds
         if vol_bnds is not None:
@@ -225,7 +222,7 @@ class DeviceDeform:
                 self._merge = self.vol._flags
             self.mesh_obj = DeviceMesh(idx)
             self.scene = Scene(idx)
-            pose = self._mounting.P
+            pose = s.P
             if rayset is None:
                 keys = dict(beam_table=m.beam_table, sector=m.sector, beam_azimuth=m.beam_azimuth)
                 rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=idx,
@@ -243,7 +240,7 @@ class DeviceDeform:
                     raise ValueError(f"DeviceDeform: the shared rayset was built for {what} than `t_{differs}`")
                 self.rayset = rayset
             # (the central rays stay in ``rayset.rays``: the return model reads its directions from them)
-            self._echoes.bind(self.rayset.rays, self.t_H, pose=pose, grid=self.rayset.grid, table=m.beam_table is not None)
+            s.bind(self.rayset.rays, self.t_H, grid=self.rayset.grid, table=m.beam_table is not None)
         self.n_rays = self.t_H * self.t_W
 
     t_beam_table = property(lambda self: self.t_model.beam_table)
@@ -336,18 +333,13 @@ class DeviceDeform:
         for k, o in enumerate(src):
             cp[k], dp[k], rp[k] = o["label_folded"].data_ptr(), o["range"].data_ptr(), o["rem"].data_ptr()
         out = self.scene.alloc_outputs(self.n_rays, label_image=True)
-        rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays, self.device)
-        rout = self._echoes.resolve_into(self._noise.render_into(rout, self.n_rays, self.device), self.n_rays, self.device)
-        sub = self._echoes.render_into(rout, self.n_rays, self.device)   # (the sub-images, or ``rout`` itself)
+        rout, sub = self._sensing.plan(out, self.n_rays, self.device)   # (what the render writes: the sub-images, or ``rout``)
         with torch.cuda.device(self.device):
-            _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self._echoes.render_set(self.rayset)._h,
+            _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self._sensing.render_set(self.rayset)._h,
                                               n, cp, dp, rp, self.H, self.W, 1.0, self._merge, _chain.origin3(origin),
                                               *_chain.out_ptrs(sub), _chain.TRACE_FLAGS, vp(st.cuda_stream), 0),
                        "lt_fusion_scan_dev")
-            seen = self._echoes.apply(sub, rout, self.rayset.rays, origin, st)
-            seen.update(self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st))
-            seen.update(self._noise.apply(rout, scan_index, origin, st))
-            self._mounting.to_target(rout, out, st)
+            seen = self._sensing.finish(out, rout, sub, scan_index, self.scene, self.rayset.rays, origin, st)
             if ev:
                 ev[2].record(st)
             res = self._result(out, rout, source=src, **seen)
@@ -437,9 +429,7 @@ class DeviceDeform:
                 raise ValueError("DeviceDeform.mergemesh: a return model needs scan_index, the output scan's index in its sequence")
             if self._noise and scan_index is None:
                 raise ValueError("DeviceDeform.mergemesh: a noise model needs scan_index, the output scan's index in its sequence")
-            rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays, self.device)
-            rout = self._echoes.resolve_into(self._noise.render_into(rout, self.n_rays, self.device), self.n_rays, self.device)
-            sub = self._echoes.render_into(rout, self.n_rays, self.device)   # (the sub-images, or ``rout`` itself)
+            rout, sub = self._sensing.plan(out, self.n_rays, self.device)   # (what the render writes: the sub-images, or ``rout``)
             first, again, more = (self._mm_composed if source_images else self._mm_native)(
                 mm, cloud, seq, _chain.origin3(origin), _chain.out_ptrs(sub), st)
             pred, vol = mm.pred, None
@@ -466,10 +456,8 @@ class DeviceDeform:
                 mm.stats["waited" if vol is None else "rerun"] += 1
                 vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
                 again(vol)
-            more.update(self._echoes.apply(sub, rout, self.rayset.rays, origin, st))   # (once, on the render that stands)
-            more.update(self._returns.apply(rout, scan_index, self.scene, self.rayset.rays, st))
-            more.update(self._noise.apply(rout, scan_index, origin, st))
-            self._mounting.to_target(rout, out, st)
+            # (once, on the render that stands)
+            more.update(self._sensing.finish(out, rout, sub, scan_index, self.scene, self.rayset.rays, origin, st))
             res = self._result(out, rout, vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
                                vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol, **more)
             if pack:
@@ -485,7 +473,7 @@ class DeviceDeform:
         cl, keep, is_f64 = _chain.cloud_table([cloud])
         beams = _chain.beam_table(self.beam_angles)   # (pointer, n, the array: alive as long as the callables)
         p = self.projector._h
-        rs = self._echoes.render_set(self.rayset)
+        rs = self._sensing.render_set(self.rayset)
 
         def first(vol):
             tflags = vol._flags if vol is not None else (_lib.LT_TSDF_HOST_MODE if self._fusion == "numpy" else self._merge)
@@ -508,7 +496,7 @@ class DeviceDeform:
         returned under ``source``"""
         vp = C.c_void_p
         src = {}
-        rs = self._echoes.render_set(self.rayset)
+        rs = self._sensing.render_set(self.rayset)
 
         def again(vol):
             cp, dp, rp = (vp * 1)(src["label_folded"].data_ptr()), (vp * 1)(src["range"].data_ptr()), (vp * 1)(src["rem"].data_ptr())
@@ -538,15 +526,11 @@ class DeviceDeform:
         ``cp`` renders no surface, so there is no incidence angle: with a return model it raises ``ValueError``; it renders
         no ray either, so there is no origin to jitter a range about: with a noise model it raises as well; and no beam to
         widen: with an echo model it raises too."""
-        if self._echoes:
-            raise ValueError("DeviceDeform.cp: the target sensor has an echo_model, but cp renders no ray (no beam to widen): "
-                             "use mesh or mergemesh, or a target file without the key")
-        if self._noise:
-            raise ValueError("DeviceDeform.cp: the target sensor has a noise_model, but cp renders no ray (no origin to jitter "
-                             "a range about): use mesh or mergemesh, or a target file without the key")
-        if self._returns:
-            raise ValueError("DeviceDeform.cp: the target sensor has a return_model, but cp renders no surface (no hit triangle, "
-                             "no incidence angle): use mesh or mergemesh, or a target file without the key")
+        for name in ("echoes", "noise", "returns"):
+            if getattr(self, name) is not None:
+                key, a, what, why = _chain.CP_REFUSALS[name]
+                raise ValueError(f"DeviceDeform.cp: the target sensor has {a} {key}, but cp renders no {what} ({why}): use mesh "
+                                 "or mergemesh, or a target file without the key")
         torch = self._torch
         st = self._stream()
         pf = self.preserve_float
@@ -625,8 +609,8 @@ class DeviceDeform:
         if getattr(self, "_mm_state", None) is not None and getattr(self, "_mm_own", False):
             self._mm_state.close()
         self._mm_state = None
-        if getattr(self, "_echoes", None) is not None:
-            self._echoes.close()
+        if getattr(self, "_sensing", None) is not None:
+            self._sensing.close()
         for name in ("rayset", "scene", "mesh_obj", "vol", "projector"):
             obj = getattr(self, name, None)
             if obj is not None:

@@ -355,19 +355,16 @@ class FusionScanPipeline:
         self.device = rays.device if device is None else torch.device("cuda", device)
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
-        self._mounting = _chain.Mount(transformation)
-        self.mount, self.origin = self._mounting.pair, self._mounting.origin
-        self._returns = _chain.Returns(returns, "FusionScanPipeline")
-        self.returns = self._returns.model
-        self._noise = _chain.Noise(noise, self.returns, "FusionScanPipeline")
-        self.noise = self._noise.model
-        self._echoes = _chain.Echoes(echoes, "FusionScanPipeline")
-        self.echoes = self._echoes.model
+        # what stands between the render and the result (and the only place that knows its order); shared by the chains
+        s = self._sensing = _chain.Sensing(transformation, returns, noise, echoes, "FusionScanPipeline")
+        self._mounting, self._returns, self._noise, self._echoes = s.mounting, s.returns, s.noise, s.echoes
+        self.mount, self.origin = s.mount, s.origin
+        self.returns, self.noise, self.echoes = s.returns.model, s.noise.model, s.echoes.model
         if self._echoes and not label_image:
             raise ValueError("FusionScanPipeline: an echo model resolves the label image (label_image=True), not colours")
-        self.rayset = RaySet(rays, H, pose=self._mounting.P, grid=grid)  # one read-only ray set for all chains
+        self.rayset = RaySet(rays, H, pose=s.P, grid=grid)  # one read-only ray set for all chains
         self.n_rays = self.rayset.n_rays
-        self._echoes.bind(rays, H, pose=self._mounting.P, grid=self.rayset.grid, sub_grid=echo_grid)   # and one over the sub-rays
+        s.bind(rays, H, grid=self.rayset.grid, sub_grid=echo_grid)   # and one over the sub-rays
         self.label_image = bool(label_image)
         self._flags = _lib.LT_TRACE_WRITE_MISSES | (_lib.LT_TRACE_LABEL_IMAGE if label_image else 0)
         self._merge = _lib.LT_TSDF_MERGE if merge else 0
@@ -413,15 +410,11 @@ class FusionScanPipeline:
                     return self._scan_mergemesh(ch, items, origin, out, seq, scan_index)
                 if ch["vol"] is None:
                     raise RuntimeError("FusionScanPipeline: constructed with fixed_volume=False (submit_mergemesh only)")
-                rout = self._returns.render_into(self._mounting.render_into(out, self.n_rays, self.device), self.n_rays,
-                                                 self.device)
-                rout = self._echoes.resolve_into(self._noise.render_into(rout, self.n_rays, self.device), self.n_rays, self.device)
-                sub =self._echoes.render_into(rout, self.n_rays, self.device)   # (the sub-images, or ``rout`` itself)
+                rout, sub = self._sensing.plan(out, self.n_rays, self.device)   # (what the render writes: the sub-images, or ``rout``)
                 scan = self._scan_clouds if kind == "clouds" else self._scan_images
                 keep = scan(ch, items, _chain.origin3(origin), _chain.out_ptrs(sub))
-                seen = self._echoes.apply(sub, rout, self.rayset.rays, origin, ch["stream"])
-                seen.update(self._returns.apply(rout, scan_index, ch["scene"], self.rayset.rays, ch["stream"], self.label_image))
-                seen.update(self._noise.apply(rout, scan_index, origin, ch["stream"], self.label_image))
+                seen = self._sensing.finish(out, rout, sub, scan_index, ch["scene"], self.rayset.rays, origin, ch["stream"],
+                                            self.label_image)
                 return self._finish(ch, out, rout, ch["mesh"], keep, items, **seen)
         except BaseException:
             if kind == "mergemesh":
@@ -429,12 +422,12 @@ class FusionScanPipeline:
             raise
 
     def _finish(self, ch, out, rout, mesh, keep, items, **more):
-        """What every scan ends in: the hits into the target's frame (a mounted target; ``rout``: what the render wrote), an
-        event behind the render on the chain's stream -- what wait() waits for, so the chain's next scan is queued while this
-        one still renders -- and the result; temporaries and inputs stay referenced until the event has passed."""
+        """What every scan ends in: an event behind the render and what followed it on the chain's stream -- what wait()
+        waits for, so the chain's next scan is queued while this one still renders -- and the result (``rout``: what the
+        render wrote; its end points are the result's ``endpoints_scene`` where the hits went into a mounted target's frame);
+        temporaries and inputs stay referenced until the event has passed."""
         res = dict(out, n_verts=mesh.n_verts, n_faces=mesh.n_faces, **more)
         if rout.get("endpoints") is not out.get("endpoints"):
-            self._mounting.to_target(rout, out, ch["stream"])
             res["endpoints_scene"] = rout["endpoints"]
         done = self._torch.cuda.Event()
         done.record(ch["stream"])
@@ -466,7 +459,7 @@ class FusionScanPipeline:
             keep += [c, d, r]
             cp[k], dp[k], rp[k] = c.data_ptr(), d.data_ptr(), r.data_ptr()
         _lib.check(self._lib.lt_fusion_scan_dev(ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h,
-                                                self._echoes.render_set(self.rayset)._h, n, cp, dp, rp, h, w,
+                                                self._sensing.render_set(self.rayset)._h, n, cp, dp, rp, h, w,
                                                 1.0, self._merge, org, *ptrs, self._flags, vp(ch["stream"].cuda_stream), 0),
                    "lt_fusion_scan_dev")
         return keep
@@ -476,8 +469,9 @@ class FusionScanPipeline:
         cl, keep, is_f64 = _chain.cloud_table(clouds)
         beams, n_beams, _ = _chain.beam_table(self._beam_angles)
         _lib.check(self._lib.lt_deform_scan_dev(ch["projector"]._h, ch["vol"]._h, ch["mesh"]._h, ch["scene"]._h,
-                                                self._echoes.render_set(self.rayset)._h, len(clouds), cl, is_f64, self._src_fov[0], self._src_fov[1], self._src_hw[0],
-                                                self._src_hw[1], beams, n_beams, 1.0, self._merge, org, *ptrs, self._flags,
+                                                self._sensing.render_set(self.rayset)._h, len(clouds), cl, is_f64, self._src_fov[0],
+                                                self._src_fov[1], self._src_hw[0], self._src_hw[1], beams, n_beams, 1.0,
+                                                self._merge, org, *ptrs, self._flags,
                                                 C.c_void_p(ch["stream"].cuda_stream), 0), "lt_deform_scan_dev")
         return keep
 
@@ -496,9 +490,8 @@ class FusionScanPipeline:
                               transformation=self.mount, returns=self.returns, noise=self.noise, echoes=self._echoes)
             ch["deform"] = dd
         got = dd.mergemesh(clouds, origin, pack=False, out=out, seq=seq, scan_index=scan_index)
-        more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after") + (_chain.Returns.KEYS if self._returns else ())
-                + (_chain.Noise.KEYS if self._noise else ()) + (_chain.Echoes.KEYS if self._echoes else ())}
-        if self.mount is not None:   # (the chain's DeviceDeform has taken the hits into the target's frame)
+        more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after") + self._sensing.keys}
+        if self.mount is not None:   # (the chain's DeviceDeform has taken the hits into the target's frame: not again here)
             more["endpoints_scene"] = got["endpoints_scene"]
         return self._finish(ch, out, out, dd.mesh_obj, [got.get("source"), got.get("_keep")], clouds, **more)
 
@@ -530,7 +523,7 @@ class FusionScanPipeline:
     def _submit(self, kind, items, origin, out, inputs_ready, seq=None, scan_index=None):
         import threading
         torch = self._torch
-        if (self._returns or self._noise) and scan_index is None:
+        if self._sensing.needs_scan_index and scan_index is None:
             raise ValueError("FusionScanPipeline: a return model or a noise model needs scan_index, the output scan's index in "
                              "its sequence")
         if not inputs_ready:
@@ -585,7 +578,7 @@ class FusionScanPipeline:
             items.append((c[0], c[1], c[2]))
         if not items:   # (before the sequence number moves: no scan would ever take it, and every later one would wait for it)
             raise ValueError("FusionScanPipeline.submit_mergemesh: no clouds")
-        if (self._returns or self._noise) and scan_index is None:   # (before the sequence number moves, like the empty list)
+        if self._sensing.needs_scan_index and scan_index is None:   # (before the sequence number moves, like the empty list)
             raise ValueError("FusionScanPipeline.submit_mergemesh: a return model or a noise model needs scan_index")
         seq, self._mm_seq = self._mm_seq, self._mm_seq + 1
         return self._submit("mergemesh", items, origin, out, inputs_ready, seq=seq, scan_index=scan_index)
@@ -650,8 +643,8 @@ class FusionScanPipeline:
             self._mm_state = None
         if getattr(self, "rayset", None) is not None and chains:
             self.rayset.close()
-        if getattr(self, "_echoes", None) is not None and chains:
-            self._echoes.close()
+        if getattr(self, "_sensing", None) is not None and chains:
+            self._sensing.close()
 
     def __enter__(self):
         return self

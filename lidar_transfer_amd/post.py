@@ -72,6 +72,47 @@ def points_to_frame(points, T, tri=None, out=None, stream=None):
     return out
 
 
+def _image_ptrs(images, n, dev, what="out", label_image=True, endpoints=True):
+    """the pointers of a scan's ``images`` of ``n`` cells under the render's keys (``None``: absent or ``None``), each image
+    checked against its dtype, its element count and the device ``dev``; ``what`` names the argument in the message"""
+    import torch
+    want = dict(endcolors=(torch.int32, n if label_image else 3 * n), range=(torch.float32, n), endrem=(torch.float32, n),
+                tri=(torch.int32, n))
+    if endpoints:
+        want = dict(endpoints=(torch.float32, 3 * n), **want)
+    ptr = {}
+    for key, (dt, numel) in want.items():
+        t = images.get(key)
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != numel or t.device != dev):
+            raise ValueError(f"{what}[{key!r}]: contiguous {dt} CUDA tensor with {numel} elements on the device of `tri`")
+        ptr[key] = t.data_ptr() if t is not None else None
+    return ptr
+
+
+def _extra_outputs(asked, n, dev):
+    """``(dict, pointers)`` of a model's extra [n] outputs, ``asked`` as ``(key, value, dtype)``: ``True`` gives a fresh
+    tensor, a tensor is used as given (and checked), ``None`` / ``False`` gives none"""
+    import torch
+    extra = {}
+    for key, t, dt in asked:
+        if t is True:
+            t = torch.empty((n,), dtype=dt, device=dev)
+        elif t is False:
+            t = None
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != dev):
+            raise ValueError(f"{key}: contiguous {dt} CUDA tensor [n] on the device of `tri`")
+        extra[key] = t
+    return extra, [t.data_ptr() if t is not None else None for t in extra.values()]
+
+
+def _check_rays(rays, n, dev, message):
+    """``rays``: the contiguous float32 CUDA tensor of at least ``n`` rays on ``dev``, else ``ValueError(message)``"""
+    import torch
+    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() \
+            or rays.numel() < 3 * n or rays.device != dev:
+        raise ValueError(message)
+
+
 def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label_image=True, stream=None):
     """The target sensor's return model (``lt_return_model_dev``) on a rendered scan, in place and asynchronous
     on ``stream`` (default the current one): a return outside the range gate, seen beyond ``max_incidence`` or dropped at
@@ -95,34 +136,16 @@ def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label
         raise ValueError("out: the render's `tri` and `range` images are needed")
     n = tri.numel()
     dev = tri.device
-    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() \
-            or rays.numel() < 3 * n or rays.device != dev:
-        raise ValueError("rays: contiguous float32 CUDA tensor [n, 3] on the images' device")
-    want = dict(endpoints=(torch.float32, 3 * n), endcolors=(torch.int32, n if label_image else 3 * n),
-                range=(torch.float32, n), endrem=(torch.float32, n), tri=(torch.int32, n))
-    ptr = {}
-    for key, (dt, numel) in want.items():
-        t = out.get(key)
-        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != numel or t.device != dev):
-            raise ValueError(f"out[{key!r}]: contiguous {dt} CUDA tensor with {numel} elements on the device of `tri`")
-        ptr[key] = t.data_ptr() if t is not None else None
-    extra = {}
-    for key, t, dt in (("incidence", incidence, torch.float32), ("drop", drop, torch.uint8)):
-        if t is True:
-            t = torch.empty((n,), dtype=dt, device=dev)
-        elif t is False:
-            t = None
-        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != dev):
-            raise ValueError(f"{key}: contiguous {dt} CUDA tensor [n] on the device of `tri`")
-        extra[key] = t
+    _check_rays(rays, n, dev, "rays: contiguous float32 CUDA tensor [n, 3] on the images' device")
+    ptr = _image_ptrs(out, n, dev, label_image=label_image)
+    extra, more = _extra_outputs((("incidence", incidence, torch.float32), ("drop", drop, torch.uint8)), n, dev)
     st = torch.cuda.current_stream(dev) if stream is None else stream
     args = model.args()
     with torch.cuda.device(dev):
         _lib.check(_lib.load().lt_return_model_dev(
             scene._h, rays.data_ptr(), n, C.byref(args), int(scan) & 0xFFFFFFFF, ptr["endpoints"], ptr["endcolors"], ptr["range"],
-            ptr["endrem"], ptr["tri"], extra["incidence"].data_ptr() if extra["incidence"] is not None else None,
-            extra["drop"].data_ptr() if extra["drop"] is not None else None,
-            _lib.LT_TRACE_LABEL_IMAGE if label_image else 0, C.c_void_p(st.cuda_stream)), "lt_return_model_dev")
+            ptr["endrem"], ptr["tri"], *more, _lib.LT_TRACE_LABEL_IMAGE if label_image else 0, C.c_void_p(st.cuda_stream)),
+            "lt_return_model_dev")
     return extra
 
 
@@ -153,32 +176,15 @@ def noise_model(origin, model, scan, out, gate=None, range_error=True, state=Tru
         raise ValueError("out: the render's `tri` and `range` images are needed")
     n = tri.numel()
     dev = tri.device
-    want = dict(endpoints=(torch.float32, 3 * n), endcolors=(torch.int32, n if label_image else 3 * n),
-                range=(torch.float32, n), endrem=(torch.float32, n), tri=(torch.int32, n))
-    ptr = {}
-    for key, (dt, numel) in want.items():
-        t = out.get(key)
-        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != numel or t.device != dev):
-            raise ValueError(f"out[{key!r}]: contiguous {dt} CUDA tensor with {numel} elements on the device of `tri`")
-        ptr[key] = t.data_ptr() if t is not None else None
-    extra = {}
-    for key, t, dt in (("range_error", range_error, torch.float32), ("noise_state", state, torch.uint8)):
-        if t is True:
-            t = torch.empty((n,), dtype=dt, device=dev)
-        elif t is False:
-            t = None
-        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != dev):
-            raise ValueError(f"{key}: contiguous {dt} CUDA tensor [n] on the device of `tri`")
-        extra[key] = t
+    ptr = _image_ptrs(out, n, dev, label_image=label_image)
+    extra, more = _extra_outputs((("range_error", range_error, torch.float32), ("noise_state", state, torch.uint8)), n, dev)
     st = torch.cuda.current_stream(dev) if stream is None else stream
     args = model.args(gate)
     o = (C.c_float * 3)(*[float(x) for x in origin])
     with torch.cuda.device(dev):
         _lib.check(_lib.load().lt_noise_model_dev(
             o, n, C.byref(args), int(scan) & 0xFFFFFFFF, ptr["endpoints"], ptr["endcolors"], ptr["range"], ptr["endrem"],
-            ptr["tri"], extra["range_error"].data_ptr() if extra["range_error"] is not None else None,
-            extra["noise_state"].data_ptr() if extra["noise_state"] is not None else None,
-            _lib.LT_TRACE_LABEL_IMAGE if label_image else 0, C.c_void_p(st.cuda_stream)), "lt_noise_model_dev")
+            ptr["tri"], *more, _lib.LT_TRACE_LABEL_IMAGE if label_image else 0, C.c_void_p(st.cuda_stream)), "lt_noise_model_dev")
     return extra
 
 
@@ -236,42 +242,17 @@ def echo_resolve(rays, origin, model, sub, out, n_echoes=True, fraction=True, st
     n = tri.numel()
     S = model.subrays
     dev = tri.device
-
-    def ptrs(images, want, what):
-        ptr = {}
-        for key, (dt, numel) in want.items():
-            t = images.get(key)
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != numel
-                                  or t.device != dev):
-                raise ValueError(f"{what}[{key!r}]: contiguous {dt} CUDA tensor with {numel} elements on the device of `tri`")
-            ptr[key] = t.data_ptr() if t is not None else None
-        return ptr
-    o = ptrs(out, dict(endpoints=(torch.float32, 3 * n), endcolors=(torch.int32, n), range=(torch.float32, n),
-                       endrem=(torch.float32, n), tri=(torch.int32, n)), "out")
-    s = ptrs(sub, dict(endcolors=(torch.int32, S * n), range=(torch.float32, S * n), endrem=(torch.float32, S * n),
-                       tri=(torch.int32, S * n)), "sub")
-    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() \
-            or rays.numel() < 3 * n or rays.device != dev:
-        raise ValueError("rays: contiguous float32 CUDA tensor [n, 3], the central rays, on the device of `tri`")
-    extra = {}
-    for key, t, dt in (("n_echoes", n_echoes, torch.uint8), ("echo_fraction", fraction, torch.float32)):
-        if t is True:
-            t = torch.empty((n,), dtype=dt, device=dev)
-        elif t is False:
-            t = None
-        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != dev):
-            raise ValueError(f"{key}: contiguous {dt} CUDA tensor [n] on the device of `tri`")
-        extra[key] = t
+    o = _image_ptrs(out, n, dev)
+    s = _image_ptrs(sub, S * n, dev, "sub", endpoints=False)
+    _check_rays(rays, n, dev, "rays: contiguous float32 CUDA tensor [n, 3], the central rays, on the device of `tri`")
+    extra, more = _extra_outputs((("n_echoes", n_echoes, torch.uint8), ("echo_fraction", fraction, torch.float32)), n, dev)
     st = torch.cuda.current_stream(dev) if stream is None else stream
     args = model.args()
     org = (C.c_float * 3)(*[float(x) for x in origin])
     with torch.cuda.device(dev):
         _lib.check(_lib.load().lt_echo_resolve_dev(
             rays.data_ptr(), org, n, C.byref(args), s["range"], s["endcolors"], s["endrem"], s["tri"], o["endpoints"],
-            o["endcolors"], o["range"], o["endrem"], o["tri"],
-            extra["n_echoes"].data_ptr() if extra["n_echoes"] is not None else None,
-            extra["echo_fraction"].data_ptr() if extra["echo_fraction"] is not None else None, C.c_void_p(st.cuda_stream)),
-            "lt_echo_resolve_dev")
+            o["endcolors"], o["range"], o["endrem"], o["tri"], *more, C.c_void_p(st.cuda_stream)), "lt_echo_resolve_dev")
     return extra
 
 

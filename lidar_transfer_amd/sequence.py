@@ -25,6 +25,7 @@ import threading
 
 import numpy as np
 
+from ._chain import CP_REFUSALS
 from .deform import DeviceDeform, MergeMeshState
 from .evaluate import Evaluator
 from .ingest import ScanIngest, SequenceSource
@@ -88,6 +89,36 @@ def plausible_output(out_dir, sequence, idx):
 def cache_scans_needed(number_of_scans, chains, batch_interval):
     """raw scans that must stay resident: those of one output scan plus what the scans in flight have moved on by"""
     return int(number_of_scans) + int(chains) * max(int(batch_interval), 1)
+
+
+class _Tally:
+    """Cells per code (uint8, ``0 .. n_codes - 1``) plus one float64 sum, kept on ``device`` without a read-back: what a run
+    sums per chain for a model that is on.  Nothing is allocated before the first :meth:`add`, which runs on the chain's
+    stream; :meth:`read` is called once per run, behind a synchronise of that stream."""
+
+    def __init__(self, n_codes, device):
+        self.n_codes, self.device = int(n_codes), device
+        self.codes = self.counts = self.sum = None
+
+    def add(self, codes_u8, value_f64=None):
+        """one scan's ``codes_u8`` [n] and ``value_f64`` (a float64 scalar tensor, or ``None``), on the current stream"""
+        if self.counts is None:
+            import torch
+            if self.codes is None:
+                self.codes = torch.arange(self.n_codes, dtype=torch.uint8, device=self.device)
+            self.counts = torch.zeros(self.n_codes, dtype=torch.int64, device=self.device)
+        self.counts += (codes_u8.unsqueeze(1) == self.codes).sum(0)
+        if value_f64 is not None:
+            self.sum = value_f64 if self.sum is None else self.sum + value_f64
+
+    def read(self):
+        """``(cells per code as ints, the sum as a float)``; waits for the current stream"""
+        counts = [0] * self.n_codes if self.counts is None else [int(x) for x in self.counts.cpu().tolist()]
+        return counts, 0.0 if self.sum is None else float(self.sum)
+
+    def reset(self):
+        """the next :meth:`add` starts from zero (on ITS stream: nothing is launched here)"""
+        self.counts = self.sum = None
 
 
 class _Writer:
@@ -183,18 +214,12 @@ class SequenceTransfer:
         self.beam_table, self.sector, self.beam_azimuth = m.beam_table, m.sector, m.beam_azimuth
         self.beam_model = "linear" if m.beam_table is None else "table"
         self.azimuth_model = "full" if m.sector is None else "sector"
-        self.returns = getattr(target_sensor, "return_model", lambda: None)()
-        if self.returns is not None and self.adaption == "cp":
-            raise ValueError("adaption cp renders no surface (no hit triangle, no incidence angle): the target sensor's "
-                             "return_model cannot be applied -- use mesh or mergemesh, or a target file without the key")
-        self.noise = getattr(target_sensor, "noise_model", lambda: None)()
-        if self.noise is not None and self.adaption == "cp":
-            raise ValueError("adaption cp renders no ray (no origin to jitter a range about): the target sensor's noise_model "
-                             "cannot be applied -- use mesh or mergemesh, or a target file without the key")
-        self.echoes = getattr(target_sensor, "echo_model", lambda: None)()
-        if self.echoes is not None and self.adaption == "cp":
-            raise ValueError("adaption cp renders no ray (no beam to widen): the target sensor's echo_model cannot be applied "
-                             "-- use mesh or mergemesh, or a target file without the key")
+        for name in ("returns", "noise", "echoes"):
+            key, _, what, why = CP_REFUSALS[name]
+            setattr(self, name, getattr(target_sensor, key, lambda: None)())
+            if getattr(self, name) is not None and self.adaption == "cp":
+                raise ValueError(f"adaption cp renders no {what} ({why}): the target sensor's {key} cannot be applied -- use "
+                                 "mesh or mergemesh, or a target file without the key")
         self.chains = 1 if self.adaption == "cp" else int(chains)     # `cp` always runs on one chain
         self.fusion, self.out_dir = fusion, out_dir
         self.nclasses = int(nclasses) if nclasses is not None else len(approach.color_map)
@@ -261,7 +286,7 @@ class SequenceTransfer:
                     rayset = dd.rayset
                     if self.echoes is not None:
                         echoes = dd._echoes          # (the first chain's sub-ray set, shared like the plain one)
-                ch = dict(dd=dd, ev=None, q=None, thread=None, totals=None, codes=None, noise_totals=None, echo_totals=None,
+                ch = dict(dd=dd, ev=None, q=None, thread=None, tally=self._tallies(),
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
                 if target_view:
                     ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx,
@@ -278,6 +303,23 @@ class SequenceTransfer:
         except BaseException:
             self.close()
             raise
+
+    def _tallies(self):
+        """one chain's accumulators: a :class:`_Tally` per model that is on"""
+        n = dict(returns=len(RETURN_CODES), noise=len(NOISE_STATES), echoes=len(ECHO_COUNTS))
+        return {name: _Tally(n[name], self.device) for name in n if getattr(self, name) is not None}
+
+    def _read_tallies(self, name):
+        """``(cells per code, sum)`` of model ``name`` over the chains, read and reset; ``(None, 0.0)`` when it is off"""
+        if getattr(self, name) is None:
+            return None, 0.0
+        counts, value = None, 0.0
+        for ch in self._chains:
+            ch["stream"].synchronize()
+            c, v = ch["tally"][name].read()
+            counts, value = c if counts is None else [a + b for a, b in zip(counts, c)], value + v
+            ch["tally"][name].reset()
+        return counts, value
 
     # ---- the scan list -------------------------------------------------------------------------------------------------
     def scan_indices(self, offset=0, one_scan=False):
@@ -303,25 +345,13 @@ class SequenceTransfer:
                 else:
                     out = dd.mergemesh(clouds, pack=False, seq=job["k"], scan_index=job["idx"])
                     job["bnds_after"] = np.array(out["vol_bnds_after"]).reshape(3, 2)
-                if self.returns is not None:         # cells per code, summed on the chain's stream: read once, in run()
-                    if ch["totals"] is None:
-                        ch["codes"] = torch.arange(len(RETURN_CODES), dtype=torch.uint8, device=self.device)
-                        ch["totals"] = torch.zeros(len(RETURN_CODES), dtype=torch.int64, device=self.device)
-                    ch["totals"] += (out["drop"].unsqueeze(1) == ch["codes"]).sum(0)
-                if self.noise is not None:           # cells per state and the squared range error (float64), summed likewise
-                    if ch["noise_totals"] is None:
-                        ch["states"] = torch.arange(len(NOISE_STATES), dtype=torch.uint8, device=self.device)
-                        ch["noise_totals"] = torch.zeros(len(NOISE_STATES), dtype=torch.int64, device=self.device)
-                        ch["noise_sq"] = torch.zeros((), dtype=torch.float64, device=self.device)
-                    ch["noise_totals"] += (out["noise_state"].unsqueeze(1) == ch["states"]).sum(0)
-                    ch["noise_sq"] += torch.linalg.vector_norm(out["range_error"], dtype=torch.float64) ** 2
-                if self.echoes is not None:          # cells per number of echoes and the reported shares, summed likewise
-                    if ch["echo_totals"] is None:
-                        ch["counts"] = torch.arange(len(ECHO_COUNTS), dtype=torch.uint8, device=self.device)
-                        ch["echo_totals"] = torch.zeros(len(ECHO_COUNTS), dtype=torch.int64, device=self.device)
-                        ch["echo_fraction"] = torch.zeros((), dtype=torch.float64, device=self.device)
-                    ch["echo_totals"] += (out["n_echoes"].clamp(max=2).unsqueeze(1) == ch["counts"]).sum(0)
-                    ch["echo_fraction"] += out["echo_fraction"].sum(dtype=torch.float64)
+                tally = ch["tally"]                  # summed on the chain's stream: read once, in run()
+                if "returns" in tally:               # cells per code
+                    tally["returns"].add(out["drop"])
+                if "noise" in tally:                 # cells per state and the squared range error (float64)
+                    tally["noise"].add(out["noise_state"], torch.linalg.vector_norm(out["range_error"], dtype=torch.float64) ** 2)
+                if "echoes" in tally:                # cells per number of echoes (two stand for several), the reported shares
+                    tally["echoes"].add(out["n_echoes"].clamp(max=2), out["echo_fraction"].sum(dtype=torch.float64))
                 if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
                     scan = ch["ev"].target_view if self.evaluate_mode == "target" else ch["ev"].source_scan
                     src = scan(*job["raw"], stream=st)
@@ -435,34 +465,11 @@ class SequenceTransfer:
             for job in pending:                          # (a failure or an abandoned generator: let what is queued finish)
                 job["done"].wait()
                 job["written"].wait()
-            totals = None
-            if self.returns is not None:
-                totals = [0] * len(RETURN_CODES)
-                for ch in self._chains:
-                    if ch["totals"] is not None:
-                        ch["stream"].synchronize()
-                        totals = [a + int(b) for a, b in zip(totals, ch["totals"].cpu().tolist())]
-                        ch["totals"] = None          # (the next run starts its own)
-            noise_totals = rms = None
-            if self.noise is not None:
-                noise_totals, sq_sum = [0] * len(NOISE_STATES), 0.0
-                for ch in self._chains:
-                    if ch["noise_totals"] is not None:
-                        ch["stream"].synchronize()
-                        noise_totals = [a + int(b) for a, b in zip(noise_totals, ch["noise_totals"].cpu().tolist())]
-                        sq_sum += float(ch["noise_sq"])
-                        ch["noise_totals"] = ch["noise_sq"] = None       # (the next run starts its own)
-                rms = float(np.sqrt(sq_sum / noise_totals[1])) if noise_totals[1] else None
-            echo_totals = echo_mean = None
-            if self.echoes is not None:
-                echo_totals, share = [0] * len(ECHO_COUNTS), 0.0
-                for ch in self._chains:
-                    if ch["echo_totals"] is not None:
-                        ch["stream"].synchronize()
-                        echo_totals = [a + int(b) for a, b in zip(echo_totals, ch["echo_totals"].cpu().tolist())]
-                        share += float(ch["echo_fraction"])
-                        ch["echo_totals"] = ch["echo_fraction"] = None   # (the next run starts its own)
-                echo_mean = share / (echo_totals[1] + echo_totals[2]) if echo_totals[1] + echo_totals[2] else None
+            totals, _ = self._read_tallies("returns")
+            noise_totals, sq_sum = self._read_tallies("noise")
+            echo_totals, share = self._read_tallies("echoes")
+            rms = float(np.sqrt(sq_sum / noise_totals[1])) if noise_totals and noise_totals[1] else None
+            echo_mean = share / (echo_totals[1] + echo_totals[2]) if echo_totals and echo_totals[1] + echo_totals[2] else None
             self.summary = dict(return_totals=totals, noise_totals=noise_totals, range_error_rms=rms, echo_totals=echo_totals,
                                 echo_fraction_mean=echo_mean, scans=n_done,
                                 chains=self.chains, adaption=self.adaption, fusion=self.fusion,
