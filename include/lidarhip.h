@@ -800,6 +800,30 @@ int lt_echo_resolve_dev(const float* rays, const float* origin, int n, const lt_
                         float* endpoints, int* endcolors, float* range, float* endrem, int* tri,
                         unsigned char* n_echoes, float* fraction, void* stream);
 
+/* The DUAL-RETURN resolve: lt_echo_resolve_dev's cell, plus a SECOND echo of it.  Steps 1 - 7 above are unchanged and give the
+ * detected echoes D_0 .. D_{m-1} in walk order, the primary P chosen by model->mode, and the primary set of outputs, bit
+ * for bit what lt_echo_resolve_dev writes.  Then:
+ *   8. the SECOND echo is chosen by second_mode among the detected echoes OTHER THAN P: LT_ECHO_FIRST the earliest of the
+ *      rest in walk order, LT_ECHO_LAST the latest of the rest, LT_ECHO_STRONGEST the one of the rest with the largest Srem,
+ *      a tie going to the larger c and a remaining tie to the earlier; with m < 2 there is no second echo;
+ *   9. its outputs are step 7's expressions on its own c, St, Srem and rep:  range2[i] = float32(St / c);  endrem2[i] =
+ *      float32(Srem / S);  fraction2[i] = float32((double)c / S);  endcolors2[i] = sub_label[rep*n+i];  tri2[i] =
+ *      sub_tri[rep*n+i];  endpoints2[i][j] = float32(o[j] + h[j] * (double)range2[i]) -- on the CENTRAL ray.
+ * A cell without a second echo, or whose central ray has !(dd > 0), gets the miss LT_TRACE_WRITE_MISSES writes in the second
+ * set (end point (0, 0, 0), label 0, remission 0, range 0, tri -1) and fraction2 = 0.  Every output of both sets is written
+ * for every cell.  ONE rule, not a sensor's: with mode = strongest and second_mode = last a cell whose strongest echo is
+ * also its last gets the latest of the OTHER echoes, where a Velodyne head would report the second strongest.
+ * The arguments are lt_echo_resolve_dev's, with second_mode behind the model and the second set behind the first: endpoints2
+ * [n,3] f32, endcolors2 [n] i32, range2 [n] f32, endrem2 [n] f32, tri2 [n] i32, fraction2 [n] f32 -- DEVICE, overlapping
+ * neither an input nor another output.  range2 and tri2 are mandatory, the others may be NULL.  Everything else is
+ * lt_echo_resolve_dev's rule: one thread per cell, one launch, asynchronous on `stream`; n == 0 is LT_OK; a bad argument,
+ * a second_mode that is none of the three included, is LT_ERR_INVALID_ARG with a message. */
+int lt_echo_resolve_dual_dev(const float* rays, const float* origin, int n, const lt_echo_model* model, unsigned second_mode,
+                             const float* sub_range, const int* sub_label, const float* sub_rem, const int* sub_tri,
+                             float* endpoints, int* endcolors, float* range, float* endrem, int* tri,
+                             unsigned char* n_echoes, float* fraction, float* endpoints2, int* endcolors2, float* range2,
+                             float* endrem2, int* tri2, float* fraction2, void* stream);
+
 /* Pack a rendered scan in SemanticKITTI layout; replaces the filtering and the per-point struct.pack loops
  * of MultiSemLaserScan.write (auxiliary/laserscan.py:1133-1178).  Keeps, in order, the cells with
  * (index == NULL or index[i] > 0) and label[i] >= 0 and x + y + z != 0.  points [n,3] f32 or f64,

@@ -105,6 +105,9 @@ def main(argv=None):
     if target.echo_model() is not None and approach.adaption == "cp":
         print("adaption cp renders no ray: the target sensor's echo_model cannot be applied (use mesh or mergemesh).")
         return 1
+    if target.dual_return() is not None and approach.adaption == "cp":
+        print("adaption cp renders no ray: the target sensor's dual_return cannot be applied (use mesh or mergemesh).")
+        return 1
     log = open(args.log, "w") if args.log else None
     try:
         with SequenceTransfer((args.dataset, args.sequence), approach, source, target, out_dir=args.output if args.write else None,
@@ -131,6 +134,8 @@ def main(argv=None):
                         row["beam_azimuth"] = True
                     if tr.echoes is not None:
                         row["echo_model"] = True
+                    if tr.dual is not None:
+                        row["dual_return"] = True
                     log.write(json.dumps(row) + "\n")
             if tr.summary.get("return_totals") is not None:
                 from .sequence import format_return_totals
@@ -141,6 +146,8 @@ def main(argv=None):
             if tr.summary.get("echo_totals") is not None:
                 from .sequence import format_echo_totals
                 print(format_echo_totals(tr.summary["echo_totals"], tr.summary["echo_fraction_mean"]), flush=True)
+            if tr.summary.get("second_returns") is not None:
+                print("Second returns: %d" % tr.summary["second_returns"], flush=True)
             if log is not None:
                 log.write(json.dumps(dict(summary=tr.summary)) + "\n")
     finally:

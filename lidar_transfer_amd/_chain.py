@@ -1,8 +1,8 @@
 """What the chain layer (``deform.py``, ``pipeline.py``, ``sequence.py``) hands the library's device entry points, in one
 place: the merged cloud, the ``lt_cloud`` and beam tables, origin and output pointers, and -- :class:`Sensing` -- what
-stands between a chain's render and its result: the target sensor's mounting and its echo, return and noise models.  The
-chain layer makes one :class:`Sensing` per chain and calls ``plan``, its native call(s) with ``render_set`` and
-``out_ptrs(sub)``, then ``finish``; the order of the models lives there and nowhere else.
+stands between a chain's render and its result: the target sensor's mounting, its echo, return and noise models and its
+dual-return setting.  The chain layer makes one :class:`Sensing` per chain and calls ``plan``, its native call(s) with
+``render_set`` and ``out_ptrs(sub)``, then ``finish``; the order of the models lives there and nowhere else.
 Private; imports without a GPU and without the library (torch and numpy on first use)."""
 from __future__ import annotations
 
@@ -16,7 +16,11 @@ OUT_KEYS = ("endpoints", "endcolors", "range", "endrem", "tri")        # the ren
 #: article, what ``cp`` does not render, what is missing).  Each site names its own order of precedence.
 CP_REFUSALS = dict(returns=("return_model", "a", "surface", "no hit triangle, no incidence angle"),
                    noise=("noise_model", "a", "ray", "no origin to jitter a range about"),
-                   echoes=("echo_model", "an", "ray", "no beam to widen"))
+                   echoes=("echo_model", "an", "ray", "no beam to widen"),
+                   dual=("dual_return", "a", "ray", "no echo to choose a second from"))
+#: what the return and noise models' seeds are xor-ed with (uint32) for a scan's SECOND return: a measurement of its own,
+#: drawn for the same ``(scan, cell)``
+SECOND_SEED_XOR = 0x9E3779B9
 
 
 def merged_cloud(clouds):
@@ -97,15 +101,17 @@ class Returns:
         copy with a ``tri`` image (the model reads the hit triangle).  Allocates on the current stream."""
         return rout if self.model is None else with_tri(rout, n_rays, device)
 
-    def apply(self, rout, scan, scene, rays, stream, label_image=True):
+    def apply(self, rout, scan, scene, rays, stream, label_image=True, seed_xor=0):
         """the model on the rendered images ``rout`` of output scan ``scan`` (its index in its sequence), on ``stream``;
-        returns ``dict(incidence=, drop=)``, or ``{}`` without a model"""
+        returns ``dict(incidence=, drop=)``, or ``{}`` without a model.  ``seed_xor``: 0, or what the model's seed is xor-ed
+        with for this call (a scan's second return)"""
         if self.model is None:
             return {}
         if scan is None:
             raise ValueError("a return model needs the output scan's index in its sequence (scan_index=)")
         from . import post
-        return post.return_model(scene, rays, self.model, scan, rout, label_image=label_image, stream=stream)
+        more = dict(seed_xor=seed_xor) if seed_xor else {}   # (0: today's call, argument for argument)
+        return post.return_model(scene, rays, self.model, scan, rout, label_image=label_image, stream=stream, **more)
 
 
 class Noise:
@@ -132,15 +138,17 @@ class Noise:
         """as ``Returns.render_into``: the model reads ``tri`` to tell a return from a miss"""
         return rout if self.model is None else with_tri(rout, n_rays, device)
 
-    def apply(self, rout, scan, origin, stream, label_image=True):
+    def apply(self, rout, scan, origin, stream, label_image=True, seed_xor=0):
         """the model on the rendered images ``rout`` of output scan ``scan`` (its index in its sequence) whose rays start at
-        ``origin``, on ``stream``; returns ``dict(range_error=, noise_state=)``, or ``{}`` without a model"""
+        ``origin``, on ``stream``; returns ``dict(range_error=, noise_state=)``, or ``{}`` without a model.  ``seed_xor``: as
+        for :meth:`Returns.apply`"""
         if self.model is None:
             return {}
         if scan is None:
             raise ValueError("a noise model needs the output scan's index in its sequence (scan_index=)")
         from . import post
-        return post.noise_model(origin, self.model, scan, rout, gate=self.gate, label_image=label_image, stream=stream)
+        more = dict(seed_xor=seed_xor) if seed_xor else {}
+        return post.noise_model(origin, self.model, scan, rout, gate=self.gate, label_image=label_image, stream=stream, **more)
 
 
 class Echoes:
@@ -237,6 +245,35 @@ class Echoes:
         self.rayset = self.subrays = None
 
 
+class Dual:
+    """The target sensor's dual-return setting on a chain (``config.DualReturn`` or ``None``), beside
+    :class:`Echoes`, whose resolve it widens: ``None`` or ``second: none`` is off, and then nothing anywhere changes.  On, a
+    scan's images are PLANE 0 of allocations of ``2 n`` cells whose plane 1 holds the second return (:meth:`planes`), so that
+    one frame change and one packing serve both."""
+
+    KEYS = ("second",)
+
+    def __init__(self, setting, who="dual return"):
+        from .config import DualReturn
+        if setting is not None and not isinstance(setting, DualReturn):
+            raise ValueError(f"{who}: dual= takes a lidar_transfer_amd.config.DualReturn (SensorModel.dual_return()) or None")
+        self.setting = None if setting is None or setting.is_default else setting
+
+    def __bool__(self):
+        return self.setting is not None
+
+    @staticmethod
+    def planes(n_rays, device):
+        """the render's five images for ``2 * n_rays`` cells, plane by plane.  Allocates on the current stream."""
+        import torch
+        m = 2 * int(n_rays)
+        return dict(endpoints=torch.empty((m, 3), dtype=torch.float32, device=device),
+                    endcolors=torch.empty((m,), dtype=torch.int32, device=device),
+                    range=torch.empty((m,), dtype=torch.float32, device=device),
+                    endrem=torch.empty((m,), dtype=torch.float32, device=device),
+                    tri=torch.empty((m,), dtype=torch.int32, device=device))
+
+
 class Mount:
     """The target sensor's mounting from the approach file's ``transformation`` (``config.mount_of``).  ``pair``: ``(T, P)``,
     or ``None`` for no mounting (``None``, empty, the identity) -- then nothing here allocates or launches.  ``T``
@@ -278,25 +315,31 @@ class Mount:
 
 class Sensing:
     """What stands between a chain's render and its result, one object per chain: the target sensor's :class:`Mount`,
-    :class:`Echoes`, :class:`Returns` and :class:`Noise` (``mounting``, ``echoes``, ``returns``, ``noise``; each may be
-    off), made from the chain's ``transformation=``, ``returns=``, ``noise=`` and ``echoes=`` with the four constructors'
-    messages, led by ``who``.  THE ORDER LIVES HERE: :meth:`finish` resolves the echoes, then runs the return model, then
-    the noise model (gated by the return model's range gate), then takes the hits into the target's frame -- each once,
-    on the render that stands.  A site that did this in another order would still run and write other bytes; no site does
-    it itself.  ``mount``, ``origin``, ``P``: the mounting's pair, ray origin and pose.  With nothing on, nothing here
-    allocates or launches."""
+    :class:`Echoes`, :class:`Returns`, :class:`Noise` and :class:`Dual` (``mounting``, ``echoes``, ``returns``, ``noise``,
+    ``dual``; each may be off), made from the chain's ``transformation=``, ``returns=``, ``noise=``, ``echoes=`` and ``dual=``
+    with the constructors' messages, led by ``who``.  THE ORDER LIVES HERE: :meth:`finish` resolves the echoes, then runs
+    the return model, then the noise model (gated by the return model's range gate), then takes the hits into the target's
+    frame -- each once, on the render that stands.  With a dual return the resolve writes two returns, each model runs on the
+    primary and then on the second (seeds xor-ed with :data:`SECOND_SEED_XOR`), and ONE frame change covers both planes.  A
+    site that did this in another order would still run and write other bytes; no site does it itself.  ``mount``,
+    ``origin``, ``P``: the mounting's pair, ray origin and pose.  With nothing on, nothing here allocates or launches."""
 
-    def __init__(self, transformation, returns, noise, echoes, who):
+    def __init__(self, transformation, returns, noise, echoes, who, dual=None):
         self.mounting = Mount(transformation)
         self.returns = Returns(returns, who)
         self.noise = Noise(noise, self.returns.model, who)
         self.echoes = Echoes(echoes, who)
+        self.dual = Dual(dual, who)
+        if self.dual and not self.echoes:
+            raise ValueError(f"{who}: dual= needs echoes=, an echo model with a divergence and at least two sub-rays (a second "
+                             "return is another echo of the same beam)")
         self.mount, self.origin, self.P = self.mounting.pair, self.mounting.origin, self.mounting.P
+        self._t_H = None
 
     @property
     def keys(self):
         """the result keys of the models that are on"""
-        return tuple(k for m in (self.returns, self.noise, self.echoes) if m for k in m.KEYS)
+        return tuple(k for m in (self.returns, self.noise, self.echoes, self.dual) if m for k in m.KEYS)
 
     @property
     def needs_scan_index(self):
@@ -305,6 +348,7 @@ class Sensing:
 
     def bind(self, rays, t_H, grid=None, table=False, sub_grid=None):
         """:meth:`Echoes.bind` with the mounting's pose"""
+        self._t_H = int(t_H)
         self.echoes.bind(rays, t_H, pose=self.P, grid=grid, table=table, sub_grid=sub_grid)
         return self
 
@@ -315,20 +359,63 @@ class Sensing:
     def plan(self, out, n_rays, device):
         """``(rout, sub)`` for a scan whose result goes to ``out``: ``sub`` is what the native call renders into
         (``out_ptrs(sub)``), ``rout`` the scan's images as rendered, which :meth:`finish` works on; both are ``out`` itself
-        with nothing on.  Allocates on the current stream."""
+        with nothing on.  With a dual return the five images of ``out`` are REPLACED, in place, by the plane-0 views of fresh
+        allocations of ``2 * n_rays`` cells, and ``rout`` carries the planes to :meth:`finish`.  Allocates on the current
+        stream."""
+        if self.dual:
+            return self._plan_dual(out, n_rays, device)
         rout = self.returns.render_into(self.mounting.render_into(out, n_rays, device), n_rays, device)
         rout = self.echoes.resolve_into(self.noise.render_into(rout, n_rays, device), n_rays, device)
         return rout, self.echoes.render_into(rout, n_rays, device)
+
+    def _plan_dual(self, out, n_rays, device):
+        import torch
+        n = int(n_rays)
+        store = Dual.planes(n, device)                      # what the result holds: end points in the target's frame
+        rstore = store if self.mount is None else dict(store, endpoints=torch.empty_like(store["endpoints"]))   # as rendered
+        for k in OUT_KEYS:
+            out[k] = store[k][:n]
+        rout = dict(out)
+        if rstore is not store:
+            rout["endpoints"] = rstore["endpoints"][:n]
+        rout["_dual"] = (rstore, store)
+        return rout, self.echoes.render_into(rout, n, device)
 
     def finish(self, out, rout, sub, scan_index, scene, rays, origin, stream, label_image=True):
         """Behind the render that stands, on ``stream``: ``sub`` resolved into ``rout``, the return model, the noise model,
         the hits into the target's frame in ``out`` (``post.echo_resolve``, ``post.return_model``, ``post.noise_model``,
         ``post.points_to_frame``, each only when it is on).  ``rays``: the CENTRAL rays, ``origin``: where they start,
         ``scene``: what rendered.  Returns what the models add to the result (:attr:`keys`)."""
+        if self.dual:
+            return self._finish_dual(rout, sub, scan_index, scene, rays, origin, stream, label_image)
         seen = self.echoes.apply(sub, rout, rays, origin, stream)
         seen.update(self.returns.apply(rout, scan_index, scene, rays, stream, label_image))
         seen.update(self.noise.apply(rout, scan_index, origin, stream, label_image))
         self.mounting.to_target(rout, out, stream)
+        return seen
+
+    def _finish_dual(self, rout, sub, scan_index, scene, rays, origin, stream, label_image):
+        """:meth:`finish` with a dual return: ONE resolve into both planes, each model on plane 0 exactly as without the
+        setting and then on plane 1 with the xor-ed seed, ONE frame change over both planes.  The result's ``second``: the
+        second return's images, and under ``_planes`` the whole allocations that the packing reads."""
+        from . import post
+        rstore, store = rout["_dual"]
+        n = rout["tri"].numel()
+        second = {k: rstore[k][n:] for k in OUT_KEYS}       # plane 1, as rendered
+        seen = post.echo_resolve_dual(rays, origin, self.echoes.model, self.dual.setting, sub, rout, second, stream=stream)
+        more = dict(echo_fraction=seen.pop("echo_fraction2"))
+        seen.update(self.returns.apply(rout, scan_index, scene, rays, stream, label_image))
+        more.update(self.returns.apply(second, scan_index, scene, rays, stream, label_image, seed_xor=SECOND_SEED_XOR))
+        seen.update(self.noise.apply(rout, scan_index, origin, stream, label_image))
+        more.update(self.noise.apply(second, scan_index, origin, stream, label_image, seed_xor=SECOND_SEED_XOR))
+        if rstore is not store:
+            post.points_to_frame(rstore["endpoints"], self.mounting.T, tri=rstore["tri"], out=store["endpoints"], stream=stream)
+        H = self._t_H or 1
+        image = (H, n // H)
+        seen["second"] = dict(range=store["range"][n:].view(image), rem=store["endrem"][n:].view(image),
+                              label=store["endcolors"][n:].view(image), endpoints=store["endpoints"][n:],
+                              endpoints_scene=second["endpoints"], tri=second["tri"],
+                              _planes=dict(endpoints=store["endpoints"], rem=store["endrem"], label=store["endcolors"]), **more)
         return seen
 
     def close(self):

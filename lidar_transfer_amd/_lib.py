@@ -52,7 +52,7 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_rayset_create_grid_dev", "lt_projector_set_sector", "lt_range_projection_set_sector",
            "lt_create_rays_beams_az_dev", "lt_projector_set_beam_azimuth", "lt_range_projection_set_beam_azimuth",
            "lt_reverse_projection_beams_az_dev", "lt_return_model_dev", "lt_target_view_dev", "lt_noise_model_dev",
-           "lt_create_subrays_dev", "lt_echo_resolve_dev"]
+           "lt_create_subrays_dev", "lt_echo_resolve_dev", "lt_echo_resolve_dual_dev"]
 LT_ABI_VERSION = 10   # include/lidarhip.h: layout version of the structs mirrored below
 
 
@@ -325,6 +325,9 @@ def load():
     lib.lt_echo_resolve_dev.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(EchoModelArgs), vp, vp, vp, vp, vp, vp,
                                         vp, vp, vp, vp, vp, vp]
     lib.lt_echo_resolve_dev.restype = C.c_int
+    lib.lt_echo_resolve_dual_dev.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(EchoModelArgs), C.c_uint, vp, vp, vp,
+                                             vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.lt_echo_resolve_dual_dev.restype = C.c_int
     lib.lt_abi_version.argtypes = []
     lib.lt_tsdf_volume_stride.argtypes = []
     if lib.lt_abi_version() != LT_ABI_VERSION:  # a stale prebuilt library: its structs are laid out differently

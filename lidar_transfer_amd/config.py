@@ -48,6 +48,10 @@ A sixth is the WIDTH of its beams, :class:`EchoModel` (``SensorModel.echo_model(
   ``mode`` (``first`` | ``strongest`` | ``last``) -- every cell is rendered with ``subrays`` rays, their hits are grouped into
   echoes along the range and one echo is reported, with the blended range of what the spot covers; ``divergence`` 0 or
   ``subrays`` 1 is none.
+* ``dual_return``: a block of ``second`` (``none`` | ``first`` | ``strongest`` | ``last``), :class:`DualReturn`
+  (``SensorModel.dual_return()``) -- a SECOND echo of every cell, chosen by ``second`` among the detected echoes other than
+  the reported one, goes through the return and noise models and into the files behind the primary's points; ``none`` is
+  off; it needs an ``echo_model`` that is on.
 """
 from __future__ import annotations
 
@@ -80,6 +84,8 @@ class SensorModel:
     noise_block: Optional[dict] = None
     #: the file's ``echo_model`` block as read (a mapping), ``None`` without the key: :meth:`echo_model`
     echo_block: Optional[dict] = None
+    #: the file's ``dual_return`` block as read (a mapping), ``None`` without the key: :meth:`dual_return`
+    dual_block: Optional[dict] = None
 
     @property
     def H(self) -> int:
@@ -144,6 +150,17 @@ class SensorModel:
         ``None`` without the ``echo_model`` key, with ``divergence`` 0 or with ``subrays`` 1.  ``ValueError`` led by the
         sensor's name for a block that cannot be used."""
         return EchoModel.of(self.echo_block, f"sensor {self.name!r}")
+
+    def dual_return(self):
+        """The sensor's :class:`DualReturn` -- a SECOND echo per cell -- or ``None`` without the ``dual_return``
+        key or with ``second: none``.  ``ValueError`` led by the sensor's name for a block that cannot be used, and for one
+        that is on while the sensor's echo model is off or absent: there is no second echo of a line."""
+        who = f"sensor {self.name!r}"
+        dual = DualReturn.of(self.dual_block, who)
+        if dual is not None and self.echo_model() is None:
+            raise ValueError(f"{who}: dual_return second: {dual.second} -- a second return needs an echo_model with a "
+                             "divergence and at least two sub-rays")
+        return dual
 
     def sector(self):
         """``None`` for ``azimuth_model: full``; for ``sector`` ``(center_deg, span_deg)`` as floats: the ``W`` columns span
@@ -582,6 +599,29 @@ class EchoModel(_ModelBlock):
         return a
 
 
+class DualReturn(_ModelBlock):
+    """A TARGET sensor's dual-return mode (the sensor file's ``dual_return`` block), beside :class:`EchoModel`:
+    ``second`` names the rule that picks a SECOND echo among a cell's detected echoes other than the reported one -- ``first``
+    the earliest of the rest, ``last`` the latest, ``strongest`` the one with the largest remission sum -- or ``none``, which
+    is off and the absence of the key.  Validated by the constructor alone, else ``ValueError`` led by ``who``."""
+
+    KEY = "dual_return"
+    DEFAULTS = dict(second="none")
+    SECONDS = ("none",) + EchoModel.MODES
+
+    def __init__(self, second="none", who="dual return"):
+        if not isinstance(second, str) or second not in self.SECONDS:
+            raise ValueError(f"{who}: dual_return second must be one of {', '.join(self.SECONDS)}, not {second!r}")
+        self.__dict__.update(second=second)
+
+    @property
+    def mode(self):
+        """``second`` as ``lt_echo_resolve_dual_dev``'s ``second_mode`` (LT_ECHO_FIRST, LT_ECHO_STRONGEST, LT_ECHO_LAST)"""
+        if self.is_default:
+            raise ValueError("dual_return second: none has no second_mode")
+        return EchoModel.MODES.index(self.second)
+
+
 def _load_yaml(path_or_dict):
     if isinstance(path_or_dict, dict):
         return path_or_dict
@@ -620,11 +660,13 @@ def load_sensor(path_or_dict) -> SensorModel:
                         beam_model=str(cfg.get("beam_model", "linear")),
                         azimuth_model=str(cfg.get("azimuth_model", "full")), azimuth_center=cfg.get("azimuth_center", 0.0),
                         beam_azimuth_offsets=offsets, return_block=cfg.get("return_model"),
-                        noise_block=cfg.get("noise_model"), echo_block=cfg.get("echo_model"))
+                        noise_block=cfg.get("noise_model"), echo_block=cfg.get("echo_model"),
+                        dual_block=cfg.get("dual_return"))
     model.target_model()   # (a table, a sector or offsets that cannot be used: said at load time)
     model.return_model()   # (and a return model that cannot be)
     model.noise_model()    # (nor a noise model)
     model.echo_model()     # (nor an echo model)
+    model.dual_return()    # (nor a second return, or one without an echo model)
     return model
 
 
@@ -671,15 +713,23 @@ def refuse_source_echo_model(source):
                          "scan holds the echoes of its own sensor's beams)")
 
 
+def refuse_source_dual_return(source):
+    """And a second return: the source scan holds the returns its own sensor wrote."""
+    if getattr(source, "dual_block", None) is not None:
+        raise ValueError(f"source sensor {getattr(source, 'name', '')!r}: dual_return is for target sensors only (the source "
+                         "scan holds the returns its own sensor wrote)")
+
+
 def refuse_source_models(source):
     """everything a :class:`TargetModel`, a :class:`ReturnModel`, a :class:`NoiseModel` or an :class:`EchoModel` holds is a
-    property of the TARGET: the six refusals, the table's first"""
+    property of the TARGET, and so is a :class:`DualReturn`: the seven refusals, the table's first"""
     refuse_source_table(source)
     refuse_source_sector(source)
     refuse_source_beam_azimuth(source)
     refuse_source_return_model(source)
     refuse_source_noise_model(source)
     refuse_source_echo_model(source)
+    refuse_source_dual_return(source)
 
 
 @dataclass

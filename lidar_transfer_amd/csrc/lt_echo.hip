@@ -19,6 +19,11 @@
 // chooses among the detected; range = float32(St / c), endrem = float32(Srem / S), fraction = float32((double)c / S),
 // label and tri are rep's, end point j = float32(o[j] + h[j] * (double)range).  No detected echo, or !(dd > 0) of the
 // central ray: the miss of LT_TRACE_WRITE_MISSES.
+// k_echo_resolve_dual (a dual-return sensor) is the same body with a SECOND echo per cell: chosen by second_mode among the
+// detected echoes other than the primary -- first: the earliest of the rest, last: the latest, strongest: the largest Srem,
+// a tie to the larger c, then to the earlier --, written with the primary's expressions on its own c, St, Srem and rep into
+// a second set of outputs; fewer than two detected echoes, or !(dd > 0): the miss, and fraction2 = 0.  The primary set is
+// bit for bit k_echo_resolve's.
 #include <limits.h>
 #include <math.h>
 
@@ -93,31 +98,74 @@ struct lt_echo_walk {
   double t_first, st, sr;  // the open echo
   int c, rep;
   double ch_st, ch_sr;     // the chosen echo (ch_c == 0: none yet)
-  int ch_c, ch_rep;
+  int ch_c, ch_rep, ch_ord;  // ch_ord: its ordinal among the detected echoes (read by the dual resolve only)
   int n_det;
 };
 
-static __device__ __forceinline__ void lt_echo_close(lt_echo_walk& w, int min_subrays, unsigned mode) {
+// SKIP: the detected echo of ordinal `skip` is passed over (the second walk of the dual resolve, which chooses among the rest)
+template <bool SKIP>
+static __device__ __forceinline__ void lt_echo_close(lt_echo_walk& w, int min_subrays, unsigned mode, int skip) {
   if (w.c < min_subrays || w.c == 0) return;
+  const int ord = w.n_det;
   ++w.n_det;
+  if (SKIP && ord == skip) return;
   bool take = w.ch_c == 0;
   if (mode == LT_ECHO_LAST) take = true;
   else if (mode == LT_ECHO_STRONGEST) take = take || w.sr > w.ch_sr || (w.sr == w.ch_sr && w.c > w.ch_c);
-  if (take) { w.ch_st = w.st; w.ch_sr = w.sr; w.ch_c = w.c; w.ch_rep = w.rep; }
+  if (take) { w.ch_st = w.st; w.ch_sr = w.sr; w.ch_c = w.c; w.ch_rep = w.rep; w.ch_ord = ord; }
 }
+
+// the fully unrolled walk over the sorted slots: steps 3 - 6 of the contract, `mode` choosing among the detected echoes
+// (without the one of ordinal `skip` when SKIP)
+template <bool SKIP>
+static __device__ __forceinline__ void lt_echo_walk_slots(lt_echo_walk& w, const lt_echo_hit (&s)[LT_ECHO_MAX_SUBRAYS],
+                                                          double separation, int min_subrays, unsigned mode, int skip) {
+  w.t_first = 0.0; w.st = 0.0; w.sr = 0.0; w.c = 0; w.rep = 0;
+  w.ch_st = 0.0; w.ch_sr = 0.0; w.ch_c = 0; w.ch_rep = 0; w.ch_ord = -1; w.n_det = 0;
+#pragma unroll
+  for (int j = 0; j < LT_ECHO_MAX_SUBRAYS; ++j) {
+    if (s[j].key != ~0ull) {
+      const int k = (int)(s[j].key & 7ull);
+      const double t = (double)__uint_as_float((unsigned)(s[j].key >> 3));
+      const double r = (double)s[j].rem;
+      if (w.c == 0 || t - w.t_first > separation) {
+        lt_echo_close<SKIP>(w, min_subrays, mode, skip);
+        w.t_first = t; w.st = t; w.sr = r; w.c = 1; w.rep = k;
+      } else {
+        w.st = w.st + t; w.sr = w.sr + r; w.c += 1; w.rep = k < w.rep ? k : w.rep;
+      }
+    }
+  }
+  lt_echo_close<SKIP>(w, min_subrays, mode, skip);
+}
+
+// the second return's outputs and its rule (the dual resolve only)
+struct lt_echo_second {
+  float* endpoints;
+  int* endcolors;
+  float* range;
+  float* endrem;
+  int* tri;
+  float* fraction;
+  unsigned mode;
+};
 
 // One thread per cell, 256-thread workgroups, no LDS, no atomics.  The S <= 8 candidates stay in registers: fixed
 // LT_ECHO_MAX_SUBRAYS slots, a fully unrolled 19-comparator sorting network on the packed keys with the remission carried
 // along, then a fully unrolled walk; nothing is indexed at run time (that would go to scratch).  The 2S (or 3S) loads of
 // the sub-images do not depend on one another and are issued together; the label and the triangle of the chosen echo's
 // representative are two dependent loads behind the walk; every load comes ahead of the cell's first store.
-__global__ __launch_bounds__(256) void k_echo_resolve(const lt_echo_args A, const float* __restrict__ rays,
-                                                      const float* __restrict__ sub_range, const int* __restrict__ sub_label,
-                                                      const float* __restrict__ sub_rem, const int* __restrict__ sub_tri,
-                                                      float* __restrict__ endpoints, int* __restrict__ endcolors,
-                                                      float* __restrict__ range, float* __restrict__ endrem,
-                                                      int* __restrict__ tri, unsigned char* __restrict__ n_echoes,
-                                                      float* __restrict__ fraction) {
+// DUAL: a second walk over the same sorted slots chooses the second echo among the detected ones other than the primary,
+// which it passes over by its ordinal; the primary's sums are four registers by then and the slots are still live, so the
+// second walk costs no register the first did not.  Both representatives' gathers are issued together behind the walks.
+template <bool DUAL>
+static __device__ __forceinline__ void lt_echo_body(const lt_echo_args& A, const lt_echo_second& B, const float* __restrict__ rays,
+                                                    const float* __restrict__ sub_range, const int* __restrict__ sub_label,
+                                                    const float* __restrict__ sub_rem, const int* __restrict__ sub_tri,
+                                                    float* __restrict__ endpoints, int* __restrict__ endcolors,
+                                                    float* __restrict__ range, float* __restrict__ endrem,
+                                                    int* __restrict__ tri, unsigned char* __restrict__ n_echoes,
+                                                    float* __restrict__ fraction) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= A.n) return;
   const double x = (double)rays[3 * (size_t)i], y = (double)rays[3 * (size_t)i + 1], z = (double)rays[3 * (size_t)i + 2];
@@ -146,33 +194,37 @@ __global__ __launch_bounds__(256) void k_echo_resolve(const lt_echo_args A, cons
   lt_echo_cx(s[1], s[2]); lt_echo_cx(s[3], s[4]); lt_echo_cx(s[5], s[6]);
 
   lt_echo_walk w;
-  w.t_first = 0.0; w.st = 0.0; w.sr = 0.0; w.c = 0; w.rep = 0;
-  w.ch_st = 0.0; w.ch_sr = 0.0; w.ch_c = 0; w.ch_rep = 0; w.n_det = 0;
-#pragma unroll
-  for (int j = 0; j < LT_ECHO_MAX_SUBRAYS; ++j) {
-    if (s[j].key != ~0ull) {
-      const int k = (int)(s[j].key & 7ull);
-      const double t = (double)__uint_as_float((unsigned)(s[j].key >> 3));
-      const double r = (double)s[j].rem;
-      if (w.c == 0 || t - w.t_first > A.separation) {
-        lt_echo_close(w, A.min_subrays, A.mode);
-        w.t_first = t; w.st = t; w.sr = r; w.c = 1; w.rep = k;
-      } else {
-        w.st = w.st + t; w.sr = w.sr + r; w.c += 1; w.rep = k < w.rep ? k : w.rep;
-      }
-    }
-  }
-  lt_echo_close(w, A.min_subrays, A.mode);
+  lt_echo_walk_slots<false>(w, s, A.separation, A.min_subrays, A.mode, 0);
 
   const double h2 = x * x + y * y;
   const double dd = h2 + z * z;
   const bool hit = w.ch_c > 0 && dd > 0.0;
+  double st2 = 0.0, sr2 = 0.0;
+  int c2 = 0, rep2 = 0;
+  if constexpr (DUAL) {
+    if (w.n_det >= 2) {   // (n_det < 2: no second echo, and no second walk)
+      lt_echo_walk w2;
+      lt_echo_walk_slots<true>(w2, s, A.separation, A.min_subrays, B.mode, w.ch_ord);
+      st2 = w2.ch_st; sr2 = w2.ch_sr; c2 = w2.ch_c; rep2 = w2.ch_rep;
+    }
+  }
+  const bool hit2 = DUAL && c2 > 0 && dd > 0.0;
   float px = 0.f, py = 0.f, pz = 0.f, rf = 0.f, er = 0.f, fr = 0.f;
-  int lab = 0, tr = -1;
+  float qx = 0.f, qy = 0.f, qz = 0.f, rf2 = 0.f, er2 = 0.f, fr2 = 0.f;
+  int lab = 0, tr = -1, lab2 = 0, tr2 = -1;
   if (hit) {
     const size_t e = (size_t)w.ch_rep * (size_t)A.n + (size_t)i;
     tr = sub_tri[e];
     if (sub_label) lab = sub_label[e];
+  }
+  if constexpr (DUAL) {
+    if (hit2) {
+      const size_t e = (size_t)rep2 * (size_t)A.n + (size_t)i;
+      tr2 = sub_tri[e];
+      if (sub_label) lab2 = sub_label[e];
+    }
+  }
+  if (hit) {
     const double nn = sqrt(dd);
     rf = (float)(w.ch_st / (double)w.ch_c);
     er = (float)(w.ch_sr / (double)A.S);
@@ -180,6 +232,16 @@ __global__ __launch_bounds__(256) void k_echo_resolve(const lt_echo_args A, cons
     px = (float)(A.ox + (x / nn) * (double)rf);
     py = (float)(A.oy + (y / nn) * (double)rf);
     pz = (float)(A.oz + (z / nn) * (double)rf);
+    if constexpr (DUAL) {
+      if (hit2) {
+        rf2 = (float)(st2 / (double)c2);
+        er2 = (float)(sr2 / (double)A.S);
+        fr2 = (float)((double)c2 / (double)A.S);
+        qx = (float)(A.ox + (x / nn) * (double)rf2);
+        qy = (float)(A.oy + (y / nn) * (double)rf2);
+        qz = (float)(A.oz + (z / nn) * (double)rf2);
+      }
+    }
   }
   if (endpoints) { endpoints[3 * (size_t)i] = px; endpoints[3 * (size_t)i + 1] = py; endpoints[3 * (size_t)i + 2] = pz; }
   if (endcolors) endcolors[i] = lab;
@@ -188,6 +250,36 @@ __global__ __launch_bounds__(256) void k_echo_resolve(const lt_echo_args A, cons
   tri[i] = tr;
   if (n_echoes) n_echoes[i] = (unsigned char)w.n_det;
   if (fraction) fraction[i] = fr;
+  if constexpr (DUAL) {
+    if (B.endpoints) { B.endpoints[3 * (size_t)i] = qx; B.endpoints[3 * (size_t)i + 1] = qy; B.endpoints[3 * (size_t)i + 2] = qz; }
+    if (B.endcolors) B.endcolors[i] = lab2;
+    B.range[i] = rf2;
+    if (B.endrem) B.endrem[i] = er2;
+    B.tri[i] = tr2;
+    if (B.fraction) B.fraction[i] = fr2;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_echo_resolve(const lt_echo_args A, const float* __restrict__ rays,
+                                                      const float* __restrict__ sub_range, const int* __restrict__ sub_label,
+                                                      const float* __restrict__ sub_rem, const int* __restrict__ sub_tri,
+                                                      float* __restrict__ endpoints, int* __restrict__ endcolors,
+                                                      float* __restrict__ range, float* __restrict__ endrem,
+                                                      int* __restrict__ tri, unsigned char* __restrict__ n_echoes,
+                                                      float* __restrict__ fraction) {
+  lt_echo_body<false>(A, lt_echo_second{}, rays, sub_range, sub_label, sub_rem, sub_tri, endpoints, endcolors, range, endrem, tri,
+                      n_echoes, fraction);
+}
+
+__global__ __launch_bounds__(256) void k_echo_resolve_dual(const lt_echo_args A, const lt_echo_second B,
+                                                           const float* __restrict__ rays, const float* __restrict__ sub_range,
+                                                           const int* __restrict__ sub_label, const float* __restrict__ sub_rem,
+                                                           const int* __restrict__ sub_tri, float* __restrict__ endpoints,
+                                                           int* __restrict__ endcolors, float* __restrict__ range,
+                                                           float* __restrict__ endrem, int* __restrict__ tri,
+                                                           unsigned char* __restrict__ n_echoes, float* __restrict__ fraction) {
+  lt_echo_body<true>(A, B, rays, sub_range, sub_label, sub_rem, sub_tri, endpoints, endcolors, range, endrem, tri, n_echoes,
+                     fraction);
 }
 
 // NULL when the model can be used, else what is wrong with it (written so that a NaN fails)
@@ -227,38 +319,79 @@ extern "C" int lt_create_subrays_dev(const float* rays, int n, const lt_echo_mod
   return LT_OK;
 }
 
-extern "C" int lt_echo_resolve_dev(const float* rays, const float* origin, int n, const lt_echo_model* model,
-                                   const float* sub_range, const int* sub_label, const float* sub_rem, const int* sub_tri,
-                                   float* endpoints, int* endcolors, float* range, float* endrem, int* tri,
-                                   unsigned char* n_echoes, float* fraction, void* stream) {
+// the checks the two resolve entries share, with `who` leading the message; LT_OK, or the error that was set
+static int lt_echo_resolve_check(const char* who, const float* rays, const float* origin, int n, const lt_echo_model* model,
+                                 const float* sub_range, const int* sub_tri, const float* range, const int* tri) {
   if (!origin || !model || n < 0 || (n > 0 && (!rays || !sub_range || !sub_tri || !range || !tri))) {
-    lt_set_error("lt_echo_resolve_dev: invalid argument (an origin, a model, n >= 0 = %d; rays, sub_range, sub_tri, range and "
-                 "tri are mandatory)", n);
+    lt_set_error("%s: invalid argument (an origin, a model, n >= 0 = %d; rays, sub_range, sub_tri, range and "
+                 "tri are mandatory)", who, n);
     return LT_ERR_INVALID_ARG;
   }
   if (!(origin[0] - origin[0] == 0.f && origin[1] - origin[1] == 0.f && origin[2] - origin[2] == 0.f)) {
-    lt_set_error("lt_echo_resolve_dev: invalid origin (three finite numbers; %g %g %g)", (double)origin[0], (double)origin[1],
+    lt_set_error("%s: invalid origin (three finite numbers; %g %g %g)", who, (double)origin[0], (double)origin[1],
                  (double)origin[2]);
     return LT_ERR_INVALID_ARG;
   }
   const char* why = lt_echo_model_problem(model);
   if (why) {
-    lt_set_error("lt_echo_resolve_dev: invalid model: %s (n_subrays=%d min_subrays=%d mode=%u separation=%g)", why,
+    lt_set_error("%s: invalid model: %s (n_subrays=%d min_subrays=%d mode=%u separation=%g)", who, why,
                  model->n_subrays, model->min_subrays, model->mode, model->separation);
     return LT_ERR_INVALID_ARG;
   }
   if ((long long)n * model->n_subrays > (long long)INT_MAX) {
-    lt_set_error("lt_echo_resolve_dev: invalid argument (n_subrays * n = %d * %d does not fit an int)", model->n_subrays, n);
+    lt_set_error("%s: invalid argument (n_subrays * n = %d * %d does not fit an int)", who, model->n_subrays, n);
     return LT_ERR_INVALID_ARG;
   }
-  if (n == 0) return LT_OK;
+  return LT_OK;
+}
+
+static lt_echo_args lt_echo_args_of(const float* origin, int n, const lt_echo_model* model) {
   lt_echo_args A;
   A.separation = model->separation;
   A.ox = (double)origin[0]; A.oy = (double)origin[1]; A.oz = (double)origin[2];
   A.S = model->n_subrays; A.min_subrays = model->min_subrays; A.n = n;
   A.mode = model->mode;
+  return A;
+}
+
+extern "C" int lt_echo_resolve_dev(const float* rays, const float* origin, int n, const lt_echo_model* model,
+                                   const float* sub_range, const int* sub_label, const float* sub_rem, const int* sub_tri,
+                                   float* endpoints, int* endcolors, float* range, float* endrem, int* tri,
+                                   unsigned char* n_echoes, float* fraction, void* stream) {
+  const int rc = lt_echo_resolve_check("lt_echo_resolve_dev", rays, origin, n, model, sub_range, sub_tri, range, tri);
+  if (rc != LT_OK) return rc;
+  if (n == 0) return LT_OK;
+  const lt_echo_args A = lt_echo_args_of(origin, n, model);
   hipLaunchKernelGGL(k_echo_resolve, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, A, rays, sub_range, sub_label,
                      sub_rem, sub_tri, endpoints, endcolors, range, endrem, tri, n_echoes, fraction);
+  LT_HIP(hipGetLastError());
+  return LT_OK;
+}
+
+extern "C" int lt_echo_resolve_dual_dev(const float* rays, const float* origin, int n, const lt_echo_model* model,
+                                        unsigned second_mode, const float* sub_range, const int* sub_label,
+                                        const float* sub_rem, const int* sub_tri, float* endpoints, int* endcolors,
+                                        float* range, float* endrem, int* tri, unsigned char* n_echoes, float* fraction,
+                                        float* endpoints2, int* endcolors2, float* range2, float* endrem2, int* tri2,
+                                        float* fraction2, void* stream) {
+  const int rc = lt_echo_resolve_check("lt_echo_resolve_dual_dev", rays, origin, n, model, sub_range, sub_tri, range, tri);
+  if (rc != LT_OK) return rc;
+  if (n > 0 && (!range2 || !tri2)) {
+    lt_set_error("lt_echo_resolve_dual_dev: invalid argument (range2 and tri2 are mandatory)");
+    return LT_ERR_INVALID_ARG;
+  }
+  if (second_mode != LT_ECHO_FIRST && second_mode != LT_ECHO_STRONGEST && second_mode != LT_ECHO_LAST) {
+    lt_set_error("lt_echo_resolve_dual_dev: invalid second_mode %u (LT_ECHO_FIRST, LT_ECHO_STRONGEST or LT_ECHO_LAST)",
+                 second_mode);
+    return LT_ERR_INVALID_ARG;
+  }
+  if (n == 0) return LT_OK;
+  const lt_echo_args A = lt_echo_args_of(origin, n, model);
+  lt_echo_second B;
+  B.endpoints = endpoints2; B.endcolors = endcolors2; B.range = range2; B.endrem = endrem2; B.tri = tri2;
+  B.fraction = fraction2; B.mode = second_mode;
+  hipLaunchKernelGGL(k_echo_resolve_dual, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, A, B, rays, sub_range,
+                     sub_label, sub_rem, sub_tri, endpoints, endcolors, range, endrem, tri, n_echoes, fraction);
   LT_HIP(hipGetLastError());
   return LT_OK;
 }

@@ -336,11 +336,16 @@ class FusionScanPipeline:
     scratch images and resolves them into the scan on its stream, ahead of the return and noise models; a result carries
     ``n_echoes`` and ``echo_fraction`` [n] as well (``post.echo_resolve``).  No ``scan_index`` is needed for it.
     ``echo_grid``: the sub-ray set's bin grid, for speed alone (``None``: ``grid``'s azimuth bins and ``H`` elevation rows; for
-    a beam table ``_chain.Echoes.grid_of(grid, H, table=True)``, the image's rule, is the faster one)."""
+    a beam table ``_chain.Echoes.grid_of(grid, H, table=True)``, the image's rule, is the faster one).
+
+    ``dual``: the target sensor's :class:`~lidar_transfer_amd.config.DualReturn` (``SensorModel.dual_return()``; ``None`` or
+    ``second: none``: nothing changes; it needs ``echoes``).  A chain's resolve then writes two returns per cell; the
+    primary's images are those without the setting, bit for bit, as plane-0 views of two-plane allocations (a caller's ``out``
+    has its five images replaced by them); a result carries the second return under ``second``."""
 
     def __init__(self, vol_bnds, voxel_size, fov_up, fov_down, rays, H, chains=3, device=None, merge=True,
                  label_image=False, source_hw=None, beam_angles=None, fixed_volume=True, transformation=None, grid=None,
-                 returns=None, noise=None, echoes=None, echo_grid=None):
+                 returns=None, noise=None, echoes=None, echo_grid=None, dual=None):
         import queue
         import threading
         import weakref
@@ -356,10 +361,10 @@ class FusionScanPipeline:
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
         # what stands between the render and the result (and the only place that knows its order); shared by the chains
-        s = self._sensing = _chain.Sensing(transformation, returns, noise, echoes, "FusionScanPipeline")
+        s = self._sensing = _chain.Sensing(transformation, returns, noise, echoes, "FusionScanPipeline", dual)
         self._mounting, self._returns, self._noise, self._echoes = s.mounting, s.returns, s.noise, s.echoes
         self.mount, self.origin = s.mount, s.origin
-        self.returns, self.noise, self.echoes = s.returns.model, s.noise.model, s.echoes.model
+        self.returns, self.noise, self.echoes, self.dual = s.returns.model, s.noise.model, s.echoes.model, s.dual.setting
         if self._echoes and not label_image:
             raise ValueError("FusionScanPipeline: an echo model resolves the label image (label_image=True), not colours")
         self.rayset = RaySet(rays, H, pose=s.P, grid=grid)  # one read-only ray set for all chains
@@ -487,7 +492,7 @@ class FusionScanPipeline:
             sensor_t = (a["H"], self.n_rays // a["H"], self._src_fov[0], self._src_fov[1])
             dd = DeviceDeform(sensor_s, sensor_t, None, a["voxel_size"], beam_angles=self._beam_angles, device=self.device.index,
                               merge=a["merge"], mesh_volume=False, rayset=self.rayset, mm_state=self._mm_state,
-                              transformation=self.mount, returns=self.returns, noise=self.noise, echoes=self._echoes)
+                              transformation=self.mount, returns=self.returns, noise=self.noise, echoes=self._echoes, dual=self.dual)
             ch["deform"] = dd
         got = dd.mergemesh(clouds, origin, pack=False, out=out, seq=seq, scan_index=scan_index)
         more = {k: got[k] for k in ("vol_dim", "vol_origin", "vol_bnds_after") + self._sensing.keys}
@@ -608,7 +613,7 @@ class FusionScanPipeline:
         # the images were allocated on the chain's stream: tell the caching allocator that the caller's stream uses them,
         # so that freeing them early cannot hand their memory back to the chain while the caller still reads it
         cur = self._torch.cuda.current_stream(self.device)
-        for v in res.values():
+        for v in list(res.values()) + list((res.get("second") or {}).values()):
             if isinstance(v, self._torch.Tensor) and v.is_cuda:
                 v.record_stream(cur)
         return res

@@ -113,7 +113,7 @@ def _check_rays(rays, n, dev, message):
         raise ValueError(message)
 
 
-def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label_image=True, stream=None):
+def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label_image=True, stream=None, seed_xor=0):
     """The target sensor's return model (``lt_return_model_dev``) on a rendered scan, in place and asynchronous
     on ``stream`` (default the current one): a return outside the range gate, seen beyond ``max_incidence`` or dropped at
     random (``hash(seed, scan, cell)``) becomes the miss the render writes -- end point (0, 0, 0), label 0, remission 0,
@@ -125,7 +125,8 @@ def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label
     ``label_image``: whether ``endcolors`` is the [n] label image or [n, 3].  ``incidence`` / ``drop``: ``True`` -- a fresh
     [n] float32 / uint8 tensor, a tensor -- that one, ``None`` -- not wanted.  Returns ``dict(incidence=..., drop=...)``:
     the cosine of every standing return (-1 elsewhere) and every cell's code (0 stands, 1 no hit, 2 too near, 3 too far,
-    4 incidence, 5 random)."""
+    4 incidence, 5 random).  ``seed_xor`` (uint32, default 0: the model's own seed) is xor-ed into the model's seed for this
+    call: a second return of the same cells draws for itself."""
     import torch
 
     from .config import ReturnModel
@@ -141,6 +142,8 @@ def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label
     extra, more = _extra_outputs((("incidence", incidence, torch.float32), ("drop", drop, torch.uint8)), n, dev)
     st = torch.cuda.current_stream(dev) if stream is None else stream
     args = model.args()
+    if seed_xor:
+        args.seed = (args.seed ^ int(seed_xor)) & 0xFFFFFFFF
     with torch.cuda.device(dev):
         _lib.check(_lib.load().lt_return_model_dev(
             scene._h, rays.data_ptr(), n, C.byref(args), int(scan) & 0xFFFFFFFF, ptr["endpoints"], ptr["endcolors"], ptr["range"],
@@ -149,7 +152,8 @@ def return_model(scene, rays, model, scan, out, incidence=True, drop=True, label
     return extra
 
 
-def noise_model(origin, model, scan, out, gate=None, range_error=True, state=True, label_image=True, stream=None):
+def noise_model(origin, model, scan, out, gate=None, range_error=True, state=True, label_image=True, stream=None,
+                seed_xor=0):
     """The target sensor's noise model (``lt_noise_model_dev``) on a rendered scan, in place and asynchronous on
     ``stream`` (default the current one).  Per return (``tri >= 0`` and ``range > 0``): the range is jittered by ``(range_sigma
     + range_sigma_rel * range) * z`` and put on the ``range_resolution`` grid, the end point is scaled about ``origin`` to
@@ -163,7 +167,8 @@ def noise_model(origin, model, scan, out, gate=None, range_error=True, state=Tru
     the sensor's :class:`~lidar_transfer_amd.config.ReturnModel` or ``None``; ``label_image``: whether ``endcolors`` is the
     [n] label image or [n, 3].  ``range_error`` / ``state``: ``True`` -- a fresh [n] float32 / uint8 tensor, a tensor -- that
     one, ``None`` -- not wanted.  Returns ``dict(range_error=..., noise_state=...)``: ``float32(new - old)`` of every noised
-    return (0 elsewhere) and every cell's state (0 untouched, 1 noised, 2 lost)."""
+    return (0 elsewhere) and every cell's state (0 untouched, 1 noised, 2 lost).  ``seed_xor``: as for
+    :func:`return_model`."""
     import torch
 
     from .config import NoiseModel, ReturnModel
@@ -180,6 +185,8 @@ def noise_model(origin, model, scan, out, gate=None, range_error=True, state=Tru
     extra, more = _extra_outputs((("range_error", range_error, torch.float32), ("noise_state", state, torch.uint8)), n, dev)
     st = torch.cuda.current_stream(dev) if stream is None else stream
     args = model.args(gate)
+    if seed_xor:
+        args.seed = (args.seed ^ int(seed_xor)) & 0xFFFFFFFF
     o = (C.c_float * 3)(*[float(x) for x in origin])
     with torch.cuda.device(dev):
         _lib.check(_lib.load().lt_noise_model_dev(
@@ -253,6 +260,50 @@ def echo_resolve(rays, origin, model, sub, out, n_echoes=True, fraction=True, st
         _lib.check(_lib.load().lt_echo_resolve_dev(
             rays.data_ptr(), org, n, C.byref(args), s["range"], s["endcolors"], s["endrem"], s["tri"], o["endpoints"],
             o["endcolors"], o["range"], o["endrem"], o["tri"], *more, C.c_void_p(st.cuda_stream)), "lt_echo_resolve_dev")
+    return extra
+
+
+def echo_resolve_dual(rays, origin, model, second, sub, out, out2, n_echoes=True, fraction=True, fraction2=True, stream=None):
+    """The dual-return resolve (``lt_echo_resolve_dual_dev``): :func:`echo_resolve` into ``out``, bit for bit, and
+    in the same launch a SECOND echo of every cell into ``out2``.  ``second``: a
+    :class:`~lidar_transfer_amd.config.DualReturn` that is on; its rule picks among the cell's detected echoes other than the
+    primary -- ``first`` the earliest of the rest, ``last`` the latest, ``strongest`` the largest remission sum (a tie to
+    the larger count, then to the earlier).  The second echo's range, remission, label, triangle and end point (on the
+    CENTRAL ray) are the primary's expressions on its own sub-hits; a cell with fewer than two detected echoes gets the miss
+    the render writes.  ``out2``: images under ``out``'s keys (``range`` and ``tri`` are needed, the others may be absent or
+    ``None``), overlapping nothing of ``out`` or ``sub``.  ``fraction2``: as ``fraction``, for the second echo.  Returns
+    ``dict(n_echoes=..., echo_fraction=..., echo_fraction2=...)``."""
+    import torch
+
+    from .config import DualReturn, EchoModel
+    if not isinstance(model, EchoModel) or model.is_default:
+        raise ValueError("model: a lidar_transfer_amd.config.EchoModel with a divergence and at least two sub-rays")
+    if not isinstance(second, DualReturn) or second.is_default:
+        raise ValueError("second: a lidar_transfer_amd.config.DualReturn whose `second` is first, strongest or last")
+    tri, rng = out.get("tri"), out.get("range")
+    if tri is None or rng is None:
+        raise ValueError("out: the scan's `tri` and `range` images are needed")
+    if out2.get("tri") is None or out2.get("range") is None:
+        raise ValueError("out2: the second return's `tri` and `range` images are needed")
+    if sub.get("tri") is None or sub.get("range") is None:
+        raise ValueError("sub: the sub-render's `tri` and `range` images are needed")
+    n = tri.numel()
+    S = model.subrays
+    dev = tri.device
+    o = _image_ptrs(out, n, dev)
+    o2 = _image_ptrs(out2, n, dev, "out2")
+    s = _image_ptrs(sub, S * n, dev, "sub", endpoints=False)
+    _check_rays(rays, n, dev, "rays: contiguous float32 CUDA tensor [n, 3], the central rays, on the device of `tri`")
+    extra, more = _extra_outputs((("n_echoes", n_echoes, torch.uint8), ("echo_fraction", fraction, torch.float32),
+                                  ("echo_fraction2", fraction2, torch.float32)), n, dev)
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    args = model.args()
+    org = (C.c_float * 3)(*[float(x) for x in origin])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lt_echo_resolve_dual_dev(
+            rays.data_ptr(), org, n, C.byref(args), second.mode, s["range"], s["endcolors"], s["endrem"], s["tri"],
+            o["endpoints"], o["endcolors"], o["range"], o["endrem"], o["tri"], more[0], more[1], o2["endpoints"], o2["endcolors"],
+            o2["range"], o2["endrem"], o2["tri"], more[2], C.c_void_p(st.cuda_stream)), "lt_echo_resolve_dual_dev")
     return extra
 
 

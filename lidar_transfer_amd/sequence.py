@@ -195,7 +195,12 @@ class SequenceTransfer:
     written files see the resolved scan.  The cells per number of detected echoes and the reported share of the beam are
     summed on the device and read once at the end of :meth:`run` (``summary["echo_totals"]``, three numbers in
     :data:`ECHO_COUNTS`' order, and ``summary["echo_fraction_mean"]`` over the cells with an echo).  ``cp`` renders no ray:
-    with such a target it raises ``ValueError``; so does a source sensor with the key."""
+    with such a target it raises ``ValueError``; so does a source sensor with the key.
+    A target ``SensorModel`` with a ``dual_return`` block that is on (kept as ``dual``; ``None``: none) has every chain resolve
+    a SECOND echo per cell: each file holds the primary's points, as without the block, followed by the second
+    returns'; a record's ``n_points`` is the file's count; evaluation sees the primary alone.  The second returns that stand
+    behind the models are summed on the device and read once at the end of :meth:`run` (``summary["second_returns"]``).
+    ``cp`` renders no ray: with such a target it raises ``ValueError``; so does a source sensor with the key."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -214,7 +219,7 @@ class SequenceTransfer:
         self.beam_table, self.sector, self.beam_azimuth = m.beam_table, m.sector, m.beam_azimuth
         self.beam_model = "linear" if m.beam_table is None else "table"
         self.azimuth_model = "full" if m.sector is None else "sector"
-        for name in ("returns", "noise", "echoes"):
+        for name in ("returns", "noise", "echoes", "dual"):
             key, _, what, why = CP_REFUSALS[name]
             setattr(self, name, getattr(target_sensor, key, lambda: None)())
             if getattr(self, name) is not None and self.adaption == "cp":
@@ -275,6 +280,8 @@ class SequenceTransfer:
             every = dict(beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
                          transformation=self.mount, t_beam_table=m.beam_table, t_sector=m.sector, t_beam_azimuth=m.beam_azimuth,
                          returns=self.returns, noise=self.noise)
+            if self.adaption != "cp":
+                every["dual"] = self.dual
             for c in range(self.chains):
                 if self.adaption == "cp":
                     dd = DeviceDeform(self.source_sensor, self.target_sensor, None, **every)
@@ -306,7 +313,7 @@ class SequenceTransfer:
 
     def _tallies(self):
         """one chain's accumulators: a :class:`_Tally` per model that is on"""
-        n = dict(returns=len(RETURN_CODES), noise=len(NOISE_STATES), echoes=len(ECHO_COUNTS))
+        n = dict(returns=len(RETURN_CODES), noise=len(NOISE_STATES), echoes=len(ECHO_COUNTS), dual=2)
         return {name: _Tally(n[name], self.device) for name in n if getattr(self, name) is not None}
 
     def _read_tallies(self, name):
@@ -352,6 +359,8 @@ class SequenceTransfer:
                     tally["noise"].add(out["noise_state"], torch.linalg.vector_norm(out["range_error"], dtype=torch.float64) ** 2)
                 if "echoes" in tally:                # cells per number of echoes (two stand for several), the reported shares
                     tally["echoes"].add(out["n_echoes"].clamp(max=2), out["echo_fraction"].sum(dtype=torch.float64))
+                if "dual" in tally:                  # second returns that stand after the models (code 1) and those that do not
+                    tally["dual"].add((out["second"]["tri"].reshape(-1) >= 0).to(torch.uint8))
                 if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
                     scan = ch["ev"].target_view if self.evaluate_mode == "target" else ch["ev"].source_scan
                     src = scan(*job["raw"], stream=st)
@@ -468,10 +477,11 @@ class SequenceTransfer:
             totals, _ = self._read_tallies("returns")
             noise_totals, sq_sum = self._read_tallies("noise")
             echo_totals, share = self._read_tallies("echoes")
+            second, _ = self._read_tallies("dual")
             rms = float(np.sqrt(sq_sum / noise_totals[1])) if noise_totals and noise_totals[1] else None
             echo_mean = share / (echo_totals[1] + echo_totals[2]) if echo_totals and echo_totals[1] + echo_totals[2] else None
             self.summary = dict(return_totals=totals, noise_totals=noise_totals, range_error_rms=rms, echo_totals=echo_totals,
-                                echo_fraction_mean=echo_mean, scans=n_done,
+                                echo_fraction_mean=echo_mean, second_returns=second[1] if second else None, scans=n_done,
                                 chains=self.chains, adaption=self.adaption, fusion=self.fusion,
                                 mounted=self.mounted, beam_model=self.beam_model, azimuth_model=self.azimuth_model,
                                 beam_azimuth=self.beam_azimuth is not None,
