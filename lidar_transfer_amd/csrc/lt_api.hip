@@ -1,5 +1,6 @@
 // lt_api.hip -- C-ABI entry points of liblidarhip.so (declared in include/lidarhip.h).
 #include "lt_internal.h"
+#include "lt_layouts.h"
 #include <cpuid.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -29,75 +30,49 @@ extern "C" const char* lt_last_error(void) { return g_err; }
 extern "C" const char* lt_version(void) { return "lidarhip 0.1 (gfx950)"; }
 extern "C" int lt_abi_version(void) { return LT_ABI_VERSION; }
 
-template <typename T>
-static int dev_alloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  LT_HIP(hipMalloc((void**)p, count * sizeof(T)));
-  return LT_OK;
-}
-
 static void ws_free(lt_scene* s) {
-  for (int k = 0; k < 2; ++k) {
-    if (s->keys[k]) (void)hipFree(s->keys[k]);
-    if (s->vals[k]) (void)hipFree(s->vals[k]);
-    s->keys[k] = s->vals[k] = nullptr;
+  void** ps[] = {(void**)&s->keys[0], (void**)&s->keys[1], (void**)&s->vals[0], (void**)&s->vals[1], (void**)&s->hist,
+                 (void**)&s->tris, (void**)&s->seg, (void**)&s->nodes, (void**)&s->nodes4};
+  for (void** p : ps) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
   }
-  if (s->hist) (void)hipFree(s->hist);
-  if (s->tris) (void)hipFree(s->tris);
-  if (s->seg) (void)hipFree(s->seg);
-  if (s->nodes) (void)hipFree(s->nodes);
-  if (s->nodes4) (void)hipFree(s->nodes4);
-  s->nodes4 = nullptr;
-  s->hist = nullptr; s->tris = nullptr; s->seg = nullptr; s->nodes = nullptr;
   s->cap_faces = 0;
 }
 
+// the workspace of a build: one group, sized for cap_faces
 int lt_scene_reserve(lt_scene* s, int n_faces) {
   if (n_faces <= s->cap_faces) return LT_OK;
   LT_HIP(hipSetDevice(s->device));
-  if (s->last_stream || s->cap_faces) LT_HIP(hipDeviceSynchronize());
-  ws_free(s);
-  size_t cap = (size_t)n_faces + (size_t)n_faces / 4 + 1024;  // headroom: meshes of a sequence vary in size
+  size_t cap = lt_headroom((size_t)n_faces);  // meshes of a sequence vary in size
   if (cap > (size_t)LT_MAX_FACES) cap = LT_MAX_FACES;
   size_t np = 1;
   while (np < cap) np <<= 1;
   const size_t nb = (cap + LT_SORT_TILE - 1) / LT_SORT_TILE;
-  for (int k = 0; k < 2; ++k) {
-    LT_CHECK(dev_alloc(&s->keys[k], cap));
-    LT_CHECK(dev_alloc(&s->vals[k], cap));
-  }
-  LT_CHECK(dev_alloc(&s->hist, 1024 * nb + 1024));  // LT_RD digits x tiles + digit totals
-  LT_CHECK(dev_alloc(&s->tris, 3 * cap));
-  LT_CHECK(dev_alloc(&s->seg, 4 * np));
-  LT_CHECK(dev_alloc(&s->nodes, 4 * cap));
-  LT_CHECK(dev_alloc(&s->nodes4, 8 * cap));
-  s->cap_faces = (int)cap;
-  return LT_OK;
+  const lt_dev_array ws[] = {
+      {(void**)&s->keys[0], cap * sizeof(uint32_t)},  {(void**)&s->vals[0], cap * sizeof(uint32_t)},
+      {(void**)&s->keys[1], cap * sizeof(uint32_t)},  {(void**)&s->vals[1], cap * sizeof(uint32_t)},
+      {(void**)&s->hist, (1024 * nb + 1024) * sizeof(uint32_t)},  // LT_RD digits x tiles + digit totals
+      {(void**)&s->tris, 3 * cap * sizeof(float4)},   {(void**)&s->seg, 4 * np * sizeof(float4)},
+      {(void**)&s->nodes, 4 * cap * sizeof(float4)},  {(void**)&s->nodes4, 8 * cap * sizeof(float4)}};
+  return lt_dev_replace("lt_scene_reserve", lt_wait_device(), &s->cap_faces, (int)cap, ws);
 }
 
+// the per-ray areas of the LBVH traversal: one group, sized for cap_rays
 int lt_scene_reserve_rays(lt_scene* s, int n_rays) {
   if (n_rays <= s->cap_rays) return LT_OK;
   LT_HIP(hipSetDevice(s->device));
-  if (s->overflow) {
-    LT_HIP(hipDeviceSynchronize());
-    (void)hipFree(s->overflow);
-    s->overflow = nullptr;
-  }
-  LT_CHECK(dev_alloc(&s->overflow, (size_t)n_rays * (LT_STACK4_MAX - LT_STACK4_LDS)));  // >= the binary kernel's 32
-  if (s->tail_stack) (void)hipFree(s->tail_stack);
-  if (s->tail_meta) (void)hipFree(s->tail_meta);
-  if (s->tail_queue) (void)hipFree(s->tail_queue);
-  s->tail_stack = nullptr; s->tail_meta = nullptr; s->tail_queue = nullptr;
-  LT_CHECK(dev_alloc(&s->tail_stack, (size_t)n_rays * LT_TAIL_SAVE));
-  LT_CHECK(dev_alloc(&s->tail_meta, (size_t)n_rays));
-  LT_CHECK(dev_alloc(&s->tail_queue, (size_t)n_rays));
-  if (!s->tail_count) {
-    LT_CHECK(dev_alloc(&s->tail_count, 4));
+  if (!s->tail_count) {  // the hand-over counters, once
+    LT_HIP(hipMalloc((void**)&s->tail_count, 4 * sizeof(int)));
     LT_HIP(hipMemset(s->tail_count, 0, 4 * sizeof(int)));
   }
-  s->cap_rays = n_rays;
-  return LT_OK;
+  const size_t n = (size_t)n_rays;
+  const lt_dev_array rays[] = {
+      {(void**)&s->overflow, n * (LT_STACK4_MAX - LT_STACK4_LDS) * sizeof(int)},  // >= the binary kernel's 32
+      {(void**)&s->tail_stack, n * LT_TAIL_SAVE * sizeof(int)},
+      {(void**)&s->tail_meta, n * sizeof(float4)},
+      {(void**)&s->tail_queue, n * sizeof(int)}};
+  return lt_dev_replace("lt_scene_reserve_rays", lt_wait_device(), &s->cap_rays, n_rays, rays);
 }
 
 extern "C" int lt_scene_create(lt_scene** out, int device) {
@@ -114,10 +89,11 @@ extern "C" int lt_scene_create(lt_scene** out, int device) {
     return LT_ERR_NO_MEMORY;
   }
   s->device = device;
-  int rc = dev_alloc(&s->partial, 6 * LT_BOUNDS_BLOCKS);
-  if (rc == LT_OK) rc = dev_alloc(&s->params, 8);
-  if (rc == LT_OK) rc = dev_alloc(&s->flags, 4);
-  if (rc == LT_OK) rc = dev_alloc(&s->counters, 8 + 4 * LT_DBG_WAVES);
+  const lt_dev_array fixed[] = {{(void**)&s->partial, 6 * LT_BOUNDS_BLOCKS * sizeof(float)},
+                                {(void**)&s->params, 8 * sizeof(float)},
+                                {(void**)&s->flags, 4 * sizeof(unsigned)},
+                                {(void**)&s->counters, (8 + 4 * LT_DBG_WAVES) * sizeof(unsigned long long)}};
+  int rc = lt_dev_replace("lt_scene_create", lt_wait_none(), fixed);
   if (rc == LT_OK && hipMemset(s->flags, 0, 4 * sizeof(unsigned)) != hipSuccess) rc = LT_ERR_HIP;
   for (int k = 0; rc == LT_OK && k < 10; ++k) {
     if (hipEventCreate(&s->ev[k]) != hipSuccess) {
@@ -185,8 +161,6 @@ extern "C" int lt_scene_set_mesh_dev(lt_scene* s, const float* verts, const int*
   return LT_OK;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }  // (also in lt_host.hip)
-
 extern "C" int lt_scene_set_mesh_host(lt_scene* s, const float* verts, const int* faces, const int* colors,
                                       const float* rem, int n_verts, int n_faces, void* stream_) {
   if (!s) {
@@ -196,24 +170,14 @@ extern "C" int lt_scene_set_mesh_host(lt_scene* s, const float* verts, const int
   LT_CHECK(lt_check_mesh_args("lt_scene_set_mesh_host", verts, faces, colors, rem, n_verts, n_faces));
   hipStream_t stream = (hipStream_t)stream_;
   LT_HIP(hipSetDevice(s->device));
-  const size_t bv = align256((size_t)n_verts * 12), bf = align256((size_t)n_faces * 12), bc = bv,
-               br = align256((size_t)n_verts * 4);
-  const size_t total = bv + bf + bc + br + 256;
-  if (total > s->owned_mesh_bytes) {
-    if (s->owned_mesh) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(s->owned_mesh);
-      s->owned_mesh = nullptr;
-      s->owned_mesh_bytes = 0;
-    }
-    LT_HIP(hipMalloc(&s->owned_mesh, total + total / 4));
-    s->owned_mesh_bytes = total + total / 4;
-  }
+  const lt_owned_mesh_layout L = lt_owned_mesh_layout_of((size_t)n_verts, (size_t)n_faces);
+  LT_CHECK(lt_dev_grow("lt_scene_set_mesh_host", lt_wait_device(), (char**)&s->owned_mesh, &s->owned_mesh_bytes, L.total,
+                       L.total + L.total / 4));
   char* base = (char*)s->owned_mesh;
-  float* dv = (float*)base;
-  int* df = (int*)(base + bv);
-  int* dc = (int*)(base + bv + bf);
-  float* dr = (float*)(base + bv + bf + bc);
+  float* dv = (float*)(base + L.verts);
+  int* df = (int*)(base + L.faces);
+  int* dc = (int*)(base + L.colors);
+  float* dr = (float*)(base + L.rem);
   if (n_verts > 0) {
     LT_HIP(hipMemcpyAsync(dv, verts, (size_t)n_verts * 12, hipMemcpyHostToDevice, stream));
     if (colors) LT_HIP(hipMemcpyAsync(dc, colors, (size_t)n_verts * 12, hipMemcpyHostToDevice, stream));

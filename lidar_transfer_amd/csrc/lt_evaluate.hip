@@ -14,6 +14,7 @@
 //                            sums in a fixed order) and one asynchronous copy of the record to the caller's memory
 // The projection arithmetic is lt_projpoint.h's (shared with lt_project.hip).  Nothing here waits for another workgroup.
 #include "lt_internal.h"
+#include "lt_devmem.h"
 #include "lt_projpoint.h"
 #include <math.h>
 #include <stdint.h>
@@ -262,6 +263,14 @@ void ev_free(lt_evaluator* e) {
     if (p) (void)hipFree(p);
 }
 
+// the z-min cells of a view of `cells` cells, exactly; new cells are not armed
+int ev_reserve_key(const char* who, lt_evaluator* e, size_t cells, hipStream_t st) {
+  if (cells <= e->cap_cells) return LT_OK;
+  LT_CHECK(lt_dev_grow(who, lt_wait_stream(st), &e->key, &e->cap_cells, cells, cells));
+  e->armed = false;
+  return LT_OK;
+}
+
 }  // namespace
 
 extern "C" int lt_evaluator_create(lt_evaluator** ev, int n_labels, int device) {
@@ -327,17 +336,7 @@ extern "C" int lt_source_scan_dev(lt_evaluator* e, const lt_raw_scan* scan, cons
   LT_HIP(hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   const size_t cells = (size_t)H * W;
-  if (cells > e->cap_cells) {
-    if (e->key) {
-      LT_HIP(hipStreamSynchronize(st));
-      (void)hipFree(e->key);
-      e->key = nullptr;
-      e->cap_cells = 0;
-    }
-    LT_HIP(hipMalloc((void**)&e->key, cells * sizeof(unsigned long long)));
-    e->cap_cells = cells;
-    e->armed = false;
-  }
+  LT_CHECK(ev_reserve_key("lt_source_scan_dev", e, cells, st));
   if (!e->armed) {  // first use, or the previous call failed half way
     LT_HIP(hipMemsetAsync(e->key, 0xFF, e->cap_cells * sizeof(unsigned long long), st));
     LT_HIP(hipMemsetAsync(e->bad, 0, sizeof(unsigned), st));
@@ -405,17 +404,7 @@ extern "C" int lt_target_view_dev(lt_evaluator* e, const lt_raw_scan* scan, cons
   LT_HIP(hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   const size_t cells = (size_t)H * W;
-  if (cells > e->cap_cells) {
-    if (e->key) {
-      LT_HIP(hipStreamSynchronize(st));
-      (void)hipFree(e->key);
-      e->key = nullptr;
-      e->cap_cells = 0;
-    }
-    LT_HIP(hipMalloc((void**)&e->key, cells * sizeof(unsigned long long)));
-    e->cap_cells = cells;
-    e->armed = false;
-  }
+  LT_CHECK(ev_reserve_key("lt_target_view_dev", e, cells, st));
   if (!e->model) LT_HIP(hipMalloc((void**)&e->model, LT_MODEL_DOUBLES * sizeof(double)));
   if (!e->armed) {  // first use, or the previous call failed half way
     LT_HIP(hipMemsetAsync(e->key, 0xFF, e->cap_cells * sizeof(unsigned long long), st));
@@ -478,16 +467,7 @@ extern "C" int lt_compare_record_dev(lt_evaluator* e, const int* src_label, cons
   LT_HIP(hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   const int nb = (n + 255) / 256;
-  if ((size_t)nb > e->cap_blocks) {
-    if (e->partial) {
-      LT_HIP(hipStreamSynchronize(st));
-      (void)hipFree(e->partial);
-      e->partial = nullptr;
-      e->cap_blocks = 0;
-    }
-    LT_HIP(hipMalloc((void**)&e->partial, (size_t)nb * sizeof(double)));
-    e->cap_blocks = (size_t)nb;
-  }
+  LT_CHECK(lt_dev_grow("lt_compare_record_dev", lt_wait_stream(st), &e->partial, &e->cap_blocks, (size_t)nb, (size_t)nb));
   if (++e->epoch == 0u) {  // 2^32 calls: the stamps start over
     LT_HIP(hipMemsetAsync(e->seen, 0, ((size_t)e->n_labels + 1) * sizeof(unsigned), st));
     e->epoch = 1u;

@@ -14,6 +14,7 @@
 //                              pre-zeroed images in (the pipe writes every cell: misses are 0 / tri -1, exactly what
 //                              the reference's pre-zeroed arrays hold afterwards).
 #include "lt_internal.h"
+#include "lt_layouts.h"
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -22,8 +23,6 @@
 #include <vector>
 #include <stdlib.h>
 #include <string.h>
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- small device helpers -------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_words_differ(const unsigned* __restrict__ a, const unsigned* __restrict__ b,
@@ -45,7 +44,7 @@ struct ctrace_ctx {
   hipStream_t stream = nullptr;
   lt_scene* scene = nullptr;
   lt_rayset* rs = nullptr;
-  void* io = nullptr;      // rays (new) | endpoints | endcolors | range | endrem | tri
+  char* io = nullptr;      // rays (new) | endpoints | endcolors | range | endrem | tri
   size_t io_bytes = 0;
   float* rays_cached = nullptr;  // device copy of the rays the ray set was built from
   size_t rays_cached_n = 0;      // floats
@@ -101,25 +100,14 @@ static int ctrace_thread(const float* rays, const float* origin, const float* ve
   hipStream_t stream = c.stream;
   const int W = n_rays / height;
   const size_t R = (size_t)W * height;
-  const size_t b3 = align256(R * 12), b1 = align256(R * 4);
-  const size_t total = 3 * b3 + 3 * b1 + 256;
-  if (total > c.io_bytes) {
-    if (c.io) {
-      LT_HIP(hipStreamSynchronize(stream));
-      (void)hipFree(c.io);
-      c.io = nullptr;
-      c.io_bytes = 0;
-    }
-    LT_HIP(hipMalloc(&c.io, total));
-    c.io_bytes = total;
-  }
-  char* io = (char*)c.io;
-  float* d_rays = (float*)io;
-  float* d_end = (float*)(io + b3);
-  int* d_col = (int*)(io + 2 * b3);
-  float* d_range = (float*)(io + 3 * b3);
-  float* d_rem = (float*)(io + 3 * b3 + b1);
-  int* d_tri = (int*)(io + 3 * b3 + 2 * b1);
+  const lt_ctrace_io_layout L = lt_ctrace_io_layout_of(R);
+  LT_CHECK(lt_dev_grow("lt_ctrace", lt_wait_stream(stream), &c.io, &c.io_bytes, L.total, L.total));
+  float* d_rays = (float*)(c.io + L.rays);
+  float* d_end = (float*)(c.io + L.endpoints);
+  int* d_col = (int*)(c.io + L.endcolors);
+  float* d_range = (float*)(c.io + L.range);
+  float* d_rem = (float*)(c.io + L.endrem);
+  int* d_tri = (int*)(c.io + L.tri);
   const unsigned norm_flag = lt_env_norm_flag();
   const char* sg = getenv("LIDARHIP_STRATEGY");
   const bool lbvh = sg && strcmp(sg, "lbvh") == 0;
@@ -163,14 +151,8 @@ static int ctrace_thread(const float* rays, const float* origin, const float* ve
     if (!maybe_same) {
       if (c.rs) (void)lt_rayset_destroy(c.rs);
       c.rs = nullptr;
-      if (c.rays_cached_n < R * 3 || !c.rays_cached) {
-        if (c.rays_cached) {
-          LT_HIP(hipStreamSynchronize(stream));
-          (void)hipFree(c.rays_cached);
-          c.rays_cached = nullptr;
-        }
-        LT_HIP(hipMalloc((void**)&c.rays_cached, (R * 3 + 1) * sizeof(float)));
-      }
+      // (rays_cached_n is the capacity too: a copy that held fewer rays is replaced)
+      LT_CHECK(lt_dev_grow("lt_ctrace", lt_wait_stream(stream), &c.rays_cached, &c.rays_cached_n, R * 3, R * 3 + 1));
       c.rays_cached_n = R * 3;
       if (R > 0) LT_HIP(hipMemcpyAsync(c.rays_cached, d_rays, R * 12, hipMemcpyDeviceToDevice, stream));
       LT_CHECK(lt_rayset_create_dev(&c.rs, d_rays, (int)R, height, norm_flag, stream));
@@ -265,7 +247,7 @@ struct lt_hostpipe {
   // of blocking pageable uploads + a staged download.  Off by default: measured slower on this platform (0.53 vs
   // 0.47 ms per C2 scan, tools/hostpipe_probe.cpp), where a pageable copy already runs at 88 % of the wire rate.
   bool use_register = false;
-  size_t b3, b1, bc;  // bytes of a [R,3] f32 image, a [R] image, the colour image
+  lt_hp_out_layout out;  // the five images of a scan in a slot's out_dev and out_pin
   lt_rayset* rs = nullptr;
   // LIDARHIP_HOSTPIPE_UPLOADERS (default: 2 when depth >= 4, else 1): uploader threads, each with its own stream, taking
   // scans alternately -- a pageable copy occupies its caller, and the fixed part of one thread's copy (staging ramp-up
@@ -291,6 +273,13 @@ struct lt_hostpipe {
   bool stop = false;
   std::thread worker[4], launcher;
 };
+
+// the arrays of a slot's mesh block (lt_hp_mesh_layout_of: the uploader fills them, the launcher hands them to the scene)
+struct hp_mesh_ptrs { float* verts; int* faces; int* colors; float* rem; unsigned char* colors_u8; };
+static hp_mesh_ptrs hp_mesh_ptrs_of(char* mesh, const lt_hp_mesh_layout& L) {
+  return {(float*)(mesh + L.verts), (int*)(mesh + L.faces), (int*)(mesh + L.colors), (float*)(mesh + L.rem),
+          (unsigned char*)(mesh + L.colors_u8)};
+}
 
 static double hp_now() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -339,24 +328,9 @@ static int hp_upload(lt_hostpipe* p, hp_slot& sl, hipStream_t s_up) {
   const double t0 = hp_now();
   p->trace[j.ticket & 255][1] = t0;
   LT_HIP(hipSetDevice(p->device));
-  const size_t bv = align256((size_t)j.n_verts * 12), bf = align256((size_t)j.n_faces * 12),
-               br = align256((size_t)j.n_verts * 4), b8 = align256((size_t)j.n_verts * 3);
-  const size_t total = 2 * bv + bf + br + b8 + 256;
-  if (total > sl.mesh_bytes) {
-    if (sl.mesh) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(sl.mesh);
-      sl.mesh = nullptr;
-      sl.mesh_bytes = 0;
-    }
-    LT_HIP(hipMalloc((void**)&sl.mesh, total + total / 4));
-    sl.mesh_bytes = total + total / 4;
-  }
-  float* dv = (float*)sl.mesh;
-  int* df = (int*)(sl.mesh + bv);
-  int* dc = (int*)(sl.mesh + bv + bf);
-  float* dr = (float*)(sl.mesh + 2 * bv + bf);
-  unsigned char* d8 = (unsigned char*)(sl.mesh + 2 * bv + bf + br);
+  const lt_hp_mesh_layout L = lt_hp_mesh_layout_of((size_t)j.n_verts, (size_t)j.n_faces);
+  LT_CHECK(lt_dev_grow("lt_hostpipe", lt_wait_device(), &sl.mesh, &sl.mesh_bytes, L.total, L.total + L.total / 4));
+  const hp_mesh_ptrs M = hp_mesh_ptrs_of(sl.mesh, L);
   // upload: straight from the caller's arrays.  Registered ranges make the copies asynchronous DMA (they queue up
   // behind each other on the upload stream); anything that cannot be registered goes the pageable way, where each
   // call returns when its transfer is done -- which is this thread's job
@@ -367,12 +341,12 @@ static int hp_upload(lt_hostpipe* p, hp_slot& sl, hipStream_t s_up) {
     hp_pin(p, j, j.faces, (size_t)j.n_faces * 12);
   }
   if (j.n_verts > 0) {
-    LT_HIP(hipMemcpyAsync(dv, j.verts, (size_t)j.n_verts * 12, hipMemcpyHostToDevice, s_up));
-    if (j.colors_u8) LT_HIP(hipMemcpyAsync(d8, j.colors, (size_t)j.n_verts * 3, hipMemcpyHostToDevice, s_up));
-    else LT_HIP(hipMemcpyAsync(dc, j.colors, (size_t)j.n_verts * 12, hipMemcpyHostToDevice, s_up));
-    LT_HIP(hipMemcpyAsync(dr, j.rem, (size_t)j.n_verts * 4, hipMemcpyHostToDevice, s_up));
+    LT_HIP(hipMemcpyAsync(M.verts, j.verts, (size_t)j.n_verts * 12, hipMemcpyHostToDevice, s_up));
+    if (j.colors_u8) LT_HIP(hipMemcpyAsync(M.colors_u8, j.colors, (size_t)j.n_verts * 3, hipMemcpyHostToDevice, s_up));
+    else LT_HIP(hipMemcpyAsync(M.colors, j.colors, (size_t)j.n_verts * 12, hipMemcpyHostToDevice, s_up));
+    LT_HIP(hipMemcpyAsync(M.rem, j.rem, (size_t)j.n_verts * 4, hipMemcpyHostToDevice, s_up));
   }
-  if (j.n_faces > 0) LT_HIP(hipMemcpyAsync(df, j.faces, (size_t)j.n_faces * 12, hipMemcpyHostToDevice, s_up));
+  if (j.n_faces > 0) LT_HIP(hipMemcpyAsync(M.faces, j.faces, (size_t)j.n_faces * 12, hipMemcpyHostToDevice, s_up));
   LT_HIP(hipEventRecord(sl.ev_up, s_up));
   {
     std::lock_guard<std::mutex> lk(p->mu);
@@ -388,23 +362,18 @@ static int hp_launch(lt_hostpipe* p, hp_slot& sl) {
   hp_job& j = sl.job;
   const double t0 = hp_now();
   LT_HIP(hipSetDevice(p->device));
-  const size_t bv = align256((size_t)j.n_verts * 12), bf = align256((size_t)j.n_faces * 12),
-               br = align256((size_t)j.n_verts * 4);
-  float* dv = (float*)sl.mesh;
-  int* df = (int*)(sl.mesh + bv);
-  int* dc = (int*)(sl.mesh + bv + bf);
-  float* dr = (float*)(sl.mesh + 2 * bv + bf);
-  unsigned char* d8 = (unsigned char*)(sl.mesh + 2 * bv + bf + br);
+  const hp_mesh_ptrs M = hp_mesh_ptrs_of(sl.mesh, lt_hp_mesh_layout_of((size_t)j.n_verts, (size_t)j.n_faces));
   LT_HIP(hipStreamWaitEvent(p->s_run, sl.ev_up, 0));
   if (j.colors_u8 && j.n_verts > 0)
-    hipLaunchKernelGGL(k_widen_u8, dim3(512), dim3(256), 0, p->s_run, d8, dc, (size_t)j.n_verts * 3);
-  LT_CHECK(lt_scene_set_mesh_dev(sl.scene, dv, df, dc, dr, j.n_verts, j.n_faces));
+    hipLaunchKernelGGL(k_widen_u8, dim3(512), dim3(256), 0, p->s_run, M.colors_u8, M.colors, (size_t)j.n_verts * 3);
+  LT_CHECK(lt_scene_set_mesh_dev(sl.scene, M.verts, M.faces, M.colors, M.rem, j.n_verts, j.n_faces));
+  const lt_hp_out_layout& O = p->out;
   char* o = sl.out_dev;
-  float* d_end = (float*)o;
-  int* d_col = (int*)(o + p->b3);
-  float* d_range = (float*)(o + p->b3 + p->bc);
-  float* d_rem = (float*)(o + p->b3 + p->bc + p->b1);
-  int* d_tri = (int*)(o + p->b3 + p->bc + 2 * p->b1);
+  float* d_end = (float*)(o + O.endpoints);
+  int* d_col = (int*)(o + O.endcolors);
+  float* d_range = (float*)(o + O.range);
+  float* d_rem = (float*)(o + O.endrem);
+  int* d_tri = (int*)(o + O.tri);
   LT_CHECK(lt_scene_render_dev(sl.scene, p->rs, j.origin, j.endpoints ? d_end : nullptr, j.endcolors ? d_col : nullptr,
                                j.range ? d_range : nullptr, j.endrem ? d_rem : nullptr, j.tri ? d_tri : nullptr,
                                p->flags | LT_TRACE_WRITE_MISSES, p->s_run, nullptr));
@@ -428,14 +397,14 @@ static int hp_launch(lt_hostpipe* p, hp_slot& sl) {
   }
   // staged: the five images are one block on the device and in the staging buffer -> ONE transfer
   if (R > 0 && !j.direct_out) {
-    LT_HIP(hipMemcpyAsync(h, o, p->b3 + p->bc + 3 * p->b1, hipMemcpyDeviceToHost, p->s_down));
+    LT_HIP(hipMemcpyAsync(h, o, O.images, hipMemcpyDeviceToHost, p->s_down));
   } else if (R > 0) {
     const bool d = j.direct_out != 0;
-    if (j.endpoints) LT_HIP(hipMemcpyAsync(d ? (void*)j.endpoints : (void*)h, d_end, R * 12, hipMemcpyDeviceToHost, p->s_down));
-    if (j.endcolors) LT_HIP(hipMemcpyAsync(d ? (void*)j.endcolors : (void*)(h + p->b3), d_col, ncol, hipMemcpyDeviceToHost, p->s_down));
-    if (j.range) LT_HIP(hipMemcpyAsync(d ? (void*)j.range : (void*)(h + p->b3 + p->bc), d_range, R * 4, hipMemcpyDeviceToHost, p->s_down));
-    if (j.endrem) LT_HIP(hipMemcpyAsync(d ? (void*)j.endrem : (void*)(h + p->b3 + p->bc + p->b1), d_rem, R * 4, hipMemcpyDeviceToHost, p->s_down));
-    if (j.tri) LT_HIP(hipMemcpyAsync(d ? (void*)j.tri : (void*)(h + p->b3 + p->bc + 2 * p->b1), d_tri, R * 4, hipMemcpyDeviceToHost, p->s_down));
+    if (j.endpoints) LT_HIP(hipMemcpyAsync(d ? (void*)j.endpoints : (void*)(h + O.endpoints), d_end, R * 12, hipMemcpyDeviceToHost, p->s_down));
+    if (j.endcolors) LT_HIP(hipMemcpyAsync(d ? (void*)j.endcolors : (void*)(h + O.endcolors), d_col, ncol, hipMemcpyDeviceToHost, p->s_down));
+    if (j.range) LT_HIP(hipMemcpyAsync(d ? (void*)j.range : (void*)(h + O.range), d_range, R * 4, hipMemcpyDeviceToHost, p->s_down));
+    if (j.endrem) LT_HIP(hipMemcpyAsync(d ? (void*)j.endrem : (void*)(h + O.endrem), d_rem, R * 4, hipMemcpyDeviceToHost, p->s_down));
+    if (j.tri) LT_HIP(hipMemcpyAsync(d ? (void*)j.tri : (void*)(h + O.tri), d_tri, R * 4, hipMemcpyDeviceToHost, p->s_down));
   }
   LT_HIP(hipEventRecord(sl.ev_done, p->s_down));
   p->t_issue += hp_now() - t0;
@@ -576,9 +545,7 @@ extern "C" int lt_hostpipe_create(lt_hostpipe** out, const float* rays, int n_ra
     p->use_register = e && strcmp(e, "1") == 0;
   }
   const size_t R = (size_t)p->n_rays;
-  p->b3 = align256(R * 12);
-  p->b1 = align256(R * 4);
-  p->bc = (flags & LT_TRACE_LABEL_IMAGE) ? p->b1 : p->b3;
+  p->out = lt_hp_out_layout_of(R, (flags & LT_TRACE_LABEL_IMAGE) != 0);
   int rc = LT_OK;
   auto ok = [&](hipError_t e, const char* what) {
     if (e != hipSuccess && rc == LT_OK) {
@@ -606,7 +573,7 @@ extern "C" int lt_hostpipe_create(lt_hostpipe** out, const float* rays, int n_ra
     if (d_rays) (void)hipFree(d_rays);
   }
   p->slots.resize(depth);
-  const size_t out_bytes = p->b3 + p->bc + 3 * p->b1 + 256;
+  const size_t out_bytes = p->out.total;
   for (int k = 0; rc == LT_OK && k < depth; ++k) {
     hp_slot& sl = p->slots[k];
     rc = lt_scene_create(&sl.scene, device);
@@ -651,11 +618,11 @@ static int hp_collect(lt_hostpipe* p, hp_slot& sl) {
     const size_t R = (size_t)p->n_rays;
     const size_t ncol = (p->flags & LT_TRACE_LABEL_IMAGE) ? R * 4 : R * 12;
     const char* h = sl.out_pin;
-    if (j.endpoints) memcpy(j.endpoints, h, R * 12);
-    if (j.endcolors) memcpy(j.endcolors, h + p->b3, ncol);
-    if (j.range) memcpy(j.range, h + p->b3 + p->bc, R * 4);
-    if (j.endrem) memcpy(j.endrem, h + p->b3 + p->bc + p->b1, R * 4);
-    if (j.tri) memcpy(j.tri, h + p->b3 + p->bc + 2 * p->b1, R * 4);
+    if (j.endpoints) memcpy(j.endpoints, h + p->out.endpoints, R * 12);
+    if (j.endcolors) memcpy(j.endcolors, h + p->out.endcolors, ncol);
+    if (j.range) memcpy(j.range, h + p->out.range, R * 4);
+    if (j.endrem) memcpy(j.endrem, h + p->out.endrem, R * 4);
+    if (j.tri) memcpy(j.tri, h + p->out.tri, R * 4);
   }
   if (rc != LT_OK) {
     for (int u = 0; u < p->n_up; ++u) (void)hipStreamSynchronize(p->s_up[u]);

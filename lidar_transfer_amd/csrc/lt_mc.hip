@@ -39,6 +39,7 @@
 // output's order); scikit-image numbers vertices by first use in a serial face stream.
 // Tables: lt_mc_lewiner_table.h (Lewiner's LookUpTable.h as scikit-image ships it, tools/gen_mc_lewiner.py).
 #include "lt_internal.h"
+#include "lt_devmem.h"
 #include <float.h>
 #include <math.h>
 #include <stdio.h>
@@ -1458,38 +1459,10 @@ extern "C" int lt_mesh_get(lt_mesh* m, int* n_verts, int* n_faces, float** verts
   return LT_OK;
 }
 
-// A group of device arrays that share one capacity is replaced: the old arrays freed (after the device has finished with
-// them), the new ones allocated, *cap = new_cap.  On failure nothing of the group is left and *cap is 0.
-struct mc_array { void** p; size_t bytes; };
-template <class C, size_t N>
-static hipError_t mc_realloc(C* cap, C new_cap, const mc_array (&group)[N]) {
-  auto drop = [&]() {
-    for (const mc_array& g : group) { (void)hipFree(*g.p); *g.p = nullptr; }
-    *cap = 0;
-  };
-  bool any = false;
-  for (const mc_array& g : group) any = any || *g.p;
-  hipError_t e = any ? hipDeviceSynchronize() : hipSuccess;
-  if (e != hipSuccess) return e;
-  drop();
-  for (const mc_array& g : group)
-    if (e == hipSuccess) e = hipMalloc(g.p, g.bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    drop();
-    return e;
-  }
-  *cap = new_cap;
-  return hipSuccess;
-}
-
+// one array of the mesh with the headroom rule (lt_devmem.h; the device has finished with the old one before it goes)
 template <class T>
-static int mc_grow(T** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return LT_OK;
-  const size_t n = need + need / 4 + 1024;
-  const mc_array one[] = {{(void**)p, n * sizeof(T)}};
-  LT_HIP(mc_realloc(cap, n, one));
-  return LT_OK;
+static int mc_reserve(T** p, size_t* cap, size_t need) {
+  return lt_dev_grow("lt_marching_cubes_dev", lt_wait_device(), p, cap, need, lt_headroom(need));
 }
 
 static mc_emit_args mc_emit_args_of(const float* tsdf, const float* color_vol, const float* rem_vol, const u64* bits,
@@ -1550,9 +1523,9 @@ static int mc_reserve_words(const mc_job& J) {  // bits / cnt / cmap
   lt_mesh* m = J.m;
   const size_t n_words = (size_t)J.D.n_words;
   if (n_words > m->cap_words || !m->bits) {
-    const mc_array words[] = {{(void**)&m->bits, (n_words + 1) * sizeof(u64)}, {(void**)&m->cnt, n_words * sizeof(unsigned)},
-                              {(void**)&m->cmap, n_words * sizeof(int)}};
-    LT_HIP(mc_realloc(&m->cap_words, n_words, words));
+    const lt_dev_array words[] = {{(void**)&m->bits, (n_words + 1) * sizeof(u64)}, {(void**)&m->cnt, n_words * sizeof(unsigned)},
+                                  {(void**)&m->cmap, n_words * sizeof(int)}};
+    LT_CHECK(lt_dev_replace("lt_marching_cubes_dev", lt_wait_device(), &m->cap_words, n_words, words));
     m->state_dirty = 1;  // (fresh buffers: swept by mc_restore_state)
   }
   return LT_OK;
@@ -1567,12 +1540,11 @@ static int mc_reserve_amb(const mc_job& J) {
   size_t tcap = 1;
   while (tcap < 4 * LT_MC_SHARDS * cap) tcap <<= 1;
   const size_t n_ctr = LT_MC_SHARDS * LT_MC_CTR_STRIDE + LT_MC_SHARDS;
-  const mc_array amb[] = {{(void**)&m->amb.queue, LT_MC_SHARDS * cap * sizeof(uint2)}, {(void**)&m->amb.table, tcap * sizeof(uint2)}};
-  if (mc_realloc(&m->amb.cap, (unsigned)cap, amb) != hipSuccess ||
-      (!m->amb.counter && hipMalloc((void**)&m->amb.counter, n_ctr * sizeof(int)) != hipSuccess)) {
-    (void)hipGetLastError();
-    lt_set_error("lt_marching_cubes_dev: hipMalloc of the ambiguous cells' buffers (%zu cells) failed", cap);
-    return LT_ERR_NO_MEMORY;
+  const lt_dev_array amb[] = {{(void**)&m->amb.queue, LT_MC_SHARDS * cap * sizeof(uint2)}, {(void**)&m->amb.table, tcap * sizeof(uint2)}};
+  LT_CHECK(lt_dev_replace("lt_marching_cubes_dev (ambiguous cells)", lt_wait_device(), &m->amb.cap, (unsigned)cap, amb));
+  if (!m->amb.counter) {  // once
+    const lt_dev_array counter[] = {{(void**)&m->amb.counter, n_ctr * sizeof(int)}};
+    LT_CHECK(lt_dev_replace("lt_marching_cubes_dev (ambiguous cells)", lt_wait_none(), counter));
   }
   m->amb_cap = cap;
   m->amb.tmask = (unsigned)(tcap - 1);
@@ -1604,12 +1576,12 @@ static int mc_restore_state(const mc_job& J) {
 
 static int mc_reserve_blocks(const mc_job& J) {  // wave_na and blk (the blocks' triples, the segment sums, four totals)
   lt_mesh* m = J.m;
-  LT_CHECK(mc_grow(&m->wave_na, &m->cap_wave_na, (size_t)J.n_blocks));
+  LT_CHECK(mc_reserve(&m->wave_na, &m->cap_wave_na, (size_t)J.n_blocks));
   if (J.n_seg > 1024) {
     lt_set_error("lt_marching_cubes_dev: volume too large (%d words)", J.D.n_words);
     return LT_ERR_TOO_LARGE;
   }
-  return mc_grow(&m->blk, &m->cap_blocks, (size_t)3 * J.n_blocks + 3 * (size_t)J.n_seg + 4);
+  return mc_reserve(&m->blk, &m->cap_blocks, (size_t)3 * J.n_blocks + 3 * (size_t)J.n_seg + 4);
 }
 
 // The counting part, up to the one synchronisation: m->totals_host holds {active words, vertices, triangles, the fullest
@@ -1651,19 +1623,16 @@ static int mc_reserve_mesh(const mc_job& J) {
     lt_set_error("lt_marching_cubes_dev: %d faces exceed LT_MAX_FACES", nf);
     return LT_ERR_TOO_LARGE;
   }
-  LT_CHECK(mc_grow(&m->rec, &m->cap_rec, (size_t)n_active));
+  LT_CHECK(mc_reserve(&m->rec, &m->cap_rec, (size_t)n_active));
   if (nv > m->cap_v || !m->verts) {
-    const size_t cap = (size_t)nv + nv / 4 + 1024;
-    const mc_array vertex[] = {{(void**)&m->verts, cap * 12}, {(void**)&m->colors, cap * 12}, {(void**)&m->rem, cap * 4}};
-    if (mc_realloc(&m->cap_v, (int)min(cap, (size_t)2147483647), vertex) != hipSuccess) {
-      lt_set_error("lt_marching_cubes_dev: hipMalloc of the vertex arrays (%zu vertices) failed", cap);
-      return LT_ERR_NO_MEMORY;
-    }
+    const size_t cap = lt_headroom((size_t)nv);
+    const lt_dev_array vertex[] = {{(void**)&m->verts, cap * 12}, {(void**)&m->colors, cap * 12}, {(void**)&m->rem, cap * 4}};
+    LT_CHECK(lt_dev_replace("lt_marching_cubes_dev (vertices)", lt_wait_device(), &m->cap_v, (int)min(cap, (size_t)2147483647), vertex));
   }
   if (nf > m->cap_f || !m->faces) {
-    const size_t cap = (size_t)nf + nf / 4 + 1024;
-    const mc_array face[] = {{(void**)&m->faces, cap * 12}};
-    LT_HIP(mc_realloc(&m->cap_f, (int)min(cap, (size_t)2147483647), face));
+    const size_t cap = lt_headroom((size_t)nf);
+    const lt_dev_array face[] = {{(void**)&m->faces, cap * 12}};
+    LT_CHECK(lt_dev_replace("lt_marching_cubes_dev (faces)", lt_wait_device(), &m->cap_f, (int)min(cap, (size_t)2147483647), face));
   }
   return LT_OK;
 }
@@ -1866,28 +1835,17 @@ extern "C" int lt_mesh_renumber_dev(lt_mesh* m, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   LT_HIP(hipSetDevice(m->device));
   const int nb = (n3 + 1023) / 1024;
+  const char* who = "lt_mesh_renumber_dev";  // (no wait of its own: hipFree waits for the device)
   if ((size_t)nv > m->cap_rn || !m->rn_first) {
-    (void)hipFree(m->rn_first); (void)hipFree(m->rn_newid);
-    m->rn_first = nullptr; m->rn_newid = nullptr; m->cap_rn = 0;
-    const size_t cap = (size_t)nv + nv / 4 + 1024;
-    LT_HIP(hipMalloc((void**)&m->rn_first, cap * sizeof(int)));
-    LT_HIP(hipMalloc((void**)&m->rn_newid, cap * sizeof(int)));
-    m->cap_rn = cap;
+    const size_t cap = lt_headroom((size_t)nv);
+    const lt_dev_array per_vertex[] = {{(void**)&m->rn_first, cap * sizeof(int)}, {(void**)&m->rn_newid, cap * sizeof(int)}};
+    LT_CHECK(lt_dev_replace(who, lt_wait_none(), &m->cap_rn, cap, per_vertex));
   }
-  if ((size_t)nb + 1 > m->cap_bsum || !m->rn_bsum) {
-    (void)hipFree(m->rn_bsum);
-    m->rn_bsum = nullptr; m->cap_bsum = 0;
-    const size_t cap = (size_t)nb + nb / 4 + 1024;
-    LT_HIP(hipMalloc((void**)&m->rn_bsum, cap * sizeof(int)));
-    m->cap_bsum = cap;
-  }
+  LT_CHECK(lt_dev_grow(who, lt_wait_none(), &m->rn_bsum, &m->cap_bsum, (size_t)nb + 1, (size_t)nb + nb / 4 + 1024));
   if (m->cap_v2 < m->cap_v || !m->verts2) {
-    (void)hipFree(m->verts2); (void)hipFree(m->colors2); (void)hipFree(m->rem2);
-    m->verts2 = nullptr; m->colors2 = nullptr; m->rem2 = nullptr; m->cap_v2 = 0;
-    LT_HIP(hipMalloc((void**)&m->verts2, (size_t)m->cap_v * 12));
-    LT_HIP(hipMalloc((void**)&m->colors2, (size_t)m->cap_v * 12));
-    LT_HIP(hipMalloc((void**)&m->rem2, (size_t)m->cap_v * 4));
-    m->cap_v2 = m->cap_v;
+    const size_t cap = (size_t)m->cap_v;
+    const lt_dev_array second[] = {{(void**)&m->verts2, cap * 12}, {(void**)&m->colors2, cap * 12}, {(void**)&m->rem2, cap * 4}};
+    LT_CHECK(lt_dev_replace(who, lt_wait_none(), &m->cap_v2, m->cap_v, second));
   }
   LT_HIP(hipMemsetAsync(m->rn_first, 0x7F, (size_t)nv * sizeof(int), stream));   // 0x7F7F7F7F: beyond any position
   LT_HIP(hipMemsetAsync(m->rn_newid, 0xFF, (size_t)nv * sizeof(int), stream));   // -1

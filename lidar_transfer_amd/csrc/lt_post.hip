@@ -6,6 +6,7 @@
 //   * compare / iouEval          (auxiliary/laserscan.py:1181-1301, np_ioueval.py:31-70): masked confusion
 //     matrix (atomic histogram) and squared range / remission differences
 #include "lt_internal.h"
+#include "lt_devmem.h"
 #include <math.h>
 #include <mutex>
 #include <type_traits>
@@ -302,13 +303,9 @@ extern "C" int lt_pack_scan_dev(const void* points, int is_f64, const float* rem
   LT_HIP(hipGetDevice(&dev));
   const int nb = (n + 255) / 256;
   if (dev != g_post_dev || (size_t)nb + 2 > g_blockcount_cap) {
-    if (g_blockcount) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(g_blockcount);
-      g_blockcount = nullptr;
-    }
-    g_blockcount_cap = (size_t)nb * 2 + 1024;
-    LT_HIP(hipMalloc((void**)&g_blockcount, g_blockcount_cap * sizeof(int)));
+    const size_t cap = (size_t)nb * 2 + 1024;
+    const lt_dev_array counts[] = {{(void**)&g_blockcount, cap * sizeof(int)}};
+    LT_CHECK(lt_dev_replace("lt_pack_scan_dev", lt_wait_device(), &g_blockcount_cap, cap, counts));
     g_post_dev = dev;
   }
   hipStream_t st = (hipStream_t)stream;

@@ -16,6 +16,7 @@
 // was read from file (laserscan.py:131-136), float64 after a pose was applied (laserscan.py:98-104).
 // float32 transcendental results are the correctly rounded value (computed in double, rounded once).
 #include "lt_internal.h"
+#include "lt_layouts.h"
 #include "lt_projpoint.h"  // project_point, pb_key: shared with lt_evaluate.hip
 #include <math.h>
 #include <string.h>
@@ -557,19 +558,25 @@ void pj_free(lt_projector* p) {
 
 int pj_reserve(lt_projector* p, size_t n_max, size_t cells, bool need_dmin, hipStream_t st) {
   if (n_max > p->cap_n || cells > p->cap_cells) {
-    if (p->cap_n || p->cap_cells) LT_HIP(hipStreamSynchronize(st));
-    const size_t cn = std::max(p->cap_n, n_max + n_max / 4 + 1024), cc = std::max(p->cap_cells, cells + 1024);
-    pj_free(p);
+    // one group under two capacities (cap_n is the group's own, cap_cells follows it); dmin is dropped with the rest and
+    // comes back below, when a call asks for it
+    const size_t cn = std::max(p->cap_n, lt_headroom(n_max)), cc = std::max(p->cap_cells, cells + 1024);
+    lt_dev_array slots[4 * LT_PB_MAX];
     for (int k = 0; k < LT_PB_MAX; ++k) {
-      LT_HIP(hipMalloc((void**)&p->key[k], cc * sizeof(unsigned long long)));
-      LT_HIP(hipMalloc((void**)&p->keep[k], (cn / 64 + 2) * sizeof(unsigned long long)));
-      LT_HIP(hipMalloc((void**)&p->wprefix[k], (cn / 64 + 2) * sizeof(int)));
+      slots[4 * k] = {(void**)&p->key[k], cc * sizeof(unsigned long long)};
+      slots[4 * k + 1] = {(void**)&p->keep[k], (cn / 64 + 2) * sizeof(unsigned long long)};
+      slots[4 * k + 2] = {(void**)&p->wprefix[k], (cn / 64 + 2) * sizeof(int)};
+      slots[4 * k + 3] = {(void**)&p->dmin[k], 0};
     }
-    p->cap_n = cn;
+    p->cap_cells = 0;
+    p->armed = p->dmin_armed = false;
+    LT_CHECK(lt_dev_replace("lt_range_projection_batch_dev", lt_wait_stream(st), &p->cap_n, cn, slots));
     p->cap_cells = cc;
   }
   if (need_dmin && !p->dmin[0]) {
-    for (int k = 0; k < LT_PB_MAX; ++k) LT_HIP(hipMalloc((void**)&p->dmin[k], p->cap_cells * sizeof(unsigned long long)));
+    lt_dev_array dmin[LT_PB_MAX];
+    for (int k = 0; k < LT_PB_MAX; ++k) dmin[k] = {(void**)&p->dmin[k], p->cap_cells * sizeof(unsigned long long)};
+    LT_CHECK(lt_dev_replace("lt_range_projection_batch_dev", lt_wait_none(), dmin));
     p->dmin_armed = false;
   }
   if (!p->armed)
@@ -746,10 +753,9 @@ static int project_clouds(lt_projector* p, const pj_model& model, int n_clouds, 
     for (int k = 0; k < n_clouds; ++k) want = want || out[k].bnds;
     const size_t nb = n_max / 256 + 2;
     if (want && nb > p->bacc_blocks) {
-      if (p->bacc) { LT_HIP(hipStreamSynchronize(st)); (void)hipFree(p->bacc); p->bacc = nullptr; p->bacc_blocks = 0; }
       const size_t cap = nb + nb / 4 + 64;
-      LT_HIP(hipMalloc((void**)&p->bacc, LT_PB_MAX * cap * 6 * sizeof(unsigned long long)));
-      p->bacc_blocks = cap;
+      const lt_dev_array bacc[] = {{(void**)&p->bacc, LT_PB_MAX * cap * 6 * sizeof(unsigned long long)}};
+      LT_CHECK(lt_dev_replace("lt_range_projection_batch_dev", lt_wait_stream(st), &p->bacc_blocks, cap, bacc));
     }
   }
   p->armed = false;  // (until the resolve pass of this call has been queued)
@@ -920,11 +926,7 @@ extern "C" int lt_deform_scan_dev(lt_projector* p, lt_tsdf* vol, lt_mesh* mesh, 
   {
     std::lock_guard<std::mutex> lock(p->mu);
     LT_HIP(hipSetDevice(p->device));
-    if (need > p->img_cap) {
-      if (p->img) { LT_HIP(hipStreamSynchronize((hipStream_t)stream)); (void)hipFree(p->img); p->img = nullptr; p->img_cap = 0; }
-      LT_HIP(hipMalloc((void**)&p->img, need * sizeof(float)));
-      p->img_cap = need;
-    }
+    LT_CHECK(lt_dev_grow("lt_deform_scan_dev", lt_wait_stream((hipStream_t)stream), &p->img, &p->img_cap, need, need));
   }
   lt_proj_images out[64];
   const float* color_ims[64];
@@ -964,14 +966,9 @@ extern "C" int lt_mergemesh_scan_dev(lt_projector* p, lt_mm_state* mm, int seq, 
   {
     std::lock_guard<std::mutex> lock(p->mu);
     if (hipSetDevice(p->device) != hipSuccess) return fail(LT_ERR_HIP);
-    if (3 * cells > p->img_cap) {
-      if (p->img) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(p->img); p->img = nullptr; p->img_cap = 0; }
-      if (hipMalloc((void**)&p->img, 3 * cells * sizeof(float)) != hipSuccess) {
-        lt_set_error("lt_mergemesh_scan_dev: hipMalloc of the source images failed");
-        return fail(LT_ERR_NO_MEMORY);
-      }
-      p->img_cap = 3 * cells;
-    }
+    const int rc_img = lt_dev_grow("lt_mergemesh_scan_dev", lt_wait_stream((hipStream_t)stream), &p->img, &p->img_cap, 3 * cells,
+                                   3 * cells);
+    if (rc_img != LT_OK) return fail(rc_img);
     if (!p->mm_bnds && hipMalloc((void**)&p->mm_bnds, 6 * sizeof(double)) != hipSuccess) {
       lt_set_error("lt_mergemesh_scan_dev: hipMalloc failed");
       return fail(LT_ERR_NO_MEMORY);
@@ -1024,20 +1021,11 @@ extern "C" int lt_range_projection(const void* points, int is_f64, const float* 
   }
   const size_t es = is_f64 ? 8 : 4, cells = (size_t)H * W, N = (size_t)n;
   // one staging allocation: inputs | per-point outputs | images
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t sz[] = {al(N * 3 * es), al(N * 4), al(N * 4), al((size_t)(lut_len > 0 ? lut_len : 0) * 12),
-                       al(N * 3 * es), al(N * 4), al(N * 4), al(N * es), al(N * 4), al(N * 4), al(N * es), al(N * es),
-                       al(cells * 4), al(cells * 4), al(cells * 12), al(cells * 4), al(cells * 4), al(cells * 12),
-                       al(cells * 4)};
-  size_t total = 256;
-  for (size_t s : sz) total += s;
+  const lt_rp_layout L = lt_rp_layout_of(N, es, (size_t)(lut_len > 0 ? lut_len : 0), cells);
   char* base = nullptr;
-  LT_HIP(hipMalloc((void**)&base, total));
-  char* p[19];
-  {
-    size_t off = 0;
-    for (int k = 0; k < 19; ++k) { p[k] = base + off; off += sz[k]; }
-  }
+  LT_HIP(hipMalloc((void**)&base, L.total));
+  char* p[LT_RP_ARRAYS];
+  for (int k = 0; k < LT_RP_ARRAYS; ++k) p[k] = base + L.at[k];
   int rc = LT_OK;
   auto H2D = [&](void* d, const void* h, size_t b) {
     if (rc == LT_OK && h && b && hipMemcpy(d, h, b, hipMemcpyHostToDevice) != hipSuccess) {

@@ -26,6 +26,7 @@
 //     k_sc_resolve one thread per ray: unpack (t, face), write-back (RayTracer.cpp:73-90), reset the cell
 //   (the z-min cells and the two queues are the state of a render in flight: they belong to the scene)
 #include "lt_internal.h"
+#include "lt_devmem.h"
 #include <math.h>
 #include <type_traits>
 #include <stdlib.h>
@@ -1063,27 +1064,15 @@ static int rs_create(const char* who, lt_rayset** out, const float* rays, int n_
   const size_t nbins = (size_t)r->nb_az * r->nb_el + 1;  // + the NaN bin
   const size_t nn = n > 0 ? n : 1;
   const int nb = (int)((nn + LT_SORT_TILE - 1) / LT_SORT_TILE);
-  int rc = LT_OK;
-#define RS_ALLOC(ptr, bytes)                                                  \
-  if (rc == LT_OK && hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) {      \
-    lt_set_error("%s: hipMalloc of %zu bytes failed", who, (size_t)(bytes)); \
-    rc = LT_ERR_NO_MEMORY;                                                    \
-  }
-  RS_ALLOC(r->dirs, nn * sizeof(float4));
-  RS_ALLOC(r->ang, nn * sizeof(float2));
-  RS_ALLOC(r->sdirs, nn * sizeof(float4));
-  RS_ALLOC(r->partial, 2 * 256 * sizeof(float));
-  RS_ALLOC(r->prm, sizeof(rs_params));
-  for (int k = 0; k < 2; ++k) {
-    RS_ALLOC(r->keys[k], nn * sizeof(uint32_t));
-    RS_ALLOC(r->vals[k], nn * sizeof(uint32_t));
-  }
-  RS_ALLOC(r->hist, ((size_t)1024 * nb + 1024) * sizeof(uint32_t));
-  RS_ALLOC(r->bin_start, (nbins + 1) * sizeof(int));
-  RS_ALLOC(r->grid, nbins * sizeof(float4));
-#undef RS_ALLOC
+  const lt_dev_array arrays[] = {
+      {(void**)&r->dirs, nn * sizeof(float4)},         {(void**)&r->ang, nn * sizeof(float2)},
+      {(void**)&r->sdirs, nn * sizeof(float4)},        {(void**)&r->partial, 2 * 256 * sizeof(float)},
+      {(void**)&r->prm, sizeof(rs_params)},            {(void**)&r->keys[0], nn * sizeof(uint32_t)},
+      {(void**)&r->vals[0], nn * sizeof(uint32_t)},    {(void**)&r->keys[1], nn * sizeof(uint32_t)},
+      {(void**)&r->vals[1], nn * sizeof(uint32_t)},    {(void**)&r->hist, ((size_t)1024 * nb + 1024) * sizeof(uint32_t)},
+      {(void**)&r->bin_start, (nbins + 1) * sizeof(int)}, {(void**)&r->grid, nbins * sizeof(float4)}};
+  const int rc = lt_dev_replace(who, lt_wait_none(), arrays);
   if (rc != LT_OK) {
-    rs_free(r);
     free(r);
     return rc;
   }
@@ -1150,29 +1139,13 @@ static int sc_reserve(lt_scene* s, int n_faces, int n_rays, hipStream_t stream) 
     LT_HIP(hipMemsetAsync(s->sc_large_count, 0, 4 * sizeof(int), stream));
   }
   if (n_rays > s->sc_cap_cells) {
-    if (s->sc_cell) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(s->sc_cell);
-      s->sc_cell = nullptr;
-      s->sc_cap_cells = 0;
-    }
-    LT_HIP(hipMalloc((void**)&s->sc_cell, (size_t)n_rays * sizeof(unsigned long long)));
-    s->sc_cap_cells = n_rays;
+    LT_CHECK(lt_dev_grow("lt_scene_render", lt_wait_device(), &s->sc_cell, &s->sc_cap_cells, (size_t)n_rays, (size_t)n_rays));
     LT_HIP(hipMemsetAsync(s->sc_cell, 0xFF, (size_t)n_rays * sizeof(unsigned long long), stream));
   }
   if (n_faces > s->sc_cap_queue) {
-    if (s->sc_large || s->sc_slices) {
-      LT_HIP(hipDeviceSynchronize());
-      (void)hipFree(s->sc_large);
-      (void)hipFree(s->sc_slices);
-      s->sc_large = nullptr;
-      s->sc_slices = nullptr;
-      s->sc_cap_queue = 0;
-    }
-    const size_t cap = (size_t)n_faces + n_faces / 4 + 1024;
-    LT_HIP(hipMalloc((void**)&s->sc_large, cap * sizeof(int)));
-    LT_HIP(hipMalloc((void**)&s->sc_slices, cap * sizeof(int2)));
-    s->sc_cap_queue = (int)cap;
+    const size_t cap = lt_headroom((size_t)n_faces);
+    const lt_dev_array queues[] = {{(void**)&s->sc_large, cap * sizeof(int)}, {(void**)&s->sc_slices, cap * sizeof(int2)}};
+    LT_CHECK(lt_dev_replace("lt_scene_render", lt_wait_device(), &s->sc_cap_queue, (int)cap, queues));
   }
   return LT_OK;
 }

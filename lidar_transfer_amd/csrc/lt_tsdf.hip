@@ -31,6 +31,7 @@
 // The one-thread-per-voxel restatement of the reference kernel is test infrastructure (oracle/lt_tsdf_dense.hip,
 // not in this library): the A/B partner of the kernels below -- bit-identical volumes, tests/test_tsdf_gpu.py.
 #include "lt_internal.h"
+#include "lt_devmem.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1543,16 +1544,11 @@ static tsdf_wedge tsdf_wedge_of(const lt_tsdf* t) {  // (after tsdf_pix_tables)
   return {t->wd_px, t->wd_ent, t->wd_key, t->wd_rho_bits, t->wd_qscale, t->rowtab, 1.0f / t->voxel_size};
 }
 
-// a per-call device buffer of `cap` elements that must hold `need`: re-allocated with `alloc` elements when it does not.
-// (A growth event, not steady state: the device is synchronised before the old buffer goes, as hipFree would anyway.)
+// a per-call device buffer of *cap elements that must hold `need`: replaced by one of `alloc` elements when it does not.
+// (A growth event, not steady state: the device is synchronised before the old buffer goes.)
 template <class T, class N>
-static int tsdf_grow(T*& buf, N& cap, size_t need, size_t alloc) {
-  if (need <= (size_t)cap) return LT_OK;
-  if (buf) { LT_HIP(hipDeviceSynchronize()); (void)hipFree(buf); buf = nullptr; }
-  cap = 0;
-  LT_HIP(hipMalloc((void**)&buf, alloc * sizeof(T)));
-  cap = (N)alloc;
-  return LT_OK;
+static int tsdf_reserve(T** buf, N* cap, size_t need, size_t alloc) {
+  return lt_dev_grow("lt_tsdf_integrate_dev", lt_wait_device(), buf, cap, need, alloc);
 }
 
 static int tsdf_full_reset(lt_tsdf* t, hipStream_t stream) {
@@ -1636,14 +1632,16 @@ extern "C" int lt_tsdf_create(lt_tsdf** out, const double* vol_bnds, double voxe
   }
   t->weight = t->tsdf + 1; t->color = t->tsdf + 2; t->rem = t->tsdf + 3;  // (the fields of voxel 0; stride 4)
   const size_t n_cols = (size_t)t->dim[0] * t->dim[1];
-  if (hipMalloc((void**)&t->col_epoch, n_cols * sizeof(unsigned)) != hipSuccess ||
-      hipMalloc((void**)&t->colinfo, (3 * n_cols + (n_cols + 63) / 64 + 64) * sizeof(int)) != hipSuccess ||  // + one flag per chunk, colz, colrho2
-      hipMalloc((void**)&t->col_zw, 2 * n_cols * sizeof(unsigned)) != hipSuccess ||
-      hipMalloc((void**)&t->chunk_epoch, ((n_cols + 63) / 64) * sizeof(unsigned)) != hipSuccess ||
-      hipMalloc((void**)&t->bits, n_cols * ((t->dim[2] + 63) / 64) * sizeof(unsigned long long)) != hipSuccess) {
-    lt_set_error("lt_tsdf_create: hipMalloc of the column tables failed");
+  const lt_dev_array columns[] = {
+      {(void**)&t->col_epoch, n_cols * sizeof(unsigned)},
+      {(void**)&t->colinfo, (3 * n_cols + (n_cols + 63) / 64 + 64) * sizeof(int)},  // + one flag per chunk, colz, colrho2
+      {(void**)&t->col_zw, 2 * n_cols * sizeof(unsigned)},
+      {(void**)&t->chunk_epoch, ((n_cols + 63) / 64) * sizeof(unsigned)},
+      {(void**)&t->bits, n_cols * ((t->dim[2] + 63) / 64) * sizeof(unsigned long long)}};
+  const int rc_cols = lt_dev_replace("lt_tsdf_create (column tables)", lt_wait_none(), columns);
+  if (rc_cols != LT_OK) {
     lt_tsdf_destroy(t);
-    return LT_ERR_NO_MEMORY;
+    return rc_cols;
   }
   const int rc = tsdf_full_reset(t, nullptr);
   if (rc != LT_OK) {
@@ -1663,32 +1661,15 @@ void lt_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, int n, 
 // sort buffers); rebuilt when an integrate comes with another image width
 static int tsdf_wedge_build(lt_tsdf* t, int im_w, int rho_bits, hipStream_t stream) {
   const int n = t->dim[0] * t->dim[1];
-  if (!t->wd_px || !t->wd_ent || !t->wd_key) {
-    // all three or none: an allocation that fails half way must not leave a non-NULL wd_px behind (the next integrate
-    // would skip this block and launch the table kernels on NULL tables)
-    auto drop = [&]() {
-      if (t->wd_px) (void)hipFree(t->wd_px);
-      if (t->wd_ent) (void)hipFree(t->wd_ent);
-      if (t->wd_key) (void)hipFree(t->wd_key);
-      t->wd_px = nullptr; t->wd_ent = nullptr; t->wd_key = nullptr;
-    };
-    if (t->wd_px || t->wd_ent || t->wd_key) LT_HIP(hipStreamSynchronize(stream));
-    drop();
-    t->wd_w = 0;
-    bool ok = hipMalloc((void**)&t->wd_px, (size_t)n * sizeof(int)) == hipSuccess &&
-              hipMalloc((void**)&t->wd_ent, (size_t)n * sizeof(int2)) == hipSuccess &&
-              hipMalloc((void**)&t->wd_key, (size_t)n * sizeof(unsigned)) == hipSuccess;
-    if (!ok) {
-      drop();
-      (void)hipGetLastError();
-      lt_set_error("lt_tsdf: out of device memory for the wedge table (%d columns)", n);
-      return LT_ERR_NO_MEMORY;
-    }
+  // wd_w is the capacity of both groups: 0 (no table) from here until the table is complete
+  if (!t->wd_px || !t->wd_ent || !t->wd_key) {  // the per-column arrays, all three or none: sized by the volume, kept
+    const lt_dev_array columns[] = {{(void**)&t->wd_px, (size_t)n * sizeof(int)}, {(void**)&t->wd_ent, (size_t)n * sizeof(int2)},
+                                    {(void**)&t->wd_key, (size_t)n * sizeof(unsigned)}};
+    LT_CHECK(lt_dev_replace("lt_tsdf_integrate_dev (wedge table)", lt_wait_stream(stream), &t->wd_w, 0, columns));
   }
-  if (t->wd_start) { LT_HIP(hipStreamSynchronize(stream)); (void)hipFree(t->wd_start); t->wd_start = nullptr; }
-  if (t->wd_qcols) { (void)hipFree(t->wd_qcols); t->wd_qcols = nullptr; }
-  t->wd_w = 0;
-  LT_HIP(hipMalloc((void**)&t->wd_start, (size_t)(im_w + 2) * sizeof(int)));
+  // the arrays sized by the image width; wd_qcols is dropped here and allocated below, once the quirk columns are counted
+  const lt_dev_array per_width[] = {{(void**)&t->wd_start, (size_t)(im_w + 2) * sizeof(int)}, {(void**)&t->wd_qcols, 0}};
+  LT_CHECK(lt_dev_replace("lt_tsdf_integrate_dev (wedge table)", lt_wait_stream(stream), &t->wd_w, 0, per_width));
   // largest horizontal distance of a voxel column from the sensor (the world origin: the kernel's pt_x, pt_y)
   double rmax = 0.0;
   for (int ix = 0; ix < 2; ++ix)
@@ -1765,7 +1746,7 @@ static int tsdf_rowtab(lt_tsdf* t, int im_h, float fu, float fd, hipStream_t str
     tab[r] = make_float4(nextafterf((float)tan(lo), -INFINITY), nextafterf((float)tan(hi), INFINITY),
                          nextafterf((float)cmin, 0.f), nextafterf((float)cmax, 2.f));
   }
-  LT_CHECK(tsdf_grow(t->rowtab, t->rowtab_h, (size_t)im_h, (size_t)im_h));
+  LT_CHECK(tsdf_reserve(&t->rowtab, &t->rowtab_h, (size_t)im_h, (size_t)im_h));
   // (a blocking copy from pageable memory: the vector may go out of scope when this returns)
   LT_HIP(hipMemcpyAsync(t->rowtab, tab.data(), (size_t)im_h * sizeof(float4), hipMemcpyHostToDevice, stream));
   LT_HIP(hipStreamSynchronize(stream));
@@ -1838,7 +1819,7 @@ static int tsdf_integrate_pix(lt_tsdf* t, const float* color_im, const float* de
                               hipStream_t stream) {
   LT_CHECK(tsdf_pix_tables(t, im_h, im_w, rho_bits, F, stream));
   const size_t n_pix = (size_t)im_w * im_h;
-  LT_CHECK(tsdf_grow(t->dct, t->cap_dct, n_pix, n_pix));
+  LT_CHECK(tsdf_reserve(&t->dct, &t->cap_dct, n_pix, n_pix));
   hipLaunchKernelGGL(k_tsdf_dct, dim3((im_h * im_w + 255) / 256), dim3(256), 0, stream, depth_im, color_im, im_h, im_w, t->dct);
   const tsdf_volume Vol = tsdf_vol_of(t);
   const tsdf_view Vw = tsdf_view_of(t, F, im_h, im_w, obs_weight);
@@ -1962,8 +1943,8 @@ extern "C" int lt_tsdf_integrate_dev(lt_tsdf* t, const float* color_im, const fl
   t->n_obs += 1;
   if (use_pix)
     return tsdf_integrate_pix(t, color_im, depth_im, rem_im, im_h, im_w, obs_weight, F, rho_bits, fresh_volume, stream);
-  LT_CHECK(tsdf_grow(t->colmax, t->cap_w, (size_t)im_w, (size_t)im_w));
-  LT_CHECK(tsdf_grow(t->dct, t->cap_dct, (size_t)im_w * im_h, (size_t)im_w * im_h));
+  LT_CHECK(tsdf_reserve(&t->colmax, &t->cap_w, (size_t)im_w, (size_t)im_w));
+  LT_CHECK(tsdf_reserve(&t->dct, &t->cap_dct, (size_t)im_w * im_h, (size_t)im_w * im_h));
   const int n_cols = t->dim[0] * t->dim[1];
   // behind the table: one flag per chunk of 64 columns, then the walks' z ranges and the columns' rho^2
   const size_t n_flags = ((size_t)n_cols + 63) / 64 + 64;
@@ -2032,7 +2013,7 @@ extern "C" int lt_tsdf_integrate_multi_dev(lt_tsdf* t, int n_obs, const float* c
     const int n = n_obs < LT_TSDF_MULTI_MAX ? n_obs : LT_TSDF_MULTI_MAX;
     LT_CHECK(tsdf_pix_tables(t, im_h, im_w, rho_bits, F, stream));
     const size_t n_pix = (size_t)im_h * im_w;
-    LT_CHECK(tsdf_grow(t->obs4, t->cap_obs4, (size_t)n * n_pix, (size_t)LT_TSDF_MULTI_MAX * n_pix));
+    LT_CHECK(tsdf_reserve(&t->obs4, &t->cap_obs4, (size_t)n * n_pix, (size_t)LT_TSDF_MULTI_MAX * n_pix));
     tsdf_obs_ptrs O;
     for (int k = 0; k < LT_TSDF_MULTI_MAX; ++k) {
       const int q = k < n ? k : 0;
