@@ -18,7 +18,7 @@
 // order, starting from its first member's value) and rep, its smallest k; it is detected when c >= min_subrays; the mode
 // chooses among the detected; range = float32(St / c), endrem = float32(Srem / S), fraction = float32((double)c / S),
 // label and tri are rep's, end point j = float32(o[j] + h[j] * (double)range).  No detected echo, or !(dd > 0) of the
-// central ray: the miss of LT_TRACE_WRITE_MISSES.
+// central ray: the miss, as lt_scan_write_miss (lt_scanimg.h) writes it.
 // k_echo_resolve_dual (a dual-return sensor) is the same body with a SECOND echo per cell: chosen by second_mode among the
 // detected echoes other than the primary -- first: the earliest of the rest, last: the latest, strongest: the largest Srem,
 // a tie to the larger c, then to the earlier --, written with the primary's expressions on its own c, St, Srem and rep into
@@ -28,6 +28,7 @@
 #include <math.h>
 
 #include "lt_internal.h"
+#include "lt_scanimg.h"
 
 struct lt_subray_args {
   double off[2 * LT_ECHO_MAX_SUBRAYS];
@@ -141,11 +142,7 @@ static __device__ __forceinline__ void lt_echo_walk_slots(lt_echo_walk& w, const
 
 // the second return's outputs and its rule (the dual resolve only)
 struct lt_echo_second {
-  float* endpoints;
-  int* endcolors;
-  float* range;
-  float* endrem;
-  int* tri;
+  lt_scan_images images;
   float* fraction;
   unsigned mode;
 };
@@ -243,21 +240,10 @@ static __device__ __forceinline__ void lt_echo_body(const lt_echo_args& A, const
       }
     }
   }
-  if (endpoints) { endpoints[3 * (size_t)i] = px; endpoints[3 * (size_t)i + 1] = py; endpoints[3 * (size_t)i + 2] = pz; }
-  if (endcolors) endcolors[i] = lab;
-  range[i] = rf;
-  if (endrem) endrem[i] = er;
-  tri[i] = tr;
+  // (a set without an echo holds the values lt_scan_write_miss writes, and fraction 0)
+  lt_scan_write_echo({endpoints, endcolors, range, endrem, tri}, fraction, (size_t)i, px, py, pz, lab, rf, er, tr, fr);
   if (n_echoes) n_echoes[i] = (unsigned char)w.n_det;
-  if (fraction) fraction[i] = fr;
-  if constexpr (DUAL) {
-    if (B.endpoints) { B.endpoints[3 * (size_t)i] = qx; B.endpoints[3 * (size_t)i + 1] = qy; B.endpoints[3 * (size_t)i + 2] = qz; }
-    if (B.endcolors) B.endcolors[i] = lab2;
-    B.range[i] = rf2;
-    if (B.endrem) B.endrem[i] = er2;
-    B.tri[i] = tr2;
-    if (B.fraction) B.fraction[i] = fr2;
-  }
+  if constexpr (DUAL) lt_scan_write_echo(B.images, B.fraction, (size_t)i, qx, qy, qz, lab2, rf2, er2, tr2, fr2);
 }
 
 __global__ __launch_bounds__(256) void k_echo_resolve(const lt_echo_args A, const float* __restrict__ rays,
@@ -327,7 +313,7 @@ static int lt_echo_resolve_check(const char* who, const float* rays, const float
                  "tri are mandatory)", who, n);
     return LT_ERR_INVALID_ARG;
   }
-  if (!(origin[0] - origin[0] == 0.f && origin[1] - origin[1] == 0.f && origin[2] - origin[2] == 0.f)) {
+  if (!lt_finite3(origin)) {
     lt_set_error("%s: invalid origin (three finite numbers; %g %g %g)", who, (double)origin[0], (double)origin[1],
                  (double)origin[2]);
     return LT_ERR_INVALID_ARG;
@@ -387,9 +373,7 @@ extern "C" int lt_echo_resolve_dual_dev(const float* rays, const float* origin, 
   }
   if (n == 0) return LT_OK;
   const lt_echo_args A = lt_echo_args_of(origin, n, model);
-  lt_echo_second B;
-  B.endpoints = endpoints2; B.endcolors = endcolors2; B.range = range2; B.endrem = endrem2; B.tri = tri2;
-  B.fraction = fraction2; B.mode = second_mode;
+  const lt_echo_second B = {{endpoints2, endcolors2, range2, endrem2, tri2}, fraction2, second_mode};
   hipLaunchKernelGGL(k_echo_resolve_dual, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, A, B, rays, sub_range,
                      sub_label, sub_rem, sub_tri, endpoints, endcolors, range, endrem, tri, n_echoes, fraction);
   LT_HIP(hipGetLastError());

@@ -15,6 +15,7 @@
 //                              the reference's pre-zeroed arrays hold afterwards).
 #include "lt_internal.h"
 #include "lt_layouts.h"
+#include "lt_scanimg.h"
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -74,7 +75,7 @@ thread_local ctrace_ctx t_ctx;
 
 static int ctrace_thread(const float* rays, const float* origin, const float* verts, const int* faces,
                          const int* colors, const float* rem, int n_rays, int n_verts, int n_faces, int height,
-                         float* endpoints, int* endcolors, float* range, float* endrem, int* tri, lt_stats* stats) {
+                         const lt_scan_images& out, lt_stats* stats) {
   ctrace_ctx& c = t_ctx;
   int dev = 0;
   LT_HIP(hipGetDevice(&dev));
@@ -103,11 +104,7 @@ static int ctrace_thread(const float* rays, const float* origin, const float* ve
   const lt_ctrace_io_layout L = lt_ctrace_io_layout_of(R);
   LT_CHECK(lt_dev_grow("lt_ctrace", lt_wait_stream(stream), &c.io, &c.io_bytes, L.total, L.total));
   float* d_rays = (float*)(c.io + L.rays);
-  float* d_end = (float*)(c.io + L.endpoints);
-  int* d_col = (int*)(c.io + L.endcolors);
-  float* d_range = (float*)(c.io + L.range);
-  float* d_rem = (float*)(c.io + L.endrem);
-  int* d_tri = (int*)(c.io + L.tri);
+  const lt_scan_images d_out = lt_scan_images_wanted(lt_scan_images_at(c.io, L), out);  // (the colour image: always [R,3])
   const unsigned norm_flag = lt_env_norm_flag();
   const char* sg = getenv("LIDARHIP_STRATEGY");
   const bool lbvh = sg && strcmp(sg, "lbvh") == 0;
@@ -127,11 +124,10 @@ static int ctrace_thread(const float* rays, const float* origin, const float* ve
   LT_CHECK(lt_scene_set_mesh_host(s, verts, faces, colors, rem, n_verts, n_faces, stream));
   if (R > 0) {
     // outputs are written only for hits (RayTracer.cpp:73): start from the caller's contents
-    if (endpoints) LT_HIP(hipMemcpyAsync(d_end, endpoints, R * 12, hipMemcpyHostToDevice, stream));
-    if (endcolors) LT_HIP(hipMemcpyAsync(d_col, endcolors, R * 12, hipMemcpyHostToDevice, stream));
-    if (range) LT_HIP(hipMemcpyAsync(d_range, range, R * 4, hipMemcpyHostToDevice, stream));
-    if (endrem) LT_HIP(hipMemcpyAsync(d_rem, endrem, R * 4, hipMemcpyHostToDevice, stream));
-    if (tri) LT_HIP(hipMemcpyAsync(d_tri, tri, R * 4, hipMemcpyHostToDevice, stream));
+    for (int k = 0; k < LT_SCAN_IMAGES; ++k) {
+      const lt_scan_copy im = lt_scan_copy_of(out, d_out, k, R, false);
+      if (im.host) LT_HIP(hipMemcpyAsync(im.dev, im.host, im.bytes, hipMemcpyHostToDevice, stream));
+    }
   }
   lt_stats st;
   memset(&st, 0, sizeof(st));
@@ -139,10 +135,8 @@ static int ctrace_thread(const float* rays, const float* origin, const float* ve
     // LIDARHIP_STRATEGY=lbvh: build the linear BVH and traverse it; default: single-origin triangle scatter
     // (lt_scatter.hip) -- both produce identical images
     LT_CHECK(lt_build_launch(s, stream, stats ? &st : nullptr));
-    LT_CHECK(lt_trace_launch(s, d_rays, origin, (int)R, height, endpoints ? d_end : nullptr,
-                             endcolors ? d_col : nullptr, range ? d_range : nullptr, endrem ? d_rem : nullptr,
-                             tri ? d_tri : nullptr, (stats ? LT_TRACE_COUNT : 0u) | norm_flag, stream,
-                             stats ? &st : nullptr));
+    LT_CHECK(lt_trace_launch(s, d_rays, origin, (int)R, height, d_out.endpoints, d_out.endcolors, d_out.range, d_out.endrem,
+                             d_out.tri, (stats ? LT_TRACE_COUNT : 0u) | norm_flag, stream, stats ? &st : nullptr));
   } else {
     if (maybe_same && R > 0) {
       LT_HIP(hipStreamSynchronize(stream));  // (the uploads above are done by now anyway when the memory is pageable)
@@ -159,16 +153,14 @@ static int ctrace_thread(const float* rays, const float* origin, const float* ve
       c.rs_height = height;
       c.rs_norm = norm_flag;
     }
-    LT_CHECK(lt_scene_render_dev(s, c.rs, origin, endpoints ? d_end : nullptr, endcolors ? d_col : nullptr,
-                                 range ? d_range : nullptr, endrem ? d_rem : nullptr, tri ? d_tri : nullptr,
+    LT_CHECK(lt_scene_render_dev(s, c.rs, origin, d_out.endpoints, d_out.endcolors, d_out.range, d_out.endrem, d_out.tri,
                                  (stats ? LT_TRACE_COUNT : 0u), stream, stats ? &st : nullptr));
   }
   if (R > 0) {
-    if (endpoints) LT_HIP(hipMemcpyAsync(endpoints, d_end, R * 12, hipMemcpyDeviceToHost, stream));
-    if (endcolors) LT_HIP(hipMemcpyAsync(endcolors, d_col, R * 12, hipMemcpyDeviceToHost, stream));
-    if (range) LT_HIP(hipMemcpyAsync(range, d_range, R * 4, hipMemcpyDeviceToHost, stream));
-    if (endrem) LT_HIP(hipMemcpyAsync(endrem, d_rem, R * 4, hipMemcpyDeviceToHost, stream));
-    if (tri) LT_HIP(hipMemcpyAsync(tri, d_tri, R * 4, hipMemcpyDeviceToHost, stream));
+    for (int k = 0; k < LT_SCAN_IMAGES; ++k) {
+      const lt_scan_copy im = lt_scan_copy_of(out, d_out, k, R, false);
+      if (im.host) LT_HIP(hipMemcpyAsync(im.host, im.dev, im.bytes, hipMemcpyDeviceToHost, stream));
+    }
   }
   LT_HIP(hipStreamSynchronize(stream));
   if (stats) *stats = st;
@@ -184,8 +176,8 @@ extern "C" int lt_ctrace_ex(const float* rays, const float* origin, const float*
     return LT_ERR_INVALID_ARG;
   }
   LT_CHECK(lt_check_mesh_args("lt_ctrace", verts, faces, colors, rem, n_verts, n_faces));
-  const int rc = ctrace_thread(rays, origin, verts, faces, colors, rem, n_rays, n_verts, n_faces, height, endpoints,
-                               endcolors, range, endrem, tri, stats);
+  const int rc = ctrace_thread(rays, origin, verts, faces, colors, rem, n_rays, n_verts, n_faces, height,
+                               {endpoints, endcolors, range, endrem, tri}, stats);
   // a failure half way may leave copies from / to the caller's arrays queued: they must not outlive the call
   if (rc != LT_OK && t_ctx.stream) (void)hipStreamSynchronize(t_ctx.stream);
   return rc;
@@ -222,7 +214,7 @@ struct hp_job {
   float origin[3];
   const float* verts; const int* faces; const void* colors; const float* rem;
   int colors_u8, n_verts, n_faces;
-  float* endpoints; int* endcolors; float* range; float* endrem; int* tri;
+  lt_scan_images images;  // the caller's arrays
   const void* pinned[9];  // ranges registered for this job (unregistered when it is collected)
   int n_pinned;
   int direct_out;         // the downloads went straight into the caller's arrays
@@ -369,42 +361,34 @@ static int hp_launch(lt_hostpipe* p, hp_slot& sl) {
   LT_CHECK(lt_scene_set_mesh_dev(sl.scene, M.verts, M.faces, M.colors, M.rem, j.n_verts, j.n_faces));
   const lt_hp_out_layout& O = p->out;
   char* o = sl.out_dev;
-  float* d_end = (float*)(o + O.endpoints);
-  int* d_col = (int*)(o + O.endcolors);
-  float* d_range = (float*)(o + O.range);
-  float* d_rem = (float*)(o + O.endrem);
-  int* d_tri = (int*)(o + O.tri);
-  LT_CHECK(lt_scene_render_dev(sl.scene, p->rs, j.origin, j.endpoints ? d_end : nullptr, j.endcolors ? d_col : nullptr,
-                               j.range ? d_range : nullptr, j.endrem ? d_rem : nullptr, j.tri ? d_tri : nullptr,
-                               p->flags | LT_TRACE_WRITE_MISSES, p->s_run, nullptr));
+  const lt_scan_images d_out = lt_scan_images_wanted(lt_scan_images_at(o, O), j.images);
+  LT_CHECK(lt_scene_render_dev(sl.scene, p->rs, j.origin, d_out.endpoints, d_out.endcolors, d_out.range, d_out.endrem,
+                               d_out.tri, p->flags | LT_TRACE_WRITE_MISSES, p->s_run, nullptr));
   LT_HIP(hipEventRecord(sl.ev_run, p->s_run));
   // download into pinned staging (asynchronous); lt_hostpipe_wait hands it to the caller's arrays
   LT_HIP(hipStreamWaitEvent(p->s_down, sl.ev_run, 0));
   const size_t R = (size_t)p->n_rays;
-  const size_t ncol = (p->flags & LT_TRACE_LABEL_IMAGE) ? R * 4 : R * 12;
+  const bool label = (p->flags & LT_TRACE_LABEL_IMAGE) != 0;
   char* h = sl.out_pin;
   // straight into the caller's arrays when all of them can be registered, else into pinned staging
   // (lt_hostpipe_wait copies from there)
   j.direct_out = 0;
   if (p->use_register && R > 0) {
     bool all = true;
-    if (j.endpoints) all = all && hp_pin(p, j, j.endpoints, R * 12);
-    if (j.endcolors) all = all && hp_pin(p, j, j.endcolors, ncol);
-    if (j.range) all = all && hp_pin(p, j, j.range, R * 4);
-    if (j.endrem) all = all && hp_pin(p, j, j.endrem, R * 4);
-    if (j.tri) all = all && hp_pin(p, j, j.tri, R * 4);
+    for (int k = 0; k < LT_SCAN_IMAGES; ++k) {
+      const lt_scan_copy im = lt_scan_copy_of(j.images, d_out, k, R, label);
+      if (im.host) all = all && hp_pin(p, j, im.host, im.bytes);
+    }
     j.direct_out = all ? 1 : 0;
   }
   // staged: the five images are one block on the device and in the staging buffer -> ONE transfer
   if (R > 0 && !j.direct_out) {
     LT_HIP(hipMemcpyAsync(h, o, O.images, hipMemcpyDeviceToHost, p->s_down));
-  } else if (R > 0) {
-    const bool d = j.direct_out != 0;
-    if (j.endpoints) LT_HIP(hipMemcpyAsync(d ? (void*)j.endpoints : (void*)(h + O.endpoints), d_end, R * 12, hipMemcpyDeviceToHost, p->s_down));
-    if (j.endcolors) LT_HIP(hipMemcpyAsync(d ? (void*)j.endcolors : (void*)(h + O.endcolors), d_col, ncol, hipMemcpyDeviceToHost, p->s_down));
-    if (j.range) LT_HIP(hipMemcpyAsync(d ? (void*)j.range : (void*)(h + O.range), d_range, R * 4, hipMemcpyDeviceToHost, p->s_down));
-    if (j.endrem) LT_HIP(hipMemcpyAsync(d ? (void*)j.endrem : (void*)(h + O.endrem), d_rem, R * 4, hipMemcpyDeviceToHost, p->s_down));
-    if (j.tri) LT_HIP(hipMemcpyAsync(d ? (void*)j.tri : (void*)(h + O.tri), d_tri, R * 4, hipMemcpyDeviceToHost, p->s_down));
+  } else if (R > 0) {  // direct_out: straight into the caller's arrays
+    for (int k = 0; k < LT_SCAN_IMAGES; ++k) {
+      const lt_scan_copy im = lt_scan_copy_of(j.images, d_out, k, R, label);
+      if (im.host) LT_HIP(hipMemcpyAsync(im.host, im.dev, im.bytes, hipMemcpyDeviceToHost, p->s_down));
+    }
   }
   LT_HIP(hipEventRecord(sl.ev_done, p->s_down));
   p->t_issue += hp_now() - t0;
@@ -614,15 +598,11 @@ static int hp_collect(lt_hostpipe* p, hp_slot& sl) {
   }
   static const bool no_copy = getenv("LIDARHIP_HOSTPIPE_DEBUG_NOCOPY") != nullptr;
   if (rc == LT_OK && !sl.job.direct_out && !no_copy) {
-    const hp_job& j = sl.job;
-    const size_t R = (size_t)p->n_rays;
-    const size_t ncol = (p->flags & LT_TRACE_LABEL_IMAGE) ? R * 4 : R * 12;
-    const char* h = sl.out_pin;
-    if (j.endpoints) memcpy(j.endpoints, h + p->out.endpoints, R * 12);
-    if (j.endcolors) memcpy(j.endcolors, h + p->out.endcolors, ncol);
-    if (j.range) memcpy(j.range, h + p->out.range, R * 4);
-    if (j.endrem) memcpy(j.endrem, h + p->out.endrem, R * 4);
-    if (j.tri) memcpy(j.tri, h + p->out.tri, R * 4);
+    const lt_scan_images staged = lt_scan_images_at(sl.out_pin, p->out);
+    for (int k = 0; k < LT_SCAN_IMAGES; ++k) {
+      const lt_scan_copy im = lt_scan_copy_of(sl.job.images, staged, k, (size_t)p->n_rays, (p->flags & LT_TRACE_LABEL_IMAGE) != 0);
+      if (im.host) memcpy(im.host, im.dev, im.bytes);
+    }
   }
   if (rc != LT_OK) {
     for (int u = 0; u < p->n_up; ++u) (void)hipStreamSynchronize(p->s_up[u]);
@@ -680,7 +660,7 @@ extern "C" int lt_hostpipe_submit(lt_hostpipe* p, const float* origin, const flo
     j.verts = verts; j.faces = faces; j.colors = colors; j.rem = rem;
     j.colors_u8 = colors_are_u8 ? 1 : 0;
     j.n_verts = n_verts; j.n_faces = n_faces;
-    j.endpoints = endpoints; j.endcolors = endcolors; j.range = range; j.endrem = endrem; j.tri = tri;
+    j.images = {endpoints, endcolors, range, endrem, tri};
     j.n_pinned = 0;
     j.direct_out = 0;
     sl.state = 1;

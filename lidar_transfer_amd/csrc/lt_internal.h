@@ -180,6 +180,16 @@ struct lt_tsdf {
 #define LT_TRACE_DEBUG_TIMES 0x8000u  // internal trace flag: per-wave wall-clock stamps into the counters area
 
 int lt_build_launch(lt_scene* s, hipStream_t stream, lt_stats* stats);
+// The five images of a rendered scan, wherever they are carried: a kernel's arguments, a batch job, a host pipe's job.  A null
+// member: the image is not wanted.  endcolors is [n_rays, 3], or [n_rays] with LT_TRACE_LABEL_IMAGE.  What a kernel writes
+// into them for a hit and for a miss is lt_scanimg.h.
+struct lt_scan_images {
+  float* endpoints;
+  int* endcolors;
+  float* range;
+  float* endrem;
+  int* tri;
+};
 int lt_trace_launch(lt_scene* s, const float* rays, const float* origin, int n_rays, int height,
                     float* endpoints, int* endcolors, float* range, float* endrem, int* tri,
                     unsigned flags, hipStream_t stream, lt_stats* stats);

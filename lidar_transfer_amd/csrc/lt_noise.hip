@@ -3,21 +3,14 @@
 // range of a return is jittered along its ray and reported on a grid, its end point follows, its remission is jittered,
 // clamped and reported on L levels; a return whose measured range leaves the sensor's gate is lost.
 #include "lt_internal.h"
-
-// mix(x) of lidarhip.h (uint32, products wrap)
-static __host__ __device__ __forceinline__ unsigned lt_noise_mix(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
+#include "lt_scanimg.h"
 
 // z of lidarhip.h: twelve 16-bit uniforms, the halves of mix(g + first) .. mix(g + first + 5), summed as integers
 static __device__ __forceinline__ double lt_noise_draw(unsigned g, unsigned first) {
   int S = 0;
 #pragma unroll
   for (unsigned k = 0; k < 6; ++k) {
-    const unsigned w = lt_noise_mix(g + first + k);
+    const unsigned w = lt_mix32(g + first + k);
     S += (int)(w & 0xffffu) + (int)(w >> 16);
   }
   return (double)(S - 393210) / 65536.0;
@@ -51,20 +44,13 @@ __global__ __launch_bounds__(256) void k_noise_model(const lt_noise_args A, floa
   int st = 0;
   float err = 0.f;
   if (t >= 0 && rf > 0.f) {
-    const unsigned g = lt_noise_mix(A.scan_hash + (unsigned)i);
+    const unsigned g = lt_mix32(A.scan_hash + (unsigned)i);
     const double r = (double)rf;
     const double r1 = r + (A.range_sigma + A.range_sigma_rel * r) * lt_noise_draw(g, 1u);
     const double r2 = A.range_resolution > 0.0 ? rint(r1 / A.range_resolution) * A.range_resolution : r1;
     if (!(r2 > 0.0) || r2 < A.min_range || r2 > A.max_range) {
-      st = 2;  // the miss of LT_TRACE_WRITE_MISSES
-      if (endpoints) { endpoints[3 * (size_t)i] = 0.f; endpoints[3 * (size_t)i + 1] = 0.f; endpoints[3 * (size_t)i + 2] = 0.f; }
-      if (endcolors) {
-        if (A.label) endcolors[i] = 0;
-        else { endcolors[3 * (size_t)i] = 0; endcolors[3 * (size_t)i + 1] = 0; endcolors[3 * (size_t)i + 2] = 0; }
-      }
-      if (endrem) endrem[i] = 0.f;
-      range[i] = 0.f;
-      tri[i] = -1;
+      st = 2;  // the return is lost: the cell becomes a miss
+      lt_scan_write_miss({endpoints, endcolors, range, endrem, tri}, (size_t)i, A.label != 0);
     } else {
       st = 1;
       err = (float)(r2 - r);
@@ -96,7 +82,7 @@ extern "C" int lt_noise_model_dev(const float* origin, int n, const lt_noise_mod
   }
   // (written so that a NaN fails)
   const double inf = HUGE_VAL;
-  if (!(origin[0] - origin[0] == 0.f && origin[1] - origin[1] == 0.f && origin[2] - origin[2] == 0.f)) {
+  if (!lt_finite3(origin)) {
     lt_set_error("lt_noise_model_dev: invalid origin (three finite numbers; %g %g %g)", (double)origin[0], (double)origin[1],
                  (double)origin[2]);
     return LT_ERR_INVALID_ARG;
@@ -118,7 +104,7 @@ extern "C" int lt_noise_model_dev(const float* origin, int n, const lt_noise_mod
   A.min_range = model->min_range; A.max_range = model->max_range;
   A.levels_m1 = model->remission_levels ? (double)(model->remission_levels - 1u) : 0.0;
   A.ox = (double)origin[0]; A.oy = (double)origin[1]; A.oz = (double)origin[2];
-  A.scan_hash = lt_noise_mix(lt_noise_mix(model->seed ^ 0x6e6f6973u) + scan);
+  A.scan_hash = lt_mix32(lt_mix32(model->seed ^ 0x6e6f6973u) + scan);
   A.label = (trace_flags & LT_TRACE_LABEL_IMAGE) != 0;
   A.n = n;
   hipLaunchKernelGGL(k_noise_model, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, A, endpoints, endcolors, range,

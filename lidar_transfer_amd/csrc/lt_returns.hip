@@ -3,14 +3,7 @@
 // range gate, seen too close to edge-on, or dropped at random becomes a miss; the remission of one that stands may fall with
 // the cosine of the incidence angle.
 #include "lt_internal.h"
-
-// mix(x) of lidarhip.h (uint32, products wrap)
-static __host__ __device__ __forceinline__ unsigned lt_ret_mix(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
+#include "lt_scanimg.h"
 
 struct lt_ret_args {
   double min_range, max_range, min_cos;
@@ -72,18 +65,11 @@ __global__ __launch_bounds__(256) void k_return_model(const lt_ret_args A, const
     if (rd < A.min_range) code = 2;
     else if (rd > A.max_range) code = 3;
     else if (c < A.min_cos) code = 4;
-    else if (lt_ret_mix(A.scan_hash + (unsigned)i) < A.drop_threshold) code = 5;
+    else if (lt_mix32(A.scan_hash + (unsigned)i) < A.drop_threshold) code = 5;
     else code = 0;
   }
-  if (code >= 2) {  // the miss of LT_TRACE_WRITE_MISSES
-    if (endpoints) { endpoints[3 * (size_t)i] = 0.f; endpoints[3 * (size_t)i + 1] = 0.f; endpoints[3 * (size_t)i + 2] = 0.f; }
-    if (endcolors) {
-      if (A.label) endcolors[i] = 0;
-      else { endcolors[3 * (size_t)i] = 0; endcolors[3 * (size_t)i + 1] = 0; endcolors[3 * (size_t)i + 2] = 0; }
-    }
-    if (endrem) endrem[i] = 0.f;
-    range[i] = 0.f;
-    tri[i] = -1;
+  if (code >= 2) {  // the return is lost: the cell becomes a miss
+    lt_scan_write_miss({endpoints, endcolors, range, endrem, tri}, (size_t)i, A.label != 0);
   } else if (code == 0 && A.lambert && endrem) {
     endrem[i] = (float)((double)er * c);
   }
@@ -116,7 +102,7 @@ extern "C" int lt_return_model_dev(lt_scene* s, const float* rays, int n_rays, c
   lt_ret_args A;
   A.min_range = model->min_range; A.max_range = model->max_range; A.min_cos = model->min_cos;
   A.drop_threshold = model->drop_threshold;
-  A.scan_hash = lt_ret_mix(lt_ret_mix(model->seed) + scan);
+  A.scan_hash = lt_mix32(lt_mix32(model->seed) + scan);
   A.lambert = (model->flags & LT_RETURN_LAMBERT) != 0;
   A.label = (trace_flags & LT_TRACE_LABEL_IMAGE) != 0;
   A.n = n_rays; A.n_faces = s->n_faces; A.n_verts = s->n_verts;

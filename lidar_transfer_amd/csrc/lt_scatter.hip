@@ -27,6 +27,7 @@
 //   (the z-min cells and the two queues are the state of a render in flight: they belong to the scene)
 #include "lt_internal.h"
 #include "lt_devmem.h"
+#include "lt_scanimg.h"
 #include <math.h>
 #include <type_traits>
 #include <stdlib.h>
@@ -766,7 +767,7 @@ struct sc_job {
   rs_params P; const float4* grid; const float4* sdirs; const float4* dirs;  // its ray set (P: by value, see lt_rayset)
   unsigned long long* cell; int* large; int* large_count; int2* slices;
   unsigned* flags; unsigned long long* counters;
-  float* endpoints; int* endcolors; float* range; float* endrem; int* tri;  // its images
+  lt_scan_images images;
   float ox, oy, oz;
   int n_verts, n_faces, n_rays, cap_slices;
   unsigned out_flags;
@@ -923,11 +924,7 @@ __global__ __launch_bounds__(256) void k_sc_resolve(const sc_batch B) {
   const int ray = ((int)blockIdx.x - B.resolve_block0[j]) * 256 + threadIdx.x;
   unsigned long long* __restrict__ cell = J.cell;
   const int* __restrict__ faces = J.faces;
-  float* __restrict__ endpoints = J.endpoints;
-  int* __restrict__ endcolors = J.endcolors;
-  float* __restrict__ range = J.range;
-  float* __restrict__ endrem = J.endrem;
-  int* __restrict__ tri_out = J.tri;
+  const lt_scan_images images = J.images;
   const unsigned flags = J.out_flags;
   if (ray == 0) { J.large_count[0] = 0; J.large_count[1] = 0; }
   bool hit = false;
@@ -939,46 +936,11 @@ __global__ __launch_bounds__(256) void k_sc_resolve(const sc_batch B) {
     if (hit) {
       const float t = __uint_as_float((unsigned)(key >> 32));
       const int face = (int)(unsigned)(key & 0xFFFFFFFFull);
-      const int i0 = faces[3 * (size_t)face], i1 = faces[3 * (size_t)face + 1], i2 = faces[3 * (size_t)face + 2];
-      // everything the images need is loaded BEFORE the first store: with the stores in between the compiler waited for
-      // each attribute in turn -- key, face, colour, remission were four dependent round trips, three are needed
-      const int* __restrict__ colors = J.colors;
-      const float* __restrict__ rem = J.rem;
-      const bool label = (flags & LT_TRACE_LABEL_IMAGE) != 0;  // deform's unpack label_image = ray_colors[..., 2], laserscan.py:912
-      int c0 = 0, c1 = 0, c2 = 0;
-      float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-      if (endcolors) {
-        c2 = colors[3 * (size_t)i0 + 2];
-        if (!label) { c0 = colors[3 * (size_t)i0]; c1 = colors[3 * (size_t)i0 + 1]; }
-      }
-      if (endrem) { r0 = rem[i0]; r1 = rem[i1]; r2 = rem[i2]; }
-      if (endpoints) {
-        endpoints[3 * (size_t)ray] = J.ox + d.x * t;
-        endpoints[3 * (size_t)ray + 1] = J.oy + d.y * t;
-        endpoints[3 * (size_t)ray + 2] = J.oz + d.z * t;
-      }
-      if (endcolors) {
-        if (label) {
-          endcolors[ray] = (int)(float)c2;
-        } else {
-          endcolors[3 * (size_t)ray] = (int)(float)c0;
-          endcolors[3 * (size_t)ray + 1] = (int)(float)c1;
-          endcolors[3 * (size_t)ray + 2] = (int)(float)c2;
-        }
-      }
-      if (endrem) endrem[ray] = ((r0 + r1) + r2) / 3.0f;
-      if (range) range[ray] = t;
-      if (tri_out) tri_out[ray] = face;
-    } else if (flags & LT_TRACE_WRITE_MISSES) {
-      if (endpoints) { endpoints[3 * (size_t)ray] = 0.f; endpoints[3 * (size_t)ray + 1] = 0.f; endpoints[3 * (size_t)ray + 2] = 0.f; }
-      if (endcolors) {
-        if (flags & LT_TRACE_LABEL_IMAGE) endcolors[ray] = 0;
-        else { endcolors[3 * (size_t)ray] = 0; endcolors[3 * (size_t)ray + 1] = 0; endcolors[3 * (size_t)ray + 2] = 0; }
-      }
-      if (endrem) endrem[ray] = 0.f;
-      if (range) range[ray] = 0.f;
-      if (tri_out) tri_out[ray] = -1;
+      lt_scan_write_hit(images, (size_t)ray, (flags & LT_TRACE_LABEL_IMAGE) != 0, t, face, J.ox, J.oy, J.oz, d.x, d.y, d.z,
+                        faces, J.colors, J.rem);
     }
+    else if (flags & LT_TRACE_WRITE_MISSES)
+      lt_scan_write_miss(images, (size_t)ray, (flags & LT_TRACE_LABEL_IMAGE) != 0);
   }
   if (COUNT) {
     unsigned long long vh = hit ? 1u : 0u;
@@ -1155,7 +1117,7 @@ struct sc_item {  // host view of one scan of a batch
   lt_scene* s;
   lt_rayset* r;
   const float* origin;
-  float* endpoints; int* endcolors; float* range; float* endrem; int* tri;
+  lt_scan_images images;
 };
 
 // Three launches for the whole batch (k_sc_tris, k_sc_rest, k_sc_resolve) on `stream`.  `probe` = the scene
@@ -1181,8 +1143,7 @@ static int sc_launch_batch(const sc_item* it, int n_items, unsigned flags, hipSt
     J.P = r->prm_host; J.grid = r->grid; J.sdirs = r->sdirs; J.dirs = r->dirs;
     J.cell = s->sc_cell; J.large = s->sc_large; J.large_count = s->sc_large_count; J.slices = s->sc_slices;
     J.flags = s->flags; J.counters = s->counters;
-    J.endpoints = it[i].endpoints; J.endcolors = it[i].endcolors; J.range = it[i].range; J.endrem = it[i].endrem;
-    J.tri = it[i].tri;
+    J.images = it[i].images;
     J.ox = it[i].origin[0]; J.oy = it[i].origin[1]; J.oz = it[i].origin[2];
     J.n_verts = s->n_verts; J.n_faces = n; J.n_rays = R; J.cap_slices = s->sc_cap_queue;
     J.out_flags = flags;
@@ -1253,7 +1214,7 @@ extern "C" int lt_scene_render_dev(lt_scene* s, lt_rayset* r, const float* origi
   if (R > 0) {
     if (count) LT_HIP(hipMemsetAsync(s->counters, 0, 4 * sizeof(unsigned long long), stream));
     if (timed) LT_HIP(hipEventRecord(s->ev[7], stream));
-    const sc_item it = {s, r, origin, endpoints, endcolors, range, endrem, tri};
+    const sc_item it = {s, r, origin, {endpoints, endcolors, range, endrem, tri}};
     LT_CHECK(sc_launch_batch(&it, 1, flags, stream, count, count ? nullptr : s));
     if (timed) LT_HIP(hipEventRecord(s->ev[8], stream));
   }
@@ -1303,9 +1264,9 @@ extern "C" int lt_scene_render_batch_dev(int n_scans, lt_scene* const* scenes, l
         lt_set_error("lt_scene_render_batch_dev: scans %d and %d are the same scene (a scene renders one scan at a time)", k, i);
         return LT_ERR_INVALID_ARG;
       }
-    it[i] = {scenes[i], raysets[i], origins + 3 * i, endpoints ? endpoints[i] : nullptr,
-             endcolors ? endcolors[i] : nullptr, range ? range[i] : nullptr, endrem ? endrem[i] : nullptr,
-             tri ? tri[i] : nullptr};
+    it[i] = {scenes[i], raysets[i], origins + 3 * i,
+             {endpoints ? endpoints[i] : nullptr, endcolors ? endcolors[i] : nullptr, range ? range[i] : nullptr,
+              endrem ? endrem[i] : nullptr, tri ? tri[i] : nullptr}};
     scenes[i]->last_stream = stream;
     scenes[i]->stats.n_rays = raysets[i]->n_rays;
     scenes[i]->stats.n_faces = scenes[i]->n_faces;

@@ -14,6 +14,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include "lt_scanimg.h"
 #include "lt_normalize.h"  // the reference's RSQRTSS seed, replayed (Intel / AMD table) or exact
 
 #define LT_DONE ((int)0x80000000)
@@ -23,7 +24,8 @@
 
 // =====================================================================================================
 // What the kernels are told, as three PODs by value (helpers: by const reference), built once per call
-// by lt_trace_launch.  The spill area, the counters, the step cap and tail_args stay arguments of their own.
+// by lt_trace_launch: the two below and the images of the call, an lt_scan_images (a null member: not wanted).
+// The spill area, the counters, the step cap and tail_args stay arguments of their own.
 // =====================================================================================================
 struct trace_scene {    // the mesh and its tree
   const float4* nodes;  // binary nodes (k_trace) or 4-wide nodes (k_trace4, k_trace4_tail)
@@ -38,13 +40,6 @@ struct trace_cast {  // one call: the rays and the image they form
   float ox, oy, oz;
   int H, W;
   unsigned flags;
-};
-struct trace_out {  // the images of a call; a null pointer: not wanted
-  float* endpoints;
-  int* endcolors;
-  float* range;
-  float* endrem;
-  int* tri;
 };
 
 // A ray as the kernels use it: origin, normalised direction, inverse direction (Ray.h:12, +-inf allowed).
@@ -134,38 +129,12 @@ __device__ __forceinline__ float trace_tri(const float4* __restrict__ T, const t
 
 // write-back of one ray (RayTracer.cpp:73-90); misses are written only with LT_TRACE_WRITE_MISSES
 __device__ __forceinline__ void trace_writeback(size_t ray, float best_t, int best_face, const trace_ray& r,
-                                                const trace_scene& sc, unsigned flags, const trace_out& o) {
-  if (best_face != LT_NO_FACE) {
-    const int i0 = sc.faces[3 * (size_t)best_face], i1 = sc.faces[3 * (size_t)best_face + 1],
-              i2 = sc.faces[3 * (size_t)best_face + 2];
-    if (o.endpoints) {  // hit = o + d * t (BVH.cpp:107)
-      o.endpoints[3 * ray] = r.ox + r.dx * best_t;
-      o.endpoints[3 * ray + 1] = r.oy + r.dy * best_t;
-      o.endpoints[3 * ray + 2] = r.oz + r.dz * best_t;
-    }
-    if (o.endcolors) {  // colour of vertex 0, int -> float -> int (RayTracer.cpp:36, :80-82)
-      if (flags & LT_TRACE_LABEL_IMAGE) {  // deform's unpack label_image = ray_colors[..., 2], laserscan.py:912
-        o.endcolors[ray] = (int)(float)sc.colors[3 * (size_t)i0 + 2];
-      } else {  // (read before the first store: the three as one load, whatever the images may alias)
-        const int c0 = sc.colors[3 * (size_t)i0], c1 = sc.colors[3 * (size_t)i0 + 1], c2 = sc.colors[3 * (size_t)i0 + 2];
-        o.endcolors[3 * ray] = (int)(float)c0;
-        o.endcolors[3 * ray + 1] = (int)(float)c1;
-        o.endcolors[3 * ray + 2] = (int)(float)c2;
-      }
-    }
-    if (o.endrem) o.endrem[ray] = ((sc.rem[i0] + sc.rem[i1]) + sc.rem[i2]) / 3.0f;  // Triangle.h:69
-    if (o.range) o.range[ray] = best_t;
-    if (o.tri) o.tri[ray] = best_face;
-  } else if (flags & LT_TRACE_WRITE_MISSES) {
-    if (o.endpoints) { o.endpoints[3 * ray] = 0.f; o.endpoints[3 * ray + 1] = 0.f; o.endpoints[3 * ray + 2] = 0.f; }
-    if (o.endcolors) {
-      if (flags & LT_TRACE_LABEL_IMAGE) o.endcolors[ray] = 0;
-      else { o.endcolors[3 * ray] = 0; o.endcolors[3 * ray + 1] = 0; o.endcolors[3 * ray + 2] = 0; }
-    }
-    if (o.endrem) o.endrem[ray] = 0.f;
-    if (o.range) o.range[ray] = 0.f;
-    if (o.tri) o.tri[ray] = -1;
-  }
+                                                const trace_scene& sc, unsigned flags, const lt_scan_images& o) {
+  const bool label = (flags & LT_TRACE_LABEL_IMAGE) != 0;
+  if (best_face != LT_NO_FACE)
+    lt_scan_write_hit(o, ray, label, best_t, best_face, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, sc.faces, sc.colors, sc.rem);
+  else if (flags & LT_TRACE_WRITE_MISSES)
+    lt_scan_write_miss(o, ray, label);
 }
 
 // LT_TRACE_COUNT: the four per-lane tallies summed over the wave into counters[0 .. 3] (nodes, triangle tests, hits,
@@ -207,7 +176,7 @@ __device__ __forceinline__ int bin_pop(const int* lds, const int* spill, int& sp
 }
 
 template <bool COUNT>
-__global__ __launch_bounds__(256) void k_trace(trace_scene scene, trace_cast cast, trace_out out,
+__global__ __launch_bounds__(256) void k_trace(trace_scene scene, trace_cast cast, lt_scan_images out,
                                                int* __restrict__ overflow, unsigned long long* __restrict__ counters) {
   __shared__ int stack[4][LT_STACK_LDS][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -497,7 +466,7 @@ __device__ __forceinline__ void park_ray(const tail_args& tail, const quad_walk&
 }
 
 template <bool COUNT>
-__global__ __launch_bounds__(256) void k_trace4(trace_scene scene, trace_cast cast, trace_out out,
+__global__ __launch_bounds__(256) void k_trace4(trace_scene scene, trace_cast cast, lt_scan_images out,
                                                 int* __restrict__ overflow, unsigned long long* __restrict__ counters,
                                                 int step_cap, tail_args tail) {
   __shared__ int stack[4][LT_STACK4_LDS][16];
@@ -564,7 +533,7 @@ __global__ __launch_bounds__(64) void k_trace4_tail(const float4* __restrict__ n
                                                     tail_args tail) {
   const trace_scene scene = {nodes4, tris, faces, colors, rem, 0};  // (n_faces, H, W: not needed, a parked ray exists)
   const trace_cast cast = {rays, ox, oy, oz, 0, 0, flags};
-  const trace_out out = {endpoints, endcolors, range, endrem, tri_out};
+  const lt_scan_images out = {endpoints, endcolors, range, endrem, tri_out};
   __shared__ int stk[LT_TAIL_STACK];
   __shared__ unsigned long long best;  // (t bits) << 32 | face: for t > 0 the integer order is the order of (t, face)
   const int lane = threadIdx.x, j = lane & 3, q = lane >> 2;
@@ -638,14 +607,14 @@ static int trace_grid(int H, int W, int tile_h, int tile_w) {
 }
 
 template <bool COUNT>
-static void launch_k_trace(const lt_scene* s, const trace_scene& scene, const trace_cast& cast, const trace_out& out,
+static void launch_k_trace(const lt_scene* s, const trace_scene& scene, const trace_cast& cast, const lt_scan_images& out,
                            hipStream_t stream) {
   hipLaunchKernelGGL(k_trace<COUNT>, dim3(trace_grid(cast.H, cast.W, LT_TILE_H, LT_TILE_W)), dim3(256), 0, stream, scene,
                      cast, out, s->overflow, s->counters);
 }
 
 template <bool COUNT>
-static void launch_k_trace4(const lt_scene* s, const trace_scene& scene, const trace_cast& cast, const trace_out& out,
+static void launch_k_trace4(const lt_scene* s, const trace_scene& scene, const trace_cast& cast, const lt_scan_images& out,
                             int step_cap, const tail_args& tail, hipStream_t stream) {
   hipLaunchKernelGGL(k_trace4<COUNT>, dim3(trace_grid(cast.H, cast.W, LT_TILE4_H, LT_TILE4_W)), dim3(256), 0, stream,
                      scene, cast, out, s->overflow, s->counters, step_cap, tail);
@@ -674,7 +643,7 @@ int lt_trace_launch(lt_scene* s, const float* rays, const float* origin, int n_r
     if (count) LT_HIP(hipMemsetAsync(s->counters, 0, 4 * sizeof(unsigned long long), stream));
     const trace_scene scene = {binary ? s->nodes : s->nodes4, s->tris, s->faces, s->colors, s->rem, s->n_faces};
     const trace_cast cast = {rays, origin[0], origin[1], origin[2], H, W, flags};
-    const trace_out out = {endpoints, endcolors, range, endrem, tri};
+    const lt_scan_images out = {endpoints, endcolors, range, endrem, tri};
     if (timed) LT_HIP(hipEventRecord(s->ev[7], stream));
     if (binary) {
       if (count) launch_k_trace<true>(s, scene, cast, out, stream);
