@@ -212,6 +212,18 @@ int lt_scene_render_batch_dev(int n_scans, lt_scene* const* scenes, lt_rayset* c
                               float* const* range, float* const* endrem, int* const* tri, unsigned flags,
                               void* stream);
 
+/* A sensor RIG: the scene's CURRENT mesh rendered from up to 8 sensors in ONE call.  Sensor i is raysets[i], cast from
+ * origins[3 * i ..] (HOST), into its own five DEVICE images (the output arguments as in the batch call: an array, or single
+ * entries of it, may be NULL); the same ray set may appear more than once, e.g. with two origins.  The flags are those of
+ * the batch call (LT_TRACE_COUNT is not accepted); asynchronous on `stream`.  Results are those of n_sensors successive
+ * lt_scene_render_dev calls on that scene, byte for byte, including what a miss leaves untouched.  n_sensors == 0 does
+ * nothing, n_sensors == 1 IS lt_scene_render_dev.  LT_ERR_INVALID_ARG: n_sensors < 0 or > 8, a NULL ray set, a ray set on
+ * another device than the scene.  The z-min cells and queues of sensors 1 .. 7 are render-state slots of the scene, allocated
+ * when a rig first needs them: a scene that never renders a rig holds nothing more than before. */
+int lt_scene_render_rig_dev(lt_scene* scene, int n_sensors, lt_rayset* const* raysets, const float* origins,
+                            float* const* endpoints, int* const* endcolors, float* const* range, float* const* endrem,
+                            int* const* tri, unsigned flags, void* stream);
+
 /* Measurement hook: record the caller's two hipEvent_t (passed as void*) on the launch stream immediately
  * before and after the dominant kernel (k_sc_tris / k_trace4) of the NEXT lt_scene_render_dev /
  * lt_scene_trace_dev call; one shot, no synchronisation.  bench.py uses it for the roofline figure. */

@@ -12,6 +12,7 @@ implementation in this package (``oracle/`` is test infrastructure).
     sequence    SequenceTransfer: a sequence on disk -> the transferred sequence on disk (lidar_deform.py's batch loop); CLI: python -m
     pipeline    ScanPipeline: the batch loop body, batches of scans in flight on one GPU; HostScanPipeline (host meshes
                 over PCIe); FusionScanPipeline (fuse -> marching cubes -> render per output scan, chains in flight)
+    rig         RigDeform: several target sensors around one chain, every further one rendered from the first one's mesh
     dist        scan_indices / partition / render_scans / gather_to_root: one process per GPU, one gather
     synth       synthetic scenes and workloads of SURVEY.md section 8d
     build       hipcc build of liblidarhip.so (in-tree)

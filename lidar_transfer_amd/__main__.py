@@ -30,7 +30,10 @@ is always headless (``--batch`` is accepted).  Per compared scan it prints the r
 every target -- mounted, with a table, a sector, offsets, a return model, another image size -- against the source scan seen
 through the target's model from its pose: the three lines are printed per scan and every row of ``--log`` carries
 ``"evaluate": "target"``, ``n_compared`` and ``MSE_compared``; ``--evaluate off`` compares nothing.  A missing dataset, labels
-or output folder ends with a message and exit status 1."""
+or output folder ends with a message and exit status 1.  An approach file with a ``rig`` (config/approach_rig_example.yaml, DESIGN
+7i) names SEVERAL target sensors: ``-t`` is refused with it, every output scan is written once per head into
+``OUT/sequences/SS/NAME/velodyne|labels`` (and, with ``rig_merged``, as one scan into the standard pair), nothing is compared,
+every row of ``--log`` carries ``sensors: {NAME: {n_points}}`` and the closing lines are printed per head, led by ``NAME: ``."""
 from __future__ import annotations
 
 import argparse
@@ -88,7 +91,18 @@ def main(argv=None):
     source_path = os.path.join(args.dataset, "config.yaml")
     target_path = args.target or source_path
     try:
-        approach, source, target = load_approach(args.config), load_sensor(source_path), load_sensor(target_path)
+        approach, source = load_approach(args.config), load_sensor(source_path)
+        rig = approach.rig()   # (a rig that cannot be used: said here; None without the key)
+        if rig is not None and args.target:
+            print("The approach file has a rig, which names its target sensors: -t / --target cannot be given with it.")
+            return 1
+        if rig is not None and approach.adaption == "cp":
+            print("adaption cp renders no ray: a rig needs mesh or mergemesh.")
+            return 1
+        if rig is not None and args.evaluate == "target":
+            print("--evaluate target: a rig is not evaluated (rig evaluation is a follow-up); use auto or off.")
+            return 1
+        target = load_sensor(target_path) if rig is None else rig[0].sensor
         approach.mount()   # (a transformation that is not a rigid motion: said here, not half way into the run)
         refuse_source_models(source)
     except Exception as e:  # noqa: BLE001  (a YAML that cannot be read: message and status, as the reference's quit())
@@ -96,22 +110,25 @@ def main(argv=None):
         print("Error opening yaml file.")
         return 1
     from .sequence import SequenceTransfer
-    if target.return_model() is not None and approach.adaption == "cp":
+    if rig is not None:
+        pass   # (cp was refused above; mesh and mergemesh take every model of every head)
+    elif target.return_model() is not None and approach.adaption == "cp":
         print("adaption cp renders no surface: the target sensor's return_model cannot be applied (use mesh or mergemesh).")
         return 1
-    if target.noise_model() is not None and approach.adaption == "cp":
+    if rig is None and target.noise_model() is not None and approach.adaption == "cp":
         print("adaption cp renders no ray: the target sensor's noise_model cannot be applied (use mesh or mergemesh).")
         return 1
-    if target.echo_model() is not None and approach.adaption == "cp":
+    if rig is None and target.echo_model() is not None and approach.adaption == "cp":
         print("adaption cp renders no ray: the target sensor's echo_model cannot be applied (use mesh or mergemesh).")
         return 1
-    if target.dual_return() is not None and approach.adaption == "cp":
+    if rig is None and target.dual_return() is not None and approach.adaption == "cp":
         print("adaption cp renders no ray: the target sensor's dual_return cannot be applied (use mesh or mergemesh).")
         return 1
     log = open(args.log, "w") if args.log else None
     try:
-        with SequenceTransfer((args.dataset, args.sequence), approach, source, target, out_dir=args.output if args.write else None,
-                              chains=args.chains, fusion=args.fusion, copy_files=(target_path, args.config),
+        with SequenceTransfer((args.dataset, args.sequence), approach, source, target if rig is None else None,
+                              out_dir=args.output if args.write else None, chains=args.chains, fusion=args.fusion,
+                              copy_files=(target_path, args.config) if rig is None else (args.config,),
                               evaluate={"auto": None, "target": "target", "off": False}[args.evaluate]) as tr:
             n_files = len(tr.source)
             for rec in tr.run(offset=args.offset, one_scan=args.one_scan, resume=args.resume):
@@ -122,6 +139,9 @@ def main(argv=None):
                 print("#" * 30, args.sequence, "-", rec["idx"], "/", n_files, "#" * 30, flush=True)
                 if log is not None:
                     row = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in rec.items()}
+                    if rig is not None:      # (`sensors` is in the record; the single-target marks below describe no rig)
+                        log.write(json.dumps(row) + "\n")
+                        continue
                     if tr.evaluate_mode == "target":
                         row["evaluate"] = "target"
                     if tr.mounted:
@@ -137,6 +157,16 @@ def main(argv=None):
                     if tr.dual is not None:
                         row["dual_return"] = True
                     log.write(json.dumps(row) + "\n")
+            for name, totals in (tr.summary.get("sensors") or {}).items():   # a rig: the closing lines per head
+                from .sequence import format_echo_totals, format_noise_totals, format_return_totals
+                if totals["return_totals"] is not None:
+                    print(name + ": " + format_return_totals(totals["return_totals"]), flush=True)
+                if totals["noise_totals"] is not None:
+                    print(name + ": " + format_noise_totals(totals["noise_totals"], totals["range_error_rms"]), flush=True)
+                if totals["echo_totals"] is not None:
+                    print(name + ": " + format_echo_totals(totals["echo_totals"], totals["echo_fraction_mean"]), flush=True)
+                if totals["second_returns"] is not None:
+                    print(name + ": Second returns: %d" % totals["second_returns"], flush=True)
             if tr.summary.get("return_totals") is not None:
                 from .sequence import format_return_totals
                 print(format_return_totals(tr.summary["return_totals"]), flush=True)

@@ -52,7 +52,7 @@ SYMBOLS = ["lt_ctrace", "lt_ctrace_ex", "lt_scene_create", "lt_scene_set_mesh_de
            "lt_rayset_create_grid_dev", "lt_projector_set_sector", "lt_range_projection_set_sector",
            "lt_create_rays_beams_az_dev", "lt_projector_set_beam_azimuth", "lt_range_projection_set_beam_azimuth",
            "lt_reverse_projection_beams_az_dev", "lt_return_model_dev", "lt_target_view_dev", "lt_noise_model_dev",
-           "lt_create_subrays_dev", "lt_echo_resolve_dev", "lt_echo_resolve_dual_dev"]
+           "lt_create_subrays_dev", "lt_echo_resolve_dev", "lt_echo_resolve_dual_dev", "lt_scene_render_rig_dev"]
 LT_ABI_VERSION = 10   # include/lidarhip.h: layout version of the structs mirrored below
 
 
@@ -197,6 +197,8 @@ def load():
     pvp = C.POINTER(vp)
     lib.lt_scene_render_batch_dev.argtypes = [C.c_int, pvp, pvp, fp, pvp, pvp, pvp, pvp, pvp, C.c_uint, vp]
     lib.lt_scene_render_batch_dev.restype = C.c_int
+    lib.lt_scene_render_rig_dev.argtypes = [vp, C.c_int, pvp, fp, pvp, pvp, pvp, pvp, pvp, C.c_uint, vp]
+    lib.lt_scene_render_rig_dev.restype = C.c_int
     lib.lt_reverse_projection_dev.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, vp]
     lib.lt_reverse_projection_dev.restype = C.c_int
     lib.lt_pack_scan_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.POINTER(C.c_int), vp]

@@ -52,9 +52,20 @@ A sixth is the WIDTH of its beams, :class:`EchoModel` (``SensorModel.echo_model(
   (``SensorModel.dual_return()``) -- a SECOND echo of every cell, chosen by ``second`` among the detected echoes other than
   the reported one, goes through the return and noise models and into the files behind the primary's points; ``none`` is
   off; it needs an ``echo_model`` that is on.
+
+The approach file has two keys of this project's own for SEVERAL target sensors on one vehicle (:meth:`Approach.rig`, DESIGN
+7i); a file without them behaves as before:
+
+* ``rig``: a list of 1 to 8 heads ``{name, sensor, transformation}`` -- ``name`` unique and ``[A-Za-z0-9_-]+`` (a folder of the
+  output), ``sensor`` the path of a sensor file relative to the approach file (or a mapping), ``transformation`` with the
+  meaning of the top-level key, absent or empty for a head at the source pose; the top-level ``transformation`` must then be
+  empty or the identity;
+* ``rig_merged`` (default ``false``): the whole rig's points are also written as one scan, in the primary scan's frame.
 """
 from __future__ import annotations
 
+import os
+import re
 from dataclasses import dataclass, field
 from functools import cached_property
 from typing import Dict, List, Optional
@@ -732,6 +743,17 @@ def refuse_source_models(source):
     refuse_source_dual_return(source)
 
 
+RIG_MAX_HEADS = 8   # sensors of one lt_scene_render_rig_dev call
+
+
+@dataclass
+class RigHead:
+    """One sensor of a rig (:meth:`Approach.rig`): its name (a folder of the output), its model, its mounting."""
+    name: str
+    sensor: SensorModel
+    mount: Optional[tuple]
+
+
 @dataclass
 class Approach:
     """``config/lidar_transfer.yaml`` (``lidar_deform.py:318-351``)."""
@@ -746,6 +768,52 @@ class Approach:
     batch_interval: int               # default 1 when absent (lidar_deform.py:352-355)
     color_map: Dict[int, List[int]]   # bgr
     labels: Dict[int, str]
+    rig_block: Optional[list] = None  # the `rig` key as read: 1 to 8 entries {name, sensor, transformation}; None: no rig
+    rig_merged: bool = False          # with a rig: also write the whole rig's points as one scan
+    base_dir: Optional[str] = None    # directory of the approach file: a head's `sensor` path is relative to it
+
+    def rig(self):
+        """The heads of the approach's sensor rig, validated, in the file's order: a list of :class:`RigHead` (``name``,
+        ``sensor``: its :class:`SensorModel`, ``mount``: :func:`mount_of` its ``transformation`` -- ``None`` at the source
+        pose); ``None`` for an approach without the key.  ``ValueError``: not 1 to 8 entries, an entry that is no mapping of
+        ``name, sensor, transformation``, a name that is not unique or does not match ``[A-Za-z0-9_-]+``, a top-level
+        ``transformation`` other than the identity next to a ``rig`` (each head has its own), ``rig_merged`` without a rig."""
+        if self.rig_block is None:
+            if self.rig_merged:
+                raise ValueError("rig_merged: true needs a rig")
+            return None
+        block = self.rig_block
+        if not isinstance(block, (list, tuple)) or not 1 <= len(block) <= RIG_MAX_HEADS:
+            n = len(block) if isinstance(block, (list, tuple)) else type(block).__name__
+            raise ValueError(f"rig: a list of 1 to {RIG_MAX_HEADS} heads {{name, sensor, transformation}}, not {n}")
+        if mount_of(self.transformation) is not None:
+            raise ValueError("rig: the top-level transformation must be empty or the identity next to a rig (every head of the "
+                             "rig has its own transformation)")
+        heads, seen = [], set()
+        for k, entry in enumerate(block):
+            if not isinstance(entry, dict) or "name" not in entry or "sensor" not in entry:
+                raise ValueError(f"rig: head {k} must be a mapping of name, sensor and (optionally) transformation")
+            unknown = sorted(set(entry) - {"name", "sensor", "transformation"})
+            if unknown:
+                raise ValueError(f"rig: head {k} has unknown key(s) {', '.join(map(str, unknown))} (known: name, sensor, "
+                                 "transformation)")
+            name = entry["name"]
+            if not isinstance(name, str) or not re.fullmatch(r"[A-Za-z0-9_-]+", name):
+                raise ValueError(f"rig: head {k}: name {name!r} must match [A-Za-z0-9_-]+")
+            if name in seen:
+                raise ValueError(f"rig: head {k}: the name {name!r} is used twice")
+            seen.add(name)
+            sensor = entry["sensor"]
+            if isinstance(sensor, str):
+                sensor = sensor if os.path.isabs(sensor) or self.base_dir is None else os.path.join(self.base_dir, sensor)
+            elif not isinstance(sensor, dict):
+                raise ValueError(f"rig: head {name!r}: sensor must be the path of a sensor file or a mapping")
+            try:
+                mount = mount_of(entry.get("transformation"))
+            except ValueError as e:
+                raise ValueError(f"rig: head {name!r}: {e}") from None
+            heads.append(RigHead(name, load_sensor(sensor), mount))
+        return heads
 
     def color_lut(self) -> np.ndarray:
         """``SemLaserScan.__init__``'s look-up table (``laserscan.py:547-555``): ``[max(key) + 1 + 100, 3]`` float32,
@@ -802,6 +870,16 @@ def mount_of(transformation):
     return T, np.ascontiguousarray(np.linalg.inv(T))
 
 
+def _rig_merged(cfg):
+    """the approach file's ``rig_merged``: a real boolean (``"false"`` is a string, and true), and only next to a ``rig``"""
+    v = cfg.get("rig_merged", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"rig_merged: true or false, not {v!r}")
+    if v and cfg.get("rig") is None:
+        raise ValueError("rig_merged: true needs a rig")
+    return v
+
+
 def load_approach(path_or_dict) -> Approach:
     cfg = _load_yaml(path_or_dict)
     vb = np.array(cfg["voxel_bounds"])
@@ -813,4 +891,5 @@ def load_approach(path_or_dict) -> Approach:
                     voxel_bounds=vb, number_of_scans=cfg["number_of_scans"], ignore=list(cfg["ignore"]),
                     moving=list(cfg["moving"]), transformation=list(cfg["transformation"]),
                     batch_interval=cfg.get("batch_interval", 1), color_map=dict(cfg["color_map"]),
-                    labels=dict(cfg.get("labels", {})))
+                    labels=dict(cfg.get("labels", {})), rig_block=cfg.get("rig"), rig_merged=_rig_merged(cfg),
+                    base_dir=None if isinstance(path_or_dict, dict) else os.path.dirname(os.path.abspath(path_or_dict)))

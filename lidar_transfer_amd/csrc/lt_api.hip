@@ -130,6 +130,9 @@ extern "C" int lt_scene_destroy(lt_scene* s) {
   if (s->sc_large) (void)hipFree(s->sc_large);
   if (s->sc_slices) (void)hipFree(s->sc_slices);
   if (s->sc_large_count) (void)hipFree(s->sc_large_count);
+  for (lt_sc_state& t : s->sc_rig)
+    for (void* p : {(void*)t.cell, (void*)t.large, (void*)t.slices, (void*)t.large_count})
+      if (p) (void)hipFree(p);
   for (int k = 0; k < s->have_events; ++k) (void)hipEventDestroy(s->ev[k]);
   free(s);
   return LT_OK;

@@ -78,6 +78,16 @@ bool beam_azimuth_ok(const char* who, const double* az, int n);
 #define LT_TAIL_DFS 256
 #define LT_TRACE4_STEP_CAP 40  // node + leaf steps a ray may take in k_trace4 before it is handed over (LIDARHIP_STEP_CAP)
 
+// Render state of ONE sensor of a rig on a scene (lt_scatter.hip): what sc_cell .. sc_cap_queue of lt_scene are for the first
+#define LT_SC_RIG_SLOTS 7
+struct lt_sc_state {
+  unsigned long long* cell;  // [cap_cells]
+  int* large;                // [cap_queue]
+  int2* slices;              // [cap_queue]
+  int* large_count;          // [4]
+  int cap_cells, cap_queue, cap_count;
+};
+
 struct lt_scene {
   int device;
   // mesh (borrowed or owned)
@@ -118,6 +128,9 @@ struct lt_scene {
   int2* sc_slices;              // [sc_cap_queue] queue of (block, first candidate) slices
   int* sc_large_count;          // [4]: [0] queued big triangles, [1] queued slices; reset by k_sc_resolve
   int sc_cap_cells, sc_cap_queue;
+  // ... and of the further sensors of a rig (lt_scene_render_rig_dev): sensor k > 0 renders into slot k - 1, sensor 0 into the
+  // members above.  Empty until a rig needs them.
+  lt_sc_state sc_rig[LT_SC_RIG_SLOTS];
   int built;
   int sorted_buf;        // which of keys[] / vals[] holds the sorted pairs of the last build (lt_sort_pairs' *out_buffer)
   hipStream_t last_stream;

@@ -1112,12 +1112,34 @@ static int sc_reserve(lt_scene* s, int n_faces, int n_rays, hipStream_t stream) 
   return LT_OK;
 }
 
+// The same for a render-state slot of a rig (lt_internal.h): created on first use, grown like the scene's own.
+static int sc_reserve_slot(lt_sc_state& t, int n_faces, int n_rays, hipStream_t stream) {
+  if (!t.large_count) {
+    // (wait: none -- there is no old array)
+    LT_CHECK(lt_dev_grow("lt_scene_render_rig", lt_wait_none(), &t.large_count, &t.cap_count, 4, 4));
+    LT_HIP(hipMemsetAsync(t.large_count, 0, 4 * sizeof(int), stream));
+  }
+  if (n_rays > t.cap_cells) {
+    // (wait: the device -- an earlier rig's kernels, on any stream, may still read and re-arm the old cells)
+    LT_CHECK(lt_dev_grow("lt_scene_render_rig", lt_wait_device(), &t.cell, &t.cap_cells, (size_t)n_rays, (size_t)n_rays));
+    LT_HIP(hipMemsetAsync(t.cell, 0xFF, (size_t)n_rays * sizeof(unsigned long long), stream));
+  }
+  if (n_faces > t.cap_queue) {
+    const size_t cap = lt_headroom((size_t)n_faces);
+    const lt_dev_array queues[] = {{(void**)&t.large, cap * sizeof(int)}, {(void**)&t.slices, cap * sizeof(int2)}};
+    // (wait: the device -- as for the cells)
+    LT_CHECK(lt_dev_replace("lt_scene_render_rig", lt_wait_device(), &t.cap_queue, (int)cap, queues));
+  }
+  return LT_OK;
+}
+
 // ---- launching a batch -----------------------------------------------------------------------------------------------
 struct sc_item {  // host view of one scan of a batch
   lt_scene* s;
   lt_rayset* r;
   const float* origin;
   lt_scan_images images;
+  int slot;  // render state: 0 = the scene's own members, k > 0 = s->sc_rig[k - 1] (a rig's further sensors)
 };
 
 // Three launches for the whole batch (k_sc_tris, k_sc_rest, k_sc_resolve) on `stream`.  `probe` = the scene
@@ -1137,15 +1159,18 @@ static int sc_launch_batch(const sc_item* it, int n_items, unsigned flags, hipSt
     lt_rayset* r = it[i].r;
     const int n = s->n_faces, R = r->n_rays;
     if (R <= 0) continue;  // nothing to write for this scan
-    LT_CHECK(sc_reserve(s, n, R, stream));
+    lt_sc_state* slot = it[i].slot > 0 ? &s->sc_rig[it[i].slot - 1] : nullptr;
+    if (slot) LT_CHECK(sc_reserve_slot(*slot, n, R, stream));
+    else LT_CHECK(sc_reserve(s, n, R, stream));
     sc_job& J = B.job[B.n++];
     J.verts = s->verts; J.faces = s->faces; J.colors = s->colors; J.rem = s->rem;
     J.P = r->prm_host; J.grid = r->grid; J.sdirs = r->sdirs; J.dirs = r->dirs;
     J.cell = s->sc_cell; J.large = s->sc_large; J.large_count = s->sc_large_count; J.slices = s->sc_slices;
+    if (slot) { J.cell = slot->cell; J.large = slot->large; J.large_count = slot->large_count; J.slices = slot->slices; }
     J.flags = s->flags; J.counters = s->counters;
     J.images = it[i].images;
     J.ox = it[i].origin[0]; J.oy = it[i].origin[1]; J.oz = it[i].origin[2];
-    J.n_verts = s->n_verts; J.n_faces = n; J.n_rays = R; J.cap_slices = s->sc_cap_queue;
+    J.n_verts = s->n_verts; J.n_faces = n; J.n_rays = R; J.cap_slices = slot ? slot->cap_queue : s->sc_cap_queue;
     J.out_flags = flags;
     B.tris_block0[B.n - 1] = tb;
     B.resolve_block0[B.n - 1] = rb;
@@ -1274,6 +1299,54 @@ extern "C" int lt_scene_render_batch_dev(int n_scans, lt_scene* const* scenes, l
   }
   LT_HIP(hipSetDevice(scenes[0]->device));
   return sc_launch_batch(it, n_scans, flags, stream, false, probe ? probe : scenes[0]);
+}
+
+// A rig: one scene, its current mesh, up to LT_SC_MAX_BATCH sensors (include/lidarhip.h).  Sensor 0 renders into the scene's
+// own cells and queues, sensor k into slot k - 1; the mesh and the error bits are shared by all jobs.
+extern "C" int lt_scene_render_rig_dev(lt_scene* s, int n_sensors, lt_rayset* const* raysets, const float* origins,
+                                       float* const* endpoints, int* const* endcolors, float* const* range,
+                                       float* const* endrem, int* const* tri, unsigned flags, void* stream_) {
+  if (!s || n_sensors < 0 || n_sensors > LT_SC_MAX_BATCH || (n_sensors > 0 && (!raysets || !origins))) {
+    lt_set_error("lt_scene_render_rig_dev: invalid argument (n_sensors=%d, at most %d per call; NULL scene / raysets / origins?)",
+                 n_sensors, LT_SC_MAX_BATCH);
+    return LT_ERR_INVALID_ARG;
+  }
+  if (flags & LT_TRACE_COUNT) {
+    lt_set_error("lt_scene_render_rig_dev: LT_TRACE_COUNT is a single-scan diagnostic (lt_scene_render_dev)");
+    return LT_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < n_sensors; ++i) {
+    if (!raysets[i]) {
+      lt_set_error("lt_scene_render_rig_dev: sensor %d: NULL rayset", i);
+      return LT_ERR_INVALID_ARG;
+    }
+    if (raysets[i]->device != s->device) {
+      lt_set_error("lt_scene_render_rig_dev: sensor %d: scene on device %d, rayset on device %d", i, s->device,
+                   raysets[i]->device);
+      return LT_ERR_INVALID_ARG;
+    }
+  }
+  if (n_sensors == 0) return LT_OK;
+  auto img = [](auto* const* a, int i) { return a ? a[i] : nullptr; };
+  if (n_sensors == 1)
+    return lt_scene_render_dev(s, raysets[0], origins, img(endpoints, 0), img(endcolors, 0), img(range, 0), img(endrem, 0),
+                               img(tri, 0), flags, stream_, nullptr);
+  hipStream_t stream = (hipStream_t)stream_;
+  LT_HIP(hipSetDevice(s->device));
+  s->last_stream = stream;
+  sc_item it[LT_SC_MAX_BATCH];
+  int n_rays = 0;
+  for (int i = 0; i < n_sensors; ++i) {
+    it[i] = {s, raysets[i], origins + 3 * i,
+             {img(endpoints, i), img(endcolors, i), img(range, i), img(endrem, i), img(tri, i)}, i};
+    n_rays += raysets[i]->n_rays;
+  }
+  s->stats.n_rays = n_rays;
+  s->stats.n_faces = s->n_faces;
+  // The job table: n_sensors jobs that share the scene's mesh pointers, each with its own render state; the three kernels
+  // do the rest.  (A kernel that loads a block's triangles once and loops over the sensors was built and measured: slower
+  // at every K > 1, profiles/rig/README.md.)
+  return sc_launch_batch(it, n_sensors, flags, stream, false, s);
 }
 
 // debug helpers (not part of the documented ABI): queue lengths of the last LT_TRACE_COUNT render (big triangles,

@@ -301,13 +301,38 @@ class DeviceDeform:
             return self._pack(out["back_points"], True, rem, label, out["index"].reshape(-1), self.n_rays, st)
         return self._pack(out["endpoints"], False, rem, label, None, self.n_rays, st)
 
-    def _result(self, out, rout, **more):
+    def scan_result(self, out, rout, t_H=None, t_W=None, **more):
         """what :meth:`mesh` and :meth:`mergemesh` return of a rendered scan (``rout``: what the render wrote, ``out`` with the
-        end points in the target's frame)"""
-        return dict(range=out["range"].view(self.t_H, self.t_W), rem=out["endrem"].view(self.t_H, self.t_W),
-                    label=out["endcolors"].view(self.t_H, self.t_W), endpoints=out["endpoints"],
-                    endpoints_scene=rout["endpoints"], tri=rout["tri"], n_verts=self.mesh_obj.n_verts,
-                    n_faces=self.mesh_obj.n_faces, **more)
+        end points in the target's frame).  ``t_H``, ``t_W``: the image of ANOTHER sensor rendered from this chain's scene (a
+        further head of a rig, ``rig.RigDeform``); default: this chain's target"""
+        H, W = (self.t_H, self.t_W) if t_H is None else (int(t_H), int(t_W))
+        return dict(range=out["range"].view(H, W), rem=out["endrem"].view(H, W), label=out["endcolors"].view(H, W),
+                    endpoints=out["endpoints"], endpoints_scene=rout["endpoints"], tri=rout["tri"],
+                    n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces, **more)
+
+    _result = scan_result
+
+    def pack_rows(self, points, rem, label, n, stream):
+        """``write``'s packing of the mesh adaptions for ``n`` cells of any sensor: float32 ``points`` [n, 3], ``rem`` [n],
+        ``label`` [n], no index filter (laserscan.py:1145-1148) -> ``(bin [N, 4] f32, label_file [N] i32)``"""
+        return self._pack(points, False, rem, label, None, int(n), stream)
+
+    @property
+    def last_stream(self):
+        """the stream of this chain's last call (``None`` before the first): what a caller that continues the scan on the
+        same scene -- a rig's further heads -- queues its work on"""
+        return getattr(self, "_last_stream", None)
+
+    @property
+    def bound_echoes(self):
+        """this chain's bound ``_chain.Echoes`` (falsy when the echo model is off): what ``echoes=`` of a further chain of
+        the same sensor takes, so that the sub-ray set is shared"""
+        return self._echoes
+
+    @property
+    def mm_state(self):
+        """the :class:`MergeMeshState` of this chain's ``mergemesh`` calls (``None`` before the first without a shared one)"""
+        return self._mm_state
 
     # ---- deform('mesh') + write ---------------------------------------------------------------------------------------
     def mesh(self, clouds, origin=None, pack=True, timing=None, scan_index=None):

@@ -241,6 +241,30 @@ class Scene:
                    "lt_scene_render_batch_dev")
         return outs
 
+    def render_rig(self, raysets, origins, outs=None, stream=None, write_misses=True, label_image=False):
+        """``lt_scene_render_rig_dev``: the CURRENT mesh seen by a rig of sensors -- ``(raysets[i], origins[i])``, at most
+        8, the same ray set allowed more than once -- in one call.  Results are those of successive :meth:`render` calls,
+        byte for byte.  ``outs[i]`` may lack images (or hold ``None``): they are not written.  Returns the list of output
+        dicts (``outs`` or freshly allocated)."""
+        n = len(raysets)
+        if n != len(origins) or (outs is not None and len(outs) != n):
+            raise ValueError("render_rig: raysets, origins (and outs) must have one entry per sensor")
+        if outs is None:
+            outs = [self.alloc_outputs(r.n_rays, label_image=label_image) for r in raysets]
+        vp = C.c_void_p
+        arr = lambda vals: (vp * max(n, 1))(*vals)  # noqa: E731
+        org = (C.c_float * max(3 * n, 1))(*[float(v) for o in origins for v in o])
+
+        def col(k):   # (an image that no sensor wants: the whole array is NULL)
+            ptrs = [(o[k].data_ptr() if o.get(k) is not None else None) for o in outs]
+            return arr(ptrs) if any(p is not None for p in ptrs) else None
+
+        flags = (_lib.LT_TRACE_WRITE_MISSES if write_misses else 0) | (_lib.LT_TRACE_LABEL_IMAGE if label_image else 0)
+        _lib.check(self._lib.lt_scene_render_rig_dev(self._h, n, arr([None if r is None else r._h for r in raysets]), org,
+                                                     col("endpoints"), col("endcolors"), col("range"), col("endrem"),
+                                                     col("tri"), flags, self._stream(stream)), "lt_scene_render_rig_dev")
+        return outs
+
     def set_probe(self, ev_start, ev_stop):
         """Record two ``torch.cuda.Event(enable_timing=True)`` around the dominant kernel of the next cast."""
         for ev in (ev_start, ev_stop):  # materialise the underlying hipEvent_t

@@ -122,7 +122,7 @@ class _Tally:
 
 
 class _Writer:
-    """ONE thread: waits for a scan's event, writes its two files"""
+    """ONE thread: waits for a scan's event, writes its files"""
 
     def __init__(self):
         self.q = queue.Queue()
@@ -134,13 +134,17 @@ class _Writer:
             item = self.q.get()
             if item is None:
                 return
-            job, paths, hb, hl, n, event = item
+            if len(item) == 3:               # a rig's scan: (paths, points, labels, n) per file pair, one per head [+ merged]
+                job, files, event = item
+            else:                            # a scan's one pair
+                job, files, event = item[0], [item[1:5]], item[5]
             try:
                 event.synchronize()
-                for p in paths:
-                    os.makedirs(os.path.dirname(p), exist_ok=True)
-                hb.numpy()[:n].tofile(paths[0])
-                hl.numpy()[:n].view(np.uint32).tofile(paths[1])
+                for paths, hb, hl, n in files:
+                    for p in paths:
+                        os.makedirs(os.path.dirname(p), exist_ok=True)
+                    hb.numpy()[:n].tofile(paths[0])
+                    hl.numpy()[:n].view(np.uint32).tofile(paths[1])
             except BaseException as e:  # noqa: BLE001  (handed to the generator as this scan's exception)
                 job["error"] = e
             job["written"].set()
@@ -200,7 +204,15 @@ class SequenceTransfer:
     a SECOND echo per cell: each file holds the primary's points, as without the block, followed by the second
     returns'; a record's ``n_points`` is the file's count; evaluation sees the primary alone.  The second returns that stand
     behind the models are summed on the device and read once at the end of :meth:`run` (``summary["second_returns"]``).
-    ``cp`` renders no ray: with such a target it raises ``ValueError``; so does a source sensor with the key."""
+    ``cp`` renders no ray: with such a target it raises ``ValueError``; so does a source sensor with the key.
+    An approach with a ``rig`` (``Approach.rig()``) names SEVERAL target sensors: ``target_sensor`` is ``None`` (one
+    given raises), every chain is a ``rig.RigDeform`` -- the later ones share the first one's ray sets --, ``mesh`` and
+    ``mergemesh`` only.  The files of head ``NAME`` go to ``<out_dir>/sequences/SS/NAME/velodyne|labels``, with ``rig_merged`` the
+    merged scan to the standard pair; a record gains ``sensors: {NAME: {n_points}}`` and its ``n_points`` is the merged scan's
+    (else the heads' sum); ``resume`` skips a scan only when EVERY file of it is plausible; the tallies above are kept per head
+    under ``summary["sensors"][NAME]`` (the top-level ones stay ``None``).  A rig is not evaluated: ``evaluate=None`` resolves
+    to no comparison, ``True`` and ``"target"`` raise ``ValueError`` naming the follow-up.  The single-target attributes
+    (``target_sensor``, ``beam_model``, ...) then describe head 0."""
 
     def __init__(self, source_seq, approach, source_sensor, target_sensor, out_dir=None, chains=1, fusion="cuda", evaluate=None,
                  device=None, sequence="00", nclasses=None, copy_files=()):
@@ -213,6 +225,22 @@ class SequenceTransfer:
         self.approach, self.adaption = approach, approach.adaption
         from .config import TargetModel, refuse_source_models
         refuse_source_models(source_sensor)
+        # a rig: the approach names the target sensors, every chain is a RigDeform, nothing is compared
+        self.rig = approach.rig()
+        self.rig_names = None if self.rig is None else [h.name for h in self.rig]
+        if self.rig is not None:
+            if target_sensor is not None:
+                raise ValueError("rig: the approach file names its target sensors (rig) -- SequenceTransfer takes no target sensor "
+                                 "with it (target_sensor=None)")
+            if self.adaption == "cp":
+                raise ValueError("rig: adaption cp renders no ray -- a rig needs mesh or mergemesh")
+            if evaluate is True or isinstance(evaluate, str):
+                raise ValueError(f"evaluate: {evaluate!r} -- a rig is not evaluated (which head is compared with the source scan, "
+                                 "and how a merged scan is, is the follow-up 'rig evaluation'); use None or False")
+            evaluate = False
+            target_sensor = self.rig[0].sensor   # (what the single-target attributes below describe: head 0)
+        elif target_sensor is None:
+            raise ValueError("SequenceTransfer: a target sensor, or an approach with a rig")
         self.source_sensor, self.target_sensor = sensor_tuple(source_sensor), sensor_tuple(target_sensor)
         # (sensor_tuple drops the model; ValueError on one that cannot be used; a plain tuple has none: the empty model)
         m = self.target_model = getattr(target_sensor, "target_model", TargetModel)()
@@ -283,7 +311,19 @@ class SequenceTransfer:
             if self.adaption != "cp":
                 every["dual"] = self.dual
             for c in range(self.chains):
-                if self.adaption == "cp":
+                if self.rig is not None:
+                    from .rig import RigDeform
+                    dd = RigDeform(self.source_sensor, self.rig, None if self._mm is not None else self._configured_bnds.copy(),
+                                   approach.voxel_size, share=self._chains[0]["dd"] if self._chains else None,
+                                   merged=approach.rig_merged, beam_angles=beams, preserve_float=approach.preserve_float,
+                                   device=idx, fusion=fusion, mesh_volume=self.adaption == "mesh", mm_state=self._mm)
+                    if self.adaption == "mergemesh":
+                        try:
+                            dd.check_mergemesh()     # (a later head that looks past head 0: said here, not at the first scan)
+                        except BaseException:
+                            dd.close()
+                            raise
+                elif self.adaption == "cp":
                     dd = DeviceDeform(self.source_sensor, self.target_sensor, None, **every)
                 else:
                     dd = DeviceDeform(self.source_sensor, self.target_sensor,
@@ -293,7 +333,8 @@ class SequenceTransfer:
                     rayset = dd.rayset
                     if self.echoes is not None:
                         echoes = dd._echoes          # (the first chain's sub-ray set, shared like the plain one)
-                ch = dict(dd=dd, ev=None, q=None, thread=None, tally=self._tallies(),
+                ch = dict(dd=dd, ev=None, q=None, thread=None,
+                          tally=self._tallies() if self.rig is None else {h.name: self._tallies(h.sensor) for h in self.rig},
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
                 if target_view:
                     ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx,
@@ -311,22 +352,98 @@ class SequenceTransfer:
             self.close()
             raise
 
-    def _tallies(self):
-        """one chain's accumulators: a :class:`_Tally` per model that is on"""
+    def _tallies(self, sensor=None):
+        """one chain's accumulators: a :class:`_Tally` per model that is on -- of the target sensor, or of ``sensor`` (a head
+        of a rig)"""
         n = dict(returns=len(RETURN_CODES), noise=len(NOISE_STATES), echoes=len(ECHO_COUNTS), dual=2)
-        return {name: _Tally(n[name], self.device) for name in n if getattr(self, name) is not None}
+        if sensor is None:
+            return {name: _Tally(n[name], self.device) for name in n if getattr(self, name) is not None}
+        return {name: _Tally(n[name], self.device) for name in n if getattr(sensor, CP_REFUSALS[name][0])() is not None}
 
-    def _read_tallies(self, name):
-        """``(cells per code, sum)`` of model ``name`` over the chains, read and reset; ``(None, 0.0)`` when it is off"""
-        if getattr(self, name) is None:
+    def _read_tallies(self, name, head=None):
+        """``(cells per code, sum)`` of model ``name`` -- of the target sensor, or of head ``head`` of a rig -- over the
+        chains, read and reset; ``(None, 0.0)`` when it is off"""
+        pick = (lambda ch: ch["tally"]) if head is None else (lambda ch: ch["tally"][head])   # noqa: E731
+        if not self._chains or name not in pick(self._chains[0]):
             return None, 0.0
         counts, value = None, 0.0
         for ch in self._chains:
             ch["stream"].synchronize()
-            c, v = ch["tally"][name].read()
+            c, v = pick(ch)[name].read()
             counts, value = c if counts is None else [a + b for a, b in zip(counts, c)], value + v
-            ch["tally"][name].reset()
+            pick(ch)[name].reset()
         return counts, value
+
+    def _totals(self, head=None):
+        """what a run sums of the models that are on (the target sensor's, or head ``head``'s of a rig): the summary's keys"""
+        totals, _ = self._read_tallies("returns", head)
+        noise_totals, sq_sum = self._read_tallies("noise", head)
+        echo_totals, share = self._read_tallies("echoes", head)
+        second, _ = self._read_tallies("dual", head)
+        rms = float(np.sqrt(sq_sum / noise_totals[1])) if noise_totals and noise_totals[1] else None
+        echo_mean = share / (echo_totals[1] + echo_totals[2]) if echo_totals and echo_totals[1] + echo_totals[2] else None
+        return dict(return_totals=totals, noise_totals=noise_totals, range_error_rms=rms, echo_totals=echo_totals,
+                    echo_fraction_mean=echo_mean, second_returns=second[1] if second else None)
+
+    @staticmethod
+    def _add_tallies(tally, out):
+        """one scan's result ``out`` into the accumulators ``tally`` of its sensor, on the current stream"""
+        import torch
+        if "returns" in tally:               # cells per code
+            tally["returns"].add(out["drop"])
+        if "noise" in tally:                 # cells per state and the squared range error (float64)
+            tally["noise"].add(out["noise_state"], torch.linalg.vector_norm(out["range_error"], dtype=torch.float64) ** 2)
+        if "echoes" in tally:                # cells per number of echoes (two stand for several), the reported shares
+            tally["echoes"].add(out["n_echoes"].clamp(max=2), out["echo_fraction"].sum(dtype=torch.float64))
+        if "dual" in tally:                  # second returns that stand after the models (code 1) and those that do not
+            tally["dual"].add((out["second"]["tri"].reshape(-1) >= 0).to(torch.uint8))
+
+    # ---- the files of an output scan ----------------------------------------------------------------------------------------
+    def file_sets(self):
+        """the folders of an output scan's file pairs, relative to ``<out_dir>/sequences``: the sequence's own -- or, with a
+        rig, ``SS/NAME`` per head, and ``SS`` for the merged scan when the approach says ``rig_merged``"""
+        if self.rig is None:
+            return [self.sequence]
+        return [os.path.join(self.sequence, n) for n in self.rig_names] + ([self.sequence] if self.approach.rig_merged else [])
+
+    def _host_copy(self, b, l):
+        """the packed rows on their way into pinned memory, on the current stream -> ``(points, labels, n)``"""
+        torch = self._torch
+        n = int(b.shape[0])
+        hb = torch.empty((max(n, 1), 4), dtype=torch.float32, pin_memory=True)
+        hl = torch.empty((max(n, 1),), dtype=torch.int32, pin_memory=True)
+        if n:
+            hb[:n].copy_(b, non_blocking=True)
+            hl[:n].copy_(l, non_blocking=True)
+        return hb, hl, n
+
+    def _work_rig(self, ch, job, st):
+        """:meth:`_work` for a rig: one ``RigDeform`` call, then tallies, packing and files per head (and the merged pair)"""
+        torch = self._torch
+        dd, clouds = ch["dd"], job["clouds"]
+        if self.adaption == "mesh":
+            outs = dd.mesh(clouds, pack=False, scan_index=job["idx"])
+        else:
+            outs = dd.mergemesh(clouds, pack=False, seq=job["k"], scan_index=job["idx"])
+            job["bnds_after"] = np.array(outs[0]["vol_bnds_after"]).reshape(3, 2)
+        packed = []
+        for k, (name, out) in enumerate(zip(self.rig_names, outs)):
+            self._add_tallies(ch["tally"][name], out)
+            packed.append(dd.pack_head(out, k, st))
+        job["sensors"] = {name: dict(n_points=int(b.shape[0])) for name, (b, _) in zip(self.rig_names, packed)}
+        if self.approach.rig_merged:
+            packed.append(dd.merged_rows(outs, st))
+            job["n_points"] = int(packed[-1][0].shape[0])
+        else:
+            job["n_points"] = sum(v["n_points"] for v in job["sensors"].values())
+        if self._writer is not None:
+            files = [(output_paths(self.out_dir, d, job["idx"]),) + self._host_copy(b, l) for d, (b, l) in zip(self.file_sets(), packed)]
+            ev = torch.cuda.Event()
+            ev.record(st)
+            job["keep"] = (packed, outs)
+            self._writer.q.put((job, files, ev))
+        else:
+            job["written"].set()
 
     # ---- the scan list -------------------------------------------------------------------------------------------------
     def scan_indices(self, offset=0, one_scan=False):
@@ -345,6 +462,9 @@ class SequenceTransfer:
                 if job["skipped"]:                   # resume: only mergemesh's bounds are replayed
                     dd.mergemesh_bounds(clouds, seq=job["k"])
                     return
+                if self.rig is not None:
+                    self._work_rig(ch, job, st)
+                    return
                 if self.adaption == "cp":
                     out = dd.cp(clouds, pack=False)
                 elif self.adaption == "mesh":
@@ -352,29 +472,16 @@ class SequenceTransfer:
                 else:
                     out = dd.mergemesh(clouds, pack=False, seq=job["k"], scan_index=job["idx"])
                     job["bnds_after"] = np.array(out["vol_bnds_after"]).reshape(3, 2)
-                tally = ch["tally"]                  # summed on the chain's stream: read once, in run()
-                if "returns" in tally:               # cells per code
-                    tally["returns"].add(out["drop"])
-                if "noise" in tally:                 # cells per state and the squared range error (float64)
-                    tally["noise"].add(out["noise_state"], torch.linalg.vector_norm(out["range_error"], dtype=torch.float64) ** 2)
-                if "echoes" in tally:                # cells per number of echoes (two stand for several), the reported shares
-                    tally["echoes"].add(out["n_echoes"].clamp(max=2), out["echo_fraction"].sum(dtype=torch.float64))
-                if "dual" in tally:                  # second returns that stand after the models (code 1) and those that do not
-                    tally["dual"].add((out["second"]["tri"].reshape(-1) >= 0).to(torch.uint8))
+                self._add_tallies(ch["tally"], out)  # summed on the chain's stream: read once, in run()
                 if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
                     scan = ch["ev"].target_view if self.evaluate_mode == "target" else ch["ev"].source_scan
                     src = scan(*job["raw"], stream=st)
                     job["record"] = ch["ev"].compare(src, out["label"], out["range"], stream=st)
                     job["images"] = (src, out)
                 b, l = dd.pack_result(out, st)
-                n = int(b.shape[0])
-                job["n_points"] = n
+                job["n_points"] = int(b.shape[0])
                 if self._writer is not None:
-                    hb = torch.empty((max(n, 1), 4), dtype=torch.float32, pin_memory=True)
-                    hl = torch.empty((max(n, 1),), dtype=torch.int32, pin_memory=True)
-                    if n:
-                        hb[:n].copy_(b, non_blocking=True)
-                        hl[:n].copy_(l, non_blocking=True)
+                    hb, hl, n = self._host_copy(b, l)
                     ev = torch.cuda.Event()
                     ev.record(st)
                     job["keep"] = (b, l, out)
@@ -393,9 +500,14 @@ class SequenceTransfer:
         torch = self._torch
         job = dict(k=k, idx=int(idx), done=threading.Event(), written=threading.Event(), error=None, record=None, skipped=False,
                    n_points=None, bnds_after=None)
-        if resume and self.out_dir is not None and plausible_output(self.out_dir, self.sequence, idx):
-            job["skipped"] = True
-            job["n_points"] = os.path.getsize(output_paths(self.out_dir, self.sequence, idx)[0]) // 16
+        sets = self.file_sets()
+        if resume and self.out_dir is not None and all(plausible_output(self.out_dir, d, idx) for d in sets):
+            job["skipped"] = True                    # (a rig: only when EVERY file of the scan is plausible)
+            sizes = [os.path.getsize(output_paths(self.out_dir, d, idx)[0]) // 16 for d in sets]
+            job["n_points"] = sizes[0]
+            if self.rig is not None:
+                job["sensors"] = {n: dict(n_points=c) for n, c in zip(self.rig_names, sizes)}
+                job["n_points"] = sizes[-1] if self.approach.rig_merged else sum(sizes)
             job["written"].set()
             if self._mm is None:
                 job["done"].set()
@@ -423,6 +535,8 @@ class SequenceTransfer:
         rec = dict(idx=job["idx"], n_points=job["n_points"], m_iou=None, m_acc=None, MSE=None, iou=None, skipped=job["skipped"])
         if job["bnds_after"] is not None:
             rec["bnds_after"] = job["bnds_after"]
+        if self.rig is not None:
+            rec["sensors"] = job.get("sensors")
         compared = self.evaluate_mode == "target"    # a sparse reference image: how many cells were compared at all
         if compared:
             rec.update(n_compared=None, MSE_compared=None)
@@ -442,6 +556,7 @@ class SequenceTransfer:
                     rec.update(n_compared=nc, MSE_compared=float(m["range_diff"].astype(np.float64).sum()) / nc if nc else None)
         if self.out_dir is not None and not self._copied and not job["skipped"]:
             base = os.path.join(self.out_dir, "sequences", self.sequence)
+            os.makedirs(base, exist_ok=True)         # (a rig without a merged scan writes into its heads' folders only)
             for p in self.copy_files:
                 shutil.copy2(p, base)
             self._copied = True
@@ -474,19 +589,14 @@ class SequenceTransfer:
             for job in pending:                          # (a failure or an abandoned generator: let what is queued finish)
                 job["done"].wait()
                 job["written"].wait()
-            totals, _ = self._read_tallies("returns")
-            noise_totals, sq_sum = self._read_tallies("noise")
-            echo_totals, share = self._read_tallies("echoes")
-            second, _ = self._read_tallies("dual")
-            rms = float(np.sqrt(sq_sum / noise_totals[1])) if noise_totals and noise_totals[1] else None
-            echo_mean = share / (echo_totals[1] + echo_totals[2]) if echo_totals and echo_totals[1] + echo_totals[2] else None
-            self.summary = dict(return_totals=totals, noise_totals=noise_totals, range_error_rms=rms, echo_totals=echo_totals,
-                                echo_fraction_mean=echo_mean, second_returns=second[1] if second else None, scans=n_done,
+            self.summary = dict(**self._totals(), scans=n_done,
                                 chains=self.chains, adaption=self.adaption, fusion=self.fusion,
                                 mounted=self.mounted, beam_model=self.beam_model, azimuth_model=self.azimuth_model,
                                 beam_azimuth=self.beam_azimuth is not None,
                                 mm_stats=dict(self._mm.stats) if self._mm is not None else None,
                                 source_stats=dict(self.source.stats))
+            if self.rig is not None:                     # the tallies are kept per head
+                self.summary["sensors"] = {name: self._totals(name) for name in self.rig_names}
 
     def close(self):
         for ch in getattr(self, "_chains", []):
