@@ -109,21 +109,14 @@ def main(argv=None):
         print(e)
         print("Error opening yaml file.")
         return 1
-    from .sequence import SequenceTransfer
-    if rig is not None:
-        pass   # (cp was refused above; mesh and mergemesh take every model of every head)
-    elif target.return_model() is not None and approach.adaption == "cp":
-        print("adaption cp renders no surface: the target sensor's return_model cannot be applied (use mesh or mergemesh).")
-        return 1
-    if rig is None and target.noise_model() is not None and approach.adaption == "cp":
-        print("adaption cp renders no ray: the target sensor's noise_model cannot be applied (use mesh or mergemesh).")
-        return 1
-    if rig is None and target.echo_model() is not None and approach.adaption == "cp":
-        print("adaption cp renders no ray: the target sensor's echo_model cannot be applied (use mesh or mergemesh).")
-        return 1
-    if rig is None and target.dual_return() is not None and approach.adaption == "cp":
-        print("adaption cp renders no ray: the target sensor's dual_return cannot be applied (use mesh or mergemesh).")
-        return 1
+    from ._chain import CP_REFUSALS
+    from .sequence import SequenceTransfer, format_closing_lines
+    if approach.adaption == "cp":   # (a rig was refused above; mesh and mergemesh take every model of every head)
+        for name in ("returns", "noise", "echoes", "dual"):
+            key, _, what, _ = CP_REFUSALS[name]
+            if getattr(target, key)() is not None:
+                print(f"adaption cp renders no {what}: the target sensor's {key} cannot be applied (use mesh or mergemesh).")
+                return 1
     log = open(args.log, "w") if args.log else None
     try:
         with SequenceTransfer((args.dataset, args.sequence), approach, source, target if rig is None else None,
@@ -157,27 +150,10 @@ def main(argv=None):
                     if tr.dual is not None:
                         row["dual_return"] = True
                     log.write(json.dumps(row) + "\n")
-            for name, totals in (tr.summary.get("sensors") or {}).items():   # a rig: the closing lines per head
-                from .sequence import format_echo_totals, format_noise_totals, format_return_totals
-                if totals["return_totals"] is not None:
-                    print(name + ": " + format_return_totals(totals["return_totals"]), flush=True)
-                if totals["noise_totals"] is not None:
-                    print(name + ": " + format_noise_totals(totals["noise_totals"], totals["range_error_rms"]), flush=True)
-                if totals["echo_totals"] is not None:
-                    print(name + ": " + format_echo_totals(totals["echo_totals"], totals["echo_fraction_mean"]), flush=True)
-                if totals["second_returns"] is not None:
-                    print(name + ": Second returns: %d" % totals["second_returns"], flush=True)
-            if tr.summary.get("return_totals") is not None:
-                from .sequence import format_return_totals
-                print(format_return_totals(tr.summary["return_totals"]), flush=True)
-            if tr.summary.get("noise_totals") is not None:
-                from .sequence import format_noise_totals
-                print(format_noise_totals(tr.summary["noise_totals"], tr.summary["range_error_rms"]), flush=True)
-            if tr.summary.get("echo_totals") is not None:
-                from .sequence import format_echo_totals
-                print(format_echo_totals(tr.summary["echo_totals"], tr.summary["echo_fraction_mean"]), flush=True)
-            if tr.summary.get("second_returns") is not None:
-                print("Second returns: %d" % tr.summary["second_returns"], flush=True)
+            heads = [(name + ": ", totals) for name, totals in (tr.summary.get("sensors") or {}).items()]   # a rig: per head
+            for lead, totals in heads + [("", tr.summary)]:
+                for line in format_closing_lines(totals, lead):
+                    print(line, flush=True)
             if log is not None:
                 log.write(json.dumps(dict(summary=tr.summary)) + "\n")
     finally:

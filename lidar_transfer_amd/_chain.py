@@ -1,8 +1,9 @@
 """What the chain layer (``deform.py``, ``pipeline.py``, ``sequence.py``) hands the library's device entry points, in one
 place: the merged cloud, the ``lt_cloud`` and beam tables, origin and output pointers, and -- :class:`Sensing` -- what
 stands between a chain's render and its result: the target sensor's mounting, its echo, return and noise models and its
-dual-return setting.  The chain layer makes one :class:`Sensing` per chain and calls ``plan``, its native call(s) with
-``render_set`` and ``out_ptrs(sub)``, then ``finish``; the order of the models lives there and nowhere else.
+dual-return setting; the order of the models lives there and nowhere else.  :class:`TargetHead` is a target sensor on a
+chain -- shape, model, ``Sensing``, ray set, origin -- and the steps of its scan: ``plan``, the chain's native call(s) with
+``render_set`` and ``out_ptrs(sub)``, ``finish``; :func:`pack_result` packs any head's result for the files.
 Private; imports without a GPU and without the library (torch and numpy on first use)."""
 from __future__ import annotations
 
@@ -80,6 +81,15 @@ def with_tri(rout, n_rays, device):
     return rout
 
 
+def need_scan_index(scan_index, what, lead=None):
+    """THE refusal of a missing ``scan_index``: ``ValueError`` when it is ``None``.  ``what``: the model(s) whose draws need it
+    (``"return"``, ``"noise"``, ``"return or noise"``); ``lead``: the chain-layer caller the message is led by
+    (:meth:`TargetHead.need_scan_index`), none for the models' own ``apply``"""
+    if scan_index is None:
+        raise ValueError(f"{lead}: a {what} model needs scan_index, the output scan's index in its sequence" if lead else
+                         f"a {what} model needs the output scan's index in its sequence (scan_index=)")
+
+
 class Returns:
     """The target sensor's return model on a chain (``config.ReturnModel`` or ``None``).  ``None``, or a model
     with every field at its default: nothing here allocates or launches.  Applied once per output scan, to the render that
@@ -107,8 +117,7 @@ class Returns:
         with for this call (a scan's second return)"""
         if self.model is None:
             return {}
-        if scan is None:
-            raise ValueError("a return model needs the output scan's index in its sequence (scan_index=)")
+        need_scan_index(scan, "return")
         from . import post
         more = dict(seed_xor=seed_xor) if seed_xor else {}   # (0: today's call, argument for argument)
         return post.return_model(scene, rays, self.model, scan, rout, label_image=label_image, stream=stream, **more)
@@ -144,8 +153,7 @@ class Noise:
         for :meth:`Returns.apply`"""
         if self.model is None:
             return {}
-        if scan is None:
-            raise ValueError("a noise model needs the output scan's index in its sequence (scan_index=)")
+        need_scan_index(scan, "noise")
         from . import post
         more = dict(seed_xor=seed_xor) if seed_xor else {}
         return post.noise_model(origin, self.model, scan, rout, gate=self.gate, label_image=label_image, stream=stream, **more)
@@ -421,3 +429,136 @@ class Sensing:
     def close(self):
         """closes the sub-ray set when this object owns it (a bound :class:`Echoes` handed in is shared)"""
         self.echoes.close()
+
+
+class TargetHead:
+    """A target sensor on a chain, ONE object for the target of a ``DeviceDeform`` and for a further head of a rig
+    (``rig.Head``): its shape (``t_H``, ``t_W``, ``t_fov_up``, ``t_fov_down``, ``n_rays``), its validated ``t_model``
+    (``config.TargetModel`` of ``beam_table``, ``sector``, ``beam_azimuth``), its :class:`Sensing` (``sensing``, of
+    ``transformation`` and the four models), its posed rays in a read-only ``RaySet`` (``rayset``) and where they start in the
+    scene (``origin``); ``who`` leads every message.  ``rayset``: a shared ray set of the same sensor at the same pose --
+    checked, taken and not closed here; ``echoes`` may likewise be a bound :class:`Echoes`.  ``cast=False``: a chain that
+    renders no ray (``cp`` without a scene) -- no ray set is made and nothing is bound.
+    A scan is :meth:`need_scan_index`, :meth:`plan`, the chain's native render(s) with ``render_set`` and
+    ``out_ptrs(plan[2])``, then :meth:`finish`."""
+
+    def __init__(self, shape, transformation, returns, noise, echoes, dual, who, device, beam_table=None, sector=None,
+                 beam_azimuth=None, rayset=None, cast=True):
+        import torch
+
+        from .config import TargetModel
+        self.who = who
+        self.t_H, self.t_W, self.t_fov_up, self.t_fov_down = int(shape[0]), int(shape[1]), float(shape[2]), float(shape[3])
+        self.n_rays = self.t_H * self.t_W
+        self.device = torch.device("cuda", int(device))
+        # what stands between the render and the result (and the only place that knows its order)
+        s = self.sensing = Sensing(transformation, returns, noise, echoes, who, dual)
+        m = self.t_model = TargetModel(beam_table, sector, beam_azimuth, who).validate(self.t_H, (self.t_fov_up, self.t_fov_down), who)
+        self.origin = s.origin       # the target sensor in the scene, where its rays are cast from by default
+        self.rayset, self._own = None, rayset is None
+        if not cast:
+            return
+        pose = s.P
+        if rayset is None:
+            from .laserscan import create_rays_device
+            from .raytracer import RaySet
+            keys = dict(beam_table=m.beam_table, sector=m.sector, beam_azimuth=m.beam_azimuth)
+            rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=int(device),
+                                      rot=pose[:3, :3] if pose is not None else None, **keys)
+            rayset = RaySet(rays, self.t_H, pose=pose, grid=m.grid(self.t_W), **keys)
+        else:
+            import numpy as np
+            theirs = getattr(rayset, "pose", None)
+            if (theirs is None) != (pose is None) or (pose is not None and not np.array_equal(theirs, pose)):
+                raise ValueError(f"{who}: the shared rayset was built for another sensor pose than `transformation`")
+            differs = m.difference(rayset.model)
+            if differs is not None:
+                what = dict(beam_table="another beam table", sector="another sector",
+                            beam_azimuth="other beam azimuth offsets")[differs]
+                raise ValueError(f"{who}: the shared rayset was built for {what} than `t_{differs}`")
+        self.rayset = rayset
+        # (the central rays stay in ``rayset.rays``: the return model reads its directions from them)
+        s.bind(rayset.rays, self.t_H, grid=rayset.grid, table=m.beam_table is not None)
+
+    @property
+    def render_set(self):
+        """the ray set the chain renders this head with (``Sensing.render_set``: the sub-ray set of an echo model)"""
+        return self.sensing.render_set(self.rayset)
+
+    def need_scan_index(self, scan_index, where=None):
+        """``ValueError`` when a return or a noise model is on and ``scan_index`` is missing; ``where``: the method that
+        leads the message and is told which model (``DeviceDeform.mesh``), default: ``who``, told both"""
+        if self.sensing.needs_scan_index:
+            need_scan_index(scan_index, "return or noise" if where is None else "return" if self.sensing.returns else "noise",
+                            where or self.who)
+
+    def plan(self, scene, out=None):
+        """``(out, rout, sub)`` of a scan on ``scene``: its outputs (``Scene.alloc_outputs`` unless the caller brings ``out``)
+        and their :meth:`Sensing.plan`.  Allocates on the current stream."""
+        if out is None:
+            out = scene.alloc_outputs(self.n_rays, label_image=True)
+        return (out,) + self.sensing.plan(out, self.n_rays, self.device)
+
+    def finish(self, plan, scan_index, scene, mesh, stream, origin=None, **more):
+        """:meth:`Sensing.finish` behind the render of ``plan`` with this head's rays, cast from ``origin`` (default: its
+        own), and what ``mesh`` / ``mergemesh`` return of the scan: the images, ``endpoints`` in the target's frame,
+        ``endpoints_scene`` and ``tri`` as rendered, the sizes of ``mesh`` (the ``DeviceMesh`` that was rendered), ``more``
+        and what the models add"""
+        out, rout, sub = plan
+        seen = self.sensing.finish(out, rout, sub, scan_index, scene, self.rayset.rays, self.origin if origin is None else origin,
+                                   stream)
+        H, W = self.t_H, self.t_W
+        return dict(range=out["range"].view(H, W), rem=out["endrem"].view(H, W), label=out["endcolors"].view(H, W),
+                    endpoints=out["endpoints"], endpoints_scene=rout["endpoints"], tri=rout["tri"],
+                    n_verts=mesh.n_verts, n_faces=mesh.n_faces, **more, **seen)
+
+    def pack(self, res, stream, scene_frame=False, rows=None):
+        """:func:`pack_result` of this head's result ``res``"""
+        return pack_result(res, self.n_rays, self.device, stream, scene_frame, rows)
+
+    def close(self):
+        """closes the sub-ray set and the ray set when this head owns them"""
+        self.sensing.close()
+        if self._own and self.rayset is not None:
+            self.rayset.close()
+        self.rayset = None
+
+
+def pack_rows(points, is_f64, rem, label, index, n, stream, device):
+    """``lt_pack_scan_dev`` (the one place it is called from on a chain; ``DeviceDeform._pack`` is this on the chain's
+    device): ``n`` cells of ``points`` [n, 3] (float64 with
+    ``is_f64``), ``rem``, ``label`` and ``index`` (or ``None``: no index filter) -> ``(bin [N, 4] f32, label_file [N] i32)``.
+    Allocates on the current stream; reads the number of kept points back."""
+    import torch
+    out_bin = torch.empty((n, 4), dtype=torch.float32, device=device)
+    out_lab = torch.empty((n,), dtype=torch.int32, device=device)
+    kept = C.c_int(0)
+    _lib.check(_lib.load().lt_pack_scan_dev(points.data_ptr(), int(is_f64), rem.data_ptr(), label.data_ptr(),
+                                            index.data_ptr() if index is not None else None, n, out_bin.data_ptr(),
+                                            out_lab.data_ptr(), C.byref(kept), C.c_void_p(stream.cuda_stream)), "lt_pack_scan_dev")
+    return out_bin[:kept.value], out_lab[:kept.value]
+
+
+def pack_result(res, n_rays, device, stream, scene_frame=False, rows=None):
+    """``write``'s filter + packing (laserscan.py:1133-1178) of a scan's result ``res`` of ``n_rays`` cells, on ``stream`` ->
+    ``(bin [N, 4] f32, label_file [N] i32)``, for any head.  ``cp`` packs its float64 ``back_points`` where ``index > 0``
+    (:1133-1144); the mesh adaptions their float32 ``endpoints``, no index filter (:1145-1148) -- with ``scene_frame`` their
+    ``endpoints_scene``, the primary scan's frame.  A dual-return result packs both of its planes in the ONE call: the
+    primary's rows in cell order, then the second returns'.  ``rows``: what packs the rows, called as :func:`pack_rows`
+    without the device (a ``DeviceDeform`` hands in its ``_pack``); default: :func:`pack_rows` on ``device``."""
+    import torch
+    n = int(n_rays)
+    if rows is None:
+        rows = lambda *a: pack_rows(*a, device)   # noqa: E731
+    with torch.cuda.device(device), torch.cuda.stream(stream):
+        if res.get("second") is not None:
+            planes = res["second"]["_planes"]
+            points = planes["endpoints"]
+            if scene_frame:
+                points = torch.cat([res["endpoints_scene"], res["second"]["endpoints_scene"]])
+            return rows(points, False, planes["rem"], planes["label"], None, 2 * n, stream)
+        rem, label = res["rem"].reshape(-1), res["label"].reshape(-1)
+        if "back_points" in res:
+            return rows(res["back_points"], True, rem, label, res["index"].reshape(-1), n, stream)
+        points = res["endpoints_scene" if scene_frame else "endpoints"].contiguous()
+        return rows(points, False, rem, label, None, n, stream)

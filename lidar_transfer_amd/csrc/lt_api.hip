@@ -126,11 +126,7 @@ extern "C" int lt_scene_destroy(lt_scene* s) {
   if (s->tail_meta) (void)hipFree(s->tail_meta);
   if (s->tail_queue) (void)hipFree(s->tail_queue);
   if (s->tail_count) (void)hipFree(s->tail_count);
-  if (s->sc_cell) (void)hipFree(s->sc_cell);
-  if (s->sc_large) (void)hipFree(s->sc_large);
-  if (s->sc_slices) (void)hipFree(s->sc_slices);
-  if (s->sc_large_count) (void)hipFree(s->sc_large_count);
-  for (lt_sc_state& t : s->sc_rig)
+  for (lt_sc_state& t : s->sc)
     for (void* p : {(void*)t.cell, (void*)t.large, (void*)t.slices, (void*)t.large_count})
       if (p) (void)hipFree(p);
   for (int k = 0; k < s->have_events; ++k) (void)hipEventDestroy(s->ev[k]);

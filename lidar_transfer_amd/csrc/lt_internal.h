@@ -78,13 +78,18 @@ bool beam_azimuth_ok(const char* who, const double* az, int n);
 #define LT_TAIL_DFS 256
 #define LT_TRACE4_STEP_CAP 40  // node + leaf steps a ray may take in k_trace4 before it is handed over (LIDARHIP_STEP_CAP)
 
-// Render state of ONE sensor of a rig on a scene (lt_scatter.hip): what sc_cell .. sc_cap_queue of lt_scene are for the first
-#define LT_SC_RIG_SLOTS 7
+// Render state of ONE sensor on a scene (lt_scatter.hip): the state of the render in flight is per SCENE, so that a ray set
+// is read-only during a render and one ray set (one sensor model) serves any number of scenes and streams at once.  A scene
+// has one slot per scan of a batch: slot 0 is the scene's own, which every single and batch render uses, slot k > 0 that of
+// sensor k of a rig (lt_scene_render_rig_dev).  A slot is empty until a render needs it (sc_reserve).
+#ifndef LT_SC_MAX_BATCH
+#define LT_SC_MAX_BATCH 8  // scans per launch of the scatter kernels: the size of their job table
+#endif
 struct lt_sc_state {
-  unsigned long long* cell;  // [cap_cells]
-  int* large;                // [cap_queue]
-  int2* slices;              // [cap_queue]
-  int* large_count;          // [4]
+  unsigned long long* cell;  // [cap_cells] packed (t, face) z-min per ray; all-ones = empty, re-armed by k_sc_resolve
+  int* large;                // [cap_queue] queue of big triangles
+  int2* slices;              // [cap_queue] queue of (block, first candidate) slices
+  int* large_count;          // [4]: [0] queued big triangles, [1] queued slices; reset by k_sc_resolve
   int cap_cells, cap_queue, cap_count;
 };
 
@@ -121,16 +126,7 @@ struct lt_scene {
   int* tail_count;      // [2] rays queued by the launch in flight; used alternately (tail_parity), each launch's
                         // tail kernel zeroes the counter of the next one
   int tail_parity;
-  // scatter strategy (lt_scatter.hip): state of the render in flight -- per SCENE, so that a ray set is read-only
-  // during a render and one ray set (one sensor model) serves any number of scenes and streams at once
-  unsigned long long* sc_cell;  // [sc_cap_cells] packed (t, face) z-min per ray; all-ones = empty, re-armed by k_sc_resolve
-  int* sc_large;                // [sc_cap_queue] queue of big triangles
-  int2* sc_slices;              // [sc_cap_queue] queue of (block, first candidate) slices
-  int* sc_large_count;          // [4]: [0] queued big triangles, [1] queued slices; reset by k_sc_resolve
-  int sc_cap_cells, sc_cap_queue;
-  // ... and of the further sensors of a rig (lt_scene_render_rig_dev): sensor k > 0 renders into slot k - 1, sensor 0 into the
-  // members above.  Empty until a rig needs them.
-  lt_sc_state sc_rig[LT_SC_RIG_SLOTS];
+  lt_sc_state sc[LT_SC_MAX_BATCH];  // scatter strategy (lt_scatter.hip): render state, slot 0 the scene's own
   int built;
   int sorted_buf;        // which of keys[] / vals[] holds the sorted pairs of the last build (lt_sort_pairs' *out_buffer)
   hipStream_t last_stream;

@@ -759,9 +759,7 @@ __device__ __forceinline__ void sc_count(unsigned n_tests, unsigned n_cand, unsi
 // between kernels than the kernels need.  Every kernel below therefore takes a BATCH of
 // scans: the per-scan arguments live in a job table passed by value (kernel arguments: scalar registers), and a
 // workgroup looks up its scan from its block index.  A batch of one is the single-scan API.
-#ifndef LT_SC_MAX_BATCH
-#define LT_SC_MAX_BATCH 8
-#endif
+// (LT_SC_MAX_BATCH: lt_internal.h)
 struct sc_job {
   const float* verts; const int* faces; const int* colors; const float* rem;  // the scan's mesh
   rs_params P; const float4* grid; const float4* sdirs; const float4* dirs;  // its ray set (P: by value, see lt_rayset)
@@ -1091,44 +1089,26 @@ extern "C" int lt_rayset_create_grid_dev(lt_rayset** out, const float* rays, int
   return rs_create("lt_rayset_create_grid_dev", out, rays, n_rays, height, nb_az, nb_el, flags, stream);
 }
 
-// Per-scene state of a render: the z-min cells (one per ray, armed = all-ones; k_sc_resolve re-arms what it reads,
-// so they are set once per allocation) and the queues of k_sc_tris -- every triangle is queued at most once as
-// "big", and a block of LT_SC_T triangles with <= LT_SC_BIG candidates each leaves at most
-// LT_SC_T * LT_SC_BIG / LT_SC_SLICE = LT_SC_T slices.
-static int sc_reserve(lt_scene* s, int n_faces, int n_rays, hipStream_t stream) {
-  if (!s->sc_large_count) {
-    LT_HIP(hipMalloc((void**)&s->sc_large_count, 4 * sizeof(int)));
-    LT_HIP(hipMemsetAsync(s->sc_large_count, 0, 4 * sizeof(int), stream));
-  }
-  if (n_rays > s->sc_cap_cells) {
-    LT_CHECK(lt_dev_grow("lt_scene_render", lt_wait_device(), &s->sc_cell, &s->sc_cap_cells, (size_t)n_rays, (size_t)n_rays));
-    LT_HIP(hipMemsetAsync(s->sc_cell, 0xFF, (size_t)n_rays * sizeof(unsigned long long), stream));
-  }
-  if (n_faces > s->sc_cap_queue) {
-    const size_t cap = lt_headroom((size_t)n_faces);
-    const lt_dev_array queues[] = {{(void**)&s->sc_large, cap * sizeof(int)}, {(void**)&s->sc_slices, cap * sizeof(int2)}};
-    LT_CHECK(lt_dev_replace("lt_scene_render", lt_wait_device(), &s->sc_cap_queue, (int)cap, queues));
-  }
-  return LT_OK;
-}
-
-// The same for a render-state slot of a rig (lt_internal.h): created on first use, grown like the scene's own.
-static int sc_reserve_slot(lt_sc_state& t, int n_faces, int n_rays, hipStream_t stream) {
+// A render-state slot of a scene (lt_sc_state, lt_internal.h), made on first use and grown like any workspace: the z-min
+// cells (one per ray, armed = all-ones; k_sc_resolve re-arms what it reads, so they are set once per allocation) and the
+// queues of k_sc_tris -- every triangle is queued at most once as "big", and a block of LT_SC_T triangles with
+// <= LT_SC_BIG candidates each leaves at most LT_SC_T * LT_SC_BIG / LT_SC_SLICE = LT_SC_T slices.  `who` leads a failure.
+static int sc_reserve(lt_sc_state& t, const char* who, int n_faces, int n_rays, hipStream_t stream) {
   if (!t.large_count) {
     // (wait: none -- there is no old array)
-    LT_CHECK(lt_dev_grow("lt_scene_render_rig", lt_wait_none(), &t.large_count, &t.cap_count, 4, 4));
+    LT_CHECK(lt_dev_grow(who, lt_wait_none(), &t.large_count, &t.cap_count, 4, 4));
     LT_HIP(hipMemsetAsync(t.large_count, 0, 4 * sizeof(int), stream));
   }
   if (n_rays > t.cap_cells) {
-    // (wait: the device -- an earlier rig's kernels, on any stream, may still read and re-arm the old cells)
-    LT_CHECK(lt_dev_grow("lt_scene_render_rig", lt_wait_device(), &t.cell, &t.cap_cells, (size_t)n_rays, (size_t)n_rays));
+    // (wait: the device -- an earlier render's kernels, on any stream, may still read and re-arm the old cells)
+    LT_CHECK(lt_dev_grow(who, lt_wait_device(), &t.cell, &t.cap_cells, (size_t)n_rays, (size_t)n_rays));
     LT_HIP(hipMemsetAsync(t.cell, 0xFF, (size_t)n_rays * sizeof(unsigned long long), stream));
   }
   if (n_faces > t.cap_queue) {
     const size_t cap = lt_headroom((size_t)n_faces);
     const lt_dev_array queues[] = {{(void**)&t.large, cap * sizeof(int)}, {(void**)&t.slices, cap * sizeof(int2)}};
     // (wait: the device -- as for the cells)
-    LT_CHECK(lt_dev_replace("lt_scene_render_rig", lt_wait_device(), &t.cap_queue, (int)cap, queues));
+    LT_CHECK(lt_dev_replace(who, lt_wait_device(), &t.cap_queue, (int)cap, queues));
   }
   return LT_OK;
 }
@@ -1139,7 +1119,7 @@ struct sc_item {  // host view of one scan of a batch
   lt_rayset* r;
   const float* origin;
   lt_scan_images images;
-  int slot;  // render state: 0 = the scene's own members, k > 0 = s->sc_rig[k - 1] (a rig's further sensors)
+  int slot;  // render state: s->sc[slot]; 0 = the scene's own, k > 0 = sensor k of a rig
 };
 
 // Three launches for the whole batch (k_sc_tris, k_sc_rest, k_sc_resolve) on `stream`.  `probe` = the scene
@@ -1159,18 +1139,16 @@ static int sc_launch_batch(const sc_item* it, int n_items, unsigned flags, hipSt
     lt_rayset* r = it[i].r;
     const int n = s->n_faces, R = r->n_rays;
     if (R <= 0) continue;  // nothing to write for this scan
-    lt_sc_state* slot = it[i].slot > 0 ? &s->sc_rig[it[i].slot - 1] : nullptr;
-    if (slot) LT_CHECK(sc_reserve_slot(*slot, n, R, stream));
-    else LT_CHECK(sc_reserve(s, n, R, stream));
+    lt_sc_state& t = s->sc[it[i].slot];
+    LT_CHECK(sc_reserve(t, it[i].slot ? "lt_scene_render_rig" : "lt_scene_render", n, R, stream));
     sc_job& J = B.job[B.n++];
     J.verts = s->verts; J.faces = s->faces; J.colors = s->colors; J.rem = s->rem;
     J.P = r->prm_host; J.grid = r->grid; J.sdirs = r->sdirs; J.dirs = r->dirs;
-    J.cell = s->sc_cell; J.large = s->sc_large; J.large_count = s->sc_large_count; J.slices = s->sc_slices;
-    if (slot) { J.cell = slot->cell; J.large = slot->large; J.large_count = slot->large_count; J.slices = slot->slices; }
+    J.cell = t.cell; J.large = t.large; J.large_count = t.large_count; J.slices = t.slices;
     J.flags = s->flags; J.counters = s->counters;
     J.images = it[i].images;
     J.ox = it[i].origin[0]; J.oy = it[i].origin[1]; J.oz = it[i].origin[2];
-    J.n_verts = s->n_verts; J.n_faces = n; J.n_rays = R; J.cap_slices = slot ? slot->cap_queue : s->sc_cap_queue;
+    J.n_verts = s->n_verts; J.n_faces = n; J.n_rays = R; J.cap_slices = t.cap_queue;
     J.out_flags = flags;
     B.tris_block0[B.n - 1] = tb;
     B.resolve_block0[B.n - 1] = rb;
@@ -1301,8 +1279,8 @@ extern "C" int lt_scene_render_batch_dev(int n_scans, lt_scene* const* scenes, l
   return sc_launch_batch(it, n_scans, flags, stream, false, probe ? probe : scenes[0]);
 }
 
-// A rig: one scene, its current mesh, up to LT_SC_MAX_BATCH sensors (include/lidarhip.h).  Sensor 0 renders into the scene's
-// own cells and queues, sensor k into slot k - 1; the mesh and the error bits are shared by all jobs.
+// A rig: one scene, its current mesh, up to LT_SC_MAX_BATCH sensors (include/lidarhip.h).  Sensor k renders into the scene's
+// render-state slot k (slot 0: the one every single render uses); the mesh and the error bits are shared by all jobs.
 extern "C" int lt_scene_render_rig_dev(lt_scene* s, int n_sensors, lt_rayset* const* raysets, const float* origins,
                                        float* const* endpoints, int* const* endcolors, float* const* range,
                                        float* const* endrem, int* const* tri, unsigned flags, void* stream_) {
@@ -1362,10 +1340,10 @@ extern "C" int lt_debug_scatter_queues(lt_scene* s, int* out2) {
   return LT_OK;
 }
 extern "C" int lt_debug_scatter_large(lt_scene* s, int* out, int n) {
-  if (!s || !out || n < 0 || n > s->sc_cap_queue) return LT_ERR_INVALID_ARG;
+  if (!s || !out || n < 0 || n > s->sc[0].cap_queue) return LT_ERR_INVALID_ARG;
   LT_HIP(hipSetDevice(s->device));
   LT_HIP(hipDeviceSynchronize());
-  LT_HIP(hipMemcpy(out, s->sc_large, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  LT_HIP(hipMemcpy(out, s->sc[0].large, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   return LT_OK;
 }
 // the bin grid a ray set was given (prm_host): nb = (nb_az, nb_el), p = (az_scale, az_off, el_lo, el_scale, dev_az, dev_el)

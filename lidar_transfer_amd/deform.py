@@ -33,7 +33,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _chain, _lib
-from .raytracer import RaySet, Scene
+from .raytracer import Scene
 
 
 class MergeMeshState:
@@ -149,7 +149,7 @@ class DeviceDeform:
         from ``float32(tp)`` into the scene, which is still fused in the primary scan's frame, and the hits' ``endpoints``
         are brought into the target's frame by ``T`` (``endpoints_scene``: as rendered); ``cp`` takes its cloud into the
         target frame on ingest (:meth:`deform`).  Empty, ``None`` or the identity: none of this runs.  A shared ``rayset``
-        must have been built for the same pose (``RaySet(..., pose=P)``).
+        must have been built for the same pose (a ``RaySet`` with ``pose=P``; ``_chain.TargetHead`` checks it).
         ``t_beam_table``, ``t_sector``, ``t_beam_azimuth``: the fields of the TARGET sensor's
         :class:`~lidar_transfer_amd.config.TargetModel` (``SensorModel.target_model()``; kept as ``t_model``, validated against
         ``target``; each ``None``: nothing of it runs).  The target's rays are the model's (turned by the pose of a
@@ -185,15 +185,13 @@ class DeviceDeform:
         import numpy as np
         import torch
 
-        from .config import TargetModel
         from .fusion import DeviceMesh, TSDFVolume
-        from .laserscan import Projector, create_rays_device
+        from .laserscan import Projector
         self._torch = torch
         self._lib = _lib.load()
         idx = torch.cuda.current_device() if device is None else int(device)
         self.device = torch.device("cuda", idx)
         self.H, self.W, self.fov_up, self.fov_down = int(source[0]), int(source[1]), float(source[2]), float(source[3])
-        self.t_H, self.t_W, self.t_fov_up, self.t_fov_down = int(target[0]), int(target[1]), float(target[2]), float(target[3])
         self.beam_angles = sorted(beam_angles) if beam_angles else None      # laserscan.py:732-735
         # the reference reads the TARGET's beam angles from the source config (laserscan.py:744)
         self.t_beam_angles = sorted(t_beam_angles) if t_beam_angles else self.beam_angles
@@ -205,20 +203,20 @@ class DeviceDeform:
         self._mm_vols = {}   # mergemesh: geometry -> TSDFVolume (the clipped bounds settle after a few output scans)
         self.vol_bnds = None
         self._mm_state, self._mm_own = mm_state, mm_state is None
-        self._rayset_own = rayset is None
-        # what stands between the render and the result (and the only place that knows its order)
-        s = self._sensing = _chain.Sensing(transformation, returns, noise, echoes, "DeviceDeform", dual)
+        if mm_state is not None and vol_bnds is None:
+            vol_bnds = mm_state.vol_bnds
+        # the target sensor: shape, model, what stands between the render and the result, rays (with a scene to cast at), origin
+        h = self.head = _chain.TargetHead(target, transformation, returns, noise, echoes, dual, "DeviceDeform", idx, t_beam_table,
+                                          t_sector, t_beam_azimuth, rayset=rayset, cast=vol_bnds is not None)
+        s = self._sensing = h.sensing
+        self.t_H, self.t_W, self.t_fov_up, self.t_fov_down, self.n_rays = h.t_H, h.t_W, h.t_fov_up, h.t_fov_down, h.n_rays
         self._mounting, self._returns, self._noise, self._echoes = s.mounting, s.returns, s.noise, s.echoes
         self.returns, self.noise, self.echoes, self.dual = s.returns.model, s.noise.model, s.echoes.model, s.dual.setting
-        m = self.t_model = TargetModel(t_beam_table, t_sector, t_beam_azimuth, "DeviceDeform").validate(
-            self.t_H, (self.t_fov_up, self.t_fov_down), "DeviceDeform")
+        m = self.t_model = h.t_model
         # what the reverse projection reads on the device: the table and the offsets in radians
         self._t_brad = None if m.rows is None else torch.from_numpy(m.rows[:self.t_H].copy()).to(self.device)
         self._t_az_dev = None if m.azimuth_rad is None else torch.from_numpy(m.azimuth_rad.copy()).to(self.device)
-        # ``origin``: the target sensor in the scene, where mesh / mergemesh cast from by default
-        self.mount, self.origin = s.mount, s.origin
-        if mm_state is not None and vol_bnds is None:
-            vol_bnds = mm_state.vol_bnds
+        self.mount, self.origin, self.rayset = s.mount, h.origin, h.rayset
         if vol_bnds is not None:
             self.vol_bnds = vol_bnds if isinstance(vol_bnds, np.ndarray) else np.array(vol_bnds)
             if self.vol_bnds.shape != (3, 2):
@@ -229,26 +227,6 @@ class DeviceDeform:
                 self._merge = self.vol._flags
             self.mesh_obj = DeviceMesh(idx)
             self.scene = Scene(idx)
-            pose = s.P
-            if rayset is None:
-                keys = dict(beam_table=m.beam_table, sector=m.sector, beam_azimuth=m.beam_azimuth)
-                rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=idx,
-                                          rot=pose[:3, :3] if pose is not None else None, **keys)
-                self.rayset = RaySet(rays, self.t_H, pose=pose, grid=m.grid(self.t_W), **keys)
-                self._rays = rays
-            else:
-                theirs = getattr(rayset, "pose", None)
-                if (theirs is None) != (pose is None) or (pose is not None and not np.array_equal(theirs, pose)):
-                    raise ValueError("DeviceDeform: the shared rayset was built for another sensor pose than `transformation`")
-                differs = m.difference(rayset.model)
-                if differs is not None:
-                    what = dict(beam_table="another beam table", sector="another sector",
-                                beam_azimuth="other beam azimuth offsets")[differs]
-                    raise ValueError(f"DeviceDeform: the shared rayset was built for {what} than `t_{differs}`")
-                self.rayset = rayset
-            # (the central rays stay in ``rayset.rays``: the return model reads its directions from them)
-            s.bind(self.rayset.rays, self.t_H, grid=self.rayset.grid, table=m.beam_table is not None)
-        self.n_rays = self.t_H * self.t_W
 
     t_beam_table = property(lambda self: self.t_model.beam_table)
     t_sector = property(lambda self: self.t_model.sector)
@@ -277,45 +255,16 @@ class DeviceDeform:
 
     # ---- write(): filter + pack (laserscan.py:1133-1178) -------------------------------------------------------------
     def _pack(self, points, is_f64, rem, label, index, n, st):
-        torch = self._torch
-        out_bin = torch.empty((n, 4), dtype=torch.float32, device=self.device)
-        out_lab = torch.empty((n,), dtype=torch.int32, device=self.device)
-        kept = C.c_int(0)
-        _lib.check(self._lib.lt_pack_scan_dev(points.data_ptr(), int(is_f64), rem.data_ptr(), label.data_ptr(),
-                                              index.data_ptr() if index is not None else None, n, out_bin.data_ptr(),
-                                              out_lab.data_ptr(), C.byref(kept), C.c_void_p(st.cuda_stream)),
-                   "lt_pack_scan_dev")
-        return out_bin[:kept.value], out_lab[:kept.value]
+        """``lt_pack_scan_dev`` on this chain's device: every packing of this chain's target goes through here"""
+        return _chain.pack_rows(points, is_f64, rem, label, index, n, st, self.device)
 
-    def pack_result(self, out, stream=None):
+    def pack_result(self, out, stream=None, scene_frame=False):
         """``write``'s packing for a result of :meth:`cp`, :meth:`mesh` or :meth:`mergemesh` made with ``pack=False``:
         ``(bin [N,4] f32, label_file [N] i32)``.  ``cp`` packs its float64 ``back_points`` where ``index > 0``
         (laserscan.py:1133-1144); the mesh adaptions their float32 ``endpoints``, no index filter (:1145-1148).  A dual-return
-        result packs both of its planes in the ONE call: the primary's rows in cell order, then the second returns'."""
-        st = stream if stream is not None else self._stream()
-        if out.get("second") is not None:
-            p = out["second"]["_planes"]
-            return self._pack(p["endpoints"], False, p["rem"], p["label"], None, 2 * self.n_rays, st)
-        rem, label = out["rem"].reshape(-1), out["label"].reshape(-1)
-        if "back_points" in out:
-            return self._pack(out["back_points"], True, rem, label, out["index"].reshape(-1), self.n_rays, st)
-        return self._pack(out["endpoints"], False, rem, label, None, self.n_rays, st)
-
-    def scan_result(self, out, rout, t_H=None, t_W=None, **more):
-        """what :meth:`mesh` and :meth:`mergemesh` return of a rendered scan (``rout``: what the render wrote, ``out`` with the
-        end points in the target's frame).  ``t_H``, ``t_W``: the image of ANOTHER sensor rendered from this chain's scene (a
-        further head of a rig, ``rig.RigDeform``); default: this chain's target"""
-        H, W = (self.t_H, self.t_W) if t_H is None else (int(t_H), int(t_W))
-        return dict(range=out["range"].view(H, W), rem=out["endrem"].view(H, W), label=out["endcolors"].view(H, W),
-                    endpoints=out["endpoints"], endpoints_scene=rout["endpoints"], tri=rout["tri"],
-                    n_verts=self.mesh_obj.n_verts, n_faces=self.mesh_obj.n_faces, **more)
-
-    _result = scan_result
-
-    def pack_rows(self, points, rem, label, n, stream):
-        """``write``'s packing of the mesh adaptions for ``n`` cells of any sensor: float32 ``points`` [n, 3], ``rem`` [n],
-        ``label`` [n], no index filter (laserscan.py:1145-1148) -> ``(bin [N, 4] f32, label_file [N] i32)``"""
-        return self._pack(points, False, rem, label, None, int(n), stream)
+        result packs both of its planes in the ONE call: the primary's rows in cell order, then the second returns'
+        (``_chain.pack_result``, the one packing of every head)."""
+        return self.head.pack(out, stream if stream is not None else self._stream(), scene_frame, self._pack)
 
     @property
     def last_stream(self):
@@ -348,10 +297,7 @@ class DeviceDeform:
         with a noise model (``noise=``): what it reports, with ``range_error`` and ``noise_state`` [n]."""
         if origin is None:
             origin = self.origin
-        if self._returns and scan_index is None:
-            raise ValueError("DeviceDeform.mesh: a return model needs scan_index, the output scan's index in its sequence")
-        if self._noise and scan_index is None:
-            raise ValueError("DeviceDeform.mesh: a noise model needs scan_index, the output scan's index in its sequence")
+        self.head.need_scan_index(scan_index, "DeviceDeform.mesh")
         if self.vol is None:
             raise RuntimeError("DeviceDeform.mesh: constructed without vol_bnds")
         torch, lib = self._torch, self._lib
@@ -368,17 +314,15 @@ class DeviceDeform:
         cp, dp, rp = (vp * max(n, 1))(), (vp * max(n, 1))(), (vp * max(n, 1))()
         for k, o in enumerate(src):
             cp[k], dp[k], rp[k] = o["label_folded"].data_ptr(), o["range"].data_ptr(), o["rem"].data_ptr()
-        out = self.scene.alloc_outputs(self.n_rays, label_image=True)
-        rout, sub = self._sensing.plan(out, self.n_rays, self.device)   # (what the render writes: the sub-images, or ``rout``)
+        plan = self.head.plan(self.scene)   # (plan[2] is what the render writes: the sub-images, or ``rout``)
         with torch.cuda.device(self.device):
-            _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self._sensing.render_set(self.rayset)._h,
+            _lib.check(lib.lt_fusion_scan_dev(self.vol._h, self.mesh_obj._h, self.scene._h, self.head.render_set._h,
                                               n, cp, dp, rp, self.H, self.W, 1.0, self._merge, _chain.origin3(origin),
-                                              *_chain.out_ptrs(sub), _chain.TRACE_FLAGS, vp(st.cuda_stream), 0),
+                                              *_chain.out_ptrs(plan[2]), _chain.TRACE_FLAGS, vp(st.cuda_stream), 0),
                        "lt_fusion_scan_dev")
-            seen = self._sensing.finish(out, rout, sub, scan_index, self.scene, self.rayset.rays, origin, st)
+            res = self.head.finish(plan, scan_index, self.scene, self.mesh_obj, st, origin, source=src)
             if ev:
                 ev[2].record(st)
-            res = self._result(out, rout, source=src, **seen)
             if pack:
                 res["bin"], res["label_file"] = self.pack_result(res, st)
             if ev:
@@ -459,15 +403,10 @@ class DeviceDeform:
         try:   # (a scan that fails before its geometry call gives up its turn; a no-op once the call has been made)
             st = self._stream()
             cloud = _chain.merged_cloud(clouds)
-            if out is None:
-                out = self.scene.alloc_outputs(self.n_rays, label_image=True)
-            if self._returns and scan_index is None:
-                raise ValueError("DeviceDeform.mergemesh: a return model needs scan_index, the output scan's index in its sequence")
-            if self._noise and scan_index is None:
-                raise ValueError("DeviceDeform.mergemesh: a noise model needs scan_index, the output scan's index in its sequence")
-            rout, sub = self._sensing.plan(out, self.n_rays, self.device)   # (what the render writes: the sub-images, or ``rout``)
+            self.head.need_scan_index(scan_index, "DeviceDeform.mergemesh")
+            plan = self.head.plan(self.scene, out)   # (plan[2] is what the render writes: the sub-images, or ``rout``)
             first, again, more = (self._mm_composed if source_images else self._mm_native)(
-                mm, cloud, seq, _chain.origin3(origin), _chain.out_ptrs(sub), st)
+                mm, cloud, seq, _chain.origin3(origin), _chain.out_ptrs(plan[2]), st)
             pred, vol = mm.pred, None
             if pred is not None:
                 vol = self._mm_vols.get(pred)
@@ -493,9 +432,9 @@ class DeviceDeform:
                 vol = self._mergemesh_volume(geo.bnds_given, geo.dim)
                 again(vol)
             # (once, on the render that stands)
-            more.update(self._sensing.finish(out, rout, sub, scan_index, self.scene, self.rayset.rays, origin, st))
-            res = self._result(out, rout, vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
-                               vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol, **more)
+            res = self.head.finish(plan, scan_index, self.scene, self.mesh_obj, st, origin,
+                                   vol_dim=tuple(int(x) for x in geo.dim), vol_origin=vol._vol_origin.copy(),
+                                   vol_bnds_after=[float(x) for x in geo.bnds_after], volume=vol, **more)
             if pack:
                 res["bin"], res["label_file"] = self.pack_result(res, st)
         return res
@@ -509,7 +448,7 @@ class DeviceDeform:
         cl, keep, is_f64 = _chain.cloud_table([cloud])
         beams = _chain.beam_table(self.beam_angles)   # (pointer, n, the array: alive as long as the callables)
         p = self.projector._h
-        rs = self._sensing.render_set(self.rayset)
+        rs = self.head.render_set
 
         def first(vol):
             tflags = vol._flags if vol is not None else (_lib.LT_TSDF_HOST_MODE if self._fusion == "numpy" else self._merge)
@@ -532,7 +471,7 @@ class DeviceDeform:
         returned under ``source``"""
         vp = C.c_void_p
         src = {}
-        rs = self._sensing.render_set(self.rayset)
+        rs = self.head.render_set
 
         def again(vol):
             cp, dp, rp = (vp * 1)(src["label_folded"].data_ptr()), (vp * 1)(src["range"].data_ptr()), (vp * 1)(src["rem"].data_ptr())
@@ -645,13 +584,13 @@ class DeviceDeform:
         if getattr(self, "_mm_state", None) is not None and getattr(self, "_mm_own", False):
             self._mm_state.close()
         self._mm_state = None
-        if getattr(self, "_sensing", None) is not None:
-            self._sensing.close()
-        for name in ("rayset", "scene", "mesh_obj", "vol", "projector"):
+        if getattr(self, "head", None) is not None:
+            self.head.close()       # (the sub-ray set and the ray set, when they are this chain's own)
+        self.rayset = None
+        for name in ("scene", "mesh_obj", "vol", "projector"):
             obj = getattr(self, name, None)
             if obj is not None:
-                if name != "rayset" or getattr(self, "_rayset_own", True):
-                    obj.close()
+                obj.close()
                 setattr(self, name, None)
 
     def __enter__(self):

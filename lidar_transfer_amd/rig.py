@@ -2,57 +2,41 @@
 projection, TSDF integration and marching cubes make of an output scan's source scans.
 
 :class:`RigDeform` owns one :class:`~lidar_transfer_amd.deform.DeviceDeform` for head 0 -- projector, volume, mesh, scene,
-head 0's ray set and ``Sensing``, unchanged -- and one light :class:`Head` per further sensor: its rays, its ``RaySet`` and
-its own ``_chain.Sensing``.  ``mesh`` / ``mergemesh`` run head 0's call as it is, then ONE ``Scene.render_rig`` call on the
-same stream renders every further head from the mesh the scene now holds, then each head's ``Sensing.finish`` and packing
+head 0's ``_chain.TargetHead``, unchanged -- and one :class:`Head`, the same object, per further sensor: its rays, its
+``RaySet`` and its own ``_chain.Sensing``.  ``mesh`` / ``mergemesh`` run head 0's call as it is, then ONE ``Scene.render_rig``
+call on the same stream renders every further head from the mesh the scene now holds, then each head's ``finish`` and packing
 follow.  A further head's scan is what a ``DeviceDeform`` of that sensor alone returns for ``mesh``; for ``mergemesh`` it is
 its render of the volume that head 0's vertical field of view selected (see :class:`RigDeform`)."""
 from __future__ import annotations
 
 from . import _chain
 from .deform import DeviceDeform
-from .raytracer import RaySet
 
 
 def head_keywords(sensor):
-    """the ``DeviceDeform`` keywords that a ``config.SensorModel`` stands for as a TARGET: its shape tuple and its models"""
+    """the ``DeviceDeform`` keywords that a ``config.SensorModel`` stands for as a TARGET: its shape tuple and its models; a
+    plain ``(H, W, fov_up, fov_down)`` is its own shape and has no model"""
+    if not hasattr(sensor, "fov_up"):
+        return (int(sensor[0]), int(sensor[1]), float(sensor[2]), float(sensor[3])), dict(
+            t_beam_table=None, t_sector=None, t_beam_azimuth=None, returns=None, noise=None, echoes=None, dual=None)
     m = sensor.target_model()
     return (sensor.H, sensor.W, float(sensor.fov_up), float(sensor.fov_down)), dict(
         t_beam_table=m.beam_table, t_sector=m.sector, t_beam_azimuth=m.beam_azimuth, returns=sensor.return_model(),
         noise=sensor.noise_model(), echoes=sensor.echo_model(), dual=sensor.dual_return())
 
 
-class Head:
-    """A further sensor of a rig: its rays (turned by its pose), its read-only ``RaySet`` and its own ``Sensing``, bound as
-    ``DeviceDeform.__init__`` binds it.  ``share``: the same head of another :class:`RigDeform` of the same rig -- its ray set
-    and bound echo sub-ray set are taken, not made again."""
+class Head(_chain.TargetHead):
+    """A further sensor of a rig: the ``_chain.TargetHead`` of a ``config.RigHead`` (``name``, ``sensor``).  ``share``: the
+    same head of another :class:`RigDeform` of the same rig -- its ray set and bound echo sub-ray set are taken, not made
+    again."""
 
     def __init__(self, head, device, share=None):
-        from .laserscan import create_rays_device
         self.name, self.sensor = head.name, head.sensor
-        (self.t_H, self.t_W, self.t_fov_up, self.t_fov_down), kw = head_keywords(head.sensor)
-        self.n_rays = self.t_H * self.t_W
-        who = f"rig head {head.name!r}"
-        m = self.t_model = head.sensor.target_model().validate(self.t_H, (self.t_fov_up, self.t_fov_down), who)
-        s = self.sensing = _chain.Sensing(head.mount, kw["returns"], kw["noise"],
-                                          share.sensing.echoes if share is not None and share.sensing.echoes else kw["echoes"],
-                                          who, kw["dual"])
-        self.origin = s.origin
-        self._own = share is None
-        if share is None:
-            keys = dict(beam_table=m.beam_table, sector=m.sector, beam_azimuth=m.beam_azimuth)
-            rays = create_rays_device(self.t_fov_up, self.t_fov_down, self.t_H, self.t_W, device=device,
-                                      rot=s.P[:3, :3] if s.P is not None else None, **keys)
-            self.rayset = RaySet(rays, self.t_H, pose=s.P, grid=m.grid(self.t_W), **keys)
-        else:
-            self.rayset = share.rayset
-        s.bind(self.rayset.rays, self.t_H, grid=self.rayset.grid, table=m.beam_table is not None)
-
-    def close(self):
-        self.sensing.close()
-        if self._own and self.rayset is not None:
-            self.rayset.close()
-        self.rayset = None
+        shape, kw = head_keywords(head.sensor)
+        if share is not None and share.sensing.echoes:
+            kw["echoes"] = share.sensing.echoes
+        super().__init__(shape, head.mount, kw["returns"], kw["noise"], kw["echoes"], kw["dual"], f"rig head {head.name!r}", device,
+                         kw["t_beam_table"], kw["t_sector"], kw["t_beam_azimuth"], rayset=None if share is None else share.rayset)
 
 
 class RigResults(list):
@@ -122,46 +106,25 @@ class RigDeform:
         results = RigResults([first])
         if self.heads:
             for h in self.heads:
-                if h.sensing.needs_scan_index and scan_index is None:
-                    raise ValueError(f"rig head {h.name!r}: a return or noise model needs scan_index, the output scan's index in its "
-                                     "sequence")
+                h.need_scan_index(scan_index)
             with torch.cuda.device(self.device), torch.cuda.stream(st):
-                plans = []
-                for h in self.heads:
-                    out = p.scene.alloc_outputs(h.n_rays, label_image=True)
-                    rout, sub = h.sensing.plan(out, h.n_rays, self.device)
-                    plans.append((out, rout, sub))
-                p.scene.render_rig([h.sensing.render_set(h.rayset) for h in self.heads], [h.origin for h in self.heads],
+                plans = [h.plan(p.scene) for h in self.heads]
+                p.scene.render_rig([h.render_set for h in self.heads], [h.origin for h in self.heads],
                                    outs=[sub for _, _, sub in plans], stream=st, write_misses=True, label_image=True)
-                for h, (out, rout, sub) in zip(self.heads, plans):
-                    seen = h.sensing.finish(out, rout, sub, scan_index, p.scene, h.rayset.rays, h.origin, st)
-                    res = p.scan_result(out, rout, h.t_H, h.t_W, **seen)
+                for h, plan in zip(self.heads, plans):
+                    res = h.finish(plan, scan_index, p.scene, p.mesh_obj, st)
                     if pack:
-                        res["bin"], res["label_file"] = self.pack_head(res, len(results), st)
+                        res["bin"], res["label_file"] = h.pack(res, st)
                     results.append(res)
         if pack and self.merged:
             results.bin, results.label_file = self.merged_rows(results, st)
         return results
 
-    def n_rays_of(self, k):
-        return self.primary.n_rays if k == 0 else self.heads[k - 1].n_rays
-
     def pack_head(self, res, k, st=None, scene_frame=False):
         """``write``'s packing of head ``k``'s result ``res`` (``DeviceDeform.pack_result`` for any head of the rig) ->
         ``(bin, label_file)``; ``scene_frame``: the rows hold ``endpoints_scene``, the primary scan's frame"""
-        import torch
-        p = self.primary
-        st = st if st is not None else p.last_stream
-        n = self.n_rays_of(k)
-        with torch.cuda.device(self.device), torch.cuda.stream(st):
-            if res.get("second") is not None:   # a dual return: both planes in the one call
-                planes = res["second"]["_planes"]
-                pts = planes["endpoints"]
-                if scene_frame:
-                    pts = torch.cat([res["endpoints_scene"], res["second"]["endpoints_scene"]])
-                return p.pack_rows(pts, planes["rem"], planes["label"], 2 * n, st)
-            pts = res["endpoints_scene" if scene_frame else "endpoints"]
-            return p.pack_rows(pts.contiguous(), res["rem"].reshape(-1), res["label"].reshape(-1), n, st)
+        st = st if st is not None else self.primary.last_stream
+        return self.primary.pack_result(res, st, scene_frame) if k == 0 else self.heads[k - 1].pack(res, st, scene_frame)
 
     def merged_rows(self, results, st=None):
         """``(bin, label_file)`` of the whole rig: every head's packed rows from ``endpoints_scene`` -- one frame for all,

@@ -29,6 +29,7 @@ from ._chain import CP_REFUSALS
 from .deform import DeviceDeform, MergeMeshState
 from .evaluate import Evaluator
 from .ingest import ScanIngest, SequenceSource
+from .rig import RigDeform, head_keywords
 
 ADAPTIONS = ("cp", "mesh", "mergemesh")
 #: what the codes of a return model's ``drop`` image mean, in code order (``return_totals``, the CLI's closing line)
@@ -60,6 +61,21 @@ def format_echo_totals(totals, fraction):
     number of detected echoes, and the mean of ``echo_fraction`` over the cells that detected one; ``None``: there was none)"""
     return "Echoes: " + ", ".join(f"{name} {int(n)}" for name, n in zip(ECHO_COUNTS, totals)) + \
         ", mean fraction " + ("n/a" if fraction is None else f"{float(fraction):.6f}")
+
+
+def format_closing_lines(totals, lead=""):
+    """the CLI's closing lines of a run, or of one head of a rig: one per model that is on in ``totals`` (:attr:`summary`, or
+    its ``sensors[NAME]``) -- returns, noise, echoes, second returns --, each led by ``lead`` (``""`` or ``"NAME: "``)"""
+    lines = []
+    if totals.get("return_totals") is not None:
+        lines.append(format_return_totals(totals["return_totals"]))
+    if totals.get("noise_totals") is not None:
+        lines.append(format_noise_totals(totals["noise_totals"], totals["range_error_rms"]))
+    if totals.get("echo_totals") is not None:
+        lines.append(format_echo_totals(totals["echo_totals"], totals["echo_fraction_mean"]))
+    if totals.get("second_returns") is not None:
+        lines.append("Second returns: %d" % totals["second_returns"])
+    return [lead + line for line in lines]
 
 
 def sensor_tuple(s):
@@ -134,10 +150,7 @@ class _Writer:
             item = self.q.get()
             if item is None:
                 return
-            if len(item) == 3:               # a rig's scan: (paths, points, labels, n) per file pair, one per head [+ merged]
-                job, files, event = item
-            else:                            # a scan's one pair
-                job, files, event = item[0], [item[1:5]], item[5]
+            job, files, event = item         # files: (paths, points, labels, n) per file pair -- one, or one per head [+ merged]
             try:
                 event.synchronize()
                 for paths, hb, hl, n in files:
@@ -228,6 +241,7 @@ class SequenceTransfer:
         # a rig: the approach names the target sensors, every chain is a RigDeform, nothing is compared
         self.rig = approach.rig()
         self.rig_names = None if self.rig is None else [h.name for h in self.rig]
+        self.merged = self.rig is not None and bool(approach.rig_merged)
         if self.rig is not None:
             if target_sensor is not None:
                 raise ValueError("rig: the approach file names its target sensors (rig) -- SequenceTransfer takes no target sensor "
@@ -304,37 +318,29 @@ class SequenceTransfer:
             if self.adaption == "mergemesh":
                 self.vol_bnds = self._configured_bnds.copy()   # the ONE array of the sequence, kept current
                 self._mm = MergeMeshState(self.vol_bnds, approach.voxel_size, idx)
-            rayset, echoes = None, self.echoes
+            # the heads of a chain by name -- ``None``: the one target sensor -- and what every chain's constructor takes
+            heads = {None: target_sensor} if self.rig is None else {h.name: h.sensor for h in self.rig}
+            self._names = list(heads)
             every = dict(beam_angles=beams, preserve_float=approach.preserve_float, device=idx, fusion=fusion,
-                         transformation=self.mount, t_beam_table=m.beam_table, t_sector=m.sector, t_beam_azimuth=m.beam_azimuth,
-                         returns=self.returns, noise=self.noise)
-            if self.adaption != "cp":
-                every["dual"] = self.dual
+                         mesh_volume=self.adaption == "mesh", mm_state=self._mm)
+            single = dict(head_keywords(target_sensor)[1], transformation=self.mount)
             for c in range(self.chains):
+                bnds = None if self._mm is not None or self.adaption == "cp" else self._configured_bnds.copy()
                 if self.rig is not None:
-                    from .rig import RigDeform
-                    dd = RigDeform(self.source_sensor, self.rig, None if self._mm is not None else self._configured_bnds.copy(),
-                                   approach.voxel_size, share=self._chains[0]["dd"] if self._chains else None,
-                                   merged=approach.rig_merged, beam_angles=beams, preserve_float=approach.preserve_float,
-                                   device=idx, fusion=fusion, mesh_volume=self.adaption == "mesh", mm_state=self._mm)
+                    dd = RigDeform(self.source_sensor, self.rig, bnds, approach.voxel_size, merged=self.merged,
+                                   share=self._chains[0]["dd"] if self._chains else None, **every)
                     if self.adaption == "mergemesh":
                         try:
                             dd.check_mergemesh()     # (a later head that looks past head 0: said here, not at the first scan)
                         except BaseException:
                             dd.close()
                             raise
-                elif self.adaption == "cp":
-                    dd = DeviceDeform(self.source_sensor, self.target_sensor, None, **every)
                 else:
-                    dd = DeviceDeform(self.source_sensor, self.target_sensor,
-                                      None if self._mm is not None else self._configured_bnds.copy(), approach.voxel_size,
-                                      mesh_volume=self.adaption == "mesh", rayset=rayset, mm_state=self._mm, echoes=echoes,
-                                      **every)
-                    rayset = dd.rayset
-                    if self.echoes is not None:
-                        echoes = dd._echoes          # (the first chain's sub-ray set, shared like the plain one)
+                    dd = DeviceDeform(self.source_sensor, self.target_sensor, bnds, approach.voxel_size, **every, **single)
+                    # (the first chain's ray set and sub-ray set are shared by the later ones)
+                    single.update(rayset=dd.rayset, echoes=dd.bound_echoes or single["echoes"])
                 ch = dict(dd=dd, ev=None, q=None, thread=None,
-                          tally=self._tallies() if self.rig is None else {h.name: self._tallies(h.sensor) for h in self.rig},
+                          tally={name: self._tallies(sensor) for name, sensor in heads.items()},
                           stream=torch.cuda.Stream(self.device) if self.chains > 1 else torch.cuda.current_stream(self.device))
                 if target_view:
                     ch["ev"] = Evaluator(self.source_sensor, approach.ignore, approach.color_lut(), device=idx,
@@ -352,30 +358,28 @@ class SequenceTransfer:
             self.close()
             raise
 
-    def _tallies(self, sensor=None):
-        """one chain's accumulators: a :class:`_Tally` per model that is on -- of the target sensor, or of ``sensor`` (a head
-        of a rig)"""
+    def _tallies(self, sensor):
+        """one head's accumulators on a chain: a :class:`_Tally` per model of ``sensor`` that is on"""
         n = dict(returns=len(RETURN_CODES), noise=len(NOISE_STATES), echoes=len(ECHO_COUNTS), dual=2)
-        if sensor is None:
-            return {name: _Tally(n[name], self.device) for name in n if getattr(self, name) is not None}
-        return {name: _Tally(n[name], self.device) for name in n if getattr(sensor, CP_REFUSALS[name][0])() is not None}
+        return {name: _Tally(n[name], self.device) for name in n
+                if getattr(sensor, CP_REFUSALS[name][0], lambda: None)() is not None}
 
-    def _read_tallies(self, name, head=None):
-        """``(cells per code, sum)`` of model ``name`` -- of the target sensor, or of head ``head`` of a rig -- over the
-        chains, read and reset; ``(None, 0.0)`` when it is off"""
-        pick = (lambda ch: ch["tally"]) if head is None else (lambda ch: ch["tally"][head])   # noqa: E731
-        if not self._chains or name not in pick(self._chains[0]):
+    def _read_tallies(self, name, head):
+        """``(cells per code, sum)`` of model ``name`` of head ``head`` (``None``: the one target sensor) over the chains, read
+        and reset; ``(None, 0.0)`` when it is off, or the run has no such head"""
+        if not self._chains or name not in self._chains[0]["tally"].get(head, {}):
             return None, 0.0
         counts, value = None, 0.0
         for ch in self._chains:
             ch["stream"].synchronize()
-            c, v = pick(ch)[name].read()
+            c, v = ch["tally"][head][name].read()
             counts, value = c if counts is None else [a + b for a, b in zip(counts, c)], value + v
-            pick(ch)[name].reset()
+            ch["tally"][head][name].reset()
         return counts, value
 
-    def _totals(self, head=None):
-        """what a run sums of the models that are on (the target sensor's, or head ``head``'s of a rig): the summary's keys"""
+    def _totals(self, head):
+        """what a run sums of the models that are on of head ``head`` (``None``: the one target sensor; all ``None`` for a rig,
+        which has no such head): the summary's keys"""
         totals, _ = self._read_tallies("returns", head)
         noise_totals, sq_sum = self._read_tallies("noise", head)
         echo_totals, share = self._read_tallies("echoes", head)
@@ -404,7 +408,13 @@ class SequenceTransfer:
         rig, ``SS/NAME`` per head, and ``SS`` for the merged scan when the approach says ``rig_merged``"""
         if self.rig is None:
             return [self.sequence]
-        return [os.path.join(self.sequence, n) for n in self.rig_names] + ([self.sequence] if self.approach.rig_merged else [])
+        return [os.path.join(self.sequence, n) for n in self.rig_names] + ([self.sequence] if self.merged else [])
+
+    def _count(self, job, counts):
+        """a scan's ``n_points`` from the points of its file pairs (in :meth:`file_sets`' order), made or found by ``resume``:
+        per head, and of the scan -- the merged scan's, else the heads' sum"""
+        job["sensors"] = {name: dict(n_points=int(c)) for name, c in zip(self._names, counts)}
+        job["n_points"] = int(counts[-1]) if self.merged else sum(int(c) for c in counts)
 
     def _host_copy(self, b, l):
         """the packed rows on their way into pinned memory, on the current stream -> ``(points, labels, n)``"""
@@ -416,34 +426,6 @@ class SequenceTransfer:
             hb[:n].copy_(b, non_blocking=True)
             hl[:n].copy_(l, non_blocking=True)
         return hb, hl, n
-
-    def _work_rig(self, ch, job, st):
-        """:meth:`_work` for a rig: one ``RigDeform`` call, then tallies, packing and files per head (and the merged pair)"""
-        torch = self._torch
-        dd, clouds = ch["dd"], job["clouds"]
-        if self.adaption == "mesh":
-            outs = dd.mesh(clouds, pack=False, scan_index=job["idx"])
-        else:
-            outs = dd.mergemesh(clouds, pack=False, seq=job["k"], scan_index=job["idx"])
-            job["bnds_after"] = np.array(outs[0]["vol_bnds_after"]).reshape(3, 2)
-        packed = []
-        for k, (name, out) in enumerate(zip(self.rig_names, outs)):
-            self._add_tallies(ch["tally"][name], out)
-            packed.append(dd.pack_head(out, k, st))
-        job["sensors"] = {name: dict(n_points=int(b.shape[0])) for name, (b, _) in zip(self.rig_names, packed)}
-        if self.approach.rig_merged:
-            packed.append(dd.merged_rows(outs, st))
-            job["n_points"] = int(packed[-1][0].shape[0])
-        else:
-            job["n_points"] = sum(v["n_points"] for v in job["sensors"].values())
-        if self._writer is not None:
-            files = [(output_paths(self.out_dir, d, job["idx"]),) + self._host_copy(b, l) for d, (b, l) in zip(self.file_sets(), packed)]
-            ev = torch.cuda.Event()
-            ev.record(st)
-            job["keep"] = (packed, outs)
-            self._writer.q.put((job, files, ev))
-        else:
-            job["written"].set()
 
     # ---- the scan list -------------------------------------------------------------------------------------------------
     def scan_indices(self, offset=0, one_scan=False):
@@ -462,30 +444,37 @@ class SequenceTransfer:
                 if job["skipped"]:                   # resume: only mergemesh's bounds are replayed
                     dd.mergemesh_bounds(clouds, seq=job["k"])
                     return
-                if self.rig is not None:
-                    self._work_rig(ch, job, st)
-                    return
                 if self.adaption == "cp":
-                    out = dd.cp(clouds, pack=False)
+                    outs = dd.cp(clouds, pack=False)
                 elif self.adaption == "mesh":
-                    out = dd.mesh(clouds, pack=False, scan_index=job["idx"])
+                    outs = dd.mesh(clouds, pack=False, scan_index=job["idx"])
                 else:
-                    out = dd.mergemesh(clouds, pack=False, seq=job["k"], scan_index=job["idx"])
-                    job["bnds_after"] = np.array(out["vol_bnds_after"]).reshape(3, 2)
-                self._add_tallies(ch["tally"], out)  # summed on the chain's stream: read once, in run()
+                    outs = dd.mergemesh(clouds, pack=False, seq=job["k"], scan_index=job["idx"])
+                if self.rig is None:                 # one result per head: a rig's call returns the list
+                    outs = [outs]
+                if self.adaption == "mergemesh":
+                    job["bnds_after"] = np.array(outs[0]["vol_bnds_after"]).reshape(3, 2)
+                for name, out in zip(self._names, outs):
+                    self._add_tallies(ch["tally"][name], out)   # summed on the chain's stream: read once, in run()
                 if ch["ev"] is not None:             # behind the render, before the packing's read-back: in flight too
                     scan = ch["ev"].target_view if self.evaluate_mode == "target" else ch["ev"].source_scan
                     src = scan(*job["raw"], stream=st)
-                    job["record"] = ch["ev"].compare(src, out["label"], out["range"], stream=st)
-                    job["images"] = (src, out)
-                b, l = dd.pack_result(out, st)
-                job["n_points"] = int(b.shape[0])
+                    job["record"] = ch["ev"].compare(src, outs[0]["label"], outs[0]["range"], stream=st)
+                    job["images"] = (src, outs[0])
+                if self.rig is None:
+                    packed = [dd.pack_result(outs[0], st)]
+                else:
+                    packed = [dd.pack_head(out, k, st) for k, out in enumerate(outs)]
+                if self.merged:
+                    packed.append(dd.merged_rows(outs, st))
+                self._count(job, [b.shape[0] for b, _ in packed])
                 if self._writer is not None:
-                    hb, hl, n = self._host_copy(b, l)
+                    files = [(output_paths(self.out_dir, d, job["idx"]),) + self._host_copy(b, l)
+                             for d, (b, l) in zip(self.file_sets(), packed)]
                     ev = torch.cuda.Event()
                     ev.record(st)
-                    job["keep"] = (b, l, out)
-                    self._writer.q.put((job, output_paths(self.out_dir, self.sequence, job["idx"]), hb, hl, n, ev))
+                    job["keep"] = (packed, outs)
+                    self._writer.q.put((job, files, ev))
                 else:
                     job["written"].set()
         except BaseException as e:  # noqa: BLE001  (handed to the generator as this scan's exception)
@@ -503,11 +492,7 @@ class SequenceTransfer:
         sets = self.file_sets()
         if resume and self.out_dir is not None and all(plausible_output(self.out_dir, d, idx) for d in sets):
             job["skipped"] = True                    # (a rig: only when EVERY file of the scan is plausible)
-            sizes = [os.path.getsize(output_paths(self.out_dir, d, idx)[0]) // 16 for d in sets]
-            job["n_points"] = sizes[0]
-            if self.rig is not None:
-                job["sensors"] = {n: dict(n_points=c) for n, c in zip(self.rig_names, sizes)}
-                job["n_points"] = sizes[-1] if self.approach.rig_merged else sum(sizes)
+            self._count(job, [os.path.getsize(output_paths(self.out_dir, d, idx)[0]) // 16 for d in sets])
             job["written"].set()
             if self._mm is None:
                 job["done"].set()
@@ -589,7 +574,7 @@ class SequenceTransfer:
             for job in pending:                          # (a failure or an abandoned generator: let what is queued finish)
                 job["done"].wait()
                 job["written"].wait()
-            self.summary = dict(**self._totals(), scans=n_done,
+            self.summary = dict(**self._totals(None), scans=n_done,
                                 chains=self.chains, adaption=self.adaption, fusion=self.fusion,
                                 mounted=self.mounted, beam_model=self.beam_model, azimuth_model=self.azimuth_model,
                                 beam_azimuth=self.beam_azimuth is not None,

@@ -135,17 +135,19 @@ def test_mergemesh_sequence_with_a_rerun():
                 scene = rig.primary.scene
                 st = torch.cuda.current_stream()
                 for h, g in zip(fresh, got[1:]):
-                    out = scene.alloc_outputs(h.n_rays, label_image=True)
-                    rout, sub = h.sensing.plan(out, h.n_rays, rig.device)
-                    scene.render(h.sensing.render_set(h.rayset), h.origin, out=sub, label_image=True)
-                    seen = h.sensing.finish(out, rout, sub, i, scene, h.rayset.rays, h.origin, st)
-                    want = rig.primary.scan_result(out, rout, h.t_H, h.t_W, **seen)
+                    plan = h.plan(scene)
+                    scene.render(h.render_set, h.origin, out=plan[2], label_image=True)
+                    want = h.finish(plan, i, scene, rig.primary.mesh_obj, st)
                     torch.cuda.synchronize()
                     _hits_and_misses(g, h.name)
                     _same({k: g[k] for k in want}, want, f"mergemesh/{h.name}/{i}")
                     assert g["bin"].shape[0] > 20 and g["n_faces"] == got[0]["n_faces"]
             stats = rig.primary.mm_state.stats
             assert stats["scans"] == 3 and stats["rerun"] >= 1, stats
+            # a shared head is held to the shared ray set's pose, as a DeviceDeform's shared ray set is
+            assert heads[1].mount is not None and heads[2].mount is not None and heads[1].sensor is not heads[2].sensor
+            with pytest.raises(ValueError, match="rig head 'side': the shared rayset was built for another sensor pose"):
+                Head(heads[1], rig.device.index, share=fresh[1])
         finally:
             for h in fresh:
                 h.close()

@@ -1,7 +1,8 @@
 """`SequenceTransfer` and the command line with an approach that has a `rig`, on golden F17's synthetic sequence
 built as tests/test_sequence_gpu.py builds its source.  A two-head `mesh` rig writes one folder per head whose files are byte
 for byte those of two single-target runs; the merged scan is the concatenation of the heads' rows in the primary scan's
-frame; `--resume` redoes a scan of which one head's file is gone; a rig is not evaluated and takes no target sensor."""
+frame; `--resume` redoes a scan of which one head's file is gone; a rig of ONE head is that head's single run, in its files,
+its records and its totals; a rig is not evaluated and takes no target sensor."""
 import json
 import os
 import subprocess
@@ -33,12 +34,13 @@ def _sensors():
     return roof, front
 
 
-def _approach(adaption="mesh", rig=True, merged=False, transformation=()):
+def _approach(adaption="mesh", rig=True, merged=False, transformation=(), heads=("roof", "front")):
     a = sc.approach_for(sc.gold18(), adaption)
     a.transformation = list(transformation)
     if rig:
         roof, front = _sensors()
-        a.rig_block = [dict(name="roof", sensor=roof), dict(name="front", sensor=front, transformation=T_FRONT)]
+        block = dict(roof=dict(name="roof", sensor=roof), front=dict(name="front", sensor=front, transformation=T_FRONT))
+        a.rig_block = [block[name] for name in heads]
         a.rig_merged = bool(merged)
     return a
 
@@ -136,6 +138,46 @@ def test_resume_redoes_a_scan_of_which_one_heads_file_is_gone(tmp_path):
     for r, r0 in zip(again, recs):
         assert r["sensors"] == r0["sensors"] and r["n_points"] == r0["n_points"]
         assert [_read(tmp_path, r["idx"], s) for s in ("00", "00/roof", "00/front")] == before[r["idx"]]
+
+
+TOTALS = ("return_totals", "noise_totals", "range_error_rms", "echo_totals", "echo_fraction_mean", "second_returns")
+
+
+def test_a_rig_of_one_head_is_that_heads_single_run(tmp_path, tmp_path_factory):
+    out, srecs, ssummary = _singles(tmp_path_factory)["front"]
+    recs, summary = _run(_approach(heads=("front",)), None, tmp_path)
+    assert [r["idx"] for r in recs] == [r["idx"] for r in srecs] and len(recs) >= 3
+    for rec, srec in zip(recs, srecs):
+        assert _read(tmp_path, rec["idx"], os.path.join("00", "front")) == _read(out, rec["idx"]), rec["idx"]
+        assert set(rec["sensors"]) == {"front"}
+        assert rec["sensors"]["front"]["n_points"] == rec["n_points"] == srec["n_points"] > 50
+    assert not os.path.exists(os.path.join(str(tmp_path), "sequences", "00", "velodyne"))
+    assert set(summary["sensors"]) == {"front"} and set(summary["sensors"]["front"]) == set(TOTALS)
+    for key in TOTALS:
+        assert summary["sensors"]["front"][key] == ssummary[key], key
+        assert summary[key] is None, key
+    assert sum(ssummary["return_totals"][1:]) > 0
+
+
+def test_a_merged_rig_of_one_head_writes_the_single_run_twice_and_resumes_by_either(tmp_path, tmp_path_factory):
+    from lidar_transfer_amd.sequence import output_paths
+    out, srecs, _ = _singles(tmp_path_factory)["roof"]
+    a = _approach(heads=("roof",), merged=True)
+    recs, _ = _run(a, None, tmp_path)
+    assert [r["idx"] for r in recs] == [r["idx"] for r in srecs] and len(recs) >= 3
+    for rec, srec in zip(recs, srecs):
+        want = _read(out, rec["idx"])
+        assert _read(tmp_path, rec["idx"], os.path.join("00", "roof")) == want == _read(tmp_path, rec["idx"]), rec["idx"]
+        assert rec["n_points"] == rec["sensors"]["roof"]["n_points"] == srec["n_points"] == len(want[0]) // 16 > 50
+    # --resume: a scan whose MERGED label file is gone is redone, and no other
+    victim = recs[1]["idx"]
+    before = {r["idx"]: [_read(tmp_path, r["idx"], s) for s in ("00", "00/roof")] for r in recs}
+    os.remove(output_paths(str(tmp_path), "00", victim)[1])
+    again, _ = _run(a, None, tmp_path, resume=True)
+    assert [r["skipped"] for r in again] == [r["idx"] != victim for r in recs] and sum(r["skipped"] for r in again) == len(recs) - 1
+    for r, r0 in zip(again, recs):
+        assert r["sensors"] == r0["sensors"] and r["n_points"] == r0["n_points"]
+        assert [_read(tmp_path, r["idx"], s) for s in ("00", "00/roof")] == before[r["idx"]]
 
 
 def test_what_a_rig_refuses():

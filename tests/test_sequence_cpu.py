@@ -133,14 +133,14 @@ def test_writer_thread_writes_the_two_files_behind_the_event_and_reports_failure
     hl = torch.arange(10, dtype=torch.int32) - 3                          # negative labels travel as uint32 bits
     job, e = dict(written=threading.Event(), error=None), Ev()
     paths = sq.output_paths(str(tmp_path), "00", 3)
-    w.q.put((job, paths, hb, hl, 7, e))
+    w.q.put((job, [(paths, hb, hl, 7)], e))
     assert job["written"].wait(30) and job["error"] is None and e.waited
     assert np.array_equal(np.fromfile(paths[0], np.float32), np.arange(28, dtype=np.float32))
     assert np.array_equal(np.fromfile(paths[1], np.uint32), (np.arange(7) - 3).astype(np.int32).view(np.uint32))
     blocked = tmp_path / "file"
     blocked.write_text("x")
     job2 = dict(written=threading.Event(), error=None)
-    w.q.put((job2, sq.output_paths(str(blocked), "00", 3), hb, hl, 7, Ev()))
+    w.q.put((job2, [(sq.output_paths(str(blocked), "00", 3), hb, hl, 7)], Ev()))
     assert job2["written"].wait(30) and isinstance(job2["error"], OSError)
     w.close()
     assert not w.thread.is_alive()
@@ -175,3 +175,76 @@ def test_shipped_approach_yaml_loads():
     a = load_approach(os.path.join(ROOT, "config", "approach_mergemesh.yaml"))
     assert a.adaption == "mergemesh" and a.number_of_scans == 5 and a.voxel_bounds.shape == (3, 2) and len(a.color_map) == 34
     assert a.color_lut().shape == (360, 3) and a.scan_indices(20) == list(range(2, 16))
+
+
+def test_closing_lines_are_the_format_functions_lines_in_order_with_the_lead():
+    from lidar_transfer_amd import sequence as sq
+    totals = dict(return_totals=[5, 4, 3, 2, 1, 0], noise_totals=[7, 8, 9], range_error_rms=0.0125, echo_totals=[1, 20, 3],
+                  echo_fraction_mean=0.75, second_returns=11, scans=2, chains=1)
+    for lead in ("", "front: "):
+        assert sq.format_closing_lines(totals, lead) == [
+            lead + sq.format_return_totals([5, 4, 3, 2, 1, 0]), lead + sq.format_noise_totals([7, 8, 9], 0.0125),
+            lead + sq.format_echo_totals([1, 20, 3], 0.75), lead + "Second returns: %d" % 11]
+    assert sq.format_closing_lines(totals, "front: ")[0] == \
+        "front: Returns: kept 5, no hit 4, below min_range 3, beyond max_range 2, beyond max_incidence 1, dropped at random 0"
+    assert sq.format_closing_lines(totals)[3] == "Second returns: 11"
+    # each line only when its model was on; a noise model that noised nothing still has its line
+    only = dict(return_totals=None, noise_totals=[4, 0, 0], range_error_rms=None, echo_totals=None, echo_fraction_mean=None,
+                second_returns=None)
+    assert sq.format_closing_lines(only, "a: ") == ["a: " + sq.format_noise_totals([4, 0, 0], None)]
+    nothing = dict(return_totals=None, noise_totals=None, range_error_rms=None, echo_totals=None, echo_fraction_mean=None,
+                   second_returns=None)
+    assert sq.format_closing_lines(nothing) == [] and sq.format_closing_lines(nothing, "front: ") == []
+
+
+CP_SENTENCES = dict(
+    return_model="adaption cp renders no surface: the target sensor's return_model cannot be applied (use mesh or mergemesh).",
+    noise_model="adaption cp renders no ray: the target sensor's noise_model cannot be applied (use mesh or mergemesh).",
+    echo_model="adaption cp renders no ray: the target sensor's echo_model cannot be applied (use mesh or mergemesh).",
+    dual_return="adaption cp renders no ray: the target sensor's dual_return cannot be applied (use mesh or mergemesh).")
+
+
+@pytest.mark.parametrize("key, name", [("return_model", "vlp32c_table_returns_1024.yaml"), ("noise_model", "vlp32c_table_noise_1024.yaml"),
+                                       ("echo_model", "vlp32c_table_echo_1024.yaml"), ("dual_return", "vlp32c_table_dual_1024.yaml")])
+def test_cli_refuses_cp_with_each_shipped_model_file_in_the_order_return_noise_echo_dual(tmp_path, capsys, monkeypatch, key, name):
+    """The shipped file of a model also holds the blocks of the models before it, so as shipped every one of the four is
+    refused for its ``return_model``.  With the blocks before its own key taken out, each is refused for its own -- but a
+    ``dual_return`` cannot be loaded without its ``echo_model``, which comes first: its own sentence is reached with a target
+    that answers for the dual return alone."""
+    import yaml
+    from lidar_transfer_amd import __main__ as cli
+    from lidar_transfer_amd import config
+    ds = tmp_path / "ds"
+    os.makedirs(ds / "sequences" / "00" / "velodyne")
+    os.makedirs(ds / "sequences" / "00" / "labels")
+    with open(os.path.join(ROOT, "config", "hdl64_1024.yaml")) as f:
+        (ds / "config.yaml").write_text(f.read())
+    with open(os.path.join(ROOT, "config", "approach_mergemesh.yaml")) as f:
+        text = f.read()
+    assert text.count('adaption: "mergemesh"') == 1
+    (tmp_path / "cp.yaml").write_text(text.replace('adaption: "mergemesh"', 'adaption: "cp"'))
+    args = ["-d", str(ds), "-c", str(tmp_path / "cp.yaml"), "-t"]
+    shipped = os.path.join(ROOT, "config", name)
+    with open(shipped) as f:
+        sensor = yaml.safe_load(f)
+    order = list(CP_SENTENCES)
+    before = order[:order.index(key)]
+    assert key in sensor and all(k in sensor for k in before)
+    assert cli.main(args + [shipped]) == 1
+    assert capsys.readouterr().out == CP_SENTENCES["return_model"] + "\n"
+    for k in before[:2]:
+        del sensor[k]
+    (tmp_path / "own.yaml").write_text(yaml.safe_dump(sensor))
+    assert cli.main(args + [str(tmp_path / "own.yaml")]) == 1
+    assert capsys.readouterr().out == CP_SENTENCES["echo_model" if key == "dual_return" else key] + "\n"
+    if key == "dual_return":
+        real = config.load_sensor
+        dual = real(shipped).dual_return()
+        assert dual is not None
+
+        class OnlyDual:
+            return_model = noise_model = echo_model = staticmethod(lambda: None)
+            dual_return = staticmethod(lambda: dual)
+        monkeypatch.setattr(config, "load_sensor", lambda path: OnlyDual() if path == shipped else real(path))
+        assert cli.main(args + [shipped]) == 1
+        assert capsys.readouterr().out == CP_SENTENCES["dual_return"] + "\n"
